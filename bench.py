@@ -153,6 +153,45 @@ def rocprof_launch_us(workload: str, batch: int):
     return None, None, None
 
 
+DUMP_SAMPLE, DUMP_SEED, DUMP_MAX_BYTES = 8, 1234, 64 * 1000 * 1000
+
+
+def dump_outputs(out_dir: str, workload: str, out, batch_size: int) -> dict:
+    """--dump-outputs: what a caller of the timed path received from its last step, as DIR/<name>.npy in float32 (float64
+    for counts and offsets).  full: probs and the graph offsets of the whole batch; label map, trimap, GrabCut mask, cleaned
+    mask, overlay, RGBA and the region graphs of a fixed, seeded sample of DUMP_SAMPLE images (its indices in
+    sample_index.npy).  gcn: the probabilities of every node.  The inputs are seeded, so two builds compare file for file."""
+    import torch
+    arrays = {}
+    if workload == "full":
+        pick = np.sort(np.random.default_rng(DUMP_SEED).choice(batch_size, min(DUMP_SAMPLE, batch_size), replace=False))
+        idx = torch.from_numpy(pick).to(out["segments"].device)
+        for name in ("segments", "trimap", "gc_mask", "binary_mask", "overlay", "rgba"):
+            arrays[name] = out[name].index_select(0, idx).cpu().numpy().astype(np.float32)
+        arrays["probs"] = out["probs"].cpu().numpy().astype(np.float32)
+        g = out["graphs"]
+        node_ptr, edge_ptr = g.node_ptr_host.astype(np.int64), g.edge_ptr_host.astype(np.int64)
+        arrays["graph_node_ptr"], arrays["graph_edge_ptr"] = node_ptr.astype(np.float64), edge_ptr.astype(np.float64)
+        nodes = np.concatenate([np.arange(node_ptr[i], node_ptr[i + 1]) for i in pick])
+        edges = np.concatenate([np.arange(edge_ptr[i], edge_ptr[i + 1]) for i in pick])
+        src, dst = g.edge_src.cpu().numpy().astype(np.int64)[edges], g.edge_dst.cpu().numpy().astype(np.int64)[edges]
+        first = np.repeat(node_ptr[pick], edge_ptr[pick + 1] - edge_ptr[pick])      # edge ids local to their image
+        arrays["graph_edge_index"] = np.stack([src - first, dst - first]).astype(np.float32)
+        for name in ("x", "centroids", "area_ratio"):
+            arrays[f"graph_{name}"] = getattr(g, name).cpu().numpy()[nodes].astype(np.float32)
+        arrays["graph_edge_attr"] = g.edge_attr.reshape(g.edge_src.numel(), -1).cpu().numpy()[edges].astype(np.float32)
+        arrays["sample_index"] = pick.astype(np.float32)
+    else:
+        arrays["probs"] = out.cpu().numpy().astype(np.float32)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes exceed the {DUMP_MAX_BYTES}-byte budget")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+    return {"dir": out_dir, "files": sorted(f"{k}.npy" for k in arrays), "bytes": int(total)}
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -177,7 +216,11 @@ def main() -> None:
     ap.add_argument("--force-collective", action="store_true", help="initialise the RCCL process group, the barriers, the MAX "
                     "all-reduce of the step time and the gather of the per-rank records even when WORLD_SIZE is 1 (warms the "
                     "N > 1 path on a one-GPU box; under torch.distributed.run --nproc-per-node 1 or on its own)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed to "
+                    "DIR/<name>.npy (float32 / float64; per-pixel outputs of a fixed, seeded sample of images, at most 64 MB)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.overlap_pass < 0:
         profiled = any(k in os.environ for k in ("ROCP_TOOL_LIBRARIES", "ROCPROF_OUTPUT_PATH", "ROCPROFILER_LIBRARY_CTOR"))
         args.overlap_pass = 0 if profiled else 3
@@ -301,6 +344,9 @@ def main() -> None:
     run_steps(args.steps)
     sync_all()
     elapsed = time.perf_counter() - t0
+    dumped = None
+    if args.dump_outputs and rank == 0:       # before any later step reuses the buffers the outputs live in
+        dumped = dump_outputs(args.dump_outputs, args.workload, last["out"], batch_size)
     stage_keys = ("gcn_gemm", "slic_assign", "slic_update", "slic_connectivity", "graph_stats", "graph_knn", "graph_prior",
                   "refine_trimap", "grabcut_init_gmm", "grabcut_gmm", "maxflow_relabel", "maxflow_push")
     q = [c.profile_query("gcn_aggregate") for c in ctxs]
@@ -533,6 +579,7 @@ def main() -> None:
             "roofline": roofline, "pipeline_roofline": pipeline_roofline, "cpu_baseline": cpu, "parity_vs_cpu_oracle": parity,
             "stage_ms_per_step": stage_ms, "stages": stage_table, "trimap_label_fractions": trimap_hist,
             "h2d_inclusive": h2d, "ranks": job["per_rank"] if collective else None, "overlapped": overlapped,
+            "dumped_outputs": dumped,
         }
         print(json.dumps(out_json), flush=True)
     if collective:

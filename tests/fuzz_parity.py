@@ -6,7 +6,7 @@ the SuperpixelGraphConfig / segment() options (use_lab, connectivity, n_nonlocal
 FUZZ_KIND=grabcut fuzzes the GrabCut class instead (trimap / rectangle starts, refine, colour spaces, 1-5 iterations).
 Round 3: 60 + 150 (sides 6-70) + 25 (sides 250-640) + 120 (with options) pipeline cases and 150 GrabCut-class cases, no mismatch."""
 import os, sys, time
-R = os.environ.get("GRAFT_REPO_ROOT", "/root/repo")
+R = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))          # the repository this script sits in
 sys.path.insert(0, R); sys.path.insert(0, os.path.join(R, "src")); sys.path.insert(0, os.path.join(R, "tests"))
 import numpy as np, torch
 from helpers import seeded_state_dict
