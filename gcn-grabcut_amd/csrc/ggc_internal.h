@@ -109,6 +109,10 @@ int set_err(ggc_ctx* ctx, int code, const char* fmt, ...);
 int read_i32(ggc_ctx* ctx, hipStream_t st, const int32_t* dev, int n, std::vector<int32_t>& host);
 // Returns nullptr (and sets error) on failure. Content is NOT preserved on growth.
 void* scratch(ggc_ctx* ctx, int slot, size_t bytes);
+// Destination CSR of an edge list, stable in edge order (ggc_resgcn.hip): row_ptr [N+1], col = src[eid] [E], eid [E],
+// dis = (1+indeg)^-1/2 [N] (may be NULL).  cursor: N+1 words of scratch.  Swapping src and dst gives the source CSR.
+int build_csr(ggc_ctx* ctx, hipStream_t st, int N, int E, const int32_t* src, const int32_t* dst,
+              int32_t* row_ptr, int32_t* col, int32_t* eid, int32_t* cursor, float* dis);
 
 #define GGC_HIP(ctx, expr)                                                          \
     do {                                                                            \

@@ -126,7 +126,7 @@ __global__ void k_fill_batch(int G, int N, const int32_t* __restrict__ node_ptr,
     }
 }
 
-static int build_csr(ggc_ctx* ctx, hipStream_t st, int N, int E, const int32_t* src, const int32_t* dst,
+int build_csr(ggc_ctx* ctx, hipStream_t st, int N, int E, const int32_t* src, const int32_t* dst,
                      int32_t* row_ptr, int32_t* col, int32_t* eid, int32_t* cursor, float* dis) {
     GGC_HIP(ctx, hipMemsetAsync(cursor, 0, sizeof(int32_t) * (size_t)(N + 1), st));
     if (E > 0) {

@@ -4,8 +4,8 @@ GCN-GrabCut on MI355X — host mirror of the reference package src/gcn_grabcut.
 Same public names as the reference (__init__.py:57-81) for the per-image
 segmentation hot path; all arithmetic runs in libggc_hip.so (hand-written
 gfx950 kernels behind the C ABI of include/ggc.h).  `dataset` holds the
-graph-cache writer behind tools/prepare_graphs.py (SURVEY.md section 8(f));
-training, loaders and plotting are out of scope.
+graph-cache writer behind tools/prepare_graphs.py; `losses`
+and `trainer` train ResGCNNet on the MI355X (train.py); plotting stays out of scope.
 """
 from ._constants import N_NODE_FEATS, N_EDGE_FEATS, N_PRIOR_FEATS, N_IMAGE_FEATS
 from .data import Data, Batch
@@ -20,6 +20,8 @@ from .model import (
 )
 from .pipeline import GCNGrabCutPipeline, SegmentationResult, clean_mask, guided_filter, refine_trimap
 from .synthetic import synthetic_image, synthetic_batch
+from .losses import FocalLoss, LabelSmoothingCE, TrimapLoss
+from .trainer import Trainer, TrainConfig
 
 __version__ = "0.3.0+mi355x.1"
 
@@ -31,4 +33,5 @@ __all__ = [
     "GCNGrabCutPipeline", "SegmentationResult", "clean_mask", "guided_filter", "refine_trimap",
     "ResGCNNet", "GCNTrimapNet", "GATTrimapNet", "build_model", "probs_to_node_trimap", "project_to_pixels",
     "Data", "Batch", "synthetic_image", "synthetic_batch",
+    "FocalLoss", "LabelSmoothingCE", "TrimapLoss", "Trainer", "TrainConfig",
 ]

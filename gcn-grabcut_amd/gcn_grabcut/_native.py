@@ -55,6 +55,15 @@ SIGNATURES = {
     "ggc_gat_forward": [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "ggc_gcn_aggregate": [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "ggc_build_csr": [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp],
+    "ggc_train_prepare": [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "ggc_train_gcn_forward": [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "ggc_train_gcn_backward": [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "ggc_train_sage_mean": [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp],
+    "ggc_train_sage_mean_backward": [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp],
+    "ggc_train_edge_mean": [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp],
+    "ggc_train_edge_mean_backward": [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp],
+    "ggc_train_graph_pool": [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp],
+    "ggc_train_graph_pool_backward": [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp],
     "ggc_refine_trimap": [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _f, _f, _i, _f, _i, _vp],
     "ggc_seed_from_prior": [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, C.c_double, _vp],
     "ggc_grabcut": [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _u64, _vp],

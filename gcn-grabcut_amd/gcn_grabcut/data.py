@@ -5,13 +5,19 @@ The reference hands its models "any object with .x, .edge_index, .edge_attr and
 an optional .batch" (reference model.py:509-513); PyG itself is not a dependency
 of this build.  `Batch.from_data_list` follows PyG's collation:
 concatenate x / edge_attr, offset edge_index by the cumulative node counts, and
-record the graph id of every node.
+record the graph id of every node.  The per-node training targets (`y`, `node_area`,
+`fg_ratio`) are concatenated too when every graph carries them, and `node_ptr32` holds
+the graph boundaries as int32 for the library.
 """
 from __future__ import annotations
 
 from typing import Optional, Sequence
 
 import torch
+
+
+# per-node training targets written by dataset.prepare_dataset (labels, region area, ground-truth coverage)
+NODE_LABEL_KEYS = ("y", "node_area", "fg_ratio")
 
 
 class Data:
@@ -75,5 +81,10 @@ class Batch(Data):
         )
         out.batch = torch.cat(bs, 0)
         out.ptr = torch.tensor(ptr, dtype=torch.long, device=out.x.device)
+        out.node_ptr32 = out.ptr.to(torch.int32)
         out.num_graphs = len(graphs)
+        for key in NODE_LABEL_KEYS:             # training supervision: kept only when every graph carries it
+            vals = [getattr(g, key, None) for g in graphs]
+            if all(torch.is_tensor(v) for v in vals):
+                setattr(out, key, torch.cat(vals, 0))
         return out

@@ -6,7 +6,8 @@ SURVEY section 8 row M0) and methods (`forward`, `predict_probs`, `predict_trima
 `layer_weights`, `param_groups`), but owns no arithmetic: the torch submodules
 below are parameter containers only, and `forward` hands raw device pointers
 to libggc_hip.so (ggc_resgcn_forward), whose kernels implement model.py:508-536
-on the MI355X.  Inference only (eval mode); there is no CPU path.
+on the MI355X.  In train mode `forward` is differentiable: the graph operators run in
+the ggc_train_* kernels and the dense layers in torch autograd.  There is no CPU path.
 """
 from __future__ import annotations
 
@@ -45,6 +46,18 @@ if _TORCH:
         def __init__(self, n_features: int, momentum: float = 0.05):
             super().__init__()
             self.norm = nn.BatchNorm1d(n_features, momentum=momentum, affine=True)
+
+        def forward(self, x):
+            """Training forward (reference model.py:205-212): batch statistics, except that a single node has no
+            variance to estimate and is normalised with the running statistics instead."""
+            if self.training and x.size(0) < 2:
+                was = self.norm.training
+                self.norm.eval()
+                try:
+                    return self.norm(x)
+                finally:
+                    self.norm.train(was)
+            return self.norm(x)
 
     class _EdgeContext(nn.Module):
         """Parameter holder for reference EdgeContext (model.py:111-139)."""
@@ -163,8 +176,8 @@ if _TORCH:
 
         def _run(self, data, want_logits: bool, want_probs: bool, ctx=None):
             if self.training:
-                raise RuntimeError("ResGCNNet on MI355X is inference-only: call .eval() first "
-                                   "(training lives in the reference and is out of scope here)")
+                raise RuntimeError("ResGCNNet._run is the eval-mode forward: call .eval() first "
+                                   "(train mode goes through _train_forward)")
             dev_index = self._device_index()
             if ctx is None:                      # a pipeline replica passes its private context (own scratch arena)
                 ctx = _native.get_context(dev_index)
@@ -187,18 +200,7 @@ if _TORCH:
             src = ei[0].to(torch.int32).contiguous()
             dst = ei[1].to(torch.int32).contiguous()
 
-            batch = getattr(data, "batch", None)
-            node_ptr = getattr(data, "node_ptr32", None)
-            if node_ptr is None:
-                if batch is None:
-                    node_ptr = torch.tensor([0, n], dtype=torch.int32, device=dev)
-                else:
-                    n_graphs = getattr(data, "num_graphs", None)
-                    if n_graphs is None:
-                        n_graphs = int(batch.max().item()) + 1   # reference model.py:86
-                    counts = torch.bincount(batch, minlength=n_graphs)
-                    node_ptr = torch.zeros(n_graphs + 1, dtype=torch.int32, device=dev)
-                    node_ptr[1:] = torch.cumsum(counts, 0).to(torch.int32)
+            node_ptr = _node_ptr(data, n, dev)
             g = node_ptr.numel() - 1
 
             logits = torch.empty(n, 3, dtype=torch.float32, device=dev) if want_logits else None
@@ -211,9 +213,60 @@ if _TORCH:
             return logits, probs
 
         def forward(self, data) -> "torch.Tensor":
-            """logits (N, 3) on the model's device — reference model.py:508-536."""
+            """logits (N, 3) on the model's device — reference model.py:508-536.  In eval mode one ggc_resgcn_forward
+            call; in train mode a differentiable forward (see `_train_forward`)."""
+            if self.training:
+                return self._train_forward(data)
             with torch.no_grad():
                 return self._run(data, True, False)[0]
+
+        def _train_forward(self, data) -> "torch.Tensor":
+            """Training forward, reference model.py:508-536 with autograd.  The dense layers are torch modules (each
+            respects its own `.training` flag); the graph operators (GCNConv aggregation + residual epilogue, SAGE mean,
+            EdgeContext scatter-mean, per-graph attention readout) are the ggc_train_* kernels, whose backward passes
+            are deterministic.  Widths 32, 64, 96 and 128 only."""
+            import torch.nn.functional as F
+            from . import train_ops
+            D = self.hidden_channels
+            if D not in train_ops.TRAIN_WIDTHS:
+                raise ValueError(f"ResGCNNet trains at hidden_channels in {train_ops.TRAIN_WIDTHS} (got {D}); "
+                                 "other widths are inference-only")
+            dev_index = self._device_index()
+            dev = torch.device("cuda", dev_index)
+            x = data.x
+            if x.device != dev:
+                raise RuntimeError(f"data.x is on {x.device}, model on {dev}")
+            x = x.to(torch.float32)
+            n = x.size(0)
+            if x.dim() != 2 or x.size(1) != N_NODE_FEATS:
+                raise ValueError(f"data.x must be (N, {N_NODE_FEATS}), got {tuple(x.shape)}")
+            ei = data.edge_index
+            edge_attr = getattr(data, "edge_attr", None)
+            if edge_attr is None:                      # reference model.py:511-512
+                edge_attr = torch.zeros(ei.size(1), N_EDGE_FEATS, device=dev)
+            prep = train_ops.GraphPrep(_native.get_context(dev_index), ei, n, _node_ptr(data, n, dev))
+            p_drop = self.dropout if self.training else 0.0
+
+            h = self.input_proj(self.in_norm(x))
+            h = h * (1.0 + self.prior_booster(x[:, -N_PRIOR_FEATS:]))
+            ctx_vec = train_ops.edge_mean(self.edge_ctx.encode(edge_attr.to(torch.float32)), prep)
+            gate = self.edge_ctx.to_gate(ctx_vec)
+            states = [h]
+            for gcn, norm in zip(self.gcn_layers, self.norms):
+                xw = F.linear(norm(h), gcn.lin.weight)
+                if p_drop > 0:
+                    h = h + F.dropout(train_ops.gcn_conv_gated(xw, gcn.bias, gate, None, prep), p=p_drop, training=True)
+                else:
+                    h = train_ops.gcn_conv_gated(xw, gcn.bias, gate, h, prep)
+                states.append(h)
+            m = train_ops.sage_mean(h, prep)
+            s = F.linear(m, self.sage.lin_l.weight, self.sage.lin_l.bias) + F.linear(h, self.sage.lin_r.weight)
+            states.append(F.gelu(self.sage_norm(s)))
+            w = torch.softmax(self.jk_logits, dim=0)
+            h_jk = torch.stack(states, 0).mul(w[:, None, None]).sum(0)
+            hb = train_ops.graph_pool(h_jk, self.ctx.attn(h_jk), prep)
+            g = torch.sigmoid(self.ctx.expand(F.relu(self.ctx.compress(hb))))
+            return self.head(self.fuse(h_jk * g))
 
         @torch.no_grad()
         def layer_weights(self) -> np.ndarray:
@@ -253,6 +306,22 @@ if _TORCH:
             groups.append({"params": ([self.jk_logits] + list(self.fuse.parameters()) +
                                       list(self.head.parameters())), "lr": base_lr})
             return groups
+
+    def _node_ptr(data, n: int, dev) -> "torch.Tensor":
+        """int32 [G+1] graph boundaries of a batch (graphs are contiguous, PyG collation)."""
+        batch = getattr(data, "batch", None)
+        node_ptr = getattr(data, "node_ptr32", None)
+        if node_ptr is None:
+            if batch is None:
+                node_ptr = torch.tensor([0, n], dtype=torch.int32, device=dev)
+            else:
+                n_graphs = getattr(data, "num_graphs", None)
+                if n_graphs is None:
+                    n_graphs = int(batch.max().item()) + 1   # reference model.py:86
+                counts = torch.bincount(batch, minlength=n_graphs)
+                node_ptr = torch.zeros(n_graphs + 1, dtype=torch.int32, device=dev)
+                node_ptr[1:] = torch.cumsum(counts, 0).to(torch.int32)
+        return node_ptr
 
     class _EdgeInjection(nn.Module):
         """Parameter holder for reference EdgeInjectionLayer (model.py:142-162)."""

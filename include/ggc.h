@@ -50,7 +50,7 @@
 extern "C" {
 #endif
 
-#define GGC_VERSION 300 /* 0.3.0: round 3 — ggc_slic_rgb added, ggc_profile_enable(ctx, 2), one max-flow driver */
+#define GGC_VERSION 310 /* 0.3.1: ggc_train_* (graph operators of the ResGCNNet training forward and their backward) */
 
 enum {
     GGC_OK            =  0,
@@ -252,6 +252,59 @@ int ggc_gcn_aggregate(ggc_ctx* ctx, ggc_stream stream, int N, int D,
 int ggc_build_csr(ggc_ctx* ctx, ggc_stream stream, int N, int E,
                   const int32_t* edge_src, const int32_t* edge_dst,
                   int32_t* row_ptr, int32_t* col, float* dis);
+
+/* ------------------------------------------------------------ training (ResGCNNet)
+ * The graph operators of the ResGCNNet training forward (model.py:508-536, train mode) and their backward passes, f32.
+ * The dense layers stay in the host's autograd.  No entry uses a float atomic: every sum runs in one fixed order, so two
+ * runs give identical bits.  A scatter in a backward pass is a gather over the SOURCE CSR.  Node widths D in
+ * {32, 64, 96, 128} (GGC_E_UNSUPPORTED otherwise).  All arrays are device arrays.
+ *
+ * Graph preparation, once per batch, shared by every layer: destination CSR (row_ptr [N+1], col = source [E],
+ * eid = edge id [E]) and source CSR (srow_ptr [N+1], scol = destination [E], seid [E]), both stable in edge order;
+ * dis [N] = (1+indeg)^-1/2 and inv_cnt [N] = 1/max(indeg, 1).  col/eid/scol/seid may be NULL when E == 0. */
+int ggc_train_prepare(ggc_ctx* ctx, ggc_stream stream, int N, int E, const int32_t* edge_src, const int32_t* edge_dst,
+                      int32_t* row_ptr, int32_t* col, int32_t* eid, int32_t* srow_ptr, int32_t* scol, int32_t* seid,
+                      float* dis, float* inv_cnt);
+
+/* GCNConv with the ResGCNNet residual epilogue, semantics as ggc_gcn_aggregate:
+ *   out_i = sum_{e: dst(e)=i} dis[src]*dis[i]*xw[src] + dis[i]^2 xw[i] + bias
+ *   y_i   = h_i + gelu(out_i * gate_i)      (y_i = gelu(out_i * gate_i) when h == NULL: the caller adds dropout + residual)
+ *   xw, gate, h, out, y [N,D]  bias [D]  row_ptr/col/dis from ggc_train_prepare */
+int ggc_train_gcn_forward(ggc_ctx* ctx, ggc_stream stream, int N, int D, const float* xw, const int32_t* row_ptr,
+                          const int32_t* col, const float* dis, const float* bias, const float* gate, const float* h,
+                          float* out, float* y);
+/* Its backward, given g_y = dL/dy and the forward's out:
+ *   g_out  = g_y * gelu'(out*gate) * gate      g_gate = g_y * gelu'(out*gate) * out        (both [N,D])
+ *   g_xw_j = sum_{e: src(e)=j} dis[j]*dis[dst]*g_out[dst] + dis[j]^2 g_out[j]             (source CSR)
+ * dL/dbias = column sums of g_out; dL/dh = g_y (the residual). */
+int ggc_train_gcn_backward(ggc_ctx* ctx, ggc_stream stream, int N, int D, const float* g_y, const float* out,
+                           const float* gate, const int32_t* srow_ptr, const int32_t* scol, const float* dis,
+                           float* g_out, float* g_gate, float* g_xw);
+
+/* SAGEConv mean: m_i = inv_cnt_i * sum_{e: dst(e)=i} x[src]   (x, m [N,D], destination CSR) */
+int ggc_train_sage_mean(ggc_ctx* ctx, ggc_stream stream, int N, int D, const float* x, const int32_t* row_ptr,
+                        const int32_t* col, const float* inv_cnt, float* out);
+/* Its backward: g_x_j = sum_{e: src(e)=j} inv_cnt[dst] * g_m[dst]   (source CSR) */
+int ggc_train_sage_mean_backward(ggc_ctx* ctx, ggc_stream stream, int N, int D, const float* g_m, const int32_t* srow_ptr,
+                                 const int32_t* scol, const float* inv_cnt, float* g_x);
+
+/* EdgeContext scatter-mean (model.py:128-139): ctx_i = inv_cnt_i * sum_{e: dst(e)=i} enc[e]
+ *   enc [E,C]  ctx [N,C]  row_ptr/eid: destination CSR.  Any C >= 1. */
+int ggc_train_edge_mean(ggc_ctx* ctx, ggc_stream stream, int N, int C, const float* enc, const int32_t* row_ptr,
+                        const int32_t* eid, const float* inv_cnt, float* out);
+/* Its backward, a gather: g_enc_e = inv_cnt[dst(e)] * g_ctx[dst(e)]   (edge_dst [E], g_ctx [N,C], g_enc [E,C]) */
+int ggc_train_edge_mean_backward(ggc_ctx* ctx, ggc_stream stream, int E, int C, const int32_t* edge_dst,
+                                 const float* inv_cnt, const float* g_ctx, float* g_enc);
+
+/* GlobalContextModule readout (model.py:90-108, 176-188), one workgroup per graph; graphs are contiguous by node_ptr [G+1]:
+ *   attn_i = exp(s_i - max_g s) / (sum_g exp(s - max_g s) + 1e-12)      (score, attn [N])
+ *   hb_i   = sum_{j in graph(i)} attn_j h_j                              (h, hb [N,D]: pooled, broadcast to every node) */
+int ggc_train_graph_pool(ggc_ctx* ctx, ggc_stream stream, int G, int N, int D, const int32_t* node_ptr, const float* h,
+                         const float* score, float* attn, float* hb);
+/* Its backward, given g_hb = dL/dhb: gp_g = sum_{i in g} g_hb_i, g_h_i = attn_i gp_g (the pooling term only),
+ * ga_i = <gp_g, h_i>, g_score_i = attn_i (ga_i - sum_{j in g} attn_j ga_j). */
+int ggc_train_graph_pool_backward(ggc_ctx* ctx, ggc_stream stream, int G, int N, int D, const int32_t* node_ptr,
+                                  const float* h, const float* attn, const float* g_hb, float* g_h, float* g_score);
 
 /* ------------------------------------------------------------ P0-P3 trimap
  * Replaces refine_trimap (pipeline.py:103-146) incl. guided_filter

@@ -76,7 +76,7 @@ def main() -> None:
     if not ckpt_path.exists():
         fallback = Path("checkpoints/final_model.pt")
         if not fallback.exists():
-            raise FileNotFoundError(f"No checkpoint at {ckpt_path} (or {fallback}). Train one with the reference's train.py.")
+            raise FileNotFoundError(f"No checkpoint at {ckpt_path} (or {fallback}). Train one with train.py.")
         print(f"[inference] {ckpt_path} not found, using {fallback}")
         ckpt_path = fallback
     state = torch.load(ckpt_path, map_location="cpu", weights_only=True)["model"]
