@@ -104,9 +104,8 @@ int ggc_ctx_destroy(ggc_ctx* ctx) {
     for (auto& e : ctx->prof_pool) (void)hipEventDestroy(e);
     for (auto& b : ctx->slots) if (b.p) (void)hipFree(b.p);
     if (ctx->h_pinned) (void)hipHostFree(ctx->h_pinned);
-    for (auto& kv : ctx->model.dev) if (kv.second.p) (void)hipFree(kv.second.p);
-    for (auto& kv : ctx->model2.dev) if (kv.second.p) (void)hipFree(kv.second.p);
-    for (auto& kv : ctx->model3.dev) if (kv.second.p) (void)hipFree(kv.second.p);
+    for (ggc::WeightSet* m : {&ctx->resgcn, &ctx->gcnnet, &ctx->gat})
+        for (auto& kv : m->dev) if (kv.second.p) (void)hipFree(kv.second.p);
     delete ctx;
     return GGC_OK;
 }

@@ -37,11 +37,14 @@ struct Buf {
     size_t bytes = 0;
 };
 
-// ResGCNNet parameters (reference model.py:449-499): host copies by state_dict
-// key, device copies (raw + packed layouts) built lazily before a forward.
-struct ResgcnWeights {
-    int D = 0, n_layers = 0, Q = 0, C = 0;
-    int Dt = 0;                            // true hidden width (ResGCNNet): D is Dt rounded up to a multiple of 32
+// One network's parameters (ggc_gnn.h): host copies by state_dict key, device copies (padded arrays + derived layouts)
+// built lazily before a forward.
+struct WeightSet {
+    int D = 0;                             // kernel width, a multiple of 32
+    int Dt = 0;                            // true hidden width: ResGCNNet runs Dt zero-padded to D, the other networks Dt == D
+    int n_layers = 0;
+    int Q = 0, C = 0;                      // ResGCNNet: prior-booster and edge-context widths
+    int heads = 0;                         // GATTrimapNet: attention heads
     std::map<std::string, std::vector<float>> host;
     std::map<std::string, Buf> dev;
     bool dev_ok = false;
@@ -74,9 +77,7 @@ struct ggc_ctx {
     std::vector<ggc::ProfRec> prof;        // recorded scopes since ggc_profile_enable
     std::vector<hipEvent_t> prof_pool;     // recycled events
     ggc::Buf slots[ggc::S_COUNT];
-    ggc::ResgcnWeights model;
-    ggc::ResgcnWeights model2;             // GCNTrimapNet (same container: host copies by key, device copies)
-    ggc::ResgcnWeights model3;             // GATTrimapNet (Q = attention heads)
+    ggc::WeightSet resgcn, gcnnet, gat;    // the three trimap networks' weights
     ggc::GraphState graph;
     int n_cu = 256;
     float prior_two_ce2 = (float)(2 * 0.45 * 0.45), prior_two_cs2 = (float)(2 * 0.40 * 0.40);   // compute_auto_prior sigmas (reference defaults)

@@ -17,16 +17,11 @@
 // D=128).  Graphs of a batch are concatenated (PyG Batch semantics); node_ptr
 // gives the per-graph ranges.  The destination CSR (row_ptr, col, eid) is
 // built once per forward, stable in edge order, and reused by all 8 gathers.
-#include "ggc_internal.h"
+#include "ggc_gnn.h"
 #include <atomic>
 #include <cmath>
-#include <type_traits>
 
 namespace ggc {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-constexpr int IN_CH = 19, EDGE_CH = 5, N_PRIOR = 3, N_CLS = 3;
 
 // ------------------------------------------------------------------ CSR build
 
@@ -116,6 +111,15 @@ __global__ void k_sort_rows(int N, const int32_t* __restrict__ row_ptr, int32_t*
         for (int i = beg; i < end; ++i) col[i] = src[eid[i]];
         if (dis) dis[r] = 1.0f / sqrtf((float)(end - beg) + 1.0f);
     }
+}
+
+// destination (row) of every CSR position: row_ptr[r] <= j < row_ptr[r + 1]
+__global__ void __launch_bounds__(256) k_csr_dst(int N, int E, const int32_t* __restrict__ row_ptr, int32_t* __restrict__ csr_dst) {
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= E) return;
+    int lo = 0, hi = N;
+    while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (row_ptr[mid] <= j) lo = mid; else hi = mid; }
+    csr_dst[j] = lo;
 }
 
 __global__ void k_fill_batch(int G, int N, const int32_t* __restrict__ node_ptr, int32_t* __restrict__ batch) {
@@ -355,22 +359,7 @@ __global__ void __launch_bounds__(256) k_edge_gate(int N, const int32_t* __restr
 // k in [hk*D/2, (hk+1)*D/2): each lane then reads one contiguous half-row of A
 // (float4 loads) and W is pre-packed on the host as Wp[s/4][t][lane][s%4] =
 // W[32t + (lane&31)][hk*D/2 + s], staged once per block into LDS and read with
-// conflict-free ds_read_b128.
-//   MODE 0: A = LayerNorm(A1); store                                   (GCN XW)
-//   MODE 1: A1 @ W1^T + A2 @ W2^T + bias -> LayerNorm -> GELU          (SAGE)
-//   MODE 2: A = LayerNorm(A1 * gvec[batch]); + bias -> GELU -> head -> softmax
-//   MODE 4: as MODE 2 without the LayerNorm (GATTrimapNet head)
-struct GemmArgs {
-    const float *A1, *A2, *Wp1, *Wp2;
-    const float *ln_w, *ln_b;        // prologue LayerNorm
-    const float *bias;               // [D]
-    const int32_t* batch;            // MODE 2
-    const float* gvec;               // MODE 2: [G,D]
-    const float *ep_w, *ep_b;        // MODE 1: LN weight/bias; MODE 2: head weight [3,D] / bias [3]
-    float *out, *out2;               // MODE 2: logits / probs (either may be null)
-    int accumulate = 0;              // MODE 3: out += A W^T instead of out = A W^T
-    int Dt = 0;                      // true width for the LayerNorm statistics (0: D), see k_input
-};
+// conflict-free ds_read_b128.  The modes and their arguments (GemmArgs) are listed in ggc_gnn.h.
 
 #ifdef GEMM_TRACE     // experiment build: per-wave phase stamps of k_gemm<128, 0> kept in SGPRs (no scheduling fences)
 __device__ unsigned long long g_gemm_trace[8192 * 8];
@@ -980,8 +969,6 @@ __global__ void __launch_bounds__(256) k_jk(int N, int n_states, const float* __
 }
 
 // ------------------------------------------------------ M6: per-graph readout
-struct CtxW { const float *wcT /*[D][D/2]*/, *bc, *weT /*[D/2][D]*/, *be; };
-
 template <int D>
 __global__ void __launch_bounds__(256) k_graph_ctx(const int32_t* __restrict__ node_ptr,
                                                    const float* __restrict__ score,
@@ -1034,151 +1021,61 @@ __global__ void __launch_bounds__(256) k_graph_ctx(const int32_t* __restrict__ n
     }
 }
 
-// ------------------------------------------------------------- weight handling
+// ------------------------------------------------------------- weights
 
-static const float* devp(const ResgcnWeights& m, const std::string& k) {
-    auto it = m.dev.find(k);
-    return it == m.dev.end() ? nullptr : reinterpret_cast<const float*>(it->second.p);
-}
-static const float* devp(ggc_ctx* ctx, const std::string& k) { return devp(ctx->model, k); }
-
-static int upload(ggc_ctx* ctx, ResgcnWeights& m, const std::string& key, const std::vector<float>& v);
-static int upload(ggc_ctx* ctx, const std::string& key, const std::vector<float>& v) { return upload(ctx, ctx->model, key, v); }
-static int upload(ggc_ctx* ctx, ResgcnWeights& m, const std::string& key, const std::vector<float>& v) {
-    Buf& b = m.dev[key];
-    const size_t bytes = v.size() * sizeof(float);
-    if (b.bytes < bytes) {
-        if (b.p) GGC_HIP(ctx, hipFree(b.p));
-        b.p = nullptr; b.bytes = 0;
-        GGC_HIP(ctx, hipMalloc(&b.p, bytes ? bytes : 16));
-        b.bytes = bytes;
-    }
-    if (bytes) GGC_HIP(ctx, hipMemcpy(b.p, v.data(), bytes, hipMemcpyHostToDevice));
-    return GGC_OK;
-}
-
-static std::vector<float> transpose(const std::vector<float>& w, int out, int in) {
-    std::vector<float> t((size_t)out * in);
-    for (int o = 0; o < out; ++o)
-        for (int k = 0; k < in; ++k) t[(size_t)k * out + o] = w[(size_t)o * in + k];
-    return t;
-}
-
-// Wp[s/4][t][lane][s%4] = W[32 t + (lane & 31)][(lane >> 5) * D/2 + s]
-static std::vector<float> pack_mfma(const std::vector<float>& w, int D) {
-    const int T = D / 32, KH = D / 2;
-    std::vector<float> p((size_t)D * D);
-    for (int s = 0; s < KH; ++s)
-        for (int t = 0; t < T; ++t)
-            for (int l = 0; l < 64; ++l)
-                p[(((size_t)(s / 4) * T + t) * 64 + l) * 4 + (s % 4)] =
-                    w[(size_t)(32 * t + (l & 31)) * D + (l >> 5) * KH + s];
-    return p;
-}
-
-// A state_dict entry: true shape [rows, cols] (cols = 1: a vector) and the shape of its device copy, where every dimension
-// that is the hidden width Dt is zero-padded to D (the multiple of 32 the kernels are built for).
-struct Need { std::string key; int64_t numel; int r = 0, c = 1, rp = 0, cp = 1; };
-
-static std::vector<Need> needed(const ResgcnWeights& m) {
-    const int D = m.D, Dt = m.Dt > 0 ? m.Dt : m.D, Q = m.Q, C = m.C, n = m.n_layers;
+static std::vector<Need> needed_resgcn(const WeightSet& m) {
+    const int D = m.D, Dt = m.Dt, Q = m.Q, C = m.C, n = m.n_layers;
     std::vector<Need> v;
-    auto add = [&](const std::string& k, int r, int c, int rp, int cp) { v.push_back({k, (int64_t)r * c, r, c, rp, cp}); };
+    auto add = [&](const std::string& k, int r, int c, int rp, int cp, char layout = 0) {
+        v.push_back({k, (int64_t)r * c, r, c, rp, cp, layout});
+    };
     auto vec = [&](const std::string& k, int len) { add(k, len, 1, len, 1); };
     auto vecD = [&](const std::string& k) { add(k, Dt, 1, D, 1); };
     vec("in_norm.norm.weight", IN_CH); vec("in_norm.norm.bias", IN_CH);
     vec("in_norm.norm.running_mean", IN_CH); vec("in_norm.norm.running_var", IN_CH);
-    add("input_proj.0.weight", Dt, IN_CH, D, IN_CH); vecD("input_proj.0.bias");
+    add("input_proj.0.weight", Dt, IN_CH, D, IN_CH, 'T'); vecD("input_proj.0.bias");
     vecD("input_proj.1.weight"); vecD("input_proj.1.bias");
     add("prior_booster.0.weight", Q, N_PRIOR, Q, N_PRIOR); vec("prior_booster.0.bias", Q);
-    add("prior_booster.2.weight", Dt, Q, D, Q); vecD("prior_booster.2.bias");
+    add("prior_booster.2.weight", Dt, Q, D, Q, 'T'); vecD("prior_booster.2.bias");
     add("edge_ctx.encode.0.weight", C, EDGE_CH, C, EDGE_CH); vec("edge_ctx.encode.0.bias", C);
-    add("edge_ctx.encode.2.weight", C, C, C, C); vec("edge_ctx.encode.2.bias", C);
+    add("edge_ctx.encode.2.weight", C, C, C, C, 'T'); vec("edge_ctx.encode.2.bias", C);
     vec("edge_ctx.to_gate.0.weight", C); vec("edge_ctx.to_gate.0.bias", C);
-    add("edge_ctx.to_gate.1.weight", Dt, C, D, C); vecD("edge_ctx.to_gate.1.bias");
-    add("sage.lin_l.weight", Dt, Dt, D, D); vecD("sage.lin_l.bias"); add("sage.lin_r.weight", Dt, Dt, D, D);
+    add("edge_ctx.to_gate.1.weight", Dt, C, D, C, 'T'); vecD("edge_ctx.to_gate.1.bias");
+    add("sage.lin_l.weight", Dt, Dt, D, D, 'P'); vecD("sage.lin_l.bias"); add("sage.lin_r.weight", Dt, Dt, D, D, 'P');
     vecD("sage_norm.weight"); vecD("sage_norm.bias"); vec("jk_logits", n + 2);
     vecD("ctx.attn.weight"); vec("ctx.attn.bias", 1);
-    add("ctx.compress.weight", Dt / 2, Dt, D / 2, D); add("ctx.compress.bias", Dt / 2, 1, D / 2, 1);
-    add("ctx.expand.weight", Dt, Dt / 2, D, D / 2); vecD("ctx.expand.bias");
-    vecD("fuse.0.weight"); vecD("fuse.0.bias"); add("fuse.1.weight", Dt, Dt, D, D); vecD("fuse.1.bias");
+    add("ctx.compress.weight", Dt / 2, Dt, D / 2, D, 'T'); add("ctx.compress.bias", Dt / 2, 1, D / 2, 1);
+    add("ctx.expand.weight", Dt, Dt / 2, D, D / 2, 'T'); vecD("ctx.expand.bias");
+    vecD("fuse.0.weight"); vecD("fuse.0.bias"); add("fuse.1.weight", Dt, Dt, D, D, 'P'); vecD("fuse.1.bias");
     add("head.weight", N_CLS, Dt, N_CLS, D); vec("head.bias", N_CLS);
     for (int i = 0; i < n; ++i) {
         const std::string s = std::to_string(i);
         vecD("gcn_layers." + s + ".bias");
-        add("gcn_layers." + s + ".lin.weight", Dt, Dt, D, D);
+        add("gcn_layers." + s + ".lin.weight", Dt, Dt, D, D, 'P');
         vecD("norms." + s + ".weight");
         vecD("norms." + s + ".bias");
     }
     return v;
 }
 
-// zero-padded copy [rp, cp] of a row-major [r, c] array
-static std::vector<float> pad2(const std::vector<float>& w, const Need& nd) {
-    if (nd.r == nd.rp && nd.c == nd.cp) return w;
-    std::vector<float> p((size_t)nd.rp * nd.cp, 0.0f);
-    for (int i = 0; i < nd.r; ++i)
-        for (int j = 0; j < nd.c; ++j) p[(size_t)i * nd.cp + j] = w[(size_t)i * nd.c + j];
-    return p;
+// softmax(jk_logits) on the host (model.py:532), same op order as the oracle
+static int derive_resgcn(ggc_ctx* ctx, WeightSet& m, std::map<std::string, std::vector<float>>& pw) {
+    const std::vector<float>& jl = pw["jk_logits"];
+    std::vector<float> w(jl.size());
+    float mx = jl[0];
+    for (float v : jl) mx = v > mx ? v : mx;
+    float s = 0.0f;
+    for (size_t k = 0; k < jl.size(); ++k) { w[k] = ggc_expf(jl[k] - mx); s += w[k]; }
+    for (size_t k = 0; k < jl.size(); ++k) w[k] = w[k] / s;
+    return upload(ctx, m, "#jk_w", w);
 }
 
-static int check_ready(ggc_ctx* ctx) {
-    ResgcnWeights& m = ctx->model;
-    GGC_REQUIRE(ctx, m.D > 0, GGC_E_STATE, "ggc_resgcn_configure has not been called");
-    for (const Need& nd : needed(m)) {
-        auto it = m.host.find(nd.key);
-        GGC_REQUIRE(ctx, it != m.host.end(), GGC_E_STATE, "missing weight '%s'", nd.key.c_str());
-        GGC_REQUIRE(ctx, (int64_t)it->second.size() == nd.numel, GGC_E_SHAPE,
-                    "weight '%s' has %zu elements, expected %lld", nd.key.c_str(), it->second.size(),
-                    (long long)nd.numel);
-    }
-    return GGC_OK;
-}
-
-static int prepare_weights(ggc_ctx* ctx) {
-    ResgcnWeights& m = ctx->model;
-    if (m.dev_ok) return GGC_OK;
-    int rc = check_ready(ctx);
-    if (rc) return rc;
-    // The device copies are about to be overwritten in place by blocking copies on the null stream, which does not wait for
-    // the (non-blocking) stream a previous forward may still be running on: drain the device first.  Weight changes are rare.
-    GGC_HIP(ctx, hipDeviceSynchronize());
-    const int D = m.D, Q = m.Q, C = m.C, n = m.n_layers;
-    // device copies are the zero-padded arrays (a width that is a multiple of 32 pads nothing); m.host keeps what was loaded
-    std::map<std::string, std::vector<float>> pw;
-    for (const Need& nd : needed(m)) pw[nd.key] = pad2(m.host[nd.key], nd);
-    for (auto& kv : pw) { rc = upload(ctx, kv.first, kv.second); if (rc) return rc; }
-    if ((rc = upload(ctx, "#input_proj.0.weightT", transpose(pw["input_proj.0.weight"], D, IN_CH)))) return rc;
-    if ((rc = upload(ctx, "#prior_booster.2.weightT", transpose(pw["prior_booster.2.weight"], D, Q)))) return rc;
-    if ((rc = upload(ctx, "#edge_ctx.encode.2.weightT", transpose(pw["edge_ctx.encode.2.weight"], C, C)))) return rc;
-    if ((rc = upload(ctx, "#edge_ctx.to_gate.1.weightT", transpose(pw["edge_ctx.to_gate.1.weight"], D, C)))) return rc;
-    if ((rc = upload(ctx, "#ctx.compress.weightT", transpose(pw["ctx.compress.weight"], D / 2, D)))) return rc;
-    if ((rc = upload(ctx, "#ctx.expand.weightT", transpose(pw["ctx.expand.weight"], D, D / 2)))) return rc;
-    for (int i = 0; i < n; ++i) {
-        const std::string k = "gcn_layers." + std::to_string(i) + ".lin.weight";
-        if ((rc = upload(ctx, "#" + k + ".p", pack_mfma(pw[k], D)))) return rc;
-    }
-    if ((rc = upload(ctx, "#sage.lin_l.weight.p", pack_mfma(pw["sage.lin_l.weight"], D)))) return rc;
-    if ((rc = upload(ctx, "#sage.lin_r.weight.p", pack_mfma(pw["sage.lin_r.weight"], D)))) return rc;
-    if ((rc = upload(ctx, "#fuse.1.weight.p", pack_mfma(pw["fuse.1.weight"], D)))) return rc;
-    {   // softmax(jk_logits) on the host (model.py:532), same op order as the oracle
-        const std::vector<float>& jl = m.host["jk_logits"];
-        std::vector<float> w(jl.size());
-        float mx = jl[0];
-        for (float v : jl) mx = v > mx ? v : mx;
-        float s = 0.0f;
-        for (size_t k = 0; k < jl.size(); ++k) { w[k] = ggc_expf(jl[k] - mx); s += w[k]; }
-        for (size_t k = 0; k < jl.size(); ++k) w[k] = w[k] / s;
-        if ((rc = upload(ctx, "#jk_w", w))) return rc;
-    }
-    m.dev_ok = true;
-    return GGC_OK;
-}
+static const NetSpec RESGCN{"ResGCNNet", "resgcn", &ggc_ctx::resgcn, true, needed_resgcn, derive_resgcn};
 
 // ------------------------------------------------------------ launch helpers
 
 template <int D, int MODE>
-static int launch_gemm(ggc_ctx* ctx, hipStream_t st, int N, const GemmArgs& a) {
+int launch_gemm(ggc_ctx* ctx, hipStream_t st, int N, const GemmArgs& a) {
     static DeviceOnce attr_set;                    // per device; contexts may live on other host threads
     const size_t lds = (size_t)D * D * sizeof(float);
     if (attr_set.need(ctx->device) && lds > 48 * 1024) {
@@ -1231,10 +1128,6 @@ static int agg_graph_slice(int N, int G) {
     return want <= AggGraph<32>::CAP ? 32 : 0;
 }
 
-// The forward pass hands over the batch structure (G graphs, node_ptr) and the packed column words built by
-// build_agg_pack for the slice width agg_graph_slice chose; without them (ggc_gcn_aggregate) the direct gather runs.
-struct AggGraphs { int G = 0, sw = 0; const int32_t* node_ptr = nullptr; const int32_t* pack = nullptr; };
-
 static int build_agg_pack(ggc_ctx* ctx, hipStream_t st, int N, int G, const int32_t* node_ptr, const int32_t* batch,
                           const int32_t* row_ptr, const int32_t* col, AggGraphs& ag) {
     ag = AggGraphs{};
@@ -1261,9 +1154,8 @@ static int launch_aggregate_graph(ggc_ctx* ctx, hipStream_t st, const AggGraphs&
 }
 
 template <int D, int MODE>
-static int launch_aggregate(ggc_ctx* ctx, hipStream_t st, int N, const float* xw, const int32_t* row_ptr,
-                            const int32_t* col, const float* dis, const float* bias, const float* gate,
-                            const float* h, float* out, const AggGraphs& ag = AggGraphs{}) {
+int launch_aggregate(ggc_ctx* ctx, hipStream_t st, int N, const float* xw, const int32_t* row_ptr, const int32_t* col,
+                     const float* dis, const float* bias, const float* gate, const float* h, float* out, const AggGraphs& ag) {
     ProfScope prof(ctx, st, MODE == 0 ? "gcn_aggregate" : "sage_aggregate");
     if (ag.sw == 32) return launch_aggregate_graph<D, MODE, 32>(ctx, st, ag, xw, row_ptr, col, dis, bias, gate, h, out);
     constexpr int threads = 256;
@@ -1275,18 +1167,60 @@ static int launch_aggregate(ggc_ctx* ctx, hipStream_t st, int N, const float* xw
 }
 
 template <int D>
+int launch_graph_ctx(ggc_ctx* ctx, hipStream_t st, int G, const int32_t* node_ptr, const float* score, const float* hjk,
+                     const CtxW& w, float* gvec) {
+    hipLaunchKernelGGL((k_graph_ctx<D>), dim3(G), dim3(256), 0, st, node_ptr, score, hjk, w, gvec);
+    GGC_LAUNCH_CHECK(ctx);
+    return GGC_OK;
+}
+
+int prepare_csr(ggc_ctx* ctx, hipStream_t st, int G, int N, int E, const int32_t* edge_src, const int32_t* edge_dst,
+                const int32_t* node_ptr, bool with_dst, Csr& g) {
+    g = Csr{};
+    g.row_ptr = scratch_t<int32_t>(ctx, S_CSR_ROWPTR, (size_t)N + 1);
+    g.col = scratch_t<int32_t>(ctx, S_CSR_COL, (size_t)E);
+    g.eid = scratch_t<int32_t>(ctx, S_CSR_EID, (size_t)E);
+    int32_t* cursor = scratch_t<int32_t>(ctx, S_CSR_CURSOR, (size_t)N + 1);
+    g.dis = scratch_t<float>(ctx, S_DIS, (size_t)N);
+    if (node_ptr) g.batch = scratch_t<int32_t>(ctx, S_BATCH, (size_t)N);
+    if (with_dst) g.dst = scratch_t<int32_t>(ctx, S_AGG_PACK, (size_t)E);
+    if (!g.row_ptr || !g.col || !g.eid || !cursor || !g.dis || (node_ptr && !g.batch) || (with_dst && !g.dst)) return GGC_E_OOM;
+    int rc = build_csr(ctx, st, N, E, edge_src, edge_dst, g.row_ptr, g.col, g.eid, cursor, g.dis);
+    if (rc) return rc;
+    if (with_dst && E > 0) {
+        hipLaunchKernelGGL(k_csr_dst, dim3(cdiv(E, 256)), dim3(256), 0, st, N, E, g.row_ptr, g.dst);
+        GGC_LAUNCH_CHECK(ctx);
+    }
+    if (node_ptr) {
+        hipLaunchKernelGGL(k_fill_batch, dim3(min(cdiv(N, 256), 4096)), dim3(256), 0, st, G, N, node_ptr, g.batch);
+        GGC_LAUNCH_CHECK(ctx);
+    }
+    return GGC_OK;
+}
+
+// the (D, MODE) pairs GCNTrimapNet (ggc_gcnnet.hip) and GATTrimapNet (ggc_gat.hip) launch
+#define GGC_GEMM(D, MODE) template int launch_gemm<D, MODE>(ggc_ctx*, hipStream_t, int, const GemmArgs&);
+GGC_GEMM(32, 3) GGC_GEMM(64, 3) GGC_GEMM(96, 3) GGC_GEMM(128, 3)
+GGC_GEMM(32, 4) GGC_GEMM(64, 4) GGC_GEMM(128, 4)
+#undef GGC_GEMM
+#define GGC_AGG(D) template int launch_aggregate<D, 0>(ggc_ctx*, hipStream_t, int, const float*, const int32_t*, const int32_t*, \
+                                                       const float*, const float*, const float*, const float*, float*, const AggGraphs&);
+GGC_AGG(32) GGC_AGG(64) GGC_AGG(96) GGC_AGG(128)
+#undef GGC_AGG
+#define GGC_CTX(D) template int launch_graph_ctx<D>(ggc_ctx*, hipStream_t, int, const int32_t*, const float*, const float*, const CtxW&, float*);
+GGC_CTX(32) GGC_CTX(64) GGC_CTX(128)
+#undef GGC_CTX
+
+template <int D>
 static int forward_t(ggc_ctx* ctx, hipStream_t st, int G, int N, int E, const float* x,
                      const int32_t* edge_src, const int32_t* edge_dst, const float* edge_attr,
                      const int32_t* node_ptr, float* logits, float* probs) {
-    ResgcnWeights& m = ctx->model;
+    WeightSet& m = ctx->resgcn;
     const int n = m.n_layers, n_states = n + 2;
     const size_t ND = (size_t)N * D;
-    int32_t* row_ptr = scratch_t<int32_t>(ctx, S_CSR_ROWPTR, (size_t)N + 1);
-    int32_t* col = scratch_t<int32_t>(ctx, S_CSR_COL, (size_t)E);
-    int32_t* eid = scratch_t<int32_t>(ctx, S_CSR_EID, (size_t)E);
-    int32_t* cursor = scratch_t<int32_t>(ctx, S_CSR_CURSOR, (size_t)N + 1);
-    float* dis = scratch_t<float>(ctx, S_DIS, (size_t)N);
-    int32_t* batch = scratch_t<int32_t>(ctx, S_BATCH, (size_t)N);
+    Csr csr;
+    int rc = prepare_csr(ctx, st, G, N, E, edge_src, edge_dst, node_ptr, false, csr);
+    if (rc) return rc;
     float* states = scratch_t<float>(ctx, S_STATES, ND * n_states);
     float* gate = scratch_t<float>(ctx, S_GATE, ND);
     float* xw = scratch_t<float>(ctx, S_XW, ND);
@@ -1294,35 +1228,28 @@ static int forward_t(ggc_ctx* ctx, hipStream_t st, int G, int N, int E, const fl
     float* hjk = scratch_t<float>(ctx, S_HJK, ND);
     float* score = scratch_t<float>(ctx, S_SCORE, (size_t)N);
     float* gvec = scratch_t<float>(ctx, S_GVEC, (size_t)G * D);
-    if (!row_ptr || !col || !eid || !cursor || !dis || !batch || !states || !gate || !xw || !agg || !hjk ||
-        !score || !gvec)
-        return GGC_E_OOM;
-
-    int rc = build_csr(ctx, st, N, E, edge_src, edge_dst, row_ptr, col, eid, cursor, dis);
-    if (rc) return rc;
-    hipLaunchKernelGGL(k_fill_batch, dim3(min(cdiv(N, 256), 4096)), dim3(256), 0, st, G, N, node_ptr, batch);
-    GGC_LAUNCH_CHECK(ctx);
+    if (!states || !gate || !xw || !agg || !hjk || !score || !gvec) return GGC_E_OOM;
     AggGraphs ag;
-    if ((rc = build_agg_pack(ctx, st, N, G, node_ptr, batch, row_ptr, col, ag))) return rc;
+    if ((rc = build_agg_pack(ctx, st, N, G, node_ptr, csr.batch, csr.row_ptr, csr.col, ag))) return rc;
 
     const int wave_blocks = min(cdiv(N, 4), 8 * ctx->n_cu);
     {
-        InputW w{devp(ctx, "in_norm.norm.weight"), devp(ctx, "in_norm.norm.bias"),
-                 devp(ctx, "in_norm.norm.running_mean"), devp(ctx, "in_norm.norm.running_var"),
-                 devp(ctx, "#input_proj.0.weightT"), devp(ctx, "input_proj.0.bias"),
-                 devp(ctx, "input_proj.1.weight"), devp(ctx, "input_proj.1.bias"),
-                 devp(ctx, "prior_booster.0.weight"), devp(ctx, "prior_booster.0.bias"),
-                 devp(ctx, "#prior_booster.2.weightT"), devp(ctx, "prior_booster.2.bias")};
+        InputW w{devp(m, "in_norm.norm.weight"), devp(m, "in_norm.norm.bias"),
+                 devp(m, "in_norm.norm.running_mean"), devp(m, "in_norm.norm.running_var"),
+                 devp(m, "#input_proj.0.weightT"), devp(m, "input_proj.0.bias"),
+                 devp(m, "input_proj.1.weight"), devp(m, "input_proj.1.bias"),
+                 devp(m, "prior_booster.0.weight"), devp(m, "prior_booster.0.bias"),
+                 devp(m, "#prior_booster.2.weightT"), devp(m, "prior_booster.2.bias")};
         hipLaunchKernelGGL((k_input<D>), dim3(wave_blocks), dim3(256), 0, st, N, x, w, m.Q, m.Dt, states);
         GGC_LAUNCH_CHECK(ctx);
     }
     {
-        EdgeW w{devp(ctx, "edge_ctx.encode.0.weight"), devp(ctx, "edge_ctx.encode.0.bias"),
-                devp(ctx, "#edge_ctx.encode.2.weightT"), devp(ctx, "edge_ctx.encode.2.bias"),
-                devp(ctx, "edge_ctx.to_gate.0.weight"), devp(ctx, "edge_ctx.to_gate.0.bias"),
-                devp(ctx, "#edge_ctx.to_gate.1.weightT"), devp(ctx, "edge_ctx.to_gate.1.bias")};
+        EdgeW w{devp(m, "edge_ctx.encode.0.weight"), devp(m, "edge_ctx.encode.0.bias"),
+                devp(m, "#edge_ctx.encode.2.weightT"), devp(m, "edge_ctx.encode.2.bias"),
+                devp(m, "edge_ctx.to_gate.0.weight"), devp(m, "edge_ctx.to_gate.0.bias"),
+                devp(m, "#edge_ctx.to_gate.1.weightT"), devp(m, "edge_ctx.to_gate.1.bias")};
         const size_t eg_lds = sizeof(float) * ((size_t)m.C * m.C + (size_t)m.C * D);            // <= 48 KB (C <= 64, D <= 128)
-        hipLaunchKernelGGL((k_edge_gate<D>), dim3(min(cdiv(N, 4 * EC_NODES), 3 * ctx->n_cu)), dim3(256), eg_lds, st, N, row_ptr, eid,
+        hipLaunchKernelGGL((k_edge_gate<D>), dim3(min(cdiv(N, 4 * EC_NODES), 3 * ctx->n_cu)), dim3(256), eg_lds, st, N, csr.row_ptr, csr.eid,
                            edge_attr, w, m.C, gate);
         GGC_LAUNCH_CHECK(ctx);
     }
@@ -1331,42 +1258,39 @@ static int forward_t(ggc_ctx* ctx, hipStream_t st, int G, int N, int E, const fl
         const float* h_in = states + ND * l;
         float* h_out = states + ND * (l + 1);
         GemmArgs a{};
-        a.A1 = h_in; a.Wp1 = devp(ctx, "#gcn_layers." + s + ".lin.weight.p");
-        a.ln_w = devp(ctx, "norms." + s + ".weight"); a.ln_b = devp(ctx, "norms." + s + ".bias");
+        a.A1 = h_in; a.Wp1 = devp(m, "#gcn_layers." + s + ".lin.weight.p");
+        a.ln_w = devp(m, "norms." + s + ".weight"); a.ln_b = devp(m, "norms." + s + ".bias");
         a.out = xw; a.Dt = m.Dt;
         if ((rc = launch_gemm<D, 0>(ctx, st, N, a))) return rc;
-        if ((rc = launch_aggregate<D, 0>(ctx, st, N, xw, row_ptr, col, dis, devp(ctx, "gcn_layers." + s + ".bias"),
+        if ((rc = launch_aggregate<D, 0>(ctx, st, N, xw, csr.row_ptr, csr.col, csr.dis, devp(m, "gcn_layers." + s + ".bias"),
                                          gate, h_in, h_out, ag)))
             return rc;
     }
     {
         const float* hl = states + ND * n;
-        if ((rc = launch_aggregate<D, 1>(ctx, st, N, hl, row_ptr, col, nullptr, nullptr, nullptr, nullptr, agg, ag)))
+        if ((rc = launch_aggregate<D, 1>(ctx, st, N, hl, csr.row_ptr, csr.col, nullptr, nullptr, nullptr, nullptr, agg, ag)))
             return rc;
         GemmArgs a{};
         a.A1 = agg; a.A2 = hl;
-        a.Wp1 = devp(ctx, "#sage.lin_l.weight.p"); a.Wp2 = devp(ctx, "#sage.lin_r.weight.p");
-        a.bias = devp(ctx, "sage.lin_l.bias");
-        a.ep_w = devp(ctx, "sage_norm.weight"); a.ep_b = devp(ctx, "sage_norm.bias");
+        a.Wp1 = devp(m, "#sage.lin_l.weight.p"); a.Wp2 = devp(m, "#sage.lin_r.weight.p");
+        a.bias = devp(m, "sage.lin_l.bias");
+        a.ep_w = devp(m, "sage_norm.weight"); a.ep_b = devp(m, "sage_norm.bias");
         a.out = states + ND * (n + 1); a.Dt = m.Dt;
         if ((rc = launch_gemm<D, 1>(ctx, st, N, a))) return rc;
     }
     hipLaunchKernelGGL((k_jk<D>), dim3(cdiv(N, AggCfg<D>::RPB)), dim3(256), 0, st, N, n_states, states,
-                       devp(ctx, "#jk_w"), devp(ctx, "ctx.attn.weight"), devp(ctx, "ctx.attn.bias"), hjk, score);
+                       devp(m, "#jk_w"), devp(m, "ctx.attn.weight"), devp(m, "ctx.attn.bias"), hjk, score);
     GGC_LAUNCH_CHECK(ctx);
-    {
-        CtxW w{devp(ctx, "#ctx.compress.weightT"), devp(ctx, "ctx.compress.bias"),
-               devp(ctx, "#ctx.expand.weightT"), devp(ctx, "ctx.expand.bias")};
-        hipLaunchKernelGGL((k_graph_ctx<D>), dim3(G), dim3(256), 0, st, node_ptr, score, hjk, w, gvec);
-        GGC_LAUNCH_CHECK(ctx);
-    }
+    if ((rc = launch_graph_ctx<D>(ctx, st, G, node_ptr, score, hjk, {devp(m, "#ctx.compress.weightT"), devp(m, "ctx.compress.bias"),
+                                                                     devp(m, "#ctx.expand.weightT"), devp(m, "ctx.expand.bias")}, gvec)))
+        return rc;
     {
         GemmArgs a{};
-        a.A1 = hjk; a.Wp1 = devp(ctx, "#fuse.1.weight.p");
-        a.ln_w = devp(ctx, "fuse.0.weight"); a.ln_b = devp(ctx, "fuse.0.bias");
-        a.bias = devp(ctx, "fuse.1.bias");
-        a.batch = batch; a.gvec = gvec;
-        a.ep_w = devp(ctx, "head.weight"); a.ep_b = devp(ctx, "head.bias");
+        a.A1 = hjk; a.Wp1 = devp(m, "#fuse.1.weight.p");
+        a.ln_w = devp(m, "fuse.0.weight"); a.ln_b = devp(m, "fuse.0.bias");
+        a.bias = devp(m, "fuse.1.bias");
+        a.batch = csr.batch; a.gvec = gvec;
+        a.ep_w = devp(m, "head.weight"); a.ep_b = devp(m, "head.bias");
         a.out = logits; a.out2 = probs; a.Dt = m.Dt;
         if ((rc = launch_gemm<D, 2>(ctx, st, N, a))) return rc;
     }
@@ -1383,63 +1307,29 @@ int ggc_resgcn_configure(ggc_ctx* ctx, int hidden, int n_layers) {
     if (!ctx) return GGC_E_INVALID_ARG;
     GGC_REQUIRE(ctx, hidden >= 8 && hidden <= 128, GGC_E_UNSUPPORTED,
                 "hidden_channels=%d unsupported: the kernels are built for widths from 8 to 128", hidden);
-    GGC_REQUIRE(ctx, n_layers >= 1 && n_layers <= 30, GGC_E_INVALID_ARG, "n_layers=%d out of range [1,30]", n_layers);
-    ResgcnWeights& m = ctx->model;
-    if (m.Dt != hidden || m.n_layers != n_layers) { m.host.clear(); }
     // widths that are not a multiple of 32 run zero-padded to the next one (k_input: only the LayerNorm statistics see Dt)
-    m.Dt = hidden; m.D = (hidden + 31) / 32 * 32; m.n_layers = n_layers;
-    m.Q = hidden / 4 > 8 ? hidden / 4 : 8;   // model.py:472
-    m.C = hidden / 2 > 8 ? hidden / 2 : 8;   // model.py:123
-    m.dev_ok = false;
+    if (int rc = configure(ctx, RESGCN, (hidden + 31) / 32 * 32, hidden, n_layers)) return rc;
+    ctx->resgcn.Q = hidden / 4 > 8 ? hidden / 4 : 8;   // model.py:472
+    ctx->resgcn.C = hidden / 2 > 8 ? hidden / 2 : 8;   // model.py:123
     return GGC_OK;
 }
 
 int ggc_resgcn_load_weight(ggc_ctx* ctx, const char* name, const float* data, int64_t numel) {
-    if (!ctx) return GGC_E_INVALID_ARG;
-    GGC_REQUIRE(ctx, name && (data || numel == 0) && numel >= 0, GGC_E_INVALID_ARG, "bad weight arguments");
-    GGC_REQUIRE(ctx, ctx->model.D > 0, GGC_E_STATE, "ggc_resgcn_configure has not been called");
-    const std::string key(name);
-    const std::string tail = "num_batches_tracked";
-    if (key.size() >= tail.size() && key.compare(key.size() - tail.size(), tail.size(), tail) == 0) return GGC_OK;
-    bool known = false;
-    for (const Need& nd : needed(ctx->model))
-        if (nd.key == key) {
-            GGC_REQUIRE(ctx, nd.numel == numel, GGC_E_SHAPE, "weight '%s' has %lld elements, expected %lld", name,
-                        (long long)numel, (long long)nd.numel);
-            known = true;
-            break;
-        }
-    GGC_REQUIRE(ctx, known, GGC_E_INVALID_ARG, "unexpected state_dict key '%s' for ResGCNNet(D=%d, n=%d)", name,
-                ctx->model.Dt, ctx->model.n_layers);
-    ctx->model.host[key].assign(data, data + numel);
-    ctx->model.dev_ok = false;
-    return GGC_OK;
+    return load_weight(ctx, RESGCN, name, data, numel);
 }
 
-int ggc_resgcn_ready(ggc_ctx* ctx) {
-    if (!ctx) return GGC_E_INVALID_ARG;
-    return check_ready(ctx);
-}
+int ggc_resgcn_ready(ggc_ctx* ctx) { return check_ready(ctx, RESGCN); }
 
 int ggc_resgcn_forward(ggc_ctx* ctx, ggc_stream stream, int G, int N, int E, const float* x,
                        const int32_t* edge_src, const int32_t* edge_dst, const float* edge_attr,
                        const int32_t* node_ptr, float* logits, float* probs) {
-    if (!ctx) return GGC_E_INVALID_ARG;
-    GGC_REQUIRE(ctx, G >= 1 && N >= 1 && E >= 0, GGC_E_SHAPE, "bad sizes G=%d N=%d E=%d", G, N, E);
-    GGC_REQUIRE(ctx, x && node_ptr && (E == 0 || (edge_src && edge_dst && edge_attr)), GGC_E_INVALID_ARG,
-                "null input pointer");
-    GGC_REQUIRE(ctx, logits || probs, GGC_E_INVALID_ARG, "both outputs are NULL");
-    GGC_HIP(ctx, hipSetDevice(ctx->device));
-    int rc = prepare_weights(ctx);
+    int rc = begin_forward(ctx, RESGCN, G, N, E, x, edge_src, edge_dst, edge_attr, node_ptr, logits, probs);
     if (rc) return rc;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    switch (ctx->model.D) {
-        case 32:  return forward_t<32>(ctx, st, G, N, E, x, edge_src, edge_dst, edge_attr, node_ptr, logits, probs);
-        case 64:  return forward_t<64>(ctx, st, G, N, E, x, edge_src, edge_dst, edge_attr, node_ptr, logits, probs);
-        case 96:  return forward_t<96>(ctx, st, G, N, E, x, edge_src, edge_dst, edge_attr, node_ptr, logits, probs);
-        case 128: return forward_t<128>(ctx, st, G, N, E, x, edge_src, edge_dst, edge_attr, node_ptr, logits, probs);
-    }
-    return set_err(ctx, GGC_E_UNSUPPORTED, "hidden=%d", ctx->model.D);
+    if (with_width<32, 64, 96, 128>(ctx->resgcn.D, rc, [&](auto w) {
+            return forward_t<decltype(w)::value>(ctx, st, G, N, E, x, edge_src, edge_dst, edge_attr, node_ptr, logits, probs); }))
+        return rc;
+    return set_err(ctx, GGC_E_UNSUPPORTED, "hidden=%d", ctx->resgcn.D);
 }
 
 int ggc_build_csr(ggc_ctx* ctx, ggc_stream stream, int N, int E, const int32_t* edge_src,
@@ -1463,869 +1353,11 @@ int ggc_gcn_aggregate(ggc_ctx* ctx, ggc_stream stream, int N, int D, const float
     GGC_REQUIRE(ctx, (gate == nullptr) == (h == nullptr), GGC_E_INVALID_ARG, "gate and h must be given together");
     GGC_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    switch (D) {
-        case 32:  return launch_aggregate<32, 0>(ctx, st, N, xw, row_ptr, col, dis, bias, gate, h, h_out);
-        case 64:  return launch_aggregate<64, 0>(ctx, st, N, xw, row_ptr, col, dis, bias, gate, h, h_out);
-        case 96:  return launch_aggregate<96, 0>(ctx, st, N, xw, row_ptr, col, dis, bias, gate, h, h_out);
-        case 128: return launch_aggregate<128, 0>(ctx, st, N, xw, row_ptr, col, dis, bias, gate, h, h_out);
-    }
+    int rc;
+    if (with_width<32, 64, 96, 128>(D, rc, [&](auto w) {
+            return launch_aggregate<decltype(w)::value, 0>(ctx, st, N, xw, row_ptr, col, dis, bias, gate, h, h_out); }))
+        return rc;
     return set_err(ctx, GGC_E_UNSUPPORTED, "D=%d unsupported (32, 64, 96, 128)", D);
-}
-
-} // extern "C"
-
-// ===================================================================================================
-// GCNTrimapNet (reference model.py:239-316), eval mode.
-//   in_norm -> Linear(19, D) + BatchNorm + ReLU -> n x ResGCNBlock -> head on the concatenated block outputs
-//   ResGCNBlock (:216-232): h' = (relu(bn(GCNConv(h))) + h) * scatter_mean_dst(sigmoid(W2 relu(W1 e + b1) + b2))
-// Reuses the destination CSR, the f32-MFMA product (k_gemm mode 3, no prologue norm) and the GCNConv gather of the
-// ResGCNNet path.  The per-edge gate MLP, its scatter-mean and the block's BatchNorm / ReLU / residual epilogue are one
-// kernel (k_gn_edge_gate, at the end of this file).  BatchNorm1d(eval) = (x - mean) / sqrt(var + 1e-5) * w + b.
-// ===================================================================================================
-namespace ggc {
-
-// destination (row) of every CSR position: row_ptr[r] <= j < row_ptr[r + 1]
-__global__ void __launch_bounds__(256) k_csr_dst(int N, int E, const int32_t* __restrict__ row_ptr, int32_t* __restrict__ csr_dst) {
-    const int j = blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= E) return;
-    int lo = 0, hi = N;
-    while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (row_ptr[mid] <= j) lo = mid; else hi = mid; }
-    csr_dst[j] = lo;
-}
-
-struct BnW { const float *w, *b, *rm, *rv; };
-__device__ __forceinline__ float bn_apply(float x, const BnW& p, int k) {
-    return (x - p.rm[k]) / sqrtf(p.rv[k] + 1e-5f) * p.w[k] + p.b[k];
-}
-
-// in_norm + input_proj: one wave per node
-template <int D>
-__global__ void __launch_bounds__(256) k_gn_input(int N, const float* __restrict__ x, BnW bn_in, const float* __restrict__ w_inT,
-                                                  const float* __restrict__ b_in, BnW bn1, float* __restrict__ h) {
-    constexpr int NC = (D + 63) / 64;
-    const int lane = threadIdx.x & 63;
-    const int wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, n_waves = (gridDim.x * blockDim.x) >> 6;
-    for (int node = wave; node < N; node += n_waves) {
-        float xn[IN_CH];
-#pragma unroll
-        for (int k = 0; k < IN_CH; ++k) xn[k] = bn_apply(x[(size_t)node * IN_CH + k], bn_in, k);
-#pragma unroll
-        for (int j = 0; j < NC; ++j) {
-            const int c = lane + 64 * j;
-            if (c < D) {
-                float acc = 0.0f;
-#pragma unroll
-                for (int k = 0; k < IN_CH; ++k) acc += xn[k] * w_inT[k * D + c];
-                const float v = bn_apply(acc + b_in[c], bn1, c);
-                h[(size_t)node * D + c] = v > 0.0f ? v : 0.0f;
-            }
-        }
-    }
-}
-
-// head tail: z = relu(bn(z0 + b0)) -> Linear(D, D/2) + ReLU -> Linear(D/2, 3) (+ softmax); one wave per node
-template <int D>
-__global__ void __launch_bounds__(256) k_gn_head(int N, const float* __restrict__ z0, const float* __restrict__ b0, BnW bn,
-                                                 const float* __restrict__ w4T /*[D][D/2]*/, const float* __restrict__ b4,
-                                                 const float* __restrict__ w6 /*[3][D/2]*/, const float* __restrict__ b6,
-                                                 float* __restrict__ logits, float* __restrict__ probs) {
-    constexpr int DH = D / 2, NC = (D + 63) / 64;
-    __shared__ float s_z[4][D];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const int wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, n_waves = (gridDim.x * blockDim.x) >> 6;
-    for (int node = wave; node < N; node += n_waves) {
-#pragma unroll
-        for (int j = 0; j < NC; ++j) {
-            const int c = lane + 64 * j;
-            if (c < D) {
-                const float v = bn_apply(z0[(size_t)node * D + c] + b0[c], bn, c);
-                s_z[wv][c] = v > 0.0f ? v : 0.0f;
-            }
-        }
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        float a = 0.0f;                                    // hidden unit `lane` of the D/2 layer (D/2 <= 64)
-        if (lane < DH) {
-            for (int k = 0; k < D; ++k) a += s_z[wv][k] * w4T[k * DH + lane];
-            a += b4[lane];
-            a = a > 0.0f ? a : 0.0f;
-        }
-        float p[N_CLS];
-#pragma unroll
-        for (int c = 0; c < N_CLS; ++c) {
-            // index-order sum like the oracle: lane k contributes a_k * w6[c][k], folded sequentially by lane 0
-            p[c] = (lane < DH) ? a * w6[c * DH + lane] : 0.0f;
-        }
-        float lg[N_CLS] = {0.0f, 0.0f, 0.0f};
-        for (int k = 0; k < DH; ++k) {
-#pragma unroll
-            for (int c = 0; c < N_CLS; ++c) lg[c] += __shfl(p[c], k, 64);
-        }
-        if (lane == 0) {
-            const float l0 = lg[0] + b6[0], l1 = lg[1] + b6[1], l2 = lg[2] + b6[2];
-            if (logits) { logits[(size_t)node * 3 + 0] = l0; logits[(size_t)node * 3 + 1] = l1; logits[(size_t)node * 3 + 2] = l2; }
-            if (probs) {
-                const float mx = fmaxf(l0, fmaxf(l1, l2));
-                const float e0 = ggc_expf(l0 - mx), e1 = ggc_expf(l1 - mx), e2 = ggc_expf(l2 - mx);
-                const float s = (e0 + e1) + e2;
-                probs[(size_t)node * 3 + 0] = e0 / s; probs[(size_t)node * 3 + 1] = e1 / s; probs[(size_t)node * 3 + 2] = e2 / s;
-            }
-        }
-        __builtin_amdgcn_wave_barrier();
-    }
-}
-
-static const char* const BN_KEYS[4] = {"weight", "bias", "running_mean", "running_var"};
-
-static std::vector<Need> needed_gcnnet(const ResgcnWeights& m) {
-    const int D = m.D, n = m.n_layers;
-    std::vector<Need> v;
-    for (const char* k : BN_KEYS) v.push_back({std::string("in_norm.norm.") + k, IN_CH});
-    v.push_back({"input_proj.0.weight", (int64_t)D * IN_CH}); v.push_back({"input_proj.0.bias", D});
-    for (const char* k : BN_KEYS) v.push_back({std::string("input_proj.1.") + k, D});
-    for (int i = 0; i < n; ++i) {
-        const std::string p = "blocks." + std::to_string(i) + ".";
-        v.push_back({p + "conv.bias", D}); v.push_back({p + "conv.lin.weight", (int64_t)D * D});
-        for (const char* k : BN_KEYS) v.push_back({p + "bn." + k, D});
-        v.push_back({p + "edge_inject.proj.0.weight", (int64_t)D * EDGE_CH}); v.push_back({p + "edge_inject.proj.0.bias", D});
-        v.push_back({p + "edge_inject.proj.2.weight", (int64_t)D * D}); v.push_back({p + "edge_inject.proj.2.bias", D});
-    }
-    v.push_back({"head.0.weight", (int64_t)D * D * (n + 1)}); v.push_back({"head.0.bias", D});
-    for (const char* k : BN_KEYS) v.push_back({std::string("head.1.") + k, D});
-    v.push_back({"head.4.weight", (int64_t)(D / 2) * D}); v.push_back({"head.4.bias", D / 2});
-    v.push_back({"head.6.weight", (int64_t)N_CLS * (D / 2)}); v.push_back({"head.6.bias", N_CLS});
-    return v;
-}
-
-static int check_ready_gcnnet(ggc_ctx* ctx) {
-    ResgcnWeights& m = ctx->model2;
-    GGC_REQUIRE(ctx, m.D > 0, GGC_E_STATE, "ggc_gcnnet_configure has not been called");
-    for (const Need& nd : needed_gcnnet(m)) {
-        auto it = m.host.find(nd.key);
-        GGC_REQUIRE(ctx, it != m.host.end(), GGC_E_STATE, "missing weight '%s'", nd.key.c_str());
-        GGC_REQUIRE(ctx, (int64_t)it->second.size() == nd.numel, GGC_E_SHAPE, "weight '%s' has %zu elements, expected %lld",
-                    nd.key.c_str(), it->second.size(), (long long)nd.numel);
-    }
-    return GGC_OK;
-}
-
-static int prepare_weights_gcnnet(ggc_ctx* ctx) {
-    ResgcnWeights& m = ctx->model2;
-    if (m.dev_ok) return GGC_OK;
-    int rc = check_ready_gcnnet(ctx);
-    if (rc) return rc;
-    GGC_HIP(ctx, hipDeviceSynchronize());                  // (see prepare_weights)
-    const int D = m.D, n = m.n_layers;
-    for (auto& kv : m.host) { if ((rc = upload(ctx, m, kv.first, kv.second))) return rc; }
-    if ((rc = upload(ctx, m, "#input_proj.0.weightT", transpose(m.host["input_proj.0.weight"], D, IN_CH)))) return rc;
-    if ((rc = upload(ctx, m, "#head.4.weightT", transpose(m.host["head.4.weight"], D / 2, D)))) return rc;
-    for (int i = 0; i < n; ++i) {
-        const std::string p = "blocks." + std::to_string(i) + ".";
-        if ((rc = upload(ctx, m, "#" + p + "conv.lin.weight.p", pack_mfma(m.host[p + "conv.lin.weight"], D)))) return rc;
-        if ((rc = upload(ctx, m, "#" + p + "edge_inject.proj.0.weightT", transpose(m.host[p + "edge_inject.proj.0.weight"], D, EDGE_CH)))) return rc;
-        if ((rc = upload(ctx, m, "#" + p + "edge_inject.proj.2.weight.p", pack_mfma(m.host[p + "edge_inject.proj.2.weight"], D)))) return rc;
-    }
-    const std::vector<float>& hw = m.host["head.0.weight"];       // [D][D (n+1)]: one D x D block per concatenated state
-    for (int s = 0; s <= n; ++s) {
-        std::vector<float> blk((size_t)D * D);
-        for (int o = 0; o < D; ++o)
-            for (int k = 0; k < D; ++k) blk[(size_t)o * D + k] = hw[(size_t)o * D * (n + 1) + (size_t)s * D + k];
-        if ((rc = upload(ctx, m, "#head.0.weight.p" + std::to_string(s), pack_mfma(blk, D)))) return rc;
-    }
-    m.dev_ok = true;
-    return GGC_OK;
-}
-
-static BnW bn_of(const ResgcnWeights& m, const std::string& prefix) {
-    return BnW{devp(m, prefix + "weight"), devp(m, prefix + "bias"), devp(m, prefix + "running_mean"), devp(m, prefix + "running_var")};
-}
-
-template <int D, bool MUL_ONLY>
-static int launch_edge_gate(ggc_ctx* ctx, hipStream_t st, int N, const int32_t* row_ptr, const int32_t* eid, const int32_t* csr_dst,
-                            const float* edge_attr, const float* w1T, const float* b1, const float* w2p, const float* b2,
-                            const float* conv, const BnW& bn, const float* h, float* out);
-
-template <int D>
-static int forward_gcnnet_t(ggc_ctx* ctx, hipStream_t st, int N, int E, const float* x, const int32_t* edge_src,
-                            const int32_t* edge_dst, const float* edge_attr, float* logits, float* probs) {
-    ResgcnWeights& m = ctx->model2;
-    const int n = m.n_layers, n_states = n + 1;
-    const size_t ND = (size_t)N * D;
-    int32_t* row_ptr = scratch_t<int32_t>(ctx, S_CSR_ROWPTR, (size_t)N + 1);
-    int32_t* col = scratch_t<int32_t>(ctx, S_CSR_COL, (size_t)std::max(E, 1));
-    int32_t* eid = scratch_t<int32_t>(ctx, S_CSR_EID, (size_t)std::max(E, 1));
-    int32_t* cursor = scratch_t<int32_t>(ctx, S_CSR_CURSOR, (size_t)N + 1);
-    float* dis = scratch_t<float>(ctx, S_DIS, (size_t)N);
-    float* states = scratch_t<float>(ctx, S_STATES, ND * n_states);
-    float* xw = scratch_t<float>(ctx, S_XW, ND);
-    float* conv = scratch_t<float>(ctx, S_AGG, ND);
-    float* z0 = scratch_t<float>(ctx, S_HJK, ND);
-    if (!row_ptr || !col || !eid || !cursor || !dis || !states || !xw || !conv || !z0) return GGC_E_OOM;
-    int rc = build_csr(ctx, st, N, E, edge_src, edge_dst, row_ptr, col, eid, cursor, dis);
-    if (rc) return rc;
-    int32_t* csr_dst = scratch_t<int32_t>(ctx, S_AGG_PACK, (size_t)std::max(E, 1));        // destination of every CSR position
-    if (!csr_dst) return GGC_E_OOM;
-    if (E > 0) {
-        hipLaunchKernelGGL(k_csr_dst, dim3(cdiv(E, 256)), dim3(256), 0, st, N, E, row_ptr, csr_dst);
-        GGC_LAUNCH_CHECK(ctx);
-    }
-    const int wave_blocks = min(cdiv(N, 4), 8 * ctx->n_cu);
-    hipLaunchKernelGGL((k_gn_input<D>), dim3(wave_blocks), dim3(256), 0, st, N, x, bn_of(m, "in_norm.norm."),
-                       devp(m, "#input_proj.0.weightT"), devp(m, "input_proj.0.bias"), bn_of(m, "input_proj.1."), states);
-    GGC_LAUNCH_CHECK(ctx);
-    for (int l = 0; l < n; ++l) {
-        const std::string p = "blocks." + std::to_string(l) + ".";
-        const float* h = states + ND * l;
-        float* out = states + ND * (l + 1);
-        GemmArgs a{};
-        a.A1 = h; a.Wp1 = devp(m, "#" + p + "conv.lin.weight.p"); a.out = xw;
-        if ((rc = launch_gemm<D, 3>(ctx, st, N, a))) return rc;
-        if ((rc = launch_aggregate<D, 0>(ctx, st, N, xw, row_ptr, col, dis, devp(m, p + "conv.bias"), nullptr, nullptr, conv))) return rc;
-        // edge MLP + scatter-mean + block epilogue in one kernel (k_gn_edge_gate below)
-        if ((rc = launch_edge_gate<D, false>(ctx, st, N, row_ptr, eid, csr_dst, edge_attr, devp(m, "#" + p + "edge_inject.proj.0.weightT"),
-                                      devp(m, p + "edge_inject.proj.0.bias"), devp(m, "#" + p + "edge_inject.proj.2.weight.p"),
-                                      devp(m, p + "edge_inject.proj.2.bias"), conv, bn_of(m, p + "bn."), h, out)))
-            return rc;
-    }
-    for (int s = 0; s < n_states; ++s) {                       // head.0 on the concatenation = sum of per-state products
-        GemmArgs a{};
-        a.A1 = states + ND * s; a.Wp1 = devp(m, "#head.0.weight.p" + std::to_string(s)); a.out = z0; a.accumulate = s > 0;
-        if ((rc = launch_gemm<D, 3>(ctx, st, N, a))) return rc;
-    }
-    hipLaunchKernelGGL((k_gn_head<D>), dim3(wave_blocks), dim3(256), 0, st, N, z0, devp(m, "head.0.bias"), bn_of(m, "head.1."),
-                       devp(m, "#head.4.weightT"), devp(m, "head.4.bias"), devp(m, "head.6.weight"), devp(m, "head.6.bias"),
-                       logits, probs);
-    GGC_LAUNCH_CHECK(ctx);
-    return GGC_OK;
-}
-
-} // namespace ggc
-
-extern "C" {
-
-int ggc_gcnnet_configure(ggc_ctx* ctx, int hidden, int n_layers) {
-    if (!ctx) return GGC_E_INVALID_ARG;
-    GGC_REQUIRE(ctx, hidden == 32 || hidden == 64 || hidden == 96 || hidden == 128, GGC_E_UNSUPPORTED,
-                "hidden_channels=%d unsupported: the MFMA tiling needs a multiple of 32 up to 128", hidden);
-    GGC_REQUIRE(ctx, n_layers >= 1 && n_layers <= 30, GGC_E_INVALID_ARG, "n_layers=%d out of range [1,30]", n_layers);
-    ResgcnWeights& m = ctx->model2;
-    if (m.D != hidden || m.n_layers != n_layers) m.host.clear();
-    m.D = hidden; m.n_layers = n_layers; m.dev_ok = false;
-    return GGC_OK;
-}
-
-int ggc_gcnnet_load_weight(ggc_ctx* ctx, const char* name, const float* data, int64_t numel) {
-    if (!ctx) return GGC_E_INVALID_ARG;
-    GGC_REQUIRE(ctx, name && (data || numel == 0) && numel >= 0, GGC_E_INVALID_ARG, "bad weight arguments");
-    GGC_REQUIRE(ctx, ctx->model2.D > 0, GGC_E_STATE, "ggc_gcnnet_configure has not been called");
-    const std::string key(name), tail = "num_batches_tracked";
-    if (key.size() >= tail.size() && key.compare(key.size() - tail.size(), tail.size(), tail) == 0) return GGC_OK;
-    bool known = false;
-    for (const Need& nd : needed_gcnnet(ctx->model2))
-        if (nd.key == key) {
-            GGC_REQUIRE(ctx, nd.numel == numel, GGC_E_SHAPE, "weight '%s' has %lld elements, expected %lld", name,
-                        (long long)numel, (long long)nd.numel);
-            known = true;
-            break;
-        }
-    GGC_REQUIRE(ctx, known, GGC_E_INVALID_ARG, "unexpected state_dict key '%s' for GCNTrimapNet(D=%d, n=%d)", name,
-                ctx->model2.D, ctx->model2.n_layers);
-    ctx->model2.host[key].assign(data, data + numel);
-    ctx->model2.dev_ok = false;
-    return GGC_OK;
-}
-
-int ggc_gcnnet_ready(ggc_ctx* ctx) {
-    if (!ctx) return GGC_E_INVALID_ARG;
-    return check_ready_gcnnet(ctx);
-}
-
-int ggc_gcnnet_forward(ggc_ctx* ctx, ggc_stream stream, int N, int E, const float* x, const int32_t* edge_src,
-                       const int32_t* edge_dst, const float* edge_attr, float* logits, float* probs) {
-    if (!ctx) return GGC_E_INVALID_ARG;
-    GGC_REQUIRE(ctx, N >= 1 && E >= 0, GGC_E_SHAPE, "bad sizes N=%d E=%d", N, E);
-    GGC_REQUIRE(ctx, x && (E == 0 || (edge_src && edge_dst && edge_attr)), GGC_E_INVALID_ARG, "null input pointer");
-    GGC_REQUIRE(ctx, logits || probs, GGC_E_INVALID_ARG, "both outputs are NULL");
-    GGC_HIP(ctx, hipSetDevice(ctx->device));
-    int rc = prepare_weights_gcnnet(ctx);
-    if (rc) return rc;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    switch (ctx->model2.D) {
-        case 32:  return forward_gcnnet_t<32>(ctx, st, N, E, x, edge_src, edge_dst, edge_attr, logits, probs);
-        case 64:  return forward_gcnnet_t<64>(ctx, st, N, E, x, edge_src, edge_dst, edge_attr, logits, probs);
-        case 96:  return forward_gcnnet_t<96>(ctx, st, N, E, x, edge_src, edge_dst, edge_attr, logits, probs);
-        case 128: return forward_gcnnet_t<128>(ctx, st, N, E, x, edge_src, edge_dst, edge_attr, logits, probs);
-    }
-    return set_err(ctx, GGC_E_STATE, "model not configured");
-}
-
-} // extern "C"
-
-// ===================================================================================================
-// GCNTrimapNet, fused edge gate.  The gate MLP of a block is 316 of the model's 350 GFLOP at batch 256, and done as
-// separate passes its E x D intermediates (2 x 824 MB) cross HBM four times per block.  Here a wave owns a contiguous
-// range of destination nodes — hence a contiguous range of CSR edge positions — and walks it in tiles of 32 edges:
-//   * the first layer relu(W1 e + b1) is generated straight into the MFMA A operand (5 multiply-adds per value);
-//   * the D x D layer runs on v_mfma_f32_32x32x2_f32 against W2 packed in LDS, like k_gemm;
-//   * sigmoid(. + b2) goes through a small LDS tile and is summed per destination in CSR (= edge) order, and at the
-//     end of a destination's edges the block epilogue out = (relu(bn(conv)) + h) * mean is written directly.
-// Nothing of size E x D reaches memory.  Same sums in the same order as the unfused kernels.
-// ===================================================================================================
-namespace ggc {
-
-constexpr int EG_WAVES = 8, EG_NODES = 32;     // waves per block, destination nodes per wave
-constexpr int EG_STAGE = 66;                   // row stride of the sigmoid tile: two 32-column tiles + 2 words of padding
-
-template <int D, bool MUL_ONLY>      // MUL_ONLY: out = conv * mean (GATTrimapNet: conv holds gelu(LayerNorm(GATv2)) already)
-__global__ void __launch_bounds__(64 * EG_WAVES) k_gn_edge_gate(int N, const int32_t* __restrict__ row_ptr, const int32_t* __restrict__ eid,
-                                                                const int32_t* __restrict__ csr_dst,
-                                                                const float* __restrict__ edge_attr, const float* __restrict__ w1T,
-                                                                const float* __restrict__ b1, const float* __restrict__ w2p,
-                                                                const float* __restrict__ b2, const float* __restrict__ conv, BnW bn,
-                                                                const float* __restrict__ h, float* __restrict__ out) {
-    constexpr int T = D / 32, KH = D / 2;
-    extern __shared__ float4 eg_smem4[];                       // W2 packed [D*D] | W1T [5][D] | b1 [D] | per wave stage [32][EG_STAGE]
-    float* s_w1 = reinterpret_cast<float*>(eg_smem4) + (size_t)D * D;
-    float* s_b1 = s_w1 + EDGE_CH * D;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    float* stage = s_b1 + D + (size_t)wave * 32 * EG_STAGE;
-    const int hk = lane >> 5, li = lane & 31;
-    for (int i = tid; i < D * D / 4; i += 64 * EG_WAVES) eg_smem4[i] = reinterpret_cast<const float4*>(w2p)[i];
-    for (int i = tid; i < EDGE_CH * D; i += 64 * EG_WAVES) s_w1[i] = w1T[i];
-    for (int i = tid; i < D; i += 64 * EG_WAVES) s_b1[i] = b1[i];
-    __syncthreads();
-    const int n0 = (blockIdx.x * EG_WAVES + wave) * EG_NODES;
-    if (n0 >= N) return;                                        // (after the only block barrier)
-    const int n1 = min(n0 + EG_NODES, N);
-    const int e0 = row_ptr[n0], e1 = row_ptr[n1];
-
-    // epilogue of one destination for this lane's column of column tile t
-    auto flush = [&](int node, int t, float sum) {
-        const int c = 32 * t + li;
-        const int cnt = row_ptr[node + 1] - row_ptr[node];
-        const float cf = (float)(cnt > 1 ? cnt : 1);
-        float v = conv[(size_t)node * D + c];
-        if (!MUL_ONLY) {
-            v = bn_apply(v, bn, c);
-            v = v > 0.0f ? v : 0.0f;
-            v = v + h[(size_t)node * D + c];
-        }
-        out[(size_t)node * D + c] = v * (sum / cf);
-    };
-    float sums[T];
-#pragma unroll
-    for (int t = 0; t < T; ++t) sums[t] = 0.0f;
-    int cur = n0;                                               // destination whose edges are being summed (wave-uniform)
-    // the tile's inputs (edge attributes through eid, destination of every CSR position) are dependent global loads: the
-    // next tile's are fetched while this tile's MFMAs run
-    float ea_n[EDGE_CH] = {0.f, 0.f, 0.f, 0.f, 0.f};
-    int dnode_n = n1;
-    auto fetch = [&](int base) {
-        const int j = base + li;
-#pragma unroll
-        for (int k = 0; k < EDGE_CH; ++k) ea_n[k] = 0.0f;
-        dnode_n = n1;
-        if (j < e1) {
-            const float* a = edge_attr + (size_t)eid[j] * EDGE_CH;
-#pragma unroll
-            for (int k = 0; k < EDGE_CH; ++k) ea_n[k] = a[k];
-            dnode_n = csr_dst[j];
-        }
-    };
-    fetch(e0);
-    for (int base = e0; base < e1; base += 32) {
-        // ---- A operand: this lane's half row of relu(W1 e + b1) for edge position base + li
-        const bool have = base + li < e1;
-        float ea[EDGE_CH];
-#pragma unroll
-        for (int k = 0; k < EDGE_CH; ++k) ea[k] = ea_n[k];
-        const int dnode = dnode_n;
-        if (base + 32 < e1) fetch(base + 32);
-        float a[KH];
-#pragma unroll
-        for (int s = 0; s < KH; s += 4) {                       // four values at a time on the packed-f32 pipe, same op order
-            const int c = hk * KH + s;
-            v4f acc4 = 0.0f;
-#pragma unroll
-            for (int k = 0; k < EDGE_CH; ++k) acc4 += ea[k] * *reinterpret_cast<const v4f*>(s_w1 + k * D + c);
-            acc4 += *reinterpret_cast<const v4f*>(s_b1 + c);
-            a[s + 0] = (have && acc4.x > 0.0f) ? acc4.x : 0.0f; a[s + 1] = (have && acc4.y > 0.0f) ? acc4.y : 0.0f;
-            a[s + 2] = (have && acc4.z > 0.0f) ? acc4.z : 0.0f; a[s + 3] = (have && acc4.w > 0.0f) ? acc4.w : 0.0f;
-        }
-        f32x16 acc[T];
-#pragma unroll
-        for (int t = 0; t < T; ++t)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[t][r] = 0.0f;
-#pragma unroll
-        for (int s4 = 0; s4 < KH / 4; ++s4) {
-#pragma unroll
-            for (int t = 0; t < T; ++t) {
-                const float4 b = eg_smem4[(s4 * T + t) * 64 + lane];
-                acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[4 * s4 + 0], b.x, acc[t], 0, 0, 0);
-                acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[4 * s4 + 1], b.y, acc[t], 0, 0, 0);
-                acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[4 * s4 + 2], b.z, acc[t], 0, 0, 0);
-                acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[4 * s4 + 3], b.w, acc[t], 0, 0, 0);
-            }
-        }
-        const int n_rows = min(32, e1 - base);
-        const int cur_in = cur;
-        // ---- two column tiles at a time: sigmoid through the LDS tile, then an ordered walk down the rows in which lane
-        // (hk, li) owns column 32 (t + hk) + li
-        int c_last = cur_in;
-#pragma unroll
-        for (int t = 0; t < T; t += 2) {
-#pragma unroll
-            for (int tt = 0; tt < 2 && t + tt < T; ++tt) {
-                const float bias = b2[32 * (t + tt) + li];
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    // sigmoid as the shared IEEE sequence (include/ggc_fmath.h): the oracle produces the same bits
-                    const float z = acc[t + tt][r] + bias;
-                    stage[((r & 3) + 8 * (r >> 2) + 4 * hk) * EG_STAGE + 32 * tt + li] = ggc_sigmoid_nr(z);
-                }
-            }
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            const int mt = t + hk;                              // this lane's column tile in the walk
-            const bool mine = mt < T;
-            float sum = 0.0f;
-#pragma unroll
-            for (int q = 0; q < T; ++q) if (q == mt) sum = sums[q];
-            int c_node = cur_in;
-            for (int row = 0; row < n_rows; ++row) {
-                const int nd = __shfl(dnode, row, 64);          // wave-uniform
-                if (nd != c_node) {
-                    if (mine) {
-                        flush(c_node, mt, sum);
-                        for (int z = c_node + 1; z < nd; ++z) flush(z, mt, 0.0f);     // destinations without edges
-                    }
-                    c_node = nd; sum = 0.0f;
-                }
-                sum += stage[row * EG_STAGE + 32 * hk + li];
-            }
-#pragma unroll
-            for (int q = 0; q < T; ++q) if (q == mt) sums[q] = sum;
-            c_last = c_node;
-            __builtin_amdgcn_wave_barrier();
-        }
-        cur = c_last;
-    }
-#pragma unroll
-    for (int t = 0; t < T; ++t) {
-        if ((t & 1) == hk) {                                    // the lane half that summed this column tile
-            flush(cur, t, sums[t]);
-            for (int z = cur + 1; z < n1; ++z) flush(z, t, 0.0f);
-        }
-    }
-}
-
-template <int D, bool MUL_ONLY>
-static int launch_edge_gate(ggc_ctx* ctx, hipStream_t st, int N, const int32_t* row_ptr, const int32_t* eid, const int32_t* csr_dst,
-                            const float* edge_attr, const float* w1T, const float* b1, const float* w2p, const float* b2,
-                            const float* conv, const BnW& bn, const float* h, float* out) {
-    const size_t lds = ((size_t)D * D + (size_t)EDGE_CH * D + D + (size_t)EG_WAVES * 32 * EG_STAGE) * sizeof(float);
-    static DeviceOnce attr_set;
-    if (attr_set.need(ctx->device)) {
-        GGC_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gn_edge_gate<D, MUL_ONLY>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                         (int)lds));
-        attr_set.done(ctx->device);
-    }
-    ProfScope prof(ctx, st, "gcnnet_edge_gate");
-    hipLaunchKernelGGL((k_gn_edge_gate<D, MUL_ONLY>), dim3(cdiv(N, EG_WAVES * EG_NODES)), dim3(64 * EG_WAVES), lds, st, N, row_ptr, eid, csr_dst,
-                       edge_attr, w1T, b1, w2p, b2, conv, bn, h, out);
-    GGC_LAUNCH_CHECK(ctx);
-    return GGC_OK;
-}
-
-} // namespace ggc
-
-// ===================================================================================================
-// GATTrimapNet (reference model.py:323-414; SURVEY.md section 8(f), last rank): GATv2 attention with edge features.
-//   h0 = GELU(LN(Linear(BN(x))));  skip = skip_proj(h0)
-//   5 x { GATv2Conv(h) -> LN -> GELU -> EdgeInjectionLayer }   ;   h + skip -> GlobalContextModule -> head
-// GATv2Conv (PyG 2.x semantics, restated from its documentation — the library is absent, parity with it unpinned):
-// x_l = lin_l(x), x_r = lin_r(x) (both with bias), one self loop per node whose edge attribute is the MEAN of the node's
-// incoming edge attributes (fill_value="mean"); for an edge j -> i and head h
-//     m = leaky_relu(x_r[i] + x_l[j] + lin_edge(e_ij), 0.2);   a = att[h] . m[h];   alpha = softmax over the edges into i
-//     out_i[h] = sum_j alpha_ij x_l[j][h];   concat heads, + bias.
-// One wave per destination node (lane l holds channels l, l + 64): the per-head dot product is a butterfly over the head's
-// C = D / heads consecutive lanes; the softmax is two passes over the node's incoming edges in CSR (= edge) order, the
-// self loop last.  LayerNorm + GELU of the block are fused in (the wave holds the whole output row).  The per-block edge
-// gate is the fused MFMA kernel of GCNTrimapNet with a multiply-only epilogue; the D x D products run on k_gemm.
-// ===================================================================================================
-namespace ggc {
-
-template <int D>
-__global__ void __launch_bounds__(256) k_gat_input(int N, const float* __restrict__ x, BnW bn_in, const float* __restrict__ w_inT,
-                                                   const float* __restrict__ b_in, const float* __restrict__ ln_w,
-                                                   const float* __restrict__ ln_b, float* __restrict__ h) {
-    constexpr int NC = (D + 63) / 64;
-    const int lane = threadIdx.x & 63;
-    const int wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, n_waves = (gridDim.x * blockDim.x) >> 6;
-    for (int node = wave; node < N; node += n_waves) {
-        float xn[IN_CH];
-#pragma unroll
-        for (int k = 0; k < IN_CH; ++k) xn[k] = bn_apply(x[(size_t)node * IN_CH + k], bn_in, k);
-        float a[NC];
-        float s1 = 0.0f;
-#pragma unroll
-        for (int j = 0; j < NC; ++j) {
-            const int c = lane + 64 * j;
-            float acc = 0.0f;
-            if (c < D) {
-#pragma unroll
-                for (int k = 0; k < IN_CH; ++k) acc += xn[k] * w_inT[k * D + c];
-                acc += b_in[c];
-                s1 += acc;
-            }
-            a[j] = acc;
-        }
-        const float mean = wave_sum(s1) / (float)D;
-        float s2 = 0.0f;
-#pragma unroll
-        for (int j = 0; j < NC; ++j) { const int c = lane + 64 * j; if (c < D) { const float dv = a[j] - mean; s2 += dv * dv; } }
-        const float rstd = 1.0f / sqrtf(wave_sum(s2) / (float)D + 1e-5f);
-#pragma unroll
-        for (int j = 0; j < NC; ++j) {
-            const int c = lane + 64 * j;
-            if (c < D) h[(size_t)node * D + c] = gelu_f((a[j] - mean) * rstd * ln_w[c] + ln_b[c]);
-        }
-    }
-}
-
-struct GatW { const float *bl, *br, *weT /*[5][D]*/, *att /*[D]*/, *bias, *ln_w, *ln_b; };
-
-template <int D, int HEADS>
-__global__ void __launch_bounds__(256) k_gat_attn(int N, const int32_t* __restrict__ row_ptr, const int32_t* __restrict__ col,
-                                                  const int32_t* __restrict__ eid, const float* __restrict__ edge_attr,
-                                                  const float* __restrict__ xl, const float* __restrict__ xr, GatW w,
-                                                  float* __restrict__ out) {
-    constexpr int NC = (D + 63) / 64, C = D / HEADS;          // a head is C consecutive channels: C <= 64 consecutive lanes of one
-                                                              // register, or (C = 128: D = 128, one head) all lanes of both
-    static_assert(C >= 4 && (C & (C - 1)) == 0 && (C <= 64 || (C == 128 && NC == 2)), "head width: a power of two from 4 to 128");
-    const int lane = threadIdx.x & 63;
-    const int wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, n_waves = (gridDim.x * blockDim.x) >> 6;
-    float bl[NC], att[NC], we[NC][EDGE_CH];
-#pragma unroll
-    for (int j = 0; j < NC; ++j) {
-        const int c = lane + 64 * j;
-        bl[j] = c < D ? w.bl[c] : 0.0f; att[j] = c < D ? w.att[c] : 0.0f;
-#pragma unroll
-        for (int k = 0; k < EDGE_CH; ++k) we[j][k] = c < D ? w.weT[k * D + c] : 0.0f;
-    }
-    for (int node = wave; node < N; node += n_waves) {
-        const int beg = row_ptr[node], end = row_ptr[node + 1], cnt = end - beg;
-        float xri[NC], xli[NC];
-#pragma unroll
-        for (int j = 0; j < NC; ++j) {
-            const int c = lane + 64 * j;
-            xri[j] = c < D ? xr[(size_t)node * D + c] + w.br[c] : 0.0f;
-            xli[j] = c < D ? xl[(size_t)node * D + c] + bl[j] : 0.0f;
-        }
-        // the self loop's edge attribute: mean of the incoming ones (sum in edge order / count; zeros without edges)
-        float am[EDGE_CH] = {0.f, 0.f, 0.f, 0.f, 0.f};
-        for (int p = beg; p < end; ++p) {
-            const float* a = edge_attr + (size_t)eid[p] * EDGE_CH;
-#pragma unroll
-            for (int k = 0; k < EDGE_CH; ++k) am[k] += a[k];
-        }
-        const float cf = (float)(cnt > 0 ? cnt : 1);
-#pragma unroll
-        for (int k = 0; k < EDGE_CH; ++k) am[k] = am[k] / cf;
-        // attention logit of one edge for this lane's head(s): every lane of a head ends with the head's value
-        auto logit = [&](const float* a, const float (&xlj)[NC], float (&lg)[NC]) {
-#pragma unroll
-            for (int j = 0; j < NC; ++j) {
-                float ev = 0.0f;
-#pragma unroll
-                for (int k = 0; k < EDGE_CH; ++k) ev += a[k] * we[j][k];
-                float m = (xri[j] + xlj[j]) + ev;
-                m = m > 0.0f ? m : 0.2f * m;
-                float v = m * att[j];
-#pragma unroll
-                for (int o = (C < 64 ? C : 64) / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-                lg[j] = v;
-            }
-            if (C == 128) { const float t = lg[0] + lg[NC - 1]; lg[0] = t; lg[NC - 1] = t; }     // one head across both registers: low half + high half
-        };
-        float mx[NC], lgs[NC];
-        logit(am, xli, lgs);                                   // self loop
-#pragma unroll
-        for (int j = 0; j < NC; ++j) mx[j] = lgs[j];
-        for (int p = beg; p < end; ++p) {
-            const int src = col[p];
-            float xlj[NC], lg[NC];
-#pragma unroll
-            for (int j = 0; j < NC; ++j) { const int c = lane + 64 * j; xlj[j] = c < D ? xl[(size_t)src * D + c] + bl[j] : 0.0f; }
-            logit(edge_attr + (size_t)eid[p] * EDGE_CH, xlj, lg);
-#pragma unroll
-            for (int j = 0; j < NC; ++j) mx[j] = fmaxf(mx[j], lg[j]);
-        }
-        float ssum[NC], acc[NC];
-#pragma unroll
-        for (int j = 0; j < NC; ++j) { ssum[j] = 0.0f; acc[j] = 0.0f; }
-        for (int p = beg; p < end; ++p) {                      // the edges in order ...
-            const int src = col[p];
-            float xlj[NC], lg[NC];
-#pragma unroll
-            for (int j = 0; j < NC; ++j) { const int c = lane + 64 * j; xlj[j] = c < D ? xl[(size_t)src * D + c] + bl[j] : 0.0f; }
-            logit(edge_attr + (size_t)eid[p] * EDGE_CH, xlj, lg);
-#pragma unroll
-            for (int j = 0; j < NC; ++j) { const float e = ggc_expf(lg[j] - mx[j]); ssum[j] += e; acc[j] += e * xlj[j]; }
-        }
-#pragma unroll
-        for (int j = 0; j < NC; ++j) { const float e = ggc_expf(lgs[j] - mx[j]); ssum[j] += e; acc[j] += e * xli[j]; }    // ... the self loop last
-        // + bias, LayerNorm, GELU
-        float o[NC];
-        float s1 = 0.0f;
-#pragma unroll
-        for (int j = 0; j < NC; ++j) {
-            const int c = lane + 64 * j;
-            o[j] = c < D ? acc[j] / (ssum[j] + 1e-16f) + w.bias[c] : 0.0f;
-            if (c < D) s1 += o[j];
-        }
-        const float mean = wave_sum(s1) / (float)D;
-        float s2 = 0.0f;
-#pragma unroll
-        for (int j = 0; j < NC; ++j) { const int c = lane + 64 * j; if (c < D) { const float dv = o[j] - mean; s2 += dv * dv; } }
-        const float rstd = 1.0f / sqrtf(wave_sum(s2) / (float)D + 1e-5f);
-#pragma unroll
-        for (int j = 0; j < NC; ++j) {
-            const int c = lane + 64 * j;
-            if (c < D) out[(size_t)node * D + c] = gelu_f((o[j] - mean) * rstd * w.ln_w[c] + w.ln_b[c]);
-        }
-    }
-}
-
-// h + skip and the readout score attn . (h + skip) + b
-template <int D>
-__global__ void __launch_bounds__(256) k_gat_score(int N, const float* __restrict__ h, const float* __restrict__ skip,
-                                                   const float* __restrict__ attn_w, const float* __restrict__ attn_b,
-                                                   float* __restrict__ hs, float* __restrict__ score) {
-    constexpr int NC = (D + 63) / 64;
-    const int lane = threadIdx.x & 63;
-    const int wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, n_waves = (gridDim.x * blockDim.x) >> 6;
-    for (int node = wave; node < N; node += n_waves) {
-        float dot = 0.0f;
-#pragma unroll
-        for (int j = 0; j < NC; ++j) {
-            const int c = lane + 64 * j;
-            if (c < D) {
-                const float v = h[(size_t)node * D + c] + skip[(size_t)node * D + c];
-                hs[(size_t)node * D + c] = v;
-                dot += v * attn_w[c];
-            }
-        }
-        dot = wave_sum(dot);
-        if (lane == 0) score[node] = dot + attn_b[0];
-    }
-}
-
-static std::vector<Need> needed_gat(const ResgcnWeights& m) {
-    const int D = m.D, n = m.n_layers;
-    std::vector<Need> v;
-    for (const char* k : BN_KEYS) v.push_back({std::string("in_norm.norm.") + k, IN_CH});
-    v.push_back({"input_proj.0.weight", (int64_t)D * IN_CH}); v.push_back({"input_proj.0.bias", D});
-    v.push_back({"input_proj.1.weight", D}); v.push_back({"input_proj.1.bias", D});
-    for (int i = 0; i < n; ++i) {
-        const std::string s = std::to_string(i);
-        v.push_back({"convs." + s + ".att", D});
-        v.push_back({"convs." + s + ".lin_l.weight", (int64_t)D * D}); v.push_back({"convs." + s + ".lin_l.bias", D});
-        v.push_back({"convs." + s + ".lin_r.weight", (int64_t)D * D}); v.push_back({"convs." + s + ".lin_r.bias", D});
-        v.push_back({"convs." + s + ".lin_edge.weight", (int64_t)D * EDGE_CH}); v.push_back({"convs." + s + ".bias", D});
-        v.push_back({"lns." + s + ".weight", D}); v.push_back({"lns." + s + ".bias", D});
-        v.push_back({"edge_gates." + s + ".proj.0.weight", (int64_t)D * EDGE_CH}); v.push_back({"edge_gates." + s + ".proj.0.bias", D});
-        v.push_back({"edge_gates." + s + ".proj.2.weight", (int64_t)D * D}); v.push_back({"edge_gates." + s + ".proj.2.bias", D});
-    }
-    v.push_back({"skip_proj.weight", (int64_t)D * D});
-    v.push_back({"ctx.attn.weight", D}); v.push_back({"ctx.attn.bias", 1});
-    v.push_back({"ctx.compress.weight", (int64_t)(D / 2) * D}); v.push_back({"ctx.compress.bias", D / 2});
-    v.push_back({"ctx.expand.weight", (int64_t)D * (D / 2)}); v.push_back({"ctx.expand.bias", D});
-    v.push_back({"head.0.weight", (int64_t)D * D}); v.push_back({"head.0.bias", D});
-    v.push_back({"head.3.weight", (int64_t)N_CLS * D}); v.push_back({"head.3.bias", N_CLS});
-    return v;
-}
-
-static int check_ready_gat(ggc_ctx* ctx) {
-    ResgcnWeights& m = ctx->model3;
-    GGC_REQUIRE(ctx, m.D > 0, GGC_E_STATE, "ggc_gat_configure has not been called");
-    for (const Need& nd : needed_gat(m)) {
-        auto it = m.host.find(nd.key);
-        GGC_REQUIRE(ctx, it != m.host.end(), GGC_E_STATE, "missing weight '%s'", nd.key.c_str());
-        GGC_REQUIRE(ctx, (int64_t)it->second.size() == nd.numel, GGC_E_SHAPE, "weight '%s' has %zu elements, expected %lld",
-                    nd.key.c_str(), it->second.size(), (long long)nd.numel);
-    }
-    return GGC_OK;
-}
-
-static int prepare_weights_gat(ggc_ctx* ctx) {
-    ResgcnWeights& m = ctx->model3;
-    if (m.dev_ok) return GGC_OK;
-    int rc = check_ready_gat(ctx);
-    if (rc) return rc;
-    GGC_HIP(ctx, hipDeviceSynchronize());                  // (see prepare_weights)
-    const int D = m.D, n = m.n_layers;
-    for (auto& kv : m.host) { if ((rc = upload(ctx, m, kv.first, kv.second))) return rc; }
-    if ((rc = upload(ctx, m, "#input_proj.0.weightT", transpose(m.host["input_proj.0.weight"], D, IN_CH)))) return rc;
-    if ((rc = upload(ctx, m, "#skip_proj.weight.p", pack_mfma(m.host["skip_proj.weight"], D)))) return rc;
-    if ((rc = upload(ctx, m, "#ctx.compress.weightT", transpose(m.host["ctx.compress.weight"], D / 2, D)))) return rc;
-    if ((rc = upload(ctx, m, "#ctx.expand.weightT", transpose(m.host["ctx.expand.weight"], D, D / 2)))) return rc;
-    if ((rc = upload(ctx, m, "#head.0.weight.p", pack_mfma(m.host["head.0.weight"], D)))) return rc;
-    for (int i = 0; i < n; ++i) {
-        const std::string c = "convs." + std::to_string(i) + ".", g = "edge_gates." + std::to_string(i) + ".";
-        if ((rc = upload(ctx, m, "#" + c + "lin_l.weight.p", pack_mfma(m.host[c + "lin_l.weight"], D)))) return rc;
-        if ((rc = upload(ctx, m, "#" + c + "lin_r.weight.p", pack_mfma(m.host[c + "lin_r.weight"], D)))) return rc;
-        if ((rc = upload(ctx, m, "#" + c + "lin_edge.weightT", transpose(m.host[c + "lin_edge.weight"], D, EDGE_CH)))) return rc;
-        if ((rc = upload(ctx, m, "#" + g + "proj.0.weightT", transpose(m.host[g + "proj.0.weight"], D, EDGE_CH)))) return rc;
-        if ((rc = upload(ctx, m, "#" + g + "proj.2.weight.p", pack_mfma(m.host[g + "proj.2.weight"], D)))) return rc;
-    }
-    m.dev_ok = true;
-    return GGC_OK;
-}
-
-template <int D>
-static int forward_gat_t(ggc_ctx* ctx, hipStream_t st, int G, int N, int E, const float* x, const int32_t* edge_src,
-                         const int32_t* edge_dst, const float* edge_attr, const int32_t* node_ptr, float* logits, float* probs) {
-    ResgcnWeights& m = ctx->model3;
-    const int heads = m.Q;
-    const int n = m.n_layers;
-    const size_t ND = (size_t)N * D;
-    int32_t* row_ptr = scratch_t<int32_t>(ctx, S_CSR_ROWPTR, (size_t)N + 1);
-    int32_t* col = scratch_t<int32_t>(ctx, S_CSR_COL, (size_t)std::max(E, 1));
-    int32_t* eid = scratch_t<int32_t>(ctx, S_CSR_EID, (size_t)std::max(E, 1));
-    int32_t* cursor = scratch_t<int32_t>(ctx, S_CSR_CURSOR, (size_t)N + 1);
-    float* dis = scratch_t<float>(ctx, S_DIS, (size_t)N);
-    int32_t* batch = scratch_t<int32_t>(ctx, S_BATCH, (size_t)N);
-    float* buf = scratch_t<float>(ctx, S_STATES, ND * 4);        // h (ping) | h (pong) | skip | gelu(LN(conv))
-    float* xl = scratch_t<float>(ctx, S_XW, ND);
-    float* xr = scratch_t<float>(ctx, S_AGG, ND);
-    float* hs = scratch_t<float>(ctx, S_HJK, ND);
-    float* score = scratch_t<float>(ctx, S_SCORE, (size_t)N);
-    float* gvec = scratch_t<float>(ctx, S_GVEC, (size_t)G * D);
-    if (!row_ptr || !col || !eid || !cursor || !dis || !batch || !buf || !xl || !xr || !hs || !score || !gvec) return GGC_E_OOM;
-    int rc = build_csr(ctx, st, N, E, edge_src, edge_dst, row_ptr, col, eid, cursor, dis);
-    if (rc) return rc;
-    int32_t* csr_dst = scratch_t<int32_t>(ctx, S_AGG_PACK, (size_t)std::max(E, 1));
-    if (!csr_dst) return GGC_E_OOM;
-    if (E > 0) {
-        hipLaunchKernelGGL(k_csr_dst, dim3(cdiv(E, 256)), dim3(256), 0, st, N, E, row_ptr, csr_dst);
-        GGC_LAUNCH_CHECK(ctx);
-    }
-    hipLaunchKernelGGL(k_fill_batch, dim3(min(cdiv(N, 256), 4096)), dim3(256), 0, st, G, N, node_ptr, batch);
-    GGC_LAUNCH_CHECK(ctx);
-    const int wave_blocks = min(cdiv(N, 4), 8 * ctx->n_cu);
-    float *h = buf, *h2 = buf + ND, *skip = buf + 2 * ND, *act = buf + 3 * ND;
-    hipLaunchKernelGGL((k_gat_input<D>), dim3(wave_blocks), dim3(256), 0, st, N, x, bn_of(m, "in_norm.norm."),
-                       devp(m, "#input_proj.0.weightT"), devp(m, "input_proj.0.bias"), devp(m, "input_proj.1.weight"),
-                       devp(m, "input_proj.1.bias"), h);
-    GGC_LAUNCH_CHECK(ctx);
-    {
-        GemmArgs a{};
-        a.A1 = h; a.Wp1 = devp(m, "#skip_proj.weight.p"); a.out = skip;
-        if ((rc = launch_gemm<D, 3>(ctx, st, N, a))) return rc;
-    }
-    for (int l = 0; l < n; ++l) {
-        const std::string c = "convs." + std::to_string(l) + ".", g = "edge_gates." + std::to_string(l) + ".", ln = "lns." + std::to_string(l) + ".";
-        GemmArgs a{};
-        a.A1 = h; a.Wp1 = devp(m, "#" + c + "lin_l.weight.p"); a.out = xl;
-        if ((rc = launch_gemm<D, 3>(ctx, st, N, a))) return rc;
-        a.Wp1 = devp(m, "#" + c + "lin_r.weight.p"); a.out = xr;
-        if ((rc = launch_gemm<D, 3>(ctx, st, N, a))) return rc;
-        GatW w{devp(m, c + "lin_l.bias"), devp(m, c + "lin_r.bias"), devp(m, "#" + c + "lin_edge.weightT"), devp(m, c + "att"),
-               devp(m, c + "bias"), devp(m, ln + "weight"), devp(m, ln + "bias")};
-        {
-            ProfScope prof(ctx, st, "gat_attention");
-            if (heads == 8) hipLaunchKernelGGL((k_gat_attn<D, 8>), dim3(wave_blocks), dim3(256), 0, st, N, row_ptr, col, eid, edge_attr, xl, xr, w, act);
-            else if (heads == 4) hipLaunchKernelGGL((k_gat_attn<D, 4>), dim3(wave_blocks), dim3(256), 0, st, N, row_ptr, col, eid, edge_attr, xl, xr, w, act);
-            else if (heads == 2) hipLaunchKernelGGL((k_gat_attn<D, 2>), dim3(wave_blocks), dim3(256), 0, st, N, row_ptr, col, eid, edge_attr, xl, xr, w, act);
-            else hipLaunchKernelGGL((k_gat_attn<D, 1>), dim3(wave_blocks), dim3(256), 0, st, N, row_ptr, col, eid, edge_attr, xl, xr, w, act);
-        }
-        GGC_LAUNCH_CHECK(ctx);
-        if ((rc = launch_edge_gate<D, true>(ctx, st, N, row_ptr, eid, csr_dst, edge_attr, devp(m, "#" + g + "proj.0.weightT"),
-                                            devp(m, g + "proj.0.bias"), devp(m, "#" + g + "proj.2.weight.p"), devp(m, g + "proj.2.bias"),
-                                            act, BnW{}, nullptr, h2)))
-            return rc;
-        std::swap(h, h2);
-    }
-    hipLaunchKernelGGL((k_gat_score<D>), dim3(wave_blocks), dim3(256), 0, st, N, h, skip, devp(m, "ctx.attn.weight"),
-                       devp(m, "ctx.attn.bias"), hs, score);
-    GGC_LAUNCH_CHECK(ctx);
-    {
-        CtxW w{devp(m, "#ctx.compress.weightT"), devp(m, "ctx.compress.bias"), devp(m, "#ctx.expand.weightT"), devp(m, "ctx.expand.bias")};
-        hipLaunchKernelGGL((k_graph_ctx<D>), dim3(G), dim3(256), 0, st, node_ptr, score, hs, w, gvec);
-        GGC_LAUNCH_CHECK(ctx);
-    }
-    {
-        GemmArgs a{};
-        a.A1 = hs; a.Wp1 = devp(m, "#head.0.weight.p"); a.bias = devp(m, "head.0.bias");
-        a.batch = batch; a.gvec = gvec;
-        a.ep_w = devp(m, "head.3.weight"); a.ep_b = devp(m, "head.3.bias");
-        a.out = logits; a.out2 = probs;
-        if ((rc = launch_gemm<D, 4>(ctx, st, N, a))) return rc;
-    }
-    return GGC_OK;
-}
-
-} // namespace ggc
-
-extern "C" {
-
-int ggc_gat_configure(ggc_ctx* ctx, int hidden, int n_heads, int n_layers) {
-    if (!ctx) return GGC_E_INVALID_ARG;
-    GGC_REQUIRE(ctx, hidden == 32 || hidden == 64 || hidden == 128, GGC_E_UNSUPPORTED,
-                "hidden_channels=%d unsupported: GATTrimapNet runs at 32, 64 or 128 (a head must span a power-of-two number of lanes)", hidden);
-    GGC_REQUIRE(ctx, n_heads == 1 || n_heads == 2 || n_heads == 4 || n_heads == 8, GGC_E_UNSUPPORTED,
-                "n_heads=%d unsupported: 1, 2, 4 or 8 (the reference's default is 8)", n_heads);
-    GGC_REQUIRE(ctx, n_layers >= 1 && n_layers <= 30, GGC_E_INVALID_ARG, "n_layers=%d out of range [1,30]", n_layers);
-    ResgcnWeights& m = ctx->model3;
-    if (m.D != hidden || m.n_layers != n_layers) m.host.clear();     // (the head count changes no weight shape: att is [1, H, D / H] = D values)
-    m.D = hidden; m.n_layers = n_layers; m.Q = n_heads; m.dev_ok = false;
-    return GGC_OK;
-}
-
-int ggc_gat_load_weight(ggc_ctx* ctx, const char* name, const float* data, int64_t numel) {
-    if (!ctx) return GGC_E_INVALID_ARG;
-    GGC_REQUIRE(ctx, name && (data || numel == 0) && numel >= 0, GGC_E_INVALID_ARG, "bad weight arguments");
-    GGC_REQUIRE(ctx, ctx->model3.D > 0, GGC_E_STATE, "ggc_gat_configure has not been called");
-    const std::string key(name), tail = "num_batches_tracked";
-    if (key.size() >= tail.size() && key.compare(key.size() - tail.size(), tail.size(), tail) == 0) return GGC_OK;
-    bool known = false;
-    for (const Need& nd : needed_gat(ctx->model3))
-        if (nd.key == key) {
-            GGC_REQUIRE(ctx, nd.numel == numel, GGC_E_SHAPE, "weight '%s' has %lld elements, expected %lld", name,
-                        (long long)numel, (long long)nd.numel);
-            known = true;
-            break;
-        }
-    GGC_REQUIRE(ctx, known, GGC_E_INVALID_ARG, "unexpected state_dict key '%s' for GATTrimapNet(D=%d, n=%d)", name,
-                ctx->model3.D, ctx->model3.n_layers);
-    ctx->model3.host[key].assign(data, data + numel);
-    ctx->model3.dev_ok = false;
-    return GGC_OK;
-}
-
-int ggc_gat_ready(ggc_ctx* ctx) {
-    if (!ctx) return GGC_E_INVALID_ARG;
-    return check_ready_gat(ctx);
-}
-
-int ggc_gat_forward(ggc_ctx* ctx, ggc_stream stream, int G, int N, int E, const float* x, const int32_t* edge_src,
-                    const int32_t* edge_dst, const float* edge_attr, const int32_t* node_ptr, float* logits, float* probs) {
-    if (!ctx) return GGC_E_INVALID_ARG;
-    GGC_REQUIRE(ctx, G >= 1 && N >= 1 && E >= 0, GGC_E_SHAPE, "bad sizes G=%d N=%d E=%d", G, N, E);
-    GGC_REQUIRE(ctx, x && node_ptr && (E == 0 || (edge_src && edge_dst && edge_attr)), GGC_E_INVALID_ARG, "null input pointer");
-    GGC_REQUIRE(ctx, logits || probs, GGC_E_INVALID_ARG, "both outputs are NULL");
-    GGC_HIP(ctx, hipSetDevice(ctx->device));
-    int rc = prepare_weights_gat(ctx);
-    if (rc) return rc;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    switch (ctx->model3.D) {
-        case 32:  return forward_gat_t<32>(ctx, st, G, N, E, x, edge_src, edge_dst, edge_attr, node_ptr, logits, probs);
-        case 64:  return forward_gat_t<64>(ctx, st, G, N, E, x, edge_src, edge_dst, edge_attr, node_ptr, logits, probs);
-        case 128: return forward_gat_t<128>(ctx, st, G, N, E, x, edge_src, edge_dst, edge_attr, node_ptr, logits, probs);
-    }
-    return set_err(ctx, GGC_E_STATE, "model not configured");
 }
 
 } // extern "C"

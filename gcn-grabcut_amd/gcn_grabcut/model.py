@@ -89,7 +89,117 @@ if _TORCH:
             self.lin_l = nn.Linear(dim, dim, bias=True)
             self.lin_r = nn.Linear(dim, dim, bias=False)
 
-    class ResGCNNet(nn.Module):
+    class _NativeNet(nn.Module):
+        """What the three networks share on the host: weights kept resident in a library context, the input checks, and
+        the inference entries.  A subclass names its library entries (`_KEY`: ggc_<key>_*) and implements `_run`."""
+        _KEY = ""
+        _TRAIN_ERROR = ""          # _run's message in train mode
+
+        def __init__(self):
+            super().__init__()
+            self._uid = next(_model_uid)   # identifies this model in a context's record of resident weights
+
+        def _device_index(self) -> int:
+            dev = next(self.parameters()).device
+            if dev.type != "cuda":
+                raise RuntimeError(f"{type(self).__name__} runs on an MI355X through libggc_hip.so only; "
+                                   f"the model is on '{dev}'. Move it with .to('cuda') — there is no CPU fallback.")
+            return dev.index if dev.index is not None else torch.cuda.current_device()
+
+        def _sync_weights(self, ctx: "_native.Context", *configure_args, transform=None) -> None:
+            """configure + load_weight (each float tensor, through `transform(key, array)` if given) + ready, unless
+            this model's current state_dict is what the context already holds."""
+            sd = self.state_dict()
+            # the record lives on the CONTEXT: another model may have replaced this one's weights there since
+            fp = (self._uid, tuple((k, v.data_ptr(), v._version) for k, v in sd.items()))
+            if ctx.resident.get(self._KEY) == fp:
+                return
+            ctx.call(f"ggc_{self._KEY}_configure", *configure_args)
+            for k, v in sd.items():
+                if not v.dtype.is_floating_point:
+                    continue   # num_batches_tracked
+                a = v.detach().to(device="cpu", dtype=torch.float32).contiguous().numpy()
+                if transform is not None:
+                    a = transform(k, a)
+                ctx.call(f"ggc_{self._KEY}_load_weight", k.encode(), a.ctypes.data, a.size)
+            ctx.call(f"ggc_{self._KEY}_ready")
+            ctx.resident[self._KEY] = fp
+
+        def _prepare(self, ctx, *configure_args, transform=None):
+            """(context, device index) of an eval-mode forward, with this model's weights resident in the context."""
+            if self.training:
+                raise RuntimeError(self._TRAIN_ERROR)
+            dev_index = self._device_index()
+            if ctx is None:                      # a pipeline replica passes its private context (own scratch arena)
+                ctx = _native.get_context(dev_index)
+            self._sync_weights(ctx, *configure_args, transform=transform)
+            return ctx, dev_index
+
+        @staticmethod
+        def _inputs(data, dev, with_node_ptr: bool = True):
+            """x (N, 19) f32, src / dst int32, edge_attr (E, 5) f32 (zeros when absent, reference model.py:511-512) and
+            the int32 graph boundaries (None unless with_node_ptr) of `data`, which must be on `dev`."""
+            x = data.x
+            if x.device != dev:
+                raise RuntimeError(f"data.x is on {x.device}, model on {dev}")
+            x = x.to(torch.float32).contiguous()
+            n = x.size(0)
+            if x.dim() != 2 or x.size(1) != N_NODE_FEATS:
+                raise ValueError(f"data.x must be (N, {N_NODE_FEATS}), got {tuple(x.shape)}")
+            ei = data.edge_index
+            edge_attr = getattr(data, "edge_attr", None)
+            if edge_attr is None:
+                edge_attr = torch.zeros(ei.size(1), N_EDGE_FEATS, device=dev)
+            edge_attr = edge_attr.to(torch.float32).contiguous()
+            src, dst = ei[0].to(torch.int32).contiguous(), ei[1].to(torch.int32).contiguous()
+            return x, src, dst, edge_attr, (_node_ptr(data, n, dev) if with_node_ptr else None)
+
+        @staticmethod
+        def _outputs(n: int, dev, want_logits: bool, want_probs: bool):
+            """(logits, probs) buffers (N, 3), None where not wanted."""
+            new = lambda want: torch.empty(n, 3, dtype=torch.float32, device=dev) if want else None
+            return new(want_logits), new(want_probs)
+
+        def forward(self, data) -> "torch.Tensor":
+            """logits (N, 3) on the model's device."""
+            with torch.no_grad():
+                return self._run(data, True, False)[0]
+
+        @torch.no_grad()
+        def predict_probs(self, data) -> np.ndarray:
+            """softmax(logits) as a host array (reference model.py:543-546)."""
+            self.eval()
+            return self._run(data, False, True)[1].float().cpu().numpy()
+
+        @torch.no_grad()
+        def predict_probs_device(self, data, ctx=None) -> "torch.Tensor":
+            """Additive: like predict_probs but the result stays in HBM (ctx: library context to run in)."""
+            if self.training:
+                self.eval()
+            return self._run(data, False, True, ctx)[1]
+
+        @torch.no_grad()
+        def predict_trimap(self, data, segments: np.ndarray,
+                           threshold_fg: float = 0.55, threshold_bg: float = 0.55) -> np.ndarray:
+            return _probs_to_trimap(self.predict_probs(data), segments, threshold_fg, threshold_bg)
+
+    def _node_ptr(data, n: int, dev) -> "torch.Tensor":
+        """int32 [G+1] graph boundaries of a batch (graphs are contiguous, PyG collation)."""
+        node_ptr = getattr(data, "node_ptr32", None)
+        if node_ptr is not None:
+            return node_ptr
+        batch = getattr(data, "batch", None)
+        if batch is None:
+            return torch.tensor([0, n], dtype=torch.int32, device=dev)
+        n_graphs = getattr(data, "num_graphs", None)
+        if n_graphs is None:
+            n_graphs = int(batch.max().item()) + 1   # reference model.py:86
+        counts = torch.bincount(batch, minlength=n_graphs)
+        node_ptr = torch.zeros(n_graphs + 1, dtype=torch.int32, device=dev)
+        node_ptr[1:] = torch.cumsum(counts, 0).to(torch.int32)
+        return node_ptr
+
+    class ResGCNNet(_NativeNet):
         """
         Residual GCN with jumping-knowledge fusion (reference model.py:421-590),
         executed by hand-written gfx950 kernels.
@@ -138,7 +248,6 @@ if _TORCH:
             self.head = nn.Linear(D, n_classes)
             self.dropout = dropout
             self._init_weights()
-            self._uid = next(_model_uid)   # identifies this model in a context's record of resident weights
 
         def _init_weights(self):
             # reference model.py:501-506
@@ -150,63 +259,17 @@ if _TORCH:
 
         # ---------------------------------------------------------------- native
 
-        def _device_index(self) -> int:
-            dev = self.jk_logits.device
-            if dev.type != "cuda":
-                raise RuntimeError(
-                    "ResGCNNet runs on an MI355X through libggc_hip.so only; "
-                    f"the model is on '{dev}'. Move it with .to('cuda') — there is no CPU fallback."
-                )
-            return dev.index if dev.index is not None else torch.cuda.current_device()
-
-        def _sync_weights(self, ctx: "_native.Context") -> None:
-            sd = self.state_dict()
-            # the record lives on the CONTEXT: another model may have replaced this one's weights there since
-            fp = (self._uid, tuple((k, v.data_ptr(), v._version) for k, v in sd.items()))
-            if ctx.resident.get("resgcn") == fp:
-                return
-            ctx.call("ggc_resgcn_configure", self.hidden_channels, self.n_layers)
-            for k, v in sd.items():
-                if not v.dtype.is_floating_point:
-                    continue   # num_batches_tracked
-                a = v.detach().to(device="cpu", dtype=torch.float32).contiguous().numpy()
-                ctx.call("ggc_resgcn_load_weight", k.encode(), a.ctypes.data, a.size)
-            ctx.call("ggc_resgcn_ready")
-            ctx.resident["resgcn"] = fp
+        _KEY = "resgcn"
+        _TRAIN_ERROR = ("ResGCNNet._run is the eval-mode forward: call .eval() first "
+                        "(train mode goes through _train_forward)")
 
         def _run(self, data, want_logits: bool, want_probs: bool, ctx=None):
-            if self.training:
-                raise RuntimeError("ResGCNNet._run is the eval-mode forward: call .eval() first "
-                                   "(train mode goes through _train_forward)")
-            dev_index = self._device_index()
-            if ctx is None:                      # a pipeline replica passes its private context (own scratch arena)
-                ctx = _native.get_context(dev_index)
-            self._sync_weights(ctx)
+            ctx, dev_index = self._prepare(ctx, self.hidden_channels, self.n_layers)
             dev = torch.device("cuda", dev_index)
-
-            x = data.x
-            if x.device != dev:
-                raise RuntimeError(f"data.x is on {x.device}, model on {dev}")
-            x = x.to(torch.float32).contiguous()
-            n = x.size(0)
-            if x.dim() != 2 or x.size(1) != N_NODE_FEATS:
-                raise ValueError(f"data.x must be (N, {N_NODE_FEATS}), got {tuple(x.shape)}")
-            ei = data.edge_index
-            e = ei.size(1)
-            edge_attr = getattr(data, "edge_attr", None)
-            if edge_attr is None:                      # reference model.py:511-512
-                edge_attr = torch.zeros(e, N_EDGE_FEATS, device=dev)
-            edge_attr = edge_attr.to(torch.float32).contiguous()
-            src = ei[0].to(torch.int32).contiguous()
-            dst = ei[1].to(torch.int32).contiguous()
-
-            node_ptr = _node_ptr(data, n, dev)
-            g = node_ptr.numel() - 1
-
-            logits = torch.empty(n, 3, dtype=torch.float32, device=dev) if want_logits else None
-            probs = torch.empty(n, 3, dtype=torch.float32, device=dev) if want_probs else None
+            x, src, dst, edge_attr, node_ptr = self._inputs(data, dev)
+            logits, probs = self._outputs(x.size(0), dev, want_logits, want_probs)
             ctx.call(
-                "ggc_resgcn_forward", _native.current_stream(dev_index), g, n, e,
+                "ggc_resgcn_forward", _native.current_stream(dev_index), node_ptr.numel() - 1, x.size(0), src.numel(),
                 x.data_ptr(), src.data_ptr(), dst.data_ptr(), edge_attr.data_ptr(), node_ptr.data_ptr(),
                 _native.ptr(logits), _native.ptr(probs),
             )
@@ -217,8 +280,7 @@ if _TORCH:
             call; in train mode a differentiable forward (see `_train_forward`)."""
             if self.training:
                 return self._train_forward(data)
-            with torch.no_grad():
-                return self._run(data, True, False)[0]
+            return super().forward(data)
 
         def _train_forward(self, data) -> "torch.Tensor":
             """Training forward, reference model.py:508-536 with autograd.  The dense layers are torch modules (each
@@ -232,24 +294,13 @@ if _TORCH:
                 raise ValueError(f"ResGCNNet trains at hidden_channels in {train_ops.TRAIN_WIDTHS} (got {D}); "
                                  "other widths are inference-only")
             dev_index = self._device_index()
-            dev = torch.device("cuda", dev_index)
-            x = data.x
-            if x.device != dev:
-                raise RuntimeError(f"data.x is on {x.device}, model on {dev}")
-            x = x.to(torch.float32)
-            n = x.size(0)
-            if x.dim() != 2 or x.size(1) != N_NODE_FEATS:
-                raise ValueError(f"data.x must be (N, {N_NODE_FEATS}), got {tuple(x.shape)}")
-            ei = data.edge_index
-            edge_attr = getattr(data, "edge_attr", None)
-            if edge_attr is None:                      # reference model.py:511-512
-                edge_attr = torch.zeros(ei.size(1), N_EDGE_FEATS, device=dev)
-            prep = train_ops.GraphPrep(_native.get_context(dev_index), ei, n, _node_ptr(data, n, dev))
+            x, _, _, edge_attr, node_ptr = self._inputs(data, torch.device("cuda", dev_index))
+            prep = train_ops.GraphPrep(_native.get_context(dev_index), data.edge_index, x.size(0), node_ptr)
             p_drop = self.dropout if self.training else 0.0
 
             h = self.input_proj(self.in_norm(x))
             h = h * (1.0 + self.prior_booster(x[:, -N_PRIOR_FEATS:]))
-            ctx_vec = train_ops.edge_mean(self.edge_ctx.encode(edge_attr.to(torch.float32)), prep)
+            ctx_vec = train_ops.edge_mean(self.edge_ctx.encode(edge_attr), prep)
             gate = self.edge_ctx.to_gate(ctx_vec)
             states = [h]
             for gcn, norm in zip(self.gcn_layers, self.norms):
@@ -273,24 +324,6 @@ if _TORCH:
             """Fusion weights over [input, block 1..n, SAGE branch] (model.py:538-541)."""
             return torch.softmax(self.jk_logits.detach(), dim=0).cpu().numpy()
 
-        @torch.no_grad()
-        def predict_probs(self, data) -> np.ndarray:
-            """softmax(logits) as a host array (model.py:543-546)."""
-            self.eval()
-            return self._run(data, False, True)[1].float().cpu().numpy()
-
-        @torch.no_grad()
-        def predict_probs_device(self, data, ctx=None) -> "torch.Tensor":
-            """Additive: like predict_probs but the result stays in HBM (ctx: library context to run in)."""
-            if self.training:
-                self.eval()
-            return self._run(data, False, True, ctx)[1]
-
-        @torch.no_grad()
-        def predict_trimap(self, data, segments: np.ndarray,
-                           threshold_fg: float = 0.55, threshold_bg: float = 0.55) -> np.ndarray:
-            return _probs_to_trimap(self.predict_probs(data), segments, threshold_fg, threshold_bg)
-
         def param_groups(self, base_lr: float) -> list[dict]:
             """Layer-wise learning-rate decay groups (model.py:559-590); kept for API parity."""
             groups = []
@@ -307,22 +340,6 @@ if _TORCH:
                                       list(self.head.parameters())), "lr": base_lr})
             return groups
 
-    def _node_ptr(data, n: int, dev) -> "torch.Tensor":
-        """int32 [G+1] graph boundaries of a batch (graphs are contiguous, PyG collation)."""
-        batch = getattr(data, "batch", None)
-        node_ptr = getattr(data, "node_ptr32", None)
-        if node_ptr is None:
-            if batch is None:
-                node_ptr = torch.tensor([0, n], dtype=torch.int32, device=dev)
-            else:
-                n_graphs = getattr(data, "num_graphs", None)
-                if n_graphs is None:
-                    n_graphs = int(batch.max().item()) + 1   # reference model.py:86
-                counts = torch.bincount(batch, minlength=n_graphs)
-                node_ptr = torch.zeros(n_graphs + 1, dtype=torch.int32, device=dev)
-                node_ptr[1:] = torch.cumsum(counts, 0).to(torch.int32)
-        return node_ptr
-
     class _EdgeInjection(nn.Module):
         """Parameter holder for reference EdgeInjectionLayer (model.py:142-162)."""
         def __init__(self, edge_dim: int, hidden_dim: int):
@@ -337,7 +354,7 @@ if _TORCH:
             self.bn = nn.BatchNorm1d(dim)
             self.edge_inject = _EdgeInjection(edge_dim, dim)
 
-    class GCNTrimapNet(nn.Module):
+    class GCNTrimapNet(_NativeNet):
         """
         Baseline GCN with residual blocks, per-block edge injection and a dense-concat head (reference
         model.py:239-316).  Same `state_dict` keys as the reference module, so a
@@ -364,28 +381,9 @@ if _TORCH:
                 nn.Linear(hidden_channels * (n_layers + 1), hidden_channels), nn.BatchNorm1d(hidden_channels), nn.ReLU(),
                 nn.Dropout(dropout), nn.Linear(hidden_channels, hidden_channels // 2), nn.ReLU(),
                 nn.Linear(hidden_channels // 2, n_classes))
-            self._uid = next(_model_uid)
 
-        def _device_index(self) -> int:
-            dev = self.head[0].weight.device
-            if dev.type != "cuda":
-                raise RuntimeError("GCNTrimapNet runs on an MI355X through libggc_hip.so only; "
-                                   f"the model is on '{dev}'. Move it with .to('cuda') — there is no CPU fallback.")
-            return dev.index if dev.index is not None else torch.cuda.current_device()
-
-        def _sync_weights(self, ctx: "_native.Context") -> None:
-            sd = self.state_dict()
-            fp = (self._uid, tuple((k, v.data_ptr(), v._version) for k, v in sd.items()))
-            if ctx.resident.get("gcnnet") == fp:
-                return
-            ctx.call("ggc_gcnnet_configure", self._kernel_width, self.n_layers)
-            for k, v in sd.items():
-                if not v.dtype.is_floating_point:
-                    continue   # num_batches_tracked
-                a = self._padded(k, v.detach().to(device="cpu", dtype=torch.float32).contiguous().numpy())
-                ctx.call("ggc_gcnnet_load_weight", k.encode(), a.ctypes.data, a.size)
-            ctx.call("ggc_gcnnet_ready")
-            ctx.resident["gcnnet"] = fp
+        _KEY = "gcnnet"
+        _TRAIN_ERROR = "GCNTrimapNet on MI355X is inference-only: call .eval() first"
 
         def _padded(self, key: str, a: np.ndarray) -> np.ndarray:
             """Tensor `key` at the kernels' width: zero rows / columns, and BatchNorm statistics (mean 0, var 1, weight 1,
@@ -415,69 +413,13 @@ if _TORCH:
             return pad(a, (w, w))
 
         def _run(self, data, want_logits: bool, want_probs: bool, ctx=None):
-            if self.training:
-                raise RuntimeError("GCNTrimapNet on MI355X is inference-only: call .eval() first")
-            dev_index = self._device_index()
-            if ctx is None:
-                ctx = _native.get_context(dev_index)
-            self._sync_weights(ctx)
+            ctx, dev_index = self._prepare(ctx, self._kernel_width, self.n_layers, transform=self._padded)
             dev = torch.device("cuda", dev_index)
-            x = data.x
-            if x.device != dev:
-                raise RuntimeError(f"data.x is on {x.device}, model on {dev}")
-            x = x.to(torch.float32).contiguous()
-            n = x.size(0)
-            if x.dim() != 2 or x.size(1) != N_NODE_FEATS:
-                raise ValueError(f"data.x must be (N, {N_NODE_FEATS}), got {tuple(x.shape)}")
-            ei = data.edge_index
-            e = ei.size(1)
-            edge_attr = getattr(data, "edge_attr", None)
-            if edge_attr is None:                      # reference model.py:294-295
-                edge_attr = torch.zeros(e, N_EDGE_FEATS, device=dev)
-            edge_attr = edge_attr.to(torch.float32).contiguous()
-            src, dst = ei[0].to(torch.int32).contiguous(), ei[1].to(torch.int32).contiguous()
-            logits = torch.empty(n, 3, dtype=torch.float32, device=dev) if want_logits else None
-            probs = torch.empty(n, 3, dtype=torch.float32, device=dev) if want_probs else None
-            ctx.call("ggc_gcnnet_forward", _native.current_stream(dev_index), n, e, x.data_ptr(), src.data_ptr(), dst.data_ptr(),
-                     edge_attr.data_ptr(), _native.ptr(logits), _native.ptr(probs))
+            x, src, dst, edge_attr, _ = self._inputs(data, dev, with_node_ptr=False)
+            logits, probs = self._outputs(x.size(0), dev, want_logits, want_probs)
+            ctx.call("ggc_gcnnet_forward", _native.current_stream(dev_index), x.size(0), src.numel(), x.data_ptr(),
+                     src.data_ptr(), dst.data_ptr(), edge_attr.data_ptr(), _native.ptr(logits), _native.ptr(probs))
             return logits, probs
-
-        def forward(self, data) -> "torch.Tensor":
-            """logits (N, 3) on the model's device — reference model.py:292-304."""
-            with torch.no_grad():
-                return self._run(data, True, False)[0]
-
-        @torch.no_grad()
-        def predict_probs(self, data) -> np.ndarray:
-            self.eval()
-            return self._run(data, False, True)[1].float().cpu().numpy()
-
-        @torch.no_grad()
-        def predict_probs_device(self, data, ctx=None) -> "torch.Tensor":
-            if self.training:
-                self.eval()
-            return self._run(data, False, True, ctx)[1]
-
-        @torch.no_grad()
-        def predict_trimap(self, data, segments: np.ndarray, threshold_fg: float = 0.55, threshold_bg: float = 0.55) -> np.ndarray:
-            return _probs_to_trimap(self.predict_probs(data), segments, threshold_fg, threshold_bg)
-
-
-    def _node_ptr_of(data, n: int, dev) -> "torch.Tensor":
-        """int32 prefix sums of the graphs' node counts from data.node_ptr32 / data.batch (contiguous graphs, PyG Batch)."""
-        node_ptr = getattr(data, "node_ptr32", None)
-        if node_ptr is not None:
-            return node_ptr
-        batch = getattr(data, "batch", None)
-        if batch is None:
-            return torch.tensor([0, n], dtype=torch.int32, device=dev)
-        n_graphs = getattr(data, "num_graphs", None)
-        if n_graphs is None:
-            n_graphs = int(batch.max().item()) + 1                   # reference model.py:86
-        counts = torch.bincount(batch, minlength=n_graphs)
-        node_ptr = torch.zeros(n_graphs + 1, dtype=torch.int32, device=dev)
-        node_ptr[1:] = torch.cumsum(counts, 0).to(torch.int32)
-        return node_ptr
 
     class _GATv2Params(nn.Module):
         """Parameter holder with the state_dict keys of torch_geometric.nn.GATv2Conv(D, D // H, heads=H, concat=True,
@@ -492,7 +434,7 @@ if _TORCH:
             self.bias = nn.Parameter(torch.zeros(heads * c))
             nn.init.xavier_uniform_(self.att)                       # PyG's glorot
 
-    class GATTrimapNet(nn.Module):
+    class GATTrimapNet(_NativeNet):
         """
         GATv2 attention variant with edge features (reference model.py:323-414; SURVEY.md section 8(f), last rank).  Same
         `state_dict` keys as the reference module.  Inference only: the forward pass runs in libggc_hip.so
@@ -518,73 +460,27 @@ if _TORCH:
             self.ctx = _GlobalContext(hidden_channels)
             self.head = nn.Sequential(nn.Linear(hidden_channels, hidden_channels), nn.GELU(), nn.Dropout(dropout),
                                       nn.Linear(hidden_channels, n_classes))
-            self._uid = next(_model_uid)
 
-        def _device_index(self) -> int:
-            dev = self.head[0].weight.device
-            if dev.type != "cuda":
-                raise RuntimeError("GATTrimapNet runs on an MI355X through libggc_hip.so only; "
-                                   f"the model is on '{dev}'. Move it with .to('cuda') — there is no CPU fallback.")
-            return dev.index if dev.index is not None else torch.cuda.current_device()
-
-        def _sync_weights(self, ctx: "_native.Context") -> None:
-            sd = self.state_dict()
-            fp = (self._uid, tuple((k, v.data_ptr(), v._version) for k, v in sd.items()))
-            if ctx.resident.get("gat") == fp:
-                return
-            ctx.call("ggc_gat_configure", self.hidden_channels, self.n_heads, self.n_layers)
-            for k, v in sd.items():
-                if not v.dtype.is_floating_point:
-                    continue   # num_batches_tracked
-                a = v.detach().to(device="cpu", dtype=torch.float32).contiguous().numpy()
-                ctx.call("ggc_gat_load_weight", k.encode(), a.ctypes.data, a.size)
-            ctx.call("ggc_gat_ready")
-            ctx.resident["gat"] = fp
+        _KEY = "gat"
+        _TRAIN_ERROR = "GATTrimapNet on MI355X is inference-only: call .eval() first"
 
         def _run(self, data, want_logits: bool, want_probs: bool, ctx=None, check_loops: bool = True):
             if self.training:
-                raise RuntimeError("GATTrimapNet on MI355X is inference-only: call .eval() first")
+                raise RuntimeError(self._TRAIN_ERROR)
             # PyG's GATv2Conv(add_self_loops=True) REMOVES i -> i edges (and their attributes) before it adds its own
             # mean-filled loops; the kernels keep every input edge.  GraphBuilder never emits a loop, so the pipeline is
             # unaffected; a user-supplied edge_index that holds one is refused rather than answered differently.
             if check_loops and data.edge_index.numel() and bool((data.edge_index[0] == data.edge_index[1]).any()):
                 raise ValueError("GATTrimapNet: edge_index holds self-loops (i -> i); PyG's GATv2Conv drops them before adding "
                                  "its own, which this build does not do — remove them (edge_attr rows included) first")
-            dev_index = self._device_index()
-            if ctx is None:
-                ctx = _native.get_context(dev_index)
-            self._sync_weights(ctx)
+            ctx, dev_index = self._prepare(ctx, self.hidden_channels, self.n_heads, self.n_layers)
             dev = torch.device("cuda", dev_index)
-            x = data.x
-            if x.device != dev:
-                raise RuntimeError(f"data.x is on {x.device}, model on {dev}")
-            x = x.to(torch.float32).contiguous()
-            n = x.size(0)
-            if x.dim() != 2 or x.size(1) != N_NODE_FEATS:
-                raise ValueError(f"data.x must be (N, {N_NODE_FEATS}), got {tuple(x.shape)}")
-            ei = data.edge_index
-            e = ei.size(1)
-            edge_attr = getattr(data, "edge_attr", None)
-            if edge_attr is None:                      # reference model.py:383-384
-                edge_attr = torch.zeros(e, N_EDGE_FEATS, device=dev)
-            edge_attr = edge_attr.to(torch.float32).contiguous()
-            src, dst = ei[0].to(torch.int32).contiguous(), ei[1].to(torch.int32).contiguous()
-            node_ptr = _node_ptr_of(data, n, dev)
-            logits = torch.empty(n, 3, dtype=torch.float32, device=dev) if want_logits else None
-            probs = torch.empty(n, 3, dtype=torch.float32, device=dev) if want_probs else None
-            ctx.call("ggc_gat_forward", _native.current_stream(dev_index), node_ptr.numel() - 1, n, e, x.data_ptr(), src.data_ptr(),
-                     dst.data_ptr(), edge_attr.data_ptr(), node_ptr.data_ptr(), _native.ptr(logits), _native.ptr(probs))
+            x, src, dst, edge_attr, node_ptr = self._inputs(data, dev)
+            logits, probs = self._outputs(x.size(0), dev, want_logits, want_probs)
+            ctx.call("ggc_gat_forward", _native.current_stream(dev_index), node_ptr.numel() - 1, x.size(0), src.numel(),
+                     x.data_ptr(), src.data_ptr(), dst.data_ptr(), edge_attr.data_ptr(), node_ptr.data_ptr(),
+                     _native.ptr(logits), _native.ptr(probs))
             return logits, probs
-
-        def forward(self, data) -> "torch.Tensor":
-            """logits (N, 3) on the model's device — reference model.py:380-404."""
-            with torch.no_grad():
-                return self._run(data, True, False)[0]
-
-        @torch.no_grad()
-        def predict_probs(self, data) -> np.ndarray:
-            self.eval()
-            return self._run(data, False, True)[1].float().cpu().numpy()
 
         @torch.no_grad()
         def predict_probs_device(self, data, ctx=None) -> "torch.Tensor":
@@ -592,10 +488,6 @@ if _TORCH:
             if self.training:
                 self.eval()
             return self._run(data, False, True, ctx, check_loops=False)[1]
-
-        @torch.no_grad()
-        def predict_trimap(self, data, segments: np.ndarray, threshold_fg: float = 0.55, threshold_bg: float = 0.55) -> np.ndarray:
-            return _probs_to_trimap(self.predict_probs(data), segments, threshold_fg, threshold_bg)
 
     def build_model(
         variant: str = "resgcn",

@@ -100,3 +100,47 @@ def test_new_entries_fail_loudly_on_bad_arguments(gpu_ctx):
     out = torch.zeros(4, 3, device="cuda")
     with pytest.raises(_native.GGCError, match="missing weight"):
         gpu_ctx.call("ggc_gcnnet_forward", st, 4, 0, x.data_ptr(), None, None, None, out.data_ptr(), None)   # weights never loaded
+
+
+# network -> (configure arguments, a real key and its numel at that configuration, forward arguments after the stream)
+_WEIGHT_PATHS = {
+    "resgcn": ((32, 2), "head.bias", 3, lambda x, o, p: (1, 4, 0, x, None, None, None, p, o, None)),
+    "gcnnet": ((32, 2), "head.6.bias", 3, lambda x, o, p: (4, 0, x, None, None, None, o, None)),
+    "gat": ((32, 4, 2), "head.3.bias", 3, lambda x, o, p: (1, 4, 0, x, None, None, None, p, o, None)),
+}
+
+
+@pytest.mark.parametrize("net", sorted(_WEIGHT_PATHS))
+def test_weight_path_errors(net):
+    """The weight entries of every network report misuse the same way: loading before configure, an unknown key, a wrong
+    size and a forward with weights missing are errors with their own codes; num_batches_tracked is accepted and ignored."""
+    from gcn_grabcut import _native
+    conf, key, numel, fwd_args = _WEIGHT_PATHS[net]
+    ctx = _native.Context(0)               # fresh: never configured by an earlier test
+    try:
+        st = _native.current_stream(0)
+        w = np.zeros(numel + 1, np.float32)
+        load = lambda k, n: ctx.call(f"ggc_{net}_load_weight", k.encode(), w.ctypes.data, n)
+        with pytest.raises(_native.GGCError, match="GGC_E_STATE") as e:
+            load(key, numel)
+        assert e.value.code == -6
+        ctx.call(f"ggc_{net}_configure", *conf)
+        with pytest.raises(_native.GGCError, match="GGC_E_INVALID_ARG: unexpected state_dict key 'no.such.weight'") as e:
+            load("no.such.weight", numel)
+        assert e.value.code == -1
+        with pytest.raises(_native.GGCError, match=f"GGC_E_SHAPE: weight '{key}' has {numel + 1} elements") as e:
+            load(key, numel + 1)
+        assert e.value.code == -2
+        load(key, numel)
+        load("in_norm.norm.num_batches_tracked", 1)
+        x = torch.zeros(4, 19, device="cuda")
+        out = torch.zeros(4, 3, device="cuda")
+        node_ptr = torch.tensor([0, 4], dtype=torch.int32, device="cuda")
+        with pytest.raises(_native.GGCError, match="missing weight") as e:
+            ctx.call(f"ggc_{net}_forward", st, *fwd_args(x.data_ptr(), out.data_ptr(), node_ptr.data_ptr()))
+        assert e.value.code == -6
+        with pytest.raises(_native.GGCError, match="missing weight"):
+            ctx.call(f"ggc_{net}_ready")
+    finally:
+        torch.cuda.synchronize()
+        ctx.close()
