@@ -2,7 +2,6 @@
 CPU torch restatement built from tests/torch_ref.py, on graphs with isolated nodes, a hub of 510 in-edges, duplicate
 edges, explicit i->i edges, directed edges, a one-node graph and an edgeless graph, at every training width.
 Tolerance: max |err| <= 1e-5 (1 + |ref|) elementwise.  Two runs must give identical bits."""
-import contextlib
 
 import numpy as np
 import pytest
@@ -10,19 +9,9 @@ import torch
 import torch.nn.functional as F
 
 import torch_ref
+from helpers import float64_default
 
 pytestmark = pytest.mark.gpu
-
-
-@contextlib.contextmanager
-def float64_default():
-    """torch_ref's helpers allocate some buffers with the default dtype; the restatement here runs in float64"""
-    old = torch.get_default_dtype()
-    torch.set_default_dtype(torch.float64)
-    try:
-        yield
-    finally:
-        torch.set_default_dtype(old)
 
 
 def _batch_graph(seed=0):

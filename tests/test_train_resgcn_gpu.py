@@ -1,7 +1,6 @@
 """GPU: ResGCNNet's differentiable training forward (train mode) — autograd, agreement with the eval-mode
 ggc_resgcn_forward, TrimapLoss gradients of every parameter against a float64 CPU differentiable restatement,
 BatchNorm running statistics, bit-identical repeated backward passes, weight re-upload after an optimizer step."""
-import contextlib
 import copy
 
 import numpy as np
@@ -10,29 +9,22 @@ import torch
 import torch.nn.functional as F
 
 import torch_ref
-from helpers import seeded_state_dict, superpixel_like_graph
+from helpers import float64_default, hub_graph, seeded_state_dict, superpixel_like_graph
 
 pytestmark = pytest.mark.gpu
 
 
-@contextlib.contextmanager
-def float64_default():
-    """torch_ref's helpers allocate some buffers with the default dtype; the restatement here runs in float64"""
-    old = torch.get_default_dtype()
-    torch.set_default_dtype(torch.float64)
-    try:
-        yield
-    finally:
-        torch.set_default_dtype(old)
-
-
-def _batch(sizes=(120, 1, 7, 200), seed=0, edgeless=(2,)):
-    """Batch of superpixel-like graphs with training targets; graph indices in `edgeless` get no edges."""
+def _batch(sizes=(120, 1, 7, 200), seed=0, edgeless=(2,), hub=False):
+    """Batch of superpixel-like graphs with training targets; graph indices in `edgeless` get no edges.  With `hub`, the
+    first graph is helpers.hub_graph() instead: 600 nodes, four of them with an in-degree above 500."""
     from gcn_grabcut.data import Batch, Data
     graphs = []
     g = torch.Generator().manual_seed(seed)
     for i, n in enumerate(sizes):
-        if n >= 4 and i not in edgeless:
+        if hub and i == 0:
+            x, ei, ea = (torch.as_tensor(a) for a in hub_graph())
+            n = x.size(0)
+        elif n >= 4 and i not in edgeless:
             x, ei, ea = superpixel_like_graph(n=n, seed=seed + i)
             x, ei, ea = torch.as_tensor(x), torch.as_tensor(ei), torch.as_tensor(ea)
         else:
@@ -99,11 +91,11 @@ def test_train_path_agrees_with_eval_path(gpu_ctx):
     assert (got.detach() - want).abs().max().item() <= 1e-4
 
 
-@pytest.mark.parametrize("hidden,layers", [(64, 3), (96, 2)])
+@pytest.mark.parametrize("hidden,layers", [(64, 3), (96, 2), (128, 3)])
 def test_parameter_gradients_match_float64_reference(gpu_ctx, hidden, layers):
     m = _model(hidden, layers, seed=hidden).cuda().train()
     ref = copy.deepcopy(m).cpu().double().train()
-    b = _batch(seed=hidden)
+    b = _batch(seed=hidden, hub=hidden == 128)          # at 128 beside a one-node and an edgeless graph: the hub graph
     logits = m(b.to("cuda"))
     _loss(logits, b.to("cuda")).backward()
     ref_logits = _ref_forward(ref, b)
