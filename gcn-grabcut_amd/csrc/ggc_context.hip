@@ -15,7 +15,6 @@ const Knobs& knobs() {
         Knobs k;
         k.mf_trace = std::getenv("GGC_MF_TRACE") != nullptr;
         k.mf_warm = num("GGC_MF_WARM", 1, 0);
-        k.mf_async = num("GGC_MF_ASYNC", 1, 0);
         k.mf_async_push_active = num("GGC_MF_ASYNC_PUSH_ACTIVE", 10000, 0);
         k.mf_async_tile = num("GGC_MF_ASYNC_TILE", 8, 8);
         k.mf_async_hops = num("GGC_MF_ASYNC_HOPS", 24, 1);

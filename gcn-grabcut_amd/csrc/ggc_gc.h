@@ -24,14 +24,21 @@ __device__ __forceinline__ int dir_nb(const GcDims& d, int y, int x, int dir) {
 // relabel visit.
 __host__ __device__ __forceinline__ size_t rc_idx(int dir, size_t i) { return i * 8 + (size_t)dir; }
 
+// The max-flow's words in ggc_grabcut's control block, which the start of every call zeroes.
+struct MfControl {
+    int32_t* active;   // [B] active pixels per image (excess that can still reach the sink)
+    int32_t* cnt;      // [8] open images | relabel list counters [3] | push list counters [3] | active pixels in total
+    int32_t* lists;    // [2B] open-image lists, current and next round
+    int32_t* err;      // receives a non-zero code if an asynchronous launch gives up
+};
+
 // Maximum preflow + canonical labels for every image with state[b] == 0.
 //   rc   [B][P][8] residual capacities (in/out), rc_idx(dir, pixel)     ex, snk [B][P] excess / residual sink capacity (in/out)
 //   dist [B][P] out: distance to the sink in the final residual graph, >= DINF when unreachable (=> foreground)
 //   rmask [B][P] arc masks of rc (bit dir = residual arc towards dir); masks_exact: every byte is current (cold start) —
-//   otherwise the tiles marked dirty by the previous solve keep their mark.  lists [2B], flags [2B+16] scratch;
-//   err_flag: device word that receives a non-zero code if an asynchronous launch gives up.
+//   otherwise the tiles marked dirty by the previous solve of this call keep their mark.
 int maxflow(ggc_ctx* ctx, hipStream_t st, const GcDims& d, const int32_t* state, int32_t* rc, int32_t* ex,
-            int32_t* snk, int32_t* dist, uint8_t* rmask, int32_t* lists, int32_t* flags, int32_t* err_flag, bool masks_exact);
+            int32_t* snk, int32_t* dist, uint8_t* rmask, const MfControl& ctl, bool masks_exact);
 
 // Tile geometry of the max-flow kernels (ggc_maxflow.hip: launches over work lists; ggc_maxflow_async.hip: one launch per sparse phase)
 constexpr int MF_RT = 32;                          // relabel tile side

@@ -520,7 +520,7 @@ __global__ void __launch_bounds__(256) k_build_graph(GcDims d, const uint8_t* __
     // own planes give the arcs towards left / up-left / up / up-right; the mirrored arcs read the neighbour's plane
     const int dirs[4] = {0, 4, 2, 6};
     int32_t inflow = 0;
-    int arcs = 0;                                        // bit dir = residual arc towards dir (ggc_maxflow_image.hip keeps it current)
+    int arcs = 0;                                        // bit dir = residual arc towards dir (the push visits of ggc_maxflow*.hip keep it current)
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
         const int dir = dirs[k];
@@ -579,7 +579,13 @@ extern "C" int ggc_grabcut(ggc_ctx* ctx, ggc_stream stream, int B, int H, int W,
     GcDims d{B, H, W, H * W, cdiv((size_t)H * W, CHUNK)};
     const size_t BP = (size_t)B * d.P;
 
-    int32_t* small = scratch_t<int32_t>(ctx, S_GC_A, (size_t)B * 8 + 32);   // f1 | f2 | state | - | max-flow flags [B+8] | err | open lists [2B]
+    // the control block, zeroed at the start of every call
+    int32_t *f1, *f2, *state, *err;     // [B] mask flags before / after promotion, [B] 1 = image skipped, [2] error words
+    MfControl mf;                       // the max-flow's counters and lists; its error word is err[1]
+    const size_t ctl_bytes = carve_scratch(ctx, S_GC_A, [&](Carve& c) {
+        f1 = c.take<int32_t>(B); f2 = c.take<int32_t>(B); state = c.take<int32_t>(B); err = c.take<int32_t>(2);
+        mf = {c.take<int32_t>(B), c.take<int32_t>(8), c.take<int32_t>(2 * (size_t)B), err ? err + 1 : nullptr};
+    });
     Gmm* gmm = scratch_t<Gmm>(ctx, S_GC_B, (size_t)B * 2);
     unsigned long long* acc = scratch_t<unsigned long long>(ctx, S_GC_C, (size_t)B * 2 * NCOMP * ACC_W + B);
     uint8_t* comp = scratch_t<uint8_t>(ctx, S_GC_D, BP);
@@ -587,13 +593,11 @@ extern "C" int ggc_grabcut(ggc_ctx* ctx, ggc_stream stream, int B, int H, int W,
     int32_t* rc = scratch_t<int32_t>(ctx, S_GC_F, BP * 8);
     int32_t* ex = scratch_t<int32_t>(ctx, S_GC_G, BP * 3);
     uint8_t* rmask = scratch_t<uint8_t>(ctx, S_GC_L, BP);
-    if (!small || !gmm || !acc || !comp || !nw || !rc || !ex || !rmask) return GGC_E_OOM;
+    if (!ctl_bytes || !gmm || !acc || !comp || !nw || !rc || !ex || !rmask) return GGC_E_OOM;
     int32_t* snk = ex + BP;
     int32_t* dist = ex + 2 * BP;
-    int32_t *f1 = small, *f2 = small + B, *state = small + 2 * B, *mf_flags = small + 4 * B;
-    int32_t* err = small + 6 * B + 8;
     unsigned long long* bsum = acc + (size_t)B * 2 * NCOMP * ACC_W;
-    GGC_HIP(ctx, hipMemsetAsync(small, 0, sizeof(int32_t) * ((size_t)B * 8 + 32), st));
+    GGC_HIP(ctx, hipMemsetAsync(f1, 0, ctl_bytes, st));                  // (f1 starts the control block)
     GGC_HIP(ctx, hipMemsetAsync(acc, 0, sizeof(unsigned long long) * ((size_t)B * 2 * NCOMP * ACC_W + B), st));
 
     if (mode == 1) {
@@ -645,9 +649,8 @@ extern "C" int ggc_grabcut(ggc_ctx* ctx, ggc_stream stream, int B, int H, int W,
                 hipLaunchKernelGGL(k_build_graph, dim3(cdiv(d.P, 256), B), dim3(256), 0, st, d, image, mask, state, gmm, nw, rc, ex, snk, rmask, warm ? 1 : 0);
             }
             GGC_LAUNCH_CHECK(ctx);
-            // who drives the rounds of the max-flow was measured in round 2 ("max-flow drivers"): launches over
-            // work lists for the dense phases, one asynchronous launch for each sparse phase (ggc_maxflow_async.hip)
-            const int rcode = maxflow(ctx, st, d, state, rc, ex, snk, dist, rmask, small + 6 * B + 16, mf_flags, err + 1, !warm);
+            // launches over work lists for the dense phases, one asynchronous launch for each sparse phase
+            const int rcode = maxflow(ctx, st, d, state, rc, ex, snk, dist, rmask, mf, !warm);
             if (rcode) return rcode;
             hipLaunchKernelGGL(k_gc_relabel, dim3(cdiv(BP, 256)), dim3(256), 0, st, d, state, dist, mask);
             GGC_LAUNCH_CHECK(ctx);

@@ -26,7 +26,7 @@ enum Slot : int {
     S_G_EDGE_ATTR, S_G_PTR, S_G_PRIOR, S_G_AUX, S_G_AUX2, S_G_AUX3, S_G_X,
     S_T_A, S_T_B, S_T_C,
     S_GC_A, S_GC_B, S_GC_C, S_GC_D, S_GC_E, S_GC_F, S_GC_G, S_GC_H, S_GC_I, S_GC_J,
-    S_GC_K, S_GC_L, S_GC_M, S_GC_N, S_GC_O,
+    S_GC_K, S_GC_L, S_GC_M,
     S_CC_A, S_CC_B, S_CC_C,
     S_MISC_A, S_MISC_B,
     S_COUNT
@@ -91,7 +91,6 @@ namespace ggc {
 struct Knobs {
     int mf_trace;               // GGC_MF_TRACE: per-round max-flow diagnostics on stderr (blocking; tools/mf_trace.py)
     int mf_warm;                // GGC_MF_WARM (1): keep the n-link flow across GrabCut iterations
-    int mf_async;               // GGC_MF_ASYNC (1): sparse max-flow phases as one asynchronous launch each; 0 = host-driven work lists only
     int mf_async_push_active;   // GGC_MF_ASYNC_PUSH_ACTIVE (10000): push rounds with at most this many active pixels run asynchronously
     int mf_async_tile;          // GGC_MF_ASYNC_TILE (8): rows of the asynchronous push tile, 8 | 16 | 32
     int mf_async_hops;          // GGC_MF_ASYNC_HOPS (24): longest chain of tile visits in an asynchronous push launch
@@ -139,6 +138,29 @@ int build_csr(ggc_ctx* ctx, hipStream_t st, int N, int E, const int32_t* src, co
 template <typename T>
 inline T* scratch_t(ggc_ctx* ctx, int slot, size_t count) {
     return reinterpret_cast<T*>(scratch(ctx, slot, count * sizeof(T)));
+}
+
+// Several typed arrays in one scratch slot, each on a 256-byte boundary.  A layout is one function of a Carve that takes
+// its arrays in order; carve_scratch runs it twice, once to size the slot and once to fill in the pointers, so the size
+// and the offsets cannot disagree.  Returns the slot's size in bytes, 0 when the allocation failed.
+struct Carve {
+    char* base = nullptr;
+    size_t bytes = 0;
+    template <typename T> T* take(size_t count) {
+        T* p = base ? reinterpret_cast<T*>(base + bytes) : nullptr;
+        bytes += (count * sizeof(T) + 255) & ~size_t(255);
+        return p;
+    }
+};
+template <typename Layout>
+inline size_t carve_scratch(ggc_ctx* ctx, int slot, Layout&& layout) {
+    Carve c;
+    layout(c);
+    c.base = static_cast<char*>(scratch(ctx, slot, c.bytes));
+    if (!c.base) return 0;
+    c.bytes = 0;
+    layout(c);
+    return c.bytes;
 }
 
 inline int cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }

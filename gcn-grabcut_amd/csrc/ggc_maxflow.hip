@@ -39,14 +39,6 @@ constexpr int PT_N = PT_W * PT_H;      // threads of a push block, one pixel eac
 // blocks per work-list launch and 64 open images: a block walks several tiles of the list (measured best, tools/mf_knobs.sh)
 constexpr int PUSH_GRID = 1024, RELAX_GRID = 1024, ASYNC_GRID = 128;
 
-__device__ __forceinline__ int ld(const int32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-// append `tile` to the next work list unless it is already on it
-__device__ __forceinline__ void push_tile(int tile, int32_t* __restrict__ flag, int32_t* __restrict__ list,
-                                          int32_t* __restrict__ count) {
-    if (ld(&flag[tile]) == 0 && atomicExch(&flag[tile], 1) == 0) list[atomicAdd(count, 1)] = tile;   // cheap test first
-}
-
 // up to three int32 regions zeroed by ONE launch (a round used to issue seven hipMemsetAsync calls: each is a launch of its own)
 __global__ void __launch_bounds__(256) k_mf_zero3(int32_t* __restrict__ a, size_t na, int32_t* __restrict__ b, size_t nb, int32_t* __restrict__ c, size_t nc) {
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
@@ -67,7 +59,7 @@ constexpr int OUT_CAP = 1024;
 struct OutList { int n, base; int buf[OUT_CAP]; };
 __device__ __forceinline__ void push_tile_l(int tile, int32_t* __restrict__ flag, OutList& L, int32_t* __restrict__ list,
                                             int32_t* __restrict__ count) {
-    if (ld(&flag[tile]) == 0 && atomicExch(&flag[tile], 1) == 0) {
+    if (ldg(&flag[tile]) == 0 && atomicExch(&flag[tile], 1) == 0) {
         const int i = atomicAdd(&L.n, 1);
         if (i < OUT_CAP) L.buf[i] = tile;
         else list[atomicAdd(count, 1)] = tile;                             // (a block that overflows its list appends directly)
@@ -133,134 +125,59 @@ __global__ void __launch_bounds__(256) k_mf_rinit(GcDims d, MfTiles tl, const in
     flush_tiles(outl, list, count);
 }
 
-// Global relabel over a work list of 32x32 tiles, a WAVE per tile (4 tiles per block, no block barrier): the labels are relaxed by alternating
-// vertical and horizontal in-register sweeps (ggc_mf_sweep.h), which carry a front across the tile in a handful of
-// sweeps where the neighbour-at-a-time iteration above needs one per pixel of the way.  32x32 tiles only.
-struct RelaxWaveLds { int d[MF_RT + 2][MF_RT + 2]; uint32_t m[MF_RT][MF_RT / 4]; };
+// Global relabel over a work list of 32x32 tiles, a WAVE per tile (4 tiles per block, no block barrier): the labels are relaxed
+// by alternating vertical and horizontal in-register sweeps (mf_relax_visit, ggc_mf_sweep.h), which carry a front across the
+// tile in a handful of sweeps where a neighbour-at-a-time iteration needs one per pixel of the way.
 template <bool PROF>
 __global__ void __launch_bounds__(256) k_mf_relax_wave(GcDims d, MfTiles tl, int phase, long long* __restrict__ prof, uint8_t* __restrict__ rmask,
                                                        int32_t* __restrict__ dirty, const int32_t* __restrict__ rc, int32_t* __restrict__ dist, int32_t* __restrict__ counters,
                                                        const int32_t* __restrict__ list_in, int32_t* __restrict__ list_out,
                                                        int32_t* __restrict__ flag_in, int32_t* __restrict__ flag_out) {
-    constexpr int T = MF_RT, N_HALO = (T + 2) * (T + 2), HALO_IT = (N_HALO + 63) / 64;
     __shared__ RelaxWaveLds lds[4];
     __shared__ OutList outl;
     if (threadIdx.x == 0) outl.n = 0;
     __syncthreads();
     const int wv = threadIdx.x >> 6;
-    RelaxWaveLds& S = lds[wv];
     const int n_in = counters[phase % 3];
     int32_t* n_out = counters + (phase + 1) % 3;
     if (blockIdx.x == 0 && threadIdx.x == 0) counters[(phase + 2) % 3] = 0;       // the list after next starts empty
     const int tiles_per_image = tl.rt_x * tl.rt_y;
     const int G = gridDim.x * 4;
-    int* sd = &S.d[0][0];
-    uint8_t* sm = reinterpret_cast<uint8_t*>(&S.m[0][0]);
-    long long pa = 0, pb = 0, pc = 0, pn = 0, psw = 0;
+    MfRelaxClocks<PROF> ck;
     // the list entry of the NEXT visit is requested one visit ahead: read at the top of its own visit it is a memory round
     // trip in front of the tile's 50 loads (measured: load + fill 12 us of a 22 us visit)
     int tile_nx = blockIdx.x * 4 + wv < n_in ? list_in[blockIdx.x * 4 + wv] : 0;
     for (int t = blockIdx.x * 4 + wv; t < n_in; t += G) {
         int lane = threadIdx.x & 63;
         asm volatile("" : "+v"(lane));                                     // keeps the lane arithmetic inside the loop (no hoist + spill)
-        const long long t_a = PROF ? wall_clock64() : 0;
+        ck.begin();
         const int tile = __builtin_amdgcn_readfirstlane(tile_nx);
         tile_nx = t + G < n_in ? list_in[t + G] : 0;
+        const int nbm = mf_relax_visit<false, PROF>(d, tl, tile, lane, lds[wv], rmask, dirty, rc, dist, flag_in, ck);
         const int b = tile / tiles_per_image, tr = tile % tiles_per_image;
         const int tyi = tr / tl.rt_x, txi = tr % tl.rt_x;
-        const int tx0 = txi * T, ty0 = tyi * T;
-        const size_t base = (size_t)b * d.P, BP = (size_t)d.B * d.P;
-        const int lx = lane & 31, h = lane >> 5;
-        int hv[HALO_IT];
-#pragma unroll
-        for (int k = 0; k < HALO_IT; ++k) {                                // unconditional loads from clamped addresses
-            const int i = min(lane + k * 64, N_HALO - 1);
-            const int gy = ty0 + i / (T + 2) - 1, gx = tx0 + i % (T + 2) - 1;
-            hv[k] = dist[base + (size_t)min(max(gy, 0), d.H - 1) * d.W + min(max(gx, 0), d.W - 1)];
-        }
-        uint32_t mv[16];
-#pragma unroll
-        for (int r = 0; r < 16; ++r)
-            mv[r] = rmask[base + (size_t)min(ty0 + 16 * h + r, d.H - 1) * d.W + min(tx0 + lx, d.W - 1)];
-        const bool dirty_t = mf_tile_dirty(dirty, tl, b, tyi, txi, lane);  // wave-uniform: a neighbour pushed into one of its push tiles
-        MfBorderArcs ba;
-        if (dirty_t) ba.load(d, rc, BP, base, ty0, tx0, lx, h);
-        if (lane == 0) flag_in[tile] = 0;                                  // consumed
-        uint32_t inv_v[4] = {0u, 0u, 0u, 0u}, inv_h[4];                    // bit set = no arc; outside the image: all blocked
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            uint32_t m = ~mv[r] & 0xffu;
-            if (dirty_t) m = ba.row(m, r);
-            sm[(16 * h + r) * T + lx] = (uint8_t)((tx0 + lx < d.W && ty0 + 16 * h + r < d.H) ? m : 0xffu);
-        }
-#pragma unroll
-        for (int k = 0; k < HALO_IT; ++k) {
-            const int i = lane + k * 64;
-            const int gy = ty0 + i / (T + 2) - 1, gx = tx0 + i % (T + 2) - 1;
-            if (i < N_HALO) sd[i] = (gx >= 0 && gx < d.W && gy >= 0 && gy < d.H) ? hv[k] : DINF;
-        }
-        mf_wave_sync();
-        if (dirty_t) {
-            if (ty0 + lx < d.H && tx0 + (h ? 31 : 0) < d.W) sm[lx * T + (h ? 31 : 0)] = (uint8_t)ba.col(sm[lx * T + (h ? 31 : 0)], h);
-            mf_wave_sync();
-            mf_tile_repair(d, tl, rmask, dirty, S, base, b, tyi, txi, ty0, tx0, lx, h, lane);
-        }
-#pragma unroll
-        for (int r = 0; r < 16; ++r) inv_v[r >> 2] |= (uint32_t)sm[(16 * h + r) * T + lx] << (8 * (r & 3));
-#pragma unroll
-        for (int k = 0; k < 4; ++k) inv_h[k] = S.m[lx][4 * h + k];         // H sweep: row lx, columns 16h .. 16h+15
-        int old[16];
-#pragma unroll
-        for (int r = 0; r < 16; ++r) old[r] = S.d[16 * h + r + 1][lx + 1];
-        bool settled = false;
-        const long long t_b = PROF ? wall_clock64() : 0;
-        int n_sw = 0;
-        for (int it = 0; it < 4 * T; ++it) {                               // a sweep pair that changes nothing: fixpoint
-            const int ch = (it & 1) ? relax_sweep_h(S, inv_h, lx, h) : relax_sweep_v(S, inv_v, lx, h);
-            mf_wave_sync();
-            if (PROF) ++n_sw;
-            if (!__any(ch)) { settled = true; break; }
-        }
-        const long long t_c = PROF ? wall_clock64() : 0;
-        int nbm = settled ? 0 : 1 << 4;                                    // bit (dy + 1) * 3 + (dx + 1)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int ly = 16 * h + r;
-            const int v = S.d[ly + 1][lx + 1];
-            if (v != old[r]) {
-                dist[base + (size_t)(ty0 + ly) * d.W + tx0 + lx] = v;
-                const int Lf = lx == 0, Rt = lx == T - 1, U = ly == 0, D = ly == T - 1;
-                nbm |= (U & Lf) | U << 1 | (U & Rt) << 2 | Lf << 3 | Rt << 5 | (D & Lf) << 6 | D << 7 | (D & Rt) << 8;
-            }
-        }
-        nbm = mf_wave_or(nbm);
         if (lane < 9 && (nbm >> lane) & 1) {
             const int ty = tyi + lane / 3 - 1, tx = txi + lane % 3 - 1;
             if (ty >= 0 && ty < tl.rt_y && tx >= 0 && tx < tl.rt_x)
                 push_tile_l(b * tiles_per_image + ty * tl.rt_x + tx, flag_out, outl, list_out, n_out);
         }
         mf_wave_sync();
-        if (PROF) { pa += t_b - t_a; pb += t_c - t_b; pc += wall_clock64() - t_c; pn += 1; psw += n_sw; }
+        ck.end();
     }
-    if (PROF && (threadIdx.x & 63) == 0 && pn) {                           // GGC_MF_TRACE: visit-phase clocks, one set of atomics per wave
+    if (PROF && (threadIdx.x & 63) == 0 && ck.sum[3]) {                     // GGC_MF_TRACE: one set of atomics per wave
         unsigned long long* q = reinterpret_cast<unsigned long long*>(prof) + (64 + (blockIdx.x & 63)) * 8;
-        atomicAdd(&q[0], (unsigned long long)pa); atomicAdd(&q[1], (unsigned long long)pb); atomicAdd(&q[2], (unsigned long long)pc);
-        atomicAdd(&q[3], (unsigned long long)pn); atomicAdd(&q[4], (unsigned long long)psw);
+        for (int k = 0; k < 5; ++k) atomicAdd(&q[k], (unsigned long long)ck.sum[k]);
     }
     flush_tiles(outl, list_out, n_out);
 }
 
-// Push-relabel sweeps over a work list of 32x8 tiles.  PPT pixels per thread: a dense launch is bound by tile visits in
-// flight per CU (visit latency ~9 us x the blocks a CU holds), and a CU holds 32 waves whatever the block size, so
-// PPT = 2 (two waves per tile) doubles the tiles in flight.
-template <int PPT>
-__global__ void __launch_bounds__(PT_N / PPT) k_mf_pr_list(GcDims d, MfTiles tl, int phase, int inner,
-                                                          int32_t* __restrict__ rc, int32_t* __restrict__ ex,
-                                                          int32_t* __restrict__ snk, int32_t* __restrict__ dist, uint8_t* __restrict__ rmask,
-                                                          int32_t* __restrict__ dirty, int32_t* __restrict__ counters, const int32_t* __restrict__ list_in,
-                                                          int32_t* __restrict__ list_out, int32_t* __restrict__ flag_in,
-                                                          int32_t* __restrict__ flag_out) {
-    constexpr int NT = PT_N / PPT;                                         // threads; pixel slot of (thread, j) = tid + j * NT
+// Push-relabel sweeps over a work list of 32x8 tiles, one pixel per thread.
+__global__ void __launch_bounds__(PT_N) k_mf_pr_list(GcDims d, MfTiles tl, int phase, int inner,
+                                                    int32_t* __restrict__ rc, int32_t* __restrict__ ex,
+                                                    int32_t* __restrict__ snk, int32_t* __restrict__ dist, uint8_t* __restrict__ rmask,
+                                                    int32_t* __restrict__ dirty, int32_t* __restrict__ counters, const int32_t* __restrict__ list_in,
+                                                    int32_t* __restrict__ list_out, int32_t* __restrict__ flag_in,
+                                                    int32_t* __restrict__ flag_out) {
     __shared__ int s_ex[PT_N];
     __shared__ int s_d[PT_H + 2][PT_W + 2];
     __shared__ int s_rc[8][PT_N];
@@ -276,26 +193,23 @@ __global__ void __launch_bounds__(PT_N / PPT) k_mf_pr_list(GcDims d, MfTiles tl,
     // The visit latency bounds the dense launches, so the next tile of this block is loaded into registers while the
     // current one is swept (its list entry one step earlier still).  Safe for the same reason concurrent tiles are:
     // ring pixels are written back as atomic deltas, interior pixels have no other writer during a launch.
-    constexpr int N_HALO = (PT_H + 2) * (PT_W + 2), HALO_IT = (N_HALO + NT - 1) / NT;
-    struct TileRegs { int e[PPT], sk[PPT], r[PPT][8], hv[HALO_IT]; };
+    constexpr int N_HALO = (PT_H + 2) * (PT_W + 2), HALO_IT = (N_HALO + PT_N - 1) / PT_N;
+    struct TileRegs { int e, sk, r[8], hv[HALO_IT]; };
     auto load_tile = [&](int tile, TileRegs& R) {
         const int b = tile / tiles_per_image, tr = tile % tiles_per_image;
         const int tyi = tr / tl.pt_x, txi = tr % tl.pt_x;
         const int x = txi * PT_W + lx;
         const size_t base = (size_t)b * d.P;
+        const int y = tyi * PT_H + (tid >> 5);
+        const bool in = x < d.W && y < d.H;
+        const int p = y * d.W + x;
+        R.e = in ? ex[base + p] : 0;
+        R.sk = in ? snk[base + p] : 0;
 #pragma unroll
-        for (int j = 0; j < PPT; ++j) {
-            const int y = tyi * PT_H + ((tid + j * NT) >> 5);
-            const bool in = x < d.W && y < d.H;
-            const int p = y * d.W + x;
-            R.e[j] = in ? ex[base + p] : 0;
-            R.sk[j] = in ? snk[base + p] : 0;
-#pragma unroll
-            for (int dir = 0; dir < 8; ++dir) R.r[j][dir] = in ? rc[rc_idx(dir, base + p)] : 0;
-        }
+        for (int dir = 0; dir < 8; ++dir) R.r[dir] = in ? rc[rc_idx(dir, base + p)] : 0;
 #pragma unroll
         for (int k = 0; k < HALO_IT; ++k) {
-            const int i = tid + k * NT;
+            const int i = tid + k * PT_N;
             const int gy = tyi * PT_H + i / (PT_W + 2) - 1, gx = txi * PT_W + i % (PT_W + 2) - 1;
             R.hv[k] = (i < N_HALO && gx >= 0 && gx < d.W && gy >= 0 && gy < d.H) ? dist[base + (size_t)gy * d.W + gx] : DINF;
         }
@@ -314,21 +228,17 @@ __global__ void __launch_bounds__(PT_N / PPT) k_mf_pr_list(GcDims d, MfTiles tl,
         const int x = txi * PT_W + lx;
         const size_t base = (size_t)b * d.P;
         __syncthreads();
-        int e0[PPT], sk0[PPT], sk[PPT], d0[PPT], r0[PPT][8], pp[PPT];
-        bool inb[PPT];
+        const int y = tyi * PT_H + (tid >> 5);
+        const bool inb = x < d.W && y < d.H;
+        const int pp = y * d.W + x;
+        const int e0 = N.e, sk0 = N.sk;
+        int sk = sk0, r0[8];
+        s_ex[tid] = e0;
 #pragma unroll
-        for (int j = 0; j < PPT; ++j) {
-            const int slot = tid + j * NT, y = tyi * PT_H + (slot >> 5);
-            inb[j] = x < d.W && y < d.H;
-            pp[j] = y * d.W + x;
-            e0[j] = N.e[j]; sk0[j] = N.sk[j]; sk[j] = sk0[j];
-            s_ex[slot] = e0[j];
-#pragma unroll
-            for (int dir = 0; dir < 8; ++dir) { r0[j][dir] = N.r[j][dir]; s_rc[dir][slot] = r0[j][dir]; }
-        }
+        for (int dir = 0; dir < 8; ++dir) { r0[dir] = N.r[dir]; s_rc[dir][tid] = r0[dir]; }
 #pragma unroll
         for (int k = 0; k < HALO_IT; ++k) {
-            const int i = tid + k * NT;
+            const int i = tid + k * PT_N;
             if (i < N_HALO) s_d[i / (PT_W + 2)][i % (PT_W + 2)] = N.hv[k];
         }
         if (t + G < n_in) {                                                // block-uniform
@@ -338,15 +248,12 @@ __global__ void __launch_bounds__(PT_N / PPT) k_mf_pr_list(GcDims d, MfTiles tl,
         }
         __syncthreads();
         if (tid == 0) { flag_in[tile] = 0; s_nbm = 0; }                                   // consumed
-#pragma unroll
-        for (int j = 0; j < PPT; ++j) d0[j] = s_d[((tid + j * NT) >> 5) + 1][lx + 1];
+        const int d0 = s_d[(tid >> 5) + 1][lx + 1];
         int nbm = 0;
         for (int it = 0; it < inner; ++it) {
             int act = 0;
-#pragma unroll
-            for (int j = 0; j < PPT; ++j) {
-                if (!inb[j]) continue;
-                const int slot = tid + j * NT, ly = slot >> 5;
+            if (inb) {
+                const int slot = tid, ly = slot >> 5;
                 const int e = __hip_atomic_load(&s_ex[slot], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
                 const int dp = s_d[ly + 1][lx + 1];
                 if (e > 0 && dp < d.P) {
@@ -359,7 +266,7 @@ __global__ void __launch_bounds__(PT_N / PPT) k_mf_pr_list(GcDims d, MfTiles tl,
                         r[dir] = __hip_atomic_load(&s_rc[dir][slot], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
                         hq[dir] = s_d[ly + 1 + dir_dy(dir)][lx + 1 + dir_dx(dir)];
                     }
-                    int hmin = sk[j] > 0 ? 0 : DINF, best = sk[j] > 0 ? 8 : -1, rb = 0;
+                    int hmin = sk > 0 ? 0 : DINF, best = sk > 0 ? 8 : -1, rb = 0;
 #pragma unroll
                     for (int dir = 0; dir < 8; ++dir) {
                         const bool ok = r[dir] > 0 && hq[dir] < hmin;
@@ -367,8 +274,8 @@ __global__ void __launch_bounds__(PT_N / PPT) k_mf_pr_list(GcDims d, MfTiles tl,
                     }
                     if (best >= 0 && dp > hmin) {
                         if (best == 8) {
-                            const int dl = min(e, sk[j]);
-                            sk[j] -= dl;
+                            const int dl = min(e, sk);
+                            sk -= dl;
                             atomicSub(&s_ex[slot], dl);
                         } else {
                             const int dl = min(e, rb);
@@ -381,11 +288,10 @@ __global__ void __launch_bounds__(PT_N / PPT) k_mf_pr_list(GcDims d, MfTiles tl,
                                 atomicAdd(&s_rc[best ^ 1][qt], dl);
                                 atomicAdd(&s_ex[qt], dl);
                             } else {                                        // across the tile edge: straight to global memory
-                                const int q = pp[j] + by * d.W + bx;
-                                const int y = tyi * PT_H + ly;
+                                const int q = pp + by * d.W + bx;
                                 atomicAdd(&rc[rc_idx((best ^ 1), base + q)], dl);
                                 atomicAdd(&ex[base + q], dl);
-                                // (the neighbour tile is told after the sweeps, see k_mf_pr_wave)
+                                // (the neighbour tile is told after the sweeps)
                                 const int tdy = qly < 0 ? -1 : (qly >= PT_H ? 1 : 0), tdx = qlx < 0 ? -1 : (qlx >= PT_W ? 1 : 0);
                                 nbm |= 1 << ((tdy + 1) * 3 + tdx + 1);
                             }
@@ -398,36 +304,34 @@ __global__ void __launch_bounds__(PT_N / PPT) k_mf_pr_list(GcDims d, MfTiles tl,
             if (!__syncthreads_or(act)) break;
         }
         int left = 0;
-#pragma unroll
-        for (int j = 0; j < PPT; ++j) {
-            if (!inb[j]) continue;
+        if (inb) {
             // only the tile's border ring can receive pushes from other tiles during this launch: the interior is
             // owned exclusively, so its write-back is a plain store (L2 atomics are the scarce resource in the
             // early rounds, when nearly every pixel changes)
-            const int slot = tid + j * NT, ly = slot >> 5, p = pp[j];
+            const int slot = tid, ly = slot >> 5, p = pp;
             const bool ring = lx == 0 || lx == PT_W - 1 || ly == 0 || ly == PT_H - 1;
             const int e1 = s_ex[slot];
-            if (e1 != e0[j]) { if (ring) atomicAdd(&ex[base + p], e1 - e0[j]); else ex[base + p] = e1; }
+            if (e1 != e0) { if (ring) atomicAdd(&ex[base + p], e1 - e0); else ex[base + p] = e1; }
             int m1 = 0, chg = 0;
 #pragma unroll
             for (int dir = 0; dir < 8; ++dir) {
                 const int r1 = s_rc[dir][slot];
                 m1 |= (r1 > 0) ? (1 << dir) : 0;
-                if (r1 != r0[j][dir]) {
+                if (r1 != r0[dir]) {
                     chg = 1;
                     // another tile's push can only add to an arc that points OUT of this tile (the reverse of its own arc):
                     // those go back as atomic deltas, every other capacity is this block's alone (L2 atomics, ~30 G/s chip-wide,
                     // are what bounds the dense rounds)
                     const bool out = (ly == 0 && dir_dy(dir) < 0) || (ly == PT_H - 1 && dir_dy(dir) > 0) ||
                                      (lx == 0 && dir_dx(dir) < 0) || (lx == PT_W - 1 && dir_dx(dir) > 0);
-                    if (out) atomicAdd(&rc[rc_idx(dir, base + p)], r1 - r0[j][dir]);
+                    if (out) atomicAdd(&rc[rc_idx(dir, base + p)], r1 - r0[dir]);
                     else rc[rc_idx(dir, base + p)] = r1;
                 }
             }
-            if (chg) rmask[base + p] = (uint8_t)m1;     // (arcs that leave the tile: the relabel reads the capacities, see k_mf_dinit)
-            if (sk[j] != sk0[j]) snk[base + p] = sk[j];
+            if (chg) rmask[base + p] = (uint8_t)m1;     // (arcs that leave the tile: the relabel reads the capacities, see mf_tile_dirty)
+            if (sk != sk0) snk[base + p] = sk;
             const int d1 = s_d[ly + 1][lx + 1];
-            if (d1 != d0[j]) dist[base + p] = d1;
+            if (d1 != d0) dist[base + p] = d1;
             left |= (e1 > 0 && d1 < d.P) ? 1 : 0;
         }
         if (nbm) atomicOr(&s_nbm, nbm);
@@ -528,179 +432,204 @@ int read_i32(ggc_ctx* ctx, hipStream_t st, const int32_t* dev, int n, std::vecto
     return GGC_OK;
 }
 
+namespace {
+
+// The max-flow's scratch, one slot.  `dirty` must outlive a solve: the warm start of the next GrabCut iteration relies on
+// the marks it left.  The slot keeps its size through the solves of a call, so it is not reallocated in between.
+struct MfWork {
+    int32_t *rl_list[2], *rl_flag[2];    // relabel tiles: ping-pong work lists and membership flags
+    int32_t *pt_list[2], *pt_flag[2];    // push tiles: the same
+    unsigned long long* ring;            // ticket ring of the asynchronous launches, one slot per tile of the larger kind
+    int32_t* aq;                         // its control words
+    int32_t* busy;                       // state word per tile of an asynchronous push
+    long long* prof;                     // GGC_MF_TRACE clocks [2][64][8]: asynchronous push waves | tile visits
+    int32_t* dirty;                      // one word per push tile: a neighbour pushed into it since its arc masks were last exact
+    void layout(Carve& c, size_t n_rt, size_t n_pt) {
+        for (auto& p : rl_list) p = c.take<int32_t>(n_rt);
+        for (auto& p : rl_flag) p = c.take<int32_t>(n_rt);
+        for (auto& p : pt_list) p = c.take<int32_t>(n_pt);
+        for (auto& p : pt_flag) p = c.take<int32_t>(n_pt);
+        ring = c.take<unsigned long long>(std::max(n_rt, n_pt));
+        aq = c.take<int32_t>(AQ_WORDS);
+        busy = c.take<int32_t>(n_pt);
+        prof = c.take<long long>(2 * 64 * 8);
+        dirty = c.take<int32_t>(n_pt);
+    }
+};
+
+// One solve: its buffers, its tiling, its workspace, and the two phases of a round.
+struct MfSolve {
+    ggc_ctx* ctx; hipStream_t st; GcDims d; MfTiles tl; size_t n_rt, n_pt;
+    int32_t *rc, *ex, *snk, *dist; uint8_t* rmask;
+    MfControl ctl;
+    int32_t *n_open, *rl_cnt, *pr_cnt;   // ctl.cnt [0], [1..3], [4..6]
+    MfWork w;
+    long long* prof;                     // w.prof under GGC_MF_TRACE, null otherwise
+
+    // Global relabel of the n_cur images on `open`.  k_mf_rinit starts the labels from the sink links and lists the tiles that
+    // have a pixel away from the sink; the first launches relax every listed tile (bandwidth work, plain stores), and the long
+    // sparse rest of the front runs inside ONE asynchronous launch that ends at the exact fixpoint (nothing to read back).
+    // A PARTIAL relabel stops after the work-list launches.  `launches`: how many relabel launches ran.
+    int relabel(const int32_t* open, int n_cur, size_t scale, bool partial, int& launches) {
+        const Knobs& kn = knobs();
+        const int per_image = tl.rt_x * tl.rt_y;
+        const int grid = (int)std::min<size_t>(RELAX_GRID * scale, std::max<size_t>(16, cdiv((size_t)n_cur * per_image, 4)));
+        ProfScope ps(ctx, st, "maxflow_relabel");
+        hipLaunchKernelGGL(k_mf_rinit, dim3(cdiv(per_image, 4), n_cur), dim3(256), 0, st, d, tl, open, snk, dist, w.rl_list[0], w.rl_flag[0],
+                           w.rl_flag[1], rl_cnt, ctl.active, n_open);
+        int phase = 0;
+        for (; phase < kn.mf_relax_dense; ++phase) {
+            int32_t *li = w.rl_list[phase & 1], *lo = w.rl_list[(phase + 1) & 1], *fi = w.rl_flag[phase & 1], *fo = w.rl_flag[(phase + 1) & 1];
+            if (prof) hipLaunchKernelGGL(k_mf_relax_wave<true>, dim3(grid), dim3(256), 0, st, d, tl, phase, prof, rmask, w.dirty, rc, dist, rl_cnt, li, lo, fi, fo);
+            else hipLaunchKernelGGL(k_mf_relax_wave<false>, dim3(grid), dim3(256), 0, st, d, tl, phase, prof, rmask, w.dirty, rc, dist, rl_cnt, li, lo, fi, fo);
+        }
+        launches = phase;
+        if (partial) return GGC_OK;
+        // (pool size: 512 waves per 64 open images; a lane alone runs the same with 128 or 2048 — the launch is a latency
+        // chain, not throughput — and four lanes with larger pools lose to each other's waiting waves: 56.6 -> 58.9 -> 62.8 ms)
+        const int pool = (int)std::min<size_t>(ASYNC_GRID * scale, std::max<size_t>(16, cdiv((size_t)n_cur * per_image, 16)));
+        launches = phase + 1;
+        return maxflow_relax_async(ctx, st, d, tl, rmask, w.dirty, rc, dist, rl_cnt + phase % 3, w.rl_list[phase & 1], w.rl_flag[phase & 1],
+                                   w.ring, w.aq, (int)n_rt, pool, ctl.err);
+    }
+
+    // Push phase over the push tiles the active scan listed.  n_cur: the images open when the round began (the grids follow
+    // them).  A sparse round is one asynchronous launch that chases the excess from tile to tile (chains of at most
+    // GGC_MF_ASYNC_HOPS hops); `waves` is its pool, 0 for a dense round of launches over work lists.
+    int push(int round, int n_cur, size_t scale, int total_active, int& waves) {
+        const Knobs& kn = knobs();
+        ProfScope ps(ctx, st, "maxflow_push");
+        if (round > 0 && total_active <= kn.mf_async_push_active) {
+            waves = (int)std::min<long long>(4ll * ASYNC_GRID * (long long)scale, std::max<long long>(64, total_active / 4));
+            return maxflow_push_async(ctx, st, d, tl, kn.mf_async_tile, kn.mf_async_sweeps, kn.mf_async_hops, rc, ex, snk, dist, rmask, w.dirty,
+                                      pr_cnt, w.pt_list[0], (int)n_pt, w.busy, w.ring, w.aq, waves, ctl.err, prof);
+        }
+        waves = 0;
+        // dense round.  First round: labels go stale fastest while most excess is still moving, an early relabel pays
+        // (8 launches vs 12: +3 %); sweeps per visit measured flat from 6 to 12 and worse either side.
+        const int launches = round == 0 ? kn.mf_dense_launches0 : kn.mf_dense_launches;
+        const int pr_grid = (int)std::min<size_t>(PUSH_GRID * scale, std::max<size_t>(64, (size_t)n_cur * tl.pt_x * tl.pt_y / 2));
+        // an active pixel opens at most its own tile: empty blocks only add dispatch time to launches that are pure latency
+        const int grid = (int)std::min<long long>(pr_grid, std::max<long long>(128, 2ll * total_active));
+        for (int phase = 0; phase < launches; ++phase)
+            hipLaunchKernelGGL(k_mf_pr_list, dim3(grid), dim3(PT_N), 0, st, d, tl, phase, kn.mf_dense_sweeps, rc, ex, snk, dist, rmask, w.dirty, pr_cnt,
+                               w.pt_list[phase & 1], w.pt_list[(phase + 1) & 1], w.pt_flag[phase & 1], w.pt_flag[(phase + 1) & 1]);
+        GGC_LAUNCH_CHECK(ctx);
+        return GGC_OK;
+    }
+};
+
+// GGC_MF_TRACE=1: per-round diagnostics on stderr, blocking (tools/mf_trace.py reads them).  The clocks of the relabel
+// visits are table 1 of the trace clocks, those of an asynchronous push tables 0 (per wave) and 1 (inside the visit).
+struct MfTrace {
+    std::chrono::steady_clock::time_point t_prev = std::chrono::steady_clock::now();
+    double push_ms = 0.0;
+
+    // after the active scan: the relabel visits' clocks, active pixels and open images, the stragglers by image
+    int round(const MfSolve& s, int round, int n_next, int total_active, int relax_launches) {
+        ggc_ctx* ctx = s.ctx;
+        long long hh[64 * 8], h[5] = {0, 0, 0, 0, 0};
+        GGC_HIP(ctx, hipStreamSynchronize(s.st));
+        GGC_HIP(ctx, hipMemcpy(hh, s.prof + 64 * 8, sizeof hh, hipMemcpyDeviceToHost));
+        GGC_HIP(ctx, hipMemsetAsync(s.prof + 64 * 8, 0, sizeof hh, s.st));
+        for (int i = 0; i < 64; ++i) for (int k = 0; k < 5; ++k) h[k] += hh[i * 8 + k];
+        if (h[3] > 0)
+            std::fprintf(stderr, "    [relabel visits] %lld dense visits: per visit load+fill %.2f us, sweeps %.2f us (%.1f sweeps), write-back %.2f us\n",
+                         h[3], 0.01 * h[0] / h[3], 0.01 * h[1] / h[3], (double)h[4] / h[3], 0.01 * h[2] / h[3]);
+        std::vector<int32_t> act;
+        if (int rcode = read_i32(ctx, s.st, s.ctl.active, s.d.B, act)) return rcode;
+        const auto t_now = std::chrono::steady_clock::now();
+        const double ms = std::chrono::duration<double, std::milli>(t_now - t_prev).count();
+        std::fprintf(stderr, "[ggc maxflow] round %d: open images %d, active pixels %d, relabel launches %d, relabel+scan %.3f ms, previous push %.3f ms\n",
+                     round, n_next, total_active, relax_launches, ms - push_ms, push_ms);
+        t_prev = t_now;
+        if (n_next > 0 && n_next <= 12) {
+            std::fprintf(stderr, "    [open]");
+            for (int b = 0; b < s.d.B; ++b) if (act[b]) std::fprintf(stderr, " %d:%d", b, act[b]);
+            std::fprintf(stderr, "\n");
+        }
+        return GGC_OK;
+    }
+
+    // after a push phase: its time, and where the waves of an asynchronous one (waves > 0) spent it
+    int push(const MfSolve& s, int waves) {
+        ggc_ctx* ctx = s.ctx;
+        GGC_HIP(ctx, hipStreamSynchronize(s.st));
+        push_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_prev).count();
+        if (waves == 0) return GGC_OK;
+        long long hh[128 * 8], h[7] = {0, 0, 0, 0, 0, 0, 0}, g[3] = {0, 0, 0};
+        GGC_HIP(ctx, hipMemcpy(hh, s.prof, sizeof hh, hipMemcpyDeviceToHost));
+        GGC_HIP(ctx, hipMemsetAsync(s.prof, 0, sizeof hh, s.st));
+        for (int i = 0; i < 64; ++i) for (int k = 0; k < 7; ++k) h[k] += hh[i * 8 + k];
+        for (int i = 0; i < 64; ++i) for (int k = 0; k < 3; ++k) g[k] += hh[(64 + i) * 8 + k];
+        if (h[3] > 0)
+            std::fprintf(stderr, "    [async visit] load+fill %.2f us, sweeps %.2f us (%.1f sweeps), write-back+drain %.2f us\n", 0.01 * g[0] / h[3],
+                         0.01 * g[1] / h[3], (double)g[2] / h[3], 0.01 * (h[1] - g[0] - g[1]) / h[3]);
+        if (h[6] > 0)
+            std::fprintf(stderr, "    [async push] %d waves alive %.1f us on average; %lld visits (%lld followed): per visit wait+lock %.2f us, "
+                         "visit %.2f us, hand-over %.2f us\n", waves, 0.01 * h[5] / h[6], h[3], h[4], h[3] ? 0.01 * h[0] / h[3] : 0.0,
+                         h[3] ? 0.01 * h[1] / h[3] : 0.0, h[3] ? 0.01 * h[2] / h[3] : 0.0);
+        return GGC_OK;
+    }
+};
+
+} // namespace
+
 int maxflow(ggc_ctx* ctx, hipStream_t st, const GcDims& d, const int32_t* state, int32_t* rc, int32_t* ex,
-            int32_t* snk, int32_t* dist, uint8_t* rmask, int32_t* lists /*[2B] open-image lists*/,
-            int32_t* flags /*[B] active | [1] n_open | [3] relabel counters | [3] push counters | [1] active total*/,
-            int32_t* err_flag, bool masks_exact) {
+            int32_t* snk, int32_t* dist, uint8_t* rmask, const MfControl& ctl, bool masks_exact) {
     const Knobs& kn = knobs();
-    const int B = d.B;
-    int32_t* active = flags;
-    int32_t* n_open = flags + B;
-    int32_t* rl_cnt = flags + B + 1;
-    int32_t* pr_cnt = flags + B + 4;
     const MfTiles tl{cdiv(d.W, RT), cdiv(d.H, RT), cdiv(d.W, PT_W), cdiv(d.H, PT_H)};
-    const size_t n_rt = (size_t)tl.rt_x * tl.rt_y * B, n_pt = (size_t)tl.pt_x * tl.pt_y * B;
-    // per tile kind: two ping-pong work lists and two ping-pong membership flags
-    int32_t* rl = scratch_t<int32_t>(ctx, S_GC_N, n_rt * 4);
-    int32_t* pt = scratch_t<int32_t>(ctx, S_GC_M, n_pt * 4);
-    if (!rl || !pt) return GGC_E_OOM;
-    int32_t *rl_list[2] = {rl, rl + n_rt}, *rl_flag[2] = {rl + 2 * n_rt, rl + 3 * n_rt};
-    int32_t *pt_list[2] = {pt, pt + n_pt}, *pt_flag[2] = {pt + 2 * n_pt, pt + 3 * n_pt};
-    int32_t *list_cur = lists, *list_nxt = lists + B;
-    // asynchronous single-launch drivers of the sparse phases (ggc_maxflow_async.hip): ring of the larger tile count, the
-    // queue words, one lock word per push tile; behind them the trace clocks and the dirty words
-    const size_t ring_cap = std::max(n_rt, n_pt);
-    GGC_REQUIRE(ctx, ring_cap < (1u << 24), GGC_E_UNSUPPORTED, "batch has more max-flow tiles than a queue entry addresses");
-    unsigned long long* ring = scratch_t<unsigned long long>(ctx, S_GC_O, ring_cap + (AQ_WORDS + n_pt + 1) / 2 + 1 + 128 * 8 + 2 + (n_pt + 1) / 2 + 1);
-    if (!ring) return GGC_E_OOM;
-    int32_t* aq = reinterpret_cast<int32_t*>(ring + ring_cap);
-    int32_t* busy = aq + AQ_WORDS;
-    long long* prof_dev = kn.mf_trace ? reinterpret_cast<long long*>(busy + ((n_pt + 3) & ~(size_t)1)) : nullptr;
-    // one word per push tile: a neighbour pushed into it since its arc masks were last exact.  k_build_graph writes exact
-    // masks for every pixel on a cold start; a warm start leaves the definite pixels alone, so their tiles' marks stay.
-    int32_t* dirty = busy + ((n_pt + 3) & ~(size_t)1) + 2 * 128 * 8;
-    if (masks_exact) GGC_HIP(ctx, hipMemsetAsync(dirty, 0, sizeof(int32_t) * n_pt, st));
-    if (prof_dev) GGC_HIP(ctx, hipMemsetAsync(prof_dev, 0, 128 * 8 * sizeof(long long), st));
-    GGC_HIP(ctx, hipMemsetAsync(n_open, 0, sizeof(int32_t), st));
-    hipLaunchKernelGGL(k_open_init, dim3(cdiv(B, 256)), dim3(256), 0, st, B, state, list_cur, n_open, rl_cnt);
+    MfSolve s{ctx, st, d, tl, (size_t)tl.rt_x * tl.rt_y * d.B, (size_t)tl.pt_x * tl.pt_y * d.B, rc, ex, snk, dist, rmask,
+              ctl, ctl.cnt, ctl.cnt + 1, ctl.cnt + 4, {}, nullptr};
+    GGC_REQUIRE(ctx, std::max(s.n_rt, s.n_pt) < (1u << 24), GGC_E_UNSUPPORTED, "batch has more max-flow tiles than a queue entry addresses");
+    if (!carve_scratch(ctx, S_GC_M, [&](Carve& c) { s.w.layout(c, s.n_rt, s.n_pt); })) return GGC_E_OOM;
+    // k_build_graph writes exact masks for every pixel on a cold start; a warm start leaves the definite pixels alone, so
+    // their tiles keep their dirty marks
+    if (masks_exact) GGC_HIP(ctx, hipMemsetAsync(s.w.dirty, 0, sizeof(int32_t) * s.n_pt, st));
+    if (kn.mf_trace) {
+        s.prof = s.w.prof;
+        GGC_HIP(ctx, hipMemsetAsync(s.prof, 0, 2 * 64 * 8 * sizeof(long long), st));
+    }
+    GGC_HIP(ctx, hipMemsetAsync(s.n_open, 0, sizeof(int32_t), st));
+    int32_t *list_cur = ctl.lists, *list_nxt = ctl.lists + d.B;
+    hipLaunchKernelGGL(k_open_init, dim3(cdiv(d.B, 256)), dim3(256), 0, st, d.B, state, list_cur, s.n_open, s.rl_cnt);
     GGC_LAUNCH_CHECK(ctx);
     std::vector<int32_t> host;
-    int rcode = read_i32(ctx, st, n_open, 1, host);
+    int rcode = read_i32(ctx, st, s.n_open, 1, host);
     if (rcode) return rcode;
     int n_cur = host[0];
     if (n_cur == 0) return GGC_OK;
+    MfTrace trace;
     const int max_rounds = 4096;
-    auto t_prev = std::chrono::steady_clock::now();
-    double push_ms = 0.0;
     for (int round = 0; round < max_rounds; ++round) {
         // Blocks walk their share of a list and load the next tile while they work on the current one, so a block should own
         // several tiles: the grid caps are per 64 open images (one GrabCut lane) and grow with the batch a call is given.
         // Late rounds (a handful of open images) are pure launch latency, and empty blocks add to it: never more blocks than tiles.
         const size_t scale = std::max<size_t>(1, ((size_t)n_cur + 32) / 64);
-        const int per_image = tl.rt_x * tl.rt_y;
         // The first rounds relabel PARTIALLY: only the work-list launches, without the asynchronous launch that follows the
         // front to its fixpoint.  Labels steer the pushes, they do not have to be exact for the result to be: whatever labels
         // a push phase sees, it turns a valid preflow into a valid preflow, and the cut is read off the EXACT relabel that
         // ends the solve.  A pixel the front has not reached keeps "infinity" for this round — its excess waits (deep inside
         // an object most of it is trapped anyway) — so an image is never closed on a partial relabel, and the round that
         // decides "no active pixel left" is always a full one.  Measured: 57.7 -> 52.9 ms per GrabCut stage (batch 256).
-        const bool partial = kn.mf_async && round < kn.mf_partial_rounds;
-        const int pr_grid = (int)std::min<size_t>(PUSH_GRID * scale, std::max<size_t>(64, (size_t)n_cur * tl.pt_x * tl.pt_y / 2));
-        const int rl_grid = (int)std::min<size_t>(RELAX_GRID * scale, std::max<size_t>(16, cdiv((size_t)n_cur * per_image, 4)));
-        // ---- global relabel of the open images
+        const bool partial = round < kn.mf_partial_rounds;
         int relax_launches = 0;
-        {
-            ProfScope prof(ctx, st, "maxflow_relabel");
-            hipLaunchKernelGGL(k_mf_rinit, dim3(cdiv(per_image, 4), n_cur), dim3(256), 0, st, d, tl, list_cur, snk, dist, rl_list[0], rl_flag[0],
-                               rl_flag[1], rl_cnt, active, n_open);
-            auto relax = [&](int phase) {
-                int32_t *li = rl_list[phase & 1], *lo = rl_list[(phase + 1) & 1], *fi = rl_flag[phase & 1], *fo = rl_flag[(phase + 1) & 1];
-                if (prof_dev) hipLaunchKernelGGL(k_mf_relax_wave<true>, dim3(rl_grid), dim3(256), 0, st, d, tl, phase, prof_dev, rmask, dirty, rc, dist, rl_cnt, li, lo, fi, fo);
-                else hipLaunchKernelGGL(k_mf_relax_wave<false>, dim3(rl_grid), dim3(256), 0, st, d, tl, phase, prof_dev, rmask, dirty, rc, dist, rl_cnt, li, lo, fi, fo);
-            };
-            // k_mf_rinit starts the labels from the sink links and lists the tiles that have a pixel away from the sink; the
-            // first launches relax every listed tile (bandwidth work, plain stores).  With the asynchronous driver the long
-            // sparse rest of the front runs inside ONE launch that ends at the exact fixpoint (nothing to read back); without
-            // it the host reads the size of the next list every fourth launch.
-            int phase = 0;
-            if (kn.mf_async && partial) {
-                for (; phase < kn.mf_relax_dense; ++phase) relax(phase);
-                relax_launches = phase;
-            } else if (kn.mf_async) {
-                for (; phase < kn.mf_relax_dense; ++phase) relax(phase);
-                // (pool size: 512 waves per 64 open images; a lane alone runs the same with 128 or 2048 — the launch is a latency
-                // chain, not throughput — and four lanes with larger pools lose to each other's waiting waves: 56.6 -> 58.9 -> 62.8 ms)
-                const int grid = (int)std::min<size_t>(ASYNC_GRID * scale, std::max<size_t>(16, cdiv((size_t)n_cur * per_image, 16)));
-                if ((rcode = maxflow_relax_async(ctx, st, d, tl, rmask, dirty, rc, dist, rl_cnt + phase % 3, rl_list[phase & 1], rl_flag[phase & 1], ring, aq,
-                                                 (int)n_rt, grid, err_flag)))
-                    return rcode;
-                relax_launches = phase + 1;
-            } else {
-                for (int guard = 0; guard < 100000; ++guard) {
-                    for (int rep = 0; rep < 4; ++rep, ++phase) relax(phase);
-                    GGC_LAUNCH_CHECK(ctx);
-                    if ((rcode = read_i32(ctx, st, rl_cnt + phase % 3, 1, host))) return rcode;   // size of the next frontier
-                    if (host[0] == 0) break;
-                }
-                relax_launches = phase;
-            }
-        }
+        if ((rcode = s.relabel(list_cur, n_cur, scale, partial, relax_launches))) return rcode;
         // ---- who still has work?  (active pixel = excess that can still reach the sink)
         // (active[], the open-image count, the push-list counters and the active total were zeroed by this round's k_mf_rinit)
         hipLaunchKernelGGL(k_mf_active, dim3(std::min(cdiv(tl.pt_x * tl.pt_y, 4), 128), n_cur), dim3(256), 0, st, d, tl, list_cur, ex, dist,
-                           active, pt_flag[0], pt_flag[1], pt_list[0], pr_cnt);
-        hipLaunchKernelGGL(k_done_update, dim3(cdiv(n_cur, 256)), dim3(256), 0, st, n_cur, list_cur, active, list_nxt, n_open, partial ? 1 : 0, rl_cnt);
+                           ctl.active, s.w.pt_flag[0], s.w.pt_flag[1], s.w.pt_list[0], s.pr_cnt);
+        hipLaunchKernelGGL(k_done_update, dim3(cdiv(n_cur, 256)), dim3(256), 0, st, n_cur, list_cur, ctl.active, list_nxt, s.n_open, partial ? 1 : 0, s.rl_cnt);
         GGC_LAUNCH_CHECK(ctx);
-        if ((rcode = read_i32(ctx, st, n_open, 8, host))) return rcode;
+        if ((rcode = read_i32(ctx, st, s.n_open, 8, host))) return rcode;
         const int n_next = host[0], total_active = host[7];
-        if (kn.mf_trace) {   // diagnostics: visit-phase clocks of the dense relabel launches, active pixels / open images per round, the stragglers by image
-            long long hh[64 * 8], h[5] = {0, 0, 0, 0, 0};
-            GGC_HIP(ctx, hipStreamSynchronize(st));
-            GGC_HIP(ctx, hipMemcpy(hh, prof_dev + 64 * 8, sizeof hh, hipMemcpyDeviceToHost));
-            GGC_HIP(ctx, hipMemsetAsync(prof_dev + 64 * 8, 0, sizeof hh, st));
-            for (int i = 0; i < 64; ++i) for (int k = 0; k < 5; ++k) h[k] += hh[i * 8 + k];
-            if (h[3] > 0)
-                std::fprintf(stderr, "    [relabel visits] %lld dense visits: per visit load+fill %.2f us, sweeps %.2f us (%.1f sweeps), write-back %.2f us\n",
-                             h[3], 0.01 * h[0] / h[3], 0.01 * h[1] / h[3], (double)h[4] / h[3], 0.01 * h[2] / h[3]);
-            std::vector<int32_t> act;
-            if ((rcode = read_i32(ctx, st, active, B, act))) return rcode;
-            const auto t_now = std::chrono::steady_clock::now();
-            const double ms = std::chrono::duration<double, std::milli>(t_now - t_prev).count();
-            std::fprintf(stderr, "[ggc maxflow] round %d: open images %d, active pixels %d, relabel launches %d, relabel+scan %.3f ms, previous push %.3f ms\n",
-                         round, n_next, total_active, relax_launches, ms - push_ms, push_ms);
-            t_prev = t_now;
-            if (n_next > 0 && n_next <= 12) {
-                std::fprintf(stderr, "    [open]");
-                for (int b = 0; b < B; ++b) if (act[b]) std::fprintf(stderr, " %d:%d", b, act[b]);
-                std::fprintf(stderr, "\n");
-            }
-        }
+        if (kn.mf_trace && (rcode = trace.round(s, round, n_next, total_active, relax_launches))) return rcode;
         if (n_next == 0) return GGC_OK;
         std::swap(list_cur, list_nxt);
+        int waves = 0;
+        if ((rcode = s.push(round, n_cur, scale, total_active, waves))) return rcode;
+        if (kn.mf_trace && (rcode = trace.push(s, waves))) return rcode;
         n_cur = n_next;
-        // ---- push-relabel sweeps
-        {
-            ProfScope prof(ctx, st, "maxflow_push");
-            if (kn.mf_async && round > 0 && total_active <= kn.mf_async_push_active) {
-                // sparse round: one asynchronous launch chases the excess from tile to tile (chains of at most async_hops hops)
-                const int waves = (int)std::min<long long>(4ll * ASYNC_GRID * (long long)scale, std::max<long long>(64, total_active / 4));
-                if ((rcode = maxflow_push_async(ctx, st, d, tl, kn.mf_async_tile, kn.mf_async_sweeps, kn.mf_async_hops, rc, ex, snk, dist, rmask, dirty, pr_cnt, pt_list[0], (int)n_pt,
-                                                busy, ring, aq, waves, err_flag, prof_dev)))
-                    return rcode;
-                if (kn.mf_trace) {
-                    GGC_HIP(ctx, hipStreamSynchronize(st));
-                    push_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_prev).count();
-                    long long hh[128 * 8], h[7] = {0, 0, 0, 0, 0, 0, 0}, g[3] = {0, 0, 0};
-                    GGC_HIP(ctx, hipMemcpy(hh, prof_dev, sizeof hh, hipMemcpyDeviceToHost));
-                    GGC_HIP(ctx, hipMemsetAsync(prof_dev, 0, sizeof hh, st));
-                    for (int i = 0; i < 64; ++i) for (int k = 0; k < 7; ++k) h[k] += hh[i * 8 + k];
-                    for (int i = 0; i < 64; ++i) for (int k = 0; k < 3; ++k) g[k] += hh[(64 + i) * 8 + k];
-                    if (h[3] > 0)
-                        std::fprintf(stderr, "    [async visit] load+fill %.2f us, sweeps %.2f us (%.1f sweeps), write-back+drain %.2f us\n", 0.01 * g[0] / h[3],
-                                     0.01 * g[1] / h[3], (double)g[2] / h[3], 0.01 * (h[1] - g[0] - g[1]) / h[3]);
-                    if (h[6] > 0)
-                        std::fprintf(stderr, "    [async push] %d waves alive %.1f us on average; %lld visits (%lld followed): per visit wait+lock %.2f us, "
-                                     "visit %.2f us, hand-over %.2f us\n", waves, 0.01 * h[5] / h[6], h[3], h[4], h[3] ? 0.01 * h[0] / h[3] : 0.0,
-                                     h[3] ? 0.01 * h[1] / h[3] : 0.0, h[3] ? 0.01 * h[2] / h[3] : 0.0);
-                }
-                continue;
-            }
-            // dense round.  First round: labels go stale fastest while most excess is still moving, an early relabel pays
-            // (8 launches vs 12: +3 %); sweeps per visit measured flat from 6 to 12 and worse either side.  Without the
-            // asynchronous driver the tail rounds (few active pixels, labels stay exact) run longer chains of cheap launches.
-            const bool tail = !kn.mf_async && total_active <= 4000;
-            const int launches = tail ? 64 : (round == 0 ? kn.mf_dense_launches0 : kn.mf_dense_launches);
-            // an active pixel opens at most its own tile: empty blocks only add dispatch time to launches that are pure latency
-            const int grid = (int)std::min<long long>(pr_grid, std::max<long long>(128, 2ll * total_active));
-            for (int phase = 0; phase < launches; ++phase)
-                hipLaunchKernelGGL((k_mf_pr_list<1>), dim3(grid), dim3(PT_N), 0, st, d, tl, phase, kn.mf_dense_sweeps, rc, ex, snk, dist, rmask, dirty, pr_cnt,
-                                   pt_list[phase & 1], pt_list[(phase + 1) & 1], pt_flag[phase & 1], pt_flag[(phase + 1) & 1]);
-            GGC_LAUNCH_CHECK(ctx);
-            if (kn.mf_trace) {
-                GGC_HIP(ctx, hipStreamSynchronize(st));
-                push_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_prev).count();
-            }
-        }
     }
     return set_err(ctx, GGC_E_DEVICE, "max-flow did not converge in %d rounds", max_rounds);
 }

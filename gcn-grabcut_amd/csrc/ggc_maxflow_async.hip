@@ -40,12 +40,9 @@
 namespace ggc {
 namespace {
 
-constexpr int RT = MF_RT, PT_W = MF_PT_W, PT_H = MF_PT_H, PT_N = PT_W * PT_H;
-constexpr int PT_PX = PT_N / 64;                     // pixels per lane in a push tile (4)
-constexpr int RT_HALO = (RT + 2) * (RT + 2), PT_HALO = (PT_H + 2) * (PT_W + 2);
+constexpr int PT_H = MF_PT_H;
 constexpr long long AQ_TIMEOUT = 200000000ll;        // 2 s of wall_clock64 (100 MHz): a wave that waits longer reports and ends the launch
 
-__device__ __forceinline__ int ldg(const int32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ unsigned long long ldg64(const unsigned long long* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ void drain() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }   // this wave's loads, stores and atomics are done
 
@@ -99,18 +96,14 @@ __global__ void __launch_bounds__(256) k_aq_init(const int32_t* __restrict__ cou
 }
 
 // ---- global relabel, asynchronous ---------------------------------------------------------------------------------
-struct RelaxWaveLds { int d[RT + 2][RT + 2]; uint32_t m[RT][RT / 4]; };
-
 __global__ void __launch_bounds__(256) k_mf_relax_async(GcDims d, MfTiles tl, uint8_t* __restrict__ rmask, int32_t* __restrict__ dirty,
                                                         const int32_t* __restrict__ rc, int32_t* __restrict__ dist, int32_t* __restrict__ flag,
                                                         unsigned long long* __restrict__ ring, int32_t* __restrict__ q, int cap,
                                                         int32_t* __restrict__ err_flag) {
-    constexpr int T = RT, HALO_IT = (RT_HALO + 63) / 64;
     __shared__ RelaxWaveLds lds[4];
     RelaxWaveLds& S = lds[threadIdx.x >> 6];
     const int tiles_per_image = tl.rt_x * tl.rt_y;
-    int* sd = &S.d[0][0];
-    uint8_t* sm = reinterpret_cast<uint8_t*>(&S.m[0][0]);
+    MfRelaxClocks<false> ck;
     int tile = -1;                                                         // >= 0: the neighbour this wave follows into
     for (;;) {
         int lane = threadIdx.x & 63;
@@ -121,70 +114,10 @@ __global__ void __launch_bounds__(256) k_mf_relax_async(GcDims d, MfTiles tl, ui
             if (lane == 0) atomicExch(&flag[tile], 0);                     // consumed: a halo change from now on re-queues the tile
             drain();                                                       // ... and the loads below come after it
         }
+        const int nbm = mf_relax_visit<true, false>(d, tl, tile, lane, S, rmask, dirty, rc, dist, flag, ck);
+        drain();                                                           // the new labels are at memory before a neighbour is told
         const int b = tile / tiles_per_image, tr = tile % tiles_per_image;
         const int tyi = tr / tl.rt_x, txi = tr % tl.rt_x;
-        const int tx0 = txi * T, ty0 = tyi * T;
-        const size_t base = (size_t)b * d.P;
-        const int lx = lane & 31, h = lane >> 5;
-        int hv[HALO_IT];
-#pragma unroll
-        for (int k = 0; k < HALO_IT; ++k) {                                // unconditional loads from clamped addresses
-            const int i = min(lane + k * 64, RT_HALO - 1);
-            const int gy = ty0 + i / (T + 2) - 1, gx = tx0 + i % (T + 2) - 1;
-            hv[k] = ldg(dist + base + (size_t)min(max(gy, 0), d.H - 1) * d.W + min(max(gx, 0), d.W - 1));
-        }
-        uint32_t mv[16];
-#pragma unroll
-        for (int r = 0; r < 16; ++r)                                       // arc masks do not change during a relabel: plain loads
-            mv[r] = rmask[base + (size_t)min(ty0 + 16 * h + r, d.H - 1) * d.W + min(tx0 + lx, d.W - 1)];
-        const bool dirty_t = mf_tile_dirty(dirty, tl, b, tyi, txi, lane);  // wave-uniform (ggc_mf_sweep.h)
-        MfBorderArcs ba;                                                   // (capacities do not change during a relabel either)
-        if (dirty_t) ba.load(d, rc, (size_t)d.B * d.P, base, ty0, tx0, lx, h);
-        uint32_t inv_v[4] = {0u, 0u, 0u, 0u}, inv_h[4];                    // bit set = no arc; outside the image: all blocked
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            uint32_t m = ~mv[r] & 0xffu;
-            if (dirty_t) m = ba.row(m, r);
-            sm[(16 * h + r) * T + lx] = (uint8_t)((tx0 + lx < d.W && ty0 + 16 * h + r < d.H) ? m : 0xffu);
-        }
-#pragma unroll
-        for (int k = 0; k < HALO_IT; ++k) {
-            const int i = lane + k * 64;
-            const int gy = ty0 + i / (T + 2) - 1, gx = tx0 + i % (T + 2) - 1;
-            if (i < RT_HALO) sd[i] = (gx >= 0 && gx < d.W && gy >= 0 && gy < d.H) ? hv[k] : DINF;
-        }
-        mf_wave_sync();
-        if (dirty_t) {      // (a second wave relaxing the same tile meanwhile writes the same bytes)
-            if (ty0 + lx < d.H && tx0 + (h ? 31 : 0) < d.W) sm[lx * T + (h ? 31 : 0)] = (uint8_t)ba.col(sm[lx * T + (h ? 31 : 0)], h);
-            mf_wave_sync();
-            mf_tile_repair(d, tl, rmask, dirty, S, base, b, tyi, txi, ty0, tx0, lx, h, lane);
-        }
-#pragma unroll
-        for (int r = 0; r < 16; ++r) inv_v[r >> 2] |= (uint32_t)sm[(16 * h + r) * T + lx] << (8 * (r & 3));
-#pragma unroll
-        for (int k = 0; k < 4; ++k) inv_h[k] = S.m[lx][4 * h + k];         // H sweep: row lx, columns 16h .. 16h+15
-        int old[16];
-#pragma unroll
-        for (int r = 0; r < 16; ++r) old[r] = S.d[16 * h + r + 1][lx + 1];
-        bool settled = false;
-        for (int it = 0; it < 4 * T; ++it) {                               // a sweep that changes nothing: fixpoint (a visit capped at 2-6 sweeps and re-queued publishes its border earlier, but costs more visits: 56.4 -> 60.3 / 58.1 / 56.6 ms)
-            const int ch = (it & 1) ? relax_sweep_h(S, inv_h, lx, h) : relax_sweep_v(S, inv_v, lx, h);
-            mf_wave_sync();
-            if (!__any(ch)) { settled = true; break; }
-        }
-        int nbm = settled ? 0 : 1 << 4;                                    // bit (dy + 1) * 3 + (dx + 1)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int ly = 16 * h + r;
-            const int v = S.d[ly + 1][lx + 1];
-            if (v != old[r]) {                                             // (pixels outside the image never change: all arcs blocked)
-                atomicMin(&dist[base + (size_t)(ty0 + ly) * d.W + tx0 + lx], v);
-                const int Lf = lx == 0, Rt = lx == T - 1, U = ly == 0, D = ly == T - 1;
-                nbm |= (U & Lf) | U << 1 | (U & Rt) << 2 | Lf << 3 | Rt << 5 | (D & Lf) << 6 | D << 7 | (D & Rt) << 8;
-            }
-        }
-        nbm = mf_wave_or(nbm);
-        drain();                                                           // the new labels are at memory before a neighbour is told
         // Neighbours whose halo changed and that are not queued: the first one this wave visits next itself (its flag stays 0,
         // as if popped; a second wave relaxing the same tile meanwhile is harmless — labels only fall, atomically), the
         // others go through the queue.
@@ -218,13 +151,12 @@ template <int TH>
 struct PushTileLds {
     int ex[32 * TH]; int sk[32 * TH]; int d[TH + 2][34]; int rc[8][32 * TH];
     uint32_t mask[32]; unsigned short list[32 * TH];
-    unsigned char streak[32 * TH];      // relabels in a row without a push (a pixel is handled by one lane at a time)
 };
 
 // Returns the 9-bit mask of tiles owed a visit: bit (dy + 1) * 3 + (dx + 1) for a neighbour that received excess, bit 4
 // when this tile still holds active pixels.
 template <int TH>
-__device__ int push_tile_visit(const GcDims& d, int tyi, int txi, int inner, int chase, int park, size_t base, size_t BP,
+__device__ int push_tile_visit(const GcDims& d, int tyi, int txi, int inner, size_t base, size_t BP,
                                int32_t* __restrict__ rc, int32_t* __restrict__ ex, int32_t* __restrict__ snk,
                                int32_t* __restrict__ dist, uint8_t* __restrict__ rmask, PushTileLds<TH>& S, int lane,
                                bool prof, long long (&pv)[4]) {
@@ -258,7 +190,6 @@ __device__ int push_tile_visit(const GcDims& d, int tyi, int txi, int inner, int
         if (i < HALO) sd[i] = (gx >= 0 && gx < d.W && gy >= 0 && gy < d.H) ? hv[k] : DINF;
     }
     if (lane < 32) S.mask[lane] = 0u;
-    for (int i = lane; i < 32 * TH / 4; i += 64) reinterpret_cast<uint32_t*>(S.streak)[i] = 0u;
     mf_wave_sync();
 #pragma unroll
     for (int j = 0; j < NPX; ++j) {
@@ -300,80 +231,68 @@ __device__ int push_tile_visit(const GcDims& d, int tyi, int txi, int inner, int
         if (lane < TH) S.mask[lane] = 0u;
         while (w) { const int bit = __ffs(w) - 1; S.list[off++] = (unsigned short)(lane * 32 + bit); w &= w - 1; }
         mf_wave_sync();
-        // ---- one active pixel per lane, and the lane CHASES the excess: after a push inside the tile it goes on with the
-        // receiving pixel at once (and after a relabel with the same pixel), up to `chase` steps.  A step is one LDS round trip
-        // (~0.2 us) where a sweep is six (0.94 us), and in the sparse rounds a visit is mostly one or two units of excess
-        // walking across the tile.  Exclusivity: a lane TAKES a pixel's excess with an exchange (two lanes that meet on a pixel:
-        // one gets it all, the other gets zero and drops out) and gives back what it could not push.
+        // ---- one active pixel per lane.  A lane TAKES the pixel's excess with an exchange and gives back what it could not
+        // push, so what a neighbouring lane pushes into the pixel meanwhile is kept.  A pixel that keeps excess, or that a push
+        // inside the tile reaches, is looked at again in the next sweep.  (Chasing a unit of excess from pixel to pixel
+        // within a sweep, and parking pixels that only climb, were measured and removed: DESIGN.md 5.5.)
         for (int k0 = 0; k0 < n_act; k0 += 64) {
             int slot = k0 + lane < n_act ? (int)S.list[k0 + lane] : -1;
-            for (int step = 0; step < chase; ++step) {
-                if (!__any(slot >= 0)) break;
-                if (slot >= 0) {
-                    const int ly = slot >> 5, plx = slot & 31;
-                    const int e = atomicExch(&S.ex[slot], 0);
-                    const int dp = S.d[ly + 1][plx + 1];
-                    const int sk = S.sk[slot];
-                    int r[8], hq[8];
+            if (slot >= 0) {
+                const int ly = slot >> 5, plx = slot & 31;
+                const int e = atomicExch(&S.ex[slot], 0);
+                const int dp = S.d[ly + 1][plx + 1];
+                const int sk = S.sk[slot];
+                int r[8], hq[8];
+#pragma unroll
+                for (int dir = 0; dir < 8; ++dir) {
+                    r[dir] = __hip_atomic_load(&S.rc[dir][slot], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                    hq[dir] = S.d[ly + 1 + dir_dy(dir)][plx + 1 + dir_dx(dir)];
+                }
+                if (e <= 0) {
+                    slot = -1;                                         // nothing left
+                } else if (dp >= d.P) {
+                    atomicAdd(&S.ex[slot], e); slot = -1;              // cannot reach the sink: the excess stays where it is
+                } else {
+                    int hmin = sk > 0 ? 0 : DINF, best = sk > 0 ? 8 : -1, rb = 0;
 #pragma unroll
                     for (int dir = 0; dir < 8; ++dir) {
-                        r[dir] = __hip_atomic_load(&S.rc[dir][slot], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                        hq[dir] = S.d[ly + 1 + dir_dy(dir)][plx + 1 + dir_dx(dir)];
+                        const bool ok = r[dir] > 0 && hq[dir] < hmin;
+                        hmin = ok ? hq[dir] : hmin; best = ok ? dir : best; rb = ok ? r[dir] : rb;
                     }
-                    if (e <= 0) {
-                        slot = -1;                                     // taken by a lane that walked in, or nothing left
-                    } else if (dp >= d.P) {
-                        atomicAdd(&S.ex[slot], e); slot = -1;          // cannot reach the sink: the excess stays where it is
-                    } else {
-                        int hmin = sk > 0 ? 0 : DINF, best = sk > 0 ? 8 : -1, rb = 0;
-#pragma unroll
-                        for (int dir = 0; dir < 8; ++dir) {
-                            const bool ok = r[dir] > 0 && hq[dir] < hmin;
-                            hmin = ok ? hq[dir] : hmin; best = ok ? dir : best; rb = ok ? r[dir] : rb;
-                        }
-                        if (best >= 0 && dp > hmin) {
-                            S.streak[slot] = 0;
-                            if (best == 8) {
-                                const int dl = min(e, sk);
-                                S.sk[slot] = sk - dl;                  // only the holder of the pixel's excess touches its sink link
-                                if (e - dl > 0) atomicAdd(&S.ex[slot], e - dl); else slot = -1;   // sink link full: on to the neighbours
-                            } else {
-                                const int dl = min(e, rb), rem = e - dl;
-                                atomicSub(&S.rc[best][slot], dl);
-                                if (rem > 0) { atomicAdd(&S.ex[slot], rem); atomicOr(&S.mask[ly], 1u << plx); }   // the rest: next sweep
-                                const int qlx = plx + dir_dx(best), qly = ly + dir_dy(best);
-                                if (qlx >= 0 && qlx < 32 && qly >= 0 && qly < TH) {
-                                    const int qt = qly * 32 + qlx;
-                                    atomicAdd(&S.rc[best ^ 1][qt], dl);
-                                    atomicAdd(&S.ex[qt], dl);
-                                    slot = qt;                          // follow the flow
-                                } else {                                // across the tile edge: straight to memory
-                                    const int gy = tyi * TH + qly, gx = txi * 32 + qlx;
-                                    const size_t qg = base + (size_t)gy * d.W + gx;
-                                    atomicAdd(&rc[rc_idx((best ^ 1), qg)], dl);
-                                    atomicAdd(&ex[qg], dl);
-                                    const int tdy = qly < 0 ? -1 : (qly >= TH ? 1 : 0), tdx = qlx < 0 ? -1 : (qlx >= 32 ? 1 : 0);
-                                    nbm |= 1 << ((tdy + 1) * 3 + tdx + 1);
-                                    slot = rem > 0 ? slot : -1;
-                                }
-                            }
+                    if (best >= 0 && dp > hmin) {
+                        if (best == 8) {
+                            const int dl = min(e, sk);
+                            S.sk[slot] = sk - dl;                      // only the holder of the pixel's excess touches its sink link
+                            if (e - dl > 0) atomicAdd(&S.ex[slot], e - dl); else slot = -1;   // sink link full: on to the neighbours
                         } else {
-                            const int nd = (best >= 0 && hmin < DINF) ? hmin + 1 : DINF;
-                            S.d[ly + 1][plx + 1] = nd;
-                            atomicAdd(&S.ex[slot], e);                 // give it back; with the new label the next step can push
-                            // A pixel that only climbs — `park` relabels in a row without a push — is left alone for the rest of
-                            // this visit and does not keep the tile on the queue; the next global relabel gives it an exact label
-                            // (or none) and the active scan finds it again.  Off by default (GGC_MF_ASYNC_PARK, 255): measured
-                            // without effect at 2-6 — trapped excess does not climb in place, it is pushed back and forth between
-                            // the pixels of its pocket, every push resetting the streak.
-                            const int sr = S.streak[slot] + 1;
-                            S.streak[slot] = (unsigned char)min(sr, 255);
-                            if (nd >= d.P || sr >= park) slot = -1;
+                            const int dl = min(e, rb), rem = e - dl;
+                            atomicSub(&S.rc[best][slot], dl);
+                            if (rem > 0) { atomicAdd(&S.ex[slot], rem); atomicOr(&S.mask[ly], 1u << plx); }   // the rest: next sweep
+                            const int qlx = plx + dir_dx(best), qly = ly + dir_dy(best);
+                            if (qlx >= 0 && qlx < 32 && qly >= 0 && qly < TH) {
+                                const int qt = qly * 32 + qlx;
+                                atomicAdd(&S.rc[best ^ 1][qt], dl);
+                                atomicAdd(&S.ex[qt], dl);
+                                slot = qt;                              // the receiver: next sweep
+                            } else {                                    // across the tile edge: straight to memory
+                                const int gy = tyi * TH + qly, gx = txi * 32 + qlx;
+                                const size_t qg = base + (size_t)gy * d.W + gx;
+                                atomicAdd(&rc[rc_idx((best ^ 1), qg)], dl);
+                                atomicAdd(&ex[qg], dl);
+                                const int tdy = qly < 0 ? -1 : (qly >= TH ? 1 : 0), tdx = qlx < 0 ? -1 : (qlx >= 32 ? 1 : 0);
+                                nbm |= 1 << ((tdy + 1) * 3 + tdx + 1);
+                                slot = rem > 0 ? slot : -1;
+                            }
                         }
+                    } else {
+                        const int nd = (best >= 0 && hmin < DINF) ? hmin + 1 : DINF;
+                        S.d[ly + 1][plx + 1] = nd;
+                        atomicAdd(&S.ex[slot], e);                     // give it back; with the new label the next sweep can push
+                        if (nd >= d.P) slot = -1;
                     }
                 }
             }
-            if (slot >= 0) atomicOr(&S.mask[slot >> 5], 1u << (slot & 31));     // step limit: the pixel is looked at again next sweep
+            if (slot >= 0) atomicOr(&S.mask[slot >> 5], 1u << (slot & 31));
             mf_wave_sync();
         }
     }
@@ -410,7 +329,7 @@ __device__ int push_tile_visit(const GcDims& d, int tyi, int txi, int inner, int
         }
         if (sk1 != sk0[j]) atomicExch(&snk[p], sk1);
         // the label: compare with the halo copy's origin is not kept, so write when the pixel was relabelled (d only rises here)
-        left |= (e1 > 0 && d1 < d.P && S.streak[slot] < park) ? 1 : 0;
+        left |= (e1 > 0 && d1 < d.P) ? 1 : 0;
     }
     // labels: a pixel's label is written when it differs from what memory held at load time
 #pragma unroll
@@ -427,7 +346,7 @@ __device__ int push_tile_visit(const GcDims& d, int tyi, int txi, int inner, int
 }
 
 template <int TH>
-__global__ void __launch_bounds__(64) k_mf_push_async(GcDims d, int bt_x, int bt_y, int pt_y, int inner, int chase, int park, int gen_max, int follow, int32_t* __restrict__ dirty, int32_t* __restrict__ rc,
+__global__ void __launch_bounds__(64) k_mf_push_async(GcDims d, int bt_x, int bt_y, int pt_y, int inner, int gen_max, int32_t* __restrict__ dirty, int32_t* __restrict__ rc,
                                                       int32_t* __restrict__ ex, int32_t* __restrict__ snk, int32_t* __restrict__ dist,
                                                       uint8_t* __restrict__ rmask, int32_t* __restrict__ st, unsigned long long* __restrict__ ring,
                                                       int32_t* __restrict__ q, int cap, int32_t* __restrict__ err_flag,
@@ -462,7 +381,7 @@ __global__ void __launch_bounds__(64) k_mf_push_async(GcDims d, int bt_x, int bt
         const long long t_1 = prof ? wall_clock64() : 0;
         const int b = tile / tiles_per_image, tr = tile % tiles_per_image;
         const int tyi = tr / bt_x, txi = tr % bt_x;
-        const int nbm = push_tile_visit<TH>(d, tyi, txi, inner, chase, park, (size_t)b * d.P, BP, rc, ex, snk, dist, rmask, S, lane, prof != nullptr, pv);
+        const int nbm = push_tile_visit<TH>(d, tyi, txi, inner, (size_t)b * d.P, BP, rc, ex, snk, dist, rmask, S, lane, prof != nullptr, pv);
         drain();                                                           // the write-back is at memory
         const long long t_2 = prof ? wall_clock64() : 0;
         const bool left = (nbm >> 4) & 1;
@@ -488,8 +407,8 @@ __global__ void __launch_bounds__(64) k_mf_push_async(GcDims d, int bt_x, int bt
         int next = -1;
         if (cm) {
             const int fl = __ffsll((long long)cm) - 1;
-            if (follow) next = __shfl(nb, fl, 64);
-            if (cand && (lane != fl || !follow)) aq_push(ring, q, cap, ((gen + 1) << 24) | nb, err_flag);
+            next = __shfl(nb, fl, 64);                                     // follow the first, queue the others
+            if (cand && lane != fl) aq_push(ring, q, cap, ((gen + 1) << 24) | nb, err_flag);
             drain();
         }
         if (next < 0 && lane == 0) aq_finish(q);
@@ -541,21 +460,17 @@ int maxflow_push_async(ggc_ctx* ctx, hipStream_t st, const GcDims& d, const MfTi
     th = th >= 32 ? 32 : (th >= 16 ? 16 : 8);
     const int bt_x = tl.pt_x, bt_y = cdiv(d.H, th), cap = bt_x * bt_y * d.B;
     gen_max = std::min(gen_max, 127);
-    // Fixed after the round-2 measurements: the wave that finishes a visit FOLLOWS the front into one of the
-    // tiles it would have queued (74.6 -> 69.9 ms per stage); chasing a unit of excess inside a sweep (chase > 1) and
-    // parking pixels that only climb (park < 255) measured slower / without effect, so both stay off.
-    const int follow = 1, park = 255, chase = 1;
     mf_zero3(st, reinterpret_cast<int32_t*>(ring), (size_t)cap * 2, q, AQ_WORDS, state, (size_t)cap);
     hipLaunchKernelGGL(k_aq_fill_big, dim3(cdiv(n_list_max, 256)), dim3(256), 0, st, count, list, tl.pt_x, tl.pt_y, th, bt_x, bt_y, state, ring, q,
                        gen_max);
     if (th == 32)
-        hipLaunchKernelGGL(k_mf_push_async<32>, dim3(waves), dim3(64), 0, st, d, bt_x, bt_y, tl.pt_y, inner, chase, park, gen_max, follow, dirty, rc, ex, snk, dist, rmask, state, ring, q, cap,
+        hipLaunchKernelGGL(k_mf_push_async<32>, dim3(waves), dim3(64), 0, st, d, bt_x, bt_y, tl.pt_y, inner, gen_max, dirty, rc, ex, snk, dist, rmask, state, ring, q, cap,
                            err_flag, prof);
     else if (th == 8)
-        hipLaunchKernelGGL(k_mf_push_async<8>, dim3(waves), dim3(64), 0, st, d, bt_x, bt_y, tl.pt_y, inner, chase, park, gen_max, follow, dirty, rc, ex, snk, dist, rmask, state, ring, q, cap,
+        hipLaunchKernelGGL(k_mf_push_async<8>, dim3(waves), dim3(64), 0, st, d, bt_x, bt_y, tl.pt_y, inner, gen_max, dirty, rc, ex, snk, dist, rmask, state, ring, q, cap,
                            err_flag, prof);
     else
-        hipLaunchKernelGGL(k_mf_push_async<16>, dim3(waves), dim3(64), 0, st, d, bt_x, bt_y, tl.pt_y, inner, chase, park, gen_max, follow, dirty, rc, ex, snk, dist, rmask, state, ring, q, cap,
+        hipLaunchKernelGGL(k_mf_push_async<16>, dim3(waves), dim3(64), 0, st, d, bt_x, bt_y, tl.pt_y, inner, gen_max, dirty, rc, ex, snk, dist, rmask, state, ring, q, cap,
                            err_flag, prof);
     GGC_LAUNCH_CHECK(ctx);
     return GGC_OK;

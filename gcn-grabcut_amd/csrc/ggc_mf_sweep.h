@@ -1,5 +1,5 @@
-// ggc_mf_sweep.h — in-register relabel sweeps over a 32x32 tile of labels + halo in LDS, shared by the max-flow drivers
-// (ggc_maxflow.hip: work lists of the whole batch; ggc_maxflow_image.hip: one workgroup per image).
+// ggc_mf_sweep.h — the relabel visit of a 32x32 tile (labels + halo in LDS, in-register sweeps), shared by the work-list
+// launches of ggc_maxflow.hip and the asynchronous launch of ggc_maxflow_async.hip.
 #pragma once
 #include "ggc_gc.h"
 
@@ -9,11 +9,14 @@ __device__ __forceinline__ void mf_wave_sync() {     // LDS traffic of one wave 
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     __builtin_amdgcn_wave_barrier();
 }
+__device__ __forceinline__ int ldg(const int32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }   // sc1 load
 __device__ __forceinline__ int mf_wave_or(int v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v |= __shfl_xor(v, o, 64);
     return v;
 }
+
+struct RelaxWaveLds { int d[MF_RT + 2][MF_RT + 2]; uint32_t m[MF_RT][MF_RT / 4]; };   // one per wave
 
 // ---- relabel tile visit -----------------------------------------------------------------------------------------
 // d(p) = 1 + min over residual arcs p -> q of d(q), relaxed to the tile's fixpoint against a fixed halo.  A sweep where
@@ -26,12 +29,6 @@ __device__ __forceinline__ int gated(int v, uint32_t inv, int bit) {        // v
     return (__builtin_amdgcn_sbfe((int)inv, bit, 1) & DINF) | v;
 }
 __device__ __forceinline__ int min3i(int a, int b, int c) { return min(a, min(b, c)); }
-__device__ __forceinline__ int relax_px(int c, uint32_t inv, int pos, int lf, int rt, int up, int dn, int ul, int dr, int ur, int dl) {
-    const int nd = min3i(min3i(gated(lf, inv, pos), gated(rt, inv, pos + 1), gated(up, inv, pos + 2)),
-                         min3i(gated(dn, inv, pos + 3), gated(ul, inv, pos + 4), gated(dr, inv, pos + 5)),
-                         min(gated(ur, inv, pos + 6), gated(dl, inv, pos + 7)));
-    return min(c, nd + 1);
-}
 // Five neighbours instead of eight: a pass that walks in one direction looks at the three neighbours it comes from and the two
 // beside it; the opposite pass of the same sweep looks at the other three and the same two.  Together they cover all eight arcs,
 // so a sweep that changes nothing is still a fixpoint test, and the fixpoint (the exact distances) is the same — at 10 gated
@@ -101,9 +98,8 @@ __device__ __forceinline__ bool mf_tile_dirty(const int32_t* __restrict__ dirty,
     return __any(v != 0);
 }
 // after the row and column patches: the corrected mask bytes of the border pixels go back to rmask, the flags are cleared
-template <class RelaxTile>
 __device__ __forceinline__ void mf_tile_repair(const GcDims& d, const MfTiles& tl, uint8_t* __restrict__ rmask, int32_t* __restrict__ dirty,
-                                               const RelaxTile& S, size_t base, int b, int tyi, int txi, int ty0, int tx0, int lx, int h, int lane) {
+                                               const RelaxWaveLds& S, size_t base, int b, int tyi, int txi, int ty0, int tx0, int lx, int h, int lane) {
     const uint8_t* sm = reinterpret_cast<const uint8_t*>(&S.m[0][0]);
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
@@ -120,8 +116,7 @@ __device__ __forceinline__ void mf_tile_repair(const GcDims& d, const MfTiles& t
 }
 
 // lane = (column lx, half h): pixels (rows 16h .. 16h+15, column lx).  Returns 1 when a label changed.
-template <class RelaxTile>
-__device__ __forceinline__ int relax_sweep_v(RelaxTile& S, const uint32_t (&inv_in)[4], int lx, int h) {
+__device__ __forceinline__ int relax_sweep_v(RelaxWaveLds& S, const uint32_t (&inv_in)[4], int lx, int h) {
     // the per-arc gate words are loop invariants of the caller's sweep loop: hide the masks from the optimiser, or it hoists
     // 128 of them out of the loop and spills
     uint32_t inv[4] = {inv_in[0], inv_in[1], inv_in[2], inv_in[3]};
@@ -152,8 +147,7 @@ __device__ __forceinline__ int relax_sweep_v(RelaxTile& S, const uint32_t (&inv_
     return chg != 0u;
 }
 // lane = (row ly, half h): pixels (row ly, columns 16h .. 16h+15)
-template <class RelaxTile>
-__device__ __forceinline__ int relax_sweep_h(RelaxTile& S, const uint32_t (&inv_in)[4], int ly, int h) {
+__device__ __forceinline__ int relax_sweep_h(RelaxWaveLds& S, const uint32_t (&inv_in)[4], int ly, int h) {
     uint32_t inv[4] = {inv_in[0], inv_in[1], inv_in[2], inv_in[3]};
     asm volatile("" : "+v"(inv[0]), "+v"(inv[1]), "+v"(inv[2]), "+v"(inv[3]));
     int w[3][18];
@@ -180,6 +174,107 @@ __device__ __forceinline__ int relax_sweep_h(RelaxTile& S, const uint32_t (&inv_
     for (int k = 0; k < 16; ++k)
         if ((chg >> k) & 1u) S.d[ly + 1][16 * h + k + 1] = w[1][k + 1];
     return chg != 0u;
+}
+
+// GGC_MF_TRACE: the phases of a wave's relabel visits in wall_clock64 ticks, kept in registers (PROF = false: nothing).
+// The kernel stamps the start of a visit (begin) and adds the visit up after its hand-over (end); mf_relax_visit stamps the sweeps.
+template <bool PROF>
+struct MfRelaxClocks {
+    long long t0 = 0, t1 = 0, t2 = 0;      // this visit: start, first sweep, end of the sweeps
+    int n_sw = 0;                          // this visit's sweeps
+    long long sum[5] = {0, 0, 0, 0, 0};    // load + fill, sweeps, write-back + hand-over, visits, sweeps
+    __device__ __forceinline__ long long now() const { return PROF ? wall_clock64() : 0; }
+    __device__ __forceinline__ void begin() { t0 = now(); n_sw = 0; }
+    __device__ __forceinline__ void end() {
+        if (PROF) { sum[0] += t1 - t0; sum[1] += t2 - t1; sum[2] += wall_clock64() - t2; sum[3] += 1; sum[4] += n_sw; }
+    }
+};
+
+// One wave relabels the 32x32 tile `tile`: labels of tile + halo and arc masks to LDS (border arcs of a dirty tile re-read
+// and repaired), V and H sweeps to the tile's fixpoint, changed labels back to dist.  Returns, in every lane, the 9-bit mask
+// of the tiles whose halo changed, bit (dy + 1) * 3 + (dx + 1), with bit 4 when the sweeps stopped short of the fixpoint.
+//   ASYNC = false (k_mf_relax_wave, launches over work lists): plain loads and stores of dist, which the kernel boundaries
+//           order; the visit consumes the tile's membership flag itself once its loads are issued.
+//   ASYNC = true (k_mf_relax_async, one launch for the whole front): labels are read with sc1 loads and lowered with a
+//           device-scope atomicMin (ggc_maxflow_async.hip); the caller consumes the flag when it pops the tile.
+template <bool ASYNC, bool PROF>
+__device__ __forceinline__ int mf_relax_visit(const GcDims& d, const MfTiles& tl, int tile, int lane, RelaxWaveLds& S,
+                                              uint8_t* rmask, int32_t* dirty, const int32_t* rc,
+                                              int32_t* dist, int32_t* flag, MfRelaxClocks<PROF>& ck) {
+    constexpr int T = MF_RT, N_HALO = (T + 2) * (T + 2), HALO_IT = (N_HALO + 63) / 64;
+    int* sd = &S.d[0][0];
+    uint8_t* sm = reinterpret_cast<uint8_t*>(&S.m[0][0]);
+    const int tiles_per_image = tl.rt_x * tl.rt_y;
+    const int b = tile / tiles_per_image, tr = tile % tiles_per_image;
+    const int tyi = tr / tl.rt_x, txi = tr % tl.rt_x;
+    const int tx0 = txi * T, ty0 = tyi * T;
+    const size_t base = (size_t)b * d.P, BP = (size_t)d.B * d.P;
+    const int lx = lane & 31, h = lane >> 5;
+    int hv[HALO_IT];
+#pragma unroll
+    for (int k = 0; k < HALO_IT; ++k) {                                    // unconditional loads from clamped addresses
+        const int i = min(lane + k * 64, N_HALO - 1);
+        const int gy = ty0 + i / (T + 2) - 1, gx = tx0 + i % (T + 2) - 1;
+        const int32_t* p = &dist[base + (size_t)min(max(gy, 0), d.H - 1) * d.W + min(max(gx, 0), d.W - 1)];
+        hv[k] = ASYNC ? ldg(p) : *p;
+    }
+    uint32_t mv[16];
+#pragma unroll
+    for (int r = 0; r < 16; ++r)                                           // arc masks do not change during a relabel: plain loads
+        mv[r] = rmask[base + (size_t)min(ty0 + 16 * h + r, d.H - 1) * d.W + min(tx0 + lx, d.W - 1)];
+    const bool dirty_t = mf_tile_dirty(dirty, tl, b, tyi, txi, lane);      // wave-uniform: a neighbour pushed into one of its push tiles
+    MfBorderArcs ba;                                                       // (capacities do not change during a relabel either)
+    if (dirty_t) ba.load(d, rc, BP, base, ty0, tx0, lx, h);
+    if (!ASYNC && lane == 0) flag[tile] = 0;                               // consumed
+    uint32_t inv_v[4] = {0u, 0u, 0u, 0u}, inv_h[4];                        // bit set = no arc; outside the image: all blocked
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        uint32_t m = ~mv[r] & 0xffu;
+        if (dirty_t) m = ba.row(m, r);
+        sm[(16 * h + r) * T + lx] = (uint8_t)((tx0 + lx < d.W && ty0 + 16 * h + r < d.H) ? m : 0xffu);
+    }
+#pragma unroll
+    for (int k = 0; k < HALO_IT; ++k) {
+        const int i = lane + k * 64;
+        const int gy = ty0 + i / (T + 2) - 1, gx = tx0 + i % (T + 2) - 1;
+        if (i < N_HALO) sd[i] = (gx >= 0 && gx < d.W && gy >= 0 && gy < d.H) ? hv[k] : DINF;
+    }
+    mf_wave_sync();
+    if (dirty_t) {      // (a second wave relaxing the same tile meanwhile writes the same bytes)
+        if (ty0 + lx < d.H && tx0 + (h ? 31 : 0) < d.W) sm[lx * T + (h ? 31 : 0)] = (uint8_t)ba.col(sm[lx * T + (h ? 31 : 0)], h);
+        mf_wave_sync();
+        mf_tile_repair(d, tl, rmask, dirty, S, base, b, tyi, txi, ty0, tx0, lx, h, lane);
+    }
+#pragma unroll
+    for (int r = 0; r < 16; ++r) inv_v[r >> 2] |= (uint32_t)sm[(16 * h + r) * T + lx] << (8 * (r & 3));
+#pragma unroll
+    for (int k = 0; k < 4; ++k) inv_h[k] = S.m[lx][4 * h + k];             // H sweep: row lx, columns 16h .. 16h+15
+    int old[16];
+#pragma unroll
+    for (int r = 0; r < 16; ++r) old[r] = S.d[16 * h + r + 1][lx + 1];
+    bool settled = false;
+    ck.t1 = ck.now();
+    for (int it = 0; it < 4 * T; ++it) {   // a sweep pair that changes nothing: fixpoint (a visit capped at 2-6 sweeps and re-queued
+                                           // publishes its border earlier, but costs more visits: 56.4 -> 60.3 / 58.1 / 56.6 ms)
+        const int ch = (it & 1) ? relax_sweep_h(S, inv_h, lx, h) : relax_sweep_v(S, inv_v, lx, h);
+        mf_wave_sync();
+        if (PROF) ++ck.n_sw;
+        if (!__any(ch)) { settled = true; break; }
+    }
+    ck.t2 = ck.now();
+    int nbm = settled ? 0 : 1 << 4;                                        // bit (dy + 1) * 3 + (dx + 1)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        const int ly = 16 * h + r;
+        const int v = S.d[ly + 1][lx + 1];
+        if (v != old[r]) {                                                 // (pixels outside the image never change: all arcs blocked)
+            int32_t* p = &dist[base + (size_t)(ty0 + ly) * d.W + tx0 + lx];
+            if (ASYNC) atomicMin(p, v); else *p = v;                       // (asynchronous: labels only fall)
+            const int Lf = lx == 0, Rt = lx == T - 1, U = ly == 0, D = ly == T - 1;
+            nbm |= (U & Lf) | U << 1 | (U & Rt) << 2 | Lf << 3 | Rt << 5 | (D & Lf) << 6 | D << 7 | (D & Rt) << 8;
+        }
+    }
+    return mf_wave_or(nbm);
 }
 
 } // namespace ggc

@@ -27,7 +27,6 @@
  * result — tests/test_maxflow_variants_gpu.py holds the max-flow ones to that):
  *   GGC_MF_TRACE=1                per-round max-flow diagnostics on stderr (blocking)
  *   GGC_MF_WARM=0                 cold max-flow start in every GrabCut iteration (default 1: keep the n-link flow)
- *   GGC_MF_ASYNC=0                host-driven work lists only (default 1: sparse phases as one asynchronous launch each)
  *   GGC_MF_ASYNC_PUSH_ACTIVE=n    push rounds with <= n active pixels run asynchronously (10000)
  *   GGC_MF_ASYNC_TILE=8|16|32     rows of the asynchronous push tile (8)
  *   GGC_MF_ASYNC_HOPS=n           longest chain of tile visits in an asynchronous push launch (24)

@@ -1,7 +1,7 @@
 """Every schedule of the max-flow gives the oracle's masks.
 
-The cut of an integer network is canonical, so who drives the rounds (host work lists or asynchronous single-launch
-phases), how long a round is and whether the flow of the previous GrabCut iteration is kept must not change a single
+The cut of an integer network is canonical, so which phases run as asynchronous single launches, how long a round is,
+whether the flow of the previous GrabCut iteration is kept and whether the per-round trace is on must not change a single
 pixel.  The switches are the documented GGC_MF_* variables of include/ggc.h, which the library reads ONCE per process,
 so each variant runs in its own interpreter (one at a time: a GPU box admits few processes on its card)."""
 import os
@@ -46,7 +46,6 @@ print("variant ok")
 
 VARIANTS = {
     "async_default": {},
-    "host_work_lists": {"GGC_MF_ASYNC": "0"},
     "exact_relabel_every_round": {"GGC_MF_PARTIAL_ROUNDS": "0", "GGC_MF_RELAX_DENSE": "2"},
     "partial_relabels_for_long": {"GGC_MF_PARTIAL_ROUNDS": "9", "GGC_MF_RELAX_DENSE": "1"},
     "cold_start_every_iteration": {"GGC_MF_WARM": "0"},
@@ -54,6 +53,7 @@ VARIANTS = {
     "async_tiles_32x16": {"GGC_MF_ASYNC_TILE": "16", "GGC_MF_ASYNC_SWEEPS": "16"},
     "async_tiles_32x32_short_chains": {"GGC_MF_ASYNC_TILE": "32", "GGC_MF_ASYNC_HOPS": "8"},
     "short_dense_rounds": {"GGC_MF_DENSE_LAUNCHES0": "3", "GGC_MF_DENSE_LAUNCHES": "2", "GGC_MF_DENSE_SWEEPS": "4", "GGC_MF_RELAX_DENSE": "4"},
+    "trace": {"GGC_MF_TRACE": "1"},                   # the clocked relabel kernel and the per-round readout
 }
 
 
@@ -63,3 +63,5 @@ def test_driver_variant_matches_oracle(name, oracle):
     env.update(VARIANTS[name])
     r = subprocess.run([sys.executable, "-c", CHILD.format(root=str(ROOT))], env=env, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0 and "variant ok" in r.stdout, f"{name}: rc {r.returncode}\n{r.stdout[-2000:]}\n{r.stderr[-4000:]}"
+    if "GGC_MF_TRACE" in VARIANTS[name]:
+        assert "[ggc maxflow] round" in r.stderr, f"{name}: no trace on stderr\n{r.stderr[-4000:]}"
