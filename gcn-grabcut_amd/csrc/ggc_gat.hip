@@ -7,7 +7,7 @@
 // incoming edge attributes (fill_value="mean"); for an edge j -> i and head h
 //     m = leaky_relu(x_r[i] + x_l[j] + lin_edge(e_ij), 0.2);   a = att[h] . m[h];   alpha = softmax over the edges into i
 //     out_i[h] = sum_j alpha_ij x_l[j][h];   concat heads, + bias.
-// One wave per destination node (lane l holds channels l, l + 64): the per-head dot product is a butterfly over the head's
+// One wave per destination node (lane l holds channels l + 64 j): the per-head dot product is a butterfly over the head's
 // C = D / heads consecutive lanes; the softmax is two passes over the node's incoming edges in CSR (= edge) order, the
 // self loop last.  LayerNorm + GELU of the block are fused in (the wave holds the whole output row).  The per-block edge
 // gate is the fused MFMA kernel of GCNTrimapNet with a multiply-only epilogue; the D x D products run on k_gemm.
@@ -62,8 +62,8 @@ __global__ void __launch_bounds__(256) k_gat_attn(int N, const int32_t* __restri
                                                   const float* __restrict__ xl, const float* __restrict__ xr, GatW w,
                                                   float* __restrict__ out) {
     constexpr int NC = (D + 63) / 64, C = D / HEADS;          // a head is C consecutive channels: C <= 64 consecutive lanes of one
-                                                              // register, or (C = 128: D = 128, one head) all lanes of both
-    static_assert(C >= 4 && (C & (C - 1)) == 0 && (C <= 64 || (C == 128 && NC == 2)), "head width: a power of two from 4 to 128");
+                                                              // register, or (C > 64) all lanes of C / 64 consecutive registers
+    static_assert(C >= 4 && (C & (C - 1)) == 0 && (C <= 64 || C % 64 == 0), "head width: a power of two from 4 to 256");
     const int lane = threadIdx.x & 63;
     const int wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, n_waves = (gridDim.x * blockDim.x) >> 6;
     float bl[NC], att[NC], we[NC][EDGE_CH];
@@ -107,7 +107,18 @@ __global__ void __launch_bounds__(256) k_gat_attn(int N, const int32_t* __restri
                 for (int o = (C < 64 ? C : 64) / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
                 lg[j] = v;
             }
-            if (C == 128) { const float t = lg[0] + lg[NC - 1]; lg[0] = t; lg[NC - 1] = t; }     // one head across both registers: low half + high half
+            if (C == 128 && NC == 2) { const float t = lg[0] + lg[NC - 1]; lg[0] = t; lg[NC - 1] = t; }     // one head across both registers: low half + high half
+            if constexpr (C > 64 && NC > 2) {                 // D = 256: a head spans R registers, their partial sums added in order
+                constexpr int R = C / 64;
+#pragma unroll
+                for (int j0 = 0; j0 < NC; j0 += R) {
+                    float t = lg[j0];
+#pragma unroll
+                    for (int r = 1; r < R; ++r) t += lg[j0 + r];
+#pragma unroll
+                    for (int r = 0; r < R; ++r) lg[j0 + r] = t;
+                }
+            }
         };
         float mx[NC], lgs[NC];
         logit(am, xli, lgs);                                   // self loop
@@ -286,8 +297,8 @@ extern "C" {
 
 int ggc_gat_configure(ggc_ctx* ctx, int hidden, int n_heads, int n_layers) {
     if (!ctx) return GGC_E_INVALID_ARG;
-    GGC_REQUIRE(ctx, hidden == 32 || hidden == 64 || hidden == 128, GGC_E_UNSUPPORTED,
-                "hidden_channels=%d unsupported: GATTrimapNet runs at 32, 64 or 128 (a head must span a power-of-two number of lanes)", hidden);
+    GGC_REQUIRE(ctx, hidden == 32 || hidden == 64 || hidden == 128 || hidden == 256, GGC_E_UNSUPPORTED,
+                "hidden_channels=%d unsupported: GATTrimapNet runs at 32, 64, 128 or 256 (a head must span a power-of-two number of lanes)", hidden);
     GGC_REQUIRE(ctx, n_heads == 1 || n_heads == 2 || n_heads == 4 || n_heads == 8, GGC_E_UNSUPPORTED,
                 "n_heads=%d unsupported: 1, 2, 4 or 8 (the reference's default is 8)", n_heads);
     if (int rc = configure(ctx, GAT, hidden, hidden, n_layers)) return rc;
@@ -306,7 +317,7 @@ int ggc_gat_forward(ggc_ctx* ctx, ggc_stream stream, int G, int N, int E, const 
     int rc = begin_forward(ctx, GAT, G, N, E, x, edge_src, edge_dst, edge_attr, node_ptr, logits, probs);
     if (rc) return rc;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if (with_width<32, 64, 128>(ctx->gat.D, rc, [&](auto w) {
+    if (with_width<32, 64, 128, 256>(ctx->gat.D, rc, [&](auto w) {
             return forward_gat_t<decltype(w)::value>(ctx, st, G, N, E, x, edge_src, edge_dst, edge_attr, node_ptr, logits, probs); }))
         return rc;
     return set_err(ctx, GGC_E_STATE, "model not configured");

@@ -107,13 +107,17 @@ __global__ void __launch_bounds__(64 * EG_WAVES) k_gn_edge_gate(int N, const int
                                                                 const float* __restrict__ b2, const float* __restrict__ conv, BnW bn,
                                                                 const float* __restrict__ h, float* __restrict__ out) {
     constexpr int T = D / 32, KH = D / 2;
-    extern __shared__ float4 eg_smem4[];                       // W2 packed [D*D] | W1T [5][D] | b1 [D] | per wave stage [32][EG_STAGE]
-    float* s_w1 = reinterpret_cast<float*>(eg_smem4) + (size_t)D * D;
+    // Above 128 the packed W2 (256 KiB at 256) does not fit the LDS: the MFMA loop reads its B fragments from memory (W2 stays
+    // in L2), and the A operand is generated four k-steps at a time next to them, in the same k order.
+    constexpr bool W2_LDS = D <= 128;
+    extern __shared__ float4 eg_smem4[];                       // W2 packed [D*D] (D <= 128) | W1T [5][D] | b1 [D] | per wave stage [32][EG_STAGE]
+    float* s_w1 = reinterpret_cast<float*>(eg_smem4) + (W2_LDS ? (size_t)D * D : 0);
     float* s_b1 = s_w1 + EDGE_CH * D;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     float* stage = s_b1 + D + (size_t)wave * 32 * EG_STAGE;
     const int hk = lane >> 5, li = lane & 31;
-    for (int i = tid; i < D * D / 4; i += 64 * EG_WAVES) eg_smem4[i] = reinterpret_cast<const float4*>(w2p)[i];
+    if constexpr (W2_LDS)
+        for (int i = tid; i < D * D / 4; i += 64 * EG_WAVES) eg_smem4[i] = reinterpret_cast<const float4*>(w2p)[i];
     for (int i = tid; i < EDGE_CH * D; i += 64 * EG_WAVES) s_w1[i] = w1T[i];
     for (int i = tid; i < D; i += 64 * EG_WAVES) s_b1[i] = b1[i];
     __syncthreads();
@@ -166,7 +170,7 @@ __global__ void __launch_bounds__(64 * EG_WAVES) k_gn_edge_gate(int N, const int
         if (base + 32 < e1) fetch(base + 32);
         float a[KH];
 #pragma unroll
-        for (int s = 0; s < KH; s += 4) {                       // four values at a time on the packed-f32 pipe, same op order
+        for (int s = 0; s < (W2_LDS ? KH : 0); s += 4) {       // four values at a time on the packed-f32 pipe, same op order
             const int c = hk * KH + s;
             v4f acc4 = 0.0f;
 #pragma unroll
@@ -180,6 +184,7 @@ __global__ void __launch_bounds__(64 * EG_WAVES) k_gn_edge_gate(int N, const int
         for (int t = 0; t < T; ++t)
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[t][r] = 0.0f;
+        if constexpr (W2_LDS) {
 #pragma unroll
         for (int s4 = 0; s4 < KH / 4; ++s4) {
 #pragma unroll
@@ -189,6 +194,27 @@ __global__ void __launch_bounds__(64 * EG_WAVES) k_gn_edge_gate(int N, const int
                 acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[4 * s4 + 1], b.y, acc[t], 0, 0, 0);
                 acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[4 * s4 + 2], b.z, acc[t], 0, 0, 0);
                 acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[4 * s4 + 3], b.w, acc[t], 0, 0, 0);
+            }
+        }
+        } else {
+            const float4* w2p4 = reinterpret_cast<const float4*>(w2p);
+#pragma unroll 1
+            for (int s4 = 0; s4 < KH / 4; ++s4) {
+                const int c = hk * KH + 4 * s4;
+                v4f acc4 = 0.0f;
+#pragma unroll
+                for (int k = 0; k < EDGE_CH; ++k) acc4 += ea[k] * *reinterpret_cast<const v4f*>(s_w1 + k * D + c);
+                acc4 += *reinterpret_cast<const v4f*>(s_b1 + c);
+                const float a0 = (have && acc4.x > 0.0f) ? acc4.x : 0.0f, a1 = (have && acc4.y > 0.0f) ? acc4.y : 0.0f;
+                const float a2 = (have && acc4.z > 0.0f) ? acc4.z : 0.0f, a3 = (have && acc4.w > 0.0f) ? acc4.w : 0.0f;
+#pragma unroll
+                for (int t = 0; t < T; ++t) {
+                    const float4 b = w2p4[(s4 * T + t) * 64 + lane];
+                    acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b.x, acc[t], 0, 0, 0);
+                    acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b.y, acc[t], 0, 0, 0);
+                    acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(a2, b.z, acc[t], 0, 0, 0);
+                    acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(a3, b.w, acc[t], 0, 0, 0);
+                }
             }
         }
         const int n_rows = min(32, e1 - base);
@@ -247,7 +273,7 @@ template <int D, bool MUL_ONLY>
 int launch_edge_gate(ggc_ctx* ctx, hipStream_t st, int N, const int32_t* row_ptr, const int32_t* eid, const int32_t* csr_dst,
                             const float* edge_attr, const float* w1T, const float* b1, const float* w2p, const float* b2,
                             const float* conv, const BnW& bn, const float* h, float* out) {
-    const size_t lds = ((size_t)D * D + (size_t)EDGE_CH * D + D + (size_t)EG_WAVES * 32 * EG_STAGE) * sizeof(float);
+    const size_t lds = ((D <= 128 ? (size_t)D * D : 0) + (size_t)EDGE_CH * D + D + (size_t)EG_WAVES * 32 * EG_STAGE) * sizeof(float);
     static DeviceOnce attr_set;
     if (attr_set.need(ctx->device)) {
         GGC_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gn_edge_gate<D, MUL_ONLY>), hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -263,7 +289,7 @@ int launch_edge_gate(ggc_ctx* ctx, hipStream_t st, int N, const int32_t* row_ptr
 // the widths GATTrimapNet (ggc_gat.hip) runs the multiply-only gate at
 #define GGC_EDGE_GATE(D) template int launch_edge_gate<D, true>(ggc_ctx*, hipStream_t, int, const int32_t*, const int32_t*, \
     const int32_t*, const float*, const float*, const float*, const float*, const float*, const float*, const BnW&, const float*, float*);
-GGC_EDGE_GATE(32) GGC_EDGE_GATE(64) GGC_EDGE_GATE(128)
+GGC_EDGE_GATE(32) GGC_EDGE_GATE(64) GGC_EDGE_GATE(128) GGC_EDGE_GATE(256)
 #undef GGC_EDGE_GATE
 
 static std::vector<Need> needed_gcnnet(const WeightSet& m) {

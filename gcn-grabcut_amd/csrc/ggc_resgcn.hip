@@ -4,6 +4,7 @@
 // Kernel map:
 //   k_input        M1  BatchNorm-eval -> Linear 19->D -> LayerNorm -> GELU -> prior booster
 //   k_edge_gate    M2  EdgeContext: edge MLP, mean over incoming edges, LN, Linear, sigmoid
+//                      (k_edge_gate_wide above D = 128: two context channels per lane, one gate column half per block)
 //   k_gemm<.,0>    M3  LayerNorm(h) @ W^T on f32 MFMA (v_mfma_f32_32x32x2_f32)
 //   k_aggregate<.,0>  M3  GCNConv scatter-gather over the destination CSR with the
 //                      fused epilogue h + gelu((agg + b) * gate)       <- graded kernel
@@ -352,6 +353,143 @@ __global__ void __launch_bounds__(256) k_edge_gate(int N, const int32_t* __restr
     }
 }
 
+// k_edge_gate at D > 128, where C = D/2 reaches 128 and the two matrices (C*C + C*D floats, 192 KiB at D = 256) no longer
+// fit the LDS: a lane owns context channels lane and lane + 64, and a block computes one column half of the gate (blockIdx
+// parity), so it stages w2T and that half of wgT (128 KiB at D = 256).  The two blocks of a node group both run the edge
+// MLP, the mean and the LayerNorm.  Each output is still its products added in k order from zero, bias last.  With one
+// block per CU at D = 256, the block is 16 waves (EGW_THREADS) so that the CU has work to switch between.
+constexpr int EGW_THREADS = 1024;
+template <int D>
+__global__ void __launch_bounds__(EGW_THREADS) k_edge_gate_wide(int N, const int32_t* __restrict__ row_ptr,
+                                                        const int32_t* __restrict__ eid,
+                                                        const float* __restrict__ edge_attr, EdgeW w, int C,
+                                                        float* __restrict__ gate) {
+    constexpr int DH = D / 2, NC = (DH + 63) / 64;
+    static_assert(D > 128 && D <= 256, "the wide form is built for 160 ... 256");
+    extern __shared__ float s_w[];                  // w2T [C][C] | wgT[:, half] [C][DH]
+    const int c_off = (blockIdx.x & 1) * DH;
+    float* s_w2 = s_w;
+    float* s_wg = s_w + C * C;
+    for (int i = threadIdx.x; i < C * C; i += EGW_THREADS) s_w2[i] = w.w2T[i];
+    for (int i = threadIdx.x; i < C * DH; i += EGW_THREADS) s_wg[i] = w.wgT[(i / DH) * D + c_off + i % DH];
+    __syncthreads();
+    const int lane = threadIdx.x & 63;
+    const int wave = ((blockIdx.x >> 1) * blockDim.x + threadIdx.x) >> 6;
+    const int n_waves = ((gridDim.x >> 1) * blockDim.x) >> 6;
+    const int C0 = min(C, 64);                      // channels k < C0 live in register 0 of lane k, the rest in register 1
+    float w0[2][EDGE_CH], b0[2], b2[2], lw[2], lb[2];
+    bool have[2];
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        const int c = lane + 64 * h;
+        have[h] = c < C;
+#pragma unroll
+        for (int k = 0; k < EDGE_CH; ++k) w0[h][k] = have[h] ? w.w0[c * EDGE_CH + k] : 0.0f;
+        b0[h] = have[h] ? w.b0[c] : 0.0f; b2[h] = have[h] ? w.b2[c] : 0.0f;
+        lw[h] = have[h] ? w.ln_w[c] : 0.0f; lb[h] = have[h] ? w.ln_b[c] : 0.0f;
+    }
+    float bg[NC];
+#pragma unroll
+    for (int j = 0; j < NC; ++j) bg[j] = lane + 64 * j < DH ? w.bg[c_off + lane + 64 * j] : 0.0f;
+    for (int n0 = wave * EC_NODES; n0 < N; n0 += n_waves * EC_NODES) {
+        int rp[EC_NODES + 1];
+#pragma unroll
+        for (int r = 0; r <= EC_NODES; ++r) rp[r] = __builtin_amdgcn_readfirstlane(row_ptr[min(n0 + r, N)]);
+        float sum[EC_NODES][2];
+#pragma unroll
+        for (int r = 0; r < EC_NODES; ++r) sum[r][0] = sum[r][1] = 0.0f;
+        for (int chunk = rp[0]; chunk < rp[EC_NODES]; chunk += 64) {
+            const int p = chunk + lane;
+            float a[EDGE_CH];
+            {
+                const bool valid = p < rp[EC_NODES];
+                const size_t e = valid ? (size_t)eid[p] : 0;
+#pragma unroll
+                for (int k = 0; k < EDGE_CH; ++k) a[k] = valid ? edge_attr[e * EDGE_CH + k] : 0.0f;
+            }
+#pragma unroll
+            for (int r = 0; r < EC_NODES; ++r) {
+                const int q0 = max(rp[r], chunk) - chunk, q1 = min(rp[r + 1], chunk + 64) - chunk;
+                for (int q = q0; q < q1; ++q) {
+                    float ak[EDGE_CH];
+#pragma unroll
+                    for (int k = 0; k < EDGE_CH; ++k) ak[k] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(a[k]), q));
+#pragma unroll
+                    for (int h = 0; h < 2; ++h) {
+                        float acc = 0.0f;
+#pragma unroll
+                        for (int k = 0; k < EDGE_CH; ++k) acc += ak[k] * w0[h][k];
+                        sum[r][h] += gelu_f(acc + b0[h]);
+                    }
+                }
+            }
+        }
+        float m[EC_NODES][2];
+        int cnt[EC_NODES];
+#pragma unroll
+        for (int r = 0; r < EC_NODES; ++r) {
+            cnt[r] = rp[r + 1] - rp[r];
+#pragma unroll
+            for (int h = 0; h < 2; ++h) m[r][h] = sum[r][h] / (float)(cnt[r] > 0 ? cnt[r] : 1);
+        }
+        float acc[EC_NODES][2];
+#pragma unroll
+        for (int r = 0; r < EC_NODES; ++r) acc[r][0] = acc[r][1] = 0.0f;
+        for (int k = 0; k < C; ++k) {
+            const int kr = k < C0 ? 0 : 1, kl = k - 64 * kr;
+            float wk[2];
+#pragma unroll
+            for (int h = 0; h < 2; ++h) wk[h] = have[h] ? s_w2[k * C + lane + 64 * h] : 0.0f;
+#pragma unroll
+            for (int r = 0; r < EC_NODES; ++r) {
+                const float mk = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(kr ? m[r][1] : m[r][0]), kl));
+#pragma unroll
+                for (int h = 0; h < 2; ++h) acc[r][h] += mk * wk[h];
+            }
+        }
+        float ln[EC_NODES][2];
+#pragma unroll
+        for (int r = 0; r < EC_NODES; ++r) {
+            float cv[2];
+#pragma unroll
+            for (int h = 0; h < 2; ++h) cv[h] = (have[h] && cnt[r] > 0) ? acc[r][h] + b2[h] : 0.0f;
+            const float mean = wave_sum(cv[0] + cv[1]) / (float)C;
+            float dv[2];
+#pragma unroll
+            for (int h = 0; h < 2; ++h) dv[h] = have[h] ? cv[h] - mean : 0.0f;
+            const float rstd = 1.0f / sqrtf(wave_sum(dv[0] * dv[0] + dv[1] * dv[1]) / (float)C + 1e-5f);
+#pragma unroll
+            for (int h = 0; h < 2; ++h) ln[r][h] = have[h] ? dv[h] * rstd * lw[h] + lb[h] : 0.0f;
+        }
+        float g[EC_NODES][NC];
+#pragma unroll
+        for (int r = 0; r < EC_NODES; ++r)
+#pragma unroll
+            for (int j = 0; j < NC; ++j) g[r][j] = 0.0f;
+        for (int k = 0; k < C; ++k) {
+            const int kr = k < C0 ? 0 : 1, kl = k - 64 * kr;
+            float wk[NC];
+#pragma unroll
+            for (int j = 0; j < NC; ++j) wk[j] = lane + 64 * j < DH ? s_wg[k * DH + lane + 64 * j] : 0.0f;
+#pragma unroll
+            for (int r = 0; r < EC_NODES; ++r) {
+                const float lk = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(kr ? ln[r][1] : ln[r][0]), kl));
+#pragma unroll
+                for (int j = 0; j < NC; ++j) g[r][j] += lk * wk[j];
+            }
+        }
+#pragma unroll
+        for (int r = 0; r < EC_NODES; ++r) {
+            if (n0 + r >= N) break;
+#pragma unroll
+            for (int j = 0; j < NC; ++j) {
+                const int c = lane + 64 * j;
+                if (c < DH) gate[(size_t)(n0 + r) * D + c_off + c] = sigmoid_f(g[r][j] + bg[j]);
+            }
+        }
+    }
+}
+
 // ---------------------------------------------------------- M3/M4/M7: MFMA GEMM
 // out[N,D] = op(A)[N,D] @ W^T, f32 in / f32 accumulate on v_mfma_f32_32x32x2_f32.
 // A block is 4 waves; each wave owns 32 rows x D columns (T = D/32 accumulator
@@ -387,6 +525,7 @@ __global__ void __launch_bounds__(256) k_gemm(int N, GemmArgs g) {
         for (int r = 0; r < 16; ++r) acc[t][r] = 0.0f;
 
     constexpr int PHASES = (MODE == 1) ? 2 : 1;
+    if constexpr (D <= 128) {
 #pragma unroll
     for (int ph = 0; ph < PHASES; ++ph) {
         const float* Wp = ph ? g.Wp2 : g.Wp1;
@@ -462,6 +601,85 @@ __global__ void __launch_bounds__(256) k_gemm(int N, GemmArgs g) {
 #pragma unroll
                 for (int t = 0; t < T; ++t)
                     acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[4 * s4 + j], bq[t][j], acc[t], 0, 0, 0);
+        }
+    }
+    } else {
+        // D > 128: the packed W (100-256 KiB) no longer fits the LDS whole, and a lane cannot hold its KH-float half-row
+        // beside T accumulators.  W is staged KC k-steps at a time (its packed form is k-major, so a chunk is contiguous)
+        // and the row is read chunk by chunk; the LayerNorm statistics take a pass over the row first.  Every output
+        // still sees its products in the same k order.
+        constexpr int KC = 16, NCH = KH / KC, WQ = KC * T / 16;           // k-steps per chunk, chunks, float4 per thread
+        static_assert(KH % KC == 0, "KH must be a multiple of the chunk");
+        const float* gv = nullptr;
+        if (MODE == 2 || MODE == 4) gv = g.gvec + (size_t)g.batch[row] * D + hk * KH;
+        float mean = 0.0f, rstd = 1.0f;
+        const int dt = g.Dt > 0 ? g.Dt : D, nv = min(max(dt - hk * KH, 0), KH);
+        if (MODE == 0 || MODE == 2) {
+            const float4* ar4 = reinterpret_cast<const float4*>(g.A1 + (size_t)row * D + hk * KH);
+            const float4* gv4 = reinterpret_cast<const float4*>(gv);
+            auto row4 = [&](int q) {                           // four channels of the (gated) row, in channel order
+                float4 v = ar4[q];
+                if (MODE == 2) { const float4 u = gv4[q]; v.x *= u.x; v.y *= u.y; v.z *= u.z; v.w *= u.w; }
+                return v;
+            };
+            float s1 = 0.0f;
+#pragma unroll 2
+            for (int q = 0; q < KH / 4; ++q) { const float4 v = row4(q); s1 += v.x; s1 += v.y; s1 += v.z; s1 += v.w; }
+            s1 += __shfl_xor(s1, 32, 64);
+            mean = s1 / (float)dt;
+            float s2 = 0.0f;
+#pragma unroll 2
+            for (int q = 0; q < KH / 4; ++q) {
+                const float4 v = row4(q);
+                const float e[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+                for (int u = 0; u < 4; ++u) { const float d = e[u] - mean; s2 += (4 * q + u < nv) ? d * d : 0.0f; }
+            }
+            s2 += __shfl_xor(s2, 32, 64);
+            rstd = 1.0f / sqrtf(s2 / (float)dt + 1e-5f);
+        }
+        for (int ph = 0; ph < PHASES; ++ph) {
+            const float4* Wp4 = reinterpret_cast<const float4*>(ph ? g.Wp2 : g.Wp1);
+            const float4* ap = reinterpret_cast<const float4*>((ph ? g.A2 : g.A1) + (size_t)row * D + hk * KH);
+            for (int c = 0; c < NCH; ++c) {
+                float4 av[KC / 4];
+#pragma unroll
+                for (int q = 0; q < KC / 4; ++q) av[q] = ap[c * (KC / 4) + q];
+                __syncthreads();                                            // the previous chunk has been read
+#pragma unroll
+                for (int q = 0; q < WQ; ++q) smem4[tid + q * 256] = Wp4[(size_t)c * WQ * 256 + tid + q * 256];
+                __syncthreads();
+                float a[KC];
+#pragma unroll
+                for (int q = 0; q < KC / 4; ++q) {
+                    const float4 v = av[q];
+                    a[4 * q + 0] = v.x; a[4 * q + 1] = v.y; a[4 * q + 2] = v.z; a[4 * q + 3] = v.w;
+                }
+                if (MODE == 2 || MODE == 4) {
+#pragma unroll
+                    for (int s = 0; s < KC; ++s) a[s] *= gv[c * KC + s];
+                }
+                if (MODE == 0 || MODE == 2) {
+                    const float* lw = g.ln_w + hk * KH + c * KC;
+                    const float* lb = g.ln_b + hk * KH + c * KC;
+#pragma unroll
+                    for (int s = 0; s < KC; ++s) a[s] = (a[s] - mean) * rstd * lw[s] + lb[s];
+                }
+#pragma unroll
+                for (int s4 = 0; s4 < KC / 4; ++s4) {
+                    float bq[T][4];
+#pragma unroll
+                    for (int t = 0; t < T; ++t) {
+                        const float4 b = smem4[(s4 * T + t) * 64 + lane];
+                        bq[t][0] = b.x; bq[t][1] = b.y; bq[t][2] = b.z; bq[t][3] = b.w;
+                    }
+#pragma unroll
+                    for (int j = 0; j < 4; ++j)
+#pragma unroll
+                        for (int t = 0; t < T; ++t)
+                            acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[4 * s4 + j], bq[t][j], acc[t], 0, 0, 0);
+                }
+            }
         }
     }
 
@@ -576,7 +794,7 @@ __global__ void __launch_bounds__(256) k_gemm(int N, GemmArgs g) {
 //                     fused epilogue h + gelu(out * gate) when gate != null.
 //   MODE 1 (SAGE mean): out = sum xw[j] / max(cnt, 1).
 template <int D> struct AggCfg {
-    static constexpr int LPR = (D <= 32) ? 8 : (D <= 64) ? 16 : 32;
+    static constexpr int LPR = (D <= 32) ? 8 : (D <= 64) ? 16 : (D <= 128) ? 32 : 64;    // D > 128: a wave per row
     static constexpr int RPW = 64 / LPR;
     static constexpr int RPB = 4 * RPW;
 };
@@ -975,7 +1193,7 @@ __global__ void __launch_bounds__(256) k_graph_ctx(const int32_t* __restrict__ n
                                                    const float* __restrict__ hjk, CtxW w,
                                                    float* __restrict__ gvec) {
     constexpr int Dh = D / 2;
-    constexpr int NG = 256 / D;  // column groups (D <= 128 -> >= 2)
+    constexpr int NG = 256 / D;  // column groups (D <= 128 -> >= 2; above 128 one, threads tid >= D add nothing)
     __shared__ float red[256];
     __shared__ float gsum[D];
     __shared__ float cbuf[Dh];
@@ -1077,7 +1295,8 @@ static const NetSpec RESGCN{"ResGCNNet", "resgcn", &ggc_ctx::resgcn, true, neede
 template <int D, int MODE>
 int launch_gemm(ggc_ctx* ctx, hipStream_t st, int N, const GemmArgs& a) {
     static DeviceOnce attr_set;                    // per device; contexts may live on other host threads
-    const size_t lds = (size_t)D * D * sizeof(float);
+    // D > 128 stages W in chunks of 16 k-steps (k_gemm): T * 4 KiB
+    const size_t lds = D <= 128 ? (size_t)D * D * sizeof(float) : (size_t)(D / 32) * 4096;
     if (attr_set.need(ctx->device) && lds > 48 * 1024) {
         GGC_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gemm<D, MODE>),
                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -1200,15 +1419,15 @@ int prepare_csr(ggc_ctx* ctx, hipStream_t st, int G, int N, int E, const int32_t
 
 // the (D, MODE) pairs GCNTrimapNet (ggc_gcnnet.hip) and GATTrimapNet (ggc_gat.hip) launch
 #define GGC_GEMM(D, MODE) template int launch_gemm<D, MODE>(ggc_ctx*, hipStream_t, int, const GemmArgs&);
-GGC_GEMM(32, 3) GGC_GEMM(64, 3) GGC_GEMM(96, 3) GGC_GEMM(128, 3)
-GGC_GEMM(32, 4) GGC_GEMM(64, 4) GGC_GEMM(128, 4)
+GGC_GEMM(32, 3) GGC_GEMM(64, 3) GGC_GEMM(96, 3) GGC_GEMM(128, 3) GGC_GEMM(256, 3)
+GGC_GEMM(32, 4) GGC_GEMM(64, 4) GGC_GEMM(128, 4) GGC_GEMM(256, 4)
 #undef GGC_GEMM
 #define GGC_AGG(D) template int launch_aggregate<D, 0>(ggc_ctx*, hipStream_t, int, const float*, const int32_t*, const int32_t*, \
                                                        const float*, const float*, const float*, const float*, float*, const AggGraphs&);
 GGC_AGG(32) GGC_AGG(64) GGC_AGG(96) GGC_AGG(128)
 #undef GGC_AGG
 #define GGC_CTX(D) template int launch_graph_ctx<D>(ggc_ctx*, hipStream_t, int, const int32_t*, const float*, const float*, const CtxW&, float*);
-GGC_CTX(32) GGC_CTX(64) GGC_CTX(128)
+GGC_CTX(32) GGC_CTX(64) GGC_CTX(128) GGC_CTX(256)
 #undef GGC_CTX
 
 template <int D>
@@ -1248,9 +1467,21 @@ static int forward_t(ggc_ctx* ctx, hipStream_t st, int G, int N, int E, const fl
                 devp(m, "#edge_ctx.encode.2.weightT"), devp(m, "edge_ctx.encode.2.bias"),
                 devp(m, "edge_ctx.to_gate.0.weight"), devp(m, "edge_ctx.to_gate.0.bias"),
                 devp(m, "#edge_ctx.to_gate.1.weightT"), devp(m, "edge_ctx.to_gate.1.bias")};
-        const size_t eg_lds = sizeof(float) * ((size_t)m.C * m.C + (size_t)m.C * D);            // <= 48 KB (C <= 64, D <= 128)
-        hipLaunchKernelGGL((k_edge_gate<D>), dim3(min(cdiv(N, 4 * EC_NODES), 3 * ctx->n_cu)), dim3(256), eg_lds, st, N, csr.row_ptr, csr.eid,
-                           edge_attr, w, m.C, gate);
+        if constexpr (D <= 128) {
+            const size_t eg_lds = sizeof(float) * ((size_t)m.C * m.C + (size_t)m.C * D);            // <= 48 KB (C <= 64, D <= 128)
+            hipLaunchKernelGGL((k_edge_gate<D>), dim3(min(cdiv(N, 4 * EC_NODES), 3 * ctx->n_cu)), dim3(256), eg_lds, st, N, csr.row_ptr, csr.eid,
+                               edge_attr, w, m.C, gate);
+        } else {
+            const size_t eg_lds = sizeof(float) * ((size_t)m.C * m.C + (size_t)m.C * (D / 2));      // <= 128 KiB (C <= 128)
+            static DeviceOnce attr_set;
+            if (attr_set.need(ctx->device)) {
+                GGC_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_edge_gate_wide<D>),
+                                                 hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
+                attr_set.done(ctx->device);
+            }
+            hipLaunchKernelGGL((k_edge_gate_wide<D>), dim3(2 * min(cdiv(N, (EGW_THREADS / 64) * EC_NODES), ctx->n_cu)), dim3(EGW_THREADS), eg_lds, st, N,
+                               csr.row_ptr, csr.eid, edge_attr, w, m.C, gate);
+        }
         GGC_LAUNCH_CHECK(ctx);
     }
     for (int l = 0; l < n; ++l) {
@@ -1305,8 +1536,8 @@ extern "C" {
 
 int ggc_resgcn_configure(ggc_ctx* ctx, int hidden, int n_layers) {
     if (!ctx) return GGC_E_INVALID_ARG;
-    GGC_REQUIRE(ctx, hidden >= 8 && hidden <= 128, GGC_E_UNSUPPORTED,
-                "hidden_channels=%d unsupported: the kernels are built for widths from 8 to 128", hidden);
+    GGC_REQUIRE(ctx, hidden >= 8 && hidden <= 256, GGC_E_UNSUPPORTED,
+                "hidden_channels=%d unsupported: the kernels are built for widths from 8 to 256", hidden);
     // widths that are not a multiple of 32 run zero-padded to the next one (k_input: only the LayerNorm statistics see Dt)
     if (int rc = configure(ctx, RESGCN, (hidden + 31) / 32 * 32, hidden, n_layers)) return rc;
     ctx->resgcn.Q = hidden / 4 > 8 ? hidden / 4 : 8;   // model.py:472
@@ -1326,7 +1557,7 @@ int ggc_resgcn_forward(ggc_ctx* ctx, ggc_stream stream, int G, int N, int E, con
     int rc = begin_forward(ctx, RESGCN, G, N, E, x, edge_src, edge_dst, edge_attr, node_ptr, logits, probs);
     if (rc) return rc;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if (with_width<32, 64, 96, 128>(ctx->resgcn.D, rc, [&](auto w) {
+    if (with_width<32, 64, 96, 128, 160, 192, 224, 256>(ctx->resgcn.D, rc, [&](auto w) {
             return forward_t<decltype(w)::value>(ctx, st, G, N, E, x, edge_src, edge_dst, edge_attr, node_ptr, logits, probs); }))
         return rc;
     return set_err(ctx, GGC_E_UNSUPPORTED, "hidden=%d", ctx->resgcn.D);
@@ -1354,10 +1585,10 @@ int ggc_gcn_aggregate(ggc_ctx* ctx, ggc_stream stream, int N, int D, const float
     GGC_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     int rc;
-    if (with_width<32, 64, 96, 128>(D, rc, [&](auto w) {
+    if (with_width<32, 64, 96, 128, 160, 192, 224, 256>(D, rc, [&](auto w) {
             return launch_aggregate<decltype(w)::value, 0>(ctx, st, N, xw, row_ptr, col, dis, bias, gate, h, h_out); }))
         return rc;
-    return set_err(ctx, GGC_E_UNSUPPORTED, "D=%d unsupported (32, 64, 96, 128)", D);
+    return set_err(ctx, GGC_E_UNSUPPORTED, "D=%d unsupported (a multiple of 32 from 32 to 256)", D);
 }
 
 } // extern "C"

@@ -134,6 +134,7 @@ __global__ void __launch_bounds__(TB) k_pool(const int32_t* __restrict__ node_pt
                                              const float* __restrict__ score, float* __restrict__ attn,
                                              float* __restrict__ hb) {
     constexpr int P = TB / D;
+    static_assert(P >= 1, "a workgroup covers the row");
     __shared__ float red[TB / 64];
     __shared__ float part[P][D];
     __shared__ float pooled[D];
@@ -173,6 +174,7 @@ __global__ void __launch_bounds__(TB) k_pool_bwd(const int32_t* __restrict__ nod
                                                  const float* __restrict__ attn, const float* __restrict__ g_hb,
                                                  float* __restrict__ g_h, float* __restrict__ g_score) {
     constexpr int P = TB / D, W = TB / 64;
+    static_assert(P >= 1, "a workgroup covers the row");
     __shared__ float red[W];
     __shared__ float part[P][D];
     __shared__ float gp[D];
@@ -231,11 +233,15 @@ static int gather_any(ggc_ctx* ctx, hipStream_t st, int N, int D, const float* x
         case 64:  return launch_gather<64, MODE, EPI>(ctx, st, N, x, row_ptr, col, w, bias, gate, h, out, y);
         case 96:  return launch_gather<96, MODE, EPI>(ctx, st, N, x, row_ptr, col, w, bias, gate, h, out, y);
         case 128: return launch_gather<128, MODE, EPI>(ctx, st, N, x, row_ptr, col, w, bias, gate, h, out, y);
+        case 160: return launch_gather<160, MODE, EPI>(ctx, st, N, x, row_ptr, col, w, bias, gate, h, out, y);
+        case 192: return launch_gather<192, MODE, EPI>(ctx, st, N, x, row_ptr, col, w, bias, gate, h, out, y);
+        case 224: return launch_gather<224, MODE, EPI>(ctx, st, N, x, row_ptr, col, w, bias, gate, h, out, y);
+        case 256: return launch_gather<256, MODE, EPI>(ctx, st, N, x, row_ptr, col, w, bias, gate, h, out, y);
     }
-    return set_err(ctx, GGC_E_UNSUPPORTED, "D=%d unsupported in training (32, 64, 96, 128)", D);
+    return set_err(ctx, GGC_E_UNSUPPORTED, "D=%d unsupported in training (a multiple of 32 from 32 to 256)", D);
 }
 
-static bool train_width(int D) { return D == 32 || D == 64 || D == 96 || D == 128; }
+static bool train_width(int D) { return D >= 32 && D <= 256 && D % 32 == 0; }
 
 } // namespace ggc
 
@@ -268,7 +274,7 @@ int ggc_train_gcn_forward(ggc_ctx* ctx, ggc_stream stream, int N, int D, const f
                           float* out, float* y) {
     if (!ctx) return GGC_E_INVALID_ARG;
     GGC_REQUIRE(ctx, N >= 1 && xw && row_ptr && col && dis && bias && gate && out && y, GGC_E_INVALID_ARG, "bad arguments");
-    GGC_REQUIRE(ctx, train_width(D), GGC_E_UNSUPPORTED, "D=%d unsupported in training (32, 64, 96, 128)", D);
+    GGC_REQUIRE(ctx, train_width(D), GGC_E_UNSUPPORTED, "D=%d unsupported in training (a multiple of 32 from 32 to 256)", D);
     GGC_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     ProfScope prof(ctx, st, "train_gcn_forward");
@@ -281,7 +287,7 @@ int ggc_train_gcn_backward(ggc_ctx* ctx, ggc_stream stream, int N, int D, const 
     if (!ctx) return GGC_E_INVALID_ARG;
     GGC_REQUIRE(ctx, N >= 1 && g_y && out && gate && srow_ptr && scol && dis && g_out && g_gate && g_xw, GGC_E_INVALID_ARG,
                 "bad arguments");
-    GGC_REQUIRE(ctx, train_width(D), GGC_E_UNSUPPORTED, "D=%d unsupported in training (32, 64, 96, 128)", D);
+    GGC_REQUIRE(ctx, train_width(D), GGC_E_UNSUPPORTED, "D=%d unsupported in training (a multiple of 32 from 32 to 256)", D);
     GGC_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     ProfScope prof(ctx, st, "train_gcn_backward");
@@ -291,6 +297,10 @@ int ggc_train_gcn_backward(ggc_ctx* ctx, ggc_stream stream, int N, int D, const 
         case 64:  hipLaunchKernelGGL(k_gcn_epi_bwd<64>, grid, dim3(TB), 0, st, N, g_y, out, gate, g_out, g_gate); break;
         case 96:  hipLaunchKernelGGL(k_gcn_epi_bwd<96>, grid, dim3(TB), 0, st, N, g_y, out, gate, g_out, g_gate); break;
         case 128: hipLaunchKernelGGL(k_gcn_epi_bwd<128>, grid, dim3(TB), 0, st, N, g_y, out, gate, g_out, g_gate); break;
+        case 160: hipLaunchKernelGGL(k_gcn_epi_bwd<160>, grid, dim3(TB), 0, st, N, g_y, out, gate, g_out, g_gate); break;
+        case 192: hipLaunchKernelGGL(k_gcn_epi_bwd<192>, grid, dim3(TB), 0, st, N, g_y, out, gate, g_out, g_gate); break;
+        case 224: hipLaunchKernelGGL(k_gcn_epi_bwd<224>, grid, dim3(TB), 0, st, N, g_y, out, gate, g_out, g_gate); break;
+        case 256: hipLaunchKernelGGL(k_gcn_epi_bwd<256>, grid, dim3(TB), 0, st, N, g_y, out, gate, g_out, g_gate); break;
     }
     GGC_LAUNCH_CHECK(ctx);
     return gather_any<G_SYM, false>(ctx, st, N, D, g_out, srow_ptr, scol, dis, nullptr, nullptr, nullptr, g_xw, nullptr);
@@ -300,7 +310,7 @@ int ggc_train_sage_mean(ggc_ctx* ctx, ggc_stream stream, int N, int D, const flo
                         const int32_t* col, const float* inv_cnt, float* out) {
     if (!ctx) return GGC_E_INVALID_ARG;
     GGC_REQUIRE(ctx, N >= 1 && x && row_ptr && col && inv_cnt && out, GGC_E_INVALID_ARG, "bad arguments");
-    GGC_REQUIRE(ctx, train_width(D), GGC_E_UNSUPPORTED, "D=%d unsupported in training (32, 64, 96, 128)", D);
+    GGC_REQUIRE(ctx, train_width(D), GGC_E_UNSUPPORTED, "D=%d unsupported in training (a multiple of 32 from 32 to 256)", D);
     GGC_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     ProfScope prof(ctx, st, "train_sage_mean");
@@ -311,7 +321,7 @@ int ggc_train_sage_mean_backward(ggc_ctx* ctx, ggc_stream stream, int N, int D, 
                                  const int32_t* scol, const float* inv_cnt, float* g_x) {
     if (!ctx) return GGC_E_INVALID_ARG;
     GGC_REQUIRE(ctx, N >= 1 && g_m && srow_ptr && scol && inv_cnt && g_x, GGC_E_INVALID_ARG, "bad arguments");
-    GGC_REQUIRE(ctx, train_width(D), GGC_E_UNSUPPORTED, "D=%d unsupported in training (32, 64, 96, 128)", D);
+    GGC_REQUIRE(ctx, train_width(D), GGC_E_UNSUPPORTED, "D=%d unsupported in training (a multiple of 32 from 32 to 256)", D);
     GGC_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     ProfScope prof(ctx, st, "train_sage_mean");
@@ -348,7 +358,7 @@ int ggc_train_graph_pool(ggc_ctx* ctx, ggc_stream stream, int G, int N, int D, c
                          const float* score, float* attn, float* hb) {
     if (!ctx) return GGC_E_INVALID_ARG;
     GGC_REQUIRE(ctx, G >= 1 && N >= 1 && node_ptr && h && score && attn && hb, GGC_E_INVALID_ARG, "bad arguments");
-    GGC_REQUIRE(ctx, train_width(D), GGC_E_UNSUPPORTED, "D=%d unsupported in training (32, 64, 96, 128)", D);
+    GGC_REQUIRE(ctx, train_width(D), GGC_E_UNSUPPORTED, "D=%d unsupported in training (a multiple of 32 from 32 to 256)", D);
     GGC_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     ProfScope prof(ctx, st, "train_graph_pool");
@@ -357,6 +367,10 @@ int ggc_train_graph_pool(ggc_ctx* ctx, ggc_stream stream, int G, int N, int D, c
         case 64:  hipLaunchKernelGGL(k_pool<64>, dim3(G), dim3(TB), 0, st, node_ptr, h, score, attn, hb); break;
         case 96:  hipLaunchKernelGGL(k_pool<96>, dim3(G), dim3(TB), 0, st, node_ptr, h, score, attn, hb); break;
         case 128: hipLaunchKernelGGL(k_pool<128>, dim3(G), dim3(TB), 0, st, node_ptr, h, score, attn, hb); break;
+        case 160: hipLaunchKernelGGL(k_pool<160>, dim3(G), dim3(TB), 0, st, node_ptr, h, score, attn, hb); break;
+        case 192: hipLaunchKernelGGL(k_pool<192>, dim3(G), dim3(TB), 0, st, node_ptr, h, score, attn, hb); break;
+        case 224: hipLaunchKernelGGL(k_pool<224>, dim3(G), dim3(TB), 0, st, node_ptr, h, score, attn, hb); break;
+        case 256: hipLaunchKernelGGL(k_pool<256>, dim3(G), dim3(TB), 0, st, node_ptr, h, score, attn, hb); break;
     }
     GGC_LAUNCH_CHECK(ctx);
     return GGC_OK;
@@ -366,7 +380,7 @@ int ggc_train_graph_pool_backward(ggc_ctx* ctx, ggc_stream stream, int G, int N,
                                   const float* h, const float* attn, const float* g_hb, float* g_h, float* g_score) {
     if (!ctx) return GGC_E_INVALID_ARG;
     GGC_REQUIRE(ctx, G >= 1 && N >= 1 && node_ptr && h && attn && g_hb && g_h && g_score, GGC_E_INVALID_ARG, "bad arguments");
-    GGC_REQUIRE(ctx, train_width(D), GGC_E_UNSUPPORTED, "D=%d unsupported in training (32, 64, 96, 128)", D);
+    GGC_REQUIRE(ctx, train_width(D), GGC_E_UNSUPPORTED, "D=%d unsupported in training (a multiple of 32 from 32 to 256)", D);
     GGC_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     ProfScope prof(ctx, st, "train_graph_pool");
@@ -375,6 +389,10 @@ int ggc_train_graph_pool_backward(ggc_ctx* ctx, ggc_stream stream, int G, int N,
         case 64:  hipLaunchKernelGGL(k_pool_bwd<64>, dim3(G), dim3(TB), 0, st, node_ptr, h, attn, g_hb, g_h, g_score); break;
         case 96:  hipLaunchKernelGGL(k_pool_bwd<96>, dim3(G), dim3(TB), 0, st, node_ptr, h, attn, g_hb, g_h, g_score); break;
         case 128: hipLaunchKernelGGL(k_pool_bwd<128>, dim3(G), dim3(TB), 0, st, node_ptr, h, attn, g_hb, g_h, g_score); break;
+        case 160: hipLaunchKernelGGL(k_pool_bwd<160>, dim3(G), dim3(TB), 0, st, node_ptr, h, attn, g_hb, g_h, g_score); break;
+        case 192: hipLaunchKernelGGL(k_pool_bwd<192>, dim3(G), dim3(TB), 0, st, node_ptr, h, attn, g_hb, g_h, g_score); break;
+        case 224: hipLaunchKernelGGL(k_pool_bwd<224>, dim3(G), dim3(TB), 0, st, node_ptr, h, attn, g_hb, g_h, g_score); break;
+        case 256: hipLaunchKernelGGL(k_pool_bwd<256>, dim3(G), dim3(TB), 0, st, node_ptr, h, attn, g_hb, g_h, g_score); break;
     }
     GGC_LAUNCH_CHECK(ctx);
     return GGC_OK;

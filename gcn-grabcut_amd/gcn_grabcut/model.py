@@ -223,8 +223,8 @@ if _TORCH:
                     "the MI355X kernels are specialised for the reference's fixed widths: "
                     f"in_channels={N_NODE_FEATS}, edge_channels={N_EDGE_FEATS}, n_classes=3"
                 )
-            if not 8 <= int(hidden_channels) <= 128:
-                raise ValueError("hidden_channels must lie in [8, 128] (the HIP kernels are built for widths up to 128; widths that "
+            if not 8 <= int(hidden_channels) <= 256:
+                raise ValueError("hidden_channels must lie in [8, 256] (the HIP kernels are built for widths up to 256; widths that "
                                  "are not a multiple of 32 run zero-padded inside the library)")
             self.n_classes = n_classes
             self.n_layers = n_layers
@@ -286,7 +286,7 @@ if _TORCH:
             """Training forward, reference model.py:508-536 with autograd.  The dense layers are torch modules (each
             respects its own `.training` flag); the graph operators (GCNConv aggregation + residual epilogue, SAGE mean,
             EdgeContext scatter-mean, per-graph attention readout) are the ggc_train_* kernels, whose backward passes
-            are deterministic.  Widths 32, 64, 96 and 128 only."""
+            are deterministic.  Widths that are multiples of 32 from 32 to 256 only."""
             import torch.nn.functional as F
             from . import train_ops
             D = self.hidden_channels
@@ -438,7 +438,7 @@ if _TORCH:
         """
         GATv2 attention variant with edge features (reference model.py:323-414; SURVEY.md section 8(f), last rank).  Same
         `state_dict` keys as the reference module.  Inference only: the forward pass runs in libggc_hip.so
-        (`ggc_gat_forward`) on an MI355X — there is no CPU fallback.  Widths 32, 64 or 128 with 1, 2, 4 or 8 heads.
+        (`ggc_gat_forward`) on an MI355X — there is no CPU fallback.  Widths 32, 64, 128 or 256 with 1, 2, 4 or 8 heads.
         """
 
         def __init__(self, in_channels: int = N_NODE_FEATS, edge_channels: int = N_EDGE_FEATS, hidden_channels: int = 128,
@@ -446,8 +446,8 @@ if _TORCH:
             super().__init__()
             if in_channels != N_NODE_FEATS or edge_channels != N_EDGE_FEATS or n_classes != 3:
                 raise ValueError("the MI355X kernels are built for 19 node features, 5 edge features and 3 classes")
-            if hidden_channels not in (32, 64, 128) or n_heads not in (1, 2, 4, 8):
-                raise ValueError("GATTrimapNet on MI355X: hidden_channels in {32, 64, 128} with n_heads in {1, 2, 4, 8} "
+            if hidden_channels not in (32, 64, 128, 256) or n_heads not in (1, 2, 4, 8):
+                raise ValueError("GATTrimapNet on MI355X: hidden_channels in {32, 64, 128, 256} with n_heads in {1, 2, 4, 8} "
                                  "(a head must span a power-of-two number of lanes; the reference's default is 128 x 8)")
             self.n_classes, self.n_heads, self.hidden_channels, self.n_layers = n_classes, n_heads, hidden_channels, n_layers
             self.in_norm = _InputNorm(in_channels)

@@ -14,7 +14,7 @@ import torch
 
 from . import _native
 
-TRAIN_WIDTHS = (32, 64, 96, 128)
+TRAIN_WIDTHS = (32, 64, 96, 128, 160, 192, 224, 256)
 
 
 def _p(t: Optional[torch.Tensor]) -> Optional[int]:

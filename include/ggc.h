@@ -49,7 +49,8 @@
 extern "C" {
 #endif
 
-#define GGC_VERSION 310 /* 0.3.1: ggc_train_* (graph operators of the ResGCNNet training forward and their backward) */
+#define GGC_VERSION 320 /* 0.3.2: ResGCNNet (forward and ggc_train_*), GATTrimapNet and ggc_gcn_aggregate at widths up to 256;
+                           0.3.1: ggc_train_* (graph operators of the ResGCNNet training forward and their backward) */
 
 enum {
     GGC_OK            =  0,
@@ -182,8 +183,9 @@ int ggc_graph_prior_sigmas(ggc_ctx* ctx, double centre_sigma, double contrast_si
  * one state_dict entry by its reference key, e.g.
  * "gcn_layers.3.lin.weight", as a contiguous f32 HOST array.  Integer buffers
  * ("...num_batches_tracked") are accepted and ignored.
- * hidden: any width from 8 to 128 (model.py:449-455 takes any); the entries are given in their TRUE shapes.  A width that is
- * not a multiple of 32 runs zero-padded to the next one inside the library (LayerNorm statistics on the true width).
+ * hidden: any width from 8 to 256 (model.py:449-455 takes any; GGC_E_UNSUPPORTED above 256); the entries are given in their
+ * TRUE shapes.  A width that is not a multiple of 32 runs zero-padded to the next one inside the library (LayerNorm
+ * statistics on the true width).
  */
 int ggc_resgcn_configure(ggc_ctx* ctx, int hidden, int n_layers);
 int ggc_resgcn_load_weight(ggc_ctx* ctx, const char* name, const float* data /*[host]*/,
@@ -218,10 +220,11 @@ int ggc_gcnnet_forward(ggc_ctx* ctx, ggc_stream stream, int N, int E,
                        const float* edge_attr, float* logits, float* probs);
 
 /* GATTrimapNet, the reference's attention variant (`--model gat`, model.py:323-414; SURVEY 8(f) last rank), eval mode: GATv2
- * attention with edge features (8 heads), LayerNorm + GELU, per-block edge gates, skip, per-graph attention readout, head.
+ * attention with edge features (n_heads heads), LayerNorm + GELU, per-block edge gates, skip, per-graph attention readout, head.
  * Same protocol: configure, load every float tensor of the state_dict by its key ("convs.0.att", "convs.0.lin_l.weight",
  * "convs.0.lin_edge.weight", "lns.0.weight", "edge_gates.0.proj.2.bias", "skip_proj.weight", "ctx.attn.weight",
- * "head.3.weight", ...), then forward.  hidden_channels in {32, 64, 128}, n_heads == 8.  Arguments as ggc_resgcn_forward
+ * "head.3.weight", ...), then forward.  hidden_channels in {32, 64, 128, 256} with n_heads in {1, 2, 4, 8} (GGC_E_UNSUPPORTED
+ * otherwise).  Arguments as ggc_resgcn_forward
  * (node_ptr delimits the graphs of the batch for the readout). */
 int ggc_gat_configure(ggc_ctx* ctx, int hidden_channels, int n_heads, int n_layers);
 int ggc_gat_load_weight(ggc_ctx* ctx, const char* name, const float* data /*[host]*/, int64_t numel);
@@ -238,6 +241,7 @@ int ggc_gat_forward(ggc_ctx* ctx, ggc_stream stream, int G, int N, int E,
  *   else:             h_out_i = out_i
  *   xw [dev] f32 [N,D]  row_ptr [dev] i32 [N+1]  col [dev] i32 [E]
  *   dis [dev] f32 [N] = (1+indeg)^-1/2   bias [dev] f32 [D]
+ * D: a multiple of 32 from 32 to 256 (GGC_E_UNSUPPORTED otherwise).
  */
 int ggc_gcn_aggregate(ggc_ctx* ctx, ggc_stream stream, int N, int D,
                       const float* xw, const int32_t* row_ptr, const int32_t* col,
@@ -255,8 +259,8 @@ int ggc_build_csr(ggc_ctx* ctx, ggc_stream stream, int N, int E,
 /* ------------------------------------------------------------ training (ResGCNNet)
  * The graph operators of the ResGCNNet training forward (model.py:508-536, train mode) and their backward passes, f32.
  * The dense layers stay in the host's autograd.  No entry uses a float atomic: every sum runs in one fixed order, so two
- * runs give identical bits.  A scatter in a backward pass is a gather over the SOURCE CSR.  Node widths D in
- * {32, 64, 96, 128} (GGC_E_UNSUPPORTED otherwise).  All arrays are device arrays.
+ * runs give identical bits.  A scatter in a backward pass is a gather over the SOURCE CSR.  Node widths D: a multiple of
+ * 32 from 32 to 256 (GGC_E_UNSUPPORTED otherwise).  All arrays are device arrays.
  *
  * Graph preparation, once per batch, shared by every layer: destination CSR (row_ptr [N+1], col = source [E],
  * eid = edge id [E]) and source CSR (srow_ptr [N+1], scol = destination [E], seid [E]), both stable in edge order;

@@ -1,9 +1,9 @@
 """
 Training throughput of ResGCNNet on one MI355X: graphs/s per optimizer step and library launches per step.
 
-    python3 tools/train_rate.py [--steps 20] [--warmup 3] [--batches 8 64] [--nodes 600]
+    python3 tools/train_rate.py [--steps 20] [--warmup 3] [--batches 8 64] [--nodes 600] [--hidden 128]
 
-Batches of superpixel-like graphs of about `--nodes` nodes (tests/helpers.py's generator), D=128, 6 layers, TrimapLoss,
+Batches of superpixel-like graphs of about `--nodes` nodes (tests/helpers.py's generator), D=`--hidden`, 6 layers, TrimapLoss,
 AdamW, dropout 0.15.  A step is zero_grad + training forward + backward + clip + optimizer step, timed with CUDA events
 over `--steps` steps after `--warmup`.  Launches per step are the ggc_train_* scopes counted by ggc_profile_query in one
 extra profiled step.  Prints one JSON line per batch size.
@@ -27,6 +27,7 @@ def main() -> None:
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batches", type=int, nargs="+", default=[8, 64])
     ap.add_argument("--nodes", type=int, default=600)
+    ap.add_argument("--hidden", type=int, default=128)
     args = ap.parse_args()
     import torch
     from helpers import superpixel_like_graph
@@ -36,7 +37,7 @@ def main() -> None:
     from gcn_grabcut.model import ResGCNNet
 
     torch.manual_seed(0)
-    model = ResGCNNet(hidden_channels=128, n_layers=6).cuda().train()
+    model = ResGCNNet(hidden_channels=args.hidden, n_layers=6).cuda().train()
     opt = torch.optim.AdamW(model.param_groups(1e-3), lr=1e-3)
     crit = TrimapLoss(weight=torch.tensor([1.5, 0.8, 1.5], device="cuda"))
     ctx = _native.get_context(0)
@@ -72,7 +73,7 @@ def main() -> None:
         step()
         per_scope = {s: ctx.profile_query(s) for s in SCOPES}
         ctx.profile_enable(0)
-        print(json.dumps({"batch_graphs": bs, "nodes": int(b.x.size(0)), "edges": int(b.edge_index.size(1)),
+        print(json.dumps({"hidden": args.hidden, "batch_graphs": bs, "nodes": int(b.x.size(0)), "edges": int(b.edge_index.size(1)),
                           "ms_per_step": round(ms, 3), "graphs_per_s": round(bs * 1000.0 / ms, 1),
                           "ggc_entries_per_step": sum(n for n, _ in per_scope.values()),
                           "ggc_ms_per_step": round(sum(t for _, t in per_scope.values()), 3),
