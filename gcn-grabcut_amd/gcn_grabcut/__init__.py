@@ -11,7 +11,7 @@ from ._constants import N_NODE_FEATS, N_EDGE_FEATS, N_PRIOR_FEATS, N_IMAGE_FEATS
 from .data import Data, Batch
 from .grabcut import GrabCut, GrabCutConfig, Label
 from .graph_builder import (
-    GraphBuilder, SuperpixelGraph, SuperpixelGraphConfig, compute_auto_prior, encode_user_hints,
+    GraphBuilder, SuperpixelGraph, SuperpixelGraphConfig, compute_auto_prior, encode_user_hints, pack_hints,
 )
 from .metrics import evaluate, evaluate_batch, evaluate_trimap, boundary_f1, SegmentationMetrics, TrimapMetrics
 from .model import (
@@ -27,7 +27,7 @@ __version__ = "0.3.0+mi355x.1"
 
 __all__ = [
     "GrabCut", "GrabCutConfig", "Label",
-    "GraphBuilder", "SuperpixelGraph", "SuperpixelGraphConfig", "compute_auto_prior", "encode_user_hints",
+    "GraphBuilder", "SuperpixelGraph", "SuperpixelGraphConfig", "compute_auto_prior", "encode_user_hints", "pack_hints",
     "N_NODE_FEATS", "N_EDGE_FEATS", "N_PRIOR_FEATS",
     "evaluate", "evaluate_batch", "evaluate_trimap", "boundary_f1", "SegmentationMetrics", "TrimapMetrics",
     "GCNGrabCutPipeline", "SegmentationResult", "clean_mask", "guided_filter", "refine_trimap",

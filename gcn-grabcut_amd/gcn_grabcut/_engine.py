@@ -208,6 +208,23 @@ class Engine:
                       seg.data_ptr(), float(seed_frac), trimap.data_ptr())
         return trimap
 
+    # ------------------------------------------------------------------ H0
+    def upload_hints(self, hints: np.ndarray, hint_ptr: np.ndarray):
+        """pack_hints' (hints [K,3], hint_ptr [B+1]) -> the same two arrays on the device, in one host-to-device copy."""
+        hint_ptr = np.asarray(hint_ptr, np.int32)
+        d = self.to_device(np.concatenate([hint_ptr, np.asarray(hints, np.int32).ravel()]))
+        return d[hint_ptr.size:].view(-1, 3), d[:hint_ptr.size]
+
+    def apply_hints(self, mask, hints, hint_ptr, radius=5, region=False, segments=None, node_ptr=None, node_hints=None,
+                    shape=None):
+        """Clicks as hard constraints, in place on mask (B,H,W) uint8 (ggc_apply_hints).  node_hints (N,3) float32, if
+        given, receives encode_user_hints of every image; mask may then be None, with shape = (B,H,W)."""
+        b, h, w = mask.shape if mask is not None else shape
+        self.ctx.call("ggc_apply_hints", self._stream(), b, h, w, _native.ptr(hints), hint_ptr.data_ptr(), int(radius),
+                      int(bool(region)), _native.ptr(segments), _native.ptr(node_ptr), _native.ptr(node_hints),
+                      _native.ptr(mask))
+        return mask
+
     # ------------------------------------------------------------------ C0-C6, K0, O0, R0
     def grabcut(self, image, mask, n_iter=5, mode=0, rects=None, seed=0, bgd=None, fgd=None):
         """In place on mask; returns (binary, mask, bgd_model, fgd_model)."""

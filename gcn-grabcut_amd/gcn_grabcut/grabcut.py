@@ -48,6 +48,8 @@ class GrabCut:
     gc = GrabCut(image)
     mask = gc.run_with_bbox((x, y, w, h))    # classical mode
     mask = gc.run_with_trimap(trimap)        # GCN-guided mode
+    gc.add_hints(fg_points=[(r, c)])         # user clicks as definite labels (additive) ...
+    mask = gc.refine(2)                      # ... then GC_EVAL from the edited mask
     """
 
     def __init__(self, image: np.ndarray, config: Optional[GrabCutConfig] = None, device="cuda"):
@@ -57,6 +59,7 @@ class GrabCut:
         self.image = image
         self.config = config or GrabCutConfig()
         self.mask: Optional[np.ndarray] = None
+        self._dmask = None                     # (1,H,W) device copy of mask as the last run / edit left it
         self._bgd = np.zeros((1, 65), np.float64)
         self._fgd = np.zeros((1, 65), np.float64)
         self.history: List[GrabCutSnapshot] = []
@@ -83,6 +86,7 @@ class GrabCut:
         _, dmask, bgd, fgd = eng.grabcut(self._proc, dmask, n_iter, mode, None if rect is None else [list(rect)],
                                          self.config.seed, bgd, fgd)
         self.mask = dmask[0].cpu().numpy()
+        self._dmask = dmask
         self._bgd, self._fgd = bgd.cpu().numpy(), fgd.cpu().numpy()
         return self._binary()
 
@@ -115,6 +119,26 @@ class GrabCut:
         out = self._run(self.mask, extra_iter, 2)
         self._snapshot("refinement")
         return out
+
+    def add_hints(self, fg_points=(), bg_points=(), radius: int = 5) -> np.ndarray:
+        """Additive: paint user clicks, (row, col) pairs, into the current mask as GC_FGD / GC_BGD disks of `radius` pixels
+        (ggc_apply_hints; background clicks win where disks overlap, clicks outside the image are ignored).  The edit runs
+        on the mask the last run left on the device; the GMMs are kept, so refine(n) continues from the edited mask."""
+        if self.mask is None:
+            raise RuntimeError("Call run_with_bbox or run_with_trimap first.")
+        if int(radius) < 0:
+            raise ValueError(f"radius must be >= 0, got {radius}")
+        from .graph_builder import pack_hints
+        rows, ptr = pack_hints([(fg_points, bg_points)])
+        eng = self._eng
+        if self._dmask is None or not self.history or not np.array_equal(self.mask, self.history[-1].mask_copy):
+            self._dmask = eng.to_device(np.ascontiguousarray(self.mask, dtype=np.uint8)[None])   # the host mask was edited
+        if ptr[-1]:
+            hints, hint_ptr = eng.upload_hints(rows, ptr)
+            eng.apply_hints(self._dmask, hints, hint_ptr, radius)
+            self.mask = self._dmask[0].cpu().numpy()
+        self._snapshot("hints")
+        return self._binary()
 
     def _binary(self) -> np.ndarray:
         return np.where((self.mask == Label.FG_DEFINITE) | (self.mask == Label.FG_PROBABLE), 1, 0).astype(np.uint8)

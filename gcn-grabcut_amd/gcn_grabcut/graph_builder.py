@@ -184,3 +184,41 @@ def encode_user_hints(segments: np.ndarray, fg_points, bg_points) -> np.ndarray:
                 hints[nid, col] = 1.0
                 hints[nid, 2] = 0.0
     return hints
+
+
+def _click_rows(points, label: int, what: str) -> np.ndarray:
+    a = np.asarray(list(points) if points is not None else [], dtype=np.float64)
+    if a.size == 0:
+        return np.zeros((0, 3), np.int64)
+    if a.ndim != 2 or a.shape[1] != 2:
+        raise ValueError(f"{what} must be a sequence of (row, col) pairs, got shape {a.shape}")
+    if not np.isfinite(a).all():
+        raise ValueError(f"{what} holds a non-finite coordinate")
+    rc = np.trunc(a).astype(np.int64)                         # int(r), int(c) as in encode_user_hints
+    if (np.abs(rc) > np.iinfo(np.int32).max).any():
+        raise ValueError(f"{what} holds a coordinate outside the int32 range")
+    return np.concatenate([rc, np.full((len(rc), 1), label, np.int64)], 1)
+
+
+def pack_hints(per_image) -> "tuple[np.ndarray, np.ndarray]":
+    """Per-image click lists -> the (hints, hint_ptr) pair of ggc_apply_hints.
+
+    per_image: one entry per image, None (no clicks) or (fg_points, bg_points), each a sequence of (row, col) as in
+    encode_user_hints.  Returns hints int32 [K,3] = (row, col, label) with label 1 = foreground, 0 = background, and
+    hint_ptr int32 [B+1].  An image's foreground clicks come first, then its background clicks, each in the order given,
+    so a background disk wins where the two overlap.  Clicks outside the image are kept: the kernel ignores them."""
+    rows, ptr = [], [0]
+    for b, entry in enumerate(per_image):
+        if entry is None:
+            ptr.append(ptr[-1])
+            continue
+        if isinstance(entry, (str, bytes)) or len(entry) != 2:
+            raise ValueError(f"hints[{b}] must be None or a (fg_points, bg_points) pair")
+        fg = _click_rows(entry[0], 1, f"hints[{b}] foreground points")
+        bg = _click_rows(entry[1], 0, f"hints[{b}] background points")
+        rows += [fg, bg]
+        ptr.append(ptr[-1] + len(fg) + len(bg))
+    if ptr[-1] > np.iinfo(np.int32).max // 3:
+        raise ValueError(f"{ptr[-1]} clicks: too many for one call")
+    hints = np.concatenate(rows).astype(np.int32) if rows else np.zeros((0, 3), np.int32)
+    return np.ascontiguousarray(hints.reshape(-1, 3)), np.asarray(ptr, np.int32)

@@ -20,7 +20,7 @@ from typing import Optional, Sequence
 import numpy as np
 
 from .grabcut import GrabCut, GrabCutConfig, Label
-from .graph_builder import GraphBuilder, SuperpixelGraphConfig, graphs_to_host, _check_image
+from .graph_builder import GraphBuilder, SuperpixelGraphConfig, graphs_to_host, _check_image, pack_hints
 from .metrics import evaluate, evaluate_trimap, SegmentationMetrics, TrimapMetrics
 from .model import CLASS_BG, CLASS_FG, project_to_pixels  # noqa: F401
 
@@ -134,6 +134,51 @@ def _colour_trimap(trimap: np.ndarray) -> np.ndarray:
     return vis
 
 
+@dataclass
+class _Hints:
+    """The clicks of a batch in ggc_apply_hints' packing, on the host, and how they are applied."""
+    rows: np.ndarray           # (K,3) int32 = row, col, label (1 = foreground)
+    ptr: np.ndarray            # (B+1,) int32
+    radius: int
+    region: bool
+    as_prior: bool
+
+    @staticmethod
+    def of(hints, b: int, radius, region, as_prior) -> "Optional[_Hints]":
+        """hints: one None or (fg_points, bg_points) per image, or an already packed (hints, hint_ptr) pair.
+        None when no image has a click, so that such a call launches exactly what a call without hints launches."""
+        if hints is None:
+            return None
+        if int(radius) < 0:
+            raise ValueError(f"hint_radius must be >= 0, got {radius}")
+        if isinstance(hints, tuple) and len(hints) == 2 and all(hasattr(a, "shape") for a in hints) and len(hints[1].shape) == 1:
+            rows, ptr = (np.asarray(a.cpu() if hasattr(a, "cpu") else a) for a in hints)
+            rows = rows.reshape(-1, 3) if rows.size else np.zeros((0, 3), np.int32)
+            if ptr.shape != (b + 1,) or ptr[0] != 0 or (np.diff(ptr) < 0).any() or ptr[-1] != len(rows):
+                raise ValueError(f"packed hints: hint_ptr must be a non-decreasing ({b + 1},) array from 0 to {len(rows)}")
+        else:
+            if len(hints) != b:
+                raise ValueError(f"hints has {len(hints)} entries for a batch of {b} images")
+            rows, ptr = pack_hints(hints)
+        if ptr[-1] == 0:
+            return None
+        return _Hints(np.ascontiguousarray(rows, np.int32), np.ascontiguousarray(ptr, np.int32), int(radius), bool(region),
+                      bool(as_prior))
+
+    def chunk(self, lo: int, hi: int) -> "Optional[_Hints]":
+        k0, k1 = int(self.ptr[lo]), int(self.ptr[hi])
+        if k1 == k0:
+            return None
+        return _Hints(self.rows[k0:k1], self.ptr[lo:hi + 1] - k0, self.radius, self.region, self.as_prior)
+
+    def clicked_images(self, h: int, w: int) -> np.ndarray:
+        """(B,) bool: the images with at least one click inside the frame."""
+        r, c = self.rows[:, 0], self.rows[:, 1]
+        ok = (r >= 0) & (r < h) & (c >= 0) & (c < w)
+        img = np.repeat(np.arange(len(self.ptr) - 1), np.diff(self.ptr))
+        return np.bincount(img[ok], minlength=len(self.ptr) - 1) > 0
+
+
 class GCNGrabCutPipeline:
     """
     Full GCN-GrabCut segmentation pipeline on the MI355X (reference pipeline.py:239-380).
@@ -211,8 +256,9 @@ class GCNGrabCutPipeline:
         return out
 
     # ------------------------------------------------------------ batched, device resident
-    def _front(self, eng, bgr, threshold_fg, threshold_bg, edge_aware, filter_radius, tick=None, timing=None):
-        """Stages 1-3 on the current stream: colour prep, SLIC, graph, network, trimap, seeding.  -> (seg, graphs, probs, trimap)"""
+    def _front(self, eng, bgr, threshold_fg, threshold_bg, edge_aware, filter_radius, tick=None, timing=None, hints=None):
+        """Stages 1-3 on the current stream: colour prep, SLIC, graph, network, trimap, seeding, then the user's clicks
+        (hints: a _Hints or None).  -> (seg, graphs, probs, trimap)"""
         cfg = self.sp_config
         t = tick() if tick else 0.0
         lab, hsv, gray, grad = eng.preprocess(bgr)
@@ -225,13 +271,43 @@ class GCNGrabCutPipeline:
         t = tick() if tick else 0.0
         if self.model.training:
             self.model.eval()
+        prior = graphs.x[:, 16:19]
+        if hints is not None:
+            hint_rows, hint_ptr = eng.upload_hints(hints.rows, hints.ptr)
+            if hints.as_prior:
+                prior = self._hints_as_prior(eng, hints, hint_rows, hint_ptr, seg, graphs)
         probs = eng.predict_probs(self.model, graphs)
         trimap = eng.refine_trimap(probs, graphs.node_ptr, seg, bgr, threshold_fg, threshold_bg, filter_radius,
                                    1e-3, edge_aware)
         if timing is not None:
             timing["gcn_inference"] = tick() - t
-        trimap = eng.seed_from_prior(trimap, graphs.x[:, 16:19], graphs.node_ptr, seg, 0.1)
+        trimap = eng.seed_from_prior(trimap, prior, graphs.node_ptr, seg, 0.1)
+        if hints is not None:                  # hard constraints: over the network's trimap and the seeding alike
+            eng.apply_hints(trimap, hint_rows, hint_ptr, hints.radius, hints.region, seg, graphs.node_ptr)
         return seg, graphs, probs, trimap
+
+    @staticmethod
+    def _hints_as_prior(eng, hints, hint_rows, hint_ptr, seg, graphs):
+        """The reference's use of encode_user_hints: the prior columns x[:, 16:19] of every image with a click inside the
+        frame become its click table; the other images keep the automatic prior.  Returns a copy of the automatic prior,
+        which seed_from_prior still reads."""
+        auto = graphs.x[:, 16:19].clone()
+        table = eng.empty(graphs.x.size(0), 3)
+        eng.apply_hints(None, hint_rows, hint_ptr, segments=seg, node_ptr=graphs.node_ptr, node_hints=table, shape=seg.shape)
+        clicked = hints.clicked_images(seg.size(1), seg.size(2))
+        nptr = graphs.node_ptr_host
+        b = 0
+        while b < len(clicked):                # one copy per run of consecutive clicked images
+            if not clicked[b]:
+                b += 1
+                continue
+            e = b
+            while e < len(clicked) and clicked[e]:
+                e += 1
+            n0, n1 = int(nptr[b]), int(nptr[e])
+            graphs.x[n0:n1, 16:19] = table[n0:n1]
+            b = e
+        return auto
 
     @staticmethod
     def chunk_plan(b: int, n_chunks: int, ratio: float = 0.8) -> list[tuple[int, int]]:
@@ -250,8 +326,17 @@ class GCNGrabCutPipeline:
                              refine_iters: int = 0, min_area_ratio: float = 0.002, keep_largest: bool = False,
                              edge_aware: bool = True, filter_radius: int = 8, compose: bool = True,
                              timing: Optional[dict] = None, grabcut_lanes: Optional[int] = None,
-                             chunks: Optional[int] = None) -> dict:
+                             chunks: Optional[int] = None, hints=None, hint_radius: int = 5, hint_region: bool = False,
+                             hints_as_prior: bool = False) -> dict:
         """bgr: (B,H,W,3) uint8 tensor on the pipeline's device.  Returns device tensors.
+
+        User clicks (additive): hints is None, a list with one None or (fg_points, bg_points) per image ((row, col) pairs,
+        as encode_user_hints takes them), or a packed (hints, hint_ptr) pair (graph_builder.pack_hints).  They are hard
+        constraints on the trimap GrabCut is given (ggc_apply_hints, after the seeding): every pixel within hint_radius of
+        a click becomes definite foreground / background, the later click winning where disks overlap; hint_region=True
+        first does the same for every superpixel whose clicks all carry one label.  hints_as_prior=True also replaces the
+        network's prior columns x[:, 16:19] of each image with a click in the frame by encode_user_hints.  clean_mask
+        still runs after GrabCut, so a foreground click on a component smaller than min_area_ratio can be removed.
 
         Large batches run as a software pipeline (additive, same results): the batch is cut into `chunks` contiguous
         chunks; the front stages of chunk k+1 run on the caller's stream while the GrabCut / clean-up of chunk k runs on a
@@ -265,18 +350,21 @@ class GCNGrabCutPipeline:
         b = bgr.size(0)
         want = self.grabcut_lanes if grabcut_lanes is None else int(grabcut_lanes)   # (an argument, so that concurrent callers do not mutate the pipeline)
         n_chunks = self.chunks if chunks is None else int(chunks)
+        hints = _Hints.of(hints, b, hint_radius, hint_region, hints_as_prior)
         if n_chunks <= 0:                          # 0: one chunk per GrabCut lane once every chunk gets a lane's worth of images
             n_chunks = max(want, 1) if b >= 16 * max(want, 1) else 1
         if n_chunks > 1 and b >= 2 * n_chunks:
             return self._segment_pipelined(bgr, self.chunk_plan(b, n_chunks, self.chunk_ratio), cs, threshold_fg, threshold_bg,
-                                           refine_iters, min_area_ratio, keep_largest, edge_aware, filter_radius, compose, timing)
+                                           refine_iters, min_area_ratio, keep_largest, edge_aware, filter_radius, compose, timing,
+                                           hints)
 
         def tick():
             if timing is not None:
                 torch.cuda.synchronize(eng.device)
             return time.perf_counter()
 
-        seg, graphs, probs, trimap = self._front(eng, bgr, threshold_fg, threshold_bg, edge_aware, filter_radius, tick, timing)
+        seg, graphs, probs, trimap = self._front(eng, bgr, threshold_fg, threshold_bg, edge_aware, filter_radius, tick, timing,
+                                                 hints)
 
         t = tick()
         mask = trimap.clone()
@@ -314,7 +402,7 @@ class GCNGrabCutPipeline:
         return out
 
     def _segment_pipelined(self, bgr, plan, cs, threshold_fg, threshold_bg, refine_iters, min_area_ratio, keep_largest,
-                           edge_aware, filter_radius, compose, timing) -> dict:
+                           edge_aware, filter_radius, compose, timing, hints=None) -> dict:
         """The software pipeline behind segment_batch_device: chunk k's GrabCut lane starts as soon as chunk k's trimaps are
         on the device; the caller's stream goes on with chunk k+1's SLIC / graph / network / trimap."""
         import torch
@@ -369,7 +457,8 @@ class GCNGrabCutPipeline:
             ev = [torch.cuda.Event(enable_timing=True) for _ in range(5)] if timing is not None else None
             if ev is not None:
                 ev[3].record(caller)
-            s_k, g_k, p_k, t_k = self._front(eng, bgr[lo:hi], threshold_fg, threshold_bg, edge_aware, filter_radius)
+            s_k, g_k, p_k, t_k = self._front(eng, bgr[lo:hi], threshold_fg, threshold_bg, edge_aware, filter_radius,
+                                             hints=None if hints is None else hints.chunk(lo, hi))
             seg[lo:hi].copy_(s_k)
             trimap[lo:hi].copy_(t_k)
             mask[lo:hi].copy_(t_k)
@@ -396,8 +485,9 @@ class GCNGrabCutPipeline:
             timing["wall"] = time.perf_counter() - t_host
         return out
 
-    def segment_batch(self, images: Sequence[np.ndarray], **kwargs) -> list[SegmentationResult]:
-        """Segment equally sized BGR images as one batch (additive API)."""
+    def segment_batch(self, images: Sequence[np.ndarray], hints=None, **kwargs) -> list[SegmentationResult]:
+        """Segment equally sized BGR images as one batch (additive API).  hints: one None or (fg_points, bg_points) per
+        image, with hint_radius / hint_region / hints_as_prior among kwargs (segment_batch_device)."""
         imgs = [_check_image(im) for im in images]
         if not imgs:
             return []
@@ -405,7 +495,7 @@ class GCNGrabCutPipeline:
             raise ValueError("segment_batch needs images of one size; group them by shape")
         timing: dict[str, float] = {}
         bgr = self._eng.to_device(np.stack(imgs))
-        out = self.segment_batch_device(bgr, timing=timing, **kwargs)
+        out = self.segment_batch_device(bgr, timing=timing, hints=hints, **kwargs)
         host = {k: out[k].cpu().numpy() for k in ("binary_mask", "trimap", "segments", "overlay", "rgba")}
         per_image = {k: v / len(imgs) for k, v in timing.items()}
         return [SegmentationResult(image=imgs[i], binary_mask=host["binary_mask"][i], trimap=host["trimap"][i],
@@ -415,12 +505,20 @@ class GCNGrabCutPipeline:
     # ------------------------------------------------------------ reference API
     def segment(self, image: np.ndarray, threshold_fg: float = 0.55, threshold_bg: float = 0.55,
                 refine_iters: int = 0, min_area_ratio: float = 0.002, keep_largest: bool = False,
-                edge_aware: bool = True, filter_radius: int = 8) -> SegmentationResult:
-        """Full pipeline on one BGR image (reference pipeline.py:265-352)."""
+                edge_aware: bool = True, filter_radius: int = 8, fg_points=None, bg_points=None, hint_radius: int = 5,
+                hint_region: bool = False, hints_as_prior: bool = False) -> SegmentationResult:
+        """Full pipeline on one BGR image (reference pipeline.py:265-352).
+
+        Additive: fg_points / bg_points are user clicks, (row, col) pairs, applied as hard constraints on the trimap
+        GrabCut starts from (see segment_batch_device for hint_radius, hint_region and hints_as_prior)."""
         image = _check_image(image)
         timing: dict[str, float] = {}
+        hints = None if fg_points is None and bg_points is None else \
+            [(() if fg_points is None else fg_points, () if bg_points is None else bg_points)]
         out = self.segment_batch_device(self._eng.to_device(image[None]), threshold_fg, threshold_bg, refine_iters,
-                                        min_area_ratio, keep_largest, edge_aware, filter_radius, timing=timing)
+                                        min_area_ratio, keep_largest, edge_aware, filter_radius, timing=timing,
+                                        hints=hints, hint_radius=hint_radius, hint_region=hint_region,
+                                        hints_as_prior=hints_as_prior)
         return SegmentationResult(
             image=image, binary_mask=out["binary_mask"][0].cpu().numpy(), trimap=out["trimap"][0].cpu().numpy(),
             segments=out["segments"][0].cpu().numpy(), overlay=out["overlay"][0].cpu().numpy(),

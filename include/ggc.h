@@ -49,7 +49,8 @@
 extern "C" {
 #endif
 
-#define GGC_VERSION 320 /* 0.3.2: ResGCNNet (forward and ggc_train_*), GATTrimapNet and ggc_gcn_aggregate at widths up to 256;
+#define GGC_VERSION 330 /* 0.3.3: ggc_apply_hints (user clicks as hard constraints on the GrabCut mask);
+                           0.3.2: ResGCNNet (forward and ggc_train_*), GATTrimapNet and ggc_gcn_aggregate at widths up to 256;
                            0.3.1: ggc_train_* (graph operators of the ResGCNNet training forward and their backward) */
 
 enum {
@@ -351,6 +352,27 @@ int ggc_grabcut(ggc_ctx* ctx, ggc_stream stream, int B, int H, int W,
                 const uint8_t* image, uint8_t* mask, const int32_t* rects,
                 double* bgd_model, double* fgd_model, int n_iter, int mode,
                 uint64_t seed, uint8_t* binary);
+
+/* H0 — user clicks as hard constraints (additive; reference graph_builder.py:457-494, batched).
+ *   hints    [dev] i32 [K,3] = (row, col, label) with label 0 = background, nonzero = foreground;
+ *            grouped by image, click order kept within an image
+ *   hint_ptr [dev] i32 [B+1]  image b owns hints[hint_ptr[b] .. hint_ptr[b+1]); hint_ptr[0] = 0, non-decreasing
+ *   radius   disk radius in pixels: (dy*dy + dx*dx) <= radius*radius; 0 = the clicked pixel only
+ *   region   0 = disks only; 1 = first the whole superpixel under a click, then the disks
+ *   segments [dev] i32 [B,H,W] local labels, node_ptr [dev] i32 [B+1]  (both may be NULL when region == 0
+ *            and node_hints == NULL)
+ *   node_hints [dev] f32 [N_total,3] out, may be NULL: encode_user_hints of each image
+ *   mask     [dev] u8 [B,H,W] in/out GrabCut labels (may be NULL when node_hints is not: only the table is written)
+ * A click outside its image is ignored.  Disks: every pixel inside the disk of a click becomes GGC_FGD or GGC_BGD, clipped
+ * to the image; where disks overlap, the last click of the image wins.  Regions (applied before the disks): a superpixel
+ * whose in-bounds clicks are all foreground becomes GGC_FGD, all background GGC_BGD; one with both is left to the disks.
+ * node_hints rows node_ptr[b].. get column 0 = foreground click, 1 = background click, 2 = neither.  Pixels no hint
+ * touches keep their label.  No float atomics: the result does not depend on launch order.  K = hint_ptr[B] == 0 or B == 0
+ * is a no-op (node_hints is not written).  A malformed hint_ptr / node_ptr or a negative radius is GGC_E_INVALID_ARG.
+ * SYNCHRONISES the stream to read hint_ptr (and node_ptr when the superpixels are used). */
+int ggc_apply_hints(ggc_ctx* ctx, ggc_stream stream, int B, int H, int W, const int32_t* hints, const int32_t* hint_ptr,
+                    int radius, int region, const int32_t* segments, const int32_t* node_ptr,
+                    float* node_hints, uint8_t* mask);
 
 /* K0 — replaces clean_mask (pipeline.py:189-227); 8-connected components.
  *   mask_in/mask_out [dev] u8 [B,H,W] in {0,1} (may alias) */

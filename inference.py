@@ -6,6 +6,7 @@ Same command line as the reference's inference.py (flags :26-56, outputs :146-15
     python3 inference.py --image path/to/image.jpg
     python3 inference.py --input path/to/folder --output results/
     python3 inference.py --image cat.jpg --keep-largest --save mask overlay
+    python3 inference.py --image cat.jpg --fg-point 120,200 --bg-point 10,10 --hint-radius 8
 
 Images are decoded / written with Pillow (OpenCV is not a dependency of this build); folders are processed in
 batches of equally sized images so that the whole batch stays resident in HBM.
@@ -43,7 +44,28 @@ def build_parser() -> argparse.ArgumentParser:
     parser.add_argument("--save", nargs="+", default=["mask", "overlay"], choices=["mask", "overlay", "rgba", "trimap"],
                         help="Which outputs to write")
     parser.add_argument("--batch", type=int, default=64, help="Images per device batch (additive flag)")
+    # additive: user clicks as hard constraints (ggc_apply_hints), single-image runs only
+    parser.add_argument("--fg-point", action="append", type=_point, default=[], metavar="ROW,COL",
+                        help="Foreground click in original-image pixels (repeatable; needs --image)")
+    parser.add_argument("--bg-point", action="append", type=_point, default=[], metavar="ROW,COL",
+                        help="Background click in original-image pixels (repeatable; needs --image)")
+    parser.add_argument("--hint-radius", type=int, default=5,
+                        help="Radius in pixels of the image as segmented (after --max-size) painted around each click")
     return parser
+
+
+def _point(text: str):
+    try:
+        r, c = (int(v) for v in text.split(","))
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"expected ROW,COL (two integers), got '{text}'")
+    return r, c
+
+
+def scale_points(points, orig_hw, new_hw):
+    """Clicks given in the original image -> the pixels they fall on after read_bgr's resize."""
+    (h0, w0), (h1, w1) = orig_hw, new_hw
+    return [(r * h1 // h0, c * w1 // w0) for r, c in points]
 
 
 def read_bgr(path: Path, max_size: int):
@@ -61,7 +83,12 @@ def read_bgr(path: Path, max_size: int):
 
 
 def main() -> None:
-    args = build_parser().parse_args()
+    parser = build_parser()
+    args = parser.parse_args()
+    if (args.fg_point or args.bg_point) and not args.image:
+        parser.error("--fg-point / --bg-point are clicks on one image: use them with --image, not --input")
+    if args.hint_radius < 0:
+        parser.error("--hint-radius must be >= 0")
     import torch
     from src.gcn_grabcut import GCNGrabCutPipeline
     from src.gcn_grabcut.graph_builder import SuperpixelGraphConfig
@@ -115,10 +142,19 @@ def main() -> None:
         for i in range(0, len(items), args.batch):
             chunk = items[i:i + args.batch]
             t0 = time.perf_counter()
+            hint_kw = {}
+            if args.fg_point or args.bg_point:          # --image only: one chunk of one image
+                from PIL import Image
+                path, image = chunk[0]
+                with Image.open(path) as im:
+                    orig_hw = im.size[::-1]
+                hint_kw = dict(hints=[(scale_points(args.fg_point, orig_hw, image.shape[:2]),
+                                       scale_points(args.bg_point, orig_hw, image.shape[:2]))],
+                               hint_radius=args.hint_radius)
             results = pipeline.segment_batch(
                 [im for _, im in chunk], threshold_fg=args.threshold, threshold_bg=args.threshold,
                 refine_iters=args.refine, min_area_ratio=args.min_area, keep_largest=args.keep_largest,
-                edge_aware=not args.no_edge_aware, filter_radius=args.filter_radius)
+                edge_aware=not args.no_edge_aware, filter_radius=args.filter_radius, **hint_kw)
             elapsed = (time.perf_counter() - t0) / len(chunk)
             for (path, _), result in zip(chunk, results):
                 total_t += elapsed
