@@ -29,6 +29,7 @@ enum Slot : int {
     S_GC_K, S_GC_L, S_GC_M,
     S_CC_A, S_CC_B, S_CC_C,
     S_MISC_A, S_MISC_B,
+    S_CLICK,
     S_COUNT
 };
 

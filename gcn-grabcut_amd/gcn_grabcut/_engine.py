@@ -225,6 +225,16 @@ class Engine:
                       _native.ptr(mask))
         return mask
 
+    def next_click(self, pred, gt) -> torch.Tensor:
+        """The next simulated click of the NoC protocol per image (ggc_next_click): pred, gt (B,H,W) uint8, nonzero =
+        foreground -> (B,4) int32 on the device = row, col, label (1 = fg, 0 = bg), d2; (-1,-1,-1,0) where pred == gt."""
+        b, h, w = pred.shape
+        if tuple(gt.shape) != (b, h, w):
+            raise ValueError(f"next_click: pred {tuple(pred.shape)} and gt {tuple(gt.shape)} differ in shape")
+        out = self.empty(b, 4, dtype=torch.int32)
+        self.ctx.call("ggc_next_click", self._stream(), b, h, w, pred.data_ptr(), gt.data_ptr(), out.data_ptr())
+        return out
+
     # ------------------------------------------------------------------ C0-C6, K0, O0, R0
     def grabcut(self, image, mask, n_iter=5, mode=0, rects=None, seed=0, bgd=None, fgd=None):
         """In place on mask; returns (binary, mask, bgd_model, fgd_model)."""

@@ -135,3 +135,25 @@ def evaluate_batch(results: list[dict], device="cuda") -> dict:
     return {"mean_iou": float(np.mean(all_iou)), "std_iou": float(np.std(all_iou)),
             "mean_dice": float(np.mean(all_dice)), "std_dice": float(np.std(all_dice)),
             "mean_bf1": float(np.mean(all_bf1)), "std_bf1": float(np.std(all_bf1)), "n": len(results)}
+
+
+def noc_summary(ious, targets=(0.85, 0.90), max_clicks: int = 20) -> dict:
+    """Number-of-clicks scores of interactive segmentation from IoU curves (pure host function).
+
+    ious: (B, max_clicks + 1) IoU after 0, 1, ..., max_clicks clicks.  Per target t:
+      noc[t] (B,) int    the first k with IoU >= t, or max_clicks if no k reaches t
+      nof[t] int         the number of images that never reach t
+    and mean_iou (max_clicks + 1,), the mean curve."""
+    ious = np.asarray(ious, dtype=np.float64)
+    max_clicks = int(max_clicks)
+    if ious.ndim != 2 or ious.shape[1] != max_clicks + 1:
+        raise ValueError(f"ious must be (B, {max_clicks + 1}), got {ious.shape}")
+    noc, nof = {}, {}
+    for t in targets:
+        t = float(t)
+        hit = ious >= t
+        reached = hit.any(axis=1)
+        noc[t] = np.where(reached, hit.argmax(axis=1), max_clicks).astype(np.int64)
+        nof[t] = int((~reached).sum())
+    mean = ious.mean(axis=0) if len(ious) else np.zeros(max_clicks + 1)
+    return {"noc": noc, "nof": nof, "mean_iou": mean}

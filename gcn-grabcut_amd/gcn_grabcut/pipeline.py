@@ -327,8 +327,12 @@ class GCNGrabCutPipeline:
                              edge_aware: bool = True, filter_radius: int = 8, compose: bool = True,
                              timing: Optional[dict] = None, grabcut_lanes: Optional[int] = None,
                              chunks: Optional[int] = None, hints=None, hint_radius: int = 5, hint_region: bool = False,
-                             hints_as_prior: bool = False) -> dict:
+                             hints_as_prior: bool = False, return_state: bool = False) -> dict:
         """bgr: (B,H,W,3) uint8 tensor on the pipeline's device.  Returns device tensors.
+
+        return_state=True (additive) also returns what a GC_EVAL edit loop continues from: "gc_binary" (B,H,W) uint8,
+        GrabCut's own binary mask before clean_mask; "bgd" / "fgd" (B,65) float64, the colour models; "gc_image"
+        (B,H,W,3) uint8, the image in GrabCutConfig.color_space (bgr itself for "rgb").  "gc_mask" is returned either way.
 
         User clicks (additive): hints is None, a list with one None or (fg_points, bg_points) per image ((row, col) pairs,
         as encode_user_hints takes them), or a packed (hints, hint_ptr) pair (graph_builder.pack_hints).  They are hard
@@ -356,7 +360,7 @@ class GCNGrabCutPipeline:
         if n_chunks > 1 and b >= 2 * n_chunks:
             return self._segment_pipelined(bgr, self.chunk_plan(b, n_chunks, self.chunk_ratio), cs, threshold_fg, threshold_bg,
                                            refine_iters, min_area_ratio, keep_largest, edge_aware, filter_radius, compose, timing,
-                                           hints)
+                                           hints, return_state)
 
         def tick():
             if timing is not None:
@@ -395,6 +399,8 @@ class GCNGrabCutPipeline:
             post(eng, 0, bgr.size(0), binary)
         out = {"binary_mask": cleaned, "trimap": trimap, "segments": seg, "graphs": graphs, "probs": probs,
                "gc_mask": mask}
+        if return_state:
+            out.update(gc_binary=binary, bgd=bgd, fgd=fgd, gc_image=gc_img)
         if compose:
             out["overlay"], out["rgba"] = overlay, rgba
         if timing is not None:
@@ -402,7 +408,7 @@ class GCNGrabCutPipeline:
         return out
 
     def _segment_pipelined(self, bgr, plan, cs, threshold_fg, threshold_bg, refine_iters, min_area_ratio, keep_largest,
-                           edge_aware, filter_radius, compose, timing, hints=None) -> dict:
+                           edge_aware, filter_radius, compose, timing, hints=None, return_state=False) -> dict:
         """The software pipeline behind segment_batch_device: chunk k's GrabCut lane starts as soon as chunk k's trimaps are
         on the device; the caller's stream goes on with chunk k+1's SLIC / graph / network / trimap."""
         import torch
@@ -424,6 +430,11 @@ class GCNGrabCutPipeline:
         cleaned = eng.empty(b, h, w, dtype=torch.uint8)
         overlay = eng.empty(b, h, w, 3, dtype=torch.uint8) if compose else None
         rgba = eng.empty(b, h, w, 4, dtype=torch.uint8) if compose else None
+        if return_state:
+            st_binary = eng.empty(b, h, w, dtype=torch.uint8)
+            st_bgd = eng.empty(b, 65, dtype=torch.float64)
+            st_fgd = eng.empty(b, 65, dtype=torch.float64)
+            st_image = bgr if cs == "rgb" else eng.empty(b, h, w, 3, dtype=torch.uint8)
         n_iter, seed = self.gc_config.n_iter, self.gc_config.seed
         t_host = time.perf_counter()
         stamps = []                                   # per chunk: events around its front stages / its lane's work
@@ -441,6 +452,12 @@ class GCNGrabCutPipeline:
                 binary, _, bgd, fgd = leng.grabcut(gc_img, m, n_iter, 0, None, seed + lo)
                 if refine_iters > 0:
                     binary, _, bgd, fgd = leng.grabcut(gc_img, m, refine_iters, 2, None, seed + lo, bgd, fgd)
+                if return_state:
+                    st_binary[lo:hi].copy_(binary)
+                    st_bgd[lo:hi].copy_(bgd)
+                    st_fgd[lo:hi].copy_(fgd)
+                    if cs != "rgb":
+                        st_image[lo:hi].copy_(gc_img)
                 if ev is not None:
                     ev[1].record(stream)
                 leng.clean_mask(binary, min_area_ratio, keep_largest, out=cleaned[lo:hi])
@@ -474,6 +491,8 @@ class GCNGrabCutPipeline:
         for f in futures:
             caller.wait_event(f.result())             # whatever the caller enqueues next sees the lanes' outputs
         out = {"binary_mask": cleaned, "trimap": trimap, "segments": seg, "graphs": graphs, "probs": probs, "gc_mask": mask}
+        if return_state:
+            out.update(gc_binary=st_binary, bgd=st_bgd, fgd=st_fgd, gc_image=st_image)
         if compose:
             out["overlay"], out["rgba"] = overlay, rgba
         if timing is not None:                        # stage times from stream events (the stages overlap: they add up to more than the wall time)
@@ -501,6 +520,104 @@ class GCNGrabCutPipeline:
         return [SegmentationResult(image=imgs[i], binary_mask=host["binary_mask"][i], trimap=host["trimap"][i],
                                    segments=host["segments"][i], overlay=host["overlay"][i], rgba=host["rgba"][i],
                                    timing=dict(per_image)) for i in range(len(imgs))]
+
+    def _click_round(self, binary, gt, mask, image, bgd, fgd, hint_ptr, hint_radius=5, n_iter=1):
+        """One round of the NoC protocol on a device-resident batch: the next click per image on GrabCut's binary mask,
+        painted into the mask as one hint per image (hint_ptr = arange(B+1); an image without a click has row -1, which
+        ggc_apply_hints ignores), GC_EVAL for n_iter iterations from the kept models, IoU.
+        -> (click (B,4) int32, binary, mask, bgd, fgd, iou (B,) float64), all on the device."""
+        eng = self._eng
+        click = eng.next_click(binary, gt)
+        eng.apply_hints(mask, click[:, :3].contiguous(), hint_ptr, hint_radius)
+        b, want = binary.size(0), max(self.grabcut_lanes, 1)
+        lanes = want if b >= 8 * want else 1
+        binary, mask, bgd, fgd = eng.grabcut_lanes(image, mask, n_iter, 2, self.gc_config.seed, lanes, bgd, fgd)
+        return (click, binary, mask, bgd, fgd, eng.iou(binary, gt)[0])
+
+    def evaluate_clicks(self, images: Sequence[np.ndarray], gt_masks: Sequence[np.ndarray], max_clicks: int = 20,
+                        iou_targets=(0.85, 0.90), hint_radius: int = 5, iters_per_click: int = 1,
+                        stop_iou: Optional[float] = None, return_masks: bool = False) -> dict:
+        """Click guidance scored by the standard NoC protocol (additive), for equally sized BGR images and their ground
+        truth (H,W) masks (nonzero = foreground).
+
+        The automatic pipeline runs once; then, max_clicks times, a simulated user clicks the centre of the largest error
+        region of every image (ggc_next_click), the click is painted as a disk of hint_radius pixels (ggc_apply_hints) and
+        GrabCut continues in GC_EVAL mode for iters_per_click iterations from the kept mask and colour models; IoU is
+        measured after each click (ggc_mask_iou).  Everything is scored on GrabCut's own binary mask, not on the
+        clean_mask output of segment(): clean_mask can delete a clicked component, and the simulated user would then click
+        the same place again and again.  With stop_iou, an image whose IoU reaches it gets no further clicks and its
+        results stay frozen (the others continue as a compacted batch; a click round does not depend on an image's
+        position in the batch, so every image gets what a one-image loop gives it).  The loop stays on the device: per
+        round the host reads only ggc_apply_hints' hint_ptr and the IoU vector.
+
+        Returns {"clicks": per image a list of (row, col, label) with label 1 = foreground, "ious": (B, max_clicks + 1)
+        float64 (IoU after 0..max_clicks clicks; a stopped image repeats its last value), "noc": {t: (B,) int},
+        "nof": {t: int}, "mean_iou": (max_clicks + 1,)} (metrics.noc_summary), and with return_masks=True "masks":
+        (B, max_clicks + 1, H, W) uint8, GrabCut's label mask after each click."""
+        import torch
+        from .metrics import noc_summary
+        imgs = [_check_image(im) for im in images]
+        if not imgs:
+            raise ValueError("evaluate_clicks needs at least one image")
+        if any(im.shape != imgs[0].shape for im in imgs):
+            raise ValueError("evaluate_clicks needs images of one size; group them by shape")
+        gts = [np.asarray(g) for g in gt_masks]
+        if len(gts) != len(imgs):
+            raise ValueError(f"{len(gts)} ground-truth masks for {len(imgs)} images")
+        if any(g.shape != imgs[0].shape[:2] for g in gts):
+            raise ValueError(f"every ground-truth mask must be {imgs[0].shape[:2]} like its image")
+        max_clicks, iters_per_click = int(max_clicks), int(iters_per_click)
+        if max_clicks < 0 or iters_per_click < 1 or int(hint_radius) < 0:
+            raise ValueError("max_clicks >= 0, iters_per_click >= 1 and hint_radius >= 0 are required")
+        eng = self._eng
+        b = len(imgs)
+        gt = eng.to_device(np.stack([(g != 0) for g in gts]).astype(np.uint8))
+        out = self.segment_batch_device(eng.to_device(np.stack(imgs)), compose=False, return_state=True)
+        binary, mask, bgd, fgd, image = out["gc_binary"], out["gc_mask"], out["bgd"], out["fgd"], out["gc_image"]
+        ious = np.zeros((b, max_clicks + 1))
+        ious[:, 0] = eng.iou(binary, gt)[0].cpu().numpy()
+        clicks_dev = torch.full((b, max(max_clicks, 1), 4), -1, dtype=torch.int32, device=eng.device)
+        masks = None
+        if return_masks:
+            masks = eng.empty(b, max_clicks + 1, *binary.shape[1:], dtype=torch.uint8)
+            masks[:, 0] = mask
+        active = np.arange(b)                              # images still being clicked, in batch order
+        idx_dev = torch.arange(b, device=eng.device)
+
+        def compact(keep):
+            nonlocal active, idx_dev, binary, mask, bgd, fgd, image, gt
+            sel = torch.from_numpy(np.nonzero(keep)[0]).to(eng.device)
+            active = active[keep]
+            idx_dev, binary, mask, gt = (t.index_select(0, sel) for t in (idx_dev, binary, mask, gt))
+            bgd, fgd, image = (t.index_select(0, sel) for t in (bgd, fgd, image))
+
+        if stop_iou is not None and (ious[:, 0] >= stop_iou).any():
+            compact(ious[:, 0] < stop_iou)
+        ptrs: dict[int, "torch.Tensor"] = {}
+        for k in range(1, max_clicks + 1):
+            ious[:, k] = ious[:, k - 1]                     # frozen unless the image is still active
+            if masks is not None:
+                masks[:, k] = masks[:, k - 1]
+            if len(active) == 0:
+                continue
+            n = len(active)
+            if n not in ptrs:
+                ptrs[n] = torch.arange(n + 1, dtype=torch.int32, device=eng.device)
+            click, binary, mask, bgd, fgd, iou = self._click_round(binary, gt, mask, image, bgd, fgd, ptrs[n], hint_radius,
+                                                                   iters_per_click)
+            clicks_dev[idx_dev, k - 1] = click
+            ious[active, k] = iou.cpu().numpy()
+            if masks is not None:
+                masks[idx_dev, k] = mask
+            if stop_iou is not None and (ious[active, k] >= stop_iou).any():
+                compact(ious[active, k] < stop_iou)
+        host_clicks = clicks_dev.cpu().numpy()
+        clicks = [[(int(r), int(c), int(l)) for r, c, l, _ in host_clicks[i, :max_clicks] if r >= 0] for i in range(b)]
+        res = {"clicks": clicks, "ious": ious}
+        res.update(noc_summary(ious, iou_targets, max_clicks))
+        if masks is not None:
+            res["masks"] = masks.cpu().numpy()
+        return res
 
     # ------------------------------------------------------------ reference API
     def segment(self, image: np.ndarray, threshold_fg: float = 0.55, threshold_bg: float = 0.55,

@@ -49,7 +49,8 @@
 extern "C" {
 #endif
 
-#define GGC_VERSION 330 /* 0.3.3: ggc_apply_hints (user clicks as hard constraints on the GrabCut mask);
+#define GGC_VERSION 340 /* 0.3.4: ggc_next_click (the next simulated click of the NoC protocol);
+                           0.3.3: ggc_apply_hints (user clicks as hard constraints on the GrabCut mask);
                            0.3.2: ResGCNNet (forward and ggc_train_*), GATTrimapNet and ggc_gcn_aggregate at widths up to 256;
                            0.3.1: ggc_train_* (graph operators of the ResGCNNet training forward and their backward) */
 
@@ -373,6 +374,20 @@ int ggc_grabcut(ggc_ctx* ctx, ggc_stream stream, int B, int H, int W,
 int ggc_apply_hints(ggc_ctx* ctx, ggc_stream stream, int B, int H, int W, const int32_t* hints, const int32_t* hint_ptr,
                     int radius, int region, const int32_t* segments, const int32_t* node_ptr,
                     float* node_hints, uint8_t* mask);
+
+/* C0 — next simulated click per image (additive; the standard NoC protocol of interactive segmentation).
+ *   pred [dev] u8  [B,H,W]  current binary mask (nonzero = foreground)
+ *   gt   [dev] u8  [B,H,W]  ground truth (nonzero = foreground; {0,1} and {0,255} both work)
+ *   out  [dev] i32 [B,4]    row, col, label (1 = fg, 0 = bg), d2; row = col = label = -1, d2 = 0 when pred == gt
+ * fn = gt & !pred, fp = !gt & pred.  d2(p) of a pixel of region R is the smallest squared Euclidean distance to a pixel
+ * not in R, pixels outside the image counting as not in R (ndimage.distance_transform_edt(np.pad(R, 1))[1:-1, 1:-1]**2).
+ * With Mfn, Mfp the maxima of d2 over fn and fp, the click is positive (in fn) iff Mfn > Mfp, else negative (in fp): a
+ * tie goes to the background click.  It lies at the chosen region's pixel of largest d2, the smallest raster index
+ * y*W + x among equals.  Integer arithmetic and integer atomics only: the result does not depend on launch order.
+ * H <= 65535 and W <= 8192, else GGC_E_INVALID_ARG (as for B < 0 or B > 65535); B == 0 is a no-op.  Scratch: 4 bytes
+ * per pixel from the context.  Does not synchronise. */
+int ggc_next_click(ggc_ctx* ctx, ggc_stream stream, int B, int H, int W,
+                   const uint8_t* pred, const uint8_t* gt, int32_t* out);
 
 /* K0 — replaces clean_mask (pipeline.py:189-227); 8-connected components.
  *   mask_in/mask_out [dev] u8 [B,H,W] in {0,1} (may alias) */

@@ -82,6 +82,36 @@ def read_bgr(path: Path, max_size: int):
     return np.ascontiguousarray(np.asarray(im)[:, :, ::-1])
 
 
+def load_model(checkpoint: str, model_name: str = "resgcn", hidden: int = 128, layers: int = 6, device: str = "cuda",
+               tag: str = "inference"):
+    """The trimap network of a train.py checkpoint, in eval mode; its width and depth come from the checkpoint."""
+    import torch
+    from src.gcn_grabcut.model import GATTrimapNet, GCNTrimapNet, ResGCNNet
+
+    if not torch.cuda.is_available():
+        raise SystemExit(f"[{tag}] no MI355X visible: this build has no CPU path")
+    model_cls = {"resgcn": ResGCNNet, "gcn": GCNTrimapNet, "gat": GATTrimapNet}[model_name]
+
+    ckpt_path = Path(checkpoint)
+    if not ckpt_path.exists():
+        fallback = Path("checkpoints/final_model.pt")
+        if not fallback.exists():
+            raise FileNotFoundError(f"No checkpoint at {ckpt_path} (or {fallback}). Train one with train.py.")
+        print(f"[{tag}] {ckpt_path} not found, using {fallback}")
+        ckpt_path = fallback
+    state = torch.load(ckpt_path, map_location="cpu", weights_only=True)["model"]
+    # width and depth are recovered from the checkpoint (reference inference.py:81-86)
+    hidden = state["input_proj.0.weight"].shape[0] if "input_proj.0.weight" in state else hidden
+    layers = (sum(1 for k in state if k.startswith("gcn_layers.") and k.endswith(".bias"))
+              or sum(1 for k in state if k.startswith("blocks.") and k.endswith(".conv.bias"))
+              or sum(1 for k in state if k.startswith("convs.") and k.endswith(".att")) or layers)
+    model = model_cls(hidden_channels=hidden, n_layers=layers)
+    model.load_state_dict(state)
+    model.eval()
+    print(f"[{tag}] loaded {model_cls.__name__} (D={hidden}, n={layers}) from {ckpt_path} on {device}")
+    return model
+
+
 def main() -> None:
     parser = build_parser()
     args = parser.parse_args()
@@ -89,33 +119,11 @@ def main() -> None:
         parser.error("--fg-point / --bg-point are clicks on one image: use them with --image, not --input")
     if args.hint_radius < 0:
         parser.error("--hint-radius must be >= 0")
-    import torch
     from src.gcn_grabcut import GCNGrabCutPipeline
     from src.gcn_grabcut.graph_builder import SuperpixelGraphConfig
-    from src.gcn_grabcut.model import GATTrimapNet, GCNTrimapNet, ResGCNNet
     from src.gcn_grabcut.pipeline import _colour_trimap, _write_png
 
-    if not torch.cuda.is_available():
-        raise SystemExit("[inference] no MI355X visible: this build has no CPU path")
-    model_cls = {"resgcn": ResGCNNet, "gcn": GCNTrimapNet, "gat": GATTrimapNet}[args.model]
-
-    ckpt_path = Path(args.checkpoint)
-    if not ckpt_path.exists():
-        fallback = Path("checkpoints/final_model.pt")
-        if not fallback.exists():
-            raise FileNotFoundError(f"No checkpoint at {ckpt_path} (or {fallback}). Train one with train.py.")
-        print(f"[inference] {ckpt_path} not found, using {fallback}")
-        ckpt_path = fallback
-    state = torch.load(ckpt_path, map_location="cpu", weights_only=True)["model"]
-    # width and depth are recovered from the checkpoint (reference inference.py:81-86)
-    hidden = state["input_proj.0.weight"].shape[0] if "input_proj.0.weight" in state else args.hidden
-    layers = (sum(1 for k in state if k.startswith("gcn_layers.") and k.endswith(".bias"))
-              or sum(1 for k in state if k.startswith("blocks.") and k.endswith(".conv.bias"))
-              or sum(1 for k in state if k.startswith("convs.") and k.endswith(".att")) or args.layers)
-    model = model_cls(hidden_channels=hidden, n_layers=layers)
-    model.load_state_dict(state)
-    model.eval()
-    print(f"[inference] loaded {model_cls.__name__} (D={hidden}, n={layers}) from {ckpt_path} on {args.device}")
+    model = load_model(args.checkpoint, args.model, args.hidden, args.layers, args.device)
 
     pipeline = GCNGrabCutPipeline(model, sp_config=SuperpixelGraphConfig(n_segments=args.superpixels), device=args.device)
 
