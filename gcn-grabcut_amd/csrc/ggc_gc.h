@@ -24,6 +24,44 @@ __device__ __forceinline__ int dir_nb(const GcDims& d, int y, int x, int dir) {
 // relabel visit.
 __host__ __device__ __forceinline__ size_t rc_idx(int dir, size_t i) { return i * 8 + (size_t)dir; }
 
+// One pixel of the network, the per-pixel part of graph construction (ggc_grabcut's k_build_graph, ggc_grid_maxflow's
+// k_gf_build): residual arcs from the n-link planes nw [4][B][P] (0 left, 1 up-left, 2 up, 3 up-right; a link that points
+// outside the image is ignored), the arc mask, and the terminal balance of the t-link difference tw (source minus sink).
+__device__ __forceinline__ void mf_init_pixel(const GcDims& d, int b, int p, int32_t tw, const int32_t* __restrict__ nw,
+                                              int32_t* __restrict__ rc, int32_t* __restrict__ ex, int32_t* __restrict__ snk,
+                                              uint8_t* __restrict__ rmask, bool warm) {
+    const size_t BP = (size_t)d.B * d.P, i = (size_t)b * d.P + p;
+    const int y = p / d.W, x = p % d.W;
+    const int32_t* nwb = nw + (size_t)b * d.P;
+    // own planes give the arcs towards left / up-left / up / up-right; the mirrored arcs read the neighbour's plane
+    const int dirs[4] = {0, 4, 2, 6};
+    int32_t inflow = 0;
+    int arcs = 0;                                        // bit dir = residual arc towards dir (the push visits of ggc_maxflow*.hip keep it current)
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int dir = dirs[k];
+        const int32_t c0 = dir_nb(d, y, x, dir) >= 0 ? nwb[(size_t)k * BP + p] : 0;
+        const int q = dir_nb(d, y, x, dir ^ 1);
+        const int32_t c1 = q >= 0 ? nwb[(size_t)k * BP + q] : 0;
+        if (warm) {   // keep the n-link flow of the previous solve: net inflow = sum (residual - capacity)
+            const int32_t ra = rc[rc_idx(dir, i)], rb = rc[rc_idx((dir ^ 1), i)];
+            inflow += (ra - c0) + (rb - c1);
+            arcs |= (ra > 0 ? 1 << dir : 0) | (rb > 0 ? 1 << (dir ^ 1) : 0);
+        } else {
+            rc[rc_idx(dir, i)] = c0;
+            rc[rc_idx((dir ^ 1), i)] = c1;
+            arcs |= (c0 > 0 ? 1 << dir : 0) | (c1 > 0 ? 1 << (dir ^ 1) : 0);
+        }
+    }
+    rmask[i] = (uint8_t)arcs;
+    // Warm start (dynamic graph cuts): only the t-links change between solves, and adding a constant to both t-links of a
+    // pixel never changes the cut, so the old n-link flow stays a valid preflow: the pixel's new terminal balance is its
+    // t-link difference plus what its neighbours sent it.
+    const int32_t bal = tw + inflow;
+    ex[i] = bal > 0 ? bal : 0;
+    snk[i] = bal < 0 ? -bal : 0;
+}
+
 // The max-flow's words in ggc_grabcut's control block, which the start of every call zeroes.
 struct MfControl {
     int32_t* active;   // [B] active pixels per image (excess that can still reach the sink)

@@ -486,7 +486,7 @@ __global__ void __launch_bounds__(256) k_nweights(GcDims d, const uint8_t* __res
     }
 }
 
-// constructGCGraph: t-links cancelled against each other, clamped to +-lambda; residual arcs from the n-link planes
+// constructGCGraph: t-links cancelled against each other, clamped to +-lambda; residual arcs from the n-link planes (mf_init_pixel)
 __global__ void __launch_bounds__(256) k_build_graph(GcDims d, const uint8_t* __restrict__ img,
                                                      const uint8_t* __restrict__ mask, const int32_t* __restrict__ state,
                                                      const Gmm* __restrict__ gmm, const int32_t* __restrict__ nw,
@@ -494,10 +494,8 @@ __global__ void __launch_bounds__(256) k_build_graph(GcDims d, const uint8_t* __
                                                      int32_t* __restrict__ snk, uint8_t* __restrict__ rmask, int warm) {
     // one image per grid row: the image index is uniform, so the two GMMs (140 doubles) come through scalar loads
     const int b = blockIdx.y, p = blockIdx.x * blockDim.x + threadIdx.x;
-    const size_t BP = (size_t)d.B * d.P;
     if (p >= d.P || state[b]) return;
     const size_t i = (size_t)b * d.P + p;
-    const int y = p / d.W, x = p % d.W;
     const uint8_t m = mask[i];
     // Warm start, definite pixel: its t-link (+-lambda) is what it was, so the new balance tw + inflow equals the old one —
     // and a finished solve leaves no pixel with both excess and sink capacity, so excess, sink link, capacities and arc
@@ -515,35 +513,7 @@ __global__ void __launch_bounds__(256) k_build_graph(GcDims d, const uint8_t* __
         if (dv > LAMBDA) dv = LAMBDA;
         if (dv < -LAMBDA) dv = -LAMBDA;
     }
-    const int32_t tw = (int32_t)rint(dv * CAP_SCALE);
-    const int32_t* nwb = nw + (size_t)b * d.P;
-    // own planes give the arcs towards left / up-left / up / up-right; the mirrored arcs read the neighbour's plane
-    const int dirs[4] = {0, 4, 2, 6};
-    int32_t inflow = 0;
-    int arcs = 0;                                        // bit dir = residual arc towards dir (the push visits of ggc_maxflow*.hip keep it current)
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const int dir = dirs[k];
-        const int32_t c0 = dir_nb(d, y, x, dir) >= 0 ? nwb[(size_t)k * BP + p] : 0;
-        const int q = dir_nb(d, y, x, dir ^ 1);
-        const int32_t c1 = q >= 0 ? nwb[(size_t)k * BP + q] : 0;
-        if (warm) {   // keep the n-link flow of the previous iteration: net inflow = sum (residual - capacity)
-            const int32_t ra = rc[rc_idx(dir, i)], rb = rc[rc_idx((dir ^ 1), i)];
-            inflow += (ra - c0) + (rb - c1);
-            arcs |= (ra > 0 ? 1 << dir : 0) | (rb > 0 ? 1 << (dir ^ 1) : 0);
-        } else {
-            rc[rc_idx(dir, i)] = c0;
-            rc[rc_idx((dir ^ 1), i)] = c1;
-            arcs |= (c0 > 0 ? 1 << dir : 0) | (c1 > 0 ? 1 << (dir ^ 1) : 0);
-        }
-    }
-    rmask[i] = (uint8_t)arcs;
-    // Warm start (dynamic graph cuts): only the t-links change between GrabCut iterations, and adding a
-    // constant to both t-links of a pixel never changes the cut, so the old n-link flow stays a valid
-    // preflow: the pixel's new terminal balance is its t-link difference plus what its neighbours sent it.
-    const int32_t bal = tw + inflow;
-    ex[i] = bal > 0 ? bal : 0;
-    snk[i] = bal < 0 ? -bal : 0;
+    mf_init_pixel(d, b, p, (int32_t)rint(dv * CAP_SCALE), nw, rc, ex, snk, rmask, warm != 0);
 }
 
 // estimateSegmentation: probable pixels take the side of the cut; foreground = cannot reach the sink

@@ -69,6 +69,7 @@ SIGNATURES = {
     "ggc_apply_hints": [_vp, _vp, _i, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp],
     "ggc_next_click": [_vp, _vp, _i, _i, _i, _vp, _vp, _vp],
     "ggc_grabcut": [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _u64, _vp],
+    "ggc_grid_maxflow": [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp],
     "ggc_clean_mask": [_vp, _vp, _i, _i, _i, _vp, _f, _i, _vp],
     "ggc_compose_outputs": [_vp, _vp, _i, _i, _i, _vp, _vp, _f, _i, _i, _i, _vp, _vp],
     "ggc_mask_iou": [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp],

@@ -34,7 +34,8 @@
  *   GGC_MF_DENSE_LAUNCHES0=n / GGC_MF_DENSE_LAUNCHES=n   push launches of the first / a later dense round (8 / 12)
  *   GGC_MF_DENSE_SWEEPS=n         sweeps per dense push visit (8)
  *   GGC_MF_RELAX_DENSE=n          work-list launches of a global relabel before the asynchronous launch takes over (3)
- *   GGC_MF_PARTIAL_ROUNDS=n       first rounds of a solve whose relabel stops after those launches (3; 0 = every relabel exact)
+ *   GGC_MF_PARTIAL_ROUNDS=n       first rounds of a solve whose relabel stops after those launches (3; 0 = every relabel exact;
+ *                                 0..64, larger values are clamped to 64: a partial round never closes an image)
  *   GGC_AGG_DIRECT=1              GCNConv gather straight from L2 instead of the graph-resident kernel
  *   GGC_SLIC_SEQ_CONNECTIVITY=1   literal one-thread-per-image replay of skimage's connectivity pass (A/B reference)
  * The Python binding adds GGC_HIP_LIBRARY=<path> (load another build of the library, tools/build_variant.sh).
@@ -49,7 +50,8 @@
 extern "C" {
 #endif
 
-#define GGC_VERSION 340 /* 0.3.4: ggc_next_click (the next simulated click of the NoC protocol);
+#define GGC_VERSION 350 /* 0.3.5: ggc_grid_maxflow (the GrabCut max-flow on a caller's network, a test hook);
+                           0.3.4: ggc_next_click (the next simulated click of the NoC protocol);
                            0.3.3: ggc_apply_hints (user clicks as hard constraints on the GrabCut mask);
                            0.3.2: ResGCNNet (forward and ggc_train_*), GATTrimapNet and ggc_gcn_aggregate at widths up to 256;
                            0.3.1: ggc_train_* (graph operators of the ResGCNNet training forward and their backward) */
@@ -353,6 +355,23 @@ int ggc_grabcut(ggc_ctx* ctx, ggc_stream stream, int B, int H, int W,
                 const uint8_t* image, uint8_t* mask, const int32_t* rects,
                 double* bgd_model, double* fgd_model, int n_iter, int mode,
                 uint64_t seed, uint8_t* binary);
+
+/* C5 — the max-flow of ggc_grabcut on a given network (additive; a test hook that runs the production solver).
+ * Per image an 8-neighbour grid with int32 capacities, in k_build_graph's layout:
+ *   tw  [dev] i32 [n_steps,B,H,W]  t-link difference, source minus sink (> 0: source link, < 0: sink link)
+ *   nw  [dev] i32 [4,B,H,W]        undirected n-links of each pixel towards left, up-left, up, up-right; a link that points
+ *                                  outside the image is ignored (never read, never checked)
+ *   source_side [dev] u8 [n_steps,B,H,W]  out: 1 = the pixel cannot reach the sink in the final residual graph of that step
+ *   residual    [dev] i32 [B,H,W,10] out, may be NULL: the final state of the last step — residual capacities of the 8 arcs
+ *               (0 left, 1 right, 2 up, 3 down, 4 up-left, 5 down-right, 6 up-right, 7 down-left), excess, residual sink
+ *               capacity (a maximum preflow: excess that cannot reach the sink stays where it is)
+ * Step 0 solves cold; a later step changes only tw and starts from the previous step's flow as a GrabCut iteration does
+ * (GGC_MF_WARM).  Bounds: |tw| <= 2^27 and 0 <= nw <= 2^24 for every in-image link (GrabCut's own t-links are at most
+ * 117 964 800 < 2^27 and its n-links at most 13 107 200 < 2^24), which keeps the largest excess, about 3 * 2^27, inside
+ * int32; a value outside them, B, H, W or n_steps < 1, or a NULL tw, nw or source_side is GGC_E_INVALID_ARG before any
+ * solve.  SYNCHRONISES. */
+int ggc_grid_maxflow(ggc_ctx* ctx, ggc_stream stream, int B, int H, int W, int n_steps,
+                     const int32_t* tw, const int32_t* nw, uint8_t* source_side, int32_t* residual);
 
 /* H0 — user clicks as hard constraints (additive; reference graph_builder.py:457-494, batched).
  *   hints    [dev] i32 [K,3] = (row, col, label) with label 0 = background, nonzero = foreground;

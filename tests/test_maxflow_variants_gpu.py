@@ -3,7 +3,11 @@
 The cut of an integer network is canonical, so which phases run as asynchronous single launches, how long a round is,
 whether the flow of the previous GrabCut iteration is kept and whether the per-round trace is on must not change a single
 pixel.  The switches are the documented GGC_MF_* variables of include/ggc.h, which the library reads ONCE per process,
-so each variant runs in its own interpreter (one at a time: a GPU box admits few processes on its card)."""
+so each variant runs in its own interpreter (one at a time: a GPU box admits few processes on its card).
+
+Each child also puts the schedule through the networks of tests/maxflow_nets.py that target its fragile parts (a long
+serpentine corridor, walls crossed only at tile corners, min cuts on tile borders, warm steps whose t-links flip sign) via
+ggc_grid_maxflow: the oracle's cut at every step and the max-flow/min-cut certificate of the final state."""
 import os
 import subprocess
 import sys
@@ -42,6 +46,17 @@ for i in range(b):
     wb, wm, *_ = orc.grabcut(imgs[i], tris[i], n_iter=n_iter, mode=0, seed=5 + i)
     assert np.array_equal(got[i], wm), (i, int((got[i] != wm).sum()))
 print("variant ok")
+import maxflow_nets as mn
+for fam, var, h, w in [("serpentine", "mid_bottleneck", 96, 128), ("corner_gates", "gates", 200, 272),
+                       ("border_bottlenecks", "tiles_32x8", 200, 272), ("border_bottlenecks", "tiles_32x32", 200, 272),
+                       ("warm", "resample", 200, 272)]:
+    tw, nw = mn.make(fam, var, h, w, seed=21)
+    side, res = mn.solve(ctx, [(tw, nw)])
+    for s in range(tw.shape[0]):
+        flow, want = orc.grid_maxflow(tw[s], nw)
+        assert np.array_equal(side[s, 0], want), (fam, var, s, int((side[s, 0] != want).sum()))
+    mn.certify(tw[-1], nw, side[-1, 0], res[0], flow, cold=tw.shape[0] == 1)
+print("stress ok")
 """
 
 VARIANTS = {
@@ -54,6 +69,7 @@ VARIANTS = {
     "async_tiles_32x32_short_chains": {"GGC_MF_ASYNC_TILE": "32", "GGC_MF_ASYNC_HOPS": "8"},
     "short_dense_rounds": {"GGC_MF_DENSE_LAUNCHES0": "3", "GGC_MF_DENSE_LAUNCHES": "2", "GGC_MF_DENSE_SWEEPS": "4", "GGC_MF_RELAX_DENSE": "4"},
     "trace": {"GGC_MF_TRACE": "1"},                   # the clocked relabel kernel and the per-round readout
+    "partial_rounds_clamped": {"GGC_MF_PARTIAL_ROUNDS": "5000"},   # clamped to 64: above the round cap it failed every solve
 }
 
 
@@ -63,5 +79,6 @@ def test_driver_variant_matches_oracle(name, oracle):
     env.update(VARIANTS[name])
     r = subprocess.run([sys.executable, "-c", CHILD.format(root=str(ROOT))], env=env, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0 and "variant ok" in r.stdout, f"{name}: rc {r.returncode}\n{r.stdout[-2000:]}\n{r.stderr[-4000:]}"
+    assert "stress ok" in r.stdout, f"{name}: stress networks\n{r.stdout[-2000:]}\n{r.stderr[-4000:]}"
     if "GGC_MF_TRACE" in VARIANTS[name]:
         assert "[ggc maxflow] round" in r.stderr, f"{name}: no trace on stderr\n{r.stderr[-4000:]}"
