@@ -56,13 +56,15 @@ __host__ __device__ inline double det_pow24(double a) {
 // ---- exp / log for the GrabCut GMM likelihoods and n-link weights (cv2.grabCut
 // uses libm).  Fixed operation sequences so that quantised
 // capacities and component assignments — and with them the final masks — are
-// identical on the CPU reference path.  Accuracy ~1 ulp (tests).
+// identical on the CPU reference path.  Accuracy <= 2 ulp of libm over the whole range, subnormal results and
+// arguments included (tests/test_grabcut_ref_cpu.py): gmm_comp scales exp(-mahal/2) by det^-1/2 (up to 1000), so a
+// subnormal exponential can still make a normal likelihood.  Same sequences as oracle/mathfn.c.
 __host__ __device__ inline double det_exp(double x) {
     const double LN2_HI = 6.93147180369123816490e-01, LN2_LO = 1.90821492927058770002e-10;
     const double INV_LN2 = 1.44269504088896338700e+00;
     if (x != x) return x;
-    if (x < -708.0) return 0.0;
-    if (x > 709.0) return bits_to_double(0x7FF0000000000000ULL);
+    if (x < -745.2) return 0.0;                                       // exp(x) rounds to 0 below -745.1332
+    if (x > 709.782712893384) return bits_to_double(0x7FF0000000000000ULL);
     const double k = rint(x * INV_LN2);
     const double r = (x - k * LN2_HI) - k * LN2_LO;
     double p = 1.0 / 6227020800.0;
@@ -79,6 +81,7 @@ __host__ __device__ inline double det_exp(double x) {
     p = p * r + 0.5;
     p = p * r + 1.0;
     p = p * r + 1.0;
+    // k in [-1075, 1024]: both factors normal, p * 2^k1 exact, one rounding (also into the subnormals)
     const long long ki = (long long)k;
     const long long k1 = ki / 2, k2 = ki - k1;
     return p * bits_to_double((uint64_t)(k1 + 1023) << 52) * bits_to_double((uint64_t)(k2 + 1023) << 52);
@@ -87,10 +90,12 @@ __host__ __device__ inline double det_exp(double x) {
 __host__ __device__ inline double det_log(double x) {
     const double LN2_HI = 6.93147180369123816490e-01, LN2_LO = 1.90821492927058770002e-10;
     if (x != x || x < 0.0) return bits_to_double(0x7FF8000000000000ULL);
-    if (x < 2.2250738585072014e-308) return bits_to_double(0xFFF0000000000000ULL);   // zero and subnormals
+    if (x == 0.0) return bits_to_double(0xFFF0000000000000ULL);
     if (x > 1.7976931348623157e308) return x;
+    long long e = -1023;
+    if (x < 2.2250738585072014e-308) { x = x * 18014398509481984.0; e -= 54; }      // subnormal: normalise (x 2^54)
     const uint64_t u = double_to_bits(x);
-    long long e = (long long)((u >> 52) & 0x7FF) - 1023;
+    e += (long long)((u >> 52) & 0x7FF);
     double m = bits_to_double((u & 0x000FFFFFFFFFFFFFULL) | 0x3FF0000000000000ULL);
     if (m > 1.4142135623730951) { m = m * 0.5; e += 1; }
     const double f = m - 1.0;

@@ -54,8 +54,11 @@ double rint(double);
 
 double ggo_exp(double x) {
     if (x != x) return x;
-    if (x < -708.0) return 0.0;        /* flushed: below ~1e-308 nothing downstream can tell */
-    if (x > 709.0) return 1.0 / 0.0;
+    /* Subnormal results are kept: gmm_comp multiplies exp(-mahal/2) by det^-1/2, which reaches 1000 after the
+     * singular-covariance fix, so exp(-712) = 1.6e-309 still makes a normal likelihood 1.6e-306 there.
+     * exp(x) rounds to 0 below -745.1332 (half the smallest subnormal) and overflows above log(DBL_MAX). */
+    if (x < -745.2) return 0.0;
+    if (x > 709.782712893384) return 1.0 / 0.0;
     const double k = rint(x * INV_LN2);
     const double r = (x - k * LN2_HI) - k * LN2_LO;
     /* exp(r), |r| <= 0.347: Taylor polynomial of degree 13, Horner */
@@ -73,7 +76,8 @@ double ggo_exp(double x) {
     p = p * r + 0.5;
     p = p * r + 1.0;
     p = p * r + 1.0;
-    /* scale by 2^k in two exact steps (k in [-1022, 1023]) */
+    /* scale by 2^k, k in [-1075, 1024], as p * 2^k1 * 2^k2 with k1 = trunc(k/2), k2 = k - k1 in [-538, 512]:
+     * both factors are normal and p * 2^k1 is exact, so the result is rounded once, also into the subnormals */
     const long long ki = (long long)k;
     const long long k1 = ki / 2, k2 = ki - k1;
     return p * from_bits((uint64_t)(k1 + 1023) << 52) * from_bits((uint64_t)(k2 + 1023) << 52);
@@ -81,10 +85,12 @@ double ggo_exp(double x) {
 
 double ggo_log(double x) {
     if (x != x || x < 0.0) return 0.0 / 0.0;
-    if (x < 2.2250738585072014e-308) return -1.0 / 0.0;   /* zero and subnormals */
+    if (x == 0.0) return -1.0 / 0.0;
     if (x > 1.7976931348623157e308) return x;
+    long long e = -1023;
+    if (x < 2.2250738585072014e-308) { x = x * 18014398509481984.0; e -= 54; }   /* subnormal: normalise (x 2^54) */
     uint64_t u = to_bits(x);
-    long long e = (long long)((u >> 52) & 0x7FF) - 1023;
+    e += (long long)((u >> 52) & 0x7FF);
     double m = from_bits((u & 0x000FFFFFFFFFFFFFULL) | 0x3FF0000000000000ULL);  /* [1, 2) */
     if (m > 1.4142135623730951) { m = m * 0.5; e += 1; }                         /* [sqrt(1/2), sqrt(2)) */
     const double f = m - 1.0;

@@ -57,6 +57,20 @@ for fam, var, h, w in [("serpentine", "mid_bottleneck", 96, 128), ("corner_gates
         assert np.array_equal(side[s, 0], want), (fam, var, s, int((side[s, 0] != want).sum()))
     mn.certify(tw[-1], nw, side[-1, 0], res[0], flow, cold=tw.shape[0] == 1)
 print("stress ok")
+import grabcut_ref as gr
+for fam, var in [("underflow", "one_side"), ("near_lambda", "sweep")]:
+    st = gr.make(fam, var, seed=3)
+    img = torch.as_tensor(st["img"][None]).cuda()
+    states = []
+    for k in range(4):
+        m = torch.as_tensor(st["mask"][None]).cuda(); bg = torch.as_tensor(st["bgd"][None]).cuda(); fg = torch.as_tensor(st["fgd"][None]).cuda()
+        bn = torch.empty_like(m)
+        ctx.call("ggc_grabcut", torch.cuda.current_stream().cuda_stream, 1, m.shape[1], m.shape[2], img.data_ptr(), m.data_ptr(),
+                 None, bg.data_ptr(), fg.data_ptr(), k, 2, 5, bn.data_ptr())
+        states.append((m[0].cpu().numpy(), bg[0].cpu().numpy(), fg[0].cpu().numpy()))
+    for k in range(1, 4):
+        gr.certify_step(orc, st["img"], *states[k - 1], *states[k], what=fam + " it" + str(k))
+print("certify ok")
 """
 
 VARIANTS = {
@@ -80,5 +94,6 @@ def test_driver_variant_matches_oracle(name, oracle):
     r = subprocess.run([sys.executable, "-c", CHILD.format(root=str(ROOT))], env=env, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0 and "variant ok" in r.stdout, f"{name}: rc {r.returncode}\n{r.stdout[-2000:]}\n{r.stderr[-4000:]}"
     assert "stress ok" in r.stdout, f"{name}: stress networks\n{r.stdout[-2000:]}\n{r.stderr[-4000:]}"
+    assert "certify ok" in r.stdout, f"{name}: certified GrabCut iterations\n{r.stdout[-2000:]}\n{r.stderr[-4000:]}"
     if "GGC_MF_TRACE" in VARIANTS[name]:
         assert "[ggc maxflow] round" in r.stderr, f"{name}: no trace on stderr\n{r.stderr[-4000:]}"
