@@ -272,6 +272,22 @@ class Engine:
                       int(tint_bgr[0]), int(tint_bgr[1]), int(tint_bgr[2]), overlay.data_ptr(), rgba.data_ptr())
         return overlay, rgba
 
+    def alpha_matte(self, bgr, binary, radius=4, eps=1e-4, want_rgba=False, out=None):
+        """Soft alpha matte of binary (B,H,W) uint8 (nonzero = foreground) under bgr (B,H,W,3) uint8 (ggc_alpha_matte).
+        -> alpha (B,H,W) float32 in [0,1], or (alpha, rgba (B,H,W,4) uint8) with want_rgba; out: the same, preallocated."""
+        check_matte_args(radius, eps)
+        b, h, w, _ = bgr.shape
+        if tuple(binary.shape) != (b, h, w):
+            raise ValueError(f"alpha_matte: binary {tuple(binary.shape)} does not match bgr {tuple(bgr.shape)}")
+        if out is not None:
+            alpha, rgba = out if want_rgba else (out, None)
+        else:
+            alpha = self.empty(b, h, w)
+            rgba = self.empty(b, h, w, 4, dtype=torch.uint8) if want_rgba else None
+        self.ctx.call("ggc_alpha_matte", self._stream(), b, h, w, bgr.data_ptr(), binary.data_ptr(), int(radius),
+                      float(eps), alpha.data_ptr(), _native.ptr(rgba))
+        return (alpha, rgba) if want_rgba else alpha
+
     def iou(self, pred, gt):
         """-> (iou (B,) float64, counts (B,3) int64 = tp, fp, fn), on device."""
         b, h, w = pred.shape
@@ -280,6 +296,18 @@ class Engine:
         self.ctx.call("ggc_mask_iou", self._stream(), b, h, w, pred.data_ptr(), gt.data_ptr(), iou.data_ptr(),
                       cnt.data_ptr())
         return iou, cnt
+
+
+MATTE_RADIUS_MAX = 64
+MATTE_EPS_MIN = 1e-12
+
+
+def check_matte_args(radius, eps) -> None:
+    """The argument range of ggc_alpha_matte, checked on the host so that a bad value is a ValueError."""
+    if int(radius) != radius or not 1 <= int(radius) <= MATTE_RADIUS_MAX:
+        raise ValueError(f"matte radius must be an integer in 1..{MATTE_RADIUS_MAX}, got {radius}")
+    if not (np.isfinite(eps) and float(eps) >= MATTE_EPS_MIN):
+        raise ValueError(f"matte eps must be finite and >= {MATTE_EPS_MIN:g}, got {eps}")
 
 
 def merge_graphs(parts: Sequence[DeviceGraphs], segments: torch.Tensor) -> DeviceGraphs:

@@ -46,12 +46,18 @@ class SegmentationResult:
     overlay: np.ndarray        # BGR with coloured overlay
     rgba: np.ndarray           # BGRA transparent background
     timing: dict = field(default_factory=dict)
+    alpha: Optional[np.ndarray] = None       # additive: (H, W) float32 soft matte in [0, 1] (matte=True)
+    rgba_soft: Optional[np.ndarray] = None   # additive: (H, W, 4) uint8 BGRA cut-out with alpha = round(255 alpha)
 
     def save(self, prefix: str = "result") -> None:
         _write_png(f"{prefix}_overlay.png", self.overlay)
         _write_png(f"{prefix}_rgba.png", self.rgba)
         _write_png(f"{prefix}_trimap_colour.png", _colour_trimap(self.trimap))
         _write_png(f"{prefix}_mask.png", self.binary_mask * 255)
+        if self.alpha is not None:
+            _write_png(f"{prefix}_alpha.png", alpha_to_u8(self.alpha))
+        if self.rgba_soft is not None:
+            _write_png(f"{prefix}_cutout.png", self.rgba_soft)
         print(f"Saved outputs with prefix: {prefix}")
 
     def evaluate_against(self, gt_mask: np.ndarray) -> "tuple[SegmentationMetrics, TrimapMetrics]":
@@ -66,6 +72,39 @@ def guided_filter(guide: np.ndarray, src: np.ndarray, radius: int = 8, eps: floa
     g = eng.to_device(np.ascontiguousarray(guide, dtype=np.float32)[None])
     s = eng.to_device(np.ascontiguousarray(src, dtype=np.float32)[None])
     return eng.guided_filter(g, s, radius, eps)[0].cpu().numpy()
+
+
+MATTE_RADIUS = 4
+MATTE_EPS = 1e-4
+
+
+def alpha_to_u8(alpha: np.ndarray) -> np.ndarray:
+    """(H, W) alpha in [0, 1] -> uint8 round(255 alpha), the alpha channel of a cut-out."""
+    return np.floor(np.asarray(alpha, np.float64) * 255.0 + 0.5).astype(np.uint8)
+
+
+def alpha_matte(image: np.ndarray, mask: np.ndarray, radius: int = MATTE_RADIUS, eps: float = MATTE_EPS,
+                device="cuda") -> np.ndarray:
+    """Soft alpha matte of a binary mask (additive): He, Sun and Tang's guided filter with the colour image as guide
+    (I = bgr / 255, a 3x3 covariance per window) and the mask as input, clamped to [0, 1] (ggc_alpha_matte).  Pixels
+    farther than 2 * radius from the mask's edge keep the mask's value exactly; near it, alpha follows the colours.
+
+    image: (H, W, 3) uint8 BGR; mask: (H, W) with values in {0, 1} (bool or integer).  radius in 1..64, eps >= 1e-12.
+    The defaults (radius 4, eps 1e-4, for images whose longest side is about 800 pixels, inference.py's --max-size) are
+    a choice, not a tuned result.
+    -> (H, W) float32."""
+    from ._engine import get_engine, check_matte_args
+    image = _check_image(image)
+    m = np.asarray(mask)
+    if m.shape != image.shape[:2]:
+        raise ValueError(f"alpha_matte: mask {m.shape} does not match image {image.shape[:2]}")
+    if m.size and not np.isin(m, (0, 1)).all():
+        raise ValueError("alpha_matte: mask values must be 0 or 1")
+    check_matte_args(radius, eps)
+    eng = get_engine(device)
+    bgr = eng.to_device(image[None])
+    binary = eng.to_device(np.ascontiguousarray(m, dtype=np.uint8)[None])
+    return eng.alpha_matte(bgr, binary, radius, eps)[0].cpu().numpy()
 
 
 def refine_trimap(probs: np.ndarray, segments: np.ndarray, image: np.ndarray, threshold_fg: float = 0.55,
@@ -177,6 +216,15 @@ class _Hints:
         ok = (r >= 0) & (r < h) & (c >= 0) & (c < w)
         img = np.repeat(np.arange(len(self.ptr) - 1), np.diff(self.ptr))
         return np.bincount(img[ok], minlength=len(self.ptr) - 1) > 0
+
+
+def _matte_args(matte: bool, radius, eps) -> "Optional[tuple[int, float]]":
+    """(radius, eps) when the matte is wanted (checked here, before any stage runs), else None."""
+    if not matte:
+        return None
+    from ._engine import check_matte_args
+    check_matte_args(radius, eps)
+    return int(radius), float(eps)
 
 
 class GCNGrabCutPipeline:
@@ -327,8 +375,13 @@ class GCNGrabCutPipeline:
                              edge_aware: bool = True, filter_radius: int = 8, compose: bool = True,
                              timing: Optional[dict] = None, grabcut_lanes: Optional[int] = None,
                              chunks: Optional[int] = None, hints=None, hint_radius: int = 5, hint_region: bool = False,
-                             hints_as_prior: bool = False, return_state: bool = False) -> dict:
+                             hints_as_prior: bool = False, return_state: bool = False, matte: bool = False,
+                             matte_radius: int = MATTE_RADIUS, matte_eps: float = MATTE_EPS) -> dict:
         """bgr: (B,H,W,3) uint8 tensor on the pipeline's device.  Returns device tensors.
+
+        matte=True (additive) also returns "alpha" (B,H,W) float32, the soft matte of the cleaned mask (alpha_matte with
+        matte_radius / matte_eps), and "rgba_soft" (B,H,W,4) uint8, the cut-out with that alpha.  Every other output is
+        the same as without it.
 
         return_state=True (additive) also returns what a GC_EVAL edit loop continues from: "gc_binary" (B,H,W) uint8,
         GrabCut's own binary mask before clean_mask; "bgd" / "fgd" (B,65) float64, the colour models; "gc_image"
@@ -355,12 +408,13 @@ class GCNGrabCutPipeline:
         want = self.grabcut_lanes if grabcut_lanes is None else int(grabcut_lanes)   # (an argument, so that concurrent callers do not mutate the pipeline)
         n_chunks = self.chunks if chunks is None else int(chunks)
         hints = _Hints.of(hints, b, hint_radius, hint_region, hints_as_prior)
+        mat = _matte_args(matte, matte_radius, matte_eps)
         if n_chunks <= 0:                          # 0: one chunk per GrabCut lane once every chunk gets a lane's worth of images
             n_chunks = max(want, 1) if b >= 16 * max(want, 1) else 1
         if n_chunks > 1 and b >= 2 * n_chunks:
             return self._segment_pipelined(bgr, self.chunk_plan(b, n_chunks, self.chunk_ratio), cs, threshold_fg, threshold_bg,
                                            refine_iters, min_area_ratio, keep_largest, edge_aware, filter_radius, compose, timing,
-                                           hints, return_state)
+                                           hints, return_state, mat)
 
         def tick():
             if timing is not None:
@@ -379,11 +433,15 @@ class GCNGrabCutPipeline:
         cleaned = eng.empty(*bgr.shape[:3], dtype=torch.uint8)
         overlay = eng.empty(*bgr.shape[:3], 3, dtype=torch.uint8) if compose else None
         rgba = eng.empty(*bgr.shape[:3], 4, dtype=torch.uint8) if compose else None
+        alpha = eng.empty(*bgr.shape[:3]) if mat else None
+        rgba_soft = eng.empty(*bgr.shape[:3], 4, dtype=torch.uint8) if mat else None
 
         def post(leng, lo, hi, binary_part):
             leng.clean_mask(binary_part, min_area_ratio, keep_largest, out=cleaned[lo:hi])
             if compose:
                 leng.compose(bgr[lo:hi], cleaned[lo:hi], out=(overlay[lo:hi], rgba[lo:hi]))
+            if mat:
+                leng.alpha_matte(bgr[lo:hi], cleaned[lo:hi], *mat, want_rgba=True, out=(alpha[lo:hi], rgba_soft[lo:hi]))
 
         fused_post = timing is None
         binary, mask, bgd, fgd = eng.grabcut_lanes(gc_img, mask, self.gc_config.n_iter, 0, self.gc_config.seed, lanes,
@@ -403,12 +461,14 @@ class GCNGrabCutPipeline:
             out.update(gc_binary=binary, bgd=bgd, fgd=fgd, gc_image=gc_img)
         if compose:
             out["overlay"], out["rgba"] = overlay, rgba
+        if mat:
+            out["alpha"], out["rgba_soft"] = alpha, rgba_soft
         if timing is not None:
             timing["postprocess"] = tick() - t
         return out
 
     def _segment_pipelined(self, bgr, plan, cs, threshold_fg, threshold_bg, refine_iters, min_area_ratio, keep_largest,
-                           edge_aware, filter_radius, compose, timing, hints=None, return_state=False) -> dict:
+                           edge_aware, filter_radius, compose, timing, hints=None, return_state=False, mat=None) -> dict:
         """The software pipeline behind segment_batch_device: chunk k's GrabCut lane starts as soon as chunk k's trimaps are
         on the device; the caller's stream goes on with chunk k+1's SLIC / graph / network / trimap."""
         import torch
@@ -430,6 +490,8 @@ class GCNGrabCutPipeline:
         cleaned = eng.empty(b, h, w, dtype=torch.uint8)
         overlay = eng.empty(b, h, w, 3, dtype=torch.uint8) if compose else None
         rgba = eng.empty(b, h, w, 4, dtype=torch.uint8) if compose else None
+        alpha = eng.empty(b, h, w) if mat else None
+        rgba_soft = eng.empty(b, h, w, 4, dtype=torch.uint8) if mat else None
         if return_state:
             st_binary = eng.empty(b, h, w, dtype=torch.uint8)
             st_bgd = eng.empty(b, 65, dtype=torch.float64)
@@ -463,6 +525,8 @@ class GCNGrabCutPipeline:
                 leng.clean_mask(binary, min_area_ratio, keep_largest, out=cleaned[lo:hi])
                 if compose:
                     leng.compose(img, cleaned[lo:hi], out=(overlay[lo:hi], rgba[lo:hi]))
+                if mat:
+                    leng.alpha_matte(img, cleaned[lo:hi], *mat, want_rgba=True, out=(alpha[lo:hi], rgba_soft[lo:hi]))
                 if ev is not None:
                     ev[2].record(stream)
                 done = torch.cuda.Event()
@@ -495,6 +559,8 @@ class GCNGrabCutPipeline:
             out.update(gc_binary=st_binary, bgd=st_bgd, fgd=st_fgd, gc_image=st_image)
         if compose:
             out["overlay"], out["rgba"] = overlay, rgba
+        if mat:
+            out["alpha"], out["rgba_soft"] = alpha, rgba_soft
         if timing is not None:                        # stage times from stream events (the stages overlap: they add up to more than the wall time)
             torch.cuda.synchronize(dev)
             front = sum(e[3].elapsed_time(e[4]) for e in stamps) / 1e3
@@ -515,11 +581,14 @@ class GCNGrabCutPipeline:
         timing: dict[str, float] = {}
         bgr = self._eng.to_device(np.stack(imgs))
         out = self.segment_batch_device(bgr, timing=timing, hints=hints, **kwargs)
-        host = {k: out[k].cpu().numpy() for k in ("binary_mask", "trimap", "segments", "overlay", "rgba")}
+        host = {k: out[k].cpu().numpy() for k in ("binary_mask", "trimap", "segments", "overlay", "rgba", "alpha", "rgba_soft")
+                if k in out}
         per_image = {k: v / len(imgs) for k, v in timing.items()}
         return [SegmentationResult(image=imgs[i], binary_mask=host["binary_mask"][i], trimap=host["trimap"][i],
                                    segments=host["segments"][i], overlay=host["overlay"][i], rgba=host["rgba"][i],
-                                   timing=dict(per_image)) for i in range(len(imgs))]
+                                   timing=dict(per_image), alpha=host["alpha"][i] if "alpha" in host else None,
+                                   rgba_soft=host["rgba_soft"][i] if "rgba_soft" in host else None)
+                for i in range(len(imgs))]
 
     def _click_round(self, binary, gt, mask, image, bgd, fgd, hint_ptr, hint_radius=5, n_iter=1):
         """One round of the NoC protocol on a device-resident batch: the next click per image on GrabCut's binary mask,
@@ -623,11 +692,13 @@ class GCNGrabCutPipeline:
     def segment(self, image: np.ndarray, threshold_fg: float = 0.55, threshold_bg: float = 0.55,
                 refine_iters: int = 0, min_area_ratio: float = 0.002, keep_largest: bool = False,
                 edge_aware: bool = True, filter_radius: int = 8, fg_points=None, bg_points=None, hint_radius: int = 5,
-                hint_region: bool = False, hints_as_prior: bool = False) -> SegmentationResult:
+                hint_region: bool = False, hints_as_prior: bool = False, matte: bool = False,
+                matte_radius: int = MATTE_RADIUS, matte_eps: float = MATTE_EPS) -> SegmentationResult:
         """Full pipeline on one BGR image (reference pipeline.py:265-352).
 
         Additive: fg_points / bg_points are user clicks, (row, col) pairs, applied as hard constraints on the trimap
-        GrabCut starts from (see segment_batch_device for hint_radius, hint_region and hints_as_prior)."""
+        GrabCut starts from (see segment_batch_device for hint_radius, hint_region and hints_as_prior); matte=True also
+        fills the result's alpha and rgba_soft (segment_batch_device)."""
         image = _check_image(image)
         timing: dict[str, float] = {}
         hints = None if fg_points is None and bg_points is None else \
@@ -635,15 +706,21 @@ class GCNGrabCutPipeline:
         out = self.segment_batch_device(self._eng.to_device(image[None]), threshold_fg, threshold_bg, refine_iters,
                                         min_area_ratio, keep_largest, edge_aware, filter_radius, timing=timing,
                                         hints=hints, hint_radius=hint_radius, hint_region=hint_region,
-                                        hints_as_prior=hints_as_prior)
+                                        hints_as_prior=hints_as_prior, matte=matte, matte_radius=matte_radius,
+                                        matte_eps=matte_eps)
         return SegmentationResult(
             image=image, binary_mask=out["binary_mask"][0].cpu().numpy(), trimap=out["trimap"][0].cpu().numpy(),
             segments=out["segments"][0].cpu().numpy(), overlay=out["overlay"][0].cpu().numpy(),
-            rgba=out["rgba"][0].cpu().numpy(), timing=timing)
+            rgba=out["rgba"][0].cpu().numpy(), timing=timing,
+            alpha=out["alpha"][0].cpu().numpy() if matte else None,
+            rgba_soft=out["rgba_soft"][0].cpu().numpy() if matte else None)
 
-    def segment_bbox(self, image: np.ndarray, bbox: tuple[int, int, int, int]) -> SegmentationResult:
-        """Classical GrabCut with a bounding box (reference pipeline.py:354-380)."""
+    def segment_bbox(self, image: np.ndarray, bbox: tuple[int, int, int, int], matte: bool = False,
+                     matte_radius: int = MATTE_RADIUS, matte_eps: float = MATTE_EPS) -> SegmentationResult:
+        """Classical GrabCut with a bounding box (reference pipeline.py:354-380).  Additive: matte=True also fills the
+        result's alpha and rgba_soft, the soft matte of the returned mask (alpha_matte)."""
         image = _check_image(image)
+        mat = _matte_args(matte, matte_radius, matte_eps)
         gc = GrabCut(image, self.gc_config, device=self.device)
         binary_mask = gc.run_with_bbox(bbox)
         x, y, w, h = bbox
@@ -653,6 +730,12 @@ class GCNGrabCutPipeline:
         y0, y1, x0, x1 = eroded_box(H, W, bbox)
         if y1 > y0 and x1 > x0:
             trimap[y0:y1, x0:x1] = Label.FG_DEFINITE
+        alpha = rgba_soft = None
+        if mat:
+            eng = self._eng
+            alpha, rgba_soft = eng.alpha_matte(eng.to_device(image[None]), eng.to_device(binary_mask[None]), *mat,
+                                               want_rgba=True)
+            alpha, rgba_soft = alpha[0].cpu().numpy(), rgba_soft[0].cpu().numpy()
         return SegmentationResult(image=image, binary_mask=binary_mask, trimap=trimap,
                                   segments=np.zeros((H, W), dtype=np.int32), overlay=gc.overlay_mask(),
-                                  rgba=gc.crop_foreground())
+                                  rgba=gc.crop_foreground(), alpha=alpha, rgba_soft=rgba_soft)

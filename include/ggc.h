@@ -50,7 +50,8 @@
 extern "C" {
 #endif
 
-#define GGC_VERSION 350 /* 0.3.5: ggc_grid_maxflow (the GrabCut max-flow on a caller's network, a test hook);
+#define GGC_VERSION 360 /* 0.3.6: ggc_alpha_matte (soft alpha matte of a binary mask: colour guided-filter feathering);
+                           0.3.5: ggc_grid_maxflow (the GrabCut max-flow on a caller's network, a test hook);
                            0.3.4: ggc_next_click (the next simulated click of the NoC protocol);
                            0.3.3: ggc_apply_hints (user clicks as hard constraints on the GrabCut mask);
                            0.3.2: ResGCNNet (forward and ggc_train_*), GATTrimapNet and ggc_gcn_aggregate at widths up to 256;
@@ -420,6 +421,18 @@ int ggc_compose_outputs(ggc_ctx* ctx, ggc_stream stream, int B, int H, int W,
                         const uint8_t* bgr, const uint8_t* binary,
                         float alpha, int tint_b, int tint_g, int tint_r,
                         uint8_t* overlay, uint8_t* rgba);
+
+/* O1 — soft alpha matte of a binary mask: colour guided filter (guide = bgr / 255, input = binary), BORDER_REFLECT_101
+ * (additive; He, Sun and Tang's guided filter used for feathering).
+ *   bgr [dev] u8 [B,H,W,3]   binary [dev] u8 [B,H,W] (nonzero = 1: any nonzero byte counts as foreground)
+ *   1 <= radius <= 64, 1e-12 <= eps < inf (else GGC_E_INVALID_ARG); windows larger than the image are legal
+ *   alpha [dev] f32 [B,H,W] in [0,1] or NULL;  rgba [dev] u8 [B,H,W,4] (bgr, round(255 alpha)) or NULL (not both NULL)
+ * The window sums are exact: integers for the covariances, int64 fixed point (rounding below 2^-28) for the averages of
+ * the coefficients, so a pixel farther than 2*radius from any mask change gets exactly the mask value.  The 3x3 solve runs
+ * in float64.  Every image's result is independent of the batch it is in (bit for bit).  Scratch: 32 bytes per pixel from the context.
+ * Does not synchronise. */
+int ggc_alpha_matte(ggc_ctx* ctx, ggc_stream stream, int B, int H, int W, const uint8_t* bgr, const uint8_t* binary,
+                    int radius, float eps, float* alpha, uint8_t* rgba);
 
 /* R0 — IoU = tp / (tp + fp + fn + 1e-8) per image (metrics.py:79-84).
  *   iou [dev] f64 [B] (may be NULL)   counts [dev] u64 [B,3] = tp, fp, fn (may be NULL) */

@@ -7,6 +7,7 @@ Same command line as the reference's inference.py (flags :26-56, outputs :146-15
     python3 inference.py --input path/to/folder --output results/
     python3 inference.py --image cat.jpg --keep-largest --save mask overlay
     python3 inference.py --image cat.jpg --fg-point 120,200 --bg-point 10,10 --hint-radius 8
+    python3 inference.py --image cat.jpg --save mask alpha cutout          # soft edges: alpha matte and cut-out
 
 Images are decoded / written with Pillow (OpenCV is not a dependency of this build); folders are processed in
 batches of equally sized images so that the whole batch stays resident in HBM.
@@ -41,8 +42,9 @@ def build_parser() -> argparse.ArgumentParser:
     parser.add_argument("--min-area", type=float, default=0.002,
                         help="Drop mask components smaller than this fraction of the image")
     parser.add_argument("--keep-largest", action="store_true", help="Keep only the largest connected component")
-    parser.add_argument("--save", nargs="+", default=["mask", "overlay"], choices=["mask", "overlay", "rgba", "trimap"],
-                        help="Which outputs to write")
+    parser.add_argument("--save", nargs="+", default=["mask", "overlay"],
+                        choices=["mask", "overlay", "rgba", "trimap", "alpha", "cutout"],
+                        help="Which outputs to write (alpha / cutout: the soft matte and the BGRA cut-out with it)")
     parser.add_argument("--batch", type=int, default=64, help="Images per device batch (additive flag)")
     # additive: user clicks as hard constraints (ggc_apply_hints), single-image runs only
     parser.add_argument("--fg-point", action="append", type=_point, default=[], metavar="ROW,COL",
@@ -51,6 +53,10 @@ def build_parser() -> argparse.ArgumentParser:
                         help="Background click in original-image pixels (repeatable; needs --image)")
     parser.add_argument("--hint-radius", type=int, default=5,
                         help="Radius in pixels of the image as segmented (after --max-size) painted around each click")
+    # additive: soft alpha matte of the mask (ggc_alpha_matte), computed when --save asks for alpha or cutout
+    parser.add_argument("--matte-radius", type=int, default=4,
+                        help="Window radius of the alpha matte, 1..64, in pixels of the image as segmented")
+    parser.add_argument("--matte-eps", type=float, default=1e-4, help="Regularisation of the alpha matte (>= 1e-12)")
     return parser
 
 
@@ -119,9 +125,14 @@ def main() -> None:
         parser.error("--fg-point / --bg-point are clicks on one image: use them with --image, not --input")
     if args.hint_radius < 0:
         parser.error("--hint-radius must be >= 0")
+    matte = "alpha" in args.save or "cutout" in args.save
+    if matte and not 1 <= args.matte_radius <= 64:
+        parser.error("--matte-radius must be in 1..64")
+    if matte and not args.matte_eps >= 1e-12:
+        parser.error("--matte-eps must be >= 1e-12")
     from src.gcn_grabcut import GCNGrabCutPipeline
     from src.gcn_grabcut.graph_builder import SuperpixelGraphConfig
-    from src.gcn_grabcut.pipeline import _colour_trimap, _write_png
+    from src.gcn_grabcut.pipeline import _colour_trimap, _write_png, alpha_to_u8
 
     model = load_model(args.checkpoint, args.model, args.hidden, args.layers, args.device)
 
@@ -159,6 +170,8 @@ def main() -> None:
                 hint_kw = dict(hints=[(scale_points(args.fg_point, orig_hw, image.shape[:2]),
                                        scale_points(args.bg_point, orig_hw, image.shape[:2]))],
                                hint_radius=args.hint_radius)
+            if matte:
+                hint_kw.update(matte=True, matte_radius=args.matte_radius, matte_eps=args.matte_eps)
             results = pipeline.segment_batch(
                 [im for _, im in chunk], threshold_fg=args.threshold, threshold_bg=args.threshold,
                 refine_iters=args.refine, min_area_ratio=args.min_area, keep_largest=args.keep_largest,
@@ -176,6 +189,10 @@ def main() -> None:
                     _write_png(f"{stem}_rgba.png", result.rgba)
                 if "trimap" in args.save:
                     _write_png(f"{stem}_trimap.png", _colour_trimap(result.trimap))
+                if "alpha" in args.save:
+                    _write_png(f"{stem}_alpha.png", alpha_to_u8(result.alpha))
+                if "cutout" in args.save:
+                    _write_png(f"{stem}_cutout.png", result.rgba_soft)
                 t = result.timing
                 print(f"[{n_done}/{len(paths)}] {path.name}  fg={result.binary_mask.mean():.1%}  "
                       f"graph={t.get('graph_build', 0):.4f}s gcn={t.get('gcn_inference', 0):.4f}s "
