@@ -41,6 +41,7 @@ constexpr int MT_IW = MT_W + 2 * MT_RMAX;   // staged columns at the largest rad
 constexpr int MT_CPL = MT_IW / MT_W;        // staged columns per lane (3)
 
 struct alignas(32) MatteAB { int64_t a0, a1, a2, b; };   // fixed point, scale 2^S
+struct alignas(32) MatteMean { double c0, c1, c2, c3; };  // mean coefficients of a pixel (stage 2')
 
 __device__ __forceinline__ int mrefl101(int i, int n) {
     if (n == 1) return 0;
@@ -178,10 +179,21 @@ __device__ __forceinline__ void row_sum_ab(const MatteAB* __restrict__ row, int 
     }
 }
 
-// stage 2: same grid; alpha [B,H,W] f32 and / or rgba [B,H,W,4] u8 (either may be NULL)
+// alpha = clamp(c0 B + c1 G + c2 R + c3, 0, 1), summed left to right: the one definition stages 2 and 3 share
+__device__ __forceinline__ double matte_value(double c0, double c1, double c2, double c3, uint8_t pb, uint8_t pg, uint8_t pr) {
+    const double a = c0 * (double)pb + c1 * (double)pg + c2 * (double)pr + c3;
+    return a < 0.0 ? 0.0 : (a > 1.0 ? 1.0 : a);
+}
+
+__device__ __forceinline__ uint8_t alpha_byte(double a) { return (uint8_t)floor(a * 255.0 + 0.5); }
+
+// stage 2: same grid.  MEAN = false: alpha [B,H,W] f32 and / or rgba [B,H,W,4] u8 (either may be NULL).  MEAN = true
+// (stage 2' of ggc_upsample_matte): the per-pixel mean coefficients C = (acc0 / dn, acc1 / dn, acc2 / dn, acc3 / db)
+// that the alpha of the other form is made of, to `mean` [B,H,W].
+template <bool MEAN>
 __global__ void __launch_bounds__(MT_W) k_matte_alpha(int H, int W, int r, double scale, const uint8_t* __restrict__ bgr,
                                                       const MatteAB* __restrict__ ab, float* __restrict__ alpha,
-                                                      uint8_t* __restrict__ rgba) {
+                                                      uint8_t* __restrict__ rgba, MatteMean* __restrict__ mean) {
     __shared__ MatteAB s_in[MT_IW], s_out[MT_IW];
     const int lane = threadIdx.x;
     const int x0 = blockIdx.x * MT_W, y0 = blockIdx.y * MT_H, y1 = min(y0 + MT_H, H);
@@ -214,15 +226,152 @@ __global__ void __launch_bounds__(MT_W) k_matte_alpha(int H, int W, int r, doubl
         }
         if (x < W) {
             const size_t i = base + (size_t)y * W + x;
-            const uint8_t pb = bgr[3 * i], pg = bgr[3 * i + 1], pr = bgr[3 * i + 2];
             const double dn = 255.0 * n * scale, db = n * scale;
-            double a = (double)(int64_t)acc[0] / dn * (double)pb + (double)(int64_t)acc[1] / dn * (double)pg +
-                       (double)(int64_t)acc[2] / dn * (double)pr + (double)(int64_t)acc[3] / db;
-            a = a < 0.0 ? 0.0 : (a > 1.0 ? 1.0 : a);
-            if (alpha) alpha[i] = (float)a;
+            const double c0 = (double)(int64_t)acc[0] / dn, c1 = (double)(int64_t)acc[1] / dn;
+            const double c2 = (double)(int64_t)acc[2] / dn, c3 = (double)(int64_t)acc[3] / db;
+            if constexpr (MEAN) {
+                mean[i] = MatteMean{c0, c1, c2, c3};
+            } else {
+                const uint8_t pb = bgr[3 * i], pg = bgr[3 * i + 1], pr = bgr[3 * i + 2];
+                const double a = matte_value(c0, c1, c2, c3, pb, pg, pr);
+                if (alpha) alpha[i] = (float)a;
+                if (rgba) {
+                    rgba[4 * i] = pb; rgba[4 * i + 1] = pg; rgba[4 * i + 2] = pr;
+                    rgba[4 * i + 3] = alpha_byte(a);
+                }
+            }
+        }
+    }
+}
+
+// ---------------------------------------------------------------- stage 3 of ggc_upsample_matte
+// One pass over the full-resolution pixels.  A block is 256 lanes x 4 consecutive output columns (1024) and UP_H output
+// rows of one image; it walks down its rows.  Each lane maps its 4 columns to (x0, x1, wx) once, and keeps the horizontal
+// lerps of the two source rows its current output row reads (h0: row y0, h1: row y1, 4 coefficients x 4 pixels each) in
+// registers: consecutive output rows mostly share them, and when y0 moves on by one row h1 becomes h0, so a source row's
+// lerps are formed once per block.  The source coefficients are read through the cache (a block's window of the 32 B/px
+// plane is small); the colour bytes and every output are streamed once, coalesced.  VEC (W1 % 4 == 0 and aligned
+// pointers): 12 B of BGR in, 16 B of alpha, 4 B of mask and 16 B of BGRA out per lane and row, as single wide accesses.
+constexpr int UP_PX = 4;                    // output columns per lane
+constexpr int UP_THREADS = 256;
+constexpr int UP_W = UP_PX * UP_THREADS;    // output columns of a block
+constexpr int UP_H = 32;                    // output rows of a block
+
+// the half-pixel-centre source coordinate of output index o of n1, over a source of n (cv2.INTER_LINEAR, align_corners=False)
+__device__ __forceinline__ void up_coord(int o, int n, int n1, int& i0, int& i1, double& w) {
+    double s = (((double)o + 0.5) * (double)n) / (double)n1 - 0.5;
+    if (s < 0.0) s = 0.0;
+    const double f = floor(s);
+    i0 = (int)f;
+    if (i0 >= n - 1) { i0 = n - 1; w = 0.0; } else { w = s - f; }
+    i1 = min(i0 + 1, n - 1);
+}
+
+__device__ __forceinline__ double lerp(double u, double v, double t) { return u + t * (v - u); }
+
+// the horizontal lerps of source row `row` at the lane's UP_PX columns
+__device__ __forceinline__ void up_row(const MatteMean* __restrict__ row, const int (&x0)[UP_PX], const int (&x1)[UP_PX],
+                                       const double (&wx)[UP_PX], double (&h)[UP_PX][4]) {
+#pragma unroll
+    for (int j = 0; j < UP_PX; ++j) {
+        const MatteMean u = row[x0[j]], v = row[x1[j]];
+        h[j][0] = lerp(u.c0, v.c0, wx[j]);
+        h[j][1] = lerp(u.c1, v.c1, wx[j]);
+        h[j][2] = lerp(u.c2, v.c2, wx[j]);
+        h[j][3] = lerp(u.c3, v.c3, wx[j]);
+    }
+}
+
+// grid (cdiv(W1, UP_W), cdiv(H1, UP_H), B), UP_THREADS threads; alpha [B,H1,W1] f32, binary [B,H1,W1] u8 and rgba
+// [B,H1,W1,4] u8, each may be NULL
+template <bool VEC>
+__global__ void __launch_bounds__(UP_THREADS) k_upsample(int H, int W, int H1, int W1, const MatteMean* __restrict__ mean,
+                                                         const uint8_t* __restrict__ bgr, float* __restrict__ alpha,
+                                                         uint8_t* __restrict__ binary, uint8_t* __restrict__ rgba) {
+    const int xb = (blockIdx.x * UP_THREADS + threadIdx.x) * UP_PX;
+    if (xb >= W1) return;                       // no barrier below: idle lanes may leave
+    const int yb = blockIdx.y * UP_H, ye = min(yb + UP_H, H1);
+    const MatteMean* src = mean + (size_t)blockIdx.z * H * W;
+    int x0[UP_PX], x1[UP_PX];
+    double wx[UP_PX];
+#pragma unroll
+    for (int j = 0; j < UP_PX; ++j) up_coord(min(xb + j, W1 - 1), W, W1, x0[j], x1[j], wx[j]);
+    double h0[UP_PX][4], h1[UP_PX][4];
+    int ra = -1, rb = -1;                       // the source rows h0 and h1 hold
+    for (int y = yb; y < ye; ++y) {
+        int y0, y1;
+        double wy;
+        up_coord(y, H, H1, y0, y1, wy);
+        if (y0 != ra) {
+            if (y0 == rb) {
+#pragma unroll
+                for (int j = 0; j < UP_PX; ++j)
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) h0[j][k] = h1[j][k];
+            } else {
+                up_row(src + (size_t)y0 * W, x0, x1, wx, h0);
+            }
+            ra = y0;
+        }
+        if (y1 != rb) {
+            if (y1 == ra) {
+#pragma unroll
+                for (int j = 0; j < UP_PX; ++j)
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) h1[j][k] = h0[j][k];
+            } else {
+                up_row(src + (size_t)y1 * W, x0, x1, wx, h1);
+            }
+            rb = y1;
+        }
+        const size_t p = ((size_t)blockIdx.z * H1 + y) * W1 + xb;
+        uint8_t px[3 * UP_PX];
+        if constexpr (VEC) {
+            const uint32_t* s32 = reinterpret_cast<const uint32_t*>(bgr + 3 * p);
+            const uint32_t w0 = s32[0], w1 = s32[1], w2 = s32[2];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                px[k] = (uint8_t)(w0 >> (8 * k));
+                px[4 + k] = (uint8_t)(w1 >> (8 * k));
+                px[8 + k] = (uint8_t)(w2 >> (8 * k));
+            }
+        } else {
+#pragma unroll
+            for (int k = 0; k < 3 * UP_PX; ++k) px[k] = xb + k / 3 < W1 ? bgr[3 * p + k] : 0;
+        }
+        double a[UP_PX];
+#pragma unroll
+        for (int j = 0; j < UP_PX; ++j)
+            a[j] = matte_value(lerp(h0[j][0], h1[j][0], wy), lerp(h0[j][1], h1[j][1], wy), lerp(h0[j][2], h1[j][2], wy),
+                               lerp(h0[j][3], h1[j][3], wy), px[3 * j], px[3 * j + 1], px[3 * j + 2]);
+        if constexpr (VEC) {
+            if (alpha)
+                *reinterpret_cast<float4*>(alpha + p) = make_float4((float)a[0], (float)a[1], (float)a[2], (float)a[3]);
+            if (binary) {
+                uint32_t m = 0;
+#pragma unroll
+                for (int j = 0; j < UP_PX; ++j) m |= (a[j] >= 0.5 ? 1u : 0u) << (8 * j);
+                *reinterpret_cast<uint32_t*>(binary + p) = m;
+            }
             if (rgba) {
-                rgba[4 * i] = pb; rgba[4 * i + 1] = pg; rgba[4 * i + 2] = pr;
-                rgba[4 * i + 3] = (uint8_t)floor(a * 255.0 + 0.5);
+                uint32_t q[UP_PX];
+#pragma unroll
+                for (int j = 0; j < UP_PX; ++j)
+                    q[j] = (uint32_t)px[3 * j] | ((uint32_t)px[3 * j + 1] << 8) | ((uint32_t)px[3 * j + 2] << 16) |
+                           ((uint32_t)alpha_byte(a[j]) << 24);
+                *reinterpret_cast<uint4*>(rgba + 4 * p) = make_uint4(q[0], q[1], q[2], q[3]);
+            }
+        } else {
+#pragma unroll
+            for (int j = 0; j < UP_PX; ++j) {
+                if (xb + j >= W1) break;
+                const size_t i = p + j;
+                if (alpha) alpha[i] = (float)a[j];
+                if (binary) binary[i] = a[j] >= 0.5 ? 1 : 0;
+                if (rgba) {
+                    rgba[4 * i] = px[3 * j]; rgba[4 * i + 1] = px[3 * j + 1]; rgba[4 * i + 2] = px[3 * j + 2];
+                    rgba[4 * i + 3] = alpha_byte(a[j]);
+                }
             }
         }
     }
@@ -233,24 +382,74 @@ __global__ void __launch_bounds__(MT_W) k_matte_alpha(int H, int W, int r, doubl
 
 using namespace ggc;
 
+namespace {
+
+// the argument checks ggc_alpha_matte and ggc_upsample_matte share, and the fixed-point scale 2^S of stage 1
+int check_matte(ggc_ctx* ctx, int radius, float eps) {
+    GGC_REQUIRE(ctx, radius >= 1 && radius <= MT_RMAX, GGC_E_INVALID_ARG, "matte radius %d outside 1..%d", radius, MT_RMAX);
+    GGC_REQUIRE(ctx, eps >= 1e-12f && std::isfinite(eps), GGC_E_INVALID_ARG, "matte eps %g outside [1e-12, inf)", (double)eps);
+    return GGC_OK;
+}
+
+double matte_scale(int radius, float eps) {
+    const double n = (double)(2 * radius + 1) * (double)(2 * radius + 1);
+    const int S = std::max(0, std::min(52, (int)std::floor(62.0 - std::log2(n * 2.0 * (1.0 + 0.5 / std::sqrt((double)eps))))));
+    return std::ldexp(1.0, S);
+}
+
+bool aligned(const void* p, size_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
+
+} // namespace
+
 extern "C" int ggc_alpha_matte(ggc_ctx* ctx, ggc_stream stream, int B, int H, int W, const uint8_t* bgr,
                                const uint8_t* binary, int radius, float eps, float* alpha, uint8_t* rgba) {
     if (!ctx) return GGC_E_INVALID_ARG;
     GGC_REQUIRE(ctx, B >= 1 && H >= 1 && W >= 1 && B <= 65535, GGC_E_SHAPE, "bad shape B=%d H=%d W=%d", B, H, W);
     GGC_REQUIRE(ctx, bgr && binary && (alpha || rgba), GGC_E_INVALID_ARG, "null pointer");
-    GGC_REQUIRE(ctx, radius >= 1 && radius <= MT_RMAX, GGC_E_INVALID_ARG, "matte radius %d outside 1..%d", radius, MT_RMAX);
-    GGC_REQUIRE(ctx, eps >= 1e-12f && std::isfinite(eps), GGC_E_INVALID_ARG, "matte eps %g outside [1e-12, inf)", (double)eps);
+    if (int e = check_matte(ctx, radius, eps)) return e;
     GGC_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     MatteAB* ab = scratch_t<MatteAB>(ctx, S_MATTE, (size_t)B * H * W);
     if (!ab) return GGC_E_OOM;
     ProfScope prof(ctx, st, "alpha_matte");
-    const double n = (double)(2 * radius + 1) * (double)(2 * radius + 1);
-    const int S = std::max(0, std::min(52, (int)std::floor(62.0 - std::log2(n * 2.0 * (1.0 + 0.5 / std::sqrt((double)eps))))));
-    const double scale = std::ldexp(1.0, S);
+    const double scale = matte_scale(radius, eps);
     const dim3 grid(cdiv(W, MT_W), cdiv(H, MT_H), B);
     hipLaunchKernelGGL(k_matte_ab, grid, dim3(MT_W), 0, st, H, W, radius, (double)eps, scale, bgr, binary, ab);
-    hipLaunchKernelGGL(k_matte_alpha, grid, dim3(MT_W), 0, st, H, W, radius, scale, bgr, ab, alpha, rgba);
+    hipLaunchKernelGGL(k_matte_alpha<false>, grid, dim3(MT_W), 0, st, H, W, radius, scale, bgr, ab, alpha, rgba,
+                       (MatteMean*)nullptr);
+    GGC_LAUNCH_CHECK(ctx);
+    return GGC_OK;
+}
+
+extern "C" int ggc_upsample_matte(ggc_ctx* ctx, ggc_stream stream, int B, int H, int W, const uint8_t* bgr,
+                                  const uint8_t* binary, int H1, int W1, const uint8_t* bgr_full, int radius, float eps,
+                                  float* alpha_full, uint8_t* binary_full, uint8_t* rgba_full) {
+    if (!ctx) return GGC_E_INVALID_ARG;
+    GGC_REQUIRE(ctx, B >= 1 && B <= 65535 && H >= 1 && W >= 1 && H1 >= H && W1 >= W && H1 <= 32768 && W1 <= 32768,
+                GGC_E_SHAPE, "bad shape B=%d H=%d W=%d -> H1=%d W1=%d", B, H, W, H1, W1);
+    GGC_REQUIRE(ctx, bgr && binary && bgr_full && (alpha_full || binary_full || rgba_full), GGC_E_INVALID_ARG, "null pointer");
+    if (int e = check_matte(ctx, radius, eps)) return e;
+    GGC_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    MatteAB* ab = scratch_t<MatteAB>(ctx, S_MATTE, (size_t)B * H * W);
+    if (!ab) return GGC_E_OOM;
+    MatteMean* mean = scratch_t<MatteMean>(ctx, S_MATTE_MEAN, (size_t)B * H * W);
+    if (!mean) return GGC_E_OOM;
+    ProfScope prof(ctx, st, "upsample_matte");
+    const double scale = matte_scale(radius, eps);
+    const dim3 grid(cdiv(W, MT_W), cdiv(H, MT_H), B);
+    hipLaunchKernelGGL(k_matte_ab, grid, dim3(MT_W), 0, st, H, W, radius, (double)eps, scale, bgr, binary, ab);
+    hipLaunchKernelGGL(k_matte_alpha<true>, grid, dim3(MT_W), 0, st, H, W, radius, scale, bgr, ab, (float*)nullptr,
+                       (uint8_t*)nullptr, mean);
+    const bool vec = W1 % UP_PX == 0 && aligned(bgr_full, 4) && aligned(alpha_full, 16) && aligned(binary_full, 4) &&
+                     aligned(rgba_full, 16);
+    const dim3 up_grid(cdiv(W1, UP_W), cdiv(H1, UP_H), B);
+    if (vec)
+        hipLaunchKernelGGL(k_upsample<true>, up_grid, dim3(UP_THREADS), 0, st, H, W, H1, W1, mean, bgr_full, alpha_full,
+                           binary_full, rgba_full);
+    else
+        hipLaunchKernelGGL(k_upsample<false>, up_grid, dim3(UP_THREADS), 0, st, H, W, H1, W1, mean, bgr_full, alpha_full,
+                           binary_full, rgba_full);
     GGC_LAUNCH_CHECK(ctx);
     return GGC_OK;
 }

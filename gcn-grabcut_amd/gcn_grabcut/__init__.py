@@ -20,7 +20,8 @@ from .model import (
     ResGCNNet, GCNTrimapNet, GATTrimapNet, build_model, _probs_to_trimap, probs_to_node_trimap, project_to_pixels,
     TRIMAP_BG, TRIMAP_FG, TRIMAP_PROB_BG, TRIMAP_PROB_FG, CLASS_BG, CLASS_UNK, CLASS_FG,
 )
-from .pipeline import GCNGrabCutPipeline, SegmentationResult, alpha_matte, clean_mask, guided_filter, refine_trimap
+from .pipeline import (GCNGrabCutPipeline, FullResolution, SegmentationResult, alpha_matte, clean_mask, guided_filter,
+                       refine_trimap, upsample_mask)
 from .synthetic import synthetic_image, synthetic_batch
 from .losses import FocalLoss, LabelSmoothingCE, TrimapLoss
 from .trainer import Trainer, TrainConfig
@@ -32,7 +33,8 @@ __all__ = [
     "GraphBuilder", "SuperpixelGraph", "SuperpixelGraphConfig", "compute_auto_prior", "encode_user_hints", "pack_hints",
     "N_NODE_FEATS", "N_EDGE_FEATS", "N_PRIOR_FEATS",
     "evaluate", "evaluate_batch", "evaluate_trimap", "boundary_f1", "noc_summary", "SegmentationMetrics", "TrimapMetrics",
-    "GCNGrabCutPipeline", "SegmentationResult", "alpha_matte", "clean_mask", "guided_filter", "refine_trimap",
+    "GCNGrabCutPipeline", "FullResolution", "SegmentationResult", "alpha_matte", "clean_mask", "guided_filter",
+    "refine_trimap", "upsample_mask",
     "ResGCNNet", "GCNTrimapNet", "GATTrimapNet", "build_model", "probs_to_node_trimap", "project_to_pixels",
     "Data", "Batch", "synthetic_image", "synthetic_batch",
     "FocalLoss", "LabelSmoothingCE", "TrimapLoss", "Trainer", "TrainConfig",

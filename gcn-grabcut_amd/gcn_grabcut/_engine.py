@@ -288,6 +288,27 @@ class Engine:
                       float(eps), alpha.data_ptr(), _native.ptr(rgba))
         return (alpha, rgba) if want_rgba else alpha
 
+    def upsample_matte(self, bgr, binary, bgr_full, radius=4, eps=1e-4, want_alpha=True, want_binary=True,
+                       want_rgba=False, out=None):
+        """The soft matte of binary (B,H,W) uint8 under bgr (B,H,W,3) uint8, carried to bgr_full (B,H1,W1,3) uint8 with
+        H1 >= H, W1 >= W by the fast guided filter (ggc_upsample_matte).  -> (alpha (B,H1,W1) float32, binary
+        (B,H1,W1) uint8 = alpha >= 0.5, rgba (B,H1,W1,4) uint8), each None unless wanted; out: the same, preallocated."""
+        check_matte_args(radius, eps)
+        check_upsample_shapes(tuple(bgr.shape), tuple(binary.shape), tuple(bgr_full.shape), "upsample_matte")
+        if not (want_alpha or want_binary or want_rgba):
+            raise ValueError("upsample_matte: ask for at least one of alpha, binary and rgba")
+        b, h, w, _ = bgr.shape
+        h1, w1 = int(bgr_full.shape[1]), int(bgr_full.shape[2])
+        if out is None:
+            out = (self.empty(b, h1, w1) if want_alpha else None,
+                   self.empty(b, h1, w1, dtype=torch.uint8) if want_binary else None,
+                   self.empty(b, h1, w1, 4, dtype=torch.uint8) if want_rgba else None)
+        alpha, mask, rgba = out
+        self.ctx.call("ggc_upsample_matte", self._stream(), b, h, w, bgr.data_ptr(), binary.data_ptr(), h1, w1,
+                      bgr_full.data_ptr(), int(radius), float(eps), _native.ptr(alpha), _native.ptr(mask),
+                      _native.ptr(rgba))
+        return alpha, mask, rgba
+
     def iou(self, pred, gt):
         """-> (iou (B,) float64, counts (B,3) int64 = tp, fp, fn), on device."""
         b, h, w = pred.shape
@@ -308,6 +329,23 @@ def check_matte_args(radius, eps) -> None:
         raise ValueError(f"matte radius must be an integer in 1..{MATTE_RADIUS_MAX}, got {radius}")
     if not (np.isfinite(eps) and float(eps) >= MATTE_EPS_MIN):
         raise ValueError(f"matte eps must be finite and >= {MATTE_EPS_MIN:g}, got {eps}")
+
+
+UPSAMPLE_SIDE_MAX = 32768
+
+
+def check_upsample_shapes(bgr_shape, mask_shape, full_shape, what="upsample") -> None:
+    """The shape rules of ggc_upsample_matte, checked on the host so that a bad shape is a ValueError: bgr (B,H,W,3),
+    mask (B,H,W), full (B,H1,W1,3) with H <= H1 <= 32768 and W <= W1 <= 32768."""
+    if len(bgr_shape) != 4 or bgr_shape[3] != 3 or min(bgr_shape[:3]) < 1:
+        raise ValueError(f"{what}: image must be (B,H,W,3), got {bgr_shape}")
+    if tuple(mask_shape) != tuple(bgr_shape[:3]):
+        raise ValueError(f"{what}: mask {tuple(mask_shape)} does not match image {tuple(bgr_shape)}")
+    if len(full_shape) != 4 or full_shape[3] != 3 or full_shape[0] != bgr_shape[0]:
+        raise ValueError(f"{what}: full image must be ({bgr_shape[0]},H1,W1,3), got {tuple(full_shape)}")
+    if not (bgr_shape[1] <= full_shape[1] <= UPSAMPLE_SIDE_MAX and bgr_shape[2] <= full_shape[2] <= UPSAMPLE_SIDE_MAX):
+        raise ValueError(f"{what}: full image {tuple(full_shape[1:3])} must be at least the working size "
+                         f"{tuple(bgr_shape[1:3])} and at most {UPSAMPLE_SIDE_MAX} on a side")
 
 
 def merge_graphs(parts: Sequence[DeviceGraphs], segments: torch.Tensor) -> DeviceGraphs:

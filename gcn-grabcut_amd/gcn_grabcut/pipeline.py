@@ -37,6 +37,16 @@ def _write_png(path: str, array: np.ndarray) -> None:
 
 
 @dataclass
+class FullResolution:
+    """The outputs of a run at the full resolution of the image it was given (additive; upsample_mask): (H1, W1) arrays."""
+    binary_mask: np.ndarray                  # (H1, W1) uint8 {0, 1}: upsampled alpha >= 0.5
+    overlay: np.ndarray                      # (H1, W1, 3) BGR with coloured overlay of binary_mask
+    rgba: np.ndarray                         # (H1, W1, 4) BGRA, alpha = 255 * binary_mask
+    alpha: Optional[np.ndarray] = None       # (H1, W1) float32 soft matte in [0, 1] (matte=True)
+    rgba_soft: Optional[np.ndarray] = None   # (H1, W1, 4) uint8 BGRA cut-out with alpha = round(255 alpha) (matte=True)
+
+
+@dataclass
 class SegmentationResult:
     """All outputs from one pipeline run (reference pipeline.py:32-68)."""
     image: np.ndarray          # original BGR
@@ -48,6 +58,7 @@ class SegmentationResult:
     timing: dict = field(default_factory=dict)
     alpha: Optional[np.ndarray] = None       # additive: (H, W) float32 soft matte in [0, 1] (matte=True)
     rgba_soft: Optional[np.ndarray] = None   # additive: (H, W, 4) uint8 BGRA cut-out with alpha = round(255 alpha)
+    full: Optional[FullResolution] = None    # additive: the outputs at the full image's resolution (full_image=...)
 
     def save(self, prefix: str = "result") -> None:
         _write_png(f"{prefix}_overlay.png", self.overlay)
@@ -58,6 +69,15 @@ class SegmentationResult:
             _write_png(f"{prefix}_alpha.png", alpha_to_u8(self.alpha))
         if self.rgba_soft is not None:
             _write_png(f"{prefix}_cutout.png", self.rgba_soft)
+        if self.full is not None:
+            f = self.full
+            _write_png(f"{prefix}_full_mask.png", f.binary_mask * 255)
+            _write_png(f"{prefix}_full_overlay.png", f.overlay)
+            _write_png(f"{prefix}_full_rgba.png", f.rgba)
+            if f.alpha is not None:
+                _write_png(f"{prefix}_full_alpha.png", alpha_to_u8(f.alpha))
+            if f.rgba_soft is not None:
+                _write_png(f"{prefix}_full_cutout.png", f.rgba_soft)
         print(f"Saved outputs with prefix: {prefix}")
 
     def evaluate_against(self, gt_mask: np.ndarray) -> "tuple[SegmentationMetrics, TrimapMetrics]":
@@ -105,6 +125,39 @@ def alpha_matte(image: np.ndarray, mask: np.ndarray, radius: int = MATTE_RADIUS,
     bgr = eng.to_device(image[None])
     binary = eng.to_device(np.ascontiguousarray(m, dtype=np.uint8)[None])
     return eng.alpha_matte(bgr, binary, radius, eps)[0].cpu().numpy()
+
+
+def upsample_mask(image: np.ndarray, mask: np.ndarray, full_image: np.ndarray, radius: int = MATTE_RADIUS,
+                  eps: float = MATTE_EPS, device="cuda") -> "tuple[np.ndarray, np.ndarray]":
+    """A mask found on a reduced image, carried to the full-resolution image (additive): He and Sun's fast guided filter.
+    The guided filter's coefficients of alpha_matte(image, mask, radius, eps) are interpolated bilinearly (half-pixel
+    centres, as cv2.resize INTER_LINEAR) to full_image's size and applied to its colours, so edges follow the full image
+    (ggc_upsample_matte).  With full_image == image the alpha is alpha_matte's, bit for bit.
+
+    image: (H, W, 3) uint8 BGR; mask: (H, W) with values in {0, 1}; full_image: (H1, W1, 3) uint8 BGR with H1 >= H and
+    W1 >= W (at most 32768 on a side).  -> (alpha (H1, W1) float32 in [0, 1], mask (H1, W1) uint8 = alpha >= 0.5)."""
+    from ._engine import get_engine, check_matte_args, check_upsample_shapes
+    image = _check_image(image)
+    full = _check_image(full_image)
+    m = np.asarray(mask)
+    check_upsample_shapes((1, *image.shape), (1, *m.shape), (1, *full.shape), "upsample_mask")
+    if m.size and not np.isin(m, (0, 1)).all():
+        raise ValueError("upsample_mask: mask values must be 0 or 1")
+    check_matte_args(radius, eps)
+    eng = get_engine(device)
+    alpha, binary, _ = eng.upsample_matte(eng.to_device(image[None]), eng.to_device(np.ascontiguousarray(m, np.uint8)[None]),
+                                          eng.to_device(full[None]), radius, eps)
+    return alpha[0].cpu().numpy(), binary[0].cpu().numpy()
+
+
+def nearest_upsample(a: np.ndarray, h1: int, w1: int) -> np.ndarray:
+    """(H, W, ...) -> (h1, w1, ...) by the source pixel under each output pixel's centre: index
+    min(floor((i + 0.5) * H / h1), H - 1), the centre mapping of upsample_mask."""
+    a = np.asarray(a)
+    h, w = a.shape[:2]
+    ys = np.minimum(((np.arange(h1) + 0.5) * h / h1).astype(np.int64), h - 1)
+    xs = np.minimum(((np.arange(w1) + 0.5) * w / w1).astype(np.int64), w - 1)
+    return a[ys][:, xs]
 
 
 def refine_trimap(probs: np.ndarray, segments: np.ndarray, image: np.ndarray, threshold_fg: float = 0.55,
@@ -216,6 +269,48 @@ class _Hints:
         ok = (r >= 0) & (r < h) & (c >= 0) & (c < w)
         img = np.repeat(np.arange(len(self.ptr) - 1), np.diff(self.ptr))
         return np.bincount(img[ok], minlength=len(self.ptr) - 1) > 0
+
+
+def _full_args(full_bgr, bgr_shape, radius, eps) -> "Optional[tuple[int, float]]":
+    """(radius, eps) of the upsample when a full-resolution batch is given (shape and arguments checked here, before any
+    stage runs), else None."""
+    if full_bgr is None:
+        return None
+    from ._engine import check_matte_args, check_upsample_shapes
+    check_upsample_shapes(tuple(bgr_shape), tuple(bgr_shape[:3]), tuple(full_bgr.shape), "full_bgr")
+    check_matte_args(radius, eps)
+    return int(radius), float(eps)
+
+
+def _full_buffers(eng, full_bgr, compose: bool, mat) -> "Optional[dict]":
+    """The device outputs at full resolution: binary_mask, overlay and rgba (compose), alpha and rgba_soft (matte)."""
+    import torch
+    if full_bgr is None:
+        return None
+    shape = tuple(full_bgr.shape[:3])
+    out = {"binary_mask": eng.empty(*shape, dtype=torch.uint8)}
+    if compose:
+        out["overlay"], out["rgba"] = eng.empty(*shape, 3, dtype=torch.uint8), eng.empty(*shape, 4, dtype=torch.uint8)
+    if mat:
+        out["alpha"], out["rgba_soft"] = eng.empty(*shape), eng.empty(*shape, 4, dtype=torch.uint8)
+    return out
+
+
+def _full_post(leng, lo, hi, bgr, cleaned, full_bgr, full, fmat) -> None:
+    """The full-resolution outputs of images lo:hi from their cleaned working masks: ggc_upsample_matte, then
+    ggc_compose_outputs on the full image and the upsampled mask."""
+    alpha, soft = full.get("alpha"), full.get("rgba_soft")
+    leng.upsample_matte(bgr[lo:hi], cleaned[lo:hi], full_bgr[lo:hi], *fmat,
+                        out=(None if alpha is None else alpha[lo:hi], full["binary_mask"][lo:hi],
+                             None if soft is None else soft[lo:hi]))
+    if "overlay" in full:
+        leng.compose(full_bgr[lo:hi], full["binary_mask"][lo:hi], out=(full["overlay"][lo:hi], full["rgba"][lo:hi]))
+
+
+def _full_result(full: dict, i: int) -> FullResolution:
+    host = {k: v[i].cpu().numpy() for k, v in full.items()}
+    return FullResolution(binary_mask=host["binary_mask"], overlay=host.get("overlay"), rgba=host.get("rgba"),
+                          alpha=host.get("alpha"), rgba_soft=host.get("rgba_soft"))
 
 
 def _matte_args(matte: bool, radius, eps) -> "Optional[tuple[int, float]]":
@@ -376,12 +471,18 @@ class GCNGrabCutPipeline:
                              timing: Optional[dict] = None, grabcut_lanes: Optional[int] = None,
                              chunks: Optional[int] = None, hints=None, hint_radius: int = 5, hint_region: bool = False,
                              hints_as_prior: bool = False, return_state: bool = False, matte: bool = False,
-                             matte_radius: int = MATTE_RADIUS, matte_eps: float = MATTE_EPS) -> dict:
+                             matte_radius: int = MATTE_RADIUS, matte_eps: float = MATTE_EPS, full_bgr=None) -> dict:
         """bgr: (B,H,W,3) uint8 tensor on the pipeline's device.  Returns device tensors.
 
         matte=True (additive) also returns "alpha" (B,H,W) float32, the soft matte of the cleaned mask (alpha_matte with
         matte_radius / matte_eps), and "rgba_soft" (B,H,W,4) uint8, the cut-out with that alpha.  Every other output is
         the same as without it.
+
+        full_bgr (additive): a (B,H1,W1,3) uint8 tensor on the device, the same images at a resolution of at least the
+        working one.  The result then also has "full", a dict of device tensors at (H1, W1): "binary_mask", the cleaned
+        mask carried to the full image by upsample_mask (with matte_radius / matte_eps), and "overlay" / "rgba" composed
+        from it (compose=True), plus "alpha" and "rgba_soft" with matte=True.  Every other output is the same as without
+        it.
 
         return_state=True (additive) also returns what a GC_EVAL edit loop continues from: "gc_binary" (B,H,W) uint8,
         GrabCut's own binary mask before clean_mask; "bgd" / "fgd" (B,65) float64, the colour models; "gc_image"
@@ -409,12 +510,13 @@ class GCNGrabCutPipeline:
         n_chunks = self.chunks if chunks is None else int(chunks)
         hints = _Hints.of(hints, b, hint_radius, hint_region, hints_as_prior)
         mat = _matte_args(matte, matte_radius, matte_eps)
+        fmat = _full_args(full_bgr, bgr.shape, matte_radius, matte_eps)
         if n_chunks <= 0:                          # 0: one chunk per GrabCut lane once every chunk gets a lane's worth of images
             n_chunks = max(want, 1) if b >= 16 * max(want, 1) else 1
         if n_chunks > 1 and b >= 2 * n_chunks:
             return self._segment_pipelined(bgr, self.chunk_plan(b, n_chunks, self.chunk_ratio), cs, threshold_fg, threshold_bg,
                                            refine_iters, min_area_ratio, keep_largest, edge_aware, filter_radius, compose, timing,
-                                           hints, return_state, mat)
+                                           hints, return_state, mat, full_bgr, fmat)
 
         def tick():
             if timing is not None:
@@ -435,6 +537,7 @@ class GCNGrabCutPipeline:
         rgba = eng.empty(*bgr.shape[:3], 4, dtype=torch.uint8) if compose else None
         alpha = eng.empty(*bgr.shape[:3]) if mat else None
         rgba_soft = eng.empty(*bgr.shape[:3], 4, dtype=torch.uint8) if mat else None
+        full = _full_buffers(eng, full_bgr, compose, mat)
 
         def post(leng, lo, hi, binary_part):
             leng.clean_mask(binary_part, min_area_ratio, keep_largest, out=cleaned[lo:hi])
@@ -442,6 +545,8 @@ class GCNGrabCutPipeline:
                 leng.compose(bgr[lo:hi], cleaned[lo:hi], out=(overlay[lo:hi], rgba[lo:hi]))
             if mat:
                 leng.alpha_matte(bgr[lo:hi], cleaned[lo:hi], *mat, want_rgba=True, out=(alpha[lo:hi], rgba_soft[lo:hi]))
+            if full is not None:
+                _full_post(leng, lo, hi, bgr, cleaned, full_bgr, full, fmat)
 
         fused_post = timing is None
         binary, mask, bgd, fgd = eng.grabcut_lanes(gc_img, mask, self.gc_config.n_iter, 0, self.gc_config.seed, lanes,
@@ -463,12 +568,15 @@ class GCNGrabCutPipeline:
             out["overlay"], out["rgba"] = overlay, rgba
         if mat:
             out["alpha"], out["rgba_soft"] = alpha, rgba_soft
+        if full is not None:
+            out["full"] = full
         if timing is not None:
             timing["postprocess"] = tick() - t
         return out
 
     def _segment_pipelined(self, bgr, plan, cs, threshold_fg, threshold_bg, refine_iters, min_area_ratio, keep_largest,
-                           edge_aware, filter_radius, compose, timing, hints=None, return_state=False, mat=None) -> dict:
+                           edge_aware, filter_radius, compose, timing, hints=None, return_state=False, mat=None,
+                           full_bgr=None, fmat=None) -> dict:
         """The software pipeline behind segment_batch_device: chunk k's GrabCut lane starts as soon as chunk k's trimaps are
         on the device; the caller's stream goes on with chunk k+1's SLIC / graph / network / trimap."""
         import torch
@@ -492,6 +600,7 @@ class GCNGrabCutPipeline:
         rgba = eng.empty(b, h, w, 4, dtype=torch.uint8) if compose else None
         alpha = eng.empty(b, h, w) if mat else None
         rgba_soft = eng.empty(b, h, w, 4, dtype=torch.uint8) if mat else None
+        full = _full_buffers(eng, full_bgr, compose, mat)
         if return_state:
             st_binary = eng.empty(b, h, w, dtype=torch.uint8)
             st_bgd = eng.empty(b, 65, dtype=torch.float64)
@@ -527,6 +636,8 @@ class GCNGrabCutPipeline:
                     leng.compose(img, cleaned[lo:hi], out=(overlay[lo:hi], rgba[lo:hi]))
                 if mat:
                     leng.alpha_matte(img, cleaned[lo:hi], *mat, want_rgba=True, out=(alpha[lo:hi], rgba_soft[lo:hi]))
+                if full is not None:
+                    _full_post(leng, lo, hi, bgr, cleaned, full_bgr, full, fmat)
                 if ev is not None:
                     ev[2].record(stream)
                 done = torch.cuda.Event()
@@ -561,6 +672,8 @@ class GCNGrabCutPipeline:
             out["overlay"], out["rgba"] = overlay, rgba
         if mat:
             out["alpha"], out["rgba_soft"] = alpha, rgba_soft
+        if full is not None:
+            out["full"] = full
         if timing is not None:                        # stage times from stream events (the stages overlap: they add up to more than the wall time)
             torch.cuda.synchronize(dev)
             front = sum(e[3].elapsed_time(e[4]) for e in stamps) / 1e3
@@ -570,24 +683,38 @@ class GCNGrabCutPipeline:
             timing["wall"] = time.perf_counter() - t_host
         return out
 
-    def segment_batch(self, images: Sequence[np.ndarray], hints=None, **kwargs) -> list[SegmentationResult]:
+    def segment_batch(self, images: Sequence[np.ndarray], hints=None, full_images=None, **kwargs) -> list[SegmentationResult]:
         """Segment equally sized BGR images as one batch (additive API).  hints: one None or (fg_points, bg_points) per
-        image, with hint_radius / hint_region / hints_as_prior among kwargs (segment_batch_device)."""
+        image, with hint_radius / hint_region / hints_as_prior among kwargs (segment_batch_device).  full_images
+        (additive): the same images at one larger size each, (H1, W1, 3) uint8 BGR; every result's `full` then holds the
+        outputs at that size (segment_batch_device's full_bgr)."""
         imgs = [_check_image(im) for im in images]
         if not imgs:
             return []
         if any(im.shape != imgs[0].shape for im in imgs):
             raise ValueError("segment_batch needs images of one size; group them by shape")
+        full_bgr = None
+        if full_images is not None:
+            fulls = [_check_image(im) for im in full_images]
+            if len(fulls) != len(imgs):
+                raise ValueError(f"{len(fulls)} full images for {len(imgs)} images")
+            if any(f.shape != fulls[0].shape for f in fulls):
+                raise ValueError("segment_batch needs full images of one size; group them by shape")
+            from ._engine import check_upsample_shapes
+            check_upsample_shapes((len(imgs), *imgs[0].shape), (len(imgs), *imgs[0].shape[:2]),
+                                  (len(imgs), *fulls[0].shape), "full_images")
+            full_bgr = self._eng.to_device(np.stack(fulls))
         timing: dict[str, float] = {}
         bgr = self._eng.to_device(np.stack(imgs))
-        out = self.segment_batch_device(bgr, timing=timing, hints=hints, **kwargs)
+        out = self.segment_batch_device(bgr, timing=timing, hints=hints, full_bgr=full_bgr, **kwargs)
         host = {k: out[k].cpu().numpy() for k in ("binary_mask", "trimap", "segments", "overlay", "rgba", "alpha", "rgba_soft")
                 if k in out}
         per_image = {k: v / len(imgs) for k, v in timing.items()}
         return [SegmentationResult(image=imgs[i], binary_mask=host["binary_mask"][i], trimap=host["trimap"][i],
                                    segments=host["segments"][i], overlay=host["overlay"][i], rgba=host["rgba"][i],
                                    timing=dict(per_image), alpha=host["alpha"][i] if "alpha" in host else None,
-                                   rgba_soft=host["rgba_soft"][i] if "rgba_soft" in host else None)
+                                   rgba_soft=host["rgba_soft"][i] if "rgba_soft" in host else None,
+                                   full=_full_result(out["full"], i) if "full" in out else None)
                 for i in range(len(imgs))]
 
     def _click_round(self, binary, gt, mask, image, bgd, fgd, hint_ptr, hint_radius=5, n_iter=1):
@@ -693,13 +820,16 @@ class GCNGrabCutPipeline:
                 refine_iters: int = 0, min_area_ratio: float = 0.002, keep_largest: bool = False,
                 edge_aware: bool = True, filter_radius: int = 8, fg_points=None, bg_points=None, hint_radius: int = 5,
                 hint_region: bool = False, hints_as_prior: bool = False, matte: bool = False,
-                matte_radius: int = MATTE_RADIUS, matte_eps: float = MATTE_EPS) -> SegmentationResult:
+                matte_radius: int = MATTE_RADIUS, matte_eps: float = MATTE_EPS,
+                full_image: Optional[np.ndarray] = None) -> SegmentationResult:
         """Full pipeline on one BGR image (reference pipeline.py:265-352).
 
         Additive: fg_points / bg_points are user clicks, (row, col) pairs, applied as hard constraints on the trimap
         GrabCut starts from (see segment_batch_device for hint_radius, hint_region and hints_as_prior); matte=True also
-        fills the result's alpha and rgba_soft (segment_batch_device)."""
+        fills the result's alpha and rgba_soft (segment_batch_device); full_image, the same image at a larger size, fills
+        the result's `full` (segment_batch_device's full_bgr)."""
         image = _check_image(image)
+        full_bgr = None if full_image is None else self._eng.to_device(_check_image(full_image)[None])
         timing: dict[str, float] = {}
         hints = None if fg_points is None and bg_points is None else \
             [(() if fg_points is None else fg_points, () if bg_points is None else bg_points)]
@@ -707,20 +837,27 @@ class GCNGrabCutPipeline:
                                         min_area_ratio, keep_largest, edge_aware, filter_radius, timing=timing,
                                         hints=hints, hint_radius=hint_radius, hint_region=hint_region,
                                         hints_as_prior=hints_as_prior, matte=matte, matte_radius=matte_radius,
-                                        matte_eps=matte_eps)
+                                        matte_eps=matte_eps, full_bgr=full_bgr)
         return SegmentationResult(
             image=image, binary_mask=out["binary_mask"][0].cpu().numpy(), trimap=out["trimap"][0].cpu().numpy(),
             segments=out["segments"][0].cpu().numpy(), overlay=out["overlay"][0].cpu().numpy(),
             rgba=out["rgba"][0].cpu().numpy(), timing=timing,
             alpha=out["alpha"][0].cpu().numpy() if matte else None,
-            rgba_soft=out["rgba_soft"][0].cpu().numpy() if matte else None)
+            rgba_soft=out["rgba_soft"][0].cpu().numpy() if matte else None,
+            full=_full_result(out["full"], 0) if "full" in out else None)
 
     def segment_bbox(self, image: np.ndarray, bbox: tuple[int, int, int, int], matte: bool = False,
-                     matte_radius: int = MATTE_RADIUS, matte_eps: float = MATTE_EPS) -> SegmentationResult:
+                     matte_radius: int = MATTE_RADIUS, matte_eps: float = MATTE_EPS,
+                     full_image: Optional[np.ndarray] = None) -> SegmentationResult:
         """Classical GrabCut with a bounding box (reference pipeline.py:354-380).  Additive: matte=True also fills the
-        result's alpha and rgba_soft, the soft matte of the returned mask (alpha_matte)."""
+        result's alpha and rgba_soft, the soft matte of the returned mask (alpha_matte); full_image, the same image at a
+        larger size, fills the result's `full` from the returned mask (upsample_mask, then the overlay and cut-out)."""
         image = _check_image(image)
         mat = _matte_args(matte, matte_radius, matte_eps)
+        full_img = None
+        if full_image is not None:
+            full_img = _check_image(full_image)
+            fmat = _full_args(full_img[None], (1, *image.shape), matte_radius, matte_eps)
         gc = GrabCut(image, self.gc_config, device=self.device)
         binary_mask = gc.run_with_bbox(bbox)
         x, y, w, h = bbox
@@ -736,6 +873,14 @@ class GCNGrabCutPipeline:
             alpha, rgba_soft = eng.alpha_matte(eng.to_device(image[None]), eng.to_device(binary_mask[None]), *mat,
                                                want_rgba=True)
             alpha, rgba_soft = alpha[0].cpu().numpy(), rgba_soft[0].cpu().numpy()
+        full = None
+        if full_img is not None:
+            eng = self._eng
+            full_bgr = eng.to_device(full_img[None])
+            bufs = _full_buffers(eng, full_bgr, True, mat)
+            _full_post(eng, 0, 1, eng.to_device(image[None]), eng.to_device(np.ascontiguousarray(binary_mask, np.uint8)[None]),
+                       full_bgr, bufs, fmat)
+            full = _full_result(bufs, 0)
         return SegmentationResult(image=image, binary_mask=binary_mask, trimap=trimap,
                                   segments=np.zeros((H, W), dtype=np.int32), overlay=gc.overlay_mask(),
-                                  rgba=gc.crop_foreground(), alpha=alpha, rgba_soft=rgba_soft)
+                                  rgba=gc.crop_foreground(), alpha=alpha, rgba_soft=rgba_soft, full=full)

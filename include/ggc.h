@@ -50,7 +50,8 @@
 extern "C" {
 #endif
 
-#define GGC_VERSION 360 /* 0.3.6: ggc_alpha_matte (soft alpha matte of a binary mask: colour guided-filter feathering);
+#define GGC_VERSION 370 /* 0.3.7: ggc_upsample_matte (the matte's mask and alpha at a larger resolution: fast guided filter);
+                           0.3.6: ggc_alpha_matte (soft alpha matte of a binary mask: colour guided-filter feathering);
                            0.3.5: ggc_grid_maxflow (the GrabCut max-flow on a caller's network, a test hook);
                            0.3.4: ggc_next_click (the next simulated click of the NoC protocol);
                            0.3.3: ggc_apply_hints (user clicks as hard constraints on the GrabCut mask);
@@ -433,6 +434,26 @@ int ggc_compose_outputs(ggc_ctx* ctx, ggc_stream stream, int B, int H, int W,
  * Does not synchronise. */
 int ggc_alpha_matte(ggc_ctx* ctx, ggc_stream stream, int B, int H, int W, const uint8_t* bgr, const uint8_t* binary,
                     int radius, float eps, float* alpha, uint8_t* rgba);
+
+/* O2 — the soft matte of O1 at a larger resolution (additive; He and Sun's fast guided filter): the mean coefficients
+ * C = (mean a / 255, mean b) of ggc_alpha_matte's stage 2 at the working resolution, interpolated bilinearly to the
+ * full resolution and applied to the full-resolution colours.
+ *   bgr [dev] u8 [B,H,W,3], binary [dev] u8 [B,H,W] (nonzero = foreground), radius and eps: as ggc_alpha_matte
+ *   bgr_full [dev] u8 [B,H1,W1,3] with H <= H1 <= 32768, W <= W1 <= 32768 (else GGC_E_SHAPE, as for B outside 1..65535)
+ * For output pixel (y, x), in float64: sx = ((x + 0.5) * W) / W1 - 0.5, raised to 0 if negative; x0 = floor(sx), and
+ * x0 = W - 1 with wx = 0 when x0 >= W - 1, else wx = sx - x0; x1 = min(x0 + 1, W - 1); the same for y with H, H1
+ * (cv2.resize INTER_LINEAR's half-pixel centres).  c_k = lerp(lerp(C_k[y0,x0], C_k[y0,x1], wx), lerp(C_k[y1,x0],
+ * C_k[y1,x1], wx), wy) with lerp(u, v, t) = u + t (v - u), and alpha = clamp(c_0 B + c_1 G + c_2 R + c_3, 0, 1) with the
+ * full-resolution bytes, summed in ggc_alpha_matte's order.
+ *   alpha_full [dev] f32 [B,H1,W1] = (float)alpha       binary_full [dev] u8 [B,H1,W1] = alpha >= 0.5 (on the double)
+ *   rgba_full [dev] u8 [B,H1,W1,4] = bgr_full, floor(255 alpha + 0.5)      (each may be NULL, not all three)
+ * With H1 = H, W1 = W and bgr_full = bgr every weight is 0: alpha_full and rgba_full are ggc_alpha_matte's outputs bit
+ * for bit.  A pixel whose four source pixels lie farther than 2*radius from every change of the mask gets exactly that
+ * mask value.  Every image's result is independent of the batch it is in (bit for bit); no atomics.  Scratch: 64 bytes
+ * per working pixel from the context.  Does not synchronise. */
+int ggc_upsample_matte(ggc_ctx* ctx, ggc_stream stream, int B, int H, int W, const uint8_t* bgr, const uint8_t* binary,
+                       int H1, int W1, const uint8_t* bgr_full, int radius, float eps,
+                       float* alpha_full, uint8_t* binary_full, uint8_t* rgba_full);
 
 /* R0 — IoU = tp / (tp + fp + fn + 1e-8) per image (metrics.py:79-84).
  *   iou [dev] f64 [B] (may be NULL)   counts [dev] u64 [B,3] = tp, fp, fn (may be NULL) */

@@ -8,6 +8,7 @@ Same command line as the reference's inference.py (flags :26-56, outputs :146-15
     python3 inference.py --image cat.jpg --keep-largest --save mask overlay
     python3 inference.py --image cat.jpg --fg-point 120,200 --bg-point 10,10 --hint-radius 8
     python3 inference.py --image cat.jpg --save mask alpha cutout          # soft edges: alpha matte and cut-out
+    python3 inference.py --image big.jpg --full-res --save mask cutout     # outputs at the photo's own size
 
 Images are decoded / written with Pillow (OpenCV is not a dependency of this build); folders are processed in
 batches of equally sized images so that the whole batch stays resident in HBM.
@@ -57,6 +58,11 @@ def build_parser() -> argparse.ArgumentParser:
     parser.add_argument("--matte-radius", type=int, default=4,
                         help="Window radius of the alpha matte, 1..64, in pixels of the image as segmented")
     parser.add_argument("--matte-eps", type=float, default=1e-4, help="Regularisation of the alpha matte (>= 1e-12)")
+    # additive: outputs at the original size (ggc_upsample_matte), for images that --max-size shrank
+    parser.add_argument("--full-res", action="store_true",
+                        help="Write every output at the original image size: the mask (and alpha) found at --max-size "
+                             "is carried to the original by a fast guided filter with --matte-radius / --matte-eps, the "
+                             "trimap by nearest neighbour; images already within --max-size are unaffected")
     return parser
 
 
@@ -74,18 +80,23 @@ def scale_points(points, orig_hw, new_hw):
     return [(r * h1 // h0, c * w1 // w0) for r, c in points]
 
 
-def read_bgr(path: Path, max_size: int):
+def read_bgr(path: Path, max_size: int, keep_original: bool = False):
+    """The image as BGR uint8, its longest side shrunk to max_size; keep_original=True -> (that, the decoded original)."""
     from PIL import Image
     try:
         im = Image.open(path).convert("RGB")
     except Exception:
         return None
+    orig = im
     if max_size > 0:
         w, h = im.size
         scale = min(max_size / max(h, w), 1.0)
         if scale < 1.0:
             im = im.resize((int(w * scale), int(h * scale)), Image.BOX)   # area averaging, as cv2.INTER_AREA
-    return np.ascontiguousarray(np.asarray(im)[:, :, ::-1])
+    bgr = np.ascontiguousarray(np.asarray(im)[:, :, ::-1])
+    if keep_original:
+        return bgr, (bgr if orig is im else np.ascontiguousarray(np.asarray(orig)[:, :, ::-1]))
+    return bgr
 
 
 def load_model(checkpoint: str, model_name: str = "resgcn", hidden: int = 128, layers: int = 6, device: str = "cuda",
@@ -126,13 +137,13 @@ def main() -> None:
     if args.hint_radius < 0:
         parser.error("--hint-radius must be >= 0")
     matte = "alpha" in args.save or "cutout" in args.save
-    if matte and not 1 <= args.matte_radius <= 64:
+    if (matte or args.full_res) and not 1 <= args.matte_radius <= 64:
         parser.error("--matte-radius must be in 1..64")
-    if matte and not args.matte_eps >= 1e-12:
+    if (matte or args.full_res) and not args.matte_eps >= 1e-12:
         parser.error("--matte-eps must be >= 1e-12")
     from src.gcn_grabcut import GCNGrabCutPipeline
     from src.gcn_grabcut.graph_builder import SuperpixelGraphConfig
-    from src.gcn_grabcut.pipeline import _colour_trimap, _write_png, alpha_to_u8
+    from src.gcn_grabcut.pipeline import _colour_trimap, _write_png, alpha_to_u8, nearest_upsample
 
     model = load_model(args.checkpoint, args.model, args.hidden, args.layers, args.device)
 
@@ -150,11 +161,16 @@ def main() -> None:
 
     by_shape: dict = {}
     for path in paths:
-        image = read_bgr(path, args.max_size)
+        image = read_bgr(path, args.max_size, keep_original=args.full_res)
         if image is None:
             print(f"[inference] skipping unreadable file: {path}")
             continue
-        by_shape.setdefault(image.shape, []).append((path, image))
+        if args.full_res:                               # grouped by (working shape, original shape)
+            image, orig = image
+            full = orig if orig.shape != image.shape else None
+            by_shape.setdefault((image.shape, orig.shape), []).append((path, image, full))
+        else:
+            by_shape.setdefault(image.shape, []).append((path, image, None))
 
     total_t, n_done = 0.0, 0
     for items in by_shape.values():
@@ -164,7 +180,7 @@ def main() -> None:
             hint_kw = {}
             if args.fg_point or args.bg_point:          # --image only: one chunk of one image
                 from PIL import Image
-                path, image = chunk[0]
+                path, image, _ = chunk[0]
                 with Image.open(path) as im:
                     orig_hw = im.size[::-1]
                 hint_kw = dict(hints=[(scale_points(args.fg_point, orig_hw, image.shape[:2]),
@@ -172,27 +188,33 @@ def main() -> None:
                                hint_radius=args.hint_radius)
             if matte:
                 hint_kw.update(matte=True, matte_radius=args.matte_radius, matte_eps=args.matte_eps)
+            if chunk[0][2] is not None:                 # --full-res on images that --max-size shrank
+                hint_kw.update(full_images=[full for _, _, full in chunk], matte_radius=args.matte_radius,
+                               matte_eps=args.matte_eps)
             results = pipeline.segment_batch(
-                [im for _, im in chunk], threshold_fg=args.threshold, threshold_bg=args.threshold,
+                [im for _, im, _ in chunk], threshold_fg=args.threshold, threshold_bg=args.threshold,
                 refine_iters=args.refine, min_area_ratio=args.min_area, keep_largest=args.keep_largest,
                 edge_aware=not args.no_edge_aware, filter_radius=args.filter_radius, **hint_kw)
             elapsed = (time.perf_counter() - t0) / len(chunk)
-            for (path, _), result in zip(chunk, results):
+            for (path, _, _), result in zip(chunk, results):
                 total_t += elapsed
                 n_done += 1
                 stem = out_dir / path.stem
+                out = result if result.full is None else result.full          # every file at one size
                 if "mask" in args.save:
-                    _write_png(f"{stem}_mask.png", result.binary_mask * 255)
+                    _write_png(f"{stem}_mask.png", out.binary_mask * 255)
                 if "overlay" in args.save:
-                    _write_png(f"{stem}_overlay.png", result.overlay)
+                    _write_png(f"{stem}_overlay.png", out.overlay)
                 if "rgba" in args.save:
-                    _write_png(f"{stem}_rgba.png", result.rgba)
+                    _write_png(f"{stem}_rgba.png", out.rgba)
                 if "trimap" in args.save:
-                    _write_png(f"{stem}_trimap.png", _colour_trimap(result.trimap))
+                    trimap = result.trimap if result.full is None else nearest_upsample(result.trimap,
+                                                                                        *out.binary_mask.shape)
+                    _write_png(f"{stem}_trimap.png", _colour_trimap(trimap))
                 if "alpha" in args.save:
-                    _write_png(f"{stem}_alpha.png", alpha_to_u8(result.alpha))
+                    _write_png(f"{stem}_alpha.png", alpha_to_u8(out.alpha))
                 if "cutout" in args.save:
-                    _write_png(f"{stem}_cutout.png", result.rgba_soft)
+                    _write_png(f"{stem}_cutout.png", out.rgba_soft)
                 t = result.timing
                 print(f"[{n_done}/{len(paths)}] {path.name}  fg={result.binary_mask.mean():.1%}  "
                       f"graph={t.get('graph_build', 0):.4f}s gcn={t.get('gcn_inference', 0):.4f}s "
