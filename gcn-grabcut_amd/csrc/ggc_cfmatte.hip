@@ -1,0 +1,518 @@
+// ggc_cfmatte.hip — O3: closed-form alpha matte (Levin, Lischinski and Weiss, TPAMI 2008) of a binary mask, solved on
+// the device by Jacobi-preconditioned conjugate gradients with the matting Laplacian applied without a matrix (He, Sun
+// and Tang, CVPR 2010).  include/ggc.h states the system; DESIGN.md §5.13 the tiling and the bytes.
+//
+// Layout.  A tile is 16 x 16 pixels of one image and a block of 256 threads, one per pixel.  The unknown band U is found
+// over the whole frame once per call (k_cf_edge, k_cf_dilate_h, k_cf_dilate_v, which also counts U per tile); the host
+// reads the counts and lists the tiles that hold U or touch a tile that does (every window centre within r <= 16 of U),
+// image by image.  Every later kernel runs over that list only.  Per listed tile and iteration:
+//   k_cf_window  a_k, b_k of the p of the product at every centre k in K of the tile (p staged with an r halo in LDS)
+//   k_cf_pixel   (L p)_i = c_i p_i - sum_k (a_k . I_i + b_k) on U (a, b staged with an r halo in LDS); per-tile d . q
+//   k_cf_alpha   per image: alpha = rz / (d . q)
+//   k_cf_update  x += alpha d, r -= alpha q on U; per-tile r . z and r . r (z = r / diag L)
+//   k_cf_beta    per image: convergence, the iteration count, beta
+//   k_cf_direction  d = z + beta d on U
+// The window statistics (mu_k and Delta_k^-1 from exact integer window sums, the 3x3 inverse by the adjugate in float64)
+// and diag L are computed once per call.  Every per-tile sum is a fixed LDS tree over the tile's 256 pixels, every
+// per-image sum one wave over that image's run of the tile list in a fixed order (lane 0's result), so an image's
+// iterates do not depend on the batch: a batch equals its single-image calls bit for bit.  No float atomics; the only
+// atomic is an integer count of converged images, which the host polls every CF_POLL iterations to stop early.
+#include "ggc_internal.h"
+#include <algorithm>
+#include <cmath>
+
+namespace ggc {
+
+namespace {
+
+constexpr int CF_T = 16;                          // tile side
+constexpr int CF_THREADS = CF_T * CF_T;
+constexpr int CF_RMAX = 8;
+constexpr int CF_SMAX = CF_T + 2 * CF_RMAX;       // staged side at the largest radius
+constexpr int CF_POLL = 8;                        // iterations between polls of the converged count
+
+constexpr uint8_t F_M = 1, F_U = 2;               // flags: mask value, unknown
+
+struct alignas(8) CfStats { double mu[3]; double d00, d01, d02, d11, d12, d22; };   // Delta^-1, symmetric
+struct alignas(32) CfAB { double a0, a1, a2, b; };
+struct CfImage {                                  // per-image solver state
+    double rz, rr0, alpha, beta, rel;
+    int iters, done, tile_lo, tile_hi;
+};
+
+__device__ __forceinline__ double colour(const uint8_t* px, int c) { return (double)px[c] * (1.0 / 255.0); }
+
+// ---------------------------------------------------------------- the band, over the whole frame
+// grid (cdiv(W, 16), cdiv(H, 16), B), 16 x 16 threads
+__global__ void __launch_bounds__(CF_THREADS) k_cf_edge(int H, int W, const uint8_t* __restrict__ binary,
+                                                        uint8_t* __restrict__ edge) {
+    const int x = blockIdx.x * CF_T + threadIdx.x, y = blockIdx.y * CF_T + threadIdx.y;
+    if (x >= W || y >= H) return;
+    const uint8_t* m = binary + (size_t)blockIdx.z * H * W;
+    bool lo = true, hi = false;
+    for (int dy = -1; dy <= 1; ++dy)
+        for (int dx = -1; dx <= 1; ++dx) {
+            const int yy = y + dy, xx = x + dx;
+            if (yy < 0 || yy >= H || xx < 0 || xx >= W) continue;
+            const bool v = m[(size_t)yy * W + xx] != 0;
+            lo = lo && v;
+            hi = hi || v;
+        }
+    edge[(size_t)blockIdx.z * H * W + (size_t)y * W + x] = hi && !lo ? 1 : 0;
+}
+
+__global__ void __launch_bounds__(CF_THREADS) k_cf_dilate_h(int H, int W, int band, const uint8_t* __restrict__ edge,
+                                                            uint8_t* __restrict__ out) {
+    const int x = blockIdx.x * CF_T + threadIdx.x, y = blockIdx.y * CF_T + threadIdx.y;
+    if (x >= W || y >= H) return;
+    const uint8_t* row = edge + (size_t)blockIdx.z * H * W + (size_t)y * W;
+    uint8_t v = 0;
+    for (int xx = max(0, x - band); xx <= min(W - 1, x + band); ++xx) v |= row[xx];
+    out[(size_t)blockIdx.z * H * W + (size_t)y * W + x] = v;
+}
+
+// flags = m | U << 1; tile_u [B, tiles] = pixels of U in each tile (a block is a tile)
+__global__ void __launch_bounds__(CF_THREADS) k_cf_dilate_v(int H, int W, int band, const uint8_t* __restrict__ hdil,
+                                                            const uint8_t* __restrict__ binary, uint8_t* __restrict__ flags,
+                                                            int32_t* __restrict__ tile_u) {
+    __shared__ int s_cnt[CF_THREADS];
+    const int tid = threadIdx.y * CF_T + threadIdx.x;
+    const int x = blockIdx.x * CF_T + threadIdx.x, y = blockIdx.y * CF_T + threadIdx.y;
+    const size_t base = (size_t)blockIdx.z * H * W;
+    int u = 0;
+    if (x < W && y < H) {
+        uint8_t v = 0;
+        for (int yy = max(0, y - band); yy <= min(H - 1, y + band); ++yy) v |= hdil[base + (size_t)yy * W + x];
+        const size_t i = base + (size_t)y * W + x;
+        flags[i] = (binary[i] != 0 ? F_M : 0) | (v ? F_U : 0);
+        u = v ? 1 : 0;
+    }
+    s_cnt[tid] = u;
+    __syncthreads();
+    for (int s = CF_THREADS / 2; s > 0; s >>= 1) {
+        if (tid < s) s_cnt[tid] += s_cnt[tid + s];
+        __syncthreads();
+    }
+    if (tid == 0) tile_u[((size_t)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x] = s_cnt[0];
+}
+
+// ---------------------------------------------------------------- per listed tile
+struct TileRef { int b, ty, tx; };
+
+__device__ __forceinline__ TileRef tile_of(const int2* __restrict__ tiles, int ntx) {
+    const int2 t = tiles[blockIdx.x];
+    return TileRef{t.x, t.y / ntx, t.y % ntx};
+}
+
+// Delta_k^-1 and mu_k of every centre of the tile that lies in K, from exact integer window sums
+__global__ void __launch_bounds__(CF_THREADS) k_cf_stats(int H, int W, int r, double eps, int ntx,
+                                                         const int2* __restrict__ tiles, const uint8_t* __restrict__ bgr,
+                                                         CfStats* __restrict__ stats) {
+    const TileRef t = tile_of(tiles, ntx);
+    const int x = t.tx * CF_T + threadIdx.x, y = t.ty * CF_T + threadIdx.y;
+    if (x < r || x >= W - r || y < r || y >= H - r) return;       // not in K (outside the image included)
+    const uint8_t* im = bgr + (size_t)t.b * H * W * 3;
+    uint32_t s[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+    for (int yy = y - r; yy <= y + r; ++yy)
+        for (int xx = x - r; xx <= x + r; ++xx) {
+            const uint8_t* px = im + ((size_t)yy * W + xx) * 3;
+            const uint32_t c0 = px[0], c1 = px[1], c2 = px[2];
+            s[0] += c0; s[1] += c1; s[2] += c2;
+            s[3] += c0 * c0; s[4] += c0 * c1; s[5] += c0 * c2; s[6] += c1 * c1; s[7] += c1 * c2; s[8] += c2 * c2;
+        }
+    const int64_t n = (int64_t)(2 * r + 1) * (2 * r + 1);
+    const double nn = (double)n * (double)n, dii = 65025.0 * nn, e = eps / (double)n;
+    auto centred = [&](uint32_t sjk, uint32_t sj, uint32_t sk) {
+        return (double)(n * (int64_t)sjk - (int64_t)sj * (int64_t)sk) / dii;
+    };
+    const double m00 = centred(s[3], s[0], s[0]) + e, m01 = centred(s[4], s[0], s[1]), m02 = centred(s[5], s[0], s[2]);
+    const double m11 = centred(s[6], s[1], s[1]) + e, m12 = centred(s[7], s[1], s[2]), m22 = centred(s[8], s[2], s[2]) + e;
+    const double c00 = m11 * m22 - m12 * m12, c01 = m02 * m12 - m01 * m22, c02 = m01 * m12 - m02 * m11;
+    const double c11 = m00 * m22 - m02 * m02, c12 = m01 * m02 - m00 * m12, c22 = m00 * m11 - m01 * m01;
+    const double det = m00 * c00 + m01 * c01 + m02 * c02;
+    const double dn = 255.0 * (double)n;
+    CfStats st;
+    st.mu[0] = (double)s[0] / dn; st.mu[1] = (double)s[1] / dn; st.mu[2] = (double)s[2] / dn;
+    st.d00 = c00 / det; st.d01 = c01 / det; st.d02 = c02 / det; st.d11 = c11 / det; st.d12 = c12 / det; st.d22 = c22 / det;
+    stats[(size_t)t.b * H * W + (size_t)y * W + x] = st;
+}
+
+// SETUP: p = the mask on every pixel; else p = d on U and 0 elsewhere
+template <bool SETUP>
+__device__ __forceinline__ double p_value(uint8_t f, const double* __restrict__ d, size_t i) {
+    if constexpr (SETUP) return (f & F_M) ? 1.0 : 0.0;
+    else return (f & F_U) ? d[i] : 0.0;
+}
+
+template <bool SETUP>
+__global__ void __launch_bounds__(CF_THREADS) k_cf_window(int H, int W, int r, int ntx, const int2* __restrict__ tiles,
+                                                          const CfImage* __restrict__ img, const uint8_t* __restrict__ bgr,
+                                                          const uint8_t* __restrict__ flags, const CfStats* __restrict__ stats,
+                                                          const double* __restrict__ d, CfAB* __restrict__ ab) {
+    __shared__ double s_p[CF_SMAX * CF_SMAX];
+    __shared__ double s_i[3][CF_SMAX * CF_SMAX];
+    const TileRef t = tile_of(tiles, ntx);
+    if (img[t.b].done) return;                                   // uniform over the block
+    const int tid = threadIdx.y * CF_T + threadIdx.x;
+    const int S = CF_T + 2 * r, x0 = t.tx * CF_T - r, y0 = t.ty * CF_T - r;
+    const size_t base = (size_t)t.b * H * W;
+    for (int e = tid; e < S * S; e += CF_THREADS) {
+        const int yy = y0 + e / S, xx = x0 + e % S;
+        double p = 0.0, i0 = 0.0, i1 = 0.0, i2 = 0.0;
+        if (yy >= 0 && yy < H && xx >= 0 && xx < W) {
+            const size_t i = base + (size_t)yy * W + xx;
+            const double pv = p_value<SETUP>(flags[i], d, i);
+            const uint8_t* px = bgr + 3 * i;
+            p = pv; i0 = colour(px, 0) * pv; i1 = colour(px, 1) * pv; i2 = colour(px, 2) * pv;
+        }
+        s_p[e] = p; s_i[0][e] = i0; s_i[1][e] = i1; s_i[2][e] = i2;
+    }
+    __syncthreads();
+    const int x = t.tx * CF_T + threadIdx.x, y = t.ty * CF_T + threadIdx.y;
+    if (x < r || x >= W - r || y < r || y >= H - r) return;
+    double sp = 0.0, s0 = 0.0, s1 = 0.0, s2 = 0.0;
+    for (int dy = 0; dy <= 2 * r; ++dy) {
+        const int row = (threadIdx.y + dy) * S + threadIdx.x;
+        for (int dx = 0; dx <= 2 * r; ++dx) {
+            sp += s_p[row + dx]; s0 += s_i[0][row + dx]; s1 += s_i[1][row + dx]; s2 += s_i[2][row + dx];
+        }
+    }
+    const double n = (double)(2 * r + 1) * (double)(2 * r + 1);
+    const CfStats st = stats[base + (size_t)y * W + x];
+    const double mp = sp / n;
+    const double v0 = s0 / n - st.mu[0] * mp, v1 = s1 / n - st.mu[1] * mp, v2 = s2 / n - st.mu[2] * mp;
+    const double a0 = st.d00 * v0 + st.d01 * v1 + st.d02 * v2;
+    const double a1 = st.d01 * v0 + st.d11 * v1 + st.d12 * v2;
+    const double a2 = st.d02 * v0 + st.d12 * v1 + st.d22 * v2;
+    ab[base + (size_t)y * W + x] = CfAB{a0, a1, a2, mp - (a0 * st.mu[0] + a1 * st.mu[1] + a2 * st.mu[2])};
+}
+
+// the fixed-order sum of the block's 256 values (thread 0 holds it)
+__device__ __forceinline__ double block_sum(double v, double* s, int tid) {
+    s[tid] = v;
+    __syncthreads();
+    for (int k = CF_THREADS / 2; k > 0; k >>= 1) {
+        if (tid < k) s[tid] += s[tid + k];
+        __syncthreads();
+    }
+    return s[0];
+}
+
+// q = (L p) on U.  SETUP: p = m; r = -q, x = m, diag L, and the per-tile r . z, r . r (into part_a, part_b); else the
+// per-tile d . q (into part_a)
+template <bool SETUP>
+__global__ void __launch_bounds__(CF_THREADS) k_cf_pixel(int H, int W, int r, int ntx, const int2* __restrict__ tiles,
+                                                         const CfImage* __restrict__ img, const uint8_t* __restrict__ bgr,
+                                                         const uint8_t* __restrict__ flags, const CfStats* __restrict__ stats,
+                                                         const CfAB* __restrict__ ab, const double* __restrict__ d,
+                                                         double* __restrict__ q, double* __restrict__ res, double* __restrict__ x,
+                                                         double* __restrict__ diag, double* __restrict__ part_a,
+                                                         double* __restrict__ part_b) {
+    __shared__ CfAB s_ab[CF_SMAX * CF_SMAX];
+    __shared__ double s_red[CF_THREADS];
+    const TileRef t = tile_of(tiles, ntx);
+    if (img[t.b].done) return;
+    const int tid = threadIdx.y * CF_T + threadIdx.x;
+    const int S = CF_T + 2 * r, x0 = t.tx * CF_T - r, y0 = t.ty * CF_T - r;
+    const size_t base = (size_t)t.b * H * W;
+    for (int e = tid; e < S * S; e += CF_THREADS) {              // centres outside K are staged as 0 and skipped below
+        const int yy = y0 + e / S, xx = x0 + e % S;
+        const bool in_k = yy >= r && yy < H - r && xx >= r && xx < W - r;
+        s_ab[e] = in_k ? ab[base + (size_t)yy * W + xx] : CfAB{0.0, 0.0, 0.0, 0.0};
+    }
+    __syncthreads();
+    const int xp = t.tx * CF_T + threadIdx.x, yp = t.ty * CF_T + threadIdx.y;
+    double va = 0.0, vb = 0.0;
+    if (xp < W && yp < H) {
+        const size_t i = base + (size_t)yp * W + xp;
+        const uint8_t f = flags[i];
+        if (f & F_U) {
+            const uint8_t* px = bgr + 3 * i;
+            const double I0 = colour(px, 0), I1 = colour(px, 1), I2 = colour(px, 2);
+            const int ky0 = max(yp - r, r), ky1 = min(yp + r, H - 1 - r), kx0 = max(xp - r, r), kx1 = min(xp + r, W - 1 - r);
+            double acc = 0.0;
+            for (int ky = ky0; ky <= ky1; ++ky)
+                for (int kx = kx0; kx <= kx1; ++kx) {
+                    const CfAB c = s_ab[(ky - y0) * S + (kx - x0)];
+                    acc += c.a0 * I0 + c.a1 * I1 + c.a2 * I2 + c.b;
+                }
+            const double cnt = (double)((ky1 - ky0 + 1) * (kx1 - kx0 + 1));
+            const double pi = p_value<SETUP>(f, d, i);
+            const double qi = cnt * pi - acc;
+            if constexpr (SETUP) {
+                // diag L = sum_k [1 - (1 + (I_i - mu_k)^T Delta_k^-1 (I_i - mu_k)) / n]
+                const double n = (double)(2 * r + 1) * (double)(2 * r + 1);
+                double quad = 0.0;
+                for (int ky = ky0; ky <= ky1; ++ky)
+                    for (int kx = kx0; kx <= kx1; ++kx) {
+                        const CfStats st = stats[base + (size_t)ky * W + kx];
+                        const double e0 = I0 - st.mu[0], e1 = I1 - st.mu[1], e2 = I2 - st.mu[2];
+                        quad += e0 * (st.d00 * e0 + st.d01 * e1 + st.d02 * e2) + e1 * (st.d01 * e0 + st.d11 * e1 + st.d12 * e2) +
+                                e2 * (st.d02 * e0 + st.d12 * e1 + st.d22 * e2);
+                    }
+                const double dg = cnt * (1.0 - 1.0 / n) - quad / n;
+                const double ri = -qi;
+                diag[i] = dg;
+                res[i] = ri;
+                x[i] = pi;
+                va = ri * (ri / dg);
+                vb = ri * ri;
+            } else {
+                q[i] = qi;
+                va = d[i] * qi;
+            }
+        }
+    }
+    const double sa = block_sum(va, s_red, tid);
+    if (tid == 0) part_a[blockIdx.x] = sa;
+    if constexpr (SETUP) {
+        __syncthreads();
+        const double sb = block_sum(vb, s_red, tid);
+        if (tid == 0) part_b[blockIdx.x] = sb;
+    }
+}
+
+// one wave per image: the sum of part over the image's run of the tile list, lane 0's fixed order
+__device__ __forceinline__ double image_sum(const double* __restrict__ part, int lo, int hi) {
+    const int lane = threadIdx.x;
+    double v = 0.0;
+    for (int k = lo + lane; k < hi; k += WAVE) v += part[k];
+    for (int o = 1; o < WAVE; o <<= 1) v += __shfl_down(v, o, WAVE);
+    return __shfl(v, 0, WAVE);
+}
+
+// MODE 0 (after setup): rz, rr0, the trivial images; MODE 1: alpha = rz / d.q; MODE 2: convergence and beta.
+// grid B, one wave
+template <int MODE>
+__global__ void __launch_bounds__(WAVE) k_cf_scalar(int max_iter, double tol, CfImage* __restrict__ img,
+                                                    const double* __restrict__ part_a, const double* __restrict__ part_b,
+                                                    int* __restrict__ n_done) {
+    CfImage& s = img[blockIdx.x];
+    if (s.done) return;
+    const double a = image_sum(part_a, s.tile_lo, s.tile_hi);
+    const double b = MODE == 1 ? 0.0 : image_sum(part_b, s.tile_lo, s.tile_hi);
+    if (threadIdx.x != 0) return;
+    if (MODE == 0) {
+        s.rz = a;
+        s.rr0 = b;
+        s.rel = 0.0;
+        s.iters = 0;
+        if (!(b > 0.0)) { s.done = 1; atomicAdd(n_done, 1); }    // (L m)_U = 0: m already solves the system
+    } else if (MODE == 1) {
+        if (a > 0.0 && std::isfinite(a)) {
+            s.alpha = s.rz / a;
+        } else {                                                 // d = 0 or a breakdown: nothing left to do
+            s.alpha = 0.0;
+            s.done = 1;
+            atomicAdd(n_done, 1);
+        }
+    } else {
+        s.iters += 1;
+        s.rel = sqrt(b / s.rr0);
+        s.beta = a / s.rz;
+        s.rz = a;
+        if (s.rel <= tol || s.iters >= max_iter) { s.done = 1; atomicAdd(n_done, 1); }
+    }
+}
+
+// x += alpha d, r -= alpha q on U; per-tile r . z (part_a), r . r (part_b)
+__global__ void __launch_bounds__(CF_THREADS) k_cf_update(int H, int W, int ntx, const int2* __restrict__ tiles,
+                                                          const CfImage* __restrict__ img, const uint8_t* __restrict__ flags,
+                                                          const double* __restrict__ d, const double* __restrict__ q,
+                                                          const double* __restrict__ diag, double* __restrict__ x,
+                                                          double* __restrict__ res, double* __restrict__ part_a,
+                                                          double* __restrict__ part_b) {
+    __shared__ double s_red[CF_THREADS];
+    const TileRef t = tile_of(tiles, ntx);
+    const CfImage& s = img[t.b];
+    if (s.done) return;
+    const int tid = threadIdx.y * CF_T + threadIdx.x;
+    const int xp = t.tx * CF_T + threadIdx.x, yp = t.ty * CF_T + threadIdx.y;
+    double va = 0.0, vb = 0.0;
+    if (xp < W && yp < H) {
+        const size_t i = (size_t)t.b * H * W + (size_t)yp * W + xp;
+        if (flags[i] & F_U) {
+            const double al = s.alpha;
+            x[i] += al * d[i];
+            const double ri = res[i] - al * q[i];
+            res[i] = ri;
+            va = ri * (ri / diag[i]);
+            vb = ri * ri;
+        }
+    }
+    const double sa = block_sum(va, s_red, tid);
+    if (tid == 0) part_a[blockIdx.x] = sa;
+    __syncthreads();
+    const double sb = block_sum(vb, s_red, tid);
+    if (tid == 0) part_b[blockIdx.x] = sb;
+}
+
+// d = z + beta d on U (SETUP: d = z)
+template <bool SETUP>
+__global__ void __launch_bounds__(CF_THREADS) k_cf_direction(int H, int W, int ntx, const int2* __restrict__ tiles,
+                                                             const CfImage* __restrict__ img, const uint8_t* __restrict__ flags,
+                                                             const double* __restrict__ res, const double* __restrict__ diag,
+                                                             double* __restrict__ d) {
+    const TileRef t = tile_of(tiles, ntx);
+    const CfImage& s = img[t.b];
+    if (s.done) return;
+    const int xp = t.tx * CF_T + threadIdx.x, yp = t.ty * CF_T + threadIdx.y;
+    if (xp >= W || yp >= H) return;
+    const size_t i = (size_t)t.b * H * W + (size_t)yp * W + xp;
+    if (!(flags[i] & F_U)) return;
+    const double z = res[i] / diag[i];
+    d[i] = SETUP ? z : z + s.beta * d[i];
+}
+
+// the outputs over the whole frame: alpha = x on U of a solved image, m elsewhere.  grid (cdiv(H*W, 256), B)
+__global__ void __launch_bounds__(CF_THREADS) k_cf_output(int H, int W, const CfImage* __restrict__ img,
+                                                          const uint8_t* __restrict__ bgr, const uint8_t* __restrict__ flags,
+                                                          const double* __restrict__ x, float* __restrict__ alpha,
+                                                          uint8_t* __restrict__ rgba, double* __restrict__ raw,
+                                                          int* __restrict__ iters, double* __restrict__ rel) {
+    const size_t P = (size_t)H * W;
+    const size_t j = (size_t)blockIdx.x * CF_THREADS + threadIdx.x;
+    const int b = blockIdx.y;
+    const CfImage& s = img[b];
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        if (iters) iters[b] = s.iters;
+        if (rel) rel[b] = s.rel;
+    }
+    if (j >= P) return;
+    const size_t i = (size_t)b * P + j;
+    const uint8_t f = flags[i];
+    const double a = (s.tile_hi > s.tile_lo && (f & F_U)) ? x[i] : ((f & F_M) ? 1.0 : 0.0);
+    if (raw) raw[i] = a;
+    const double c = a < 0.0 ? 0.0 : (a > 1.0 ? 1.0 : a);
+    if (alpha) alpha[i] = (float)c;
+    if (rgba) {
+        rgba[4 * i] = bgr[3 * i]; rgba[4 * i + 1] = bgr[3 * i + 1]; rgba[4 * i + 2] = bgr[3 * i + 2];
+        rgba[4 * i + 3] = (uint8_t)floor(c * 255.0 + 0.5);
+    }
+}
+
+} // namespace
+} // namespace ggc
+
+using namespace ggc;
+
+extern "C" int ggc_closed_form_matte(ggc_ctx* ctx, ggc_stream stream, int B, int H, int W, const uint8_t* bgr,
+                                     const uint8_t* binary, int radius, float eps, int band, int max_iter, float tol,
+                                     float* alpha, uint8_t* rgba, double* raw, int32_t* iters, double* rel_residual) {
+    if (!ctx) return GGC_E_INVALID_ARG;
+    GGC_REQUIRE(ctx, B >= 0 && B <= 65535 && H >= 1 && W >= 1 && H <= 32768 && W <= 32768, GGC_E_SHAPE,
+                "bad shape B=%d H=%d W=%d", B, H, W);
+    GGC_REQUIRE(ctx, alpha || rgba || raw || iters || rel_residual, GGC_E_INVALID_ARG, "null pointer: no output asked for");
+    GGC_REQUIRE(ctx, B == 0 || (bgr && binary), GGC_E_INVALID_ARG, "null pointer");
+    GGC_REQUIRE(ctx, radius >= 1 && radius <= CF_RMAX, GGC_E_INVALID_ARG, "closed-form radius %d outside 1..%d", radius, CF_RMAX);
+    GGC_REQUIRE(ctx, std::isfinite(eps) && eps >= 1e-12f && eps <= 1.0f, GGC_E_INVALID_ARG,
+                "closed-form eps %g outside [1e-12, 1]", (double)eps);
+    GGC_REQUIRE(ctx, band >= 0 && band <= 64, GGC_E_INVALID_ARG, "closed-form band %d outside 0..64", band);
+    GGC_REQUIRE(ctx, max_iter >= 1 && max_iter <= 100000, GGC_E_INVALID_ARG, "closed-form max_iter %d outside 1..100000",
+                max_iter);
+    GGC_REQUIRE(ctx, std::isfinite(tol) && tol >= 1e-12f && tol < 1.0f, GGC_E_INVALID_ARG,
+                "closed-form tol %g outside [1e-12, 1)", (double)tol);
+    GGC_REQUIRE(ctx, H >= 2 * radius + 1 && W >= 2 * radius + 1, GGC_E_SHAPE,
+                "closed-form matte needs H, W >= 2r+1 = %d, got %dx%d", 2 * radius + 1, H, W);
+    if (B == 0) return GGC_OK;
+    GGC_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const size_t P = (size_t)B * H * W;
+    const int ntx = cdiv(W, CF_T), nty = cdiv(H, CF_T), nt = ntx * nty;
+    uint8_t *flags = nullptr, *edge = nullptr, *hdil = nullptr;
+    int32_t* tile_u = nullptr;
+    CfImage* img = nullptr;
+    int* n_done = nullptr;
+    CfStats* stats = nullptr;
+    CfAB* ab = nullptr;
+    double *x = nullptr, *res = nullptr, *d = nullptr, *q = nullptr, *diag = nullptr;
+    int2* tiles = nullptr;
+    double *part_a = nullptr, *part_b = nullptr;
+    // the per-pixel arrays (147 bytes per pixel) and the per-tile, per-image ones, sized for every tile of the batch
+    const size_t n_tiles_max = (size_t)B * nt;
+    if (!carve_scratch(ctx, S_CFMATTE, [&](Carve& c) {
+            flags = c.take<uint8_t>(P); edge = c.take<uint8_t>(P); hdil = c.take<uint8_t>(P);
+            stats = c.take<CfStats>(P); ab = c.take<CfAB>(P);
+            x = c.take<double>(P); res = c.take<double>(P); d = c.take<double>(P); q = c.take<double>(P);
+            diag = c.take<double>(P);
+            tile_u = c.take<int32_t>(n_tiles_max); tiles = c.take<int2>(n_tiles_max);
+            part_a = c.take<double>(n_tiles_max); part_b = c.take<double>(n_tiles_max);
+            img = c.take<CfImage>(B); n_done = c.take<int>(1);
+        }))
+        return GGC_E_OOM;
+    ProfScope prof(ctx, st, "closed_form_matte");
+    const dim3 fgrid(ntx, nty, B), tblk(CF_T, CF_T);
+    hipLaunchKernelGGL(k_cf_edge, fgrid, tblk, 0, st, H, W, binary, edge);
+    hipLaunchKernelGGL(k_cf_dilate_h, fgrid, tblk, 0, st, H, W, band, edge, hdil);
+    hipLaunchKernelGGL(k_cf_dilate_v, fgrid, tblk, 0, st, H, W, band, hdil, binary, flags, tile_u);
+    GGC_LAUNCH_CHECK(ctx);
+
+    // the tile list, image by image: tiles with U and their eight neighbours (r <= 16 = the tile side).  An image whose
+    // band is empty or covers every pixel gets no tiles: alpha = m, 0 iterations.
+    std::vector<int32_t> cnt(n_tiles_max);
+    GGC_HIP(ctx, hipMemcpyAsync(cnt.data(), tile_u, n_tiles_max * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    GGC_HIP(ctx, hipStreamSynchronize(st));
+    std::vector<int2> list;
+    std::vector<CfImage> host_img(B);
+    int n_solve = 0;
+    for (int b = 0; b < B; ++b) {
+        const int32_t* c = cnt.data() + (size_t)b * nt;
+        int64_t u = 0;
+        for (int k = 0; k < nt; ++k) u += c[k];
+        CfImage& s = host_img[b];
+        s = CfImage{0.0, 0.0, 0.0, 0.0, 0.0, 0, 1, (int)list.size(), (int)list.size()};
+        if (u == 0 || u == (int64_t)H * W) continue;
+        for (int ty = 0; ty < nty; ++ty)
+            for (int tx = 0; tx < ntx; ++tx) {
+                bool near = false;
+                for (int dy = -1; dy <= 1 && !near; ++dy)
+                    for (int dx = -1; dx <= 1 && !near; ++dx) {
+                        const int yy = ty + dy, xx = tx + dx;
+                        near = yy >= 0 && yy < nty && xx >= 0 && xx < ntx && c[yy * ntx + xx] > 0;
+                    }
+                if (near) list.push_back(make_int2(b, ty * ntx + tx));
+            }
+        s.tile_hi = (int)list.size();
+        s.done = 0;
+        ++n_solve;
+    }
+    const int n_list = (int)list.size();
+    if (n_list > 0) GGC_HIP(ctx, hipMemcpyAsync(tiles, list.data(), list.size() * sizeof(int2), hipMemcpyHostToDevice, st));
+    GGC_HIP(ctx, hipMemcpyAsync(img, host_img.data(), B * sizeof(CfImage), hipMemcpyHostToDevice, st));
+    GGC_HIP(ctx, hipMemsetAsync(n_done, 0, sizeof(int), st));
+    GGC_HIP(ctx, hipStreamSynchronize(st));            // the host vectors go out of scope below
+
+    if (n_list > 0) {
+        const double e = (double)eps, tl = (double)tol;
+        hipLaunchKernelGGL(k_cf_stats, dim3(n_list), tblk, 0, st, H, W, radius, e, ntx, tiles, bgr, stats);
+        hipLaunchKernelGGL(k_cf_window<true>, dim3(n_list), tblk, 0, st, H, W, radius, ntx, tiles, img, bgr, flags, stats,
+                           d, ab);
+        hipLaunchKernelGGL(k_cf_pixel<true>, dim3(n_list), tblk, 0, st, H, W, radius, ntx, tiles, img, bgr, flags, stats, ab,
+                           d, q, res, x, diag, part_a, part_b);
+        hipLaunchKernelGGL(k_cf_scalar<0>, dim3(B), dim3(WAVE), 0, st, max_iter, tl, img, part_a, part_b, n_done);
+        hipLaunchKernelGGL(k_cf_direction<true>, dim3(n_list), tblk, 0, st, H, W, ntx, tiles, img, flags, res, diag, d);
+        GGC_LAUNCH_CHECK(ctx);
+        for (int it = 0; it < max_iter; ++it) {
+            hipLaunchKernelGGL(k_cf_window<false>, dim3(n_list), tblk, 0, st, H, W, radius, ntx, tiles, img, bgr, flags,
+                               stats, d, ab);
+            hipLaunchKernelGGL(k_cf_pixel<false>, dim3(n_list), tblk, 0, st, H, W, radius, ntx, tiles, img, bgr, flags,
+                               stats, ab, d, q, res, x, diag, part_a, part_b);
+            hipLaunchKernelGGL(k_cf_scalar<1>, dim3(B), dim3(WAVE), 0, st, max_iter, tl, img, part_a, part_b, n_done);
+            hipLaunchKernelGGL(k_cf_update, dim3(n_list), tblk, 0, st, H, W, ntx, tiles, img, flags, d, q, diag, x, res,
+                               part_a, part_b);
+            hipLaunchKernelGGL(k_cf_scalar<2>, dim3(B), dim3(WAVE), 0, st, max_iter, tl, img, part_a, part_b, n_done);
+            hipLaunchKernelGGL(k_cf_direction<false>, dim3(n_list), tblk, 0, st, H, W, ntx, tiles, img, flags, res, diag, d);
+            GGC_LAUNCH_CHECK(ctx);
+            if ((it + 1) % CF_POLL == 0 && it + 1 < max_iter) {
+                std::vector<int32_t> h;
+                if (int e2 = read_i32(ctx, st, n_done, 1, h)) return e2;
+                if (h[0] >= n_solve) break;
+            }
+        }
+    }
+    const dim3 ogrid(cdiv((int64_t)H * W, CF_THREADS), B);
+    hipLaunchKernelGGL(k_cf_output, ogrid, dim3(CF_THREADS), 0, st, H, W, img, bgr, flags, x, alpha, rgba, raw, iters,
+                       rel_residual);
+    GGC_LAUNCH_CHECK(ctx);
+    return GGC_OK;
+}

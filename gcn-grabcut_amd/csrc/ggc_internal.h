@@ -30,7 +30,7 @@ enum Slot : int {
     S_CC_A, S_CC_B, S_CC_C,
     S_MISC_A, S_MISC_B,
     S_CLICK,
-    S_MATTE, S_MATTE_MEAN,
+    S_MATTE, S_MATTE_MEAN, S_CFMATTE,
     S_COUNT
 };
 

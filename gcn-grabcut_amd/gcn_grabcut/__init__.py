@@ -20,8 +20,8 @@ from .model import (
     ResGCNNet, GCNTrimapNet, GATTrimapNet, build_model, _probs_to_trimap, probs_to_node_trimap, project_to_pixels,
     TRIMAP_BG, TRIMAP_FG, TRIMAP_PROB_BG, TRIMAP_PROB_FG, CLASS_BG, CLASS_UNK, CLASS_FG,
 )
-from .pipeline import (GCNGrabCutPipeline, FullResolution, SegmentationResult, alpha_matte, clean_mask, guided_filter,
-                       refine_trimap, upsample_mask)
+from .pipeline import (GCNGrabCutPipeline, ClosedFormMatte, FullResolution, SegmentationResult, alpha_matte,
+                       clean_mask, closed_form_matte, guided_filter, refine_trimap, upsample_mask)
 from .synthetic import synthetic_image, synthetic_batch
 from .losses import FocalLoss, LabelSmoothingCE, TrimapLoss
 from .trainer import Trainer, TrainConfig
@@ -34,7 +34,7 @@ __all__ = [
     "N_NODE_FEATS", "N_EDGE_FEATS", "N_PRIOR_FEATS",
     "evaluate", "evaluate_batch", "evaluate_trimap", "boundary_f1", "noc_summary", "SegmentationMetrics", "TrimapMetrics",
     "GCNGrabCutPipeline", "FullResolution", "SegmentationResult", "alpha_matte", "clean_mask", "guided_filter",
-    "refine_trimap", "upsample_mask",
+    "refine_trimap", "upsample_mask", "ClosedFormMatte", "closed_form_matte",
     "ResGCNNet", "GCNTrimapNet", "GATTrimapNet", "build_model", "probs_to_node_trimap", "project_to_pixels",
     "Data", "Batch", "synthetic_image", "synthetic_batch",
     "FocalLoss", "LabelSmoothingCE", "TrimapLoss", "Trainer", "TrainConfig",

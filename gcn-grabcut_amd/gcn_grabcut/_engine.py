@@ -309,6 +309,28 @@ class Engine:
                       _native.ptr(rgba))
         return alpha, mask, rgba
 
+    def closed_form_matte(self, bgr, binary, radius, eps, band, max_iter, tol, want_rgba=False, out=None):
+        """Closed-form alpha matte of binary (B,H,W) uint8 (nonzero = foreground) under bgr (B,H,W,3) uint8
+        (ggc_closed_form_matte): the matting Laplacian solved on the band of `band` pixels around the mask's edge.
+        -> (alpha (B,H,W) float32 in [0,1], iters (B,) int32, rel_residual (B,) float64), with want_rgba also rgba
+        (B,H,W,4) uint8 after alpha; out: (alpha, rgba or None), preallocated.  The call synchronises its stream."""
+        check_closed_form_args(radius, eps, band, max_iter, tol)
+        b, h, w, _ = bgr.shape
+        if tuple(binary.shape) != (b, h, w):
+            raise ValueError(f"closed_form_matte: binary {tuple(binary.shape)} does not match bgr {tuple(bgr.shape)}")
+        check_closed_form_shape(h, w, radius)
+        if out is not None:
+            alpha, rgba = out
+        else:
+            alpha = self.empty(b, h, w)
+            rgba = self.empty(b, h, w, 4, dtype=torch.uint8) if want_rgba else None
+        iters = self.empty(b, dtype=torch.int32)
+        rel = self.empty(b, dtype=torch.float64)
+        self.ctx.call("ggc_closed_form_matte", self._stream(), b, h, w, bgr.data_ptr(), binary.data_ptr(), int(radius),
+                      float(eps), int(band), int(max_iter), float(tol), _native.ptr(alpha), _native.ptr(rgba), None,
+                      iters.data_ptr(), rel.data_ptr())
+        return (alpha, rgba, iters, rel) if want_rgba else (alpha, iters, rel)
+
     def iou(self, pred, gt):
         """-> (iou (B,) float64, counts (B,3) int64 = tp, fp, fn), on device."""
         b, h, w = pred.shape
@@ -329,6 +351,33 @@ def check_matte_args(radius, eps) -> None:
         raise ValueError(f"matte radius must be an integer in 1..{MATTE_RADIUS_MAX}, got {radius}")
     if not (np.isfinite(eps) and float(eps) >= MATTE_EPS_MIN):
         raise ValueError(f"matte eps must be finite and >= {MATTE_EPS_MIN:g}, got {eps}")
+
+
+CF_RADIUS_MAX = 8
+CF_BAND_MAX = 64
+CF_MAX_ITER_MAX = 100000
+
+
+def check_closed_form_args(radius, eps, band, max_iter, tol) -> None:
+    """The argument range of ggc_closed_form_matte, checked on the host so that a bad value is a ValueError."""
+    if int(radius) != radius or not 1 <= int(radius) <= CF_RADIUS_MAX:
+        raise ValueError(f"closed-form radius must be an integer in 1..{CF_RADIUS_MAX}, got {radius}")
+    if not (np.isfinite(eps) and 1e-12 <= float(eps) <= 1.0):
+        raise ValueError(f"closed-form eps must be in [1e-12, 1], got {eps}")
+    if int(band) != band or not 0 <= int(band) <= CF_BAND_MAX:
+        raise ValueError(f"closed-form band must be an integer in 0..{CF_BAND_MAX}, got {band}")
+    if int(max_iter) != max_iter or not 1 <= int(max_iter) <= CF_MAX_ITER_MAX:
+        raise ValueError(f"closed-form max_iter must be an integer in 1..{CF_MAX_ITER_MAX}, got {max_iter}")
+    if not (np.isfinite(tol) and 1e-12 <= float(tol) < 1.0):
+        raise ValueError(f"closed-form tol must be in [1e-12, 1), got {tol}")
+
+
+def check_closed_form_shape(h, w, radius) -> None:
+    """Every window of the closed-form matte lies inside the image: H, W >= 2 radius + 1."""
+    if h < 2 * int(radius) + 1 or w < 2 * int(radius) + 1:
+        raise ValueError(f"closed-form matte needs H, W >= 2r+1 = {2 * int(radius) + 1}, got {h}x{w}")
+    if h > UPSAMPLE_SIDE_MAX or w > UPSAMPLE_SIDE_MAX:
+        raise ValueError(f"closed-form matte takes images of at most {UPSAMPLE_SIDE_MAX} on a side, got {h}x{w}")
 
 
 UPSAMPLE_SIDE_MAX = 32768

@@ -127,6 +127,57 @@ def alpha_matte(image: np.ndarray, mask: np.ndarray, radius: int = MATTE_RADIUS,
     return eng.alpha_matte(bgr, binary, radius, eps)[0].cpu().numpy()
 
 
+CF_RADIUS = 1
+CF_EPS = 1e-5
+CF_BAND = 1
+CF_MAX_ITER = 500
+CF_TOL = 1e-4
+
+
+@dataclass(frozen=True)
+class ClosedFormMatte:
+    """matte=ClosedFormMatte(...) asks segment / segment_batch / segment_batch_device / segment_bbox for the closed-form
+    matte (closed_form_matte) of the cleaned mask instead of the guided one (matte=True).  The defaults are a recorded
+    choice from a float64 CPU study (tools/closed_form_study.py), not a tuned result."""
+    radius: int = CF_RADIUS
+    eps: float = CF_EPS
+    band: int = CF_BAND
+    max_iter: int = CF_MAX_ITER
+    tol: float = CF_TOL
+
+    def args(self) -> "tuple[int, float, int, int, float]":
+        return int(self.radius), float(self.eps), int(self.band), int(self.max_iter), float(self.tol)
+
+
+def closed_form_matte(image: np.ndarray, mask: np.ndarray, radius: int = CF_RADIUS, eps: float = CF_EPS,
+                      band: int = CF_BAND, max_iter: int = CF_MAX_ITER, tol: float = CF_TOL, return_info: bool = False,
+                      device="cuda"):
+    """Closed-form alpha matte of a binary mask (additive): Levin, Lischinski and Weiss's matting Laplacian (colour-line
+    model, windows of (2 radius + 1)^2 pixels wholly inside the image, regulariser eps / n) minimised over the pixels
+    within `band` of the mask's edge, every other pixel held at the mask's value (ggc_closed_form_matte).  Solved by
+    Jacobi-preconditioned conjugate gradients on the device until the residual falls to tol times its start, or for
+    max_iter iterations.  Unlike alpha_matte it can give fractional alpha that the mask got wrong (thin strands).
+
+    image: (H, W, 3) uint8 BGR; mask: (H, W) with values in {0, 1}.  radius in 1..8 with H, W >= 2 radius + 1,
+    1e-12 <= eps <= 1, band in 0..64, max_iter in 1..100000, 1e-12 <= tol < 1.  The defaults are a recorded choice
+    (DESIGN.md §5.13), not a tuned result.
+    -> (H, W) float32 in [0, 1]; with return_info, (alpha, iterations, relative residual)."""
+    from ._engine import get_engine, check_closed_form_args, check_closed_form_shape
+    image = _check_image(image)
+    m = np.asarray(mask)
+    if m.shape != image.shape[:2]:
+        raise ValueError(f"closed_form_matte: mask {m.shape} does not match image {image.shape[:2]}")
+    if m.size and not np.isin(m, (0, 1)).all():
+        raise ValueError("closed_form_matte: mask values must be 0 or 1")
+    check_closed_form_args(radius, eps, band, max_iter, tol)
+    check_closed_form_shape(*image.shape[:2], radius)
+    eng = get_engine(device)
+    alpha, iters, rel = eng.closed_form_matte(eng.to_device(image[None]), eng.to_device(np.ascontiguousarray(m, np.uint8)[None]),
+                                              radius, eps, band, max_iter, tol)
+    a = alpha[0].cpu().numpy()
+    return (a, int(iters[0].item()), float(rel[0].item())) if return_info else a
+
+
 def upsample_mask(image: np.ndarray, mask: np.ndarray, full_image: np.ndarray, radius: int = MATTE_RADIUS,
                   eps: float = MATTE_EPS, device="cuda") -> "tuple[np.ndarray, np.ndarray]":
     """A mask found on a reduced image, carried to the full-resolution image (additive): He and Sun's fast guided filter.
@@ -313,6 +364,28 @@ def _full_result(full: dict, i: int) -> FullResolution:
                           alpha=host.get("alpha"), rgba_soft=host.get("rgba_soft"))
 
 
+def _closed_form_args(matte, h: int, w: int, full: bool) -> "Optional[tuple[int, float, int, int, float]]":
+    """The closed-form matte's arguments when matte is a ClosedFormMatte (checked here, before any stage runs, with the
+    working size h x w, and refused together with full-resolution outputs), else None."""
+    if not isinstance(matte, ClosedFormMatte):
+        return None
+    from ._engine import check_closed_form_args, check_closed_form_shape
+    if full:
+        raise ValueError("the closed-form matte is not carried to full resolution: use matte=True with full_image(s)")
+    args = matte.args()
+    check_closed_form_args(*args)
+    check_closed_form_shape(h, w, args[0])
+    return args
+
+
+def _soft_matte(leng, img, cleaned, mat, cfm, alpha, rgba_soft) -> None:
+    """alpha and rgba_soft of the cleaned masks: the guided matte (mat) or the closed-form one (cfm)."""
+    if mat:
+        leng.alpha_matte(img, cleaned, *mat, want_rgba=True, out=(alpha, rgba_soft))
+    elif cfm:
+        leng.closed_form_matte(img, cleaned, *cfm, out=(alpha, rgba_soft))
+
+
 def _matte_args(matte: bool, radius, eps) -> "Optional[tuple[int, float]]":
     """(radius, eps) when the matte is wanted (checked here, before any stage runs), else None."""
     if not matte:
@@ -476,7 +549,8 @@ class GCNGrabCutPipeline:
 
         matte=True (additive) also returns "alpha" (B,H,W) float32, the soft matte of the cleaned mask (alpha_matte with
         matte_radius / matte_eps), and "rgba_soft" (B,H,W,4) uint8, the cut-out with that alpha.  Every other output is
-        the same as without it.
+        the same as without it.  matte=ClosedFormMatte(...) fills the same two outputs with closed_form_matte of the
+        cleaned mask instead (matte_radius / matte_eps do not apply); it cannot be combined with full_bgr.
 
         full_bgr (additive): a (B,H1,W1,3) uint8 tensor on the device, the same images at a resolution of at least the
         working one.  The result then also has "full", a dict of device tensors at (H1, W1): "binary_mask", the cleaned
@@ -509,14 +583,15 @@ class GCNGrabCutPipeline:
         want = self.grabcut_lanes if grabcut_lanes is None else int(grabcut_lanes)   # (an argument, so that concurrent callers do not mutate the pipeline)
         n_chunks = self.chunks if chunks is None else int(chunks)
         hints = _Hints.of(hints, b, hint_radius, hint_region, hints_as_prior)
-        mat = _matte_args(matte, matte_radius, matte_eps)
+        cfm = _closed_form_args(matte, bgr.shape[1], bgr.shape[2], full_bgr is not None)
+        mat = None if cfm else _matte_args(matte, matte_radius, matte_eps)
         fmat = _full_args(full_bgr, bgr.shape, matte_radius, matte_eps)
         if n_chunks <= 0:                          # 0: one chunk per GrabCut lane once every chunk gets a lane's worth of images
             n_chunks = max(want, 1) if b >= 16 * max(want, 1) else 1
         if n_chunks > 1 and b >= 2 * n_chunks:
             return self._segment_pipelined(bgr, self.chunk_plan(b, n_chunks, self.chunk_ratio), cs, threshold_fg, threshold_bg,
                                            refine_iters, min_area_ratio, keep_largest, edge_aware, filter_radius, compose, timing,
-                                           hints, return_state, mat, full_bgr, fmat)
+                                           hints, return_state, mat, full_bgr, fmat, cfm)
 
         def tick():
             if timing is not None:
@@ -535,16 +610,16 @@ class GCNGrabCutPipeline:
         cleaned = eng.empty(*bgr.shape[:3], dtype=torch.uint8)
         overlay = eng.empty(*bgr.shape[:3], 3, dtype=torch.uint8) if compose else None
         rgba = eng.empty(*bgr.shape[:3], 4, dtype=torch.uint8) if compose else None
-        alpha = eng.empty(*bgr.shape[:3]) if mat else None
-        rgba_soft = eng.empty(*bgr.shape[:3], 4, dtype=torch.uint8) if mat else None
+        alpha = eng.empty(*bgr.shape[:3]) if (mat or cfm) else None
+        rgba_soft = eng.empty(*bgr.shape[:3], 4, dtype=torch.uint8) if (mat or cfm) else None
         full = _full_buffers(eng, full_bgr, compose, mat)
 
         def post(leng, lo, hi, binary_part):
             leng.clean_mask(binary_part, min_area_ratio, keep_largest, out=cleaned[lo:hi])
             if compose:
                 leng.compose(bgr[lo:hi], cleaned[lo:hi], out=(overlay[lo:hi], rgba[lo:hi]))
-            if mat:
-                leng.alpha_matte(bgr[lo:hi], cleaned[lo:hi], *mat, want_rgba=True, out=(alpha[lo:hi], rgba_soft[lo:hi]))
+            if mat or cfm:
+                _soft_matte(leng, bgr[lo:hi], cleaned[lo:hi], mat, cfm, alpha[lo:hi], rgba_soft[lo:hi])
             if full is not None:
                 _full_post(leng, lo, hi, bgr, cleaned, full_bgr, full, fmat)
 
@@ -566,7 +641,7 @@ class GCNGrabCutPipeline:
             out.update(gc_binary=binary, bgd=bgd, fgd=fgd, gc_image=gc_img)
         if compose:
             out["overlay"], out["rgba"] = overlay, rgba
-        if mat:
+        if mat or cfm:
             out["alpha"], out["rgba_soft"] = alpha, rgba_soft
         if full is not None:
             out["full"] = full
@@ -576,7 +651,7 @@ class GCNGrabCutPipeline:
 
     def _segment_pipelined(self, bgr, plan, cs, threshold_fg, threshold_bg, refine_iters, min_area_ratio, keep_largest,
                            edge_aware, filter_radius, compose, timing, hints=None, return_state=False, mat=None,
-                           full_bgr=None, fmat=None) -> dict:
+                           full_bgr=None, fmat=None, cfm=None) -> dict:
         """The software pipeline behind segment_batch_device: chunk k's GrabCut lane starts as soon as chunk k's trimaps are
         on the device; the caller's stream goes on with chunk k+1's SLIC / graph / network / trimap."""
         import torch
@@ -598,8 +673,8 @@ class GCNGrabCutPipeline:
         cleaned = eng.empty(b, h, w, dtype=torch.uint8)
         overlay = eng.empty(b, h, w, 3, dtype=torch.uint8) if compose else None
         rgba = eng.empty(b, h, w, 4, dtype=torch.uint8) if compose else None
-        alpha = eng.empty(b, h, w) if mat else None
-        rgba_soft = eng.empty(b, h, w, 4, dtype=torch.uint8) if mat else None
+        alpha = eng.empty(b, h, w) if (mat or cfm) else None
+        rgba_soft = eng.empty(b, h, w, 4, dtype=torch.uint8) if (mat or cfm) else None
         full = _full_buffers(eng, full_bgr, compose, mat)
         if return_state:
             st_binary = eng.empty(b, h, w, dtype=torch.uint8)
@@ -634,8 +709,8 @@ class GCNGrabCutPipeline:
                 leng.clean_mask(binary, min_area_ratio, keep_largest, out=cleaned[lo:hi])
                 if compose:
                     leng.compose(img, cleaned[lo:hi], out=(overlay[lo:hi], rgba[lo:hi]))
-                if mat:
-                    leng.alpha_matte(img, cleaned[lo:hi], *mat, want_rgba=True, out=(alpha[lo:hi], rgba_soft[lo:hi]))
+                if mat or cfm:
+                    _soft_matte(leng, img, cleaned[lo:hi], mat, cfm, alpha[lo:hi], rgba_soft[lo:hi])
                 if full is not None:
                     _full_post(leng, lo, hi, bgr, cleaned, full_bgr, full, fmat)
                 if ev is not None:
@@ -670,7 +745,7 @@ class GCNGrabCutPipeline:
             out.update(gc_binary=st_binary, bgd=st_bgd, fgd=st_fgd, gc_image=st_image)
         if compose:
             out["overlay"], out["rgba"] = overlay, rgba
-        if mat:
+        if mat or cfm:
             out["alpha"], out["rgba_soft"] = alpha, rgba_soft
         if full is not None:
             out["full"] = full
@@ -693,6 +768,7 @@ class GCNGrabCutPipeline:
             return []
         if any(im.shape != imgs[0].shape for im in imgs):
             raise ValueError("segment_batch needs images of one size; group them by shape")
+        _closed_form_args(kwargs.get("matte"), *imgs[0].shape[:2], full_images is not None)
         full_bgr = None
         if full_images is not None:
             fulls = [_check_image(im) for im in full_images]
@@ -826,9 +902,11 @@ class GCNGrabCutPipeline:
 
         Additive: fg_points / bg_points are user clicks, (row, col) pairs, applied as hard constraints on the trimap
         GrabCut starts from (see segment_batch_device for hint_radius, hint_region and hints_as_prior); matte=True also
-        fills the result's alpha and rgba_soft (segment_batch_device); full_image, the same image at a larger size, fills
+        fills the result's alpha and rgba_soft (segment_batch_device), matte=ClosedFormMatte(...) with the closed-form
+        matte; full_image, the same image at a larger size, fills
         the result's `full` (segment_batch_device's full_bgr)."""
         image = _check_image(image)
+        _closed_form_args(matte, *image.shape[:2], full_image is not None)
         full_bgr = None if full_image is None else self._eng.to_device(_check_image(full_image)[None])
         timing: dict[str, float] = {}
         hints = None if fg_points is None and bg_points is None else \
@@ -850,10 +928,12 @@ class GCNGrabCutPipeline:
                      matte_radius: int = MATTE_RADIUS, matte_eps: float = MATTE_EPS,
                      full_image: Optional[np.ndarray] = None) -> SegmentationResult:
         """Classical GrabCut with a bounding box (reference pipeline.py:354-380).  Additive: matte=True also fills the
-        result's alpha and rgba_soft, the soft matte of the returned mask (alpha_matte); full_image, the same image at a
+        result's alpha and rgba_soft, the soft matte of the returned mask (alpha_matte; closed_form_matte with
+        matte=ClosedFormMatte(...)); full_image, the same image at a
         larger size, fills the result's `full` from the returned mask (upsample_mask, then the overlay and cut-out)."""
         image = _check_image(image)
-        mat = _matte_args(matte, matte_radius, matte_eps)
+        cfm = _closed_form_args(matte, *image.shape[:2], full_image is not None)
+        mat = None if cfm else _matte_args(matte, matte_radius, matte_eps)
         full_img = None
         if full_image is not None:
             full_img = _check_image(full_image)
@@ -872,6 +952,12 @@ class GCNGrabCutPipeline:
             eng = self._eng
             alpha, rgba_soft = eng.alpha_matte(eng.to_device(image[None]), eng.to_device(binary_mask[None]), *mat,
                                                want_rgba=True)
+            alpha, rgba_soft = alpha[0].cpu().numpy(), rgba_soft[0].cpu().numpy()
+        elif cfm:
+            eng = self._eng
+            alpha, rgba_soft, _, _ = eng.closed_form_matte(eng.to_device(image[None]),
+                                                           eng.to_device(np.ascontiguousarray(binary_mask, np.uint8)[None]),
+                                                           *cfm, want_rgba=True)
             alpha, rgba_soft = alpha[0].cpu().numpy(), rgba_soft[0].cpu().numpy()
         full = None
         if full_img is not None:

@@ -50,7 +50,8 @@
 extern "C" {
 #endif
 
-#define GGC_VERSION 370 /* 0.3.7: ggc_upsample_matte (the matte's mask and alpha at a larger resolution: fast guided filter);
+#define GGC_VERSION 380 /* 0.3.8: ggc_closed_form_matte (closed-form alpha matte: matting Laplacian solved by PCG on the device);
+                           0.3.7: ggc_upsample_matte (the matte's mask and alpha at a larger resolution: fast guided filter);
                            0.3.6: ggc_alpha_matte (soft alpha matte of a binary mask: colour guided-filter feathering);
                            0.3.5: ggc_grid_maxflow (the GrabCut max-flow on a caller's network, a test hook);
                            0.3.4: ggc_next_click (the next simulated click of the NoC protocol);
@@ -454,6 +455,36 @@ int ggc_alpha_matte(ggc_ctx* ctx, ggc_stream stream, int B, int H, int W, const 
 int ggc_upsample_matte(ggc_ctx* ctx, ggc_stream stream, int B, int H, int W, const uint8_t* bgr, const uint8_t* binary,
                        int H1, int W1, const uint8_t* bgr_full, int radius, float eps,
                        float* alpha_full, uint8_t* binary_full, uint8_t* rgba_full);
+
+/* O3 — closed-form alpha matte of a binary mask (additive; Levin, Lischinski and Weiss, TPAMI 2008, with He, Sun and
+ * Tang's matrix-free L p, CVPR 2010).  Per image, with I_i = bgr_i / 255 and m = (binary != 0):
+ *   windows   K = {k : r <= y_k < H-r, r <= x_k < W-r} (only windows wholly inside the image: L stays symmetric), w_k the
+ *             (2r+1)^2 window at k, n = (2r+1)^2; mu_k the window mean of I, Sigma_k its population covariance,
+ *             Delta_k = Sigma_k + (eps / n) U (Levin's convention)
+ *   L         = sum_{k in K} L_k, (L_k)_ij = delta_ij - (1/n) (1 + (I_i - mu_k)^T Delta_k^-1 (I_j - mu_k)), i, j in w_k;
+ *             L 1 = 0, and with eps > 0 its null space is the constants
+ *   L p       a_k = Delta_k^-1 (mean_k(I p) - mu_k mean_k(p)), b_k = mean_k(p) - a_k^T mu_k,
+ *             (L p)_i = c_i p_i - sum_{k in K, i in w_k} (a_k^T I_i + b_k), c_i = #{k in K : i in w_k}
+ *   U         the pixels within Chebyshev distance `band` of a pixel whose 3x3 neighbourhood (clipped to the image) holds
+ *             both mask values; every other pixel is known, alpha = m
+ *   solve     L_UU alpha_U = -L_{U,known} m_known by Jacobi-preconditioned CG (preconditioner diag L on U) from alpha = m;
+ *             an image stops when ||r_j||_2 <= tol ||r_0||_2 (unpreconditioned residual, r_0 = -(L m)_U) or after
+ *             max_iter iterations.  An image whose U is empty or covers every pixel gets alpha = m and 0 iterations.
+ *   bgr [dev] u8 [B,H,W,3]   binary [dev] u8 [B,H,W] (any nonzero byte is 1)
+ *   1 <= radius <= 8, 1e-12 <= eps <= 1, 0 <= band <= 64, 1 <= max_iter <= 100000, 1e-12 <= tol < 1 (else
+ *   GGC_E_INVALID_ARG); H, W >= 2 radius + 1, H, W <= 32768, B <= 65535 (else GGC_E_SHAPE); B == 0 does nothing
+ *   alpha [dev] f32 [B,H,W] = clamp(alpha, 0, 1)     rgba [dev] u8 [B,H,W,4] = bgr, floor(255 clamp(alpha) + 0.5)
+ *   raw [dev] f64 [B,H,W] = alpha unclamped         iters [dev] i32 [B]     rel_residual [dev] f64 [B] = ||r_j|| / ||r_0||
+ *   (each may be NULL, not all of them; rel_residual is 0 for an image with 0 iterations)
+ * mu_k and Sigma_k come from exact integer window sums, Delta_k^-1 from the adjugate in float64; the CG vectors and dot
+ * products are float64.  Every per-image reduction runs in one fixed order over that image's tiles, so every image's
+ * outputs equal its single-image call bit for bit; no float atomics.  Work is restricted to the 16 x 16 tiles that hold U
+ * and their neighbours, listed once per call.  The entry SYNCHRONISES its stream: once to build that list on the host,
+ * and every 8 iterations to read the count of converged images (an integer atomic) and stop when all are done.
+ * Scratch: 147 bytes per pixel plus 28 bytes per 16 x 16 tile and 56 bytes per image, from the context. */
+int ggc_closed_form_matte(ggc_ctx* ctx, ggc_stream stream, int B, int H, int W, const uint8_t* bgr, const uint8_t* binary,
+                          int radius, float eps, int band, int max_iter, float tol,
+                          float* alpha, uint8_t* rgba, double* raw, int32_t* iters, double* rel_residual);
 
 /* R0 — IoU = tp / (tp + fp + fn + 1e-8) per image (metrics.py:79-84).
  *   iou [dev] f64 [B] (may be NULL)   counts [dev] u64 [B,3] = tp, fp, fn (may be NULL) */

@@ -9,6 +9,7 @@ Same command line as the reference's inference.py (flags :26-56, outputs :146-15
     python3 inference.py --image cat.jpg --fg-point 120,200 --bg-point 10,10 --hint-radius 8
     python3 inference.py --image cat.jpg --save mask alpha cutout          # soft edges: alpha matte and cut-out
     python3 inference.py --image big.jpg --full-res --save mask cutout     # outputs at the photo's own size
+    python3 inference.py --image cat.jpg --matte-method closed-form --save alpha cutout   # closed-form matte
 
 Images are decoded / written with Pillow (OpenCV is not a dependency of this build); folders are processed in
 batches of equally sized images so that the whole batch stays resident in HBM.
@@ -58,6 +59,16 @@ def build_parser() -> argparse.ArgumentParser:
     parser.add_argument("--matte-radius", type=int, default=4,
                         help="Window radius of the alpha matte, 1..64, in pixels of the image as segmented")
     parser.add_argument("--matte-eps", type=float, default=1e-4, help="Regularisation of the alpha matte (>= 1e-12)")
+    # additive: the closed-form matte (ggc_closed_form_matte) instead of the guided one; its own window and regulariser
+    parser.add_argument("--matte-method", choices=["guided", "closed-form"], default="guided",
+                        help="How alpha / cutout are computed: guided-filter feathering of the mask (--matte-radius, "
+                             "--matte-eps) or the closed-form matte solved on a band around its edge (--cf-* flags)")
+    parser.add_argument("--cf-radius", type=int, default=1, help="Window radius of the closed-form matte, 1..8")
+    parser.add_argument("--cf-eps", type=float, default=1e-5, help="Regularisation of the closed-form matte, [1e-12, 1]")
+    parser.add_argument("--cf-band", type=int, default=1,
+                        help="Half-width in pixels of the unknown band around the mask's edge, 0..64")
+    parser.add_argument("--cf-iters", type=int, default=500, help="Most conjugate-gradient iterations per image")
+    parser.add_argument("--cf-tol", type=float, default=1e-4, help="Stop when the residual falls to this fraction")
     # additive: outputs at the original size (ggc_upsample_matte), for images that --max-size shrank
     parser.add_argument("--full-res", action="store_true",
                         help="Write every output at the original image size: the mask (and alpha) found at --max-size "
@@ -141,6 +152,18 @@ def main() -> None:
         parser.error("--matte-radius must be in 1..64")
     if (matte or args.full_res) and not args.matte_eps >= 1e-12:
         parser.error("--matte-eps must be >= 1e-12")
+    closed_form = None
+    if matte and args.matte_method == "closed-form":
+        if args.full_res:
+            parser.error("--matte-method closed-form is not carried to the original size: drop --full-res, or use "
+                         "--matte-method guided")
+        from src.gcn_grabcut.pipeline import ClosedFormMatte
+        from src.gcn_grabcut._engine import check_closed_form_args
+        closed_form = ClosedFormMatte(args.cf_radius, args.cf_eps, args.cf_band, args.cf_iters, args.cf_tol)
+        try:
+            check_closed_form_args(*closed_form.args())
+        except ValueError as e:
+            parser.error(str(e))
     from src.gcn_grabcut import GCNGrabCutPipeline
     from src.gcn_grabcut.graph_builder import SuperpixelGraphConfig
     from src.gcn_grabcut.pipeline import _colour_trimap, _write_png, alpha_to_u8, nearest_upsample
@@ -186,7 +209,9 @@ def main() -> None:
                 hint_kw = dict(hints=[(scale_points(args.fg_point, orig_hw, image.shape[:2]),
                                        scale_points(args.bg_point, orig_hw, image.shape[:2]))],
                                hint_radius=args.hint_radius)
-            if matte:
+            if closed_form is not None:
+                hint_kw.update(matte=closed_form)
+            elif matte:
                 hint_kw.update(matte=True, matte_radius=args.matte_radius, matte_eps=args.matte_eps)
             if chunk[0][2] is not None:                 # --full-res on images that --max-size shrank
                 hint_kw.update(full_images=[full for _, _, full in chunk], matte_radius=args.matte_radius,
