@@ -31,6 +31,7 @@ enum Slot : int {
     S_MISC_A, S_MISC_B,
     S_CLICK,
     S_MATTE, S_MATTE_MEAN, S_CFMATTE,
+    S_FOREGROUND, S_FOREGROUND_VEC,
     S_COUNT
 };
 

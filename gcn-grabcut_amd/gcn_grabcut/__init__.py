@@ -20,8 +20,9 @@ from .model import (
     ResGCNNet, GCNTrimapNet, GATTrimapNet, build_model, _probs_to_trimap, probs_to_node_trimap, project_to_pixels,
     TRIMAP_BG, TRIMAP_FG, TRIMAP_PROB_BG, TRIMAP_PROB_FG, CLASS_BG, CLASS_UNK, CLASS_FG,
 )
-from .pipeline import (GCNGrabCutPipeline, ClosedFormMatte, FullResolution, SegmentationResult, alpha_matte,
-                       clean_mask, closed_form_matte, guided_filter, refine_trimap, upsample_mask)
+from .pipeline import (GCNGrabCutPipeline, ClosedFormMatte, ForegroundColours, FullResolution, SegmentationResult,
+                       alpha_matte, clean_mask, closed_form_matte, estimate_foreground, guided_filter, refine_trimap,
+                       upsample_mask)
 from .synthetic import synthetic_image, synthetic_batch
 from .losses import FocalLoss, LabelSmoothingCE, TrimapLoss
 from .trainer import Trainer, TrainConfig
@@ -34,7 +35,7 @@ __all__ = [
     "N_NODE_FEATS", "N_EDGE_FEATS", "N_PRIOR_FEATS",
     "evaluate", "evaluate_batch", "evaluate_trimap", "boundary_f1", "noc_summary", "SegmentationMetrics", "TrimapMetrics",
     "GCNGrabCutPipeline", "FullResolution", "SegmentationResult", "alpha_matte", "clean_mask", "guided_filter",
-    "refine_trimap", "upsample_mask", "ClosedFormMatte", "closed_form_matte",
+    "refine_trimap", "upsample_mask", "ClosedFormMatte", "closed_form_matte", "ForegroundColours", "estimate_foreground",
     "ResGCNNet", "GCNTrimapNet", "GATTrimapNet", "build_model", "probs_to_node_trimap", "project_to_pixels",
     "Data", "Batch", "synthetic_image", "synthetic_batch",
     "FocalLoss", "LabelSmoothingCE", "TrimapLoss", "Trainer", "TrainConfig",

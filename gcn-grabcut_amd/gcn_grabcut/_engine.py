@@ -331,6 +331,32 @@ class Engine:
                       iters.data_ptr(), rel.data_ptr())
         return (alpha, rgba, iters, rel) if want_rgba else (alpha, iters, rel)
 
+    def estimate_foreground(self, bgr, alpha, eps_r, omega, max_iter, tol, want_rgba=False, out=None):
+        """Foreground colours of bgr (B,H,W,3) uint8 under alpha (B,H,W) float32 (ggc_estimate_foreground): F where
+        alpha is fractional, the image's bytes elsewhere.
+        -> (foreground (B,H,W,3) uint8, iters (B,) int32, rel_residual (B,) float64), with want_rgba also rgba
+        (B,H,W,4) uint8, that colour with round(255 alpha), after foreground; out: (foreground, rgba or None),
+        preallocated.  The call synchronises its stream."""
+        check_foreground_args(eps_r, omega, max_iter, tol)
+        b, h, w, _ = bgr.shape
+        if tuple(alpha.shape) != (b, h, w):
+            raise ValueError(f"estimate_foreground: alpha {tuple(alpha.shape)} does not match bgr {tuple(bgr.shape)}")
+        if alpha.dtype != torch.float32:
+            raise ValueError(f"estimate_foreground: alpha must be float32, got {alpha.dtype}")
+        if h > UPSAMPLE_SIDE_MAX or w > UPSAMPLE_SIDE_MAX:
+            raise ValueError(f"estimate_foreground takes images of at most {UPSAMPLE_SIDE_MAX} on a side, got {h}x{w}")
+        if out is not None:
+            fg, rgba = out
+        else:
+            fg = self.empty(b, h, w, 3, dtype=torch.uint8)
+            rgba = self.empty(b, h, w, 4, dtype=torch.uint8) if want_rgba else None
+        iters = self.empty(b, dtype=torch.int32)
+        rel = self.empty(b, dtype=torch.float64)
+        self.ctx.call("ggc_estimate_foreground", self._stream(), b, h, w, bgr.data_ptr(), alpha.data_ptr(), float(eps_r),
+                      float(omega), int(max_iter), float(tol), _native.ptr(fg), _native.ptr(rgba), None, None,
+                      iters.data_ptr(), rel.data_ptr())
+        return (fg, rgba, iters, rel) if want_rgba else (fg, iters, rel)
+
     def iou(self, pred, gt):
         """-> (iou (B,) float64, counts (B,3) int64 = tp, fp, fn), on device."""
         b, h, w = pred.shape
@@ -378,6 +404,23 @@ def check_closed_form_shape(h, w, radius) -> None:
         raise ValueError(f"closed-form matte needs H, W >= 2r+1 = {2 * int(radius) + 1}, got {h}x{w}")
     if h > UPSAMPLE_SIDE_MAX or w > UPSAMPLE_SIDE_MAX:
         raise ValueError(f"closed-form matte takes images of at most {UPSAMPLE_SIDE_MAX} on a side, got {h}x{w}")
+
+
+FG_OMEGA_MAX = 1e3
+
+
+def check_foreground_args(eps_r, omega, max_iter, tol) -> None:
+    """The argument range of ggc_estimate_foreground, checked on the host so that a bad value is a ValueError."""
+    if not (np.isfinite(eps_r) and 0.0 <= float(eps_r) <= 1.0):
+        raise ValueError(f"foreground eps_r must be in [0, 1], got {eps_r}")
+    if not (np.isfinite(omega) and 0.0 <= float(omega) <= FG_OMEGA_MAX):
+        raise ValueError(f"foreground omega must be in [0, {FG_OMEGA_MAX:g}], got {omega}")
+    if not np.float32(eps_r) + np.float32(omega) > 0.0:
+        raise ValueError("foreground eps_r + omega must be positive (as float32)")
+    if int(max_iter) != max_iter or not 1 <= int(max_iter) <= CF_MAX_ITER_MAX:
+        raise ValueError(f"foreground max_iter must be an integer in 1..{CF_MAX_ITER_MAX}, got {max_iter}")
+    if not (np.isfinite(tol) and 1e-12 <= float(tol) < 1.0):
+        raise ValueError(f"foreground tol must be in [1e-12, 1), got {tol}")
 
 
 UPSAMPLE_SIDE_MAX = 32768

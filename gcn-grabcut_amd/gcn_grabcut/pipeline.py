@@ -59,6 +59,8 @@ class SegmentationResult:
     alpha: Optional[np.ndarray] = None       # additive: (H, W) float32 soft matte in [0, 1] (matte=True)
     rgba_soft: Optional[np.ndarray] = None   # additive: (H, W, 4) uint8 BGRA cut-out with alpha = round(255 alpha)
     full: Optional[FullResolution] = None    # additive: the outputs at the full image's resolution (full_image=...)
+    foreground: Optional[np.ndarray] = None  # additive: (H, W, 3) uint8 BGR estimated foreground colours (foreground=True)
+    rgba_clean: Optional[np.ndarray] = None  # additive: (H, W, 4) uint8 BGRA cut-out of `foreground`, alpha = round(255 alpha)
 
     def save(self, prefix: str = "result") -> None:
         _write_png(f"{prefix}_overlay.png", self.overlay)
@@ -69,6 +71,8 @@ class SegmentationResult:
             _write_png(f"{prefix}_alpha.png", alpha_to_u8(self.alpha))
         if self.rgba_soft is not None:
             _write_png(f"{prefix}_cutout.png", self.rgba_soft)
+        if self.rgba_clean is not None:
+            _write_png(f"{prefix}_cutout_clean.png", self.rgba_clean)
         if self.full is not None:
             f = self.full
             _write_png(f"{prefix}_full_mask.png", f.binary_mask * 255)
@@ -176,6 +180,57 @@ def closed_form_matte(image: np.ndarray, mask: np.ndarray, radius: int = CF_RADI
                                               radius, eps, band, max_iter, tol)
     a = alpha[0].cpu().numpy()
     return (a, int(iters[0].item()), float(rel[0].item())) if return_info else a
+
+
+FG_EPS_R = 5e-3
+FG_OMEGA = 1.0
+FG_MAX_ITER = 2000
+FG_TOL = 1e-6
+
+
+@dataclass(frozen=True)
+class ForegroundColours:
+    """foreground=ForegroundColours(...) (or foreground=True for the defaults) asks segment / segment_batch /
+    segment_batch_device / segment_bbox, together with a matte, for the estimated foreground colours under that matte
+    (estimate_foreground): result.foreground and the clean cut-out result.rgba_clean.  The defaults are a recorded choice
+    from a float64 CPU study (tools/foreground_study.py), not a tuned result."""
+    eps_r: float = FG_EPS_R
+    omega: float = FG_OMEGA
+    max_iter: int = FG_MAX_ITER
+    tol: float = FG_TOL
+
+    def args(self) -> "tuple[float, float, int, float]":
+        return float(self.eps_r), float(self.omega), int(self.max_iter), float(self.tol)
+
+
+def estimate_foreground(image: np.ndarray, alpha: np.ndarray, eps_r: float = FG_EPS_R, omega: float = FG_OMEGA,
+                        max_iter: int = FG_MAX_ITER, tol: float = FG_TOL, return_info: bool = False, device="cuda"):
+    """Foreground colours under an alpha matte (additive): where alpha is fractional the image's colour is the blend
+    alpha F + (1 - alpha) B, and a cut-out that keeps it shows a halo of the old background on a new one.  This solves
+    for F (and B) on those pixels: Germer, Uelwer, Conrad and Harmeling's foreground estimation energy (the blend
+    equation plus smoothness of F and B, weaker across changes of alpha: weight eps_r + omega |alpha_i - alpha_j|) with
+    the pixels of alpha 0 and 1 held at the image's colour, by preconditioned conjugate gradients on the device until the
+    residual falls to tol times its start, or for max_iter iterations (ggc_estimate_foreground).
+
+    image: (H, W, 3) uint8 BGR; alpha: (H, W) float in [0, 1] (alpha_matte's or closed_form_matte's output; values whose
+    byte round(255 alpha) is 0 or 255 count as 0 and 1; a NaN counts as 0).  0 <= eps_r <= 1, 0 <= omega <= 1000, not
+    both 0, max_iter in 1..100000, 1e-12 <= tol < 1.
+    -> (H, W, 3) uint8 BGR: F where alpha is fractional, the image elsewhere; with return_info, (foreground, iterations,
+    relative residual)."""
+    from ._engine import get_engine, check_foreground_args
+    image = _check_image(image)
+    a = np.asarray(alpha)
+    if a.shape != image.shape[:2]:
+        raise ValueError(f"estimate_foreground: alpha {a.shape} does not match image {image.shape[:2]}")
+    if a.dtype.kind != "f":
+        raise ValueError(f"estimate_foreground: alpha must be a float array, got {a.dtype}")
+    check_foreground_args(eps_r, omega, max_iter, tol)
+    eng = get_engine(device)
+    fg, iters, rel = eng.estimate_foreground(eng.to_device(image[None]),
+                                             eng.to_device(np.ascontiguousarray(a, np.float32)[None]), eps_r, omega,
+                                             max_iter, tol)
+    f = fg[0].cpu().numpy()
+    return (f, int(iters[0].item()), float(rel[0].item())) if return_info else f
 
 
 def upsample_mask(image: np.ndarray, mask: np.ndarray, full_image: np.ndarray, radius: int = MATTE_RADIUS,
@@ -378,6 +433,25 @@ def _closed_form_args(matte, h: int, w: int, full: bool) -> "Optional[tuple[int,
     return args
 
 
+def _foreground_args(foreground, matte, full: bool) -> "Optional[tuple[float, float, int, float]]":
+    """The foreground estimation's arguments when foreground is True or a ForegroundColours (checked here, before any
+    stage runs; refused without a matte and together with full-resolution outputs), else None."""
+    if foreground is None or foreground is False:
+        return None
+    if foreground is True:
+        foreground = ForegroundColours()
+    if not isinstance(foreground, ForegroundColours):
+        raise ValueError(f"foreground must be True, False or a ForegroundColours, got {type(foreground).__name__}")
+    from ._engine import check_foreground_args
+    if not (matte is True or isinstance(matte, ClosedFormMatte)):
+        raise ValueError("foreground needs the alpha of a matte: pass matte=True or matte=ClosedFormMatte(...)")
+    if full:
+        raise ValueError("the foreground colours are not carried to full resolution: drop foreground or full_image(s)")
+    args = foreground.args()
+    check_foreground_args(*args)
+    return args
+
+
 def _soft_matte(leng, img, cleaned, mat, cfm, alpha, rgba_soft) -> None:
     """alpha and rgba_soft of the cleaned masks: the guided matte (mat) or the closed-form one (cfm)."""
     if mat:
@@ -544,13 +618,19 @@ class GCNGrabCutPipeline:
                              timing: Optional[dict] = None, grabcut_lanes: Optional[int] = None,
                              chunks: Optional[int] = None, hints=None, hint_radius: int = 5, hint_region: bool = False,
                              hints_as_prior: bool = False, return_state: bool = False, matte: bool = False,
-                             matte_radius: int = MATTE_RADIUS, matte_eps: float = MATTE_EPS, full_bgr=None) -> dict:
+                             matte_radius: int = MATTE_RADIUS, matte_eps: float = MATTE_EPS, full_bgr=None,
+                             foreground=False) -> dict:
         """bgr: (B,H,W,3) uint8 tensor on the pipeline's device.  Returns device tensors.
 
         matte=True (additive) also returns "alpha" (B,H,W) float32, the soft matte of the cleaned mask (alpha_matte with
         matte_radius / matte_eps), and "rgba_soft" (B,H,W,4) uint8, the cut-out with that alpha.  Every other output is
         the same as without it.  matte=ClosedFormMatte(...) fills the same two outputs with closed_form_matte of the
         cleaned mask instead (matte_radius / matte_eps do not apply); it cannot be combined with full_bgr.
+
+        foreground=True or ForegroundColours(...) (additive, needs a matte) also returns "foreground" (B,H,W,3) uint8,
+        the estimated foreground colours under that matte's alpha (estimate_foreground), and "rgba_clean" (B,H,W,4)
+        uint8, the cut-out with those colours and the byte round(255 alpha) of that alpha.  Every other output is the
+        same as without it; it cannot be combined with full_bgr.
 
         full_bgr (additive): a (B,H1,W1,3) uint8 tensor on the device, the same images at a resolution of at least the
         working one.  The result then also has "full", a dict of device tensors at (H1, W1): "binary_mask", the cleaned
@@ -586,12 +666,13 @@ class GCNGrabCutPipeline:
         cfm = _closed_form_args(matte, bgr.shape[1], bgr.shape[2], full_bgr is not None)
         mat = None if cfm else _matte_args(matte, matte_radius, matte_eps)
         fmat = _full_args(full_bgr, bgr.shape, matte_radius, matte_eps)
+        fga = _foreground_args(foreground, matte, full_bgr is not None)
         if n_chunks <= 0:                          # 0: one chunk per GrabCut lane once every chunk gets a lane's worth of images
             n_chunks = max(want, 1) if b >= 16 * max(want, 1) else 1
         if n_chunks > 1 and b >= 2 * n_chunks:
             return self._segment_pipelined(bgr, self.chunk_plan(b, n_chunks, self.chunk_ratio), cs, threshold_fg, threshold_bg,
                                            refine_iters, min_area_ratio, keep_largest, edge_aware, filter_radius, compose, timing,
-                                           hints, return_state, mat, full_bgr, fmat, cfm)
+                                           hints, return_state, mat, full_bgr, fmat, cfm, fga)
 
         def tick():
             if timing is not None:
@@ -613,6 +694,8 @@ class GCNGrabCutPipeline:
         alpha = eng.empty(*bgr.shape[:3]) if (mat or cfm) else None
         rgba_soft = eng.empty(*bgr.shape[:3], 4, dtype=torch.uint8) if (mat or cfm) else None
         full = _full_buffers(eng, full_bgr, compose, mat)
+        fg_col = eng.empty(*bgr.shape[:3], 3, dtype=torch.uint8) if fga else None
+        rgba_clean = eng.empty(*bgr.shape[:3], 4, dtype=torch.uint8) if fga else None
 
         def post(leng, lo, hi, binary_part):
             leng.clean_mask(binary_part, min_area_ratio, keep_largest, out=cleaned[lo:hi])
@@ -620,6 +703,8 @@ class GCNGrabCutPipeline:
                 leng.compose(bgr[lo:hi], cleaned[lo:hi], out=(overlay[lo:hi], rgba[lo:hi]))
             if mat or cfm:
                 _soft_matte(leng, bgr[lo:hi], cleaned[lo:hi], mat, cfm, alpha[lo:hi], rgba_soft[lo:hi])
+            if fga:
+                leng.estimate_foreground(bgr[lo:hi], alpha[lo:hi], *fga, out=(fg_col[lo:hi], rgba_clean[lo:hi]))
             if full is not None:
                 _full_post(leng, lo, hi, bgr, cleaned, full_bgr, full, fmat)
 
@@ -643,6 +728,8 @@ class GCNGrabCutPipeline:
             out["overlay"], out["rgba"] = overlay, rgba
         if mat or cfm:
             out["alpha"], out["rgba_soft"] = alpha, rgba_soft
+        if fga:
+            out["foreground"], out["rgba_clean"] = fg_col, rgba_clean
         if full is not None:
             out["full"] = full
         if timing is not None:
@@ -651,7 +738,7 @@ class GCNGrabCutPipeline:
 
     def _segment_pipelined(self, bgr, plan, cs, threshold_fg, threshold_bg, refine_iters, min_area_ratio, keep_largest,
                            edge_aware, filter_radius, compose, timing, hints=None, return_state=False, mat=None,
-                           full_bgr=None, fmat=None, cfm=None) -> dict:
+                           full_bgr=None, fmat=None, cfm=None, fga=None) -> dict:
         """The software pipeline behind segment_batch_device: chunk k's GrabCut lane starts as soon as chunk k's trimaps are
         on the device; the caller's stream goes on with chunk k+1's SLIC / graph / network / trimap."""
         import torch
@@ -676,6 +763,8 @@ class GCNGrabCutPipeline:
         alpha = eng.empty(b, h, w) if (mat or cfm) else None
         rgba_soft = eng.empty(b, h, w, 4, dtype=torch.uint8) if (mat or cfm) else None
         full = _full_buffers(eng, full_bgr, compose, mat)
+        fg_col = eng.empty(b, h, w, 3, dtype=torch.uint8) if fga else None
+        rgba_clean = eng.empty(b, h, w, 4, dtype=torch.uint8) if fga else None
         if return_state:
             st_binary = eng.empty(b, h, w, dtype=torch.uint8)
             st_bgd = eng.empty(b, 65, dtype=torch.float64)
@@ -711,6 +800,8 @@ class GCNGrabCutPipeline:
                     leng.compose(img, cleaned[lo:hi], out=(overlay[lo:hi], rgba[lo:hi]))
                 if mat or cfm:
                     _soft_matte(leng, img, cleaned[lo:hi], mat, cfm, alpha[lo:hi], rgba_soft[lo:hi])
+                if fga:
+                    leng.estimate_foreground(img, alpha[lo:hi], *fga, out=(fg_col[lo:hi], rgba_clean[lo:hi]))
                 if full is not None:
                     _full_post(leng, lo, hi, bgr, cleaned, full_bgr, full, fmat)
                 if ev is not None:
@@ -747,6 +838,8 @@ class GCNGrabCutPipeline:
             out["overlay"], out["rgba"] = overlay, rgba
         if mat or cfm:
             out["alpha"], out["rgba_soft"] = alpha, rgba_soft
+        if fga:
+            out["foreground"], out["rgba_clean"] = fg_col, rgba_clean
         if full is not None:
             out["full"] = full
         if timing is not None:                        # stage times from stream events (the stages overlap: they add up to more than the wall time)
@@ -762,13 +855,15 @@ class GCNGrabCutPipeline:
         """Segment equally sized BGR images as one batch (additive API).  hints: one None or (fg_points, bg_points) per
         image, with hint_radius / hint_region / hints_as_prior among kwargs (segment_batch_device).  full_images
         (additive): the same images at one larger size each, (H1, W1, 3) uint8 BGR; every result's `full` then holds the
-        outputs at that size (segment_batch_device's full_bgr)."""
+        outputs at that size (segment_batch_device's full_bgr).  foreground=True | ForegroundColours(...) among kwargs
+        (with a matte) fills every result's foreground and rgba_clean."""
         imgs = [_check_image(im) for im in images]
         if not imgs:
             return []
         if any(im.shape != imgs[0].shape for im in imgs):
             raise ValueError("segment_batch needs images of one size; group them by shape")
         _closed_form_args(kwargs.get("matte"), *imgs[0].shape[:2], full_images is not None)
+        _foreground_args(kwargs.get("foreground"), kwargs.get("matte"), full_images is not None)
         full_bgr = None
         if full_images is not None:
             fulls = [_check_image(im) for im in full_images]
@@ -783,14 +878,17 @@ class GCNGrabCutPipeline:
         timing: dict[str, float] = {}
         bgr = self._eng.to_device(np.stack(imgs))
         out = self.segment_batch_device(bgr, timing=timing, hints=hints, full_bgr=full_bgr, **kwargs)
-        host = {k: out[k].cpu().numpy() for k in ("binary_mask", "trimap", "segments", "overlay", "rgba", "alpha", "rgba_soft")
+        host = {k: out[k].cpu().numpy() for k in ("binary_mask", "trimap", "segments", "overlay", "rgba", "alpha", "rgba_soft",
+                                                     "foreground", "rgba_clean")
                 if k in out}
         per_image = {k: v / len(imgs) for k, v in timing.items()}
         return [SegmentationResult(image=imgs[i], binary_mask=host["binary_mask"][i], trimap=host["trimap"][i],
                                    segments=host["segments"][i], overlay=host["overlay"][i], rgba=host["rgba"][i],
                                    timing=dict(per_image), alpha=host["alpha"][i] if "alpha" in host else None,
                                    rgba_soft=host["rgba_soft"][i] if "rgba_soft" in host else None,
-                                   full=_full_result(out["full"], i) if "full" in out else None)
+                                   full=_full_result(out["full"], i) if "full" in out else None,
+                                   foreground=host["foreground"][i] if "foreground" in host else None,
+                                   rgba_clean=host["rgba_clean"][i] if "rgba_clean" in host else None)
                 for i in range(len(imgs))]
 
     def _click_round(self, binary, gt, mask, image, bgd, fgd, hint_ptr, hint_radius=5, n_iter=1):
@@ -897,16 +995,18 @@ class GCNGrabCutPipeline:
                 edge_aware: bool = True, filter_radius: int = 8, fg_points=None, bg_points=None, hint_radius: int = 5,
                 hint_region: bool = False, hints_as_prior: bool = False, matte: bool = False,
                 matte_radius: int = MATTE_RADIUS, matte_eps: float = MATTE_EPS,
-                full_image: Optional[np.ndarray] = None) -> SegmentationResult:
+                full_image: Optional[np.ndarray] = None, foreground=False) -> SegmentationResult:
         """Full pipeline on one BGR image (reference pipeline.py:265-352).
 
         Additive: fg_points / bg_points are user clicks, (row, col) pairs, applied as hard constraints on the trimap
         GrabCut starts from (see segment_batch_device for hint_radius, hint_region and hints_as_prior); matte=True also
         fills the result's alpha and rgba_soft (segment_batch_device), matte=ClosedFormMatte(...) with the closed-form
         matte; full_image, the same image at a larger size, fills
-        the result's `full` (segment_batch_device's full_bgr)."""
+        the result's `full` (segment_batch_device's full_bgr); foreground=True | ForegroundColours(...), with a matte,
+        fills the result's foreground and rgba_clean (estimate_foreground under that matte's alpha)."""
         image = _check_image(image)
         _closed_form_args(matte, *image.shape[:2], full_image is not None)
+        _foreground_args(foreground, matte, full_image is not None)
         full_bgr = None if full_image is None else self._eng.to_device(_check_image(full_image)[None])
         timing: dict[str, float] = {}
         hints = None if fg_points is None and bg_points is None else \
@@ -915,24 +1015,28 @@ class GCNGrabCutPipeline:
                                         min_area_ratio, keep_largest, edge_aware, filter_radius, timing=timing,
                                         hints=hints, hint_radius=hint_radius, hint_region=hint_region,
                                         hints_as_prior=hints_as_prior, matte=matte, matte_radius=matte_radius,
-                                        matte_eps=matte_eps, full_bgr=full_bgr)
+                                        matte_eps=matte_eps, full_bgr=full_bgr, foreground=foreground)
         return SegmentationResult(
             image=image, binary_mask=out["binary_mask"][0].cpu().numpy(), trimap=out["trimap"][0].cpu().numpy(),
             segments=out["segments"][0].cpu().numpy(), overlay=out["overlay"][0].cpu().numpy(),
             rgba=out["rgba"][0].cpu().numpy(), timing=timing,
             alpha=out["alpha"][0].cpu().numpy() if matte else None,
             rgba_soft=out["rgba_soft"][0].cpu().numpy() if matte else None,
-            full=_full_result(out["full"], 0) if "full" in out else None)
+            full=_full_result(out["full"], 0) if "full" in out else None,
+            foreground=out["foreground"][0].cpu().numpy() if "foreground" in out else None,
+            rgba_clean=out["rgba_clean"][0].cpu().numpy() if "rgba_clean" in out else None)
 
     def segment_bbox(self, image: np.ndarray, bbox: tuple[int, int, int, int], matte: bool = False,
                      matte_radius: int = MATTE_RADIUS, matte_eps: float = MATTE_EPS,
-                     full_image: Optional[np.ndarray] = None) -> SegmentationResult:
+                     full_image: Optional[np.ndarray] = None, foreground=False) -> SegmentationResult:
         """Classical GrabCut with a bounding box (reference pipeline.py:354-380).  Additive: matte=True also fills the
         result's alpha and rgba_soft, the soft matte of the returned mask (alpha_matte; closed_form_matte with
         matte=ClosedFormMatte(...)); full_image, the same image at a
-        larger size, fills the result's `full` from the returned mask (upsample_mask, then the overlay and cut-out)."""
+        larger size, fills the result's `full` from the returned mask (upsample_mask, then the overlay and cut-out);
+        foreground=True | ForegroundColours(...), with a matte, fills the result's foreground and rgba_clean."""
         image = _check_image(image)
         cfm = _closed_form_args(matte, *image.shape[:2], full_image is not None)
+        fga = _foreground_args(foreground, matte, full_image is not None)
         mat = None if cfm else _matte_args(matte, matte_radius, matte_eps)
         full_img = None
         if full_image is not None:
@@ -947,17 +1051,21 @@ class GCNGrabCutPipeline:
         y0, y1, x0, x1 = eroded_box(H, W, bbox)
         if y1 > y0 and x1 > x0:
             trimap[y0:y1, x0:x1] = Label.FG_DEFINITE
-        alpha = rgba_soft = None
+        alpha = rgba_soft = fg_col = rgba_clean = None
         if mat:
             eng = self._eng
             alpha, rgba_soft = eng.alpha_matte(eng.to_device(image[None]), eng.to_device(binary_mask[None]), *mat,
                                                want_rgba=True)
+            if fga:
+                fg_col, rgba_clean, _, _ = eng.estimate_foreground(eng.to_device(image[None]), alpha, *fga, want_rgba=True)
             alpha, rgba_soft = alpha[0].cpu().numpy(), rgba_soft[0].cpu().numpy()
         elif cfm:
             eng = self._eng
             alpha, rgba_soft, _, _ = eng.closed_form_matte(eng.to_device(image[None]),
                                                            eng.to_device(np.ascontiguousarray(binary_mask, np.uint8)[None]),
                                                            *cfm, want_rgba=True)
+            if fga:
+                fg_col, rgba_clean, _, _ = eng.estimate_foreground(eng.to_device(image[None]), alpha, *fga, want_rgba=True)
             alpha, rgba_soft = alpha[0].cpu().numpy(), rgba_soft[0].cpu().numpy()
         full = None
         if full_img is not None:
@@ -969,4 +1077,6 @@ class GCNGrabCutPipeline:
             full = _full_result(bufs, 0)
         return SegmentationResult(image=image, binary_mask=binary_mask, trimap=trimap,
                                   segments=np.zeros((H, W), dtype=np.int32), overlay=gc.overlay_mask(),
-                                  rgba=gc.crop_foreground(), alpha=alpha, rgba_soft=rgba_soft, full=full)
+                                  rgba=gc.crop_foreground(), alpha=alpha, rgba_soft=rgba_soft, full=full,
+                                  foreground=None if fg_col is None else fg_col[0].cpu().numpy(),
+                                  rgba_clean=None if rgba_clean is None else rgba_clean[0].cpu().numpy())

@@ -50,7 +50,8 @@
 extern "C" {
 #endif
 
-#define GGC_VERSION 380 /* 0.3.8: ggc_closed_form_matte (closed-form alpha matte: matting Laplacian solved by PCG on the device);
+#define GGC_VERSION 390 /* 0.3.9: ggc_estimate_foreground (foreground colours under an alpha matte: clean cut-outs, PCG on the device);
+                           0.3.8: ggc_closed_form_matte (closed-form alpha matte: matting Laplacian solved by PCG on the device);
                            0.3.7: ggc_upsample_matte (the matte's mask and alpha at a larger resolution: fast guided filter);
                            0.3.6: ggc_alpha_matte (soft alpha matte of a binary mask: colour guided-filter feathering);
                            0.3.5: ggc_grid_maxflow (the GrabCut max-flow on a caller's network, a test hook);
@@ -485,6 +486,46 @@ int ggc_upsample_matte(ggc_ctx* ctx, ggc_stream stream, int B, int H, int W, con
 int ggc_closed_form_matte(ggc_ctx* ctx, ggc_stream stream, int B, int H, int W, const uint8_t* bgr, const uint8_t* binary,
                           int radius, float eps, int band, int max_iter, float tol,
                           float* alpha, uint8_t* rgba, double* raw, int32_t* iters, double* rel_residual);
+
+/* O4 — foreground colour estimation under a given alpha matte (additive; the multi-level foreground estimation energy of
+ * Germer, Uelwer, Conrad and Harmeling, ICPR 2020, restricted to the pixels of fractional alpha with Dirichlet values).
+ * A cut-out that keeps the image's bytes carries the old background along wherever alpha is fractional (I = alpha F +
+ * (1 - alpha) B); this entry estimates F there.  Per image and independently per colour channel, I = byte / 255, alpha
+ * read as float64:
+ *   snap      alpha' = 0 where alpha < 1/510, 1 where alpha > 1 - 1/510, else alpha (the pixels whose alpha byte is 0 or
+ *             255).  A NaN is not >= 1/510 and is snapped to 0; -inf and +inf snap to 0 and 1.  Z = {alpha' = 0},
+ *             O = {alpha' = 1}, unknown set U = {0 < alpha' < 1}; no dilation
+ *   known     F = I on O, B = I on Z; F on Z and B on O are not part of the system
+ *   energy    E = sum_{i in U} (alpha'_i F_i + (1 - alpha'_i) B_i - I_i)^2
+ *               + delta sum_{i in U} [(F_i - I_i)^2 + (B_i - I_i)^2],                          delta = 1e-6, fixed
+ *               + sum_{(i,j)} w_ij [phiF_ij (F_i - F_j)^2 + phiB_ij (B_i - B_j)^2],  w_ij = eps_r + omega |alpha'_i - alpha'_j|
+ *             over the horizontal and vertical neighbour pairs inside the image with at least one end in U; phiF_ij = 1
+ *             when both ends are in U or O (an end in O contributes its known F = I), else 0; phiB_ij = 1 when both ends
+ *             are in U or Z, else 0.  No links across the image border.
+ *   solve     the normal equations A x = b (symmetric positive definite for eps_r >= 0) by preconditioned CG from
+ *             F = B = I; preconditioner: the exact 2 x 2 diagonal block of each pixel, [[alpha'^2 + delta + sum w phiF,
+ *             alpha' (1 - alpha')], [alpha' (1 - alpha'), (1 - alpha')^2 + delta + sum w phiB]]; one CG over the three
+ *             channels of an image.  An image stops when ||r_j||_2 <= max(tol ||r_0||_2, 1e-12 sqrt(6 |U|))
+ *             (unpreconditioned residual) or after max_iter iterations; the test is made on r_0 too, so an image whose U
+ *             is empty, or whose start already solves the system (a flat-colour image), takes 0 iterations.
+ *   bgr [dev] u8 [B,H,W,3]   alpha [dev] f32 [B,H,W]
+ *   0 <= eps_r <= 1, 0 <= omega <= 1000, eps_r + omega > 0, 1 <= max_iter <= 100000, 1e-12 <= tol < 1 (else
+ *   GGC_E_INVALID_ARG); H, W <= 32768, B <= 65535 (else GGC_E_SHAPE); B == 0 does nothing
+ *   foreground [dev] u8 [B,H,W,3] = floor(255 clamp(F, 0, 1) + 0.5) on U, the image's bytes everywhere else
+ *   rgba [dev] u8 [B,H,W,4] = that colour, floor(255 clamp(alpha, 0, 1) + 0.5) of the UNSNAPPED alpha (0 for a NaN)
+ *   raw_f, raw_b [dev] f64 [B,H,W,3] = F, B unclamped (I outside U)
+ *   iters [dev] i32 [B]     rel_residual [dev] f64 [B] = ||r_j|| / ||r_0|| (0 for an image with 0 iterations)
+ *   (each may be NULL, not all of them)
+ * The CG vectors and dot products are float64.  Every per-image reduction runs in one fixed order over that image's
+ * tiles, so every image's outputs equal its single-image call bit for bit and two runs are identical; no float atomics.
+ * Work is restricted to the 16 x 16 tiles that hold U, listed once per call.  The entry SYNCHRONISES its stream: once to
+ * build that list on the host, and every 8 iterations to read the count of finished images (an integer atomic) and stop
+ * when all are done.  Scratch from the context: 4 bytes per pixel, 32 bytes per 16 x 16 tile and 72 bytes per image over
+ * the whole batch, plus 61440 bytes (256 pixels x 5 vectors x 48 bytes) per LISTED tile. */
+int ggc_estimate_foreground(ggc_ctx* ctx, ggc_stream stream, int B, int H, int W, const uint8_t* bgr, const float* alpha,
+                            float eps_r, float omega, int max_iter, float tol,
+                            uint8_t* foreground, uint8_t* rgba, double* raw_f, double* raw_b, int32_t* iters,
+                            double* rel_residual);
 
 /* R0 — IoU = tp / (tp + fp + fn + 1e-8) per image (metrics.py:79-84).
  *   iou [dev] f64 [B] (may be NULL)   counts [dev] u64 [B,3] = tp, fp, fn (may be NULL) */

@@ -69,6 +69,15 @@ def build_parser() -> argparse.ArgumentParser:
                         help="Half-width in pixels of the unknown band around the mask's edge, 0..64")
     parser.add_argument("--cf-iters", type=int, default=500, help="Most conjugate-gradient iterations per image")
     parser.add_argument("--cf-tol", type=float, default=1e-4, help="Stop when the residual falls to this fraction")
+    # additive: foreground colours under the matte (ggc_estimate_foreground), so that the cut-out carries no old background
+    parser.add_argument("--decontaminate", action="store_true",
+                        help="Write the cut-out (--save cutout) with estimated foreground colours where alpha is "
+                             "fractional, instead of the image's own, so that it shows no halo on a new background")
+    parser.add_argument("--decon-eps", type=float, default=5e-3, help="Constant part of the colour smoothness weight, [0, 1]")
+    parser.add_argument("--decon-omega", type=float, default=1.0,
+                        help="Weight of |alpha_i - alpha_j| in the colour smoothness weight, [0, 1000]")
+    parser.add_argument("--decon-iters", type=int, default=2000, help="Most conjugate-gradient iterations per image")
+    parser.add_argument("--decon-tol", type=float, default=1e-6, help="Stop when the residual falls to this fraction")
     # additive: outputs at the original size (ggc_upsample_matte), for images that --max-size shrank
     parser.add_argument("--full-res", action="store_true",
                         help="Write every output at the original image size: the mask (and alpha) found at --max-size "
@@ -164,6 +173,19 @@ def main() -> None:
             check_closed_form_args(*closed_form.args())
         except ValueError as e:
             parser.error(str(e))
+    foreground = None
+    if args.decontaminate:
+        if "cutout" not in args.save:
+            parser.error("--decontaminate changes the cut-out: add cutout to --save")
+        if args.full_res:
+            parser.error("--decontaminate is not carried to the original size: drop --full-res")
+        from src.gcn_grabcut.pipeline import ForegroundColours
+        from src.gcn_grabcut._engine import check_foreground_args
+        foreground = ForegroundColours(args.decon_eps, args.decon_omega, args.decon_iters, args.decon_tol)
+        try:
+            check_foreground_args(*foreground.args())
+        except ValueError as e:
+            parser.error(str(e))
     from src.gcn_grabcut import GCNGrabCutPipeline
     from src.gcn_grabcut.graph_builder import SuperpixelGraphConfig
     from src.gcn_grabcut.pipeline import _colour_trimap, _write_png, alpha_to_u8, nearest_upsample
@@ -213,6 +235,8 @@ def main() -> None:
                 hint_kw.update(matte=closed_form)
             elif matte:
                 hint_kw.update(matte=True, matte_radius=args.matte_radius, matte_eps=args.matte_eps)
+            if foreground is not None:
+                hint_kw.update(foreground=foreground)
             if chunk[0][2] is not None:                 # --full-res on images that --max-size shrank
                 hint_kw.update(full_images=[full for _, _, full in chunk], matte_radius=args.matte_radius,
                                matte_eps=args.matte_eps)
@@ -239,7 +263,7 @@ def main() -> None:
                 if "alpha" in args.save:
                     _write_png(f"{stem}_alpha.png", alpha_to_u8(out.alpha))
                 if "cutout" in args.save:
-                    _write_png(f"{stem}_cutout.png", out.rgba_soft)
+                    _write_png(f"{stem}_cutout.png", out.rgba_soft if foreground is None else result.rgba_clean)
                 t = result.timing
                 print(f"[{n_done}/{len(paths)}] {path.name}  fg={result.binary_mask.mean():.1%}  "
                       f"graph={t.get('graph_build', 0):.4f}s gcn={t.get('gcn_inference', 0):.4f}s "
