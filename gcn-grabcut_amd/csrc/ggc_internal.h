@@ -32,6 +32,7 @@ enum Slot : int {
     S_CLICK,
     S_MATTE, S_MATTE_MEAN, S_CFMATTE,
     S_FOREGROUND, S_FOREGROUND_VEC,
+    S_MATTE_EVAL,
     S_COUNT
 };
 
@@ -104,6 +105,7 @@ struct Knobs {
     int mf_partial_rounds;      // GGC_MF_PARTIAL_ROUNDS (3, at most 64): first rounds of a solve whose relabel stops after the work-list launches
     int agg_direct;             // GGC_AGG_DIRECT (0): 1 = GCNConv gather straight from L2 (k_aggregate) instead of the graph-resident kernel
     int slic_seq_connectivity;  // GGC_SLIC_SEQ_CONNECTIVITY (0): 1 = literal one-thread-per-image raster replay of skimage's connectivity pass
+    int matte_eval_levels;      // GGC_MATTE_EVAL_LEVELS (0): threshold levels labelled per pass of ggc_matte_errors, 1 | 2 | 5 | 10; 0 = 10 while the maps fit 4 GiB, else 1
 };
 const Knobs& knobs();
 

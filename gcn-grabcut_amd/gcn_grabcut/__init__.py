@@ -15,6 +15,7 @@ from .graph_builder import (
 )
 from .metrics import (
     evaluate, evaluate_batch, evaluate_trimap, boundary_f1, noc_summary, SegmentationMetrics, TrimapMetrics,
+    evaluate_matte, evaluate_matte_batch, MatteMetrics,
 )
 from .model import (
     ResGCNNet, GCNTrimapNet, GATTrimapNet, build_model, _probs_to_trimap, probs_to_node_trimap, project_to_pixels,
@@ -34,6 +35,7 @@ __all__ = [
     "GraphBuilder", "SuperpixelGraph", "SuperpixelGraphConfig", "compute_auto_prior", "encode_user_hints", "pack_hints",
     "N_NODE_FEATS", "N_EDGE_FEATS", "N_PRIOR_FEATS",
     "evaluate", "evaluate_batch", "evaluate_trimap", "boundary_f1", "noc_summary", "SegmentationMetrics", "TrimapMetrics",
+    "evaluate_matte", "evaluate_matte_batch", "MatteMetrics",
     "GCNGrabCutPipeline", "FullResolution", "SegmentationResult", "alpha_matte", "clean_mask", "guided_filter",
     "refine_trimap", "upsample_mask", "ClosedFormMatte", "closed_form_matte", "ForegroundColours", "estimate_foreground",
     "ResGCNNet", "GCNTrimapNet", "GATTrimapNet", "build_model", "probs_to_node_trimap", "project_to_pixels",

@@ -357,6 +357,23 @@ class Engine:
                       iters.data_ptr(), rel.data_ptr())
         return (fg, rgba, iters, rel) if want_rgba else (fg, iters, rel)
 
+    def matte_errors(self, pred_u8, gt_u8, region=None, want_grad=True, want_levels=False):
+        """The four matte errors of pred_u8 against gt_u8, both (B,H,W) uint8 alpha levels on the device
+        (ggc_matte_errors); region (B,H,W) uint8 or None restricts the sums to its nonzero pixels.
+        -> (sums (B,4) int64 = n, SAD, SSE, CONN, grad (B,) float64 or None, levels (B,H,W) uint8 or None), on the
+        device.  The call does not synchronise."""
+        check_matte_eval_args(tuple(pred_u8.shape), tuple(gt_u8.shape), None if region is None else tuple(region.shape),
+                              (pred_u8.dtype, gt_u8.dtype) + (() if region is None else (region.dtype,)))
+        b, h, w = pred_u8.shape
+        sums = self.empty(b, 4, dtype=torch.int64)
+        grad = self.empty(b, dtype=torch.float64) if want_grad else None
+        levels = self.empty(b, h, w, dtype=torch.uint8) if want_levels else None
+        pred_u8, gt_u8 = pred_u8.contiguous(), gt_u8.contiguous()
+        region = None if region is None else region.contiguous()
+        self.ctx.call("ggc_matte_errors", self._stream(), b, h, w, pred_u8.data_ptr(), gt_u8.data_ptr(),
+                      _native.ptr(region), sums.data_ptr(), _native.ptr(grad), _native.ptr(levels))
+        return sums, grad, levels
+
     def iou(self, pred, gt):
         """-> (iou (B,) float64, counts (B,3) int64 = tp, fp, fn), on device."""
         b, h, w = pred.shape
@@ -421,6 +438,27 @@ def check_foreground_args(eps_r, omega, max_iter, tol) -> None:
         raise ValueError(f"foreground max_iter must be an integer in 1..{CF_MAX_ITER_MAX}, got {max_iter}")
     if not (np.isfinite(tol) and 1e-12 <= float(tol) < 1.0):
         raise ValueError(f"foreground tol must be in [1e-12, 1), got {tol}")
+
+
+MATTE_EVAL_BATCH_MAX = 65535
+
+
+def check_matte_eval_args(pred_shape, gt_shape, region_shape=None, dtypes=()) -> None:
+    """The shape rules of ggc_matte_errors, checked on the host so that a bad argument is a ValueError: pred, gt and
+    region (B,H,W) uint8 of one shape, B <= 65535, H, W in 1..32768, H W < 2^31."""
+    if len(pred_shape) != 3:
+        raise ValueError(f"matte_errors: mattes must be (B,H,W), got {tuple(pred_shape)}")
+    if tuple(gt_shape) != tuple(pred_shape):
+        raise ValueError(f"matte_errors: pred {tuple(pred_shape)} and gt {tuple(gt_shape)} differ in shape")
+    if region_shape is not None and tuple(region_shape) != tuple(pred_shape):
+        raise ValueError(f"matte_errors: region {tuple(region_shape)} does not match the mattes {tuple(pred_shape)}")
+    b, h, w = (int(v) for v in pred_shape)
+    if b > MATTE_EVAL_BATCH_MAX or not (1 <= h <= UPSAMPLE_SIDE_MAX and 1 <= w <= UPSAMPLE_SIDE_MAX) or h * w >= 2 ** 31:
+        raise ValueError(f"matte_errors: B <= {MATTE_EVAL_BATCH_MAX}, H and W in 1..{UPSAMPLE_SIDE_MAX} and H*W < 2^31, "
+                         f"got {tuple(pred_shape)}")
+    for dt in dtypes:
+        if dt != torch.uint8:
+            raise ValueError(f"matte_errors: mattes and region must be uint8 levels, got {dt}")
 
 
 UPSAMPLE_SIDE_MAX = 32768

@@ -76,6 +76,7 @@ SIGNATURES = {
     "ggc_upsample_matte": [_vp, _vp, _i, _i, _i, _vp, _vp, _i, _i, _vp, _i, _f, _vp, _vp, _vp],
     "ggc_closed_form_matte": [_vp, _vp, _i, _i, _i, _vp, _vp, _i, _f, _i, _i, _f, _vp, _vp, _vp, _vp, _vp],
     "ggc_estimate_foreground": [_vp, _vp, _i, _i, _i, _vp, _vp, _f, _f, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp],
+    "ggc_matte_errors": [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp],
     "ggc_mask_iou": [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp],
     "ggc_region_label_stats": [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp],
     "ggc_eval_counts": [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _i, _vp],

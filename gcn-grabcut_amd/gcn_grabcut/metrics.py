@@ -4,6 +4,9 @@ Segmentation metrics — host mirror of reference src/gcn_grabcut/metrics.py: `e
 (:204-229).  Every metric is a ratio of integer tallies; the tallies (confusion counts,
 eroded-boundary overlaps, trimap confusion) come from `ggc_eval_counts` on the MI355X,
 the ratios use the reference's formulas (+1e-8 denominators) on the host.
+
+Additive: `evaluate_matte` scores an alpha matte against the true one by the four errors of Rhemann et al. (CVPR 2009),
+SAD, MSE, gradient and connectivity; the sums come from `ggc_matte_errors`, the conventional scaling is done here.
 """
 from __future__ import annotations
 
@@ -135,6 +138,105 @@ def evaluate_batch(results: list[dict], device="cuda") -> dict:
     return {"mean_iou": float(np.mean(all_iou)), "std_iou": float(np.std(all_iou)),
             "mean_dice": float(np.mean(all_dice)), "std_dice": float(np.std(all_dice)),
             "mean_bf1": float(np.mean(all_bf1)), "std_bf1": float(np.std(all_bf1)), "n": len(results)}
+
+
+@dataclass
+class MatteMetrics:
+    """The four matte errors in their conventional units: sad = sum |a - g| / 1000, mse = mean (a - g)^2, grad = sum
+    (m(a) - m(g))^2 / 1000, conn = sum |phi(a) - phi(g)| / 1000, alpha in [0, 1], over the n_pixels counted pixels."""
+    sad: float
+    mse: float
+    grad: float
+    conn: float
+    n_pixels: int
+
+    def __str__(self) -> str:
+        return (f"SAD={self.sad:.4f}  MSE={self.mse:.6f}  Grad={self.grad:.4f}  Conn={self.conn:.4f}  "
+                f"N={self.n_pixels}")
+
+    def as_dict(self) -> dict:
+        return {"sad": self.sad, "mse": self.mse, "grad": self.grad, "conn": self.conn, "n_pixels": self.n_pixels}
+
+
+def matte_metrics_from_sums(sums, grad) -> MatteMetrics:
+    """Raw sums of ggc_matte_errors (n, SAD in 1/255, SSE in 1/255^2, CONN in 1/2550; GRAD) -> MatteMetrics."""
+    n, sad, sse, conn = (int(v) for v in sums)
+    return MatteMetrics(sad=sad / 255.0 / 1000.0, mse=sse / 65025.0 / n if n else 0.0, grad=float(grad) / 1000.0,
+                        conn=conn / 2550.0 / 1000.0, n_pixels=n)
+
+
+def _matte_levels(alpha, what: str) -> np.ndarray:
+    """uint8 levels as they are; floats in [0, 1] through pipeline.alpha_to_u8; anything else is a ValueError."""
+    from .pipeline import alpha_to_u8
+    a = np.asarray(alpha)
+    if a.dtype == np.uint8:
+        return a
+    if not np.issubdtype(a.dtype, np.floating):
+        raise ValueError(f"{what} must be uint8 levels or floats in [0, 1], got {a.dtype}")
+    if not np.isfinite(a).all():
+        raise ValueError(f"{what} holds a value that is not finite")
+    if a.size and (a.min() < 0.0 or a.max() > 1.0):
+        raise ValueError(f"{what} must lie in [0, 1], got [{a.min():g}, {a.max():g}]")
+    return alpha_to_u8(a)
+
+
+def _matte_inputs(alpha, gt_alpha, region):
+    """Checked (B,H,W) uint8 arrays of one call, and whether the input was a single (H,W) pair."""
+    a, g = _matte_levels(alpha, "alpha"), _matte_levels(gt_alpha, "gt_alpha")
+    if a.shape != g.shape:
+        raise ValueError(f"shape mismatch: alpha {a.shape} vs gt_alpha {g.shape}")
+    if a.ndim not in (2, 3):
+        raise ValueError(f"mattes must be (H,W) or (B,H,W), got {a.shape}")
+    r = None
+    if region is not None:
+        r = np.asarray(region)
+        if r.shape != a.shape:
+            raise ValueError(f"shape mismatch: region {r.shape} vs alpha {a.shape}")
+        r = (r != 0).astype(np.uint8)
+    single = a.ndim == 2
+    if single:
+        a, g, r = a[None], g[None], None if r is None else r[None]
+    from ._engine import check_matte_eval_args
+    check_matte_eval_args(a.shape, g.shape, None if r is None else r.shape)
+    return a, g, r, single
+
+
+def evaluate_matte(alpha, gt_alpha, region=None, device="cuda"):
+    """SAD, MSE, gradient and connectivity error of a matte against the true matte (Rhemann et al., CVPR 2009), on the
+    device (ggc_matte_errors, whose header entry states the definition).
+
+    alpha, gt_alpha: one (H, W) pair -> MatteMetrics, or a (B, H, W) stack -> a list of them; uint8 levels, or floats
+    in [0, 1], which are rounded to levels by pipeline.alpha_to_u8 (a float that is not finite or lies outside [0, 1] is
+    a ValueError).  region: nonzero = counted, the unknown part of a trimap in the benchmarks; it restricts the sums
+    only.  None counts every pixel."""
+    a, g, r, single = _matte_inputs(alpha, gt_alpha, region)
+    from ._engine import get_engine
+    eng = get_engine(device)
+    sums, grad, _ = eng.matte_errors(eng.to_device(np.ascontiguousarray(a)), eng.to_device(np.ascontiguousarray(g)),
+                                     None if r is None else eng.to_device(np.ascontiguousarray(r)))
+    sums, grad = sums.cpu().numpy(), grad.cpu().numpy()
+    out = [matte_metrics_from_sums(sums[i], grad[i]) for i in range(len(a))]
+    return out[0] if single else out
+
+
+def evaluate_matte_batch(results: list[dict], device="cuda") -> dict:
+    """Per-image MatteMetrics and their means over result dicts with "alpha" and "gt_alpha" (and optionally "region"),
+    mirroring evaluate_batch.  Equally sized pairs with the same kind of region are scored in one device call."""
+    groups: dict[tuple, list[int]] = {}
+    for i, r in enumerate(results):
+        groups.setdefault((np.asarray(r["alpha"]).shape, r.get("region") is not None), []).append(i)
+    per: dict[int, MatteMetrics] = {}
+    for (shape, has_region), idx in groups.items():
+        a = np.stack([_matte_levels(results[i]["alpha"], "alpha") for i in idx])
+        g = np.stack([_matte_levels(results[i]["gt_alpha"], "gt_alpha") for i in idx])
+        reg = np.stack([np.asarray(results[i]["region"]) for i in idx]) if has_region else None
+        for i, m in zip(idx, evaluate_matte(a, g, reg, device)):
+            per[i] = m
+    metrics = [per[i] for i in range(len(results))]
+    out = {"metrics": metrics, "n": len(metrics)}
+    for k in ("sad", "mse", "grad", "conn"):
+        out[f"mean_{k}"] = float(np.mean([getattr(m, k) for m in metrics])) if metrics else 0.0
+    return out
 
 
 def noc_summary(ious, targets=(0.85, 0.90), max_clicks: int = 20) -> dict:

@@ -21,7 +21,7 @@ import numpy as np
 
 from .grabcut import GrabCut, GrabCutConfig, Label
 from .graph_builder import GraphBuilder, SuperpixelGraphConfig, graphs_to_host, _check_image, pack_hints
-from .metrics import evaluate, evaluate_trimap, SegmentationMetrics, TrimapMetrics
+from .metrics import evaluate, evaluate_matte, evaluate_trimap, MatteMetrics, SegmentationMetrics, TrimapMetrics
 from .model import CLASS_BG, CLASS_FG, project_to_pixels  # noqa: F401
 
 
@@ -87,6 +87,13 @@ class SegmentationResult:
     def evaluate_against(self, gt_mask: np.ndarray) -> "tuple[SegmentationMetrics, TrimapMetrics]":
         """Segmentation and trimap metrics against a ground-truth mask (reference pipeline.py:62-68)."""
         return evaluate(self.binary_mask, gt_mask), evaluate_trimap(self.trimap, gt_mask)
+
+    def evaluate_matte_against(self, gt_alpha: np.ndarray, region: Optional[np.ndarray] = None) -> "MatteMetrics":
+        """SAD, MSE, gradient and connectivity error of this result's matte against the true matte (additive;
+        metrics.evaluate_matte).  gt_alpha: (H, W) uint8 levels or floats in [0, 1]; region: nonzero = counted."""
+        if self.alpha is None:
+            raise ValueError("this result carries no matte: segment with matte=True or a ClosedFormMatte")
+        return evaluate_matte(self.alpha, gt_alpha, region)
 
 
 def guided_filter(guide: np.ndarray, src: np.ndarray, radius: int = 8, eps: float = 1e-3, device="cuda") -> np.ndarray:

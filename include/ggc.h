@@ -38,6 +38,7 @@
  *                                 0..64, larger values are clamped to 64: a partial round never closes an image)
  *   GGC_AGG_DIRECT=1              GCNConv gather straight from L2 instead of the graph-resident kernel
  *   GGC_SLIC_SEQ_CONNECTIVITY=1   literal one-thread-per-image replay of skimage's connectivity pass (A/B reference)
+ *   GGC_MATTE_EVAL_LEVELS=1|2|5|10   threshold levels that ggc_matte_errors labels per pass (default: 10 while its maps fit 4 GiB, else 1)
  * The Python binding adds GGC_HIP_LIBRARY=<path> (load another build of the library, tools/build_variant.sh).
  */
 #ifndef GGC_H
@@ -50,7 +51,8 @@
 extern "C" {
 #endif
 
-#define GGC_VERSION 390 /* 0.3.9: ggc_estimate_foreground (foreground colours under an alpha matte: clean cut-outs, PCG on the device);
+#define GGC_VERSION 400 /* 0.4.0: ggc_matte_errors (SAD, MSE, gradient and connectivity error of an alpha matte against the true one);
+                           0.3.9: ggc_estimate_foreground (foreground colours under an alpha matte: clean cut-outs, PCG on the device);
                            0.3.8: ggc_closed_form_matte (closed-form alpha matte: matting Laplacian solved by PCG on the device);
                            0.3.7: ggc_upsample_matte (the matte's mask and alpha at a larger resolution: fast guided filter);
                            0.3.6: ggc_alpha_matte (soft alpha matte of a binary mask: colour guided-filter feathering);
@@ -548,6 +550,41 @@ int ggc_convert_color8(ggc_ctx* ctx, ggc_stream stream, int64_t n_pixels, const 
 int ggc_eval_counts(ggc_ctx* ctx, ggc_stream stream, int B, int H, int W,
                     const uint8_t* pred, const uint8_t* gt, const uint8_t* trimap, int boundary_width,
                     uint64_t* counts);
+
+/* R2 — the four errors of an alpha matte against the true matte (additive; Rhemann, Rother, Wang, Gelautz, Kohli and
+ * Rott, CVPR 2009, as the matting benchmarks report them), per image.  Both mattes are 8-bit levels, alpha = level / 255.
+ *   pred, gt [dev] u8 [B,H,W]: a (the matte under test) and g (the true matte)
+ *   region   [dev] u8 [B,H,W] or NULL: nonzero = counted (NULL: every pixel).  It restricts the SUMS only; the filter and
+ *            the components always see the whole image.  With R the counted pixels:
+ *   n     = |R|
+ *   SAD   = sum_R |a - g|                                             (integer, unit 1/255)
+ *   SSE   = sum_R (a - g)^2                                           (integer, unit 1/255^2)
+ *   CONN  for k = 1..10, S_k = {10 a >= 255 k} & {10 g >= 255 k} (integer compares: level >= k/10) and Omega_k the largest
+ *         4-CONNECTED component of S_k, among components of equal largest area the one that holds the smallest raster
+ *         index y*W + x; Omega_k is empty when S_k is.  lev(p) = (the smallest k >= 1 with p not in Omega_k) - 1, and 10
+ *         when there is none (the first failure: the Omega_k need not be nested).  d_a = 10 a - 255 lev,
+ *         d_g = 10 g - 255 lev (both >= 0: p is in Omega_lev), D(d) = d if d >= 383 else 0 (d / 2550 >= 0.15).
+ *         CONN = sum_R |D(d_a) - D(d_g)|                              (integer, unit 1/2550)
+ *   GRAD  sigma = 1.4, taps x = -4..4, G(x) = exp(-x^2 / 2 sigma^2) / (sigma sqrt(2 pi)), G'(x) = -x G(x) / sigma^2,
+ *         F_x[i][j] = G(i) G'(j) / N with N = sqrt(sum_ij (G(i) G'(j))^2), F_y its transpose; correlation of alpha in
+ *         float64 with the border replicated, m(u) = sqrt((F_x * u)^2 + (F_y * u)^2), GRAD = sum_R (m(a) - m(g))^2.  The
+ *         9 + 9 normalised taps are computed once on the host in float64 and passed to the kernel, which applies them
+ *         separably (rows, then columns).
+ *   sums   [dev] u64 [B,4] = n, SAD, SSE, CONN
+ *   grad   [dev] f64 [B] = GRAD, or NULL: the filter is not run
+ *   levels [dev] u8  [B,H,W] = lev, 0..10, or NULL
+ * Conventional reporting (the host's business): sad = SAD / 255 / 1000, mse = SSE / 255^2 / n, grad = GRAD / 1000,
+ * conn = CONN / 2550 / 1000.
+ * B == 0 does nothing; B > 65535, H or W outside 1..32768 or H*W >= 2^31: GGC_E_SHAPE; pred, gt or sums NULL:
+ * GGC_E_INVALID_ARG.  The integer sums use integer atomics, one set per block; GRAD uses none: fixed tiles, a fixed tree
+ * per tile, the tiles of an image added in a fixed order.  Every image's five outputs and its levels equal its
+ * single-image call bit for bit, and two runs are identical.  Scratch from the context: 8 L + 1 bytes per pixel (8 L when
+ * `levels` is given), 80 bytes per image and, with `grad`, 8 bytes per 16 x 16 tile; L, the levels labelled per pass, is 10
+ * (81 bytes per pixel) while 80 bytes x B x H x W is at most 4 GiB, else 1 (9 bytes per pixel), unless GGC_MATTE_EVAL_LEVELS
+ * fixes it; the results do not depend on it.  Does not synchronise and reads nothing back on the host. */
+int ggc_matte_errors(ggc_ctx* ctx, ggc_stream stream, int B, int H, int W,
+                     const uint8_t* pred, const uint8_t* gt, const uint8_t* region,
+                     uint64_t* sums, double* grad, uint8_t* levels);
 
 /* D0 — per-region ground-truth coverage for the graph-cache writer: the integer sums behind
  * derive_trimap_labels and prepare_sample's fg_ratio (dataset.py:194-206, 245-248):
