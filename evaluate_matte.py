@@ -4,12 +4,15 @@ evaluate_matte.py — how good an alpha matte is: SAD, MSE, gradient and connect
     python3 evaluate_matte.py --pred out/alphas --alphas data/alphas --trimaps data/trimaps
     python3 evaluate_matte.py --images data/images --masks data/masks --alphas data/alphas --method closed-form --cf-band 2
     python3 evaluate_matte.py --images imgs --masks masks --alphas gts --method guided --matte-radius 6 --json guided6.json
+    python3 evaluate_matte.py --images data/images --trimaps data/trimaps --alphas data/alphas --method trimap
 
 The four errors of Rhemann et al. (CVPR 2009) as the matting benchmarks report them, computed on the device
 (gcn_grabcut.evaluate_matte).  Either --pred names a directory of saved mattes (8-bit, what
 `inference.py --save alpha` writes), or --images and --masks name colour images and binary masks from which --method
 makes the matte on the device: `mask` scores the hard mask itself, `guided` the guided-filter matte, `closed-form` the
-closed-form matte.  Files are matched by stem with --alphas, the true mattes (8-bit grey).  With --trimaps only the pixels
+closed-form matte.  `--method trimap` takes --images and --trimaps and no --masks: each image's matte is solved from its
+trimap (255 foreground, 0 background, else unknown; gcn_grabcut.trimap_matte) and scored on that trimap's unknown
+region.  Files are matched by stem with --alphas, the true mattes (8-bit grey).  With --trimaps only the pixels
 whose trimap byte is neither 0 nor 255 are counted.  Images of one size are scored as one batch.
 """
 import argparse
@@ -30,8 +33,8 @@ def build_parser() -> argparse.ArgumentParser:
     parser.add_argument("--images", default=None, help="Directory of colour images (with --masks and --method)")
     parser.add_argument("--masks", default=None, help="Directory of binary masks (> 127 = foreground)")
     parser.add_argument("--trimaps", default=None, help="Directory of trimaps: count only bytes that are neither 0 nor 255")
-    parser.add_argument("--method", choices=["mask", "guided", "closed-form"], default="guided",
-                        help="How the matte is made from --images and --masks")
+    parser.add_argument("--method", choices=["mask", "guided", "closed-form", "trimap"], default="guided",
+                        help="How the matte is made from --images and --masks (trimap: from --images and --trimaps)")
     parser.add_argument("--matte-radius", type=int, default=4, help="Window radius of the guided matte, 1..64")
     parser.add_argument("--matte-eps", type=float, default=1e-4, help="Regularisation of the guided matte (>= 1e-12)")
     parser.add_argument("--cf-radius", type=int, default=1, help="Window radius of the closed-form matte, 1..8")
@@ -69,6 +72,8 @@ def collect(args) -> list:
     must exist and have the true matte's size."""
     truth = _by_stem(args.alphas, "--alphas")
     dirs = {"pred": args.pred} if args.pred else {"image": args.images, "mask": args.masks}
+    if args.method == "trimap" and not args.pred:
+        del dirs["mask"]
     if args.trimaps:
         dirs["trimap"] = args.trimaps
     flags = {"pred": "--pred", "image": "--images", "mask": "--masks", "trimap": "--trimaps"}
@@ -90,20 +95,23 @@ def collect(args) -> list:
                                  f"{item['gt'].shape[1]}x{item['gt'].shape[0]}")
             item[kind] = a
         if "trimap" in item:
-            t = item.pop("trimap")
+            t = item["trimap"]
             item["region"] = ((t != 0) & (t != 255)).astype(np.uint8)
         items.append(item)
     return items
 
 
 def make_mattes(args, eng, images: np.ndarray, masks: np.ndarray):
-    """(B,H,W) uint8 levels on the device of the chosen method's matte of masks (B,H,W) {0,1} under images."""
+    """(B,H,W) uint8 levels on the device of the chosen method's matte of masks (B,H,W) {0,1} under images; for the
+    trimap method, masks holds the trimaps' bytes."""
     import torch
     m = eng.to_device(np.ascontiguousarray(masks))
     if args.method == "mask":
         return m * 255
     bgr = eng.to_device(np.ascontiguousarray(images))
-    if args.method == "guided":
+    if args.method == "trimap":
+        alpha = eng.trimap_matte(bgr, m, args.cf_radius, args.cf_eps, args.cf_iters, args.cf_tol)[0]
+    elif args.method == "guided":
         alpha = eng.alpha_matte(bgr, m, args.matte_radius, args.matte_eps)
     else:
         alpha = eng.closed_form_matte(bgr, m, args.cf_radius, args.cf_eps, args.cf_band, args.cf_iters, args.cf_tol)[0]
@@ -117,7 +125,12 @@ def main() -> None:
     from_masks = args.images is not None or args.masks is not None
     if from_files == from_masks:
         parser.error("give either --pred, or --images and --masks")
-    if from_masks and (args.images is None or args.masks is None):
+    by_trimap = from_masks and args.method == "trimap"
+    if by_trimap and args.masks is not None:
+        parser.error("--method trimap makes the matte from --images and --trimaps: drop --masks")
+    if by_trimap and (args.images is None or args.trimaps is None):
+        parser.error("--method trimap needs --images and --trimaps")
+    if from_masks and not by_trimap and (args.images is None or args.masks is None):
         parser.error("--images and --masks go together")
     if args.batch < 1:
         parser.error("--batch must be >= 1")
@@ -128,6 +141,8 @@ def main() -> None:
             check_matte_args(args.matte_radius, args.matte_eps)
         if from_masks and args.method == "closed-form":
             check_closed_form_args(args.cf_radius, args.cf_eps, args.cf_band, args.cf_iters, args.cf_tol)
+        if by_trimap:
+            check_closed_form_args(args.cf_radius, args.cf_eps, 0, args.cf_iters, args.cf_tol)
     except ValueError as e:
         parser.error(str(e))
 
@@ -135,7 +150,7 @@ def main() -> None:
     by_shape: dict = {}
     for it in items:
         by_shape.setdefault(it["gt"].shape, []).append(it)
-    if from_masks and args.method == "closed-form":
+    if from_masks and args.method in ("closed-form", "trimap"):
         for h, w in by_shape:
             try:
                 check_closed_form_shape(h, w, args.cf_radius)
@@ -152,7 +167,8 @@ def main() -> None:
                 pred = eng.to_device(np.stack([c["pred"] for c in chunk]))
             else:
                 pred = make_mattes(args, eng, np.stack([c["image"] for c in chunk]),
-                                   np.stack([(c["mask"] > 127).astype(np.uint8) for c in chunk]))
+                                   np.stack([c["trimap"] if by_trimap else (c["mask"] > 127).astype(np.uint8)
+                                             for c in chunk]))
             region = eng.to_device(np.stack([c["region"] for c in chunk])) if args.trimaps else None
             sums, grad, _ = eng.matte_errors(pred, gt, region)
             sums, grad = sums.cpu().numpy(), grad.cpu().numpy()
@@ -160,7 +176,8 @@ def main() -> None:
                 metrics[c["name"]] = matte_metrics_from_sums(sums[j], grad[j])
 
     names = [it["name"] for it in items]
-    what = f"mattes of {args.pred}" if from_files else f"{args.method} mattes of the masks of {args.masks}"
+    what = (f"mattes of {args.pred}" if from_files else f"trimap mattes of the trimaps of {args.trimaps}" if by_trimap
+            else f"{args.method} mattes of the masks of {args.masks}")
     print(f"{TAG} {len(names)} image(s), {what}" + (", unknown region of the trimaps" if args.trimaps else ""))
     width = max(len(n) for n in names + ["mean"])
     print(f"  {'name':<{width}}  {'SAD':>10}  {'MSE':>12}  {'Grad':>10}  {'Conn':>10}  {'pixels':>9}")

@@ -1,11 +1,18 @@
-// ggc_cfmatte.hip — O3: closed-form alpha matte (Levin, Lischinski and Weiss, TPAMI 2008) of a binary mask, solved on
-// the device by Jacobi-preconditioned conjugate gradients with the matting Laplacian applied without a matrix (He, Sun
-// and Tang, CVPR 2010).  include/ggc.h states the system; DESIGN.md §5.13 the tiling and the bytes.
+// ggc_cfmatte.hip — O3, O3t: closed-form alpha matte (Levin, Lischinski and Weiss, TPAMI 2008) of a binary mask or of a
+// caller's trimap, solved on the device by Jacobi-preconditioned conjugate gradients with the matting Laplacian applied
+// without a matrix (He, Sun and Tang, CVPR 2010).  include/ggc.h states the systems; DESIGN.md §5.13 the tiling and the
+// bytes, §5.16 the trimap entry.
 //
-// Layout.  A tile is 16 x 16 pixels of one image and a block of 256 threads, one per pixel.  The unknown band U is found
-// over the whole frame once per call (k_cf_edge, k_cf_dilate_h, k_cf_dilate_v, which also counts U per tile); the host
-// reads the counts and lists the tiles that hold U or touch a tile that does (every window centre within r <= 16 of U),
-// image by image.  Every later kernel runs over that list only.  Per listed tile and iteration:
+// One solver, two front ends.  A front end says which pixels are unknown (U), what the known ones are and where the
+// unknown ones start: it writes the flag plane (F_M = the known value, F_U = unknown), the start x on U, and the
+// number of U pixels of every tile.  ggc_closed_form_matte's is the band around the mask's edge, started at the mask
+// (k_cf_edge, k_cf_dilate_h, k_cf_dilate_v); ggc_trimap_matte's reads the trimap's bytes and the caller's start
+// (k_cf_trimap).  Everything after that (cf_solve) is shared.
+//
+// Layout.  A tile is 16 x 16 pixels of one image and a block of 256 threads, one per pixel.  U is found over the whole
+// frame once per call by the front end; the host reads the counts and lists the tiles that hold U or touch a tile that
+// does (every window centre within r <= 16 of U), image by image.  Every later kernel runs over that list only.  Per
+// listed tile and iteration:
 //   k_cf_window  a_k, b_k of the p of the product at every centre k in K of the tile (p staged with an r halo in LDS)
 //   k_cf_pixel   (L p)_i = c_i p_i - sum_k (a_k . I_i + b_k) on U (a, b staged with an r halo in LDS); per-tile d . q
 //   k_cf_alpha   per image: alpha = rz / (d . q)
@@ -31,7 +38,7 @@ constexpr int CF_RMAX = 8;
 constexpr int CF_SMAX = CF_T + 2 * CF_RMAX;       // staged side at the largest radius
 constexpr int CF_POLL = 8;                        // iterations between polls of the converged count
 
-constexpr uint8_t F_M = 1, F_U = 2;               // flags: mask value, unknown
+constexpr uint8_t F_M = 1, F_U = 2;               // flags: known value (meaningful off U), unknown
 
 struct alignas(8) CfStats { double mu[3]; double d00, d01, d02, d11, d12, d22; };   // Delta^-1, symmetric
 struct alignas(32) CfAB { double a0, a1, a2, b; };
@@ -42,7 +49,7 @@ struct CfImage {                                  // per-image solver state
 
 __device__ __forceinline__ double colour(const uint8_t* px, int c) { return (double)px[c] * (1.0 / 255.0); }
 
-// ---------------------------------------------------------------- the band, over the whole frame
+// ---------------------------------------------------------------- front end of the mask: the band, over the whole frame
 // grid (cdiv(W, 16), cdiv(H, 16), B), 16 x 16 threads
 __global__ void __launch_bounds__(CF_THREADS) k_cf_edge(int H, int W, const uint8_t* __restrict__ binary,
                                                         uint8_t* __restrict__ edge) {
@@ -71,10 +78,21 @@ __global__ void __launch_bounds__(CF_THREADS) k_cf_dilate_h(int H, int W, int ba
     out[(size_t)blockIdx.z * H * W + (size_t)y * W + x] = v;
 }
 
-// flags = m | U << 1; tile_u [B, tiles] = pixels of U in each tile (a block is a tile)
+// tile_u of the block's tile = the sum of the block's u, a fixed LDS tree
+__device__ __forceinline__ void count_tile(int u, int* s_cnt, int tid, int32_t* __restrict__ tile_u) {
+    s_cnt[tid] = u;
+    __syncthreads();
+    for (int s = CF_THREADS / 2; s > 0; s >>= 1) {
+        if (tid < s) s_cnt[tid] += s_cnt[tid + s];
+        __syncthreads();
+    }
+    if (tid == 0) tile_u[((size_t)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x] = s_cnt[0];
+}
+
+// flags = m | U << 1; start = m on U; tile_u [B, tiles] = pixels of U in each tile (a block is a tile)
 __global__ void __launch_bounds__(CF_THREADS) k_cf_dilate_v(int H, int W, int band, const uint8_t* __restrict__ hdil,
                                                             const uint8_t* __restrict__ binary, uint8_t* __restrict__ flags,
-                                                            int32_t* __restrict__ tile_u) {
+                                                            double* __restrict__ start, int32_t* __restrict__ tile_u) {
     __shared__ int s_cnt[CF_THREADS];
     const int tid = threadIdx.y * CF_T + threadIdx.x;
     const int x = blockIdx.x * CF_T + threadIdx.x, y = blockIdx.y * CF_T + threadIdx.y;
@@ -84,16 +102,39 @@ __global__ void __launch_bounds__(CF_THREADS) k_cf_dilate_v(int H, int W, int ba
         uint8_t v = 0;
         for (int yy = max(0, y - band); yy <= min(H - 1, y + band); ++yy) v |= hdil[base + (size_t)yy * W + x];
         const size_t i = base + (size_t)y * W + x;
-        flags[i] = (binary[i] != 0 ? F_M : 0) | (v ? F_U : 0);
+        const bool m = binary[i] != 0;
+        flags[i] = (m ? F_M : 0) | (v ? F_U : 0);
+        if (v) start[i] = m ? 1.0 : 0.0;
         u = v ? 1 : 0;
     }
-    s_cnt[tid] = u;
-    __syncthreads();
-    for (int s = CF_THREADS / 2; s > 0; s >>= 1) {
-        if (tid < s) s_cnt[tid] += s_cnt[tid + s];
-        __syncthreads();
+    count_tile(u, s_cnt, tid, tile_u);
+}
+
+// ---------------------------------------------------------------- front end of the trimap, over the whole frame
+// 255 is foreground, 0 background, every other byte unknown.  flags as above; the start x on U = alpha0 clamped to
+// [0, 1] (a NaN reads as 0), or 0.5 without alpha0; tile_u as above
+__global__ void __launch_bounds__(CF_THREADS) k_cf_trimap(int H, int W, const uint8_t* __restrict__ trimap,
+                                                          const float* __restrict__ alpha0, uint8_t* __restrict__ flags,
+                                                          double* __restrict__ x, int32_t* __restrict__ tile_u) {
+    __shared__ int s_cnt[CF_THREADS];
+    const int tid = threadIdx.y * CF_T + threadIdx.x;
+    const int xp = blockIdx.x * CF_T + threadIdx.x, yp = blockIdx.y * CF_T + threadIdx.y;
+    int u = 0;
+    if (xp < W && yp < H) {
+        const size_t i = (size_t)blockIdx.z * H * W + (size_t)yp * W + xp;
+        const uint8_t t = trimap[i];
+        u = t != 0 && t != 255 ? 1 : 0;
+        flags[i] = (t == 255 ? F_M : 0) | (u ? F_U : 0);
+        if (u) {
+            double a = 0.5;
+            if (alpha0) {
+                a = (double)alpha0[i];
+                a = !(a >= 0.0) ? 0.0 : (a > 1.0 ? 1.0 : a);
+            }
+            x[i] = a;
+        }
     }
-    if (tid == 0) tile_u[((size_t)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x] = s_cnt[0];
+    count_tile(u, s_cnt, tid, tile_u);
 }
 
 // ---------------------------------------------------------------- per listed tile
@@ -137,10 +178,10 @@ __global__ void __launch_bounds__(CF_THREADS) k_cf_stats(int H, int W, int r, do
     stats[(size_t)t.b * H * W + (size_t)y * W + x] = st;
 }
 
-// SETUP: p = the mask on every pixel; else p = d on U and 0 elsewhere
+// SETUP: p = the start image (d is x: the start on U, the known value elsewhere); else p = d on U and 0 elsewhere
 template <bool SETUP>
 __device__ __forceinline__ double p_value(uint8_t f, const double* __restrict__ d, size_t i) {
-    if constexpr (SETUP) return (f & F_M) ? 1.0 : 0.0;
+    if constexpr (SETUP) return (f & F_U) ? d[i] : ((f & F_M) ? 1.0 : 0.0);
     else return (f & F_U) ? d[i] : 0.0;
 }
 
@@ -198,14 +239,14 @@ __device__ __forceinline__ double block_sum(double v, double* s, int tid) {
     return s[0];
 }
 
-// q = (L p) on U.  SETUP: p = m; r = -q, x = m, diag L, and the per-tile r . z, r . r (into part_a, part_b); else the
-// per-tile d . q (into part_a)
+// q = (L p) on U.  SETUP: p = the start image (d is x); r = -q, diag L, and the per-tile r . z, r . r (into part_a,
+// part_b); else the per-tile d . q (into part_a)
 template <bool SETUP>
 __global__ void __launch_bounds__(CF_THREADS) k_cf_pixel(int H, int W, int r, int ntx, const int2* __restrict__ tiles,
                                                          const CfImage* __restrict__ img, const uint8_t* __restrict__ bgr,
                                                          const uint8_t* __restrict__ flags, const CfStats* __restrict__ stats,
                                                          const CfAB* __restrict__ ab, const double* __restrict__ d,
-                                                         double* __restrict__ q, double* __restrict__ res, double* __restrict__ x,
+                                                         double* __restrict__ q, double* __restrict__ res,
                                                          double* __restrict__ diag, double* __restrict__ part_a,
                                                          double* __restrict__ part_b) {
     __shared__ CfAB s_ab[CF_SMAX * CF_SMAX];
@@ -254,7 +295,6 @@ __global__ void __launch_bounds__(CF_THREADS) k_cf_pixel(int H, int W, int r, in
                 const double ri = -qi;
                 diag[i] = dg;
                 res[i] = ri;
-                x[i] = pi;
                 va = ri * (ri / dg);
                 vb = ri * ri;
             } else {
@@ -297,7 +337,7 @@ __global__ void __launch_bounds__(WAVE) k_cf_scalar(int max_iter, double tol, Cf
         s.rr0 = b;
         s.rel = 0.0;
         s.iters = 0;
-        if (!(b > 0.0)) { s.done = 1; atomicAdd(n_done, 1); }    // (L m)_U = 0: m already solves the system
+        if (!(b > 0.0)) { s.done = 1; atomicAdd(n_done, 1); }    // r_0 = 0: the start already solves the system
     } else if (MODE == 1) {
         if (a > 0.0 && std::isfinite(a)) {
             s.alpha = s.rz / a;
@@ -364,7 +404,8 @@ __global__ void __launch_bounds__(CF_THREADS) k_cf_direction(int H, int W, int n
     d[i] = SETUP ? z : z + s.beta * d[i];
 }
 
-// the outputs over the whole frame: alpha = x on U of a solved image, m elsewhere.  grid (cdiv(H*W, 256), B)
+// the outputs over the whole frame: alpha = x on U (the start where nothing was solved), the known value elsewhere.
+// grid (cdiv(H*W, 256), B)
 __global__ void __launch_bounds__(CF_THREADS) k_cf_output(int H, int W, const CfImage* __restrict__ img,
                                                           const uint8_t* __restrict__ bgr, const uint8_t* __restrict__ flags,
                                                           const double* __restrict__ x, float* __restrict__ alpha,
@@ -381,7 +422,7 @@ __global__ void __launch_bounds__(CF_THREADS) k_cf_output(int H, int W, const Cf
     if (j >= P) return;
     const size_t i = (size_t)b * P + j;
     const uint8_t f = flags[i];
-    const double a = (s.tile_hi > s.tile_lo && (f & F_U)) ? x[i] : ((f & F_M) ? 1.0 : 0.0);
+    const double a = (f & F_U) ? x[i] : ((f & F_M) ? 1.0 : 0.0);
     if (raw) raw[i] = a;
     const double c = a < 0.0 ? 0.0 : (a > 1.0 ? 1.0 : a);
     if (alpha) alpha[i] = (float)c;
@@ -396,14 +437,15 @@ __global__ void __launch_bounds__(CF_THREADS) k_cf_output(int H, int W, const Cf
 
 using namespace ggc;
 
-extern "C" int ggc_closed_form_matte(ggc_ctx* ctx, ggc_stream stream, int B, int H, int W, const uint8_t* bgr,
-                                     const uint8_t* binary, int radius, float eps, int band, int max_iter, float tol,
-                                     float* alpha, uint8_t* rgba, double* raw, int32_t* iters, double* rel_residual) {
-    if (!ctx) return GGC_E_INVALID_ARG;
+namespace {
+
+// the argument ranges the two entries share, in the order they are reported (the trimap entry has no band: it passes 0)
+int cf_check(ggc_ctx* ctx, int B, int H, int W, const void* bgr, const void* guide, int radius, float eps, int band,
+             int max_iter, float tol, bool any_output) {
     GGC_REQUIRE(ctx, B >= 0 && B <= 65535 && H >= 1 && W >= 1 && H <= 32768 && W <= 32768, GGC_E_SHAPE,
                 "bad shape B=%d H=%d W=%d", B, H, W);
-    GGC_REQUIRE(ctx, alpha || rgba || raw || iters || rel_residual, GGC_E_INVALID_ARG, "null pointer: no output asked for");
-    GGC_REQUIRE(ctx, B == 0 || (bgr && binary), GGC_E_INVALID_ARG, "null pointer");
+    GGC_REQUIRE(ctx, any_output, GGC_E_INVALID_ARG, "null pointer: no output asked for");
+    GGC_REQUIRE(ctx, B == 0 || (bgr && guide), GGC_E_INVALID_ARG, "null pointer");
     GGC_REQUIRE(ctx, radius >= 1 && radius <= CF_RMAX, GGC_E_INVALID_ARG, "closed-form radius %d outside 1..%d", radius, CF_RMAX);
     GGC_REQUIRE(ctx, std::isfinite(eps) && eps >= 1e-12f && eps <= 1.0f, GGC_E_INVALID_ARG,
                 "closed-form eps %g outside [1e-12, 1]", (double)eps);
@@ -414,41 +456,53 @@ extern "C" int ggc_closed_form_matte(ggc_ctx* ctx, ggc_stream stream, int B, int
                 "closed-form tol %g outside [1e-12, 1)", (double)tol);
     GGC_REQUIRE(ctx, H >= 2 * radius + 1 && W >= 2 * radius + 1, GGC_E_SHAPE,
                 "closed-form matte needs H, W >= 2r+1 = %d, got %dx%d", 2 * radius + 1, H, W);
-    if (B == 0) return GGC_OK;
+    return GGC_OK;
+}
+
+// what a front end fills in: the flag plane, the start on U, the U count of every tile (and two byte planes of its own)
+struct CfFront { uint8_t *flags, *edge, *hdil; double* x; int32_t* tile_u; };
+
+// The solver behind both entries.  front(f, fgrid, tblk) launches the front end's kernels on st; n_byte_planes is 1
+// (flags) plus the byte planes the front end needs for itself.
+template <class Front>
+int cf_solve(ggc_ctx* ctx, hipStream_t st, const char* name, int B, int H, int W, const uint8_t* bgr, int n_byte_planes,
+             int radius, float eps, int max_iter, float tol, float* alpha, uint8_t* rgba, double* raw, int32_t* iters,
+             double* rel_residual, Front&& front) {
     GGC_HIP(ctx, hipSetDevice(ctx->device));
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const size_t P = (size_t)B * H * W;
     const int ntx = cdiv(W, CF_T), nty = cdiv(H, CF_T), nt = ntx * nty;
-    uint8_t *flags = nullptr, *edge = nullptr, *hdil = nullptr;
-    int32_t* tile_u = nullptr;
+    CfFront f{nullptr, nullptr, nullptr, nullptr, nullptr};
     CfImage* img = nullptr;
     int* n_done = nullptr;
     CfStats* stats = nullptr;
     CfAB* ab = nullptr;
-    double *x = nullptr, *res = nullptr, *d = nullptr, *q = nullptr, *diag = nullptr;
+    double *res = nullptr, *d = nullptr, *q = nullptr, *diag = nullptr;
     int2* tiles = nullptr;
     double *part_a = nullptr, *part_b = nullptr;
-    // the per-pixel arrays (147 bytes per pixel) and the per-tile, per-image ones, sized for every tile of the batch
+    // the per-pixel arrays (144 bytes per pixel and the byte planes) and the per-tile, per-image ones, sized for every
+    // tile of the batch
     const size_t n_tiles_max = (size_t)B * nt;
     if (!carve_scratch(ctx, S_CFMATTE, [&](Carve& c) {
-            flags = c.take<uint8_t>(P); edge = c.take<uint8_t>(P); hdil = c.take<uint8_t>(P);
+            f.flags = c.take<uint8_t>(P);
+            f.edge = c.take<uint8_t>(n_byte_planes > 1 ? P : 0); f.hdil = c.take<uint8_t>(n_byte_planes > 2 ? P : 0);
             stats = c.take<CfStats>(P); ab = c.take<CfAB>(P);
-            x = c.take<double>(P); res = c.take<double>(P); d = c.take<double>(P); q = c.take<double>(P);
+            f.x = c.take<double>(P); res = c.take<double>(P); d = c.take<double>(P); q = c.take<double>(P);
             diag = c.take<double>(P);
-            tile_u = c.take<int32_t>(n_tiles_max); tiles = c.take<int2>(n_tiles_max);
+            f.tile_u = c.take<int32_t>(n_tiles_max); tiles = c.take<int2>(n_tiles_max);
             part_a = c.take<double>(n_tiles_max); part_b = c.take<double>(n_tiles_max);
             img = c.take<CfImage>(B); n_done = c.take<int>(1);
         }))
         return GGC_E_OOM;
-    ProfScope prof(ctx, st, "closed_form_matte");
+    ProfScope prof(ctx, st, name);
     const dim3 fgrid(ntx, nty, B), tblk(CF_T, CF_T);
-    hipLaunchKernelGGL(k_cf_edge, fgrid, tblk, 0, st, H, W, binary, edge);
-    hipLaunchKernelGGL(k_cf_dilate_h, fgrid, tblk, 0, st, H, W, band, edge, hdil);
-    hipLaunchKernelGGL(k_cf_dilate_v, fgrid, tblk, 0, st, H, W, band, hdil, binary, flags, tile_u);
+    uint8_t* const flags = f.flags;
+    double* const x = f.x;
+    int32_t* const tile_u = f.tile_u;
+    front(f, fgrid, tblk);
     GGC_LAUNCH_CHECK(ctx);
 
     // the tile list, image by image: tiles with U and their eight neighbours (r <= 16 = the tile side).  An image whose
-    // band is empty or covers every pixel gets no tiles: alpha = m, 0 iterations.
+    // U is empty or covers every pixel (nothing anchors it) gets no tiles: alpha = the start, 0 iterations.
     std::vector<int32_t> cnt(n_tiles_max);
     GGC_HIP(ctx, hipMemcpyAsync(cnt.data(), tile_u, n_tiles_max * sizeof(int32_t), hipMemcpyDeviceToHost, st));
     GGC_HIP(ctx, hipStreamSynchronize(st));
@@ -486,9 +540,9 @@ extern "C" int ggc_closed_form_matte(ggc_ctx* ctx, ggc_stream stream, int B, int
         const double e = (double)eps, tl = (double)tol;
         hipLaunchKernelGGL(k_cf_stats, dim3(n_list), tblk, 0, st, H, W, radius, e, ntx, tiles, bgr, stats);
         hipLaunchKernelGGL(k_cf_window<true>, dim3(n_list), tblk, 0, st, H, W, radius, ntx, tiles, img, bgr, flags, stats,
-                           d, ab);
+                           x, ab);
         hipLaunchKernelGGL(k_cf_pixel<true>, dim3(n_list), tblk, 0, st, H, W, radius, ntx, tiles, img, bgr, flags, stats, ab,
-                           d, q, res, x, diag, part_a, part_b);
+                           x, q, res, diag, part_a, part_b);
         hipLaunchKernelGGL(k_cf_scalar<0>, dim3(B), dim3(WAVE), 0, st, max_iter, tl, img, part_a, part_b, n_done);
         hipLaunchKernelGGL(k_cf_direction<true>, dim3(n_list), tblk, 0, st, H, W, ntx, tiles, img, flags, res, diag, d);
         GGC_LAUNCH_CHECK(ctx);
@@ -496,7 +550,7 @@ extern "C" int ggc_closed_form_matte(ggc_ctx* ctx, ggc_stream stream, int B, int
             hipLaunchKernelGGL(k_cf_window<false>, dim3(n_list), tblk, 0, st, H, W, radius, ntx, tiles, img, bgr, flags,
                                stats, d, ab);
             hipLaunchKernelGGL(k_cf_pixel<false>, dim3(n_list), tblk, 0, st, H, W, radius, ntx, tiles, img, bgr, flags,
-                               stats, ab, d, q, res, x, diag, part_a, part_b);
+                               stats, ab, d, q, res, diag, part_a, part_b);
             hipLaunchKernelGGL(k_cf_scalar<1>, dim3(B), dim3(WAVE), 0, st, max_iter, tl, img, part_a, part_b, n_done);
             hipLaunchKernelGGL(k_cf_update, dim3(n_list), tblk, 0, st, H, W, ntx, tiles, img, flags, d, q, diag, x, res,
                                part_a, part_b);
@@ -515,4 +569,39 @@ extern "C" int ggc_closed_form_matte(ggc_ctx* ctx, ggc_stream stream, int B, int
                        rel_residual);
     GGC_LAUNCH_CHECK(ctx);
     return GGC_OK;
+}
+
+} // namespace
+
+extern "C" int ggc_closed_form_matte(ggc_ctx* ctx, ggc_stream stream, int B, int H, int W, const uint8_t* bgr,
+                                     const uint8_t* binary, int radius, float eps, int band, int max_iter, float tol,
+                                     float* alpha, uint8_t* rgba, double* raw, int32_t* iters, double* rel_residual) {
+    if (!ctx) return GGC_E_INVALID_ARG;
+    if (int e = cf_check(ctx, B, H, W, bgr, binary, radius, eps, band, max_iter, tol,
+                         alpha || rgba || raw || iters || rel_residual))
+        return e;
+    if (B == 0) return GGC_OK;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    return cf_solve(ctx, st, "closed_form_matte", B, H, W, bgr, 3, radius, eps, max_iter, tol, alpha, rgba, raw, iters,
+                    rel_residual, [&](const CfFront& f, dim3 fgrid, dim3 tblk) {
+                        hipLaunchKernelGGL(k_cf_edge, fgrid, tblk, 0, st, H, W, binary, f.edge);
+                        hipLaunchKernelGGL(k_cf_dilate_h, fgrid, tblk, 0, st, H, W, band, f.edge, f.hdil);
+                        hipLaunchKernelGGL(k_cf_dilate_v, fgrid, tblk, 0, st, H, W, band, f.hdil, binary, f.flags, f.x,
+                                           f.tile_u);
+                    });
+}
+
+extern "C" int ggc_trimap_matte(ggc_ctx* ctx, ggc_stream stream, int B, int H, int W, const uint8_t* bgr,
+                                const uint8_t* trimap, int radius, float eps, int max_iter, float tol, const float* alpha0,
+                                float* alpha, uint8_t* rgba, double* raw, int32_t* iters, double* rel_residual) {
+    if (!ctx) return GGC_E_INVALID_ARG;
+    if (int e = cf_check(ctx, B, H, W, bgr, trimap, radius, eps, 0, max_iter, tol,
+                         alpha || rgba || raw || iters || rel_residual))
+        return e;
+    if (B == 0) return GGC_OK;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    return cf_solve(ctx, st, "trimap_matte", B, H, W, bgr, 1, radius, eps, max_iter, tol, alpha, rgba, raw, iters,
+                    rel_residual, [&](const CfFront& f, dim3 fgrid, dim3 tblk) {
+                        hipLaunchKernelGGL(k_cf_trimap, fgrid, tblk, 0, st, H, W, trimap, alpha0, f.flags, f.x, f.tile_u);
+                    });
 }

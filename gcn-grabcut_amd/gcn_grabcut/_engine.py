@@ -331,6 +331,38 @@ class Engine:
                       iters.data_ptr(), rel.data_ptr())
         return (alpha, rgba, iters, rel) if want_rgba else (alpha, iters, rel)
 
+    def trimap_matte(self, bgr, trimap, radius, eps, max_iter, tol, alpha0=None, want_rgba=False, out=None):
+        """Closed-form alpha matte of bgr (B,H,W,3) uint8 on the unknown region of trimap (B,H,W) uint8: 255 foreground,
+        0 background, every other byte unknown (ggc_trimap_matte).  alpha0 (B,H,W) float32 or None: where the unknown
+        pixels start (clamped to [0, 1]; 0.5 without it).  -> (alpha (B,H,W) float32 in [0,1], iters (B,) int32,
+        rel_residual (B,) float64), with want_rgba also rgba (B,H,W,4) uint8 after alpha; out: (alpha, rgba or None),
+        preallocated.  The call synchronises its stream."""
+        check_closed_form_args(radius, eps, 0, max_iter, tol)
+        b, h, w, _ = bgr.shape
+        if tuple(trimap.shape) != (b, h, w):
+            raise ValueError(f"trimap_matte: trimap {tuple(trimap.shape)} does not match bgr {tuple(bgr.shape)}")
+        if trimap.dtype != torch.uint8:
+            raise ValueError(f"trimap_matte: trimap must be uint8, got {trimap.dtype}")
+        if alpha0 is not None:
+            if tuple(alpha0.shape) != (b, h, w):
+                raise ValueError(f"trimap_matte: alpha0 {tuple(alpha0.shape)} does not match bgr {tuple(bgr.shape)}")
+            if alpha0.dtype != torch.float32:
+                raise ValueError(f"trimap_matte: alpha0 must be float32, got {alpha0.dtype}")
+            alpha0 = alpha0.contiguous()
+        check_closed_form_shape(h, w, radius)
+        if out is not None:
+            alpha, rgba = out
+        else:
+            alpha = self.empty(b, h, w)
+            rgba = self.empty(b, h, w, 4, dtype=torch.uint8) if want_rgba else None
+        iters = self.empty(b, dtype=torch.int32)
+        rel = self.empty(b, dtype=torch.float64)
+        trimap = trimap.contiguous()
+        self.ctx.call("ggc_trimap_matte", self._stream(), b, h, w, bgr.data_ptr(), trimap.data_ptr(), int(radius),
+                      float(eps), int(max_iter), float(tol), _native.ptr(alpha0), _native.ptr(alpha), _native.ptr(rgba),
+                      None, iters.data_ptr(), rel.data_ptr())
+        return (alpha, rgba, iters, rel) if want_rgba else (alpha, iters, rel)
+
     def estimate_foreground(self, bgr, alpha, eps_r, omega, max_iter, tol, want_rgba=False, out=None):
         """Foreground colours of bgr (B,H,W,3) uint8 under alpha (B,H,W) float32 (ggc_estimate_foreground): F where
         alpha is fractional, the image's bytes elsewhere.

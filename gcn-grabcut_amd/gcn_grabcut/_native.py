@@ -75,6 +75,7 @@ SIGNATURES = {
     "ggc_alpha_matte": [_vp, _vp, _i, _i, _i, _vp, _vp, _i, _f, _vp, _vp],
     "ggc_upsample_matte": [_vp, _vp, _i, _i, _i, _vp, _vp, _i, _i, _vp, _i, _f, _vp, _vp, _vp],
     "ggc_closed_form_matte": [_vp, _vp, _i, _i, _i, _vp, _vp, _i, _f, _i, _i, _f, _vp, _vp, _vp, _vp, _vp],
+    "ggc_trimap_matte": [_vp, _vp, _i, _i, _i, _vp, _vp, _i, _f, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp],
     "ggc_estimate_foreground": [_vp, _vp, _i, _i, _i, _vp, _vp, _f, _f, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp],
     "ggc_matte_errors": [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp],
     "ggc_mask_iou": [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp],

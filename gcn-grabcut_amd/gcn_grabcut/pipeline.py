@@ -189,6 +189,47 @@ def closed_form_matte(image: np.ndarray, mask: np.ndarray, radius: int = CF_RADI
     return (a, int(iters[0].item()), float(rel[0].item())) if return_info else a
 
 
+def trimap_matte(image: np.ndarray, trimap: np.ndarray, radius: int = CF_RADIUS, eps: float = CF_EPS,
+                 max_iter: int = CF_MAX_ITER, tol: float = CF_TOL, alpha0: "Optional[np.ndarray]" = None,
+                 return_info: bool = False, device="cuda"):
+    """Closed-form alpha matte from an image and a trimap (additive): the matting Laplacian of closed_form_matte
+    minimised over the trimap's unknown pixels, with alpha 1 on its foreground and 0 on its background
+    (ggc_trimap_matte).  Where closed_form_matte can only look within `band` of a mask's edge, with a
+    mask that is wrong exactly there as its anchor, here the caller says where the hair is.  A tight trimap helps; a loose
+    one leaves Levin's energy free to smooth fine structure away.
+
+    image: (H, W, 3) uint8 BGR; trimap: (H, W) uint8, 255 = foreground, 0 = background, every other byte unknown (the
+    convention of the matting benchmarks and of evaluate_matte.py --trimaps).  alpha0: (H, W) float, finite, or None:
+    where the unknown pixels start (clamped to [0, 1]; 0.5 without it); it changes the iterations, and the answer within
+    tol.  radius, eps, max_iter and tol as closed_form_matte.  A trimap without unknown pixels, or with nothing else,
+    returns the start.
+    -> (H, W) float32 in [0, 1]; with return_info, (alpha, iterations, relative residual)."""
+    from ._engine import get_engine, check_closed_form_args, check_closed_form_shape
+    image = _check_image(image)
+    t = np.asarray(trimap)
+    if t.shape != image.shape[:2]:
+        raise ValueError(f"trimap_matte: trimap {t.shape} does not match image {image.shape[:2]}")
+    if t.dtype != np.uint8:
+        raise ValueError(f"trimap_matte: trimap must be uint8 (255 foreground, 0 background, else unknown), got {t.dtype}")
+    a0 = None
+    if alpha0 is not None:
+        a0 = np.asarray(alpha0)
+        if a0.shape != image.shape[:2]:
+            raise ValueError(f"trimap_matte: alpha0 {a0.shape} does not match image {image.shape[:2]}")
+        if a0.dtype.kind != "f":
+            raise ValueError(f"trimap_matte: alpha0 must be a float array, got {a0.dtype}")
+        if not np.isfinite(a0).all():
+            raise ValueError("trimap_matte: alpha0 must be finite")
+    check_closed_form_args(radius, eps, 0, max_iter, tol)
+    check_closed_form_shape(*image.shape[:2], radius)
+    eng = get_engine(device)
+    start = None if a0 is None else eng.to_device(np.ascontiguousarray(a0, np.float32)[None])
+    alpha, iters, rel = eng.trimap_matte(eng.to_device(image[None]), eng.to_device(np.ascontiguousarray(t)[None]), radius,
+                                         eps, max_iter, tol, alpha0=start)
+    a = alpha[0].cpu().numpy()
+    return (a, int(iters[0].item()), float(rel[0].item())) if return_info else a
+
+
 FG_EPS_R = 5e-3
 FG_OMEGA = 1.0
 FG_MAX_ITER = 2000

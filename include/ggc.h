@@ -51,7 +51,9 @@
 extern "C" {
 #endif
 
-#define GGC_VERSION 400 /* 0.4.0: ggc_matte_errors (SAD, MSE, gradient and connectivity error of an alpha matte against the true one);
+#define GGC_VERSION 401 /* 0.4.1: ggc_trimap_matte (closed-form alpha matte on the unknown region of a caller's trimap; one solver with
+                                  ggc_closed_form_matte, whose results do not change);
+                           0.4.0: ggc_matte_errors (SAD, MSE, gradient and connectivity error of an alpha matte against the true one);
                            0.3.9: ggc_estimate_foreground (foreground colours under an alpha matte: clean cut-outs, PCG on the device);
                            0.3.8: ggc_closed_form_matte (closed-form alpha matte: matting Laplacian solved by PCG on the device);
                            0.3.7: ggc_upsample_matte (the matte's mask and alpha at a larger resolution: fast guided filter);
@@ -488,6 +490,30 @@ int ggc_upsample_matte(ggc_ctx* ctx, ggc_stream stream, int B, int H, int W, con
 int ggc_closed_form_matte(ggc_ctx* ctx, ggc_stream stream, int B, int H, int W, const uint8_t* bgr, const uint8_t* binary,
                           int radius, float eps, int band, int max_iter, float tol,
                           float* alpha, uint8_t* rgba, double* raw, int32_t* iters, double* rel_residual);
+
+/* O3t — closed-form alpha matte on the unknown region of a caller's trimap (additive): the system of O3 with the unknown
+ * set, the known values and the start taken from the caller instead of from a mask's edge.  Per image, with K, Delta_k, L
+ * and the matrix-free L p exactly those of O3:
+ *   regions   F = {trimap == 255}, G = {trimap == 0}, U = every other byte; alpha = 1 on F, 0 on G
+ *   start     alpha_U = alpha0 read as float64 and clamped to [0, 1] (a NaN reads as 0), or 0.5 when alpha0 is NULL;
+ *             alpha0 is read on U only
+ *   solve     L_UU alpha_U = -L_{U,F} 1_F by the Jacobi-preconditioned CG of O3; an image stops when
+ *             ||r_j||_2 <= tol ||r_0||_2 or after max_iter iterations, r_0 = -(L x0)_U the unpreconditioned residual of the
+ *             start image x0 (the known values off U, the start on U), one application of L
+ *   trivial   an image whose U is empty, or covers every pixel (nothing anchors the system: it is singular), or whose
+ *             r_0 is 0, gets the start image, 0 iterations and rel_residual 0.  An image with G but no F is not special:
+ *             its solution is alpha_U = 0 and CG goes there
+ *   bgr [dev] u8 [B,H,W,3]   trimap [dev] u8 [B,H,W]   alpha0 [dev] f32 [B,H,W] or NULL
+ *   radius, eps, max_iter, tol, the shape limits, the error codes, B == 0 and the five outputs with their NULL rule: as
+ *   O3 (there is no band)
+ * The two entries share one solver: after the flag plane, the start and the per-tile counts of U are written (O3: by the
+ * band kernels; here: by one kernel over the trimap), the same tile list, set-up and iteration kernels run.  With
+ * trimap = 128 on O3's U, else 255 m, and alpha0 = m, every output equals O3's bit for bit.  Reductions, batch
+ * independence, atomics and the synchronisation of the stream are O3's.
+ * Scratch: 145 bytes per pixel plus 28 bytes per 16 x 16 tile and 56 bytes per image, from the context. */
+int ggc_trimap_matte(ggc_ctx* ctx, ggc_stream stream, int B, int H, int W, const uint8_t* bgr, const uint8_t* trimap,
+                     int radius, float eps, int max_iter, float tol, const float* alpha0,
+                     float* alpha, uint8_t* rgba, double* raw, int32_t* iters, double* rel_residual);
 
 /* O4 — foreground colour estimation under a given alpha matte (additive; the multi-level foreground estimation energy of
  * Germer, Uelwer, Conrad and Harmeling, ICPR 2020, restricted to the pixels of fractional alpha with Dirichlet values).

@@ -1,0 +1,146 @@
+"""
+matte.py — alpha mattes from images and trimaps with the closed-form matte on MI355X.  No segmentation is run.
+
+    python3 matte.py --image cat.jpg --trimap cat_trimap.png
+    python3 matte.py --input data/images --trimaps data/trimaps --output mattes/ --save alpha cutout
+    python3 matte.py --image cat.jpg --trimap cat_trimap.png --save cutout --decontaminate
+
+A trimap is an 8-bit grey image of the photo's size: 255 = foreground, 0 = background, every other byte unknown (the
+convention of the matting benchmarks and of evaluate_matte.py --trimaps).  The matting Laplacian is solved on the
+unknown pixels (gcn_grabcut.trimap_matte, ggc_trimap_matte).  With --input, trimaps are matched by stem;
+images of one size are solved as one batch.  Outputs are named as inference.py names them: <stem>_alpha.png (8-bit grey)
+and <stem>_cutout.png (BGRA cut-out with that alpha).
+"""
+import argparse
+import sys
+import time
+from pathlib import Path
+
+import numpy as np
+
+IMAGE_EXTS = {".jpg", ".jpeg", ".png", ".bmp", ".tif", ".tiff", ".webp"}
+TAG = "[matte]"
+
+
+def build_parser() -> argparse.ArgumentParser:
+    parser = argparse.ArgumentParser(description="Closed-form alpha mattes from images and trimaps (MI355X)")
+    src = parser.add_mutually_exclusive_group(required=True)
+    src.add_argument("--image", help="Path to a single input image (with --trimap)")
+    src.add_argument("--input", help="Directory of images (with --trimaps)")
+    parser.add_argument("--trimap", default=None, help="Trimap of --image: 255 foreground, 0 background, else unknown")
+    parser.add_argument("--trimaps", default=None, help="Directory of trimaps of --input, matched by stem")
+    parser.add_argument("--output", default="results", help="Output directory")
+    parser.add_argument("--save", nargs="+", default=["alpha"], choices=["alpha", "cutout"],
+                        help="Which outputs to write: the matte, the BGRA cut-out with it")
+    parser.add_argument("--device", default="cuda")
+    parser.add_argument("--batch", type=int, default=64, help="Images per device batch")
+    parser.add_argument("--cf-radius", type=int, default=1, help="Window radius of the closed-form matte, 1..8")
+    parser.add_argument("--cf-eps", type=float, default=1e-5, help="Regularisation of the closed-form matte, [1e-12, 1]")
+    parser.add_argument("--cf-iters", type=int, default=500, help="Most conjugate-gradient iterations per image")
+    parser.add_argument("--cf-tol", type=float, default=1e-4, help="Stop when the residual falls to this fraction")
+    parser.add_argument("--decontaminate", action="store_true",
+                        help="Write the cut-out (--save cutout) with estimated foreground colours where alpha is "
+                             "fractional, instead of the image's own, so that it shows no halo on a new background")
+    return parser
+
+
+def _read(path: Path, mode: str):
+    from PIL import Image
+    try:
+        with Image.open(path) as im:
+            a = np.asarray(im.convert(mode), dtype=np.uint8)
+    except Exception:
+        raise SystemExit(f"{TAG} cannot read {path}")
+    return np.ascontiguousarray(a[:, :, ::-1]) if mode == "RGB" else np.ascontiguousarray(a)
+
+
+def collect(args) -> list:
+    """(image path, trimap path) pairs."""
+    if args.image:
+        pairs = [(Path(args.image), Path(args.trimap))]
+    else:
+        in_dir, tri_dir = Path(args.input), Path(args.trimaps)
+        for d, flag in ((in_dir, "--input"), (tri_dir, "--trimaps")):
+            if not d.is_dir():
+                raise SystemExit(f"{TAG} {flag} directory {d} does not exist")
+        tris = {p.stem: p for p in sorted(tri_dir.iterdir()) if p.suffix.lower() in IMAGE_EXTS}
+        images = sorted(p for p in in_dir.iterdir() if p.suffix.lower() in IMAGE_EXTS)
+        if not images:
+            raise SystemExit(f"{TAG} no image files in {in_dir}")
+        for p in images:
+            if p.stem not in tris:
+                raise SystemExit(f"{TAG} {p} has no trimap of the same stem in {tri_dir}")
+        pairs = [(p, tris[p.stem]) for p in images]
+    for p, t in pairs:
+        for f in (p, t):
+            if not f.is_file():
+                raise SystemExit(f"{TAG} {f} does not exist")
+    return pairs
+
+
+def main() -> None:
+    parser = build_parser()
+    args = parser.parse_args()
+    if args.image and (args.trimap is None or args.trimaps is not None):
+        parser.error("--image goes with --trimap (one file), not --trimaps")
+    if args.input and (args.trimaps is None or args.trimap is not None):
+        parser.error("--input goes with --trimaps (a directory), not --trimap")
+    if args.decontaminate and "cutout" not in args.save:
+        parser.error("--decontaminate changes the cut-out: add cutout to --save")
+    if args.batch < 1:
+        parser.error("--batch must be >= 1")
+    from src.gcn_grabcut._engine import check_closed_form_args, check_closed_form_shape, get_engine
+    from src.gcn_grabcut.pipeline import ForegroundColours, _write_png, alpha_to_u8
+    cf = (args.cf_radius, args.cf_eps, args.cf_iters, args.cf_tol)
+    try:
+        check_closed_form_args(cf[0], cf[1], 0, cf[2], cf[3])
+    except ValueError as e:
+        parser.error(str(e))
+
+    by_shape: dict = {}
+    for path, tri in collect(args):
+        image, trimap = _read(path, "RGB"), _read(tri, "L")
+        if trimap.shape != image.shape[:2]:
+            raise SystemExit(f"{TAG} {tri} is {trimap.shape[1]}x{trimap.shape[0]} but {path} is "
+                             f"{image.shape[1]}x{image.shape[0]}")
+        try:
+            check_closed_form_shape(*image.shape[:2], cf[0])
+        except ValueError as e:
+            raise SystemExit(f"{TAG} {path}: {e}")
+        by_shape.setdefault(image.shape, []).append((path, image, trimap))
+
+    import torch
+    if not torch.cuda.is_available():
+        raise SystemExit(f"{TAG} no MI355X visible: this build has no CPU path")
+    eng = get_engine(args.device)
+    out_dir = Path(args.output)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    n_all, n_done, total_t = sum(len(v) for v in by_shape.values()), 0, 0.0
+    for items in by_shape.values():
+        for i in range(0, len(items), args.batch):
+            chunk = items[i:i + args.batch]
+            t0 = time.perf_counter()
+            bgr = eng.to_device(np.stack([im for _, im, _ in chunk]))
+            tri = eng.to_device(np.stack([t for _, _, t in chunk]))
+            alpha, rgba, iters, rel = eng.trimap_matte(bgr, tri, *cf, want_rgba=True)
+            if args.decontaminate:
+                rgba = eng.estimate_foreground(bgr, alpha, *ForegroundColours().args(), want_rgba=True)[1]
+            alpha, rgba, iters, rel = alpha.cpu().numpy(), rgba.cpu().numpy(), iters.cpu().numpy(), rel.cpu().numpy()
+            elapsed = (time.perf_counter() - t0) / len(chunk)
+            for j, (path, _, trimap) in enumerate(chunk):
+                n_done += 1
+                total_t += elapsed
+                stem = out_dir / path.stem
+                if "alpha" in args.save:
+                    _write_png(f"{stem}_alpha.png", alpha_to_u8(alpha[j]))
+                if "cutout" in args.save:
+                    rgba[j][..., 3] = alpha_to_u8(alpha[j])       # the byte of the float32 matte: both files agree
+                    _write_png(f"{stem}_cutout.png", rgba[j])
+                unknown = ((trimap != 0) & (trimap != 255)).mean()
+                print(f"[{n_done}/{n_all}] {path.name}  unknown={unknown:.1%}  iterations={int(iters[j])}  "
+                      f"residual={float(rel[j]):.2e}  total={elapsed:.4f}s")
+    print(f"\n{TAG} {n_done} image(s) → {out_dir}/  ({total_t / n_done:.4f}s per image)")
+
+
+if __name__ == "__main__":
+    sys.exit(main())
