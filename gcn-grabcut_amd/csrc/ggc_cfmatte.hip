@@ -7,7 +7,10 @@
 // unknown ones start: it writes the flag plane (F_M = the known value, F_U = unknown), the start x on U, and the
 // number of U pixels of every tile.  ggc_closed_form_matte's is the band around the mask's edge, started at the mask
 // (k_cf_edge, k_cf_dilate_h, k_cf_dilate_v); ggc_trimap_matte's reads the trimap's bytes and the caller's start
-// (k_cf_trimap).  Everything after that (cf_solve) is shared.
+// (k_cf_trimap).  Everything after that (cf_solve) is shared.  ggc_trimap_matte_warm is the trimap front end with a
+// second stop reference: the residual of the 0.5 start, one more application of L in the set-up.
+// ggc_lift_trimap and ggc_closed_form_band solve nothing: they write trimaps (a working-size trimap and alpha carried to
+// a larger size; the band of the mask front end as a trimap) with the band front end's separable dilation.
 //
 // Layout.  A tile is 16 x 16 pixels of one image and a block of 256 threads, one per pixel.  U is found over the whole
 // frame once per call by the front end; the host reads the counts and lists the tiles that hold U or touch a tile that
@@ -137,6 +140,70 @@ __global__ void __launch_bounds__(CF_THREADS) k_cf_trimap(int H, int W, const ui
     count_tile(u, s_cnt, tid, tile_u);
 }
 
+// ---------------------------------------------------------------- trimaps for a later solve, over the whole frame
+// the half-pixel-centre source coordinate of output index o of n1 over a source of n: ggc_upsample_matte's (ggc_matte.hip)
+__device__ __forceinline__ void lift_coord(int o, int n, int n1, int& i0, int& i1, double& w) {
+    double s = (((double)o + 0.5) * (double)n) / (double)n1 - 0.5;
+    if (s < 0.0) s = 0.0;
+    const double f = floor(s);
+    i0 = (int)f;
+    if (i0 >= n - 1) { i0 = n - 1; w = 0.0; } else { w = s - f; }
+    i1 = min(i0 + 1, n - 1);
+}
+
+__device__ __forceinline__ double lerp(double u, double v, double t) { return u + t * (v - u); }
+
+__device__ __forceinline__ double unit_clamp(float a) {
+    const double v = (double)a;
+    return !(v >= 0.0) ? 0.0 : (v > 1.0 ? 1.0 : v);
+}
+
+// One output pixel per thread, grid (cdiv(W1, 16), cdiv(H1, 16), B).  trimap_full = 255 / 0 where the source pixels of
+// nonzero weight all are, else 128 (unknown = that as a 0 / 1 plane, for the dilation); alpha0_full = the bilinear
+// interpolation of the clamped alpha.  Each output may be NULL.
+__global__ void __launch_bounds__(CF_THREADS) k_cf_lift(int H, int W, int H1, int W1, const uint8_t* __restrict__ trimap,
+                                                        const float* __restrict__ alpha, uint8_t* __restrict__ trimap_full,
+                                                        uint8_t* __restrict__ unknown, float* __restrict__ alpha0_full) {
+    const int x = blockIdx.x * CF_T + threadIdx.x, y = blockIdx.y * CF_T + threadIdx.y;
+    if (x >= W1 || y >= H1) return;
+    int x0, x1, y0, y1;
+    double wx, wy;
+    lift_coord(x, W, W1, x0, x1, wx);
+    lift_coord(y, H, H1, y0, y1, wy);
+    const size_t src = (size_t)blockIdx.z * H * W, o = (size_t)blockIdx.z * H1 * W1 + (size_t)y * W1 + x;
+    if (trimap_full) {
+        const uint8_t* t = trimap + src;
+        const int xb = wx > 0.0 ? x1 : x0, yb = wy > 0.0 ? y1 : y0;      // a source pixel of weight 0 does not count
+        const uint8_t t00 = t[(size_t)y0 * W + x0], t01 = t[(size_t)y0 * W + xb];
+        const uint8_t t10 = t[(size_t)yb * W + x0], t11 = t[(size_t)yb * W + xb];
+        const uint8_t all_and = t00 & t01 & t10 & t11, all_or = t00 | t01 | t10 | t11;
+        const uint8_t v = all_and == 255 ? 255 : (all_or == 0 ? 0 : 128);
+        trimap_full[o] = v;
+        if (unknown) unknown[o] = v == 128 ? 1 : 0;
+    }
+    if (alpha0_full) {
+        const float* a = alpha + src;
+        const double a00 = unit_clamp(a[(size_t)y0 * W + x0]), a01 = unit_clamp(a[(size_t)y0 * W + x1]);
+        const double a10 = unit_clamp(a[(size_t)y1 * W + x0]), a11 = unit_clamp(a[(size_t)y1 * W + x1]);
+        alpha0_full[o] = (float)lerp(lerp(a00, a01, wx), lerp(a10, a11, wx), wy);
+    }
+}
+
+// the vertical half of the dilation, written as a trimap: 128 where the column of hdil within `band` holds a set byte,
+// else the known value: base's own byte, with MASK 255 (base != 0).  out may be base: a thread reads its own pixel only
+template <bool MASK>
+__global__ void __launch_bounds__(CF_THREADS) k_cf_dilate_v_trimap(int H, int W, int band, const uint8_t* __restrict__ hdil,
+                                                                   const uint8_t* base, uint8_t* out) {
+    const int x = blockIdx.x * CF_T + threadIdx.x, y = blockIdx.y * CF_T + threadIdx.y;
+    if (x >= W || y >= H) return;
+    const size_t plane = (size_t)blockIdx.z * H * W;
+    uint8_t v = 0;
+    for (int yy = max(0, y - band); yy <= min(H - 1, y + band); ++yy) v |= hdil[plane + (size_t)yy * W + x];
+    const size_t i = plane + (size_t)y * W + x;
+    const uint8_t known = MASK ? (base[i] != 0 ? 255 : 0) : base[i];
+    out[i] = v ? 128 : known;
+}
+
 // ---------------------------------------------------------------- per listed tile
 struct TileRef { int b, ty, tx; };
 
@@ -178,14 +245,15 @@ __global__ void __launch_bounds__(CF_THREADS) k_cf_stats(int H, int W, int r, do
     stats[(size_t)t.b * H * W + (size_t)y * W + x] = st;
 }
 
-// SETUP: p = the start image (d is x: the start on U, the known value elsewhere); else p = d on U and 0 elsewhere
-template <bool SETUP>
+// SETUP: p = the start image (d is x: the start on U, the known value elsewhere), with HALF the image of the stop
+// reference instead (0.5 on U, d is not read); else p = d on U and 0 elsewhere
+template <bool SETUP, bool HALF>
 __device__ __forceinline__ double p_value(uint8_t f, const double* __restrict__ d, size_t i) {
-    if constexpr (SETUP) return (f & F_U) ? d[i] : ((f & F_M) ? 1.0 : 0.0);
+    if constexpr (SETUP) return (f & F_U) ? (HALF ? 0.5 : d[i]) : ((f & F_M) ? 1.0 : 0.0);
     else return (f & F_U) ? d[i] : 0.0;
 }
 
-template <bool SETUP>
+template <bool SETUP, bool HALF = false>
 __global__ void __launch_bounds__(CF_THREADS) k_cf_window(int H, int W, int r, int ntx, const int2* __restrict__ tiles,
                                                           const CfImage* __restrict__ img, const uint8_t* __restrict__ bgr,
                                                           const uint8_t* __restrict__ flags, const CfStats* __restrict__ stats,
@@ -202,7 +270,7 @@ __global__ void __launch_bounds__(CF_THREADS) k_cf_window(int H, int W, int r, i
         double p = 0.0, i0 = 0.0, i1 = 0.0, i2 = 0.0;
         if (yy >= 0 && yy < H && xx >= 0 && xx < W) {
             const size_t i = base + (size_t)yy * W + xx;
-            const double pv = p_value<SETUP>(flags[i], d, i);
+            const double pv = p_value<SETUP, HALF>(flags[i], d, i);
             const uint8_t* px = bgr + 3 * i;
             p = pv; i0 = colour(px, 0) * pv; i1 = colour(px, 1) * pv; i2 = colour(px, 2) * pv;
         }
@@ -240,8 +308,8 @@ __device__ __forceinline__ double block_sum(double v, double* s, int tid) {
 }
 
 // q = (L p) on U.  SETUP: p = the start image (d is x); r = -q, diag L, and the per-tile r . z, r . r (into part_a,
-// part_b); else the per-tile d . q (into part_a)
-template <bool SETUP>
+// part_b); else the per-tile d . q (into part_a).  HALF (with SETUP): the same of the stop reference's image
+template <bool SETUP, bool HALF = false>
 __global__ void __launch_bounds__(CF_THREADS) k_cf_pixel(int H, int W, int r, int ntx, const int2* __restrict__ tiles,
                                                          const CfImage* __restrict__ img, const uint8_t* __restrict__ bgr,
                                                          const uint8_t* __restrict__ flags, const CfStats* __restrict__ stats,
@@ -278,7 +346,7 @@ __global__ void __launch_bounds__(CF_THREADS) k_cf_pixel(int H, int W, int r, in
                     acc += c.a0 * I0 + c.a1 * I1 + c.a2 * I2 + c.b;
                 }
             const double cnt = (double)((ky1 - ky0 + 1) * (kx1 - kx0 + 1));
-            const double pi = p_value<SETUP>(f, d, i);
+            const double pi = p_value<SETUP, HALF>(f, d, i);
             const double qi = cnt * pi - acc;
             if constexpr (SETUP) {
                 // diag L = sum_k [1 - (1 + (I_i - mu_k)^T Delta_k^-1 (I_i - mu_k)) / n]
@@ -322,6 +390,8 @@ __device__ __forceinline__ double image_sum(const double* __restrict__ part, int
 }
 
 // MODE 0 (after setup): rz, rr0, the trivial images; MODE 1: alpha = rz / d.q; MODE 2: convergence and beta.
+// The warm entry's set-up: MODE 3 (after the pass over the stop reference's image) rr0 = ||r_ref||^2 and the trivial
+// images; MODE 4 (after setup, in MODE 0's place) rz and the stop test on r_0 against that rr0.
 // grid B, one wave
 template <int MODE>
 __global__ void __launch_bounds__(WAVE) k_cf_scalar(int max_iter, double tol, CfImage* __restrict__ img,
@@ -338,6 +408,15 @@ __global__ void __launch_bounds__(WAVE) k_cf_scalar(int max_iter, double tol, Cf
         s.rel = 0.0;
         s.iters = 0;
         if (!(b > 0.0)) { s.done = 1; atomicAdd(n_done, 1); }    // r_0 = 0: the start already solves the system
+    } else if (MODE == 3) {
+        s.rr0 = b;
+        s.rel = 0.0;
+        s.iters = 0;
+        if (!(b > 0.0)) { s.done = 1; atomicAdd(n_done, 1); }    // r_ref = 0: nothing to measure a residual against
+    } else if (MODE == 4) {
+        s.rz = a;
+        s.rel = sqrt(b / s.rr0);
+        if (s.rel <= tol) { s.done = 1; atomicAdd(n_done, 1); }  // the start is already good enough
     } else if (MODE == 1) {
         if (a > 0.0 && std::isfinite(a)) {
             s.alpha = s.rz / a;
@@ -463,11 +542,12 @@ int cf_check(ggc_ctx* ctx, int B, int H, int W, const void* bgr, const void* gui
 struct CfFront { uint8_t *flags, *edge, *hdil; double* x; int32_t* tile_u; };
 
 // The solver behind both entries.  front(f, fgrid, tblk) launches the front end's kernels on st; n_byte_planes is 1
-// (flags) plus the byte planes the front end needs for itself.
+// (flags) plus the byte planes the front end needs for itself.  warm: images stop against the residual of the 0.5 start
+// (one more pass of the set-up kernels) instead of against their own start's.
 template <class Front>
 int cf_solve(ggc_ctx* ctx, hipStream_t st, const char* name, int B, int H, int W, const uint8_t* bgr, int n_byte_planes,
              int radius, float eps, int max_iter, float tol, float* alpha, uint8_t* rgba, double* raw, int32_t* iters,
-             double* rel_residual, Front&& front) {
+             double* rel_residual, bool warm, Front&& front) {
     GGC_HIP(ctx, hipSetDevice(ctx->device));
     const size_t P = (size_t)B * H * W;
     const int ntx = cdiv(W, CF_T), nty = cdiv(H, CF_T), nt = ntx * nty;
@@ -539,11 +619,19 @@ int cf_solve(ggc_ctx* ctx, hipStream_t st, const char* name, int B, int H, int W
     if (n_list > 0) {
         const double e = (double)eps, tl = (double)tol;
         hipLaunchKernelGGL(k_cf_stats, dim3(n_list), tblk, 0, st, H, W, radius, e, ntx, tiles, bgr, stats);
+        if (warm) {     // r_ref = -(L x^1/2)_U; ab, res, diag and the partial sums are written again by the set-up proper
+            hipLaunchKernelGGL((k_cf_window<true, true>), dim3(n_list), tblk, 0, st, H, W, radius, ntx, tiles, img, bgr,
+                               flags, stats, x, ab);
+            hipLaunchKernelGGL((k_cf_pixel<true, true>), dim3(n_list), tblk, 0, st, H, W, radius, ntx, tiles, img, bgr,
+                               flags, stats, ab, x, q, res, diag, part_a, part_b);
+            hipLaunchKernelGGL(k_cf_scalar<3>, dim3(B), dim3(WAVE), 0, st, max_iter, tl, img, part_a, part_b, n_done);
+        }
         hipLaunchKernelGGL(k_cf_window<true>, dim3(n_list), tblk, 0, st, H, W, radius, ntx, tiles, img, bgr, flags, stats,
                            x, ab);
         hipLaunchKernelGGL(k_cf_pixel<true>, dim3(n_list), tblk, 0, st, H, W, radius, ntx, tiles, img, bgr, flags, stats, ab,
                            x, q, res, diag, part_a, part_b);
-        hipLaunchKernelGGL(k_cf_scalar<0>, dim3(B), dim3(WAVE), 0, st, max_iter, tl, img, part_a, part_b, n_done);
+        if (warm) hipLaunchKernelGGL(k_cf_scalar<4>, dim3(B), dim3(WAVE), 0, st, max_iter, tl, img, part_a, part_b, n_done);
+        else hipLaunchKernelGGL(k_cf_scalar<0>, dim3(B), dim3(WAVE), 0, st, max_iter, tl, img, part_a, part_b, n_done);
         hipLaunchKernelGGL(k_cf_direction<true>, dim3(n_list), tblk, 0, st, H, W, ntx, tiles, img, flags, res, diag, d);
         GGC_LAUNCH_CHECK(ctx);
         for (int it = 0; it < max_iter; ++it) {
@@ -583,7 +671,7 @@ extern "C" int ggc_closed_form_matte(ggc_ctx* ctx, ggc_stream stream, int B, int
     if (B == 0) return GGC_OK;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     return cf_solve(ctx, st, "closed_form_matte", B, H, W, bgr, 3, radius, eps, max_iter, tol, alpha, rgba, raw, iters,
-                    rel_residual, [&](const CfFront& f, dim3 fgrid, dim3 tblk) {
+                    rel_residual, false, [&](const CfFront& f, dim3 fgrid, dim3 tblk) {
                         hipLaunchKernelGGL(k_cf_edge, fgrid, tblk, 0, st, H, W, binary, f.edge);
                         hipLaunchKernelGGL(k_cf_dilate_h, fgrid, tblk, 0, st, H, W, band, f.edge, f.hdil);
                         hipLaunchKernelGGL(k_cf_dilate_v, fgrid, tblk, 0, st, H, W, band, f.hdil, binary, f.flags, f.x,
@@ -601,7 +689,76 @@ extern "C" int ggc_trimap_matte(ggc_ctx* ctx, ggc_stream stream, int B, int H, i
     if (B == 0) return GGC_OK;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     return cf_solve(ctx, st, "trimap_matte", B, H, W, bgr, 1, radius, eps, max_iter, tol, alpha, rgba, raw, iters,
-                    rel_residual, [&](const CfFront& f, dim3 fgrid, dim3 tblk) {
+                    rel_residual, false, [&](const CfFront& f, dim3 fgrid, dim3 tblk) {
                         hipLaunchKernelGGL(k_cf_trimap, fgrid, tblk, 0, st, H, W, trimap, alpha0, f.flags, f.x, f.tile_u);
                     });
+}
+
+extern "C" int ggc_trimap_matte_warm(ggc_ctx* ctx, ggc_stream stream, int B, int H, int W, const uint8_t* bgr,
+                                     const uint8_t* trimap, int radius, float eps, int max_iter, float tol,
+                                     const float* alpha0, float* alpha, uint8_t* rgba, double* raw, int32_t* iters,
+                                     double* rel_residual) {
+    if (!ctx) return GGC_E_INVALID_ARG;
+    if (int e = cf_check(ctx, B, H, W, bgr, trimap, radius, eps, 0, max_iter, tol,
+                         alpha || rgba || raw || iters || rel_residual))
+        return e;
+    GGC_REQUIRE(ctx, alpha0, GGC_E_INVALID_ARG, "null pointer: the warm solve needs alpha0");
+    if (B == 0) return GGC_OK;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    return cf_solve(ctx, st, "trimap_matte_warm", B, H, W, bgr, 1, radius, eps, max_iter, tol, alpha, rgba, raw, iters,
+                    rel_residual, true, [&](const CfFront& f, dim3 fgrid, dim3 tblk) {
+                        hipLaunchKernelGGL(k_cf_trimap, fgrid, tblk, 0, st, H, W, trimap, alpha0, f.flags, f.x, f.tile_u);
+                    });
+}
+
+extern "C" int ggc_lift_trimap(ggc_ctx* ctx, ggc_stream stream, int B, int H, int W, const uint8_t* trimap,
+                               const float* alpha, int H1, int W1, int grow, uint8_t* trimap_full, float* alpha0_full) {
+    if (!ctx) return GGC_E_INVALID_ARG;
+    GGC_REQUIRE(ctx, B >= 0 && B <= 65535 && H >= 1 && W >= 1 && H1 >= H && W1 >= W && H1 <= 32768 && W1 <= 32768,
+                GGC_E_SHAPE, "bad shape B=%d H=%d W=%d H1=%d W1=%d", B, H, W, H1, W1);
+    GGC_REQUIRE(ctx, trimap_full || alpha0_full, GGC_E_INVALID_ARG, "null pointer: no output asked for");
+    GGC_REQUIRE(ctx, B == 0 || ((trimap || !trimap_full) && (alpha || !alpha0_full)), GGC_E_INVALID_ARG, "null pointer");
+    GGC_REQUIRE(ctx, grow >= 0 && grow <= 64, GGC_E_INVALID_ARG, "lift grow %d outside 0..64", grow);
+    if (B == 0) return GGC_OK;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    GGC_HIP(ctx, hipSetDevice(ctx->device));
+    const bool dilate = trimap_full && grow > 0;
+    const size_t P1 = (size_t)B * H1 * W1;
+    uint8_t *unknown = nullptr, *hdil = nullptr;
+    if (dilate && !carve_scratch(ctx, S_CFMATTE, [&](Carve& c) { unknown = c.take<uint8_t>(P1); hdil = c.take<uint8_t>(P1); }))
+        return GGC_E_OOM;
+    ProfScope prof(ctx, st, "lift_trimap");
+    const dim3 grid(cdiv(W1, CF_T), cdiv(H1, CF_T), B), tblk(CF_T, CF_T);
+    hipLaunchKernelGGL(k_cf_lift, grid, tblk, 0, st, H, W, H1, W1, trimap, alpha, trimap_full, dilate ? unknown : nullptr,
+                       alpha0_full);
+    if (dilate) {
+        hipLaunchKernelGGL(k_cf_dilate_h, grid, tblk, 0, st, H1, W1, grow, unknown, hdil);
+        hipLaunchKernelGGL(k_cf_dilate_v_trimap<false>, grid, tblk, 0, st, H1, W1, grow, hdil, trimap_full, trimap_full);
+    }
+    GGC_LAUNCH_CHECK(ctx);
+    return GGC_OK;
+}
+
+extern "C" int ggc_closed_form_band(ggc_ctx* ctx, ggc_stream stream, int B, int H, int W, const uint8_t* binary, int band,
+                                    uint8_t* trimap) {
+    if (!ctx) return GGC_E_INVALID_ARG;
+    GGC_REQUIRE(ctx, B >= 0 && B <= 65535 && H >= 1 && W >= 1 && H <= 32768 && W <= 32768, GGC_E_SHAPE,
+                "bad shape B=%d H=%d W=%d", B, H, W);
+    GGC_REQUIRE(ctx, trimap, GGC_E_INVALID_ARG, "null pointer: no output asked for");
+    GGC_REQUIRE(ctx, B == 0 || binary, GGC_E_INVALID_ARG, "null pointer");
+    GGC_REQUIRE(ctx, band >= 0 && band <= 64, GGC_E_INVALID_ARG, "closed-form band %d outside 0..64", band);
+    if (B == 0) return GGC_OK;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    GGC_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t P = (size_t)B * H * W;
+    uint8_t *edge = nullptr, *hdil = nullptr;
+    if (!carve_scratch(ctx, S_CFMATTE, [&](Carve& c) { edge = c.take<uint8_t>(P); hdil = c.take<uint8_t>(P); }))
+        return GGC_E_OOM;
+    ProfScope prof(ctx, st, "closed_form_band");
+    const dim3 grid(cdiv(W, CF_T), cdiv(H, CF_T), B), tblk(CF_T, CF_T);
+    hipLaunchKernelGGL(k_cf_edge, grid, tblk, 0, st, H, W, binary, edge);
+    hipLaunchKernelGGL(k_cf_dilate_h, grid, tblk, 0, st, H, W, band, edge, hdil);
+    hipLaunchKernelGGL(k_cf_dilate_v_trimap<true>, grid, tblk, 0, st, H, W, band, hdil, binary, trimap);
+    GGC_LAUNCH_CHECK(ctx);
+    return GGC_OK;
 }

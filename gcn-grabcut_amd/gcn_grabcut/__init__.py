@@ -23,7 +23,8 @@ from .model import (
 )
 from .pipeline import (GCNGrabCutPipeline, ClosedFormMatte, ForegroundColours, FullResolution, SegmentationResult,
                        alpha_matte, clean_mask, closed_form_matte, estimate_foreground, guided_filter, refine_trimap,
-                       trimap_matte, upsample_mask)
+                       closed_form_matte_full, lift_trimap, trimap_matte, trimap_matte_full,
+                       trimap_matte_warm, upsample_mask)
 from .synthetic import synthetic_image, synthetic_batch
 from .losses import FocalLoss, LabelSmoothingCE, TrimapLoss
 from .trainer import Trainer, TrainConfig
@@ -38,7 +39,7 @@ __all__ = [
     "evaluate_matte", "evaluate_matte_batch", "MatteMetrics",
     "GCNGrabCutPipeline", "FullResolution", "SegmentationResult", "alpha_matte", "clean_mask", "guided_filter",
     "refine_trimap", "upsample_mask", "ClosedFormMatte", "closed_form_matte", "ForegroundColours", "estimate_foreground",
-    "trimap_matte",
+    "trimap_matte", "trimap_matte_warm", "lift_trimap", "closed_form_matte_full", "trimap_matte_full",
     "ResGCNNet", "GCNTrimapNet", "GATTrimapNet", "build_model", "probs_to_node_trimap", "project_to_pixels",
     "Data", "Batch", "synthetic_image", "synthetic_batch",
     "FocalLoss", "LabelSmoothingCE", "TrimapLoss", "Trainer", "TrainConfig",

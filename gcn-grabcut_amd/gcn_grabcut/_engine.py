@@ -331,13 +331,17 @@ class Engine:
                       iters.data_ptr(), rel.data_ptr())
         return (alpha, rgba, iters, rel) if want_rgba else (alpha, iters, rel)
 
-    def trimap_matte(self, bgr, trimap, radius, eps, max_iter, tol, alpha0=None, want_rgba=False, out=None):
+    def trimap_matte(self, bgr, trimap, radius, eps, max_iter, tol, alpha0=None, want_rgba=False, out=None, warm=False):
         """Closed-form alpha matte of bgr (B,H,W,3) uint8 on the unknown region of trimap (B,H,W) uint8: 255 foreground,
         0 background, every other byte unknown (ggc_trimap_matte).  alpha0 (B,H,W) float32 or None: where the unknown
         pixels start (clamped to [0, 1]; 0.5 without it).  -> (alpha (B,H,W) float32 in [0,1], iters (B,) int32,
         rel_residual (B,) float64), with want_rgba also rgba (B,H,W,4) uint8 after alpha; out: (alpha, rgba or None),
-        preallocated.  The call synchronises its stream."""
+        preallocated.  The call synchronises its stream.  warm=True (needs alpha0; ggc_trimap_matte_warm): an image
+        stops on the residual of the 0.5 start instead of on its own start's, so a good alpha0 saves iterations, and
+        rel_residual is relative to that."""
         check_closed_form_args(radius, eps, 0, max_iter, tol)
+        if warm and alpha0 is None:
+            raise ValueError("trimap_matte: warm=True needs alpha0, the start it is warm from")
         b, h, w, _ = bgr.shape
         if tuple(trimap.shape) != (b, h, w):
             raise ValueError(f"trimap_matte: trimap {tuple(trimap.shape)} does not match bgr {tuple(bgr.shape)}")
@@ -358,10 +362,54 @@ class Engine:
         iters = self.empty(b, dtype=torch.int32)
         rel = self.empty(b, dtype=torch.float64)
         trimap = trimap.contiguous()
-        self.ctx.call("ggc_trimap_matte", self._stream(), b, h, w, bgr.data_ptr(), trimap.data_ptr(), int(radius),
+        self.ctx.call("ggc_trimap_matte_warm" if warm else "ggc_trimap_matte", self._stream(), b, h, w, bgr.data_ptr(),
+                      trimap.data_ptr(), int(radius),
                       float(eps), int(max_iter), float(tol), _native.ptr(alpha0), _native.ptr(alpha), _native.ptr(rgba),
                       None, iters.data_ptr(), rel.data_ptr())
         return (alpha, rgba, iters, rel) if want_rgba else (alpha, iters, rel)
+
+    def lift_trimap(self, trimap, alpha, full_shape, grow=0, want_trimap=True, want_alpha0=True):
+        """trimap (B,H,W) uint8 (255 foreground, 0 background, else unknown) and alpha (B,H,W) float32 carried to
+        full_shape = (H1, W1) >= (H, W) (ggc_lift_trimap): the trimap and the start of a solve at that size.
+        -> (trimap_full (B,H1,W1) uint8 with unknown = 128, dilated by grow pixels; alpha0_full (B,H1,W1) float32, the
+        bilinear interpolation of the clamped alpha), each None unless wanted."""
+        check_lift_args(tuple(trimap.shape), None if alpha is None else tuple(alpha.shape), full_shape, grow)
+        if not (want_trimap or want_alpha0):
+            raise ValueError("lift_trimap: ask for at least one of trimap and alpha0")
+        if trimap.dtype != torch.uint8:
+            raise ValueError(f"lift_trimap: trimap must be uint8, got {trimap.dtype}")
+        if want_alpha0 and (alpha is None or alpha.dtype != torch.float32):
+            raise ValueError(f"lift_trimap: alpha must be float32, got {None if alpha is None else alpha.dtype}")
+        b, h, w = trimap.shape
+        h1, w1 = int(full_shape[0]), int(full_shape[1])
+        trimap = trimap.contiguous()
+        alpha = alpha.contiguous() if want_alpha0 else None
+        t_full = self.empty(b, h1, w1, dtype=torch.uint8) if want_trimap else None
+        a_full = self.empty(b, h1, w1) if want_alpha0 else None
+        self.ctx.call("ggc_lift_trimap", self._stream(), b, h, w, trimap.data_ptr(), _native.ptr(alpha), h1, w1, int(grow),
+                      _native.ptr(t_full), _native.ptr(a_full))
+        return t_full, a_full
+
+    def closed_form_band(self, binary, band):
+        """The unknown band closed_form_matte(binary, band) solves on, as a trimap (B,H,W) uint8: 128 on the band, else
+        255 (binary != 0) (ggc_closed_form_band, the kernels of that solver's front end)."""
+        check_closed_form_args(1, 1e-5, band, 1, 0.5)          # only the band is this entry's
+        if binary.dim() != 3 or binary.dtype != torch.uint8:
+            raise ValueError(f"closed_form_band: binary must be (B,H,W) uint8, got {tuple(binary.shape)} {binary.dtype}")
+        b, h, w = binary.shape
+        binary = binary.contiguous()
+        trimap = self.empty(b, h, w, dtype=torch.uint8)
+        self.ctx.call("ggc_closed_form_band", self._stream(), b, h, w, binary.data_ptr(), int(band), trimap.data_ptr())
+        return trimap
+
+    def closed_form_full(self, bgr, trimap, alpha, bgr_full, radius, eps, grow, max_iter, tol, out=None):
+        """The full-resolution end of closed_form_matte_full / trimap_matte_full: a working-size trimap (B,H,W) uint8 and
+        its solved alpha (B,H,W) float32 lifted to bgr_full (B,H1,W1,3) uint8 (lift_trimap), then the warm solve there.
+        -> (alpha_full (B,H1,W1) float32, rgba_full (B,H1,W1,4) uint8, iters (B,), rel_residual (B,)); out: (alpha_full,
+        rgba_full), preallocated."""
+        t_full, a0_full = self.lift_trimap(trimap, alpha, tuple(bgr_full.shape[1:3]), grow)
+        return self.trimap_matte(bgr_full, t_full, radius, eps, max_iter, tol, alpha0=a0_full, want_rgba=True, out=out,
+                                 warm=True)
 
     def estimate_foreground(self, bgr, alpha, eps_r, omega, max_iter, tol, want_rgba=False, out=None):
         """Foreground colours of bgr (B,H,W,3) uint8 under alpha (B,H,W) float32 (ggc_estimate_foreground): F where
@@ -453,6 +501,26 @@ def check_closed_form_shape(h, w, radius) -> None:
         raise ValueError(f"closed-form matte needs H, W >= 2r+1 = {2 * int(radius) + 1}, got {h}x{w}")
     if h > UPSAMPLE_SIDE_MAX or w > UPSAMPLE_SIDE_MAX:
         raise ValueError(f"closed-form matte takes images of at most {UPSAMPLE_SIDE_MAX} on a side, got {h}x{w}")
+
+
+LIFT_GROW_MAX = 64
+
+
+def check_lift_args(trimap_shape, alpha_shape, full_shape, grow) -> None:
+    """The rules of ggc_lift_trimap, checked on the host so that a bad argument is a ValueError: trimap and alpha
+    (B,H,W), full_shape (H1, W1) with H <= H1 <= 32768 and W <= W1 <= 32768, grow an integer in 0..64."""
+    if len(trimap_shape) != 3 or min(trimap_shape[1:]) < 1:
+        raise ValueError(f"lift_trimap: trimap must be (B,H,W), got {tuple(trimap_shape)}")
+    if alpha_shape is not None and tuple(alpha_shape) != tuple(trimap_shape):
+        raise ValueError(f"lift_trimap: alpha {tuple(alpha_shape)} does not match trimap {tuple(trimap_shape)}")
+    if len(full_shape) != 2:
+        raise ValueError(f"lift_trimap: full_shape must be (H1, W1), got {tuple(full_shape)}")
+    h, w = trimap_shape[1:]
+    if not (h <= full_shape[0] <= UPSAMPLE_SIDE_MAX and w <= full_shape[1] <= UPSAMPLE_SIDE_MAX):
+        raise ValueError(f"lift_trimap: full size {tuple(full_shape)} must be at least the working size {(h, w)} and at "
+                         f"most {UPSAMPLE_SIDE_MAX} on a side")
+    if isinstance(grow, bool) or int(grow) != grow or not 0 <= int(grow) <= LIFT_GROW_MAX:
+        raise ValueError(f"lift_trimap: grow must be an integer in 0..{LIFT_GROW_MAX}, got {grow}")
 
 
 FG_OMEGA_MAX = 1e3

@@ -143,18 +143,27 @@ CF_EPS = 1e-5
 CF_BAND = 1
 CF_MAX_ITER = 500
 CF_TOL = 1e-4
+CF_FULL_MAX_ITER = 2000      # the iteration limit of the full-size solve: a recorded choice, not a tuned one
+CF_GROW = 0
 
 
 @dataclass(frozen=True)
 class ClosedFormMatte:
     """matte=ClosedFormMatte(...) asks segment / segment_batch / segment_batch_device / segment_bbox for the closed-form
     matte (closed_form_matte) of the cleaned mask instead of the guided one (matte=True).  The defaults are a recorded
-    choice from a float64 CPU study (tools/closed_form_study.py), not a tuned result."""
+    choice from a float64 CPU study (tools/closed_form_study.py), not a tuned result.
+
+    full_resolution=True (with a full image: full_image / full_images / full_bgr) also solves at the full image's size
+    (closed_form_matte_full with grow and full_max_iter) and fills the result's full alpha, rgba_soft
+    and binary_mask (alpha >= 0.5) from that.  Without it a full image is refused, as before."""
     radius: int = CF_RADIUS
     eps: float = CF_EPS
     band: int = CF_BAND
     max_iter: int = CF_MAX_ITER
     tol: float = CF_TOL
+    full_resolution: bool = False
+    grow: int = CF_GROW
+    full_max_iter: int = CF_FULL_MAX_ITER
 
     def args(self) -> "tuple[int, float, int, int, float]":
         return int(self.radius), float(self.eps), int(self.band), int(self.max_iter), float(self.tol)
@@ -202,8 +211,27 @@ def trimap_matte(image: np.ndarray, trimap: np.ndarray, radius: int = CF_RADIUS,
     convention of the matting benchmarks and of evaluate_matte.py --trimaps).  alpha0: (H, W) float, finite, or None:
     where the unknown pixels start (clamped to [0, 1]; 0.5 without it); it changes the iterations, and the answer within
     tol.  radius, eps, max_iter and tol as closed_form_matte.  A trimap without unknown pixels, or with nothing else,
-    returns the start.
+    returns the start.  trimap_matte_warm is the same solve with a stop rule made for a good alpha0.
     -> (H, W) float32 in [0, 1]; with return_info, (alpha, iterations, relative residual)."""
+    return _trimap_matte(image, trimap, radius, eps, max_iter, tol, alpha0, return_info, device, False)
+
+
+def trimap_matte_warm(image: np.ndarray, trimap: np.ndarray, alpha0: np.ndarray, radius: int = CF_RADIUS,
+                      eps: float = CF_EPS, max_iter: int = CF_MAX_ITER, tol: float = CF_TOL, return_info: bool = False,
+                      device="cuda"):
+    """trimap_matte from a start that is already close (additive; ggc_trimap_matte_warm): the solve stops
+    when the residual falls to tol times that of the 0.5 start, not of alpha0's own, so a good alpha0 saves iterations
+    (none at all when it is already within tol), and the relative residual returned is relative to that too.  With
+    alpha0 = 0.5 it is trimap_matte(alpha0=None) bit for bit.  alpha0 is required (None is a ValueError); every other
+    argument as trimap_matte.  It is a function of its own because trimap_matte's parameter list is pinned.
+    -> (H, W) float32 in [0, 1]; with return_info, (alpha, iterations, relative residual)."""
+    if alpha0 is None:
+        raise ValueError("trimap_matte_warm needs alpha0, the start it is warm from")
+    return _trimap_matte(image, trimap, radius, eps, max_iter, tol, alpha0, return_info, device, True)
+
+
+def _trimap_matte(image, trimap, radius, eps, max_iter, tol, alpha0, return_info, device, warm):
+    """trimap_matte and trimap_matte_warm: the checks, then Engine.trimap_matte on a batch of one."""
     from ._engine import get_engine, check_closed_form_args, check_closed_form_shape
     image = _check_image(image)
     t = np.asarray(trimap)
@@ -225,9 +253,108 @@ def trimap_matte(image: np.ndarray, trimap: np.ndarray, radius: int = CF_RADIUS,
     eng = get_engine(device)
     start = None if a0 is None else eng.to_device(np.ascontiguousarray(a0, np.float32)[None])
     alpha, iters, rel = eng.trimap_matte(eng.to_device(image[None]), eng.to_device(np.ascontiguousarray(t)[None]), radius,
-                                         eps, max_iter, tol, alpha0=start)
+                                         eps, max_iter, tol, alpha0=start, warm=warm)
     a = alpha[0].cpu().numpy()
     return (a, int(iters[0].item()), float(rel[0].item())) if return_info else a
+
+
+def lift_trimap(trimap: np.ndarray, alpha: np.ndarray, full_shape, grow: int = CF_GROW, device="cuda"):
+    """A working-size trimap and alpha carried to a larger size (additive; ggc_lift_trimap): the trimap
+    and the start of a closed-form solve on the full image.  Every output pixel looks at the source pixels bilinear
+    interpolation (half-pixel centres, as upsample_mask) gives it a nonzero weight for: it is foreground (255) or
+    background (0) when all of them are, else unknown (128); the unknown region is then dilated by `grow` full-size
+    pixels.  The start is the bilinear interpolation of alpha clamped to [0, 1].
+
+    trimap: (H, W) uint8, 255 = foreground, 0 = background, every other byte unknown; alpha: (H, W) float, finite;
+    full_shape: (H1, W1) with H <= H1 <= 32768, W <= W1 <= 32768; grow in 0..64.
+    -> (trimap_full (H1, W1) uint8, alpha0_full (H1, W1) float32)."""
+    from ._engine import get_engine, check_lift_args
+    t, a = np.asarray(trimap), np.asarray(alpha)
+    if t.ndim != 2 or t.dtype != np.uint8:
+        raise ValueError(f"lift_trimap: trimap must be (H, W) uint8, got {t.shape} {t.dtype}")
+    if a.dtype.kind != "f":
+        raise ValueError(f"lift_trimap: alpha must be a float array, got {a.dtype}")
+    full_shape = tuple(int(v) for v in full_shape)
+    check_lift_args((1, *t.shape), (1, *a.shape), full_shape, grow)
+    if not np.isfinite(a).all():
+        raise ValueError("lift_trimap: alpha must be finite")
+    eng = get_engine(device)
+    t_full, a_full = eng.lift_trimap(eng.to_device(np.ascontiguousarray(t)[None]),
+                                     eng.to_device(np.ascontiguousarray(a, np.float32)[None]), full_shape, grow)
+    return t_full[0].cpu().numpy(), a_full[0].cpu().numpy()
+
+
+def _check_full_solve(image, full_image, radius, eps, band, max_iter, tol, grow, full_max_iter, what):
+    """The arguments the two full-resolution chains share, checked before any device call -> (image, full_image)."""
+    from ._engine import check_closed_form_args, check_closed_form_shape, check_lift_args
+    image, full = _check_image(image), _check_image(full_image)
+    check_closed_form_args(radius, eps, band, max_iter, tol)
+    check_closed_form_args(radius, eps, band, full_max_iter, tol)
+    check_closed_form_shape(*image.shape[:2], radius)
+    try:
+        check_lift_args((1, *image.shape[:2]), None, full.shape[:2], grow)
+    except ValueError as e:
+        raise ValueError(str(e).replace("lift_trimap", what)) from None
+    return image, full
+
+
+def _full_solve_result(eng, bgr_full, trimap, alpha, radius, eps, grow, full_max_iter, tol, return_info):
+    a_full, _, iters, rel = eng.closed_form_full(bgr_full, trimap, alpha, bgr_full, radius, eps, grow, full_max_iter, tol)
+    a = a_full[0].cpu().numpy()
+    return (a, int(iters[0].item()), float(rel[0].item())) if return_info else a
+
+
+def closed_form_matte_full(image: np.ndarray, mask: np.ndarray, full_image: np.ndarray, radius: int = CF_RADIUS,
+                           eps: float = CF_EPS, band: int = CF_BAND, max_iter: int = CF_MAX_ITER, tol: float = CF_TOL,
+                           grow: int = CF_GROW, full_max_iter: int = CF_FULL_MAX_ITER, return_info: bool = False,
+                           device="cuda"):
+    """The closed-form matte of a working-size mask, solved again on the full-resolution image (additive; DESIGN.md
+    §5.17).  Four steps, all on the device: closed_form_matte(image, mask, radius, eps, band, max_iter, tol); the band
+    that solve ran on written as a trimap (128 on the band, else 255 mask; ggc_closed_form_band); that trimap and the
+    solved alpha lifted to full_image's size (lift_trimap with grow); and the warm solve there
+    (trimap_matte_warm(full_image, lifted trimap, lifted alpha, max_iter=full_max_iter)), which sees the
+    full image's colours where upsample_mask can only interpolate coefficients.
+
+    image: (H, W, 3) uint8 BGR; mask: (H, W) in {0, 1}; full_image: (H1, W1, 3) uint8 BGR, H <= H1 <= 32768 and
+    W <= W1 <= 32768; grow in 0..64 (0: growing the lifted region did not help in the study); full_max_iter in
+    1..100000 (an image that reaches it reports it in the iterations).
+    -> (H1, W1) float32 in [0, 1]; with return_info, (alpha, iterations, relative residual) of the full-size solve."""
+    from ._engine import get_engine
+    image, full = _check_full_solve(image, full_image, radius, eps, band, max_iter, tol, grow, full_max_iter,
+                                    "closed_form_matte_full")
+    m = np.asarray(mask)
+    if m.shape != image.shape[:2]:
+        raise ValueError(f"closed_form_matte_full: mask {m.shape} does not match image {image.shape[:2]}")
+    if m.size and not np.isin(m, (0, 1)).all():
+        raise ValueError("closed_form_matte_full: mask values must be 0 or 1")
+    eng = get_engine(device)
+    binary = eng.to_device(np.ascontiguousarray(m, np.uint8)[None])
+    alpha, _, _ = eng.closed_form_matte(eng.to_device(image[None]), binary, radius, eps, band, max_iter, tol)
+    return _full_solve_result(eng, eng.to_device(full[None]), eng.closed_form_band(binary, band), alpha, radius, eps, grow,
+                              full_max_iter, tol, return_info)
+
+
+def trimap_matte_full(image: np.ndarray, trimap: np.ndarray, full_image: np.ndarray, radius: int = CF_RADIUS,
+                      eps: float = CF_EPS, max_iter: int = CF_MAX_ITER, tol: float = CF_TOL, grow: int = CF_GROW,
+                      full_max_iter: int = CF_FULL_MAX_ITER, return_info: bool = False, device="cuda"):
+    """closed_form_matte_full from a caller's working-size trimap (additive): trimap_matte(image, trimap) at the working
+    size, that trimap and alpha lifted to full_image's size (lift_trimap with grow), and the warm solve there.
+
+    trimap: (H, W) uint8, 255 = foreground, 0 = background, every other byte unknown; the rest as
+    closed_form_matte_full.
+    -> (H1, W1) float32 in [0, 1]; with return_info, (alpha, iterations, relative residual) of the full-size solve."""
+    from ._engine import get_engine
+    image, full = _check_full_solve(image, full_image, radius, eps, 0, max_iter, tol, grow, full_max_iter,
+                                    "trimap_matte_full")
+    t = np.asarray(trimap)
+    if t.shape != image.shape[:2]:
+        raise ValueError(f"trimap_matte_full: trimap {t.shape} does not match image {image.shape[:2]}")
+    if t.dtype != np.uint8:
+        raise ValueError(f"trimap_matte_full: trimap must be uint8 (255 foreground, 0 background, else unknown), got {t.dtype}")
+    eng = get_engine(device)
+    tri = eng.to_device(np.ascontiguousarray(t)[None])
+    alpha, _, _ = eng.trimap_matte(eng.to_device(image[None]), tri, radius, eps, max_iter, tol)
+    return _full_solve_result(eng, eng.to_device(full[None]), tri, alpha, radius, eps, grow, full_max_iter, tol, return_info)
 
 
 FG_EPS_R = 5e-3
@@ -450,13 +577,22 @@ def _full_buffers(eng, full_bgr, compose: bool, mat) -> "Optional[dict]":
     return out
 
 
-def _full_post(leng, lo, hi, bgr, cleaned, full_bgr, full, fmat) -> None:
+def _full_post(leng, lo, hi, bgr, cleaned, full_bgr, full, fmat, cfm=None, cff=None, work_alpha=None) -> None:
     """The full-resolution outputs of images lo:hi from their cleaned working masks: ggc_upsample_matte, then
-    ggc_compose_outputs on the full image and the upsampled mask."""
+    ggc_compose_outputs on the full image and the upsampled mask.  With cff (ClosedFormMatte(full_resolution=True): its
+    grow and full_max_iter, next to cfm) the alpha comes from the full-size closed-form solve instead, warm from the
+    working-size alpha work_alpha on its lifted band, and the mask is that alpha >= 0.5 (closed_form_matte_full)."""
+    import torch
     alpha, soft = full.get("alpha"), full.get("rgba_soft")
-    leng.upsample_matte(bgr[lo:hi], cleaned[lo:hi], full_bgr[lo:hi], *fmat,
-                        out=(None if alpha is None else alpha[lo:hi], full["binary_mask"][lo:hi],
-                             None if soft is None else soft[lo:hi]))
+    if cff:
+        radius, eps, band, _, tol = cfm
+        leng.closed_form_full(bgr[lo:hi], leng.closed_form_band(cleaned[lo:hi], band), work_alpha[lo:hi], full_bgr[lo:hi],
+                              radius, eps, cff[0], cff[1], tol, out=(alpha[lo:hi], soft[lo:hi]))
+        full["binary_mask"][lo:hi].copy_(torch.ge(alpha[lo:hi], 0.5))
+    else:
+        leng.upsample_matte(bgr[lo:hi], cleaned[lo:hi], full_bgr[lo:hi], *fmat,
+                            out=(None if alpha is None else alpha[lo:hi], full["binary_mask"][lo:hi],
+                                 None if soft is None else soft[lo:hi]))
     if "overlay" in full:
         leng.compose(full_bgr[lo:hi], full["binary_mask"][lo:hi], out=(full["overlay"][lo:hi], full["rgba"][lo:hi]))
 
@@ -469,16 +605,30 @@ def _full_result(full: dict, i: int) -> FullResolution:
 
 def _closed_form_args(matte, h: int, w: int, full: bool) -> "Optional[tuple[int, float, int, int, float]]":
     """The closed-form matte's arguments when matte is a ClosedFormMatte (checked here, before any stage runs, with the
-    working size h x w, and refused together with full-resolution outputs), else None."""
+    working size h x w, and refused together with full-resolution outputs unless it asks for them itself), else None."""
     if not isinstance(matte, ClosedFormMatte):
         return None
     from ._engine import check_closed_form_args, check_closed_form_shape
-    if full:
-        raise ValueError("the closed-form matte is not carried to full resolution: use matte=True with full_image(s)")
+    if full and not matte.full_resolution:
+        raise ValueError("the closed-form matte is not carried to full resolution: use matte=True with full_image(s), "
+                         "or ask for the full-size solve with ClosedFormMatte(full_resolution=True)")
+    if matte.full_resolution and not full:
+        raise ValueError("ClosedFormMatte(full_resolution=True) needs the full image: pass full_image(s) / full_bgr")
     args = matte.args()
     check_closed_form_args(*args)
     check_closed_form_shape(h, w, args[0])
+    _closed_form_full_args(matte)
     return args
+
+
+def _closed_form_full_args(matte) -> "Optional[tuple[int, int]]":
+    """(grow, full_max_iter) when matte is a ClosedFormMatte(full_resolution=True) (checked here), else None."""
+    if not (isinstance(matte, ClosedFormMatte) and matte.full_resolution):
+        return None
+    from ._engine import check_closed_form_args, check_lift_args
+    check_closed_form_args(matte.radius, matte.eps, matte.band, matte.full_max_iter, matte.tol)
+    check_lift_args((1, 1, 1), None, (1, 1), matte.grow)
+    return int(matte.grow), int(matte.full_max_iter)
 
 
 def _foreground_args(foreground, matte, full: bool) -> "Optional[tuple[float, float, int, float]]":
@@ -673,7 +823,9 @@ class GCNGrabCutPipeline:
         matte=True (additive) also returns "alpha" (B,H,W) float32, the soft matte of the cleaned mask (alpha_matte with
         matte_radius / matte_eps), and "rgba_soft" (B,H,W,4) uint8, the cut-out with that alpha.  Every other output is
         the same as without it.  matte=ClosedFormMatte(...) fills the same two outputs with closed_form_matte of the
-        cleaned mask instead (matte_radius / matte_eps do not apply); it cannot be combined with full_bgr.
+        cleaned mask instead (matte_radius / matte_eps do not apply); it cannot be combined with full_bgr unless it says
+        full_resolution=True, and then "full" holds "alpha" and "rgba_soft" of closed_form_matte_full and "binary_mask"
+        = that alpha >= 0.5 (with "overlay" / "rgba" composed from it); every working-size output stays the same.
 
         foreground=True or ForegroundColours(...) (additive, needs a matte) also returns "foreground" (B,H,W,3) uint8,
         the estimated foreground colours under that matte's alpha (estimate_foreground), and "rgba_clean" (B,H,W,4)
@@ -715,12 +867,13 @@ class GCNGrabCutPipeline:
         mat = None if cfm else _matte_args(matte, matte_radius, matte_eps)
         fmat = _full_args(full_bgr, bgr.shape, matte_radius, matte_eps)
         fga = _foreground_args(foreground, matte, full_bgr is not None)
+        cff = _closed_form_full_args(matte) if cfm else None
         if n_chunks <= 0:                          # 0: one chunk per GrabCut lane once every chunk gets a lane's worth of images
             n_chunks = max(want, 1) if b >= 16 * max(want, 1) else 1
         if n_chunks > 1 and b >= 2 * n_chunks:
             return self._segment_pipelined(bgr, self.chunk_plan(b, n_chunks, self.chunk_ratio), cs, threshold_fg, threshold_bg,
                                            refine_iters, min_area_ratio, keep_largest, edge_aware, filter_radius, compose, timing,
-                                           hints, return_state, mat, full_bgr, fmat, cfm, fga)
+                                           hints, return_state, mat, full_bgr, fmat, cfm, fga, cff)
 
         def tick():
             if timing is not None:
@@ -741,7 +894,7 @@ class GCNGrabCutPipeline:
         rgba = eng.empty(*bgr.shape[:3], 4, dtype=torch.uint8) if compose else None
         alpha = eng.empty(*bgr.shape[:3]) if (mat or cfm) else None
         rgba_soft = eng.empty(*bgr.shape[:3], 4, dtype=torch.uint8) if (mat or cfm) else None
-        full = _full_buffers(eng, full_bgr, compose, mat)
+        full = _full_buffers(eng, full_bgr, compose, mat or cff)
         fg_col = eng.empty(*bgr.shape[:3], 3, dtype=torch.uint8) if fga else None
         rgba_clean = eng.empty(*bgr.shape[:3], 4, dtype=torch.uint8) if fga else None
 
@@ -754,7 +907,7 @@ class GCNGrabCutPipeline:
             if fga:
                 leng.estimate_foreground(bgr[lo:hi], alpha[lo:hi], *fga, out=(fg_col[lo:hi], rgba_clean[lo:hi]))
             if full is not None:
-                _full_post(leng, lo, hi, bgr, cleaned, full_bgr, full, fmat)
+                _full_post(leng, lo, hi, bgr, cleaned, full_bgr, full, fmat, cfm, cff, alpha)
 
         fused_post = timing is None
         binary, mask, bgd, fgd = eng.grabcut_lanes(gc_img, mask, self.gc_config.n_iter, 0, self.gc_config.seed, lanes,
@@ -786,7 +939,7 @@ class GCNGrabCutPipeline:
 
     def _segment_pipelined(self, bgr, plan, cs, threshold_fg, threshold_bg, refine_iters, min_area_ratio, keep_largest,
                            edge_aware, filter_radius, compose, timing, hints=None, return_state=False, mat=None,
-                           full_bgr=None, fmat=None, cfm=None, fga=None) -> dict:
+                           full_bgr=None, fmat=None, cfm=None, fga=None, cff=None) -> dict:
         """The software pipeline behind segment_batch_device: chunk k's GrabCut lane starts as soon as chunk k's trimaps are
         on the device; the caller's stream goes on with chunk k+1's SLIC / graph / network / trimap."""
         import torch
@@ -810,7 +963,7 @@ class GCNGrabCutPipeline:
         rgba = eng.empty(b, h, w, 4, dtype=torch.uint8) if compose else None
         alpha = eng.empty(b, h, w) if (mat or cfm) else None
         rgba_soft = eng.empty(b, h, w, 4, dtype=torch.uint8) if (mat or cfm) else None
-        full = _full_buffers(eng, full_bgr, compose, mat)
+        full = _full_buffers(eng, full_bgr, compose, mat or cff)
         fg_col = eng.empty(b, h, w, 3, dtype=torch.uint8) if fga else None
         rgba_clean = eng.empty(b, h, w, 4, dtype=torch.uint8) if fga else None
         if return_state:
@@ -851,7 +1004,7 @@ class GCNGrabCutPipeline:
                 if fga:
                     leng.estimate_foreground(img, alpha[lo:hi], *fga, out=(fg_col[lo:hi], rgba_clean[lo:hi]))
                 if full is not None:
-                    _full_post(leng, lo, hi, bgr, cleaned, full_bgr, full, fmat)
+                    _full_post(leng, lo, hi, bgr, cleaned, full_bgr, full, fmat, cfm, cff, alpha)
                 if ev is not None:
                     ev[2].record(stream)
                 done = torch.cuda.Event()
@@ -1050,8 +1203,9 @@ class GCNGrabCutPipeline:
         GrabCut starts from (see segment_batch_device for hint_radius, hint_region and hints_as_prior); matte=True also
         fills the result's alpha and rgba_soft (segment_batch_device), matte=ClosedFormMatte(...) with the closed-form
         matte; full_image, the same image at a larger size, fills
-        the result's `full` (segment_batch_device's full_bgr); foreground=True | ForegroundColours(...), with a matte,
-        fills the result's foreground and rgba_clean (estimate_foreground under that matte's alpha)."""
+        the result's `full` (segment_batch_device's full_bgr; with matte=ClosedFormMatte(full_resolution=True) its
+        alpha, rgba_soft and binary_mask come from closed_form_matte_full); foreground=True | ForegroundColours(...),
+        with a matte, fills the result's foreground and rgba_clean (estimate_foreground under that matte's alpha)."""
         image = _check_image(image)
         _closed_form_args(matte, *image.shape[:2], full_image is not None)
         _foreground_args(foreground, matte, full_image is not None)
@@ -1080,7 +1234,8 @@ class GCNGrabCutPipeline:
         """Classical GrabCut with a bounding box (reference pipeline.py:354-380).  Additive: matte=True also fills the
         result's alpha and rgba_soft, the soft matte of the returned mask (alpha_matte; closed_form_matte with
         matte=ClosedFormMatte(...)); full_image, the same image at a
-        larger size, fills the result's `full` from the returned mask (upsample_mask, then the overlay and cut-out);
+        larger size, fills the result's `full` from the returned mask (upsample_mask, then the overlay and cut-out;
+        closed_form_matte_full with matte=ClosedFormMatte(full_resolution=True));
         foreground=True | ForegroundColours(...), with a matte, fills the result's foreground and rgba_clean."""
         image = _check_image(image)
         cfm = _closed_form_args(matte, *image.shape[:2], full_image is not None)
@@ -1119,9 +1274,11 @@ class GCNGrabCutPipeline:
         if full_img is not None:
             eng = self._eng
             full_bgr = eng.to_device(full_img[None])
-            bufs = _full_buffers(eng, full_bgr, True, mat)
+            cff = _closed_form_full_args(matte) if cfm else None
+            bufs = _full_buffers(eng, full_bgr, True, mat or cff)
             _full_post(eng, 0, 1, eng.to_device(image[None]), eng.to_device(np.ascontiguousarray(binary_mask, np.uint8)[None]),
-                       full_bgr, bufs, fmat)
+                       full_bgr, bufs, fmat, cfm, cff,
+                       None if not cff else eng.to_device(np.ascontiguousarray(alpha, np.float32)[None]))
             full = _full_result(bufs, 0)
         return SegmentationResult(image=image, binary_mask=binary_mask, trimap=trimap,
                                   segments=np.zeros((H, W), dtype=np.int32), overlay=gc.overlay_mask(),

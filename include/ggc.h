@@ -51,7 +51,10 @@
 extern "C" {
 #endif
 
-#define GGC_VERSION 401 /* 0.4.1: ggc_trimap_matte (closed-form alpha matte on the unknown region of a caller's trimap; one solver with
+#define GGC_VERSION 402 /* 0.4.2: ggc_lift_trimap, ggc_trimap_matte_warm, ggc_closed_form_band (a working-size closed-form matte carried to a
+                                  larger image: lifted trimap and start, a stop rule that does not move with the start; the two
+                                  existing closed-form entries do not change);
+                           0.4.1: ggc_trimap_matte (closed-form alpha matte on the unknown region of a caller's trimap; one solver with
                                   ggc_closed_form_matte, whose results do not change);
                            0.4.0: ggc_matte_errors (SAD, MSE, gradient and connectivity error of an alpha matte against the true one);
                            0.3.9: ggc_estimate_foreground (foreground colours under an alpha matte: clean cut-outs, PCG on the device);
@@ -514,6 +517,54 @@ int ggc_closed_form_matte(ggc_ctx* ctx, ggc_stream stream, int B, int H, int W, 
 int ggc_trimap_matte(ggc_ctx* ctx, ggc_stream stream, int B, int H, int W, const uint8_t* bgr, const uint8_t* trimap,
                      int radius, float eps, int max_iter, float tol, const float* alpha0,
                      float* alpha, uint8_t* rgba, double* raw, int32_t* iters, double* rel_residual);
+
+/* O3w — O3t with a stop rule that does not move with the start (additive; for warm starts).  O3t stops an image on
+ * ||r_j|| <= tol ||r_0|| with r_0 the residual of its own start: a good start has a small r_0 and earns nothing.  Here
+ * the reference is the residual of the 0.5 start, whatever alpha0 holds:
+ *   r_ref     = -(L x^1/2)_U, x^1/2 the known values off U and 0.5 on U: one more application of L in the set-up
+ *   stop      an image stops when ||r_j||_2 <= tol ||r_ref||_2 or after max_iter iterations; the test is made on r_0 too,
+ *             so a start that is already good enough comes back as it is, with 0 iterations
+ *   trivial   the cases of O3t with r_ref = 0 in the place of r_0 = 0
+ *   rel_residual = ||r_j|| / ||r_ref|| (||r_0|| / ||r_ref|| for an image that stopped on its start, 0 for a trivial one)
+ * alpha0 is required (NULL is GGC_E_INVALID_ARG); every other argument, limit, error code and output is O3t's.  The
+ * system, the CG and its kernels are O3t's; only the number an image's residual is divided by differs.  With alpha0 = 0.5
+ * on U every output equals ggc_trimap_matte(alpha0 = NULL) bit for bit.  Reductions, batch independence, atomics and the
+ * synchronisation of the stream are O3's.
+ * Scratch: 145 bytes per pixel plus 28 bytes per 16 x 16 tile and 56 bytes per image, from the context (the reference
+ * pass reuses the set-up's arrays). */
+int ggc_trimap_matte_warm(ggc_ctx* ctx, ggc_stream stream, int B, int H, int W, const uint8_t* bgr, const uint8_t* trimap,
+                          int radius, float eps, int max_iter, float tol, const float* alpha0,
+                          float* alpha, uint8_t* rgba, double* raw, int32_t* iters, double* rel_residual);
+
+/* O3l — a working-size trimap and alpha carried to a larger size (additive): the trimap and the start of a closed-form
+ * solve on the full image (O3w) from a solve at the working size.
+ *   trimap [dev] u8 [B,H,W] (255 foreground, 0 background, any other byte unknown)   alpha [dev] f32 [B,H,W]
+ *   H <= H1 <= 32768, W <= W1 <= 32768, H, W >= 1, B <= 65535 (else GGC_E_SHAPE); 0 <= grow <= 64 (else
+ *   GGC_E_INVALID_ARG); B == 0 does nothing
+ * For output pixel (y, x) the source pixels (y0|y1, x0|x1) and the weights wy, wx are those of ggc_upsample_matte (O2),
+ * its float64 half-pixel formula word for word.
+ *   trimap_full [dev] u8 [B,H1,W1]  255 if every source pixel of nonzero weight is 255, 0 if every one is 0, else 128
+ *               (x1 counts when wx > 0, y1 when wy > 0: a pixel that does not enter the interpolation does not make its
+ *               neighbour unknown); the 128 set is then dilated by `grow` full-size pixels (Chebyshev, clipped to the image)
+ *   alpha0_full [dev] f32 [B,H1,W1] = (float) lerp(lerp(a00, a01, wx), lerp(a10, a11, wx), wy), a = clamp((double)alpha,
+ *               0, 1) with a NaN read as 0, lerp(u, v, t) = u + t (v - u) in float64, no contraction
+ *   (either output may be NULL, not both; trimap is not read without trimap_full, alpha not without alpha0_full)
+ * With H1 = H, W1 = W and grow = 0 every weight is 0: trimap_full is the trimap with every unknown byte written as 128,
+ * alpha0_full the clamped alpha bit for bit.  A known pixel of trimap_full has a known nearest source pixel of the same
+ * value.  No atomics; every image is independent of its batch.  Scratch: 2 bytes per full-size pixel from the context
+ * when grow > 0 and trimap_full is given, else none.  Does not synchronise. */
+int ggc_lift_trimap(ggc_ctx* ctx, ggc_stream stream, int B, int H, int W, const uint8_t* trimap, const float* alpha,
+                    int H1, int W1, int grow, uint8_t* trimap_full, float* alpha0_full);
+
+/* O3b — the unknown band of O3 as a trimap (additive): what ggc_closed_form_matte(binary, band) solved on, written by the
+ * kernels of its own front end, so that a later entry (O3l) starts from the solver's band and not from a restatement.
+ *   binary [dev] u8 [B,H,W] (any nonzero byte is 1)   0 <= band <= 64 (else GGC_E_INVALID_ARG); H, W >= 1, H, W <= 32768,
+ *   B <= 65535 (else GGC_E_SHAPE); B == 0 does nothing
+ *   trimap [dev] u8 [B,H,W] = 128 on O3's U, else 255 (binary != 0) (NULL is GGC_E_INVALID_ARG)
+ * ggc_trimap_matte with this trimap and alpha0 = (binary != 0) equals ggc_closed_form_matte bit for bit (O3t).  No atomics.
+ * Scratch: 2 bytes per pixel from the context.  Does not synchronise. */
+int ggc_closed_form_band(ggc_ctx* ctx, ggc_stream stream, int B, int H, int W, const uint8_t* binary, int band,
+                         uint8_t* trimap);
 
 /* O4 — foreground colour estimation under a given alpha matte (additive; the multi-level foreground estimation energy of
  * Germer, Uelwer, Conrad and Harmeling, ICPR 2020, restricted to the pixels of fractional alpha with Dirichlet values).

@@ -10,6 +10,7 @@ Same command line as the reference's inference.py (flags :26-56, outputs :146-15
     python3 inference.py --image cat.jpg --save mask alpha cutout          # soft edges: alpha matte and cut-out
     python3 inference.py --image big.jpg --full-res --save mask cutout     # outputs at the photo's own size
     python3 inference.py --image cat.jpg --matte-method closed-form --save alpha cutout   # closed-form matte
+    python3 inference.py --image big.jpg --full-res --matte-method closed-form-full --save alpha cutout   # ... solved at the photo's own size
 
 Images are decoded / written with Pillow (OpenCV is not a dependency of this build); folders are processed in
 batches of equally sized images so that the whole batch stays resident in HBM.
@@ -60,15 +61,21 @@ def build_parser() -> argparse.ArgumentParser:
                         help="Window radius of the alpha matte, 1..64, in pixels of the image as segmented")
     parser.add_argument("--matte-eps", type=float, default=1e-4, help="Regularisation of the alpha matte (>= 1e-12)")
     # additive: the closed-form matte (ggc_closed_form_matte) instead of the guided one; its own window and regulariser
-    parser.add_argument("--matte-method", choices=["guided", "closed-form"], default="guided",
+    parser.add_argument("--matte-method", choices=["guided", "closed-form", "closed-form-full"], default="guided",
                         help="How alpha / cutout are computed: guided-filter feathering of the mask (--matte-radius, "
-                             "--matte-eps) or the closed-form matte solved on a band around its edge (--cf-* flags)")
+                             "--matte-eps), the closed-form matte solved on a band around its edge (--cf-* flags), or "
+                             "that matte solved again at the original size from the working-size one (closed-form-full: "
+                             "needs --full-res; --cf-grow, --cf-full-iters)")
     parser.add_argument("--cf-radius", type=int, default=1, help="Window radius of the closed-form matte, 1..8")
     parser.add_argument("--cf-eps", type=float, default=1e-5, help="Regularisation of the closed-form matte, [1e-12, 1]")
     parser.add_argument("--cf-band", type=int, default=1,
                         help="Half-width in pixels of the unknown band around the mask's edge, 0..64")
     parser.add_argument("--cf-iters", type=int, default=500, help="Most conjugate-gradient iterations per image")
     parser.add_argument("--cf-tol", type=float, default=1e-4, help="Stop when the residual falls to this fraction")
+    parser.add_argument("--cf-grow", type=int, default=0,
+                        help="closed-form-full: pixels of the original size the lifted unknown band is grown by, 0..64")
+    parser.add_argument("--cf-full-iters", type=int, default=2000,
+                        help="closed-form-full: most conjugate-gradient iterations per image at the original size")
     # additive: foreground colours under the matte (ggc_estimate_foreground), so that the cut-out carries no old background
     parser.add_argument("--decontaminate", action="store_true",
                         help="Write the cut-out (--save cutout) with estimated foreground colours where alpha is "
@@ -162,15 +169,20 @@ def main() -> None:
     if (matte or args.full_res) and not args.matte_eps >= 1e-12:
         parser.error("--matte-eps must be >= 1e-12")
     closed_form = None
-    if matte and args.matte_method == "closed-form":
-        if args.full_res:
-            parser.error("--matte-method closed-form is not carried to the original size: drop --full-res, or use "
-                         "--matte-method guided")
-        from src.gcn_grabcut.pipeline import ClosedFormMatte
+    if args.matte_method == "closed-form-full" and not args.full_res:
+        parser.error("--matte-method closed-form-full solves at the original size: add --full-res")
+    if matte and args.matte_method in ("closed-form", "closed-form-full"):
+        full_solve = args.matte_method == "closed-form-full"
+        if args.full_res and not full_solve:
+            parser.error("--matte-method closed-form is not carried to the original size: drop --full-res, use "
+                         "--matte-method guided, or solve there with --matte-method closed-form-full")
+        from src.gcn_grabcut.pipeline import ClosedFormMatte, _closed_form_full_args
         from src.gcn_grabcut._engine import check_closed_form_args
-        closed_form = ClosedFormMatte(args.cf_radius, args.cf_eps, args.cf_band, args.cf_iters, args.cf_tol)
+        closed_form = ClosedFormMatte(args.cf_radius, args.cf_eps, args.cf_band, args.cf_iters, args.cf_tol,
+                                      full_resolution=full_solve, grow=args.cf_grow, full_max_iter=args.cf_full_iters)
         try:
             check_closed_form_args(*closed_form.args())
+            _closed_form_full_args(closed_form)
         except ValueError as e:
             parser.error(str(e))
     foreground = None
@@ -231,8 +243,10 @@ def main() -> None:
                 hint_kw = dict(hints=[(scale_points(args.fg_point, orig_hw, image.shape[:2]),
                                        scale_points(args.bg_point, orig_hw, image.shape[:2]))],
                                hint_radius=args.hint_radius)
-            if closed_form is not None:
-                hint_kw.update(matte=closed_form)
+            if closed_form is not None:                 # an image within --max-size is already solved at its own size
+                import dataclasses
+                hint_kw.update(matte=closed_form if chunk[0][2] is not None else
+                               dataclasses.replace(closed_form, full_resolution=False))
             elif matte:
                 hint_kw.update(matte=True, matte_radius=args.matte_radius, matte_eps=args.matte_eps)
             if foreground is not None:

@@ -4,12 +4,17 @@ matte.py — alpha mattes from images and trimaps with the closed-form matte on 
     python3 matte.py --image cat.jpg --trimap cat_trimap.png
     python3 matte.py --input data/images --trimaps data/trimaps --output mattes/ --save alpha cutout
     python3 matte.py --image cat.jpg --trimap cat_trimap.png --save cutout --decontaminate
+    python3 matte.py --image cat_small.jpg --trimap cat_small_trimap.png --full-image cat.jpg   # solved at cat.jpg's size
 
 A trimap is an 8-bit grey image of the photo's size: 255 = foreground, 0 = background, every other byte unknown (the
 convention of the matting benchmarks and of evaluate_matte.py --trimaps).  The matting Laplacian is solved on the
 unknown pixels (gcn_grabcut.trimap_matte, ggc_trimap_matte; DESIGN.md §5.16).  With --input, trimaps are matched by stem;
 images of one size are solved as one batch.  Outputs are named as inference.py names them: <stem>_alpha.png (8-bit grey)
 and <stem>_cutout.png (BGRA cut-out with that alpha).
+
+With --full-image (or --full-images DIR, matched by stem) the image and trimap are the working-size version of a larger
+photo: the matte is solved at the working size, lifted, and solved again on the larger photo from there
+(gcn_grabcut.trimap_matte_full), and the outputs have the larger photo's size.
 """
 import argparse
 import sys
@@ -38,6 +43,13 @@ def build_parser() -> argparse.ArgumentParser:
     parser.add_argument("--cf-eps", type=float, default=1e-5, help="Regularisation of the closed-form matte, [1e-12, 1]")
     parser.add_argument("--cf-iters", type=int, default=500, help="Most conjugate-gradient iterations per image")
     parser.add_argument("--cf-tol", type=float, default=1e-4, help="Stop when the residual falls to this fraction")
+    parser.add_argument("--full-image", default=None,
+                        help="The photo of --image at a larger size: solve there too, from the working-size matte")
+    parser.add_argument("--full-images", default=None, help="Directory of larger versions of --input, matched by stem")
+    parser.add_argument("--cf-grow", type=int, default=0,
+                        help="With a full image: pixels of its size the lifted unknown region is grown by, 0..64")
+    parser.add_argument("--cf-full-iters", type=int, default=2000,
+                        help="With a full image: most conjugate-gradient iterations per image at its size")
     parser.add_argument("--decontaminate", action="store_true",
                         help="Write the cut-out (--save cutout) with estimated foreground colours where alpha is "
                              "fractional, instead of the image's own, so that it shows no halo on a new background")
@@ -55,9 +67,9 @@ def _read(path: Path, mode: str):
 
 
 def collect(args) -> list:
-    """(image path, trimap path) pairs."""
+    """(image path, trimap path, full image path or None) triples."""
     if args.image:
-        pairs = [(Path(args.image), Path(args.trimap))]
+        pairs = [(Path(args.image), Path(args.trimap), Path(args.full_image) if args.full_image else None)]
     else:
         in_dir, tri_dir = Path(args.input), Path(args.trimaps)
         for d, flag in ((in_dir, "--input"), (tri_dir, "--trimaps")):
@@ -70,9 +82,18 @@ def collect(args) -> list:
         for p in images:
             if p.stem not in tris:
                 raise SystemExit(f"{TAG} {p} has no trimap of the same stem in {tri_dir}")
-        pairs = [(p, tris[p.stem]) for p in images]
-    for p, t in pairs:
-        for f in (p, t):
+        fulls = {}
+        if args.full_images:
+            full_dir = Path(args.full_images)
+            if not full_dir.is_dir():
+                raise SystemExit(f"{TAG} --full-images directory {full_dir} does not exist")
+            fulls = {p.stem: p for p in sorted(full_dir.iterdir()) if p.suffix.lower() in IMAGE_EXTS}
+            for p in images:
+                if p.stem not in fulls:
+                    raise SystemExit(f"{TAG} {p} has no full image of the same stem in {full_dir}")
+        pairs = [(p, tris[p.stem], fulls.get(p.stem)) for p in images]
+    for p, t, full in pairs:
+        for f in (p, t) if full is None else (p, t, full):
             if not f.is_file():
                 raise SystemExit(f"{TAG} {f} does not exist")
     return pairs
@@ -85,21 +106,28 @@ def main() -> None:
         parser.error("--image goes with --trimap (one file), not --trimaps")
     if args.input and (args.trimaps is None or args.trimap is not None):
         parser.error("--input goes with --trimaps (a directory), not --trimap")
+    if args.image and args.full_images is not None:
+        parser.error("--image goes with --full-image (one file), not --full-images")
+    if args.input and args.full_image is not None:
+        parser.error("--input goes with --full-images (a directory), not --full-image")
     if args.decontaminate and "cutout" not in args.save:
         parser.error("--decontaminate changes the cut-out: add cutout to --save")
     if args.batch < 1:
         parser.error("--batch must be >= 1")
-    from src.gcn_grabcut._engine import check_closed_form_args, check_closed_form_shape, get_engine
+    from src.gcn_grabcut._engine import (check_closed_form_args, check_closed_form_shape, check_lift_args, get_engine)
     from src.gcn_grabcut.pipeline import ForegroundColours, _write_png, alpha_to_u8
     cf = (args.cf_radius, args.cf_eps, args.cf_iters, args.cf_tol)
     try:
         check_closed_form_args(cf[0], cf[1], 0, cf[2], cf[3])
+        check_closed_form_args(cf[0], cf[1], 0, args.cf_full_iters, cf[3])
+        check_lift_args((1, 1, 1), None, (1, 1), args.cf_grow)
     except ValueError as e:
         parser.error(str(e))
 
     by_shape: dict = {}
-    for path, tri in collect(args):
+    for path, tri, full_path in collect(args):
         image, trimap = _read(path, "RGB"), _read(tri, "L")
+        full = None if full_path is None else _read(full_path, "RGB")
         if trimap.shape != image.shape[:2]:
             raise SystemExit(f"{TAG} {tri} is {trimap.shape[1]}x{trimap.shape[0]} but {path} is "
                              f"{image.shape[1]}x{image.shape[0]}")
@@ -107,7 +135,12 @@ def main() -> None:
             check_closed_form_shape(*image.shape[:2], cf[0])
         except ValueError as e:
             raise SystemExit(f"{TAG} {path}: {e}")
-        by_shape.setdefault(image.shape, []).append((path, image, trimap))
+        if full is not None:
+            try:
+                check_lift_args((1, *trimap.shape), None, full.shape[:2], args.cf_grow)
+            except ValueError as e:
+                raise SystemExit(f"{TAG} {full_path}: {e}")
+        by_shape.setdefault((image.shape, None if full is None else full.shape), []).append((path, image, trimap, full))
 
     import torch
     if not torch.cuda.is_available():
@@ -120,14 +153,20 @@ def main() -> None:
         for i in range(0, len(items), args.batch):
             chunk = items[i:i + args.batch]
             t0 = time.perf_counter()
-            bgr = eng.to_device(np.stack([im for _, im, _ in chunk]))
-            tri = eng.to_device(np.stack([t for _, _, t in chunk]))
-            alpha, rgba, iters, rel = eng.trimap_matte(bgr, tri, *cf, want_rgba=True)
+            bgr = eng.to_device(np.stack([im for _, im, _, _ in chunk]))
+            tri = eng.to_device(np.stack([t for _, _, t, _ in chunk]))
+            if chunk[0][3] is None:
+                alpha, rgba, iters, rel = eng.trimap_matte(bgr, tri, *cf, want_rgba=True)
+            else:                                         # the working-size solve, the lift, the warm solve at full size
+                work_alpha = eng.trimap_matte(bgr, tri, *cf)[0]
+                bgr = eng.to_device(np.stack([f for _, _, _, f in chunk]))
+                alpha, rgba, iters, rel = eng.closed_form_full(bgr, tri, work_alpha, bgr, cf[0], cf[1], args.cf_grow,
+                                                               args.cf_full_iters, cf[3])
             if args.decontaminate:
                 rgba = eng.estimate_foreground(bgr, alpha, *ForegroundColours().args(), want_rgba=True)[1]
             alpha, rgba, iters, rel = alpha.cpu().numpy(), rgba.cpu().numpy(), iters.cpu().numpy(), rel.cpu().numpy()
             elapsed = (time.perf_counter() - t0) / len(chunk)
-            for j, (path, _, trimap) in enumerate(chunk):
+            for j, (path, _, trimap, _) in enumerate(chunk):
                 n_done += 1
                 total_t += elapsed
                 stem = out_dir / path.stem
