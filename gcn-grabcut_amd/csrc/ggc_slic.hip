@@ -6,7 +6,8 @@
 //   k_lab2          rescale to [0,1] and the second rgb2lab, float32
 //   k_gauss<axis>   separable Gaussian, f64 accumulation, y then x, * 1/compactness
 //   k_init_centers  regular-grid seeds, colour part 0
-//   10 x { k_slic_assign, k_slic_update }
+//   10 x k_slic_assign, with k_slic_update between two assignments (9 x): the
+//                   update skimage runs after the tenth assignment feeds nothing
 //   k_connectivity  skimage's raster-order connectivity enforcement
 //
 // Bit-exactness with the CPU path (integer label map) dictates the structure:
@@ -846,7 +847,7 @@ extern "C" int ggc_slic(ggc_ctx* ctx, ggc_stream stream, int B, int H, int W, co
             hipLaunchKernelGGL(k_slic_assign, dim3(cdiv(W, TILE_W), cdiv(H, TILE_H), B), dim3(256), 0, st, g, km_img,
                                centers, bounds, raw, stale + (size_t)it * B);
         }
-        {
+        if (it < 9) {                       // nothing reads the centres after the last assignment
             ProfScope prof(ctx, st, "slic_update");
             hipLaunchKernelGGL(k_slic_update, dim3(cdiv(g.K, 4 * UPD_GROUPS), B), dim3(256), 0, st, g, km_img, raw,
                                stale + (size_t)it * B, centers, bounds);
@@ -1135,7 +1136,8 @@ extern "C" int ggc_slic_rgb(ggc_ctx* ctx, ggc_stream stream, int B, int H, int W
     for (int it = 0; it < 10; ++it) {
         hipLaunchKernelGGL(k_slic_assign64, dim3(cdiv(W, 32), cdiv(H, 8), B), dim3(256), 0, st, g, sw, km_img, centers, bounds, raw,
                            stale + (size_t)it * B);
-        hipLaunchKernelGGL(k_slic_update64, dim3(cdiv(g.K, 4 * UPD_GROUPS), B), dim3(256), 0, st, g, km_img, raw, stale + (size_t)it * B,
+        if (it < 9)
+            hipLaunchKernelGGL(k_slic_update64, dim3(cdiv(g.K, 4 * UPD_GROUPS), B), dim3(256), 0, st, g, km_img, raw, stale + (size_t)it * B,
                            centers, bounds);
         GGC_LAUNCH_CHECK(ctx);
     }

@@ -15,6 +15,8 @@
 // HBM layout: planes [plane][B][H*W]; the six first-stage planes (g, s_bg, s_fg,
 // g*g, g*s_bg, g*s_fg) are blurred together, then the four (a, b) planes.  The
 // guide statistics are shared between the BG and FG filters (10 blurs, not 14).
+// For radius 1..8 the edge-aware trimap runs as two fused kernels (k_t_stage1,
+// k_t_stage2) in which only the four (a, b) planes exist in HBM.
 #include "ggc_internal.h"
 #include <cmath>
 
@@ -193,6 +195,165 @@ __global__ void __launch_bounds__(256) k_t_final(size_t BP, float thr_fg, float 
     trimap[i] = decide(b, f, thr_bg, thr_fg);
 }
 
+// ---- edge-aware trimap in two kernels for radius 1..8 (the pipeline uses 8)
+// A block owns a 32 x 32 output tile and keeps tile + halo in LDS, reflected coordinates applied at load.  Stage 1 builds
+// guide and projected probabilities there straight from bgr / segments / probs, box-filters the six planes of k_t_prep
+// one after the other (the products are formed as rounded f32 values when a tap is read) and finishes with k_t_ab's
+// arithmetic, so only the four (a, b) planes reach HBM.  Stage 2 box-filters those and finishes with k_t_final.  Every
+// sum is the fresh 2r+1-term f64 sum of the file header in the same order — row sums left to right, column sums top to
+// bottom, * 1/k^2, cast — so the trimap is bit-identical to the plane-by-plane route, which is kept for radius > 8.
+// LDS at radius 8: 3 x 48 x 49 floats + 48 x 33 doubles = 40,896 B, four blocks per CU.
+constexpr int FT = 32;
+
+__device__ __forceinline__ float guide_of(const uint8_t* __restrict__ px) {
+    const int g8 = (px[0] * 3735 + px[1] * 19235 + px[2] * 9798 + (1 << 14)) >> 15;
+    return (float)g8 / (float)255.0;
+}
+
+// reflected source column / row of every halo column / row of the tile, once per block (tab: 2 * iw ints)
+template <int radius>
+__device__ __forceinline__ void ft_coords(const TDims& d, int* tab) {
+    constexpr int iw = FT + 2 * radius;
+    const int t = threadIdx.x;
+    // rows / columns past the image edge are never used by an in-image output, clamp them into range first
+    if (t < iw) tab[t] = refl101(min((int)blockIdx.x * FT + t - radius, d.W - 1 + radius), d.W);
+    else if (t >= 64 && t < 64 + iw) tab[iw + t - 64] = refl101(min((int)blockIdx.y * FT + t - 64 - radius, d.H - 1 + radius), d.H);
+}
+
+// f64 row sums of one plane of the tile: 8 adjacent outputs per work item share their 2r+8 taps
+template <int radius, typename Tap>
+__device__ __forceinline__ void ft_row_sums(double (*s_rs)[FT + 1], Tap tap) {
+    constexpr int ih = FT + 2 * radius;
+    for (int w = threadIdx.x; w < ih * (FT / 8); w += 256) {
+        const int ly = w / (FT / 8), x8 = (w - ly * (FT / 8)) * 8;
+        double v[2 * radius + 8];
+#pragma unroll
+        for (int j = 0; j < 2 * radius + 8; ++j) v[j] = (double)tap(ly, x8 + j);
+#pragma unroll
+        for (int o = 0; o < 8; ++o) {
+            double sum = 0.0;
+#pragma unroll
+            for (int j = 0; j <= 2 * radius; ++j) sum += v[o + j];
+            s_rs[ly][x8 + o] = sum;
+        }
+    }
+}
+
+// column sums, scale, cast: thread t owns column t % 32, rows 4 (t / 32) .. + 3 of the tile
+template <int radius>
+__device__ __forceinline__ void ft_col_means(const double (*s_rs)[FT + 1], float* out) {
+    const int x = threadIdx.x % FT, y4 = (threadIdx.x / FT) * 4;
+    const int k = 2 * radius + 1;
+    const double scale = 1.0 / ((double)k * (double)k);
+    double v[2 * radius + 4];
+#pragma unroll
+    for (int j = 0; j < 2 * radius + 4; ++j) v[j] = s_rs[y4 + j][x];
+#pragma unroll
+    for (int o = 0; o < 4; ++o) {
+        double sum = 0.0;
+#pragma unroll
+        for (int j = 0; j <= 2 * radius; ++j) sum += v[o + j];
+        out[o] = (float)(sum * scale);
+        // pin the mean here: otherwise the compiler sinks the sums of every plane into the caller's in-image branch
+        // and carries all their taps (spilled) to the end of the kernel
+        asm volatile("" : "+v"(out[o]));
+    }
+}
+
+template <int radius>
+__global__ void __launch_bounds__(256, 4) k_t_stage1(TDims d, float eps, const float* __restrict__ probs,
+                                                  const int32_t* __restrict__ node_ptr, const int32_t* __restrict__ seg,
+                                                  const uint8_t* __restrict__ bgr, float* __restrict__ ab /*4 planes*/) {
+    constexpr int iw = FT + 2 * radius;
+    __shared__ float s_g[iw][iw + 1], s_pb[iw][iw + 1], s_pf[iw][iw + 1];
+    __shared__ double s_rs[iw][FT + 1];
+    const int tid = threadIdx.x, b = blockIdx.z;
+    const size_t P = (size_t)d.H * d.W, BP = P * d.B;
+    int* tab = reinterpret_cast<int*>(&s_rs[0][0]);            // free until the first row sums
+    ft_coords<radius>(d, tab);
+    __syncthreads();
+    const int n0 = node_ptr[b], n = node_ptr[b + 1] - n0;
+    for (int i = tid; i < iw * iw; i += 256) {
+        const int ly = i / iw, lx = i - ly * iw;
+        const size_t p = (size_t)b * P + (size_t)tab[iw + ly] * d.W + tab[lx];
+        const int s = seg[p];
+        float pb = 0.0f, pf = 0.0f;                 // project_to_pixels zero-pads missing regions
+        if (s >= 0 && s < n) { pb = probs[(size_t)(n0 + s) * 3 + 0]; pf = probs[(size_t)(n0 + s) * 3 + 2]; }
+        s_g[ly][lx] = guide_of(bgr + p * 3);
+        s_pb[ly][lx] = pb;
+        s_pf[ly][lx] = pf;
+    }
+    __syncthreads();
+    float m[6][4];                                  // means of g, s_bg, s_fg, g*g, g*s_bg, g*s_fg at this thread's 4 pixels
+#define GGC_PLANE(I, EXPR)                                                                  \
+    ft_row_sums<radius>(s_rs, [&](int y, int x) -> float { return EXPR; });                \
+    __syncthreads();                                                                        \
+    ft_col_means<radius>(s_rs, m[I]);                                                       \
+    __syncthreads();
+    GGC_PLANE(0, s_g[y][x])
+    GGC_PLANE(1, s_pb[y][x])
+    GGC_PLANE(2, s_pf[y][x])
+    GGC_PLANE(3, s_g[y][x] * s_g[y][x])
+    GGC_PLANE(4, s_g[y][x] * s_pb[y][x])
+    GGC_PLANE(5, s_g[y][x] * s_pf[y][x])
+#undef GGC_PLANE
+    const int gx = blockIdx.x * FT + tid % FT, gy0 = blockIdx.y * FT + (tid / FT) * 4;
+    if (gx >= d.W) return;
+#pragma unroll
+    for (int o = 0; o < 4; ++o) {
+        if (gy0 + o >= d.H) break;
+        const size_t i = (size_t)b * P + (size_t)(gy0 + o) * d.W + gx;
+        const float mg = m[0][o], msb = m[1][o], msf = m[2][o];                  // k_t_ab
+        const float var = m[3][o] - mg * mg;
+        const float cov_b = m[4][o] - mg * msb;
+        const float cov_f = m[5][o] - mg * msf;
+        const float a_b = cov_b / (var + eps), a_f = cov_f / (var + eps);
+        ab[i] = a_b;
+        ab[BP + i] = msb - a_b * mg;
+        ab[2 * BP + i] = a_f;
+        ab[3 * BP + i] = msf - a_f * mg;
+    }
+}
+
+template <int radius>
+__global__ void __launch_bounds__(256, 4) k_t_stage2(TDims d, float thr_fg, float thr_bg, const float* __restrict__ ab,
+                                                  const uint8_t* __restrict__ bgr, uint8_t* __restrict__ trimap) {
+    constexpr int iw = FT + 2 * radius;
+    __shared__ float s_in[iw][iw + 1];
+    __shared__ double s_rs[iw][FT + 1];
+    __shared__ int tab[2 * iw];
+    const int tid = threadIdx.x, b = blockIdx.z;
+    const size_t P = (size_t)d.H * d.W, BP = P * d.B;
+    ft_coords<radius>(d, tab);
+    __syncthreads();
+    float m[4][4];                                  // means of a_b, b_b, a_f, b_f
+#pragma unroll
+    for (int pl = 0; pl < 4; ++pl) {                // s_in is free after a plane's row sums, s_rs after the next load
+        const float* src = ab + pl * BP + (size_t)b * P;
+        for (int i = tid; i < iw * iw; i += 256) {
+            const int ly = i / iw, lx = i - ly * iw;
+            s_in[ly][lx] = src[(size_t)tab[iw + ly] * d.W + tab[lx]];
+        }
+        __syncthreads();
+        ft_row_sums<radius>(s_rs, [&](int y, int x) -> float { return s_in[y][x]; });
+        __syncthreads();
+        ft_col_means<radius>(s_rs, m[pl]);
+    }
+    const int gx = blockIdx.x * FT + tid % FT, gy0 = blockIdx.y * FT + (tid / FT) * 4;
+    if (gx >= d.W) return;
+#pragma unroll
+    for (int o = 0; o < 4; ++o) {
+        if (gy0 + o >= d.H) break;
+        const size_t i = (size_t)b * P + (size_t)(gy0 + o) * d.W + gx;
+        const float g = guide_of(bgr + i * 3);                                   // k_t_final
+        float bb = m[0][o] * g + m[1][o];
+        float f = m[2][o] * g + m[3][o];
+        bb = bb < 0.0f ? 0.0f : (bb > 1.0f ? 1.0f : bb);
+        f = f < 0.0f ? 0.0f : (f > 1.0f ? 1.0f : f);
+        trimap[i] = decide(bb, f, thr_bg, thr_fg);
+    }
+}
+
 // non-edge-aware path: threshold region probabilities, pad with PR_BGD, gather
 __global__ void __launch_bounds__(256) k_t_plain(TDims d, float thr_fg, float thr_bg, const float* __restrict__ probs,
                                                  const int32_t* __restrict__ node_ptr, const int32_t* __restrict__ seg,
@@ -304,11 +465,26 @@ extern "C" int ggc_refine_trimap(ggc_ctx* ctx, ggc_stream stream, int B, int H, 
         GGC_LAUNCH_CHECK(ctx);
         return GGC_OK;
     }
+    ProfScope prof(ctx, st, "refine_trimap");
+    if (radius >= 1 && radius <= BX_R && B <= 65535) {          // two fused kernels; only the (a, b) planes cross HBM
+        float* ab = scratch_t<float>(ctx, S_T_A, BP * 4);
+        if (!ab) return GGC_E_OOM;
+        const dim3 grid(cdiv(W, FT), cdiv(H, FT), B);
+        switch (radius) {
+#define GGC_FUSED(R) case R:                                                                                            \
+            hipLaunchKernelGGL(k_t_stage1<R>, grid, dim3(256), 0, st, d, eps, probs, node_ptr, segments, bgr, ab);      \
+            hipLaunchKernelGGL(k_t_stage2<R>, grid, dim3(256), 0, st, d, threshold_fg, threshold_bg, ab, bgr, trimap);  \
+            break;
+            GGC_FUSED(1) GGC_FUSED(2) GGC_FUSED(3) GGC_FUSED(4) GGC_FUSED(5) GGC_FUSED(6) GGC_FUSED(7) GGC_FUSED(8)
+#undef GGC_FUSED
+        }
+        GGC_LAUNCH_CHECK(ctx);
+        return GGC_OK;
+    }
     float* planes = scratch_t<float>(ctx, S_T_A, BP * 6);
     double* hs = scratch_t<double>(ctx, S_T_B, BP * 6);
     float* means = scratch_t<float>(ctx, S_T_C, BP * 6);
     if (!planes || !hs || !means) return GGC_E_OOM;
-    ProfScope prof(ctx, st, "refine_trimap");
     hipLaunchKernelGGL(k_t_prep, dim3(cdiv(BP, 256)), dim3(256), 0, st, d, probs, node_ptr, segments, bgr, planes);
     box_filter(st, d, 6, radius, planes, hs, means);
     float* ab = planes + BP;                      // planes 1..4 are dead now; plane 0 (guide) stays
