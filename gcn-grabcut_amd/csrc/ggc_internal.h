@@ -33,6 +33,7 @@ enum Slot : int {
     S_MATTE, S_MATTE_MEAN, S_CFMATTE,
     S_FOREGROUND, S_FOREGROUND_VEC,
     S_MATTE_EVAL,
+    S_FULLCUT,
     S_COUNT
 };
 

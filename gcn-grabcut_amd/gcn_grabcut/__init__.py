@@ -24,7 +24,7 @@ from .model import (
 from .pipeline import (GCNGrabCutPipeline, ClosedFormMatte, ForegroundColours, FullResolution, SegmentationResult,
                        alpha_matte, clean_mask, closed_form_matte, estimate_foreground, guided_filter, refine_trimap,
                        closed_form_matte_full, lift_trimap, trimap_matte, trimap_matte_full,
-                       trimap_matte_warm, upsample_mask)
+                       trimap_matte_warm, upsample_mask, FullCut, cut_mask_full, lift_labels)
 from .synthetic import synthetic_image, synthetic_batch
 from .losses import FocalLoss, LabelSmoothingCE, TrimapLoss
 from .trainer import Trainer, TrainConfig
@@ -40,6 +40,7 @@ __all__ = [
     "GCNGrabCutPipeline", "FullResolution", "SegmentationResult", "alpha_matte", "clean_mask", "guided_filter",
     "refine_trimap", "upsample_mask", "ClosedFormMatte", "closed_form_matte", "ForegroundColours", "estimate_foreground",
     "trimap_matte", "trimap_matte_warm", "lift_trimap", "closed_form_matte_full", "trimap_matte_full",
+    "FullCut", "cut_mask_full", "lift_labels",
     "ResGCNNet", "GCNTrimapNet", "GATTrimapNet", "build_model", "probs_to_node_trimap", "project_to_pixels",
     "Data", "Batch", "synthetic_image", "synthetic_batch",
     "FocalLoss", "LabelSmoothingCE", "TrimapLoss", "Trainer", "TrainConfig",

@@ -402,6 +402,47 @@ class Engine:
         self.ctx.call("ggc_closed_form_band", self._stream(), b, h, w, binary.data_ptr(), int(band), trimap.data_ptr())
         return trimap
 
+    def lift_labels(self, binary, full_shape, band, want_labels=True, want_mask=False):
+        """binary (B,H,W) uint8 (nonzero = foreground) carried to full_shape = (H1, W1) >= (H, W) as the start of a banded
+        cut there (ggc_lift_labels).  -> (labels (B,H1,W1) uint8: GrabCut labels, probable (2, 3) within band pixels of
+        the lifted mask's edge and definite (0, 1) elsewhere; mask_full (B,H1,W1) uint8 {0, 1}: the lifted mask, the
+        bilinear interpolation >= 0.5), each None unless wanted."""
+        check_full_cut_args(tuple(binary.shape), full_shape, band)
+        if not (want_labels or want_mask):
+            raise ValueError("lift_labels: ask for at least one of labels and mask")
+        if binary.dtype != torch.uint8:
+            raise ValueError(f"lift_labels: binary must be uint8, got {binary.dtype}")
+        b, h, w = binary.shape
+        h1, w1 = int(full_shape[0]), int(full_shape[1])
+        binary = binary.contiguous()
+        labels = self.empty(b, h1, w1, dtype=torch.uint8) if want_labels else None
+        mask = self.empty(b, h1, w1, dtype=torch.uint8) if want_mask else None
+        self.ctx.call("ggc_lift_labels", self._stream(), b, h, w, binary.data_ptr(), h1, w1, int(band), _native.ptr(labels),
+                      _native.ptr(mask))
+        return labels, mask
+
+    def cut_mask_full(self, binary, bgr_full, band, n_iter=1, seed=0, color_space="rgb", min_area_ratio=0.002,
+                      keep_largest=False, out=None, max_pixels=None, want_labels=False):
+        """The banded cut of cut_mask_full on a batch: binary (B,H,W) uint8 and bgr_full (B,H1,W1,3) uint8 -> (B,H1,W1)
+        uint8 {0, 1} (out: the same, preallocated).  ggc_lift_labels, ggc_convert_color8 (color_space other than rgb),
+        ggc_grabcut(mode 0, n_iter) cold from the labels with image b on seed + b, ggc_clean_mask.  max_pixels: the
+        images go through those entries in sub-batches of at most that many pixels (at least one image); every entry
+        is independent per image, so the split does not change the result."""
+        b, h1, w1, _ = bgr_full.shape
+        if out is None:
+            out = self.empty(b, h1, w1, dtype=torch.uint8)
+        step = b if not max_pixels else max(1, int(max_pixels) // (h1 * w1))
+        kept = []
+        for lo in range(0, b, max(step, 1)):
+            hi = min(b, lo + step)
+            labels, _ = self.lift_labels(binary[lo:hi], (h1, w1), band)
+            if want_labels:
+                kept.append(labels.clone())
+            img = bgr_full[lo:hi] if color_space == "rgb" else self.convert_color8(bgr_full[lo:hi].contiguous(), color_space)
+            cut = self.grabcut(img, labels, n_iter, 0, None, seed + lo)[0]
+            self.clean_mask(cut, min_area_ratio, keep_largest, out=out[lo:hi])
+        return (out, torch.cat(kept)) if want_labels else out
+
     def closed_form_full(self, bgr, trimap, alpha, bgr_full, radius, eps, grow, max_iter, tol, out=None):
         """The full-resolution end of closed_form_matte_full / trimap_matte_full: a working-size trimap (B,H,W) uint8 and
         its solved alpha (B,H,W) float32 lifted to bgr_full (B,H1,W1,3) uint8 (lift_trimap), then the warm solve there.
@@ -521,6 +562,41 @@ def check_lift_args(trimap_shape, alpha_shape, full_shape, grow) -> None:
                          f"most {UPSAMPLE_SIDE_MAX} on a side")
     if isinstance(grow, bool) or int(grow) != grow or not 0 <= int(grow) <= LIFT_GROW_MAX:
         raise ValueError(f"lift_trimap: grow must be an integer in 0..{LIFT_GROW_MAX}, got {grow}")
+
+
+FULL_CUT_BAND_MAX = 64
+FULL_CUT_ITER_MAX = 100
+FULL_CUT_PIXEL_MAX = 2 ** 28          # ggc_grabcut's limit on the pixels of one image
+
+
+def default_full_cut_band(shape, full_shape) -> int:
+    """The band of the full-resolution cut when none is given: one and a half working pixels,
+    min(64, max(1, ceil(1.5 max(H1 / H, W1 / W)))) (a choice backed by DESIGN.md §5.18's table, not a tuned result)."""
+    import math
+    ratio = max(int(full_shape[0]) / int(shape[0]), int(full_shape[1]) / int(shape[1]))
+    return min(FULL_CUT_BAND_MAX, max(1, math.ceil(1.5 * ratio)))
+
+
+def check_full_cut_args(mask_shape, full_shape, band, n_iter=1, color_space="rgb") -> None:
+    """The rules of ggc_lift_labels and of the cut after it, checked on the host so that a bad argument is a ValueError:
+    mask (B,H,W), full_shape (H1, W1) with H <= H1 <= 32768, W <= W1 <= 32768 and H1 W1 < 2^28, band an integer in 0..64,
+    n_iter an integer in 1..100, color_space rgb | hsv | lab."""
+    if len(mask_shape) != 3 or min(mask_shape[1:]) < 1:
+        raise ValueError(f"full cut: mask must be (B,H,W), got {tuple(mask_shape)}")
+    if len(full_shape) != 2:
+        raise ValueError(f"full cut: full_shape must be (H1, W1), got {tuple(full_shape)}")
+    h, w = mask_shape[1:]
+    if not (h <= full_shape[0] <= UPSAMPLE_SIDE_MAX and w <= full_shape[1] <= UPSAMPLE_SIDE_MAX):
+        raise ValueError(f"full cut: full size {tuple(full_shape)} must be at least the working size {(h, w)} and at "
+                         f"most {UPSAMPLE_SIDE_MAX} on a side")
+    if int(full_shape[0]) * int(full_shape[1]) >= FULL_CUT_PIXEL_MAX:
+        raise ValueError(f"full cut: GrabCut takes images below 2^28 pixels, got {tuple(full_shape)}")
+    if isinstance(band, bool) or int(band) != band or not 0 <= int(band) <= FULL_CUT_BAND_MAX:
+        raise ValueError(f"full cut: band must be an integer in 0..{FULL_CUT_BAND_MAX}, got {band}")
+    if isinstance(n_iter, bool) or int(n_iter) != n_iter or not 1 <= int(n_iter) <= FULL_CUT_ITER_MAX:
+        raise ValueError(f"full cut: n_iter must be an integer in 1..{FULL_CUT_ITER_MAX}, got {n_iter}")
+    if str(color_space).lower() not in ("rgb", "hsv", "lab"):
+        raise ValueError(f"unknown color_space '{color_space}': rgb | hsv | lab")
 
 
 FG_OMEGA_MAX = 1e3

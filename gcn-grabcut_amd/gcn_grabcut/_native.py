@@ -79,6 +79,7 @@ SIGNATURES = {
     "ggc_trimap_matte_warm": [_vp, _vp, _i, _i, _i, _vp, _vp, _i, _f, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp],
     "ggc_lift_trimap": [_vp, _vp, _i, _i, _i, _vp, _vp, _i, _i, _i, _vp, _vp],
     "ggc_closed_form_band": [_vp, _vp, _i, _i, _i, _vp, _i, _vp],
+    "ggc_lift_labels": [_vp, _vp, _i, _i, _i, _vp, _i, _i, _i, _vp, _vp],
     "ggc_estimate_foreground": [_vp, _vp, _i, _i, _i, _vp, _vp, _f, _f, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp],
     "ggc_matte_errors": [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp],
     "ggc_mask_iou": [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp],

@@ -39,7 +39,7 @@ def _write_png(path: str, array: np.ndarray) -> None:
 @dataclass
 class FullResolution:
     """The outputs of a run at the full resolution of the image it was given (additive; upsample_mask): (H1, W1) arrays."""
-    binary_mask: np.ndarray                  # (H1, W1) uint8 {0, 1}: upsampled alpha >= 0.5
+    binary_mask: np.ndarray                  # (H1, W1) uint8 {0, 1}: upsampled alpha >= 0.5 (full_cut: cut_mask_full)
     overlay: np.ndarray                      # (H1, W1, 3) BGR with coloured overlay of binary_mask
     rgba: np.ndarray                         # (H1, W1, 4) BGRA, alpha = 255 * binary_mask
     alpha: Optional[np.ndarray] = None       # (H1, W1) float32 soft matte in [0, 1] (matte=True)
@@ -431,6 +431,100 @@ def upsample_mask(image: np.ndarray, mask: np.ndarray, full_image: np.ndarray, r
     return alpha[0].cpu().numpy(), binary[0].cpu().numpy()
 
 
+FULL_CUT_ITERS = 1
+# The most pixels one ggc_grabcut call of the full-resolution cut is given: a batch of full images goes through it in
+# sub-batches of at most this many (at least one image).  ggc_grabcut's arena is 66 bytes per pixel,
+# so this is about 2.2 GB per context.  Read when a call runs, so a test can override it; results do not depend on it.
+FULL_CUT_PIXELS = 1 << 25
+
+
+@dataclass(frozen=True)
+class FullCut:
+    """full_cut=FullCut(...) (or full_cut=True for the defaults) asks segment / segment_batch / segment_batch_device /
+    segment_bbox, together with a full image, for the full-size binary mask of cut_mask_full (a banded graph cut on the
+    full image's own pixels) instead of the guided upsample's alpha >= 0.5.  band=None: one and a half
+    working pixels, min(64, max(1, ceil(1.5 max(H1 / H, W1 / W)))), a choice backed by §5.18's table, not a tuned result."""
+    band: Optional[int] = None
+    n_iter: int = FULL_CUT_ITERS
+
+
+def lift_labels(mask: np.ndarray, full_shape, band: Optional[int] = None, device="cuda") -> np.ndarray:
+    """A working-size mask carried to a larger size as GrabCut labels for a banded cut there (additive; ggc_lift_labels,
+    DESIGN.md §5.18).  The mask is interpolated bilinearly (half-pixel centres, as upsample_mask) and thresholded at 0.5;
+    the pixels within `band` (Chebyshev) of that lifted mask's edge become probable foreground / background (3 / 2), every
+    other pixel definite (1 / 0).
+
+    mask: (H, W) with values in {0, 1}; full_shape: (H1, W1) with H <= H1 <= 32768, W <= W1 <= 32768; band in 0..64, or
+    None for one and a half working pixels.  -> (H1, W1) uint8 in {0, 1, 2, 3}."""
+    from ._engine import get_engine, check_full_cut_args, default_full_cut_band
+    m = _check_cut_mask(mask, "lift_labels")
+    full_shape = tuple(int(v) for v in full_shape)
+    if len(full_shape) == 2 and band is None and min(full_shape) >= 1:
+        band = default_full_cut_band(m.shape, full_shape)
+    check_full_cut_args((1, *m.shape), full_shape, band)
+    eng = get_engine(device)
+    return eng.lift_labels(eng.to_device(m[None]), full_shape, band)[0][0].cpu().numpy()
+
+
+def _check_cut_mask(mask, what: str) -> np.ndarray:
+    m = np.asarray(mask)
+    if m.ndim != 2 or m.size == 0:
+        raise ValueError(f"{what}: mask must be (H, W), got {m.shape}")
+    if m.dtype.kind not in "bui" or not np.isin(m, (0, 1)).all():
+        raise ValueError(f"{what}: mask values must be 0 or 1")
+    return np.ascontiguousarray(m, np.uint8)
+
+
+def cut_mask_full(mask: np.ndarray, full_image: np.ndarray, band: Optional[int] = None, n_iter: int = FULL_CUT_ITERS,
+                  seed: int = 0, color_space: str = "rgb", min_area_ratio: float = 0.002, keep_largest: bool = False,
+                  return_labels: bool = False, device="cuda"):
+    """A mask found on a reduced image, cut again on the full-resolution image's own pixels (additive; the banded graph
+    cut of Lombaert et al., ICCV 2005; DESIGN.md §5.18).  Four steps on the device: lift_labels(mask, full size, band);
+    the colour conversion of GrabCutConfig.color_space; GrabCut from those labels (mode 0, n_iter iterations, cold: the
+    colour models are learned on the full image, nothing of the working-size solve is needed); clean_mask.  Outside the
+    band the lifted mask stands, so the cost of being wrong is bounded by the band, and a working mask that is off by a
+    working pixel is repaired.  A component of the lifted mask thinner than twice the band keeps no definite pixel and
+    the cut may delete it: use a smaller band for thin structures.  A mask that lifts to all background or all
+    foreground has no band and comes back as it is.
+
+    mask: (H, W) in {0, 1}; full_image: (H1, W1, 3) uint8 BGR, H <= H1 <= 32768, W <= W1 <= 32768, below 2^28 pixels;
+    band in 0..64 or None (one and a half working pixels); n_iter in 1..100; color_space rgb | hsv | lab.
+    -> (H1, W1) uint8 in {0, 1}; with return_labels, (mask, labels) with the labels GrabCut started from."""
+    from ._engine import get_engine, check_full_cut_args, default_full_cut_band
+    m = _check_cut_mask(mask, "cut_mask_full")
+    full = _check_image(full_image)
+    if band is None and min(full.shape[:2]) >= 1:
+        band = default_full_cut_band(m.shape, full.shape[:2])
+    check_full_cut_args((1, *m.shape), full.shape[:2], band, n_iter, color_space)
+    eng = get_engine(device)
+    out = eng.cut_mask_full(eng.to_device(m[None]), eng.to_device(full[None]), band, n_iter, int(seed), color_space.lower(),
+                            min_area_ratio, keep_largest, want_labels=return_labels)
+    if return_labels:
+        return out[0][0].cpu().numpy(), out[1][0].cpu().numpy()
+    return out[0].cpu().numpy()
+
+
+def _full_cut_args(full_cut, has_full: bool, matte, shape=None, full_shape=None) -> "Optional[tuple[Optional[int], int]]":
+    """(band or None, n_iter) when full_cut is True or a FullCut (checked here, before any stage runs; refused without a
+    full image and together with the full-size closed-form solve), else None."""
+    if full_cut is None or full_cut is False:
+        return None
+    if full_cut is True:
+        full_cut = FullCut()
+    if not isinstance(full_cut, FullCut):
+        raise ValueError(f"full_cut must be True, False or a FullCut, got {type(full_cut).__name__}")
+    if not has_full:
+        raise ValueError("full_cut needs the full image: pass full_image(s) / full_bgr")
+    if isinstance(matte, ClosedFormMatte) and matte.full_resolution:
+        raise ValueError("full_cut cannot be combined with ClosedFormMatte(full_resolution=True), which defines the full mask "
+                         "as its alpha >= 0.5: run with full_cut alone and call closed_form_matte(full_image, "
+                         "result.full.binary_mask) for the matte")
+    from ._engine import check_full_cut_args
+    check_full_cut_args((1, 1, 1) if shape is None else (1, *shape), (1, 1) if full_shape is None else tuple(full_shape),
+                        0 if full_cut.band is None else full_cut.band, full_cut.n_iter)
+    return (None if full_cut.band is None else int(full_cut.band)), int(full_cut.n_iter)
+
+
 def nearest_upsample(a: np.ndarray, h1: int, w1: int) -> np.ndarray:
     """(H, W, ...) -> (h1, w1, ...) by the source pixel under each output pixel's centre: index
     min(floor((i + 0.5) * H / h1), H - 1), the centre mapping of upsample_mask."""
@@ -577,14 +671,25 @@ def _full_buffers(eng, full_bgr, compose: bool, mat) -> "Optional[dict]":
     return out
 
 
-def _full_post(leng, lo, hi, bgr, cleaned, full_bgr, full, fmat, cfm=None, cff=None, work_alpha=None) -> None:
+def _full_post(leng, lo, hi, bgr, cleaned, full_bgr, full, fmat, cfm=None, cff=None, work_alpha=None, fcut=None) -> None:
     """The full-resolution outputs of images lo:hi from their cleaned working masks: ggc_upsample_matte, then
     ggc_compose_outputs on the full image and the upsampled mask.  With cff (ClosedFormMatte(full_resolution=True): its
     grow and full_max_iter, next to cfm) the alpha comes from the full-size closed-form solve instead, warm from the
-    working-size alpha work_alpha on its lifted band, and the mask is that alpha >= 0.5 (closed_form_matte_full)."""
+    working-size alpha work_alpha on its lifted band, and the mask is that alpha >= 0.5 (closed_form_matte_full).  With
+    fcut (full_cut: band or None, n_iter, the batch's seed, colour space, min_area_ratio, keep_largest) the mask is
+    cut_mask_full of the cleaned mask, image b on seed + b; the alpha, if wanted, stays the guided upsample's."""
     import torch
     alpha, soft = full.get("alpha"), full.get("rgba_soft")
-    if cff:
+    if fcut:
+        from ._engine import default_full_cut_band
+        band, n_iter, seed, cs, min_area_ratio, keep_largest = fcut
+        if band is None:
+            band = default_full_cut_band(cleaned.shape[1:], full_bgr.shape[1:3])
+        if alpha is not None:
+            leng.upsample_matte(bgr[lo:hi], cleaned[lo:hi], full_bgr[lo:hi], *fmat, out=(alpha[lo:hi], None, soft[lo:hi]))
+        leng.cut_mask_full(cleaned[lo:hi], full_bgr[lo:hi], band, n_iter, seed + lo, cs, min_area_ratio, keep_largest,
+                           out=full["binary_mask"][lo:hi], max_pixels=FULL_CUT_PIXELS)
+    elif cff:
         radius, eps, band, _, tol = cfm
         leng.closed_form_full(bgr[lo:hi], leng.closed_form_band(cleaned[lo:hi], band), work_alpha[lo:hi], full_bgr[lo:hi],
                               radius, eps, cff[0], cff[1], tol, out=(alpha[lo:hi], soft[lo:hi]))
@@ -817,7 +922,7 @@ class GCNGrabCutPipeline:
                              chunks: Optional[int] = None, hints=None, hint_radius: int = 5, hint_region: bool = False,
                              hints_as_prior: bool = False, return_state: bool = False, matte: bool = False,
                              matte_radius: int = MATTE_RADIUS, matte_eps: float = MATTE_EPS, full_bgr=None,
-                             foreground=False) -> dict:
+                             foreground=False, full_cut=False) -> dict:
         """bgr: (B,H,W,3) uint8 tensor on the pipeline's device.  Returns device tensors.
 
         matte=True (additive) also returns "alpha" (B,H,W) float32, the soft matte of the cleaned mask (alpha_matte with
@@ -836,7 +941,10 @@ class GCNGrabCutPipeline:
         working one.  The result then also has "full", a dict of device tensors at (H1, W1): "binary_mask", the cleaned
         mask carried to the full image by upsample_mask (with matte_radius / matte_eps), and "overlay" / "rgba" composed
         from it (compose=True), plus "alpha" and "rgba_soft" with matte=True.  Every other output is the same as without
-        it.
+        it.  full_cut=True or FullCut(...) (additive, needs full_bgr) makes that "binary_mask" cut_mask_full of the cleaned
+        mask instead, a banded graph cut on the full image (GrabCutConfig.color_space, this call's min_area_ratio and
+        keep_largest, image b on GrabCutConfig.seed + b), with "overlay" / "rgba" composed from it; "alpha" and
+        "rgba_soft" stay the guided upsample's.  It cannot be combined with ClosedFormMatte(full_resolution=True).
 
         return_state=True (additive) also returns what a GC_EVAL edit loop continues from: "gc_binary" (B,H,W) uint8,
         GrabCut's own binary mask before clean_mask; "bgd" / "fgd" (B,65) float64, the colour models; "gc_image"
@@ -868,12 +976,16 @@ class GCNGrabCutPipeline:
         fmat = _full_args(full_bgr, bgr.shape, matte_radius, matte_eps)
         fga = _foreground_args(foreground, matte, full_bgr is not None)
         cff = _closed_form_full_args(matte) if cfm else None
+        fcut = _full_cut_args(full_cut, full_bgr is not None, matte, bgr.shape[1:3],
+                              None if full_bgr is None else full_bgr.shape[1:3])
+        if fcut:
+            fcut = (*fcut, self.gc_config.seed, cs, min_area_ratio, keep_largest)
         if n_chunks <= 0:                          # 0: one chunk per GrabCut lane once every chunk gets a lane's worth of images
             n_chunks = max(want, 1) if b >= 16 * max(want, 1) else 1
         if n_chunks > 1 and b >= 2 * n_chunks:
             return self._segment_pipelined(bgr, self.chunk_plan(b, n_chunks, self.chunk_ratio), cs, threshold_fg, threshold_bg,
                                            refine_iters, min_area_ratio, keep_largest, edge_aware, filter_radius, compose, timing,
-                                           hints, return_state, mat, full_bgr, fmat, cfm, fga, cff)
+                                           hints, return_state, mat, full_bgr, fmat, cfm, fga, cff, fcut)
 
         def tick():
             if timing is not None:
@@ -907,7 +1019,7 @@ class GCNGrabCutPipeline:
             if fga:
                 leng.estimate_foreground(bgr[lo:hi], alpha[lo:hi], *fga, out=(fg_col[lo:hi], rgba_clean[lo:hi]))
             if full is not None:
-                _full_post(leng, lo, hi, bgr, cleaned, full_bgr, full, fmat, cfm, cff, alpha)
+                _full_post(leng, lo, hi, bgr, cleaned, full_bgr, full, fmat, cfm, cff, alpha, fcut)
 
         fused_post = timing is None
         binary, mask, bgd, fgd = eng.grabcut_lanes(gc_img, mask, self.gc_config.n_iter, 0, self.gc_config.seed, lanes,
@@ -939,7 +1051,7 @@ class GCNGrabCutPipeline:
 
     def _segment_pipelined(self, bgr, plan, cs, threshold_fg, threshold_bg, refine_iters, min_area_ratio, keep_largest,
                            edge_aware, filter_radius, compose, timing, hints=None, return_state=False, mat=None,
-                           full_bgr=None, fmat=None, cfm=None, fga=None, cff=None) -> dict:
+                           full_bgr=None, fmat=None, cfm=None, fga=None, cff=None, fcut=None) -> dict:
         """The software pipeline behind segment_batch_device: chunk k's GrabCut lane starts as soon as chunk k's trimaps are
         on the device; the caller's stream goes on with chunk k+1's SLIC / graph / network / trimap."""
         import torch
@@ -1004,7 +1116,7 @@ class GCNGrabCutPipeline:
                 if fga:
                     leng.estimate_foreground(img, alpha[lo:hi], *fga, out=(fg_col[lo:hi], rgba_clean[lo:hi]))
                 if full is not None:
-                    _full_post(leng, lo, hi, bgr, cleaned, full_bgr, full, fmat, cfm, cff, alpha)
+                    _full_post(leng, lo, hi, bgr, cleaned, full_bgr, full, fmat, cfm, cff, alpha, fcut)
                 if ev is not None:
                     ev[2].record(stream)
                 done = torch.cuda.Event()
@@ -1057,7 +1169,8 @@ class GCNGrabCutPipeline:
         image, with hint_radius / hint_region / hints_as_prior among kwargs (segment_batch_device).  full_images
         (additive): the same images at one larger size each, (H1, W1, 3) uint8 BGR; every result's `full` then holds the
         outputs at that size (segment_batch_device's full_bgr).  foreground=True | ForegroundColours(...) among kwargs
-        (with a matte) fills every result's foreground and rgba_clean."""
+        (with a matte) fills every result's foreground and rgba_clean.  full_cut=True | FullCut(...) among kwargs (with
+        full_images) makes every result's full binary_mask, overlay and rgba those of cut_mask_full."""
         imgs = [_check_image(im) for im in images]
         if not imgs:
             return []
@@ -1065,6 +1178,7 @@ class GCNGrabCutPipeline:
             raise ValueError("segment_batch needs images of one size; group them by shape")
         _closed_form_args(kwargs.get("matte"), *imgs[0].shape[:2], full_images is not None)
         _foreground_args(kwargs.get("foreground"), kwargs.get("matte"), full_images is not None)
+        _full_cut_args(kwargs.get("full_cut"), full_images is not None, kwargs.get("matte"))
         full_bgr = None
         if full_images is not None:
             fulls = [_check_image(im) for im in full_images]
@@ -1196,7 +1310,7 @@ class GCNGrabCutPipeline:
                 edge_aware: bool = True, filter_radius: int = 8, fg_points=None, bg_points=None, hint_radius: int = 5,
                 hint_region: bool = False, hints_as_prior: bool = False, matte: bool = False,
                 matte_radius: int = MATTE_RADIUS, matte_eps: float = MATTE_EPS,
-                full_image: Optional[np.ndarray] = None, foreground=False) -> SegmentationResult:
+                full_image: Optional[np.ndarray] = None, foreground=False, full_cut=False) -> SegmentationResult:
         """Full pipeline on one BGR image (reference pipeline.py:265-352).
 
         Additive: fg_points / bg_points are user clicks, (row, col) pairs, applied as hard constraints on the trimap
@@ -1205,10 +1319,13 @@ class GCNGrabCutPipeline:
         matte; full_image, the same image at a larger size, fills
         the result's `full` (segment_batch_device's full_bgr; with matte=ClosedFormMatte(full_resolution=True) its
         alpha, rgba_soft and binary_mask come from closed_form_matte_full); foreground=True | ForegroundColours(...),
-        with a matte, fills the result's foreground and rgba_clean (estimate_foreground under that matte's alpha)."""
+        with a matte, fills the result's foreground and rgba_clean (estimate_foreground under that matte's alpha);
+        full_cut=True | FullCut(...), with full_image, makes the full binary_mask, overlay and rgba those of
+        cut_mask_full of the cleaned mask (segment_batch_device)."""
         image = _check_image(image)
         _closed_form_args(matte, *image.shape[:2], full_image is not None)
         _foreground_args(foreground, matte, full_image is not None)
+        _full_cut_args(full_cut, full_image is not None, matte)
         full_bgr = None if full_image is None else self._eng.to_device(_check_image(full_image)[None])
         timing: dict[str, float] = {}
         hints = None if fg_points is None and bg_points is None else \
@@ -1217,7 +1334,7 @@ class GCNGrabCutPipeline:
                                         min_area_ratio, keep_largest, edge_aware, filter_radius, timing=timing,
                                         hints=hints, hint_radius=hint_radius, hint_region=hint_region,
                                         hints_as_prior=hints_as_prior, matte=matte, matte_radius=matte_radius,
-                                        matte_eps=matte_eps, full_bgr=full_bgr, foreground=foreground)
+                                        matte_eps=matte_eps, full_bgr=full_bgr, foreground=foreground, full_cut=full_cut)
         return SegmentationResult(
             image=image, binary_mask=out["binary_mask"][0].cpu().numpy(), trimap=out["trimap"][0].cpu().numpy(),
             segments=out["segments"][0].cpu().numpy(), overlay=out["overlay"][0].cpu().numpy(),
@@ -1230,16 +1347,25 @@ class GCNGrabCutPipeline:
 
     def segment_bbox(self, image: np.ndarray, bbox: tuple[int, int, int, int], matte: bool = False,
                      matte_radius: int = MATTE_RADIUS, matte_eps: float = MATTE_EPS,
-                     full_image: Optional[np.ndarray] = None, foreground=False) -> SegmentationResult:
+                     full_image: Optional[np.ndarray] = None, foreground=False, full_cut=False) -> SegmentationResult:
         """Classical GrabCut with a bounding box (reference pipeline.py:354-380).  Additive: matte=True also fills the
         result's alpha and rgba_soft, the soft matte of the returned mask (alpha_matte; closed_form_matte with
         matte=ClosedFormMatte(...)); full_image, the same image at a
         larger size, fills the result's `full` from the returned mask (upsample_mask, then the overlay and cut-out;
         closed_form_matte_full with matte=ClosedFormMatte(full_resolution=True));
-        foreground=True | ForegroundColours(...), with a matte, fills the result's foreground and rgba_clean."""
+        foreground=True | ForegroundColours(...), with a matte, fills the result's foreground and rgba_clean;
+        full_cut=True | FullCut(...), with full_image, makes the full binary_mask cut_mask_full of the returned mask
+        (GrabCutConfig's colour space and seed, clean_mask's defaults)."""
         image = _check_image(image)
         cfm = _closed_form_args(matte, *image.shape[:2], full_image is not None)
         fga = _foreground_args(foreground, matte, full_image is not None)
+        fcut = _full_cut_args(full_cut, full_image is not None, matte, image.shape[:2],
+                              None if full_image is None else np.shape(full_image)[:2])
+        if fcut:
+            cs = self.gc_config.color_space.lower()
+            if cs not in ("rgb", "hsv", "lab"):
+                raise ValueError(f"unknown color_space '{cs}': rgb | hsv | lab")
+            fcut = (*fcut, self.gc_config.seed, cs, 0.002, False)
         mat = None if cfm else _matte_args(matte, matte_radius, matte_eps)
         full_img = None
         if full_image is not None:
@@ -1278,7 +1404,7 @@ class GCNGrabCutPipeline:
             bufs = _full_buffers(eng, full_bgr, True, mat or cff)
             _full_post(eng, 0, 1, eng.to_device(image[None]), eng.to_device(np.ascontiguousarray(binary_mask, np.uint8)[None]),
                        full_bgr, bufs, fmat, cfm, cff,
-                       None if not cff else eng.to_device(np.ascontiguousarray(alpha, np.float32)[None]))
+                       None if not cff else eng.to_device(np.ascontiguousarray(alpha, np.float32)[None]), fcut)
             full = _full_result(bufs, 0)
         return SegmentationResult(image=image, binary_mask=binary_mask, trimap=trimap,
                                   segments=np.zeros((H, W), dtype=np.int32), overlay=gc.overlay_mask(),

@@ -51,7 +51,9 @@
 extern "C" {
 #endif
 
-#define GGC_VERSION 402 /* 0.4.2: ggc_lift_trimap, ggc_trimap_matte_warm, ggc_closed_form_band (a working-size closed-form matte carried to a
+#define GGC_VERSION 403 /* 0.4.3: ggc_lift_labels (a working-size mask carried to a larger size as GrabCut labels with an open band
+                                  around its edge: the start of a banded graph cut on the full image; no existing entry changes);
+                           0.4.2: ggc_lift_trimap, ggc_trimap_matte_warm, ggc_closed_form_band (a working-size closed-form matte carried to a
                                   larger image: lifted trimap and start, a stop rule that does not move with the start; the two
                                   existing closed-form entries do not change);
                            0.4.1: ggc_trimap_matte (closed-form alpha matte on the unknown region of a caller's trimap; one solver with
@@ -565,6 +567,27 @@ int ggc_lift_trimap(ggc_ctx* ctx, ggc_stream stream, int B, int H, int W, const 
  * Scratch: 2 bytes per pixel from the context.  Does not synchronise. */
 int ggc_closed_form_band(ggc_ctx* ctx, ggc_stream stream, int B, int H, int W, const uint8_t* binary, int band,
                          uint8_t* trimap);
+
+/* O3f — a working-size binary mask carried to a larger size as the start of a banded graph cut there (additive; Lombaert,
+ * Sun, Grady and Xu, ICCV 2005): the lifted mask, and GrabCut labels that fix every pixel but a band around its edge.
+ *   binary [dev] u8 [B,H,W] (any nonzero byte is 1)
+ *   H <= H1 <= 32768, W <= W1 <= 32768, H, W >= 1, B <= 65535 (else GGC_E_SHAPE); 0 <= band <= 64 (else
+ *   GGC_E_INVALID_ARG); B == 0 does nothing
+ * For output pixel (y, x) the source pixels (y0|y1, x0|x1) and the weights wy, wx are those of ggc_upsample_matte (O2),
+ * its float64 half-pixel formula word for word.  With m = (binary != 0) as 0.0 / 1.0:
+ *   v         = lerp(lerp(m00, m01, wx), lerp(m10, m11, wx), wy), lerp(u, v, t) = u + t (v - u) in float64, no contraction
+ *   M1        = (v >= 0.5), the lifted mask
+ *   E         the pixels whose 3x3 neighbourhood of M1 (clipped to the image) holds both values
+ *   U         the pixels within Chebyshev distance `band` of a pixel of E (clipped): O3's rule, so that
+ *             ggc_closed_form_band(M1, band) writes 128 exactly on U
+ *   labels_full [dev] u8 [B,H1,W1]  3 (PR_FGD) on U and M1, 2 (PR_BGD) on U and not M1, 1 (FGD) on M1 off U, else 0 (BGD)
+ *   mask_full   [dev] u8 [B,H1,W1]  = M1                                  (either may be NULL, not both)
+ * With H1 = H, W1 = W every weight is 0 and M1 = m.  An image whose M1 is empty or full has no E and no band: its labels
+ * are all 0 or all 1.  No atomics; every image is independent of its batch.  Scratch: one bit per full-size pixel (rows
+ * padded to 64 pixels) for M1 and, with labels_full, one more for the dilation, from the context: 1/4 byte per pixel.
+ * Does not synchronise. */
+int ggc_lift_labels(ggc_ctx* ctx, ggc_stream stream, int B, int H, int W, const uint8_t* binary,
+                    int H1, int W1, int band, uint8_t* labels_full, uint8_t* mask_full);
 
 /* O4 — foreground colour estimation under a given alpha matte (additive; the multi-level foreground estimation energy of
  * Germer, Uelwer, Conrad and Harmeling, ICPR 2020, restricted to the pixels of fractional alpha with Dirichlet values).

@@ -9,6 +9,7 @@ Same command line as the reference's inference.py (flags :26-56, outputs :146-15
     python3 inference.py --image cat.jpg --fg-point 120,200 --bg-point 10,10 --hint-radius 8
     python3 inference.py --image cat.jpg --save mask alpha cutout          # soft edges: alpha matte and cut-out
     python3 inference.py --image big.jpg --full-res --save mask cutout     # outputs at the photo's own size
+    python3 inference.py --image big.jpg --full-res --full-mask cut --save mask   # ... the mask cut again on the photo's pixels
     python3 inference.py --image cat.jpg --matte-method closed-form --save alpha cutout   # closed-form matte
     python3 inference.py --image big.jpg --full-res --matte-method closed-form-full --save alpha cutout   # ... solved at the photo's own size
 
@@ -90,6 +91,15 @@ def build_parser() -> argparse.ArgumentParser:
                         help="Write every output at the original image size: the mask (and alpha) found at --max-size "
                              "is carried to the original by a fast guided filter with --matte-radius / --matte-eps, the "
                              "trimap by nearest neighbour; images already within --max-size are unaffected")
+    # additive: the hard mask at the original size by a banded graph cut there (ggc_lift_labels, ggc_grabcut)
+    parser.add_argument("--full-mask", choices=["guided", "cut"], default="guided",
+                        help="With --full-res, how the hard mask (mask, overlay, rgba) reaches the original size: the "
+                             "guided upsample's alpha >= 0.5, or GrabCut run again on the original pixels inside a band "
+                             "around the lifted mask's edge (cut: --full-cut-band, --full-cut-iters)")
+    parser.add_argument("--full-cut-band", type=int, default=None,
+                        help="--full-mask cut: half-width of the open band in original pixels, 0..64 "
+                             "(default: one and a half working pixels)")
+    parser.add_argument("--full-cut-iters", type=int, default=1, help="--full-mask cut: GrabCut iterations at the original size")
     return parser
 
 
@@ -185,6 +195,19 @@ def main() -> None:
             _closed_form_full_args(closed_form)
         except ValueError as e:
             parser.error(str(e))
+    full_cut = None
+    if args.full_mask == "cut":
+        if not args.full_res:
+            parser.error("--full-mask cut cuts at the original size: add --full-res")
+        if args.matte_method == "closed-form-full":
+            parser.error("--full-mask cut cannot be combined with --matte-method closed-form-full, whose mask is its "
+                         "alpha >= 0.5: use --matte-method guided")
+        from src.gcn_grabcut.pipeline import FullCut, _full_cut_args
+        full_cut = FullCut(args.full_cut_band, args.full_cut_iters)
+        try:
+            _full_cut_args(full_cut, True, None)
+        except ValueError as e:
+            parser.error(str(e))
     foreground = None
     if args.decontaminate:
         if "cutout" not in args.save:
@@ -254,6 +277,8 @@ def main() -> None:
             if chunk[0][2] is not None:                 # --full-res on images that --max-size shrank
                 hint_kw.update(full_images=[full for _, _, full in chunk], matte_radius=args.matte_radius,
                                matte_eps=args.matte_eps)
+                if full_cut is not None:
+                    hint_kw.update(full_cut=full_cut)
             results = pipeline.segment_batch(
                 [im for _, im, _ in chunk], threshold_fg=args.threshold, threshold_bg=args.threshold,
                 refine_iters=args.refine, min_area_ratio=args.min_area, keep_largest=args.keep_largest,
