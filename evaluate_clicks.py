@@ -33,6 +33,13 @@ def build_parser() -> argparse.ArgumentParser:
     parser.add_argument("--max-clicks", type=int, default=20)
     parser.add_argument("--targets", type=float, nargs="+", default=[0.85, 0.90], help="IoU targets of NoC / NoF")
     parser.add_argument("--hint-radius", type=int, default=5, help="Radius in pixels of the disk painted around a click")
+    # additive: geodesic click hints (ggc_geodesic_hints) instead of disks
+    parser.add_argument("--hint-mode", choices=["disk", "geodesic"], default="disk",
+                        help="How a click is painted: a disk of --hint-radius, or the pixels within a geodesic distance of "
+                             "it that does not cross colour edges (--geodesic-radius, --hint-gamma; --hint-radius is ignored)")
+    parser.add_argument("--hint-gamma", type=int, default=2, help="Weight of the colour term of the geodesic distance, 0..64")
+    parser.add_argument("--geodesic-radius", type=int, default=40,
+                        help="Reach of a geodesic click over flat colour, in pixels of the image as segmented, 0..16384")
     parser.add_argument("--iters-per-click", type=int, default=1, help="GrabCut (GC_EVAL) iterations after each click")
     parser.add_argument("--stop-iou", type=float, default=None, help="No further clicks for an image at this IoU")
     parser.add_argument("--json", default=None, help="Write per-image curves and clicks here")
@@ -58,10 +65,14 @@ def main() -> None:
         parser.error("--iters-per-click must be >= 1")
     if args.hint_radius < 0:
         parser.error("--hint-radius must be >= 0")
+    if not 0 <= args.hint_gamma <= 64:
+        parser.error("--hint-gamma must be in 0..64")
+    if not 0 <= args.geodesic_radius <= 16384:
+        parser.error("--geodesic-radius must be in 0..16384")
     if args.batch < 1:
         parser.error("--batch must be >= 1")
     from inference import load_model
-    from src.gcn_grabcut import GCNGrabCutPipeline
+    from src.gcn_grabcut import GCNGrabCutPipeline, GeodesicHints
     from src.gcn_grabcut.dataset import list_image_mask_pairs, materialise
     from src.gcn_grabcut.graph_builder import SuperpixelGraphConfig
     from src.gcn_grabcut.metrics import noc_summary
@@ -73,6 +84,7 @@ def main() -> None:
     model = load_model(args.checkpoint, args.model, args.hidden, args.layers, args.device, tag="evaluate_clicks")
     pipeline = GCNGrabCutPipeline(model, sp_config=SuperpixelGraphConfig(n_segments=args.superpixels), device=args.device)
 
+    geodesic = GeodesicHints(args.geodesic_radius, args.hint_gamma) if args.hint_mode == "geodesic" else False
     by_shape: dict = {}
     for p in pairs:
         s = materialise(p)
@@ -88,7 +100,7 @@ def main() -> None:
             r = pipeline.evaluate_clicks([s["image"] for s in chunk], [s["gt_mask"] for s in chunk],
                                          max_clicks=args.max_clicks, iou_targets=tuple(args.targets),
                                          hint_radius=args.hint_radius, iters_per_click=args.iters_per_click,
-                                         stop_iou=args.stop_iou)
+                                         stop_iou=args.stop_iou, geodesic=geodesic)
             names += [s["name"] for s in chunk]
             ious.append(r["ious"])
             clicks += r["clicks"]
@@ -98,7 +110,9 @@ def main() -> None:
     ious = np.concatenate(ious)
     summary = noc_summary(ious, args.targets, args.max_clicks)
 
-    print(f"\n[evaluate_clicks] {len(names)} image(s), up to {args.max_clicks} clicks, hint radius {args.hint_radius}, "
+    how = f"hint radius {args.hint_radius}" if not geodesic else \
+        f"geodesic hints (radius {args.geodesic_radius}, gamma {args.hint_gamma})"
+    print(f"\n[evaluate_clicks] {len(names)} image(s), up to {args.max_clicks} clicks, {how}, "
           f"{args.iters_per_click} GrabCut iteration(s) per click")
     for t in summary["noc"]:
         print(f"  NoC@{t:.2f} = {summary['noc'][t].mean():.2f}   NoF@{t:.2f} = {summary['nof'][t]}")
@@ -107,7 +121,8 @@ def main() -> None:
 
     if args.json:
         doc = {
-            "config": {k: getattr(args, k) for k in ("max_clicks", "targets", "hint_radius", "iters_per_click", "stop_iou",
+            "config": {k: getattr(args, k) for k in ("max_clicks", "targets", "hint_radius", "hint_mode", "hint_gamma",
+                                                      "geodesic_radius", "iters_per_click", "stop_iou",
                                                       "superpixels", "max_size", "checkpoint", "model")},
             "noc": {f"{t:.2f}": float(summary["noc"][t].mean()) for t in summary["noc"]},
             "nof": {f"{t:.2f}": summary["nof"][t] for t in summary["nof"]},

@@ -34,6 +34,7 @@ enum Slot : int {
     S_FOREGROUND, S_FOREGROUND_VEC,
     S_MATTE_EVAL,
     S_FULLCUT,
+    S_GEODESIC,
     S_COUNT
 };
 

@@ -12,6 +12,7 @@ from .data import Data, Batch
 from .grabcut import GrabCut, GrabCutConfig, Label
 from .graph_builder import (
     GraphBuilder, SuperpixelGraph, SuperpixelGraphConfig, compute_auto_prior, encode_user_hints, pack_hints,
+    encode_geodesic_hints,
 )
 from .metrics import (
     evaluate, evaluate_batch, evaluate_trimap, boundary_f1, noc_summary, SegmentationMetrics, TrimapMetrics,
@@ -24,7 +25,8 @@ from .model import (
 from .pipeline import (GCNGrabCutPipeline, ClosedFormMatte, ForegroundColours, FullResolution, SegmentationResult,
                        alpha_matte, clean_mask, closed_form_matte, estimate_foreground, guided_filter, refine_trimap,
                        closed_form_matte_full, lift_trimap, trimap_matte, trimap_matte_full,
-                       trimap_matte_warm, upsample_mask, FullCut, cut_mask_full, lift_labels)
+                       trimap_matte_warm, upsample_mask, FullCut, cut_mask_full, lift_labels,
+                       GeodesicHints, geodesic_hints)
 from .synthetic import synthetic_image, synthetic_batch
 from .losses import FocalLoss, LabelSmoothingCE, TrimapLoss
 from .trainer import Trainer, TrainConfig
@@ -41,6 +43,7 @@ __all__ = [
     "refine_trimap", "upsample_mask", "ClosedFormMatte", "closed_form_matte", "ForegroundColours", "estimate_foreground",
     "trimap_matte", "trimap_matte_warm", "lift_trimap", "closed_form_matte_full", "trimap_matte_full",
     "FullCut", "cut_mask_full", "lift_labels",
+    "GeodesicHints", "geodesic_hints", "encode_geodesic_hints",
     "ResGCNNet", "GCNTrimapNet", "GATTrimapNet", "build_model", "probs_to_node_trimap", "project_to_pixels",
     "Data", "Batch", "synthetic_image", "synthetic_batch",
     "FocalLoss", "LabelSmoothingCE", "TrimapLoss", "Trainer", "TrainConfig",

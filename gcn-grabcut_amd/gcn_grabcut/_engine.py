@@ -225,6 +225,17 @@ class Engine:
                       _native.ptr(mask))
         return mask
 
+    def geodesic_hints(self, bgr, hints, hint_ptr, radius=40, gamma=2, mask=None, segments=None, node_ptr=None,
+                       dist_fg=None, dist_bg=None, node_dist=None):
+        """Geodesic click hints (ggc_geodesic_hints, include/ggc.h H1): bgr (B,H,W,3) uint8 is the guide, hints / hint_ptr
+        as for apply_hints.  mask (B,H,W) uint8 is painted in place; dist_fg / dist_bg (B,H,W) int32 and node_dist (N,2)
+        int32 (with segments and node_ptr) receive the capped distances.  At least one output is needed."""
+        b, h, w, _ = bgr.shape
+        self.ctx.call("ggc_geodesic_hints", self._stream(), b, h, w, bgr.data_ptr(), _native.ptr(hints), hint_ptr.data_ptr(),
+                      int(radius), int(gamma), _native.ptr(segments), _native.ptr(node_ptr), _native.ptr(mask),
+                      _native.ptr(dist_fg), _native.ptr(dist_bg), _native.ptr(node_dist))
+        return mask
+
     def next_click(self, pred, gt) -> torch.Tensor:
         """The next simulated click of the NoC protocol per image (ggc_next_click): pred, gt (B,H,W) uint8, nonzero =
         foreground -> (B,4) int32 on the device = row, col, label (1 = fg, 0 = bg), d2; (-1,-1,-1,0) where pred == gt."""

@@ -120,14 +120,18 @@ class GrabCut:
         self._snapshot("refinement")
         return out
 
-    def add_hints(self, fg_points=(), bg_points=(), radius: int = 5) -> np.ndarray:
+    def add_hints(self, fg_points=(), bg_points=(), radius: int = 5, geodesic=False) -> np.ndarray:
         """Additive: paint user clicks, (row, col) pairs, into the current mask as GC_FGD / GC_BGD disks of `radius` pixels
         (ggc_apply_hints; background clicks win where disks overlap, clicks outside the image are ignored).  The edit runs
-        on the mask the last run left on the device; the GMMs are kept, so refine(n) continues from the edited mask."""
+        on the mask the last run left on the device; the GMMs are kept, so refine(n) continues from the edited mask.
+        geodesic=True or a pipeline.GeodesicHints paints by geodesic distance on self.image instead (ggc_geodesic_hints;
+        `radius` is then ignored): only the clicks of this call bound each other's reach."""
         if self.mask is None:
             raise RuntimeError("Call run_with_bbox or run_with_trimap first.")
         if int(radius) < 0:
             raise ValueError(f"radius must be >= 0, got {radius}")
+        from .pipeline import _geodesic_args
+        geo = _geodesic_args(geodesic)
         from .graph_builder import pack_hints
         rows, ptr = pack_hints([(fg_points, bg_points)])
         eng = self._eng
@@ -135,7 +139,11 @@ class GrabCut:
             self._dmask = eng.to_device(np.ascontiguousarray(self.mask, dtype=np.uint8)[None])   # the host mask was edited
         if ptr[-1]:
             hints, hint_ptr = eng.upload_hints(rows, ptr)
-            eng.apply_hints(self._dmask, hints, hint_ptr, radius)
+            if geo is not None:
+                eng.geodesic_hints(eng.to_device(np.ascontiguousarray(self.image)[None]), hints, hint_ptr, geo.radius, geo.gamma,
+                                   mask=self._dmask)
+            else:
+                eng.apply_hints(self._dmask, hints, hint_ptr, radius)
             self.mask = self._dmask[0].cpu().numpy()
         self._snapshot("hints")
         return self._binary()

@@ -186,6 +186,46 @@ def encode_user_hints(segments: np.ndarray, fg_points, bg_points) -> np.ndarray:
     return hints
 
 
+def geodesic_prior_columns(node_dist: np.ndarray, radius: int, sigma: float) -> np.ndarray:
+    """(N,2) int32 capped per-superpixel distances (min Df, min Db) -> (N,3) float32 soft click columns: e_f =
+    exp(-Df / (80 sigma)), 0 where Df is the cap 80 radius + 1 (no foreground click within reach), e_b likewise, and
+    1 - max(e_f, e_b).  Computed in float64, cast to float32."""
+    nd = np.asarray(node_dist, np.float64).reshape(-1, 2)
+    e = np.where(nd > 80 * int(radius), 0.0, np.exp(-nd / (80.0 * float(sigma))))
+    return np.concatenate([e, 1.0 - e.max(axis=1, keepdims=True)], 1).astype(np.float32)
+
+
+def encode_geodesic_hints(image: np.ndarray, segments: np.ndarray, fg_points, bg_points, geodesic=None,
+                          device="cuda") -> np.ndarray:
+    """Soft click features (additive): the reference paper's "soft distance-based propagation (geodesic
+    distance to the nearest click)" in place of encode_user_hints' binary columns.  image: (H, W, 3) uint8 BGR;
+    segments: (H, W) labels 0..n-1; geodesic: a pipeline.GeodesicHints (None: its defaults).  Row n is (e_f, e_b,
+    1 - max(e_f, e_b)) with e = exp(-D_n / (80 sigma)), D_n the smallest geodesic distance from a pixel of superpixel n
+    to a click of that label (ggc_geodesic_hints' node_dist), and e = 0 beyond the cap.  Without a click in the frame
+    every row is (0, 0, 1), as encode_user_hints gives.  No shipped network was trained on this encoding: it is what
+    segment(..., hints_as_prior=True, geodesic=...) feeds the network, offered for training such a network."""
+    import torch
+    from ._engine import get_engine
+    from .pipeline import GeodesicHints
+    g = GeodesicHints() if geodesic is None or geodesic is True else geodesic
+    if not isinstance(g, GeodesicHints):
+        raise ValueError(f"geodesic must be a GeodesicHints, got {type(geodesic).__name__}")
+    img = _check_image(image)
+    seg = np.ascontiguousarray(segments, np.int32)
+    if seg.shape != img.shape[:2]:
+        raise ValueError(f"segments {seg.shape} do not match the image {img.shape[:2]}")
+    n = int(seg.max()) + 1
+    rows, ptr = pack_hints([(fg_points if fg_points is not None else [], bg_points if bg_points is not None else [])])
+    if len(rows) == 0:
+        return geodesic_prior_columns(np.full((n, 2), 80 * g.radius + 1, np.int32), g.radius, g.sigma)
+    eng = get_engine(device)
+    hint_rows, hint_ptr = eng.upload_hints(rows, ptr)
+    nd = eng.empty(n, 2, dtype=torch.int32)
+    eng.geodesic_hints(eng.to_device(img[None]), hint_rows, hint_ptr, g.radius, g.gamma, segments=eng.to_device(seg[None]),
+                       node_ptr=eng.to_device(np.array([0, n], np.int32)), node_dist=nd)
+    return geodesic_prior_columns(nd.cpu().numpy(), g.radius, g.sigma)
+
+
 def _click_rows(points, label: int, what: str) -> np.ndarray:
     a = np.asarray(list(points) if points is not None else [], dtype=np.float64)
     if a.size == 0:

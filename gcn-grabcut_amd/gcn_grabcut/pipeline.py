@@ -448,6 +448,74 @@ class FullCut:
     n_iter: int = FULL_CUT_ITERS
 
 
+@dataclass(frozen=True)
+class GeodesicHints:
+    """geodesic=GeodesicHints(...) (or geodesic=True for the defaults) makes a click label the pixels that are close to it
+    along paths that do not cross colour edges (ggc_geodesic_hints) instead of a disk of hint_radius.
+    radius in 0..16384: the reach in pixels over flat colour (limit = 80 radius); gamma in 0..64: the weight of the
+    colour term; sigma > 0: the decay, in pixels, of the soft prior columns that hints_as_prior builds from the
+    distances.  The defaults are recorded choices backed by §5.19's study table, not tuned results."""
+    radius: int = 40
+    gamma: int = 2
+    sigma: float = 10.0
+
+    def __post_init__(self):
+        for name, hi in (("radius", 16384), ("gamma", 64)):
+            v = getattr(self, name)
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= int(v) <= hi:
+                raise ValueError(f"GeodesicHints: {name} must be an integer in [0, {hi}], got {v!r}")
+        if not (isinstance(self.sigma, (int, float, np.integer, np.floating)) and np.isfinite(self.sigma) and self.sigma > 0):
+            raise ValueError(f"GeodesicHints: sigma must be a positive number, got {self.sigma!r}")
+
+
+def _geodesic_args(geodesic, hint_region: bool = False) -> "Optional[GeodesicHints]":
+    """The GeodesicHints of a call (True: the defaults), None when the option is off; refused with hint_region."""
+    if geodesic is None or geodesic is False:
+        return None
+    if geodesic is True:
+        geodesic = GeodesicHints()
+    if not isinstance(geodesic, GeodesicHints):
+        raise ValueError(f"geodesic must be True, False or a GeodesicHints, got {type(geodesic).__name__}")
+    if hint_region:
+        raise ValueError("geodesic hints cannot be combined with hint_region=True: the superpixel pass belongs to the disks")
+    return geodesic
+
+
+def geodesic_hints(image: np.ndarray, fg_points, bg_points, radius: int = 40, gamma: int = 2, mask=None,
+                   return_dist: bool = False, device="cuda"):
+    """Geodesic click hints of one image (additive; ggc_geodesic_hints, DESIGN.md §5.19).  image: (H, W, 3) uint8 BGR;
+    fg_points / bg_points: (row, col) pairs as encode_user_hints takes them.  A pixel becomes definite foreground (1) /
+    background (0) when its geodesic distance to the nearest click of that label is at most 80 radius and smaller than
+    the distance to any click of the other label; every other pixel keeps the label of `mask` ((H, W) uint8 GrabCut
+    labels; None: all probable background, 2).  -> the painted (H, W) uint8 mask, or with return_dist=True the two
+    (H, W) int32 maps (Df, Db), capped at 80 radius + 1."""
+    import torch
+    from ._engine import get_engine
+    img = _check_image(image)
+    g = GeodesicHints(radius, gamma)
+    h, w = img.shape[:2]
+    if mask is None:
+        m = np.full((h, w), 2, np.uint8)
+    else:
+        m = np.ascontiguousarray(mask, np.uint8)
+        if m.shape != (h, w):
+            raise ValueError(f"geodesic_hints: mask {m.shape} does not match the image {(h, w)}")
+    eng = get_engine(device)
+    rows, ptr = pack_hints([(fg_points if fg_points is not None else [], bg_points if bg_points is not None else [])])
+    if return_dist and len(rows) == 0:
+        cap = np.full((h, w), 80 * g.radius + 1, np.int32)
+        return cap, cap.copy()
+    hint_rows, hint_ptr = eng.upload_hints(rows, ptr)
+    bgr = eng.to_device(img[None])
+    if return_dist:
+        df, db = eng.empty(1, h, w, dtype=torch.int32), eng.empty(1, h, w, dtype=torch.int32)
+        eng.geodesic_hints(bgr, hint_rows, hint_ptr, g.radius, g.gamma, dist_fg=df, dist_bg=db)
+        return df[0].cpu().numpy(), db[0].cpu().numpy()
+    md = eng.to_device(m[None])
+    eng.geodesic_hints(bgr, hint_rows, hint_ptr, g.radius, g.gamma, mask=md)
+    return md[0].cpu().numpy()
+
+
 def lift_labels(mask: np.ndarray, full_shape, band: Optional[int] = None, device="cuda") -> np.ndarray:
     """A working-size mask carried to a larger size as GrabCut labels for a banded cut there (additive; ggc_lift_labels,
     DESIGN.md §5.18).  The mask is interpolated bilinearly (half-pixel centres, as upsample_mask) and thresholded at 0.5;
@@ -609,11 +677,13 @@ class _Hints:
     radius: int
     region: bool
     as_prior: bool
+    geodesic: "Optional[GeodesicHints]" = None     # set: ggc_geodesic_hints paints the clicks, radius and region do not apply
 
     @staticmethod
-    def of(hints, b: int, radius, region, as_prior) -> "Optional[_Hints]":
+    def of(hints, b: int, radius, region, as_prior, geodesic=None) -> "Optional[_Hints]":
         """hints: one None or (fg_points, bg_points) per image, or an already packed (hints, hint_ptr) pair.
         None when no image has a click, so that such a call launches exactly what a call without hints launches."""
+        geodesic = _geodesic_args(geodesic, region)
         if hints is None:
             return None
         if int(radius) < 0:
@@ -630,13 +700,13 @@ class _Hints:
         if ptr[-1] == 0:
             return None
         return _Hints(np.ascontiguousarray(rows, np.int32), np.ascontiguousarray(ptr, np.int32), int(radius), bool(region),
-                      bool(as_prior))
+                      bool(as_prior), geodesic)
 
     def chunk(self, lo: int, hi: int) -> "Optional[_Hints]":
         k0, k1 = int(self.ptr[lo]), int(self.ptr[hi])
         if k1 == k0:
             return None
-        return _Hints(self.rows[k0:k1], self.ptr[lo:hi + 1] - k0, self.radius, self.region, self.as_prior)
+        return _Hints(self.rows[k0:k1], self.ptr[lo:hi + 1] - k0, self.radius, self.region, self.as_prior, self.geodesic)
 
     def clicked_images(self, h: int, w: int) -> np.ndarray:
         """(B,) bool: the images with at least one click inside the frame."""
@@ -868,25 +938,36 @@ class GCNGrabCutPipeline:
         if hints is not None:
             hint_rows, hint_ptr = eng.upload_hints(hints.rows, hints.ptr)
             if hints.as_prior:
-                prior = self._hints_as_prior(eng, hints, hint_rows, hint_ptr, seg, graphs)
+                prior = self._hints_as_prior(eng, hints, hint_rows, hint_ptr, seg, graphs, bgr)
         probs = eng.predict_probs(self.model, graphs)
         trimap = eng.refine_trimap(probs, graphs.node_ptr, seg, bgr, threshold_fg, threshold_bg, filter_radius,
                                    1e-3, edge_aware)
         if timing is not None:
             timing["gcn_inference"] = tick() - t
         trimap = eng.seed_from_prior(trimap, prior, graphs.node_ptr, seg, 0.1)
-        if hints is not None:                  # hard constraints: over the network's trimap and the seeding alike
+        if hints is not None and hints.geodesic is not None:   # the guide is the caller's BGR batch, never gc_image
+            eng.geodesic_hints(bgr, hint_rows, hint_ptr, hints.geodesic.radius, hints.geodesic.gamma, mask=trimap)
+        elif hints is not None:                # hard constraints: over the network's trimap and the seeding alike
             eng.apply_hints(trimap, hint_rows, hint_ptr, hints.radius, hints.region, seg, graphs.node_ptr)
         return seg, graphs, probs, trimap
 
     @staticmethod
-    def _hints_as_prior(eng, hints, hint_rows, hint_ptr, seg, graphs):
+    def _hints_as_prior(eng, hints, hint_rows, hint_ptr, seg, graphs, bgr=None):
         """The reference's use of encode_user_hints: the prior columns x[:, 16:19] of every image with a click inside the
         frame become its click table; the other images keep the automatic prior.  Returns a copy of the automatic prior,
-        which seed_from_prior still reads."""
+        which seed_from_prior still reads.  Geodesic hints: the table is encode_geodesic_hints', computed on the host
+        in float64 from the per-superpixel distances of ggc_geodesic_hints."""
+        import torch
         auto = graphs.x[:, 16:19].clone()
-        table = eng.empty(graphs.x.size(0), 3)
-        eng.apply_hints(None, hint_rows, hint_ptr, segments=seg, node_ptr=graphs.node_ptr, node_hints=table, shape=seg.shape)
+        if hints.geodesic is not None:
+            from .graph_builder import geodesic_prior_columns
+            g = hints.geodesic
+            nd = eng.empty(graphs.x.size(0), 2, dtype=torch.int32)
+            eng.geodesic_hints(bgr, hint_rows, hint_ptr, g.radius, g.gamma, segments=seg, node_ptr=graphs.node_ptr, node_dist=nd)
+            table = eng.to_device(geodesic_prior_columns(nd.cpu().numpy(), g.radius, g.sigma))
+        else:
+            table = eng.empty(graphs.x.size(0), 3)
+            eng.apply_hints(None, hint_rows, hint_ptr, segments=seg, node_ptr=graphs.node_ptr, node_hints=table, shape=seg.shape)
         clicked = hints.clicked_images(seg.size(1), seg.size(2))
         nptr = graphs.node_ptr_host
         b = 0
@@ -922,7 +1003,7 @@ class GCNGrabCutPipeline:
                              chunks: Optional[int] = None, hints=None, hint_radius: int = 5, hint_region: bool = False,
                              hints_as_prior: bool = False, return_state: bool = False, matte: bool = False,
                              matte_radius: int = MATTE_RADIUS, matte_eps: float = MATTE_EPS, full_bgr=None,
-                             foreground=False, full_cut=False) -> dict:
+                             foreground=False, full_cut=False, geodesic=False) -> dict:
         """bgr: (B,H,W,3) uint8 tensor on the pipeline's device.  Returns device tensors.
 
         matte=True (additive) also returns "alpha" (B,H,W) float32, the soft matte of the cleaned mask (alpha_matte with
@@ -957,6 +1038,11 @@ class GCNGrabCutPipeline:
         first does the same for every superpixel whose clicks all carry one label.  hints_as_prior=True also replaces the
         network's prior columns x[:, 16:19] of each image with a click in the frame by encode_user_hints.  clean_mask
         still runs after GrabCut, so a foreground click on a component smaller than min_area_ratio can be removed.
+        geodesic=True or GeodesicHints(...) (additive) paints the clicks by ggc_geodesic_hints instead: a pixel becomes
+        definite where its geodesic distance on bgr to the nearest click of a label is within the cap and below the
+        distance to every click of the other label.  hint_radius is ignored in geodesic mode,
+        hint_region=True is a ValueError, and hints_as_prior=True then writes encode_geodesic_hints' soft columns (an
+        encoding no shipped network was trained on).  Without clicks the option launches nothing.
 
         Large batches run as a software pipeline (additive, same results): the batch is cut into `chunks` contiguous
         chunks; the front stages of chunk k+1 run on the caller's stream while the GrabCut / clean-up of chunk k runs on a
@@ -970,7 +1056,7 @@ class GCNGrabCutPipeline:
         b = bgr.size(0)
         want = self.grabcut_lanes if grabcut_lanes is None else int(grabcut_lanes)   # (an argument, so that concurrent callers do not mutate the pipeline)
         n_chunks = self.chunks if chunks is None else int(chunks)
-        hints = _Hints.of(hints, b, hint_radius, hint_region, hints_as_prior)
+        hints = _Hints.of(hints, b, hint_radius, hint_region, hints_as_prior, geodesic)
         cfm = _closed_form_args(matte, bgr.shape[1], bgr.shape[2], full_bgr is not None)
         mat = None if cfm else _matte_args(matte, matte_radius, matte_eps)
         fmat = _full_args(full_bgr, bgr.shape, matte_radius, matte_eps)
@@ -1166,7 +1252,7 @@ class GCNGrabCutPipeline:
 
     def segment_batch(self, images: Sequence[np.ndarray], hints=None, full_images=None, **kwargs) -> list[SegmentationResult]:
         """Segment equally sized BGR images as one batch (additive API).  hints: one None or (fg_points, bg_points) per
-        image, with hint_radius / hint_region / hints_as_prior among kwargs (segment_batch_device).  full_images
+        image, with hint_radius / hint_region / hints_as_prior / geodesic among kwargs (segment_batch_device).  full_images
         (additive): the same images at one larger size each, (H1, W1, 3) uint8 BGR; every result's `full` then holds the
         outputs at that size (segment_batch_device's full_bgr).  foreground=True | ForegroundColours(...) among kwargs
         (with a matte) fills every result's foreground and rgba_clean.  full_cut=True | FullCut(...) among kwargs (with
@@ -1179,6 +1265,7 @@ class GCNGrabCutPipeline:
         _closed_form_args(kwargs.get("matte"), *imgs[0].shape[:2], full_images is not None)
         _foreground_args(kwargs.get("foreground"), kwargs.get("matte"), full_images is not None)
         _full_cut_args(kwargs.get("full_cut"), full_images is not None, kwargs.get("matte"))
+        _geodesic_args(kwargs.get("geodesic"), kwargs.get("hint_region", False))
         full_bgr = None
         if full_images is not None:
             fulls = [_check_image(im) for im in full_images]
@@ -1219,9 +1306,23 @@ class GCNGrabCutPipeline:
         binary, mask, bgd, fgd = eng.grabcut_lanes(image, mask, n_iter, 2, self.gc_config.seed, lanes, bgd, fgd)
         return (click, binary, mask, bgd, fgd, eng.iou(binary, gt)[0])
 
+    def _click_round_geodesic(self, binary, gt, mask, image, bgd, fgd, bgr, clicks_dev, idx_dev, k, hint_ptr, geodesic, n_iter=1):
+        """_click_round with geodesic hints: the new click is recorded first, then ALL k clicks made so far on each image
+        are painted (clicks_dev[idx, :k, :3]: exactly k rows per image, rows of -1 are out of frame and ignored, so
+        hint_ptr = arange(n+1) * k), so that an earlier click of the other label bounds the new one's reach."""
+        eng = self._eng
+        click = eng.next_click(binary, gt)
+        clicks_dev[idx_dev, k - 1] = click
+        rows = clicks_dev[idx_dev, :k, :3].reshape(-1, 3).contiguous()
+        eng.geodesic_hints(bgr, rows, hint_ptr, geodesic.radius, geodesic.gamma, mask=mask)
+        b, want = binary.size(0), max(self.grabcut_lanes, 1)
+        lanes = want if b >= 8 * want else 1
+        binary, mask, bgd, fgd = eng.grabcut_lanes(image, mask, n_iter, 2, self.gc_config.seed, lanes, bgd, fgd)
+        return (click, binary, mask, bgd, fgd, eng.iou(binary, gt)[0])
+
     def evaluate_clicks(self, images: Sequence[np.ndarray], gt_masks: Sequence[np.ndarray], max_clicks: int = 20,
                         iou_targets=(0.85, 0.90), hint_radius: int = 5, iters_per_click: int = 1,
-                        stop_iou: Optional[float] = None, return_masks: bool = False) -> dict:
+                        stop_iou: Optional[float] = None, return_masks: bool = False, geodesic=False) -> dict:
         """Click guidance scored by the standard NoC protocol (additive), for equally sized BGR images and their ground
         truth (H,W) masks (nonzero = foreground).
 
@@ -1233,7 +1334,9 @@ class GCNGrabCutPipeline:
         the same place again and again.  With stop_iou, an image whose IoU reaches it gets no further clicks and its
         results stay frozen (the others continue as a compacted batch; a click round does not depend on an image's
         position in the batch, so every image gets what a one-image loop gives it).  The loop stays on the device: per
-        round the host reads only ggc_apply_hints' hint_ptr and the IoU vector.
+        round the host reads only ggc_apply_hints' hint_ptr and the IoU vector.  geodesic=True or GeodesicHints(...)
+        (additive) paints by ggc_geodesic_hints instead of disks: every round passes all the clicks made so far on each
+        active image, guided by the BGR images, which stay on the device; hint_radius is then ignored.
 
         Returns {"clicks": per image a list of (row, col, label) with label 1 = foreground, "ious": (B, max_clicks + 1)
         float64 (IoU after 0..max_clicks clicks; a stopped image repeats its last value), "noc": {t: (B,) int},
@@ -1254,10 +1357,14 @@ class GCNGrabCutPipeline:
         max_clicks, iters_per_click = int(max_clicks), int(iters_per_click)
         if max_clicks < 0 or iters_per_click < 1 or int(hint_radius) < 0:
             raise ValueError("max_clicks >= 0, iters_per_click >= 1 and hint_radius >= 0 are required")
+        geo = _geodesic_args(geodesic)
         eng = self._eng
         b = len(imgs)
         gt = eng.to_device(np.stack([(g != 0) for g in gts]).astype(np.uint8))
-        out = self.segment_batch_device(eng.to_device(np.stack(imgs)), compose=False, return_state=True)
+        bgr = eng.to_device(np.stack(imgs))
+        out = self.segment_batch_device(bgr, compose=False, return_state=True)
+        if geo is None:
+            bgr = None
         binary, mask, bgd, fgd, image = out["gc_binary"], out["gc_mask"], out["bgd"], out["fgd"], out["gc_image"]
         ious = np.zeros((b, max_clicks + 1))
         ious[:, 0] = eng.iou(binary, gt)[0].cpu().numpy()
@@ -1270,11 +1377,13 @@ class GCNGrabCutPipeline:
         idx_dev = torch.arange(b, device=eng.device)
 
         def compact(keep):
-            nonlocal active, idx_dev, binary, mask, bgd, fgd, image, gt
+            nonlocal active, idx_dev, binary, mask, bgd, fgd, image, gt, bgr
             sel = torch.from_numpy(np.nonzero(keep)[0]).to(eng.device)
             active = active[keep]
             idx_dev, binary, mask, gt = (t.index_select(0, sel) for t in (idx_dev, binary, mask, gt))
             bgd, fgd, image = (t.index_select(0, sel) for t in (bgd, fgd, image))
+            if bgr is not None:
+                bgr = bgr.index_select(0, sel)
 
         if stop_iou is not None and (ious[:, 0] >= stop_iou).any():
             compact(ious[:, 0] < stop_iou)
@@ -1288,9 +1397,13 @@ class GCNGrabCutPipeline:
             n = len(active)
             if n not in ptrs:
                 ptrs[n] = torch.arange(n + 1, dtype=torch.int32, device=eng.device)
-            click, binary, mask, bgd, fgd, iou = self._click_round(binary, gt, mask, image, bgd, fgd, ptrs[n], hint_radius,
-                                                                   iters_per_click)
-            clicks_dev[idx_dev, k - 1] = click
+            if geo is not None:
+                click, binary, mask, bgd, fgd, iou = self._click_round_geodesic(
+                    binary, gt, mask, image, bgd, fgd, bgr, clicks_dev, idx_dev, k, ptrs[n] * k, geo, iters_per_click)
+            else:
+                click, binary, mask, bgd, fgd, iou = self._click_round(binary, gt, mask, image, bgd, fgd, ptrs[n], hint_radius,
+                                                                       iters_per_click)
+                clicks_dev[idx_dev, k - 1] = click
             ious[active, k] = iou.cpu().numpy()
             if masks is not None:
                 masks[idx_dev, k] = mask
@@ -1310,7 +1423,8 @@ class GCNGrabCutPipeline:
                 edge_aware: bool = True, filter_radius: int = 8, fg_points=None, bg_points=None, hint_radius: int = 5,
                 hint_region: bool = False, hints_as_prior: bool = False, matte: bool = False,
                 matte_radius: int = MATTE_RADIUS, matte_eps: float = MATTE_EPS,
-                full_image: Optional[np.ndarray] = None, foreground=False, full_cut=False) -> SegmentationResult:
+                full_image: Optional[np.ndarray] = None, foreground=False, full_cut=False,
+                geodesic=False) -> SegmentationResult:
         """Full pipeline on one BGR image (reference pipeline.py:265-352).
 
         Additive: fg_points / bg_points are user clicks, (row, col) pairs, applied as hard constraints on the trimap
@@ -1321,8 +1435,10 @@ class GCNGrabCutPipeline:
         alpha, rgba_soft and binary_mask come from closed_form_matte_full); foreground=True | ForegroundColours(...),
         with a matte, fills the result's foreground and rgba_clean (estimate_foreground under that matte's alpha);
         full_cut=True | FullCut(...), with full_image, makes the full binary_mask, overlay and rgba those of
-        cut_mask_full of the cleaned mask (segment_batch_device)."""
+        cut_mask_full of the cleaned mask (segment_batch_device); geodesic=True | GeodesicHints(...) paints the clicks by
+        their geodesic distance on the image instead of disks (hint_radius is then ignored; segment_batch_device)."""
         image = _check_image(image)
+        _geodesic_args(geodesic, hint_region)
         _closed_form_args(matte, *image.shape[:2], full_image is not None)
         _foreground_args(foreground, matte, full_image is not None)
         _full_cut_args(full_cut, full_image is not None, matte)
@@ -1334,7 +1450,8 @@ class GCNGrabCutPipeline:
                                         min_area_ratio, keep_largest, edge_aware, filter_radius, timing=timing,
                                         hints=hints, hint_radius=hint_radius, hint_region=hint_region,
                                         hints_as_prior=hints_as_prior, matte=matte, matte_radius=matte_radius,
-                                        matte_eps=matte_eps, full_bgr=full_bgr, foreground=foreground, full_cut=full_cut)
+                                        matte_eps=matte_eps, full_bgr=full_bgr, foreground=foreground, full_cut=full_cut,
+                                        geodesic=geodesic)
         return SegmentationResult(
             image=image, binary_mask=out["binary_mask"][0].cpu().numpy(), trimap=out["trimap"][0].cpu().numpy(),
             segments=out["segments"][0].cpu().numpy(), overlay=out["overlay"][0].cpu().numpy(),

@@ -51,7 +51,9 @@
 extern "C" {
 #endif
 
-#define GGC_VERSION 403 /* 0.4.3: ggc_lift_labels (a working-size mask carried to a larger size as GrabCut labels with an open band
+#define GGC_VERSION 404 /* 0.4.4: ggc_geodesic_hints (clicks propagated by a capped, colour-aware shortest-path distance instead of a fixed
+                                  disk; additive, ggc_apply_hints does not change);
+                           0.4.3: ggc_lift_labels (a working-size mask carried to a larger size as GrabCut labels with an open band
                                   around its edge: the start of a banded graph cut on the full image; no existing entry changes);
                            0.4.2: ggc_lift_trimap, ggc_trimap_matte_warm, ggc_closed_form_band (a working-size closed-form matte carried to a
                                   larger image: lifted trimap and start, a stop rule that does not move with the start; the two
@@ -406,6 +408,40 @@ int ggc_grid_maxflow(ggc_ctx* ctx, ggc_stream stream, int B, int H, int W, int n
 int ggc_apply_hints(ggc_ctx* ctx, ggc_stream stream, int B, int H, int W, const int32_t* hints, const int32_t* hint_ptr,
                     int radius, int region, const int32_t* segments, const int32_t* node_ptr,
                     float* node_hints, uint8_t* mask);
+
+/* H1 — geodesic click hints (additive): a click labels the pixels that are close to it along paths that do not cross colour
+ * edges, instead of ggc_apply_hints' fixed disk.  One exact integer definition; no float is involved anywhere.
+ *   bgr      [dev] u8  [B,H,W,3] the images (the guide)
+ *   hints, hint_ptr             ggc_apply_hints' packing: rows (row, col, label != 0 = foreground), image b owns
+ *                               hints[hint_ptr[b] .. hint_ptr[b+1]); hint_ptr[0] = 0, non-decreasing
+ *   radius   0 .. 16384: limit = 80 * radius          gamma   0 .. 64: weight of the colour term
+ *   segments [dev] i32 [B,H,W] local labels, node_ptr [dev] i32 [B+1]  (both may be NULL unless node_dist is given)
+ *   mask     [dev] u8  [B,H,W] in/out GrabCut labels, may be NULL
+ *   dist_fg, dist_bg [dev] i32 [B,H,W] out, each may be NULL
+ *   node_dist [dev] i32 [N_total,2] out, may be NULL           (at least one of the four outputs must be given)
+ * Guide: S_c(y,x) = sum of the nine bytes I_c(clamp(y+dy, 0, H-1), clamp(x+dx, 0, W-1)), dy, dx in {-1,0,1}: a 3x3 box sum with
+ * replicated border, 0 .. 2295 per channel.  Arcs: the grid is 8-connected, arcs only between pixels inside the image, and
+ *   c(p,q) = L(p,q) + gamma * (|S_0(p)-S_0(q)| + |S_1(p)-S_1(q)| + |S_2(p)-S_2(q)|),   L = 80 axial, 113 diagonal (80 * sqrt 2),
+ * symmetric.  Sources: a click outside its image is ignored; a pixel clicked more than once takes the label of the image's LAST
+ * click on it, so an image's foreground and background sources are disjoint.  Df(p), Db(p) = cost of the cheapest path from p
+ * to the nearest foreground / background source.  dist_fg / dist_bg receive min(D, limit + 1); an image or label without a
+ * source reports limit + 1 everywhere.  Label rule: mask = GGC_FGD where Df <= limit and Df < Db, GGC_BGD where Db <= limit and
+ * Db < Df; every other pixel, ties included, is neither read nor written.  A source has distance 0 and takes its own label.
+ * node_dist[n] = (min Df, min Db) of the capped values over the pixels of superpixel n of its image (labels outside
+ * [0, n_nodes) are skipped), written for every node of every image, by integer atomicMin.
+ * Ranges: the largest arc is 113 + 64 * 6885 = 440 753 and no stored value exceeds limit + 1 <= 1 310 721, so every sum the
+ * relaxation forms stays below 2^21 + 2^19: everything fits int32.  radius or gamma out of range, a malformed hint_ptr /
+ * node_ptr, or no output at all is GGC_E_INVALID_ARG, before any launch; B <= 65535, H, W >= 1 else GGC_E_SHAPE.  B == 0 or
+ * K = hint_ptr[B] == 0 is a no-op: nothing is written.  The shortest-path value is unique, so the outputs do not depend on
+ * the schedule, and every image's outputs equal those of its single-image call bit for bit.  Work beyond two streaming
+ * launches is O(clicks * radius^2): tiles farther than `radius` pixels from every click are never visited.  The relaxation
+ * runs in rounds, one launch each; past min(radius, 1024 * tiles per image - 1) + 2 rounds it returns GGC_E_DEVICE
+ * "geodesic hints did not converge" (it cannot hang).  Scratch: 6 bytes per pixel for the guide, 4 more for each of dist_fg /
+ * dist_bg that is NULL, and 16 bytes per 32x32 tile.  SYNCHRONISES the stream: hint_ptr, node_ptr (with node_dist) and the
+ * work-list length every few rounds are read back. */
+int ggc_geodesic_hints(ggc_ctx* ctx, ggc_stream stream, int B, int H, int W, const uint8_t* bgr, const int32_t* hints,
+                       const int32_t* hint_ptr, int radius, int gamma, const int32_t* segments, const int32_t* node_ptr,
+                       uint8_t* mask, int32_t* dist_fg, int32_t* dist_bg, int32_t* node_dist);
 
 /* C0 — next simulated click per image (additive; the standard NoC protocol of interactive segmentation).
  *   pred [dev] u8  [B,H,W]  current binary mask (nonzero = foreground)

@@ -57,6 +57,13 @@ def build_parser() -> argparse.ArgumentParser:
                         help="Background click in original-image pixels (repeatable; needs --image)")
     parser.add_argument("--hint-radius", type=int, default=5,
                         help="Radius in pixels of the image as segmented (after --max-size) painted around each click")
+    # additive: geodesic click hints (ggc_geodesic_hints) instead of disks
+    parser.add_argument("--hint-mode", choices=["disk", "geodesic"], default="disk",
+                        help="How a click is painted: a disk of --hint-radius, or the pixels within a geodesic distance of "
+                             "it that does not cross colour edges (--geodesic-radius, --hint-gamma; --hint-radius is ignored)")
+    parser.add_argument("--hint-gamma", type=int, default=2, help="Weight of the colour term of the geodesic distance, 0..64")
+    parser.add_argument("--geodesic-radius", type=int, default=40,
+                        help="Reach of a geodesic click over flat colour, in pixels of the image as segmented, 0..16384")
     # additive: soft alpha matte of the mask (ggc_alpha_matte), computed when --save asks for alpha or cutout
     parser.add_argument("--matte-radius", type=int, default=4,
                         help="Window radius of the alpha matte, 1..64, in pixels of the image as segmented")
@@ -173,6 +180,10 @@ def main() -> None:
         parser.error("--fg-point / --bg-point are clicks on one image: use them with --image, not --input")
     if args.hint_radius < 0:
         parser.error("--hint-radius must be >= 0")
+    if not 0 <= args.hint_gamma <= 64:
+        parser.error("--hint-gamma must be in 0..64")
+    if not 0 <= args.geodesic_radius <= 16384:
+        parser.error("--geodesic-radius must be in 0..16384")
     matte = "alpha" in args.save or "cutout" in args.save
     if (matte or args.full_res) and not 1 <= args.matte_radius <= 64:
         parser.error("--matte-radius must be in 1..64")
@@ -266,6 +277,9 @@ def main() -> None:
                 hint_kw = dict(hints=[(scale_points(args.fg_point, orig_hw, image.shape[:2]),
                                        scale_points(args.bg_point, orig_hw, image.shape[:2]))],
                                hint_radius=args.hint_radius)
+                if args.hint_mode == "geodesic":
+                    from src.gcn_grabcut import GeodesicHints
+                    hint_kw.update(geodesic=GeodesicHints(args.geodesic_radius, args.hint_gamma))
             if closed_form is not None:                 # an image within --max-size is already solved at its own size
                 import dataclasses
                 hint_kw.update(matte=closed_form if chunk[0][2] is not None else
