@@ -153,7 +153,7 @@ __global__ void __launch_bounds__(256) k_mf_relax_wave(GcDims d, MfTiles tl, int
         ck.begin();
         const int tile = __builtin_amdgcn_readfirstlane(tile_nx);
         tile_nx = t + G < n_in ? list_in[t + G] : 0;
-        const int nbm = mf_relax_visit<false, PROF>(d, tl, tile, lane, lds[wv], rmask, dirty, rc, dist, flag_in, ck);
+        const int nbm = mf_relax_visit<false, PROF, GGC_MF_RELAX_BFS != 0>(d, tl, tile, lane, lds[wv], rmask, dirty, rc, dist, flag_in, ck);
         const int b = tile / tiles_per_image, tr = tile % tiles_per_image;
         const int tyi = tr / tl.rt_x, txi = tr % tl.rt_x;
         if (lane < 9 && (nbm >> lane) & 1) {
@@ -166,7 +166,7 @@ __global__ void __launch_bounds__(256) k_mf_relax_wave(GcDims d, MfTiles tl, int
     }
     if (PROF && (threadIdx.x & 63) == 0 && ck.sum[3]) {                     // GGC_MF_TRACE: one set of atomics per wave
         unsigned long long* q = reinterpret_cast<unsigned long long*>(prof) + (64 + (blockIdx.x & 63)) * 8;
-        for (int k = 0; k < 5; ++k) atomicAdd(&q[k], (unsigned long long)ck.sum[k]);
+        for (int k = 0; k < 7; ++k) atomicAdd(&q[k], (unsigned long long)ck.sum[k]);
     }
     flush_tiles(outl, list_out, n_out);
 }
@@ -528,14 +528,14 @@ struct MfTrace {
     // after the active scan: the relabel visits' clocks, active pixels and open images, the stragglers by image
     int round(const MfSolve& s, int round, int n_next, int total_active, int relax_launches) {
         ggc_ctx* ctx = s.ctx;
-        long long hh[64 * 8], h[5] = {0, 0, 0, 0, 0};
+        long long hh[64 * 8], h[7] = {0, 0, 0, 0, 0, 0, 0};
         GGC_HIP(ctx, hipStreamSynchronize(s.st));
         GGC_HIP(ctx, hipMemcpy(hh, s.prof + 64 * 8, sizeof hh, hipMemcpyDeviceToHost));
         GGC_HIP(ctx, hipMemsetAsync(s.prof + 64 * 8, 0, sizeof hh, s.st));
-        for (int i = 0; i < 64; ++i) for (int k = 0; k < 5; ++k) h[k] += hh[i * 8 + k];
+        for (int i = 0; i < 64; ++i) for (int k = 0; k < 7; ++k) h[k] += hh[i * 8 + k];
         if (h[3] > 0)
-            std::fprintf(stderr, "    [relabel visits] %lld dense visits: per visit load+fill %.2f us, sweeps %.2f us (%.1f sweeps), write-back %.2f us\n",
-                         h[3], 0.01 * h[0] / h[3], 0.01 * h[1] / h[3], (double)h[4] / h[3], 0.01 * h[2] / h[3]);
+            std::fprintf(stderr, "    [relabel visits] %lld dense visits: per visit load+fill %.2f us, sweeps %.2f us (%.1f sweeps, %.1f BFS levels, %lld visits fell back), write-back %.2f us\n",
+                         h[3], 0.01 * h[0] / h[3], 0.01 * h[1] / h[3], (double)h[4] / h[3], (double)h[5] / h[3], h[6], 0.01 * h[2] / h[3]);
         std::vector<int32_t> act;
         if (int rcode = read_i32(ctx, s.st, s.ctl.active, s.d.B, act)) return rcode;
         const auto t_now = std::chrono::steady_clock::now();

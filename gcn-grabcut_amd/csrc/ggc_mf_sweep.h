@@ -181,14 +181,146 @@ __device__ __forceinline__ int relax_sweep_h(RelaxWaveLds& S, const uint32_t (&i
 template <bool PROF>
 struct MfRelaxClocks {
     long long t0 = 0, t1 = 0, t2 = 0;      // this visit: start, first sweep, end of the sweeps
-    int n_sw = 0;                          // this visit's sweeps
-    long long sum[5] = {0, 0, 0, 0, 0};    // load + fill, sweeps, write-back + hand-over, visits, sweeps
+    int n_sw = 0, n_lv = 0, n_fb = 0;      // this visit's sweeps, BFS levels, 1 when the BFS handed it to the sweeps
+    long long sum[7] = {0, 0, 0, 0, 0, 0, 0};   // load + fill, sweeps | levels, write-back + hand-over, visits, sweeps, BFS levels, fallbacks
     __device__ __forceinline__ long long now() const { return PROF ? wall_clock64() : 0; }
-    __device__ __forceinline__ void begin() { t0 = now(); n_sw = 0; }
+    __device__ __forceinline__ void begin() { t0 = now(); n_sw = n_lv = n_fb = 0; }
     __device__ __forceinline__ void end() {
-        if (PROF) { sum[0] += t1 - t0; sum[1] += t2 - t1; sum[2] += wall_clock64() - t2; sum[3] += 1; sum[4] += n_sw; }
+        if (PROF) {
+            sum[0] += t1 - t0; sum[1] += t2 - t1; sum[2] += wall_clock64() - t2; sum[3] += 1; sum[4] += n_sw; sum[5] += n_lv; sum[6] += n_fb;
+        }
     }
 };
+
+// ---- relabel tile visit as a level-synchronous BFS on bit rows ------------------------------------------------------
+// Every arc has length 1, so the fixpoint of a visit whose labelled pixels are all sink pixels (label 1) is a multi-source
+// BFS: from the label-1 pixels at level 1 and from the halo, a border pixel entering at 1 + the lowest halo label behind
+// its arcs that leave the tile.  Lane r (both halves of the wave carry the same rows) holds row r as 32-bit words: A[dir]
+// (bit x: pixel (r, x) has a residual arc towards dir), `done`, `front`.  A level is eight shifted ANDs against the front
+// rows r - 1, r, r + 1 — 75 instructions for the whole tile, where a min-plus sweep is ~640.  A pixel's level INDEX
+// (< MF_BFS_CAP <= 128) is kept in seven bit planes, the level's label in a table (levels skip when the front runs dry and
+// the next source enters), so nothing is stored per pixel inside the loop; one decode pass writes the labels that fell.
+// The sweeps remain the general visit: a start label below the BFS label (or a labelled pixel the BFS does not reach)
+// would have to be carried on, and a tile with more than MF_BFS_CAP levels (corridors: the serpentine nets have in-tile
+// paths of 1 024) is theirs too.  Both tests are wave-uniform; a visit that fails the first puts the start labels back.
+#ifndef GGC_MF_RELAX_BFS
+#define GGC_MF_RELAX_BFS 1          // k_mf_relax_wave: 1 = BFS visit with the sweeps as fallback, 0 = sweeps only
+#endif
+constexpr int MF_BFS_CAP = 96;      // levels per visit; an unobstructed front crosses the tile in 32
+
+__device__ __forceinline__ uint64_t bit_transpose8(uint64_t x) {            // 8x8 bits: bit 8 i + j <-> bit 8 j + i
+    uint64_t t;
+    t = (x ^ (x >> 7)) & 0x00AA00AA00AA00AAull;  x ^= t ^ (t << 7);
+    t = (x ^ (x >> 14)) & 0x0000CCCC0000CCCCull; x ^= t ^ (t << 14);
+    t = (x ^ (x >> 28)) & 0x00000000F0F0F0F0ull; x ^= t ^ (t << 28);
+    return x;
+}
+__device__ __forceinline__ int mf_wave_min(int v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o, 64));
+    return v;
+}
+// entry level of a border pixel: 1 + the lowest halo label behind an open arc (b*: the INVERTED arc bit), DINF if none
+__device__ __forceinline__ int mf_entry3(int v0, uint32_t b0, int v1, uint32_t b1, int v2, uint32_t b2) {
+    const int m = min3i((b0 & 1u) ? DINF : v0, (b1 & 1u) ? DINF : v1, (b2 & 1u) ? DINF : v2);
+    return min(m, DINF - 1) + 1;
+}
+
+// S.d / S.m as the load phase left them, old[]: the lane's 16 start labels (rows 16h .., column lx).  Returns true with the
+// visit's labels in S.d, or false with S.d as it was (the caller sweeps).  S.m is dead once the arc rows are in registers
+// (the caller holds its gate words already): its first MF_BFS_CAP words become the level table.
+template <bool PROF>
+__device__ __forceinline__ bool mf_relax_visit_bfs(RelaxWaveLds& S, const int (&old)[16], int lane, MfRelaxClocks<PROF>& ck) {
+    constexpr int T = MF_RT;
+    static_assert(MF_BFS_CAP <= 4 * T && MF_BFS_CAP <= 128 && MF_BFS_CAP * 4 <= (int)sizeof(S.m), "level index: 7 bits; table inside S.m");
+    const int r = lane & 31, h = lane >> 5;
+    const uint8_t* sm = reinterpret_cast<const uint8_t*>(&S.m[0][0]);
+    int* lv = reinterpret_cast<int*>(&S.m[0][0]);
+    uint32_t A[8] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {                                          // 8 pixels x 8 arcs at a time
+        const uint64_t x = bit_transpose8((uint64_t)S.m[r][2 * g] | (uint64_t)S.m[r][2 * g + 1] << 32);
+#pragma unroll
+        for (int dir = 0; dir < 8; ++dir) A[dir] |= (uint32_t)((x >> (8 * dir)) & 0xffu) << (8 * g);
+    }
+#pragma unroll
+    for (int dir = 0; dir < 8; ++dir) A[dir] = ~A[dir];                    // the bytes are inverted
+    // entry levels: left / right border pixel of row r; lanes 0..31 the top row's pixel x = r, lanes 32..63 the bottom row's
+    const int eL = mf_entry3(S.d[r][0], ~A[4], S.d[r + 1][0], ~A[0], S.d[r + 2][0], ~A[7]);
+    const int eR = mf_entry3(S.d[r][T + 1], ~A[6] >> 31, S.d[r + 1][T + 1], ~A[1] >> 31, S.d[r + 2][T + 1], ~A[5] >> 31);
+    const uint32_t ib = sm[(h ? T - 1 : 0) * T + r];
+    const int hr = h ? T + 1 : 0;
+    const int eTB = mf_entry3(S.d[hr][r], ib >> (h ? 7 : 4), S.d[hr][r + 1], ib >> (h ? 3 : 2), S.d[hr][r + 2], ib >> (h ? 5 : 6));
+    uint32_t one = 0u;                                                      // row r: pixels that start at label 1
+#pragma unroll
+    for (int q = 0; q < 16; ++q) {                                         // a ballot over the column layout IS two bit rows
+        const unsigned long long bal = __ballot(old[q] == 1);
+        one = (r == q) ? (uint32_t)bal : one;
+        one = (r == 16 + q) ? (uint32_t)(bal >> 32) : one;
+    }
+    mf_wave_sync();                                                        // S.m is read: the level table may overwrite it
+    uint32_t done = 0u, front = 0u, pl[7] = {0u, 0u, 0u, 0u, 0u, 0u, 0u};
+    const int up_lane = (r == 0 ? lane : lane - 1) * 4, dn_lane = (r == T - 1 ? lane : lane + 1) * 4;   // ds_bpermute byte addresses
+    const uint32_t up_ok = r == 0 ? 0u : ~0u, dn_ok = r == T - 1 ? 0u : ~0u;    // row 0 has no row above in the tile, row 31 none below
+    // the lowest entry level still pending (DINF: none) — at the start and whenever the front runs dry
+    auto next_level = [&]() {
+        int c = (one & ~done) ? 1 : DINF;
+        c = min(c, (done & 1u) ? DINF : eL);
+        c = min(c, (done >> 31) ? DINF : eR);
+        const uint32_t d0 = __builtin_amdgcn_readlane(done, 0), d31 = __builtin_amdgcn_readlane(done, 31);
+        c = min(c, (((h ? d31 : d0) >> r) & 1u) ? DINF : eTB);
+        return __builtin_amdgcn_readfirstlane(mf_wave_min(c));
+    };
+    int L = next_level();                                                  // wave-uniform, kept scalar
+    bool finished = L >= DINF;
+    for (int k = 0; k < MF_BFS_CAP && !finished; ++k) {
+        if (lane == 0) lv[k] = L;
+        const unsigned long long tb = __ballot(eTB == L);                  // top row's entries | bottom row's entries
+        uint32_t own = (eL == L ? 1u : 0u) | (eR == L ? 0x80000000u : 0u);
+        own |= ((uint32_t)tb & ~up_ok) | ((uint32_t)(tb >> 32) & ~dn_ok);
+        if (L == 1) own |= one;
+        const uint32_t fu = (uint32_t)__builtin_amdgcn_ds_bpermute(up_lane, (int)front) & up_ok;   // rows r - 1, r + 1
+        const uint32_t fd = (uint32_t)__builtin_amdgcn_ds_bpermute(dn_lane, (int)front) & dn_ok;
+        const uint32_t reach = (A[0] & (front << 1)) | (A[1] & (front >> 1)) | (A[2] & fu) | (A[3] & fd) |
+                               (A[4] & (fu << 1)) | (A[5] & (fd >> 1)) | (A[6] & (fu >> 1)) | (A[7] & (fd << 1));
+        const uint32_t nw = (reach | own) & ~done;
+        done |= nw;
+#pragma unroll
+        for (int j = 0; j < 7; ++j) pl[j] |= ((k >> j) & 1) ? nw : 0u;
+        front = nw;
+        if (PROF) ++ck.n_lv;
+        if (__any(nw != 0u)) ++L;
+        else { L = next_level(); finished = L >= DINF; }
+    }
+    if (!finished) return false;
+    mf_wave_sync();
+    // decode: lane (r, h) has columns 16h .. 16h + 15 of row r
+    uint32_t viol = 0u;
+#pragma unroll
+    for (int g = 0; g < 2; ++g) {
+        uint64_t x = 0;
+#pragma unroll
+        for (int j = 0; j < 7; ++j) x |= (uint64_t)((pl[j] >> (16 * h + 8 * g)) & 0xffu) << (8 * j);
+        x = bit_transpose8(x);                                             // byte i: level index of pixel 8g + i
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            const int c = 16 * h + 8 * g + i;
+            const bool reached = (done >> c) & 1u;
+            const int start = S.d[r + 1][c + 1];
+            const int b = reached ? lv[(int)((x >> (8 * i)) & 0x7fu)] : DINF;
+            viol |= reached ? (uint32_t)(start < b) : (uint32_t)(start != DINF);
+            if (b < start) S.d[r + 1][c + 1] = b;
+        }
+    }
+    mf_wave_sync();
+    if (__any(viol != 0u)) {                                               // back to the start labels (column layout)
+#pragma unroll
+        for (int q = 0; q < 16; ++q) S.d[16 * h + q + 1][r + 1] = old[q];
+        mf_wave_sync();
+        return false;
+    }
+    return true;
+}
 
 // One wave relabels the 32x32 tile `tile`: labels of tile + halo and arc masks to LDS (border arcs of a dirty tile re-read
 // and repaired), V and H sweeps to the tile's fixpoint, changed labels back to dist.  Returns, in every lane, the 9-bit mask
@@ -197,7 +329,8 @@ struct MfRelaxClocks {
 //           order; the visit consumes the tile's membership flag itself once its loads are issued.
 //   ASYNC = true (k_mf_relax_async, one launch for the whole front): labels are read with sc1 loads and lowered with a
 //           device-scope atomicMin (ggc_maxflow_async.hip); the caller consumes the flag when it pops the tile.
-template <bool ASYNC, bool PROF>
+//   BFS (k_mf_relax_wave only): mf_relax_visit_bfs first, the sweeps where it declines.
+template <bool ASYNC, bool PROF, bool BFS = false>
 __device__ __forceinline__ int mf_relax_visit(const GcDims& d, const MfTiles& tl, int tile, int lane, RelaxWaveLds& S,
                                               uint8_t* rmask, int32_t* dirty, const int32_t* rc,
                                               int32_t* dist, int32_t* flag, MfRelaxClocks<PROF>& ck) {
@@ -254,7 +387,11 @@ __device__ __forceinline__ int mf_relax_visit(const GcDims& d, const MfTiles& tl
     for (int r = 0; r < 16; ++r) old[r] = S.d[16 * h + r + 1][lx + 1];
     bool settled = false;
     ck.t1 = ck.now();
-    for (int it = 0; it < 4 * T; ++it) {   // a sweep pair that changes nothing: fixpoint (a visit capped at 2-6 sweeps and re-queued
+    if (BFS) {
+        settled = mf_relax_visit_bfs<PROF>(S, old, lane, ck);
+        if (PROF && !settled) ck.n_fb = 1;
+    }
+    for (int it = 0; it < 4 * T && !(BFS && settled); ++it) {   // a sweep pair that changes nothing: fixpoint (a visit capped at 2-6 sweeps and re-queued
                                            // publishes its border earlier, but costs more visits: 56.4 -> 60.3 / 58.1 / 56.6 ms)
         const int ch = (it & 1) ? relax_sweep_h(S, inv_h, lx, h) : relax_sweep_v(S, inv_v, lx, h);
         mf_wave_sync();
