@@ -109,6 +109,31 @@ MATTE_RADIUS = 4
 MATTE_EPS = 1e-4
 
 
+def _check_mask(mask, what: str, shape=None) -> np.ndarray:
+    """`what`'s mask as an array: values in {0, 1}, and (H, W) = shape when that is given."""
+    m = np.asarray(mask)
+    if shape is not None and m.shape != shape:
+        raise ValueError(f"{what}: mask {m.shape} does not match image {shape}")
+    if m.size and not np.isin(m, (0, 1)).all():
+        raise ValueError(f"{what}: mask values must be 0 or 1")
+    return m
+
+
+def _check_trimap(trimap, what: str, shape) -> np.ndarray:
+    """`what`'s trimap as an array: (H, W) = shape, uint8."""
+    t = np.asarray(trimap)
+    if t.shape != shape:
+        raise ValueError(f"{what}: trimap {t.shape} does not match image {shape}")
+    if t.dtype != np.uint8:
+        raise ValueError(f"{what}: trimap must be uint8 (255 foreground, 0 background, else unknown), got {t.dtype}")
+    return t
+
+
+def _with_info(value, iters, rel, return_info: bool):
+    """A solver's host result for one image: with return_info, (value, iterations, relative residual)."""
+    return (value, int(iters[0].item()), float(rel[0].item())) if return_info else value
+
+
 def alpha_to_u8(alpha: np.ndarray) -> np.ndarray:
     """(H, W) alpha in [0, 1] -> uint8 round(255 alpha), the alpha channel of a cut-out."""
     return np.floor(np.asarray(alpha, np.float64) * 255.0 + 0.5).astype(np.uint8)
@@ -126,11 +151,7 @@ def alpha_matte(image: np.ndarray, mask: np.ndarray, radius: int = MATTE_RADIUS,
     -> (H, W) float32."""
     from ._engine import get_engine, check_matte_args
     image = _check_image(image)
-    m = np.asarray(mask)
-    if m.shape != image.shape[:2]:
-        raise ValueError(f"alpha_matte: mask {m.shape} does not match image {image.shape[:2]}")
-    if m.size and not np.isin(m, (0, 1)).all():
-        raise ValueError("alpha_matte: mask values must be 0 or 1")
+    m = _check_mask(mask, "alpha_matte", image.shape[:2])
     check_matte_args(radius, eps)
     eng = get_engine(device)
     bgr = eng.to_device(image[None])
@@ -184,18 +205,13 @@ def closed_form_matte(image: np.ndarray, mask: np.ndarray, radius: int = CF_RADI
     -> (H, W) float32 in [0, 1]; with return_info, (alpha, iterations, relative residual)."""
     from ._engine import get_engine, check_closed_form_args, check_closed_form_shape
     image = _check_image(image)
-    m = np.asarray(mask)
-    if m.shape != image.shape[:2]:
-        raise ValueError(f"closed_form_matte: mask {m.shape} does not match image {image.shape[:2]}")
-    if m.size and not np.isin(m, (0, 1)).all():
-        raise ValueError("closed_form_matte: mask values must be 0 or 1")
+    m = _check_mask(mask, "closed_form_matte", image.shape[:2])
     check_closed_form_args(radius, eps, band, max_iter, tol)
     check_closed_form_shape(*image.shape[:2], radius)
     eng = get_engine(device)
     alpha, iters, rel = eng.closed_form_matte(eng.to_device(image[None]), eng.to_device(np.ascontiguousarray(m, np.uint8)[None]),
                                               radius, eps, band, max_iter, tol)
-    a = alpha[0].cpu().numpy()
-    return (a, int(iters[0].item()), float(rel[0].item())) if return_info else a
+    return _with_info(alpha[0].cpu().numpy(), iters, rel, return_info)
 
 
 def trimap_matte(image: np.ndarray, trimap: np.ndarray, radius: int = CF_RADIUS, eps: float = CF_EPS,
@@ -234,11 +250,7 @@ def _trimap_matte(image, trimap, radius, eps, max_iter, tol, alpha0, return_info
     """trimap_matte and trimap_matte_warm: the checks, then Engine.trimap_matte on a batch of one."""
     from ._engine import get_engine, check_closed_form_args, check_closed_form_shape
     image = _check_image(image)
-    t = np.asarray(trimap)
-    if t.shape != image.shape[:2]:
-        raise ValueError(f"trimap_matte: trimap {t.shape} does not match image {image.shape[:2]}")
-    if t.dtype != np.uint8:
-        raise ValueError(f"trimap_matte: trimap must be uint8 (255 foreground, 0 background, else unknown), got {t.dtype}")
+    t = _check_trimap(trimap, "trimap_matte", image.shape[:2])
     a0 = None
     if alpha0 is not None:
         a0 = np.asarray(alpha0)
@@ -254,8 +266,7 @@ def _trimap_matte(image, trimap, radius, eps, max_iter, tol, alpha0, return_info
     start = None if a0 is None else eng.to_device(np.ascontiguousarray(a0, np.float32)[None])
     alpha, iters, rel = eng.trimap_matte(eng.to_device(image[None]), eng.to_device(np.ascontiguousarray(t)[None]), radius,
                                          eps, max_iter, tol, alpha0=start, warm=warm)
-    a = alpha[0].cpu().numpy()
-    return (a, int(iters[0].item()), float(rel[0].item())) if return_info else a
+    return _with_info(alpha[0].cpu().numpy(), iters, rel, return_info)
 
 
 def lift_trimap(trimap: np.ndarray, alpha: np.ndarray, full_shape, grow: int = CF_GROW, device="cuda"):
@@ -300,8 +311,7 @@ def _check_full_solve(image, full_image, radius, eps, band, max_iter, tol, grow,
 
 def _full_solve_result(eng, bgr_full, trimap, alpha, radius, eps, grow, full_max_iter, tol, return_info):
     a_full, _, iters, rel = eng.closed_form_full(bgr_full, trimap, alpha, bgr_full, radius, eps, grow, full_max_iter, tol)
-    a = a_full[0].cpu().numpy()
-    return (a, int(iters[0].item()), float(rel[0].item())) if return_info else a
+    return _with_info(a_full[0].cpu().numpy(), iters, rel, return_info)
 
 
 def closed_form_matte_full(image: np.ndarray, mask: np.ndarray, full_image: np.ndarray, radius: int = CF_RADIUS,
@@ -322,11 +332,7 @@ def closed_form_matte_full(image: np.ndarray, mask: np.ndarray, full_image: np.n
     from ._engine import get_engine
     image, full = _check_full_solve(image, full_image, radius, eps, band, max_iter, tol, grow, full_max_iter,
                                     "closed_form_matte_full")
-    m = np.asarray(mask)
-    if m.shape != image.shape[:2]:
-        raise ValueError(f"closed_form_matte_full: mask {m.shape} does not match image {image.shape[:2]}")
-    if m.size and not np.isin(m, (0, 1)).all():
-        raise ValueError("closed_form_matte_full: mask values must be 0 or 1")
+    m = _check_mask(mask, "closed_form_matte_full", image.shape[:2])
     eng = get_engine(device)
     binary = eng.to_device(np.ascontiguousarray(m, np.uint8)[None])
     alpha, _, _ = eng.closed_form_matte(eng.to_device(image[None]), binary, radius, eps, band, max_iter, tol)
@@ -346,11 +352,7 @@ def trimap_matte_full(image: np.ndarray, trimap: np.ndarray, full_image: np.ndar
     from ._engine import get_engine
     image, full = _check_full_solve(image, full_image, radius, eps, 0, max_iter, tol, grow, full_max_iter,
                                     "trimap_matte_full")
-    t = np.asarray(trimap)
-    if t.shape != image.shape[:2]:
-        raise ValueError(f"trimap_matte_full: trimap {t.shape} does not match image {image.shape[:2]}")
-    if t.dtype != np.uint8:
-        raise ValueError(f"trimap_matte_full: trimap must be uint8 (255 foreground, 0 background, else unknown), got {t.dtype}")
+    t = _check_trimap(trimap, "trimap_matte_full", image.shape[:2])
     eng = get_engine(device)
     tri = eng.to_device(np.ascontiguousarray(t)[None])
     alpha, _, _ = eng.trimap_matte(eng.to_device(image[None]), tri, radius, eps, max_iter, tol)
@@ -404,8 +406,7 @@ def estimate_foreground(image: np.ndarray, alpha: np.ndarray, eps_r: float = FG_
     fg, iters, rel = eng.estimate_foreground(eng.to_device(image[None]),
                                              eng.to_device(np.ascontiguousarray(a, np.float32)[None]), eps_r, omega,
                                              max_iter, tol)
-    f = fg[0].cpu().numpy()
-    return (f, int(iters[0].item()), float(rel[0].item())) if return_info else f
+    return _with_info(fg[0].cpu().numpy(), iters, rel, return_info)
 
 
 def upsample_mask(image: np.ndarray, mask: np.ndarray, full_image: np.ndarray, radius: int = MATTE_RADIUS,
@@ -422,8 +423,7 @@ def upsample_mask(image: np.ndarray, mask: np.ndarray, full_image: np.ndarray, r
     full = _check_image(full_image)
     m = np.asarray(mask)
     check_upsample_shapes((1, *image.shape), (1, *m.shape), (1, *full.shape), "upsample_mask")
-    if m.size and not np.isin(m, (0, 1)).all():
-        raise ValueError("upsample_mask: mask values must be 0 or 1")
+    _check_mask(m, "upsample_mask")
     check_matte_args(radius, eps)
     eng = get_engine(device)
     alpha, binary, _ = eng.upsample_matte(eng.to_device(image[None]), eng.to_device(np.ascontiguousarray(m, np.uint8)[None]),
@@ -718,64 +718,14 @@ class _Hints:
 
 def _full_args(full_bgr, bgr_shape, radius, eps) -> "Optional[tuple[int, float]]":
     """(radius, eps) of the upsample when a full-resolution batch is given (shape and arguments checked here, before any
-    stage runs), else None."""
+    stage runs), else None.  full_bgr: the batch or its shape; True when only its presence is known yet."""
     if full_bgr is None:
         return None
     from ._engine import check_matte_args, check_upsample_shapes
-    check_upsample_shapes(tuple(bgr_shape), tuple(bgr_shape[:3]), tuple(full_bgr.shape), "full_bgr")
+    if full_bgr is not True:
+        check_upsample_shapes(tuple(bgr_shape), tuple(bgr_shape[:3]), tuple(getattr(full_bgr, "shape", full_bgr)), "full_bgr")
     check_matte_args(radius, eps)
     return int(radius), float(eps)
-
-
-def _full_buffers(eng, full_bgr, compose: bool, mat) -> "Optional[dict]":
-    """The device outputs at full resolution: binary_mask, overlay and rgba (compose), alpha and rgba_soft (matte)."""
-    import torch
-    if full_bgr is None:
-        return None
-    shape = tuple(full_bgr.shape[:3])
-    out = {"binary_mask": eng.empty(*shape, dtype=torch.uint8)}
-    if compose:
-        out["overlay"], out["rgba"] = eng.empty(*shape, 3, dtype=torch.uint8), eng.empty(*shape, 4, dtype=torch.uint8)
-    if mat:
-        out["alpha"], out["rgba_soft"] = eng.empty(*shape), eng.empty(*shape, 4, dtype=torch.uint8)
-    return out
-
-
-def _full_post(leng, lo, hi, bgr, cleaned, full_bgr, full, fmat, cfm=None, cff=None, work_alpha=None, fcut=None) -> None:
-    """The full-resolution outputs of images lo:hi from their cleaned working masks: ggc_upsample_matte, then
-    ggc_compose_outputs on the full image and the upsampled mask.  With cff (ClosedFormMatte(full_resolution=True): its
-    grow and full_max_iter, next to cfm) the alpha comes from the full-size closed-form solve instead, warm from the
-    working-size alpha work_alpha on its lifted band, and the mask is that alpha >= 0.5 (closed_form_matte_full).  With
-    fcut (full_cut: band or None, n_iter, the batch's seed, colour space, min_area_ratio, keep_largest) the mask is
-    cut_mask_full of the cleaned mask, image b on seed + b; the alpha, if wanted, stays the guided upsample's."""
-    import torch
-    alpha, soft = full.get("alpha"), full.get("rgba_soft")
-    if fcut:
-        from ._engine import default_full_cut_band
-        band, n_iter, seed, cs, min_area_ratio, keep_largest = fcut
-        if band is None:
-            band = default_full_cut_band(cleaned.shape[1:], full_bgr.shape[1:3])
-        if alpha is not None:
-            leng.upsample_matte(bgr[lo:hi], cleaned[lo:hi], full_bgr[lo:hi], *fmat, out=(alpha[lo:hi], None, soft[lo:hi]))
-        leng.cut_mask_full(cleaned[lo:hi], full_bgr[lo:hi], band, n_iter, seed + lo, cs, min_area_ratio, keep_largest,
-                           out=full["binary_mask"][lo:hi], max_pixels=FULL_CUT_PIXELS)
-    elif cff:
-        radius, eps, band, _, tol = cfm
-        leng.closed_form_full(bgr[lo:hi], leng.closed_form_band(cleaned[lo:hi], band), work_alpha[lo:hi], full_bgr[lo:hi],
-                              radius, eps, cff[0], cff[1], tol, out=(alpha[lo:hi], soft[lo:hi]))
-        full["binary_mask"][lo:hi].copy_(torch.ge(alpha[lo:hi], 0.5))
-    else:
-        leng.upsample_matte(bgr[lo:hi], cleaned[lo:hi], full_bgr[lo:hi], *fmat,
-                            out=(None if alpha is None else alpha[lo:hi], full["binary_mask"][lo:hi],
-                                 None if soft is None else soft[lo:hi]))
-    if "overlay" in full:
-        leng.compose(full_bgr[lo:hi], full["binary_mask"][lo:hi], out=(full["overlay"][lo:hi], full["rgba"][lo:hi]))
-
-
-def _full_result(full: dict, i: int) -> FullResolution:
-    host = {k: v[i].cpu().numpy() for k, v in full.items()}
-    return FullResolution(binary_mask=host["binary_mask"], overlay=host.get("overlay"), rgba=host.get("rgba"),
-                          alpha=host.get("alpha"), rgba_soft=host.get("rgba_soft"))
 
 
 def _closed_form_args(matte, h: int, w: int, full: bool) -> "Optional[tuple[int, float, int, int, float]]":
@@ -825,14 +775,6 @@ def _foreground_args(foreground, matte, full: bool) -> "Optional[tuple[float, fl
     return args
 
 
-def _soft_matte(leng, img, cleaned, mat, cfm, alpha, rgba_soft) -> None:
-    """alpha and rgba_soft of the cleaned masks: the guided matte (mat) or the closed-form one (cfm)."""
-    if mat:
-        leng.alpha_matte(img, cleaned, *mat, want_rgba=True, out=(alpha, rgba_soft))
-    elif cfm:
-        leng.closed_form_matte(img, cleaned, *cfm, out=(alpha, rgba_soft))
-
-
 def _matte_args(matte: bool, radius, eps) -> "Optional[tuple[int, float]]":
     """(radius, eps) when the matte is wanted (checked here, before any stage runs), else None."""
     if not matte:
@@ -840,6 +782,157 @@ def _matte_args(matte: bool, radius, eps) -> "Optional[tuple[int, float]]":
     from ._engine import check_matte_args
     check_matte_args(radius, eps)
     return int(radius), float(eps)
+
+
+# the arguments of segment / segment_batch / segment_batch_device that _OutputPlan.of takes under their own names
+_PLAN_OPTIONS = ("compose", "min_area_ratio", "keep_largest", "matte", "matte_radius", "matte_eps", "foreground", "full_cut",
+                 "geodesic", "hint_region")
+
+
+@dataclass(frozen=True)
+class _OutputPlan:
+    """What one call asked for beyond the cleaned mask, checked: which optional outputs exist and the arguments of the
+    entries that fill them.  Built once per call by of(), the one place where an option is refused; _OutputStage runs it."""
+    compose: bool                                 # overlay and rgba, at the working size and on the full image
+    min_area_ratio: float                         # clean_mask's, also of the full cut
+    keep_largest: bool
+    mat: "Optional[tuple[int, float]]"            # guided matte: (radius, eps) ...
+    cfm: "Optional[tuple[int, float, int, int, float]]"   # ... or the closed-form one: (radius, eps, band, max_iter, tol)
+    cff: "Optional[tuple[int, int]]"              # its full-size solve: (grow, full_max_iter)
+    fmat: "Optional[tuple[int, float]]"           # the upsample's (radius, eps); set exactly when there is a full image
+    fga: "Optional[tuple[float, float, int, float]]"      # foreground colours: (eps_r, omega, max_iter, tol)
+    fcut: "Optional[tuple[Optional[int], int]]"   # full cut: (band or None for the default, n_iter), on seed and color_space
+    seed: int
+    color_space: str
+
+    @classmethod
+    def of(cls, pipe, shape, full, compose: bool = True, min_area_ratio: float = 0.002, keep_largest: bool = False,
+           matte=False, matte_radius=MATTE_RADIUS, matte_eps=MATTE_EPS, foreground=False, full_cut=False, geodesic=False,
+           hint_region: bool = False) -> "_OutputPlan":
+        """shape: (B,H,W,3) of the working batch; full: the (B,H1,W1,3) shape of the full images, None without them, or
+        True when they are given but not read yet (segment_batch refuses options before it looks at its list; the shape
+        checks are then left to the call that knows it).  A call that is wrong in several ways is refused for the first
+        of: hints, closed-form matte, guided matte, full image, foreground, full-size closed form, full cut.  pipe, whose
+        GrabCutConfig gives the seed and the colour space, is not touched before all of them had their chance."""
+        has_full, sized = full is not None, full is not None and full is not True
+        _geodesic_args(geodesic, hint_region)
+        cfm = _closed_form_args(matte, shape[1], shape[2], has_full)
+        mat = None if cfm else _matte_args(matte, matte_radius, matte_eps)
+        fmat = _full_args(full, shape, matte_radius, matte_eps)
+        fga = _foreground_args(foreground, matte, has_full)
+        cff = _closed_form_full_args(matte) if cfm else None
+        fcut = _full_cut_args(full_cut, has_full, matte, shape[1:3] if sized else None, full[1:3] if sized else None)
+        cs = pipe.gc_config.color_space.lower()
+        if cs not in ("rgb", "hsv", "lab"):
+            raise ValueError(f"unknown color_space '{cs}': rgb | hsv | lab")
+        return cls(bool(compose), min_area_ratio, keep_largest, mat, cfm, cff, fmat, fga, fcut, pipe.gc_config.seed, cs)
+
+
+class _OutputStage:
+    """Everything after GrabCut for one batch under one _OutputPlan.  It owns the output buffers; run() issues the work of
+    images lo:hi on whatever engine and stream the caller is on (a GrabCut lane, a chunk's lane, or the caller's own), so
+    the schedules differ only in who calls it and when.  final_mask: (B,H,W) uint8 masks that are final already
+    (segment_bbox: GrabCut's own, with its own overlay); they stand in for the cleaned masks, from_mask() is the entry,
+    and there is no working-size overlay."""
+
+    def __init__(self, eng, plan: _OutputPlan, bgr, full_bgr=None, final_mask=None):
+        import torch
+        self.plan, self.bgr, self.full_bgr = plan, bgr, full_bgr
+
+        def u8(shape, *channels):
+            return eng.empty(*shape, *channels, dtype=torch.uint8)
+
+        def buffers(shape, compose, matte) -> dict:
+            out = {}
+            if compose:
+                out["overlay"], out["rgba"] = u8(shape, 3), u8(shape, 4)
+            if matte:
+                out["alpha"], out["rgba_soft"] = eng.empty(*shape), u8(shape, 4)
+            return out
+
+        shape = tuple(bgr.shape[:3])
+        self.cleaned = u8(shape) if final_mask is None else final_mask
+        # the optional entries of segment_batch_device's dict, in its order
+        self.out = buffers(shape, plan.compose and final_mask is None, plan.mat or plan.cfm)
+        if plan.fga:
+            self.out["foreground"], self.out["rgba_clean"] = u8(shape, 3), u8(shape, 4)
+        if full_bgr is not None:
+            full_shape = tuple(full_bgr.shape[:3])
+            self.out["full"] = {"binary_mask": u8(full_shape), **buffers(full_shape, plan.compose, plan.mat or plan.cff)}
+
+    def run(self, leng, lo: int, hi: int, binary_part) -> None:
+        """Images lo:hi from GrabCut's binary masks binary_part: ggc_clean_mask, ggc_compose_outputs, then from_mask."""
+        p, o = self.plan, self.out
+        leng.clean_mask(binary_part, p.min_area_ratio, p.keep_largest, out=self.cleaned[lo:hi])
+        if p.compose:
+            leng.compose(self.bgr[lo:hi], self.cleaned[lo:hi], out=(o["overlay"][lo:hi], o["rgba"][lo:hi]))
+        self.from_mask(leng, lo, hi)
+
+    def from_mask(self, leng, lo: int, hi: int) -> None:
+        """What follows the final masks of images lo:hi.  alpha and rgba_soft: the guided matte (mat) or the closed-form one
+        (cfm); the foreground colours under that alpha (fga).  With a full image, its outputs: ggc_upsample_matte, then
+        ggc_compose_outputs on the full image and the upsampled mask.  With cff (ClosedFormMatte(full_resolution=True))
+        the alpha comes from the full-size closed-form solve instead, warm from the working-size alpha on its lifted
+        band, and the mask is that alpha >= 0.5 (closed_form_matte_full).  With fcut (full_cut) the mask is
+        cut_mask_full of the final mask, image b on seed + b; the alpha, if wanted, stays the guided upsample's."""
+        import torch
+        p, o = self.plan, self.out
+        img, cleaned = self.bgr[lo:hi], self.cleaned[lo:hi]
+        if p.mat:
+            leng.alpha_matte(img, cleaned, *p.mat, want_rgba=True, out=(o["alpha"][lo:hi], o["rgba_soft"][lo:hi]))
+        elif p.cfm:
+            leng.closed_form_matte(img, cleaned, *p.cfm, out=(o["alpha"][lo:hi], o["rgba_soft"][lo:hi]))
+        if p.fga:
+            leng.estimate_foreground(img, o["alpha"][lo:hi], *p.fga, out=(o["foreground"][lo:hi], o["rgba_clean"][lo:hi]))
+        if "full" not in o:
+            return
+        full, big = o["full"], self.full_bgr[lo:hi]
+        mask = full["binary_mask"][lo:hi]
+        alpha, soft = (full[k][lo:hi] if k in full else None for k in ("alpha", "rgba_soft"))
+        if p.fcut:
+            from ._engine import default_full_cut_band
+            band, n_iter = p.fcut
+            if band is None:
+                band = default_full_cut_band(cleaned.shape[1:], big.shape[1:3])
+            if alpha is not None:
+                leng.upsample_matte(img, cleaned, big, *p.fmat, out=(alpha, None, soft))
+            leng.cut_mask_full(cleaned, big, band, n_iter, p.seed + lo, p.color_space, p.min_area_ratio, p.keep_largest,
+                               out=mask, max_pixels=FULL_CUT_PIXELS)
+        elif p.cff:
+            radius, eps, band, _, tol = p.cfm
+            leng.closed_form_full(img, leng.closed_form_band(cleaned, band), o["alpha"][lo:hi], big, radius, eps, *p.cff, tol,
+                                  out=(alpha, soft))
+            mask.copy_(torch.ge(alpha, 0.5))
+        else:
+            leng.upsample_matte(img, cleaned, big, *p.fmat, out=(alpha, mask, soft))
+        if p.compose:
+            leng.compose(big, mask, out=(full["overlay"][lo:hi], full["rgba"][lo:hi]))
+
+    def result(self, trimap, segments, graphs, probs, gc_mask, state: "Optional[dict]" = None) -> dict:
+        """segment_batch_device's dict: the front stages' tensors, GrabCut's state when it was asked for, this stage's outputs."""
+        return {"binary_mask": self.cleaned, "trimap": trimap, "segments": segments, "graphs": graphs, "probs": probs,
+                "gc_mask": gc_mask, **(state or {}), **self.out}
+
+
+_REFERENCE_FIELDS = ("binary_mask", "trimap", "segments", "overlay", "rgba")     # of SegmentationResult, as keys of the dict
+_ADDITIVE_FIELDS = ("alpha", "rgba_soft", "foreground", "rgba_clean")
+
+
+def _optional_results(out: dict, i: int) -> dict:
+    """The additive fields of image i's SegmentationResult that the device dict `out` holds."""
+    res = {k: out[k][i].cpu().numpy() for k in _ADDITIVE_FIELDS if k in out}
+    if "full" in out:
+        host = {k: v[i].cpu().numpy() for k, v in out["full"].items()}
+        res["full"] = FullResolution(binary_mask=host["binary_mask"], overlay=host.get("overlay"), rgba=host.get("rgba"),
+                                     alpha=host.get("alpha"), rgba_soft=host.get("rgba_soft"))
+    return res
+
+
+def _result(out: dict, i: int, image: np.ndarray, timing: dict) -> SegmentationResult:
+    """Image i of segment_batch_device's dict as a SegmentationResult on the host."""
+    return SegmentationResult(image=image, timing=timing, **_optional_results(out, i),
+                              **{k: out[k][i].cpu().numpy() if k in out else None
+                                 for k in _REFERENCE_FIELDS})
 
 
 class GCNGrabCutPipeline:
@@ -1049,29 +1142,20 @@ class GCNGrabCutPipeline:
         lane of its own (private context, stream and host thread).  Images are independent and image b keeps seed + b, so
         every output equals the one-chunk run bit for bit."""
         import torch
-        eng, cfg = self._eng, self.sp_config
-        cs = self.gc_config.color_space.lower()
-        if cs not in ("rgb", "hsv", "lab"):
-            raise ValueError(f"unknown color_space '{cs}': rgb | hsv | lab")
+        eng = self._eng
         b = bgr.size(0)
         want = self.grabcut_lanes if grabcut_lanes is None else int(grabcut_lanes)   # (an argument, so that concurrent callers do not mutate the pipeline)
         n_chunks = self.chunks if chunks is None else int(chunks)
         hints = _Hints.of(hints, b, hint_radius, hint_region, hints_as_prior, geodesic)
-        cfm = _closed_form_args(matte, bgr.shape[1], bgr.shape[2], full_bgr is not None)
-        mat = None if cfm else _matte_args(matte, matte_radius, matte_eps)
-        fmat = _full_args(full_bgr, bgr.shape, matte_radius, matte_eps)
-        fga = _foreground_args(foreground, matte, full_bgr is not None)
-        cff = _closed_form_full_args(matte) if cfm else None
-        fcut = _full_cut_args(full_cut, full_bgr is not None, matte, bgr.shape[1:3],
-                              None if full_bgr is None else full_bgr.shape[1:3])
-        if fcut:
-            fcut = (*fcut, self.gc_config.seed, cs, min_area_ratio, keep_largest)
+        plan = _OutputPlan.of(self, bgr.shape, None if full_bgr is None else full_bgr.shape, compose=compose,
+                              min_area_ratio=min_area_ratio, keep_largest=keep_largest, matte=matte, matte_radius=matte_radius,
+                              matte_eps=matte_eps, foreground=foreground, full_cut=full_cut)
+        cs = plan.color_space
         if n_chunks <= 0:                          # 0: one chunk per GrabCut lane once every chunk gets a lane's worth of images
             n_chunks = max(want, 1) if b >= 16 * max(want, 1) else 1
         if n_chunks > 1 and b >= 2 * n_chunks:
-            return self._segment_pipelined(bgr, self.chunk_plan(b, n_chunks, self.chunk_ratio), cs, threshold_fg, threshold_bg,
-                                           refine_iters, min_area_ratio, keep_largest, edge_aware, filter_radius, compose, timing,
-                                           hints, return_state, mat, full_bgr, fmat, cfm, fga, cff, fcut)
+            return self._segment_pipelined(bgr, full_bgr, self.chunk_plan(b, n_chunks, self.chunk_ratio), plan, threshold_fg,
+                                           threshold_bg, refine_iters, edge_aware, filter_radius, timing, hints, return_state)
 
         def tick():
             if timing is not None:
@@ -1083,70 +1167,47 @@ class GCNGrabCutPipeline:
 
         t = tick()
         mask = trimap.clone()
-        lanes = want if b >= 8 * max(want, 1) else 1
+        lanes = self._lane_count(b, want)
         gc_img = bgr if cs == "rgb" else eng.convert_color8(bgr, cs)      # reference grabcut.py:73-79
-        # clean-up and composition are per image: without stage timing each GrabCut lane runs them for its own sub-batch as
-        # soon as it is cut (on its stream, under the other lanes' tails); with timing they stay a stage of their own
-        cleaned = eng.empty(*bgr.shape[:3], dtype=torch.uint8)
-        overlay = eng.empty(*bgr.shape[:3], 3, dtype=torch.uint8) if compose else None
-        rgba = eng.empty(*bgr.shape[:3], 4, dtype=torch.uint8) if compose else None
-        alpha = eng.empty(*bgr.shape[:3]) if (mat or cfm) else None
-        rgba_soft = eng.empty(*bgr.shape[:3], 4, dtype=torch.uint8) if (mat or cfm) else None
-        full = _full_buffers(eng, full_bgr, compose, mat or cff)
-        fg_col = eng.empty(*bgr.shape[:3], 3, dtype=torch.uint8) if fga else None
-        rgba_clean = eng.empty(*bgr.shape[:3], 4, dtype=torch.uint8) if fga else None
-
-        def post(leng, lo, hi, binary_part):
-            leng.clean_mask(binary_part, min_area_ratio, keep_largest, out=cleaned[lo:hi])
-            if compose:
-                leng.compose(bgr[lo:hi], cleaned[lo:hi], out=(overlay[lo:hi], rgba[lo:hi]))
-            if mat or cfm:
-                _soft_matte(leng, bgr[lo:hi], cleaned[lo:hi], mat, cfm, alpha[lo:hi], rgba_soft[lo:hi])
-            if fga:
-                leng.estimate_foreground(bgr[lo:hi], alpha[lo:hi], *fga, out=(fg_col[lo:hi], rgba_clean[lo:hi]))
-            if full is not None:
-                _full_post(leng, lo, hi, bgr, cleaned, full_bgr, full, fmat, cfm, cff, alpha, fcut)
-
+        # the output stage is per image: without stage timing each GrabCut lane runs it for its own sub-batch as soon as
+        # it is cut (on its stream, under the other lanes' tails); with timing it stays a stage of its own
+        stage = _OutputStage(eng, plan, bgr, full_bgr)
         fused_post = timing is None
         binary, mask, bgd, fgd = eng.grabcut_lanes(gc_img, mask, self.gc_config.n_iter, 0, self.gc_config.seed, lanes,
-                                                   post=post if (fused_post and refine_iters <= 0) else None)
+                                                   post=stage.run if (fused_post and refine_iters <= 0) else None)
         if refine_iters > 0:
             binary, mask, bgd, fgd = eng.grabcut_lanes(gc_img, mask, refine_iters, 2, self.gc_config.seed, lanes, bgd, fgd,
-                                                       post=post if fused_post else None)
+                                                       post=stage.run if fused_post else None)
         if timing is not None:
             timing["grabcut"] = tick() - t
 
         t = tick()
         if not fused_post:
-            post(eng, 0, bgr.size(0), binary)
-        out = {"binary_mask": cleaned, "trimap": trimap, "segments": seg, "graphs": graphs, "probs": probs,
-               "gc_mask": mask}
-        if return_state:
-            out.update(gc_binary=binary, bgd=bgd, fgd=fgd, gc_image=gc_img)
-        if compose:
-            out["overlay"], out["rgba"] = overlay, rgba
-        if mat or cfm:
-            out["alpha"], out["rgba_soft"] = alpha, rgba_soft
-        if fga:
-            out["foreground"], out["rgba_clean"] = fg_col, rgba_clean
-        if full is not None:
-            out["full"] = full
+            stage.run(eng, 0, b, binary)
+        out = stage.result(trimap, seg, graphs, probs, mask,
+                           dict(gc_binary=binary, bgd=bgd, fgd=fgd, gc_image=gc_img) if return_state else None)
         if timing is not None:
             timing["postprocess"] = tick() - t
         return out
 
-    def _segment_pipelined(self, bgr, plan, cs, threshold_fg, threshold_bg, refine_iters, min_area_ratio, keep_largest,
-                           edge_aware, filter_radius, compose, timing, hints=None, return_state=False, mat=None,
-                           full_bgr=None, fmat=None, cfm=None, fga=None, cff=None, fcut=None) -> dict:
+    def _lane_count(self, b: int, want: Optional[int] = None) -> int:
+        """The GrabCut lanes a batch of b images runs on: the wanted number once every lane gets eight images, else one."""
+        want = max(self.grabcut_lanes if want is None else want, 1)
+        return want if b >= 8 * want else 1
+
+    def _segment_pipelined(self, bgr, full_bgr, chunks, plan, threshold_fg, threshold_bg, refine_iters, edge_aware,
+                           filter_radius, timing, hints=None, return_state=False) -> dict:
         """The software pipeline behind segment_batch_device: chunk k's GrabCut lane starts as soon as chunk k's trimaps are
-        on the device; the caller's stream goes on with chunk k+1's SLIC / graph / network / trimap."""
+        on the device; the caller's stream goes on with chunk k+1's SLIC / graph / network / trimap.  plan: the call's
+        _OutputPlan; each lane runs the output stage for its chunk."""
         import torch
         from concurrent.futures import ThreadPoolExecutor
         from ._engine import merge_graphs
         eng = self._eng
         dev = eng.device
         b, h, w, _ = bgr.shape
-        n = len(plan)
+        n = len(chunks)
+        cs = plan.color_space
         caller = torch.cuda.current_stream(dev)
         lanes = eng.lanes(n)
         if getattr(self, "_chunk_pool", None) is None or self._chunk_pool._max_workers != n:
@@ -1156,19 +1217,12 @@ class GCNGrabCutPipeline:
         seg = eng.empty(b, h, w, dtype=torch.int32)
         trimap = eng.empty(b, h, w, dtype=torch.uint8)
         mask = eng.empty(b, h, w, dtype=torch.uint8)
-        cleaned = eng.empty(b, h, w, dtype=torch.uint8)
-        overlay = eng.empty(b, h, w, 3, dtype=torch.uint8) if compose else None
-        rgba = eng.empty(b, h, w, 4, dtype=torch.uint8) if compose else None
-        alpha = eng.empty(b, h, w) if (mat or cfm) else None
-        rgba_soft = eng.empty(b, h, w, 4, dtype=torch.uint8) if (mat or cfm) else None
-        full = _full_buffers(eng, full_bgr, compose, mat or cff)
-        fg_col = eng.empty(b, h, w, 3, dtype=torch.uint8) if fga else None
-        rgba_clean = eng.empty(b, h, w, 4, dtype=torch.uint8) if fga else None
+        stage = _OutputStage(eng, plan, bgr, full_bgr)
+        state = None
         if return_state:
-            st_binary = eng.empty(b, h, w, dtype=torch.uint8)
-            st_bgd = eng.empty(b, 65, dtype=torch.float64)
-            st_fgd = eng.empty(b, 65, dtype=torch.float64)
-            st_image = bgr if cs == "rgb" else eng.empty(b, h, w, 3, dtype=torch.uint8)
+            state = dict(gc_binary=eng.empty(b, h, w, dtype=torch.uint8), bgd=eng.empty(b, 65, dtype=torch.float64),
+                         fgd=eng.empty(b, 65, dtype=torch.float64),
+                         gc_image=bgr if cs == "rgb" else eng.empty(b, h, w, 3, dtype=torch.uint8))
         n_iter, seed = self.gc_config.n_iter, self.gc_config.seed
         t_host = time.perf_counter()
         stamps = []                                   # per chunk: events around its front stages / its lane's work
@@ -1187,22 +1241,14 @@ class GCNGrabCutPipeline:
                 if refine_iters > 0:
                     binary, _, bgd, fgd = leng.grabcut(gc_img, m, refine_iters, 2, None, seed + lo, bgd, fgd)
                 if return_state:
-                    st_binary[lo:hi].copy_(binary)
-                    st_bgd[lo:hi].copy_(bgd)
-                    st_fgd[lo:hi].copy_(fgd)
+                    state["gc_binary"][lo:hi].copy_(binary)
+                    state["bgd"][lo:hi].copy_(bgd)
+                    state["fgd"][lo:hi].copy_(fgd)
                     if cs != "rgb":
-                        st_image[lo:hi].copy_(gc_img)
+                        state["gc_image"][lo:hi].copy_(gc_img)
                 if ev is not None:
                     ev[1].record(stream)
-                leng.clean_mask(binary, min_area_ratio, keep_largest, out=cleaned[lo:hi])
-                if compose:
-                    leng.compose(img, cleaned[lo:hi], out=(overlay[lo:hi], rgba[lo:hi]))
-                if mat or cfm:
-                    _soft_matte(leng, img, cleaned[lo:hi], mat, cfm, alpha[lo:hi], rgba_soft[lo:hi])
-                if fga:
-                    leng.estimate_foreground(img, alpha[lo:hi], *fga, out=(fg_col[lo:hi], rgba_clean[lo:hi]))
-                if full is not None:
-                    _full_post(leng, lo, hi, bgr, cleaned, full_bgr, full, fmat, cfm, cff, alpha, fcut)
+                stage.run(leng, lo, hi, binary)
                 if ev is not None:
                     ev[2].record(stream)
                 done = torch.cuda.Event()
@@ -1210,7 +1256,7 @@ class GCNGrabCutPipeline:
             return done
 
         futures, parts = [], []
-        for k, (lo, hi) in enumerate(plan):
+        for k, (lo, hi) in enumerate(chunks):
             ev = [torch.cuda.Event(enable_timing=True) for _ in range(5)] if timing is not None else None
             if ev is not None:
                 ev[3].record(caller)
@@ -1230,17 +1276,7 @@ class GCNGrabCutPipeline:
         probs = torch.cat([p for _, p in parts])
         for f in futures:
             caller.wait_event(f.result())             # whatever the caller enqueues next sees the lanes' outputs
-        out = {"binary_mask": cleaned, "trimap": trimap, "segments": seg, "graphs": graphs, "probs": probs, "gc_mask": mask}
-        if return_state:
-            out.update(gc_binary=st_binary, bgd=st_bgd, fgd=st_fgd, gc_image=st_image)
-        if compose:
-            out["overlay"], out["rgba"] = overlay, rgba
-        if mat or cfm:
-            out["alpha"], out["rgba_soft"] = alpha, rgba_soft
-        if fga:
-            out["foreground"], out["rgba_clean"] = fg_col, rgba_clean
-        if full is not None:
-            out["full"] = full
+        out = stage.result(trimap, seg, graphs, probs, mask, state)
         if timing is not None:                        # stage times from stream events (the stages overlap: they add up to more than the wall time)
             torch.cuda.synchronize(dev)
             front = sum(e[3].elapsed_time(e[4]) for e in stamps) / 1e3
@@ -1262,10 +1298,8 @@ class GCNGrabCutPipeline:
             return []
         if any(im.shape != imgs[0].shape for im in imgs):
             raise ValueError("segment_batch needs images of one size; group them by shape")
-        _closed_form_args(kwargs.get("matte"), *imgs[0].shape[:2], full_images is not None)
-        _foreground_args(kwargs.get("foreground"), kwargs.get("matte"), full_images is not None)
-        _full_cut_args(kwargs.get("full_cut"), full_images is not None, kwargs.get("matte"))
-        _geodesic_args(kwargs.get("geodesic"), kwargs.get("hint_region", False))
+        _OutputPlan.of(self, (len(imgs), *imgs[0].shape), None if full_images is None else True,   # options before the list
+                       **{k: kwargs[k] for k in _PLAN_OPTIONS if k in kwargs})
         full_bgr = None
         if full_images is not None:
             fulls = [_check_image(im) for im in full_images]
@@ -1280,31 +1314,18 @@ class GCNGrabCutPipeline:
         timing: dict[str, float] = {}
         bgr = self._eng.to_device(np.stack(imgs))
         out = self.segment_batch_device(bgr, timing=timing, hints=hints, full_bgr=full_bgr, **kwargs)
-        host = {k: out[k].cpu().numpy() for k in ("binary_mask", "trimap", "segments", "overlay", "rgba", "alpha", "rgba_soft",
-                                                     "foreground", "rgba_clean")
-                if k in out}
+        out.update({k: out[k].cpu() for k in _REFERENCE_FIELDS + _ADDITIVE_FIELDS if k in out})      # one copy per output, not one per image
         per_image = {k: v / len(imgs) for k, v in timing.items()}
-        return [SegmentationResult(image=imgs[i], binary_mask=host["binary_mask"][i], trimap=host["trimap"][i],
-                                   segments=host["segments"][i], overlay=host["overlay"][i], rgba=host["rgba"][i],
-                                   timing=dict(per_image), alpha=host["alpha"][i] if "alpha" in host else None,
-                                   rgba_soft=host["rgba_soft"][i] if "rgba_soft" in host else None,
-                                   full=_full_result(out["full"], i) if "full" in out else None,
-                                   foreground=host["foreground"][i] if "foreground" in host else None,
-                                   rgba_clean=host["rgba_clean"][i] if "rgba_clean" in host else None)
-                for i in range(len(imgs))]
+        return [_result(out, i, imgs[i], dict(per_image)) for i in range(len(imgs))]
 
     def _click_round(self, binary, gt, mask, image, bgd, fgd, hint_ptr, hint_radius=5, n_iter=1):
         """One round of the NoC protocol on a device-resident batch: the next click per image on GrabCut's binary mask,
         painted into the mask as one hint per image (hint_ptr = arange(B+1); an image without a click has row -1, which
         ggc_apply_hints ignores), GC_EVAL for n_iter iterations from the kept models, IoU.
         -> (click (B,4) int32, binary, mask, bgd, fgd, iou (B,) float64), all on the device."""
-        eng = self._eng
-        click = eng.next_click(binary, gt)
-        eng.apply_hints(mask, click[:, :3].contiguous(), hint_ptr, hint_radius)
-        b, want = binary.size(0), max(self.grabcut_lanes, 1)
-        lanes = want if b >= 8 * want else 1
-        binary, mask, bgd, fgd = eng.grabcut_lanes(image, mask, n_iter, 2, self.gc_config.seed, lanes, bgd, fgd)
-        return (click, binary, mask, bgd, fgd, eng.iou(binary, gt)[0])
+        click = self._eng.next_click(binary, gt)
+        self._eng.apply_hints(mask, click[:, :3].contiguous(), hint_ptr, hint_radius)
+        return self._click_cut(click, binary, gt, mask, image, bgd, fgd, n_iter)
 
     def _click_round_geodesic(self, binary, gt, mask, image, bgd, fgd, bgr, clicks_dev, idx_dev, k, hint_ptr, geodesic, n_iter=1):
         """_click_round with geodesic hints: the new click is recorded first, then ALL k clicks made so far on each image
@@ -1315,9 +1336,13 @@ class GCNGrabCutPipeline:
         clicks_dev[idx_dev, k - 1] = click
         rows = clicks_dev[idx_dev, :k, :3].reshape(-1, 3).contiguous()
         eng.geodesic_hints(bgr, rows, hint_ptr, geodesic.radius, geodesic.gamma, mask=mask)
-        b, want = binary.size(0), max(self.grabcut_lanes, 1)
-        lanes = want if b >= 8 * want else 1
-        binary, mask, bgd, fgd = eng.grabcut_lanes(image, mask, n_iter, 2, self.gc_config.seed, lanes, bgd, fgd)
+        return self._click_cut(click, binary, gt, mask, image, bgd, fgd, n_iter)
+
+    def _click_cut(self, click, binary, gt, mask, image, bgd, fgd, n_iter):
+        """The end of a click round: GC_EVAL for n_iter iterations from the kept models on the painted mask, then IoU."""
+        eng = self._eng
+        binary, mask, bgd, fgd = eng.grabcut_lanes(image, mask, n_iter, 2, self.gc_config.seed, self._lane_count(binary.size(0)),
+                                                   bgd, fgd)
         return (click, binary, mask, bgd, fgd, eng.iou(binary, gt)[0])
 
     def evaluate_clicks(self, images: Sequence[np.ndarray], gt_masks: Sequence[np.ndarray], max_clicks: int = 20,
@@ -1438,11 +1463,11 @@ class GCNGrabCutPipeline:
         cut_mask_full of the cleaned mask (segment_batch_device); geodesic=True | GeodesicHints(...) paints the clicks by
         their geodesic distance on the image instead of disks (hint_radius is then ignored; segment_batch_device)."""
         image = _check_image(image)
-        _geodesic_args(geodesic, hint_region)
-        _closed_form_args(matte, *image.shape[:2], full_image is not None)
-        _foreground_args(foreground, matte, full_image is not None)
-        _full_cut_args(full_cut, full_image is not None, matte)
-        full_bgr = None if full_image is None else self._eng.to_device(_check_image(full_image)[None])
+        full = None if full_image is None else _check_image(full_image)
+        _OutputPlan.of(self, (1, *image.shape), None if full is None else (1, *full.shape), min_area_ratio=min_area_ratio,
+                       keep_largest=keep_largest, matte=matte, matte_radius=matte_radius, matte_eps=matte_eps,
+                       foreground=foreground, full_cut=full_cut, geodesic=geodesic, hint_region=hint_region)
+        full_bgr = None if full is None else self._eng.to_device(full[None])
         timing: dict[str, float] = {}
         hints = None if fg_points is None and bg_points is None else \
             [(() if fg_points is None else fg_points, () if bg_points is None else bg_points)]
@@ -1452,15 +1477,7 @@ class GCNGrabCutPipeline:
                                         hints_as_prior=hints_as_prior, matte=matte, matte_radius=matte_radius,
                                         matte_eps=matte_eps, full_bgr=full_bgr, foreground=foreground, full_cut=full_cut,
                                         geodesic=geodesic)
-        return SegmentationResult(
-            image=image, binary_mask=out["binary_mask"][0].cpu().numpy(), trimap=out["trimap"][0].cpu().numpy(),
-            segments=out["segments"][0].cpu().numpy(), overlay=out["overlay"][0].cpu().numpy(),
-            rgba=out["rgba"][0].cpu().numpy(), timing=timing,
-            alpha=out["alpha"][0].cpu().numpy() if matte else None,
-            rgba_soft=out["rgba_soft"][0].cpu().numpy() if matte else None,
-            full=_full_result(out["full"], 0) if "full" in out else None,
-            foreground=out["foreground"][0].cpu().numpy() if "foreground" in out else None,
-            rgba_clean=out["rgba_clean"][0].cpu().numpy() if "rgba_clean" in out else None)
+        return _result(out, 0, image, timing)
 
     def segment_bbox(self, image: np.ndarray, bbox: tuple[int, int, int, int], matte: bool = False,
                      matte_radius: int = MATTE_RADIUS, matte_eps: float = MATTE_EPS,
@@ -1474,20 +1491,9 @@ class GCNGrabCutPipeline:
         full_cut=True | FullCut(...), with full_image, makes the full binary_mask cut_mask_full of the returned mask
         (GrabCutConfig's colour space and seed, clean_mask's defaults)."""
         image = _check_image(image)
-        cfm = _closed_form_args(matte, *image.shape[:2], full_image is not None)
-        fga = _foreground_args(foreground, matte, full_image is not None)
-        fcut = _full_cut_args(full_cut, full_image is not None, matte, image.shape[:2],
-                              None if full_image is None else np.shape(full_image)[:2])
-        if fcut:
-            cs = self.gc_config.color_space.lower()
-            if cs not in ("rgb", "hsv", "lab"):
-                raise ValueError(f"unknown color_space '{cs}': rgb | hsv | lab")
-            fcut = (*fcut, self.gc_config.seed, cs, 0.002, False)
-        mat = None if cfm else _matte_args(matte, matte_radius, matte_eps)
-        full_img = None
-        if full_image is not None:
-            full_img = _check_image(full_image)
-            fmat = _full_args(full_img[None], (1, *image.shape), matte_radius, matte_eps)
+        full = None if full_image is None else _check_image(full_image)
+        plan = _OutputPlan.of(self, (1, *image.shape), None if full is None else (1, *full.shape), matte=matte,
+                              matte_radius=matte_radius, matte_eps=matte_eps, foreground=foreground, full_cut=full_cut)
         gc = GrabCut(image, self.gc_config, device=self.device)
         binary_mask = gc.run_with_bbox(bbox)
         x, y, w, h = bbox
@@ -1497,34 +1503,13 @@ class GCNGrabCutPipeline:
         y0, y1, x0, x1 = eroded_box(H, W, bbox)
         if y1 > y0 and x1 > x0:
             trimap[y0:y1, x0:x1] = Label.FG_DEFINITE
-        alpha = rgba_soft = fg_col = rgba_clean = None
-        if mat:
+        extra = {}
+        if plan.mat or plan.cfm or full is not None:   # GrabCut's mask is final: no clean-up, and the overlay is GrabCut's own
             eng = self._eng
-            alpha, rgba_soft = eng.alpha_matte(eng.to_device(image[None]), eng.to_device(binary_mask[None]), *mat,
-                                               want_rgba=True)
-            if fga:
-                fg_col, rgba_clean, _, _ = eng.estimate_foreground(eng.to_device(image[None]), alpha, *fga, want_rgba=True)
-            alpha, rgba_soft = alpha[0].cpu().numpy(), rgba_soft[0].cpu().numpy()
-        elif cfm:
-            eng = self._eng
-            alpha, rgba_soft, _, _ = eng.closed_form_matte(eng.to_device(image[None]),
-                                                           eng.to_device(np.ascontiguousarray(binary_mask, np.uint8)[None]),
-                                                           *cfm, want_rgba=True)
-            if fga:
-                fg_col, rgba_clean, _, _ = eng.estimate_foreground(eng.to_device(image[None]), alpha, *fga, want_rgba=True)
-            alpha, rgba_soft = alpha[0].cpu().numpy(), rgba_soft[0].cpu().numpy()
-        full = None
-        if full_img is not None:
-            eng = self._eng
-            full_bgr = eng.to_device(full_img[None])
-            cff = _closed_form_full_args(matte) if cfm else None
-            bufs = _full_buffers(eng, full_bgr, True, mat or cff)
-            _full_post(eng, 0, 1, eng.to_device(image[None]), eng.to_device(np.ascontiguousarray(binary_mask, np.uint8)[None]),
-                       full_bgr, bufs, fmat, cfm, cff,
-                       None if not cff else eng.to_device(np.ascontiguousarray(alpha, np.float32)[None]), fcut)
-            full = _full_result(bufs, 0)
+            stage = _OutputStage(eng, plan, eng.to_device(image[None]), None if full is None else eng.to_device(full[None]),
+                                 final_mask=eng.to_device(np.ascontiguousarray(binary_mask, np.uint8)[None]))
+            stage.from_mask(eng, 0, 1)
+            extra = _optional_results(stage.out, 0)
         return SegmentationResult(image=image, binary_mask=binary_mask, trimap=trimap,
                                   segments=np.zeros((H, W), dtype=np.int32), overlay=gc.overlay_mask(),
-                                  rgba=gc.crop_foreground(), alpha=alpha, rgba_soft=rgba_soft, full=full,
-                                  foreground=None if fg_col is None else fg_col[0].cpu().numpy(),
-                                  rgba_clean=None if rgba_clean is None else rgba_clean[0].cpu().numpy())
+                                  rgba=gc.crop_foreground(), **extra)

@@ -319,6 +319,41 @@ def test_software_pipeline_gives_the_one_chunk_outputs(oracle, gpu_ctx):
             assert {"graph_build", "grabcut", "postprocess", "wall"} <= set(timing) and timing["grabcut"] > 0
 
 
+@pytest.mark.parametrize("case", ["matte_full_cut_hints", "closed_form_full", "matte_foreground_state"])
+def test_output_stage_is_the_same_in_every_schedule(gpu_ctx, case):
+    """The one post-GrabCut stage under its three callers: one GrabCut lane with the stage fused into it, two lanes with
+    stage timing (the stage runs on its own after GrabCut), and two chunks of the software pipeline.  Batch 16 is the
+    smallest at which two lanes engage (b >= 8 lanes) and allows two chunks.  Every tensor of the result, and of its
+    "full", is the same bit for bit.  (The per-feature tests pin the first schedule against the stand-alone functions.)"""
+    from gcn_grabcut import ClosedFormMatte, GCNGrabCutPipeline, SuperpixelGraphConfig
+    from gcn_grabcut.synthetic import synthetic_batch
+    model, _ = seeded_state_dict(64, 3, seed=2)
+    pipe = GCNGrabCutPipeline(model.eval(), sp_config=SuperpixelGraphConfig(n_segments=120), device="cuda:0")
+    full_bgr = torch.from_numpy(synthetic_batch(16, 192, 256, config_id=5)).cuda()
+    bgr = full_bgr[:, ::2, ::2].contiguous()                                        # (16, 96, 128, 3)
+    clicks = [None] * 16
+    clicks[3], clicks[12] = ([(40, 60)], [(5, 5)]), ([(50, 30), (60, 90)], [])      # one in each chunk and lane
+    options = {"matte_full_cut_hints": dict(matte=True, full_bgr=full_bgr, full_cut=True, hints=clicks),
+               "closed_form_full": dict(matte=ClosedFormMatte(full_resolution=True), full_bgr=full_bgr),
+               "matte_foreground_state": dict(matte=True, foreground=True, return_state=True)}[case]
+
+    def tensors(out):
+        flat = {k: v for k, v in out.items() if torch.is_tensor(v)}
+        flat.update({f"full.{k}": v for k, v in out.get("full", {}).items()})
+        flat.update({f"graphs.{k}": v for k, v in vars(out["graphs"]).items() if torch.is_tensor(v)})
+        return flat
+
+    ref = tensors(pipe.segment_batch_device(bgr, chunks=1, grabcut_lanes=1, **options))
+    assert {"binary_mask", "alpha", "rgba_soft", "overlay", "rgba", "graphs.x"} <= set(ref)
+    assert ("full.binary_mask" in ref) == ("full_bgr" in options) and ("rgba_clean" in ref) == ("foreground" in options)
+    assert ("gc_binary" in ref) == ("return_state" in options)
+    for schedule in (dict(chunks=1, grabcut_lanes=2, timing={}), dict(chunks=2, grabcut_lanes=2)):
+        got = tensors(pipe.segment_batch_device(bgr, **schedule, **options))
+        assert set(got) == set(ref)
+        for k in ref:
+            assert torch.equal(got[k], ref[k]), (case, schedule["chunks"], k)
+
+
 def test_use_lab_false_runs_the_float64_slic_end_to_end(oracle, gpu_ctx):
     """SuperpixelGraphConfig(use_lab=False) (reference graph_builder.py:177-179): GraphBuilder, the pipeline and the graph-cache
     writer take skimage's float64 SLIC on the RGB image; everything downstream is unchanged.  Label map, trimap and mask equal
