@@ -35,6 +35,7 @@ enum Slot : int {
     S_MATTE_EVAL,
     S_FULLCUT,
     S_GEODESIC,
+    S_STROKES,
     S_COUNT
 };
 

@@ -236,6 +236,34 @@ class Engine:
                       _native.ptr(dist_fg), _native.ptr(dist_bg), _native.ptr(node_dist))
         return mask
 
+    # ------------------------------------------------------------------ H2
+    def upload_strokes(self, strokes: np.ndarray, stroke_ptr: np.ndarray):
+        """pack_strokes' (strokes [S,5], stroke_ptr [B+1]) -> the same two arrays on the device, in one host-to-device copy."""
+        stroke_ptr = np.asarray(stroke_ptr, np.int32)
+        d = self.to_device(np.concatenate([stroke_ptr, np.asarray(strokes, np.int32).ravel()]))
+        return d[stroke_ptr.size:].view(-1, 5), d[:stroke_ptr.size]
+
+    def apply_strokes(self, mask, strokes, stroke_ptr, radius=3):
+        """Brush strokes as hard constraints, in place on mask (B,H,W) uint8 (ggc_apply_strokes): strokes (S,5) int32 =
+        r0, c0, r1, c1, label and stroke_ptr (B+1,) int32 on the device (upload_strokes)."""
+        b, h, w = mask.shape
+        self.ctx.call("ggc_apply_strokes", self._stream(), b, h, w, _native.ptr(strokes), stroke_ptr.data_ptr(), int(radius),
+                      mask.data_ptr())
+        return mask
+
+    def stroke_pixels(self, shape, strokes, stroke_ptr):
+        """The centre-line pixels of a batch's strokes as a click list (ggc_stroke_pixels): shape = (B,H,W) ->
+        (hints (P,3) int32 = row, col, label; hint_ptr (B+1,) int32), both on the device.  One call counts, the next fills."""
+        b, h, w = shape
+        hint_ptr = self.empty(b + 1, dtype=torch.int32)
+        args = (self._stream(), b, h, w, _native.ptr(strokes), stroke_ptr.data_ptr(), hint_ptr.data_ptr())
+        self.ctx.call("ggc_stroke_pixels", *args, None, 0)
+        n = int(hint_ptr[-1].item()) if b else 0
+        hints = self.empty(n, 3, dtype=torch.int32)
+        if n:
+            self.ctx.call("ggc_stroke_pixels", *args, hints.data_ptr(), n)
+        return hints, hint_ptr
+
     def next_click(self, pred, gt) -> torch.Tensor:
         """The next simulated click of the NoC protocol per image (ggc_next_click): pred, gt (B,H,W) uint8, nonzero =
         foreground -> (B,4) int32 on the device = row, col, label (1 = fg, 0 = bg), d2; (-1,-1,-1,0) where pred == gt."""

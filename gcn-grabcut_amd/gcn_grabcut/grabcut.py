@@ -148,6 +148,35 @@ class GrabCut:
         self._snapshot("hints")
         return self._binary()
 
+    def add_strokes(self, fg_strokes=(), bg_strokes=(), radius: int = 3, geodesic=False) -> np.ndarray:
+        """Additive: paint brush strokes, polylines of (row, col) vertices, into the current mask as GC_FGD / GC_BGD within
+        `radius` pixels of each stroke (ggc_apply_strokes; radius 0: the centre line; background strokes win where the two
+        overlap; the part of a stroke inside the image is painted).  The edit runs on the mask the last run left on the
+        device; the GMMs are kept, so refine(n) continues from the edited mask.  geodesic=True or a pipeline.GeodesicHints
+        paints by geodesic distance on self.image from the strokes' centre-line pixels instead (ggc_stroke_pixels, then
+        ggc_geodesic_hints; `radius` is then ignored)."""
+        if self.mask is None:
+            raise RuntimeError("Call run_with_bbox or run_with_trimap first.")
+        from .pipeline import _geodesic_args, _check_stroke_radius
+        radius = _check_stroke_radius(radius, "radius")
+        geo = _geodesic_args(geodesic)
+        from .graph_builder import pack_strokes
+        segs, ptr = pack_strokes([(fg_strokes, bg_strokes)])
+        eng = self._eng
+        if self._dmask is None or not self.history or not np.array_equal(self.mask, self.history[-1].mask_copy):
+            self._dmask = eng.to_device(np.ascontiguousarray(self.mask, dtype=np.uint8)[None])   # the host mask was edited
+        if ptr[-1]:
+            d_segs, d_ptr = eng.upload_strokes(segs, ptr)
+            if geo is not None:
+                rows, row_ptr = eng.stroke_pixels(tuple(self._dmask.shape), d_segs, d_ptr)
+                eng.geodesic_hints(eng.to_device(np.ascontiguousarray(self.image)[None]), rows, row_ptr, geo.radius, geo.gamma,
+                                   mask=self._dmask)
+            else:
+                eng.apply_strokes(self._dmask, d_segs, d_ptr, radius)
+            self.mask = self._dmask[0].cpu().numpy()
+        self._snapshot("strokes")
+        return self._binary()
+
     def _binary(self) -> np.ndarray:
         return np.where((self.mask == Label.FG_DEFINITE) | (self.mask == Label.FG_PROBABLE), 1, 0).astype(np.uint8)
 

@@ -262,3 +262,51 @@ def pack_hints(per_image) -> "tuple[np.ndarray, np.ndarray]":
         raise ValueError(f"{ptr[-1]} clicks: too many for one call")
     hints = np.concatenate(rows).astype(np.int32) if rows else np.zeros((0, 3), np.int32)
     return np.ascontiguousarray(hints.reshape(-1, 3)), np.asarray(ptr, np.int32)
+
+
+STROKE_MAX_COORD = 1 << 20          # ggc_apply_strokes' limit on an endpoint coordinate
+
+
+def _stroke_segments(strokes, label: int, what: str) -> np.ndarray:
+    """The polylines of one label -> their segments, int64 [n,5] = (r0, c0, r1, c1, label)."""
+    out = []
+    if strokes is None:
+        return np.zeros((0, 5), np.int64)
+    if isinstance(strokes, (str, bytes)):
+        raise ValueError(f"{what} must be a sequence of strokes, each a sequence of (row, col) vertices")
+    for i, stroke in enumerate(strokes):
+        v = _click_rows(stroke, label, f"{what}[{i}]")[:, :2] if not isinstance(stroke, (str, bytes)) else None
+        if v is None or len(v) == 0:
+            raise ValueError(f"{what}[{i}] is empty: a stroke has at least one (row, col) vertex")
+        if (np.abs(v) > STROKE_MAX_COORD).any():
+            raise ValueError(f"{what}[{i}] holds a coordinate beyond +-2^20")
+        a, b = (v, v) if len(v) == 1 else (v[:-1], v[1:])
+        out.append(np.concatenate([a, b, np.full((len(a), 1), label, np.int64)], 1))
+    return np.concatenate(out) if out else np.zeros((0, 5), np.int64)
+
+
+def pack_strokes(per_image) -> "tuple[np.ndarray, np.ndarray]":
+    """Per-image brush strokes -> the (strokes, stroke_ptr) pair of ggc_apply_strokes; the sibling of pack_hints.
+
+    per_image: one entry per image, None (no strokes) or (fg_strokes, bg_strokes), each a sequence of strokes, a stroke
+    being a sequence of (row, col) vertices: a polyline of n >= 2 vertices gives n-1 segments, a one-vertex stroke one
+    segment with both ends equal.  Returns strokes int32 [S,5] = (r0, c0, r1, c1, label) with label 1 = foreground,
+    0 = background, and stroke_ptr int32 [B+1].  An image's foreground strokes come first, then its background strokes,
+    each in the order given, so background wins where the two overlap.  Vertices outside the image are kept: the kernel
+    paints the part of a segment that lies inside.  An empty stroke, a wrong shape or a coordinate beyond +-2^20 is a
+    ValueError."""
+    rows, ptr = [], [0]
+    for b, entry in enumerate(per_image):
+        if entry is None:
+            ptr.append(ptr[-1])
+            continue
+        if isinstance(entry, (str, bytes)) or not hasattr(entry, "__len__") or len(entry) != 2:
+            raise ValueError(f"strokes[{b}] must be None or a (fg_strokes, bg_strokes) pair")
+        fg = _stroke_segments(entry[0], 1, f"strokes[{b}] foreground strokes")
+        bg = _stroke_segments(entry[1], 0, f"strokes[{b}] background strokes")
+        rows += [fg, bg]
+        ptr.append(ptr[-1] + len(fg) + len(bg))
+    if ptr[-1] > np.iinfo(np.int32).max // 5:
+        raise ValueError(f"{ptr[-1]} stroke segments: too many for one call")
+    seg = np.concatenate(rows).astype(np.int32) if rows else np.zeros((0, 5), np.int32)
+    return np.ascontiguousarray(seg.reshape(-1, 5)), np.asarray(ptr, np.int32)

@@ -20,7 +20,7 @@ from typing import Optional, Sequence
 import numpy as np
 
 from .grabcut import GrabCut, GrabCutConfig, Label
-from .graph_builder import GraphBuilder, SuperpixelGraphConfig, graphs_to_host, _check_image, pack_hints
+from .graph_builder import GraphBuilder, SuperpixelGraphConfig, graphs_to_host, _check_image, pack_hints, pack_strokes
 from .metrics import evaluate, evaluate_matte, evaluate_trimap, MatteMetrics, SegmentationMetrics, TrimapMetrics
 from .model import CLASS_BG, CLASS_FG, project_to_pixels  # noqa: F401
 
@@ -516,6 +516,54 @@ def geodesic_hints(image: np.ndarray, fg_points, bg_points, radius: int = 40, ga
     return md[0].cpu().numpy()
 
 
+def _check_stroke_radius(radius, what: str = "stroke_radius") -> int:
+    if isinstance(radius, bool) or not isinstance(radius, (int, np.integer)) or not 0 <= int(radius) <= 16384:
+        raise ValueError(f"{what} must be an integer in [0, 16384], got {radius!r}")
+    return int(radius)
+
+
+def paint_strokes(mask_or_shape, fg_strokes, bg_strokes, radius: int = 3, device="cuda") -> np.ndarray:
+    """Brush strokes painted into a GrabCut label mask (additive; ggc_apply_strokes).  mask_or_shape: an
+    (H, W) uint8 mask of GrabCut labels, or an (H, W) shape for a mask that starts all probable background (2).
+    fg_strokes / bg_strokes: sequences of strokes, each a sequence of (row, col) vertices (graph_builder.pack_strokes).
+    Every pixel within `radius` of a stroke becomes definite foreground (1) / background (0), background winning where
+    the two overlap; radius 0 paints the centre line; vertices may lie outside the image.  -> the painted (H, W) uint8
+    mask (a copy)."""
+    from ._engine import get_engine
+    radius = _check_stroke_radius(radius, "radius")
+    if isinstance(mask_or_shape, (tuple, list)) and len(mask_or_shape) == 2 and all(isinstance(v, (int, np.integer)) for v in mask_or_shape):
+        h, w = (int(v) for v in mask_or_shape)
+        if h < 1 or w < 1:
+            raise ValueError(f"paint_strokes: bad shape {(h, w)}")
+        m = np.full((h, w), 2, np.uint8)
+    else:
+        m = np.ascontiguousarray(mask_or_shape, np.uint8)
+        if m.ndim != 2 or m.size == 0:
+            raise ValueError(f"paint_strokes: the mask must be (H, W), got {m.shape}")
+    segs, ptr = pack_strokes([(fg_strokes, bg_strokes)])
+    if ptr[-1] == 0:
+        return m.copy()
+    eng = get_engine(device)
+    d_segs, d_ptr = eng.upload_strokes(segs, ptr)
+    return eng.apply_strokes(eng.to_device(m[None]), d_segs, d_ptr, radius)[0].cpu().numpy()
+
+
+def stroke_pixels(shape, fg_strokes, bg_strokes, device="cuda") -> np.ndarray:
+    """The centre-line pixels of brush strokes inside an (H, W) image as a click list (additive; ggc_stroke_pixels):
+    -> (P, 3) int32 rows (row, col, label 1 | 0) in raster order, each pixel once with the label of the last stroke
+    segment whose centre line holds it (background strokes come after foreground ones)."""
+    from ._engine import get_engine
+    h, w = (int(v) for v in shape)
+    if h < 1 or w < 1:
+        raise ValueError(f"stroke_pixels: bad shape {(h, w)}")
+    segs, ptr = pack_strokes([(fg_strokes, bg_strokes)])
+    if ptr[-1] == 0:
+        return np.zeros((0, 3), np.int32)
+    eng = get_engine(device)
+    d_segs, d_ptr = eng.upload_strokes(segs, ptr)
+    return eng.stroke_pixels((1, h, w), d_segs, d_ptr)[0].cpu().numpy()
+
+
 def lift_labels(mask: np.ndarray, full_shape, band: Optional[int] = None, device="cuda") -> np.ndarray:
     """A working-size mask carried to a larger size as GrabCut labels for a banded cut there (additive; ggc_lift_labels,
     DESIGN.md §5.18).  The mask is interpolated bilinearly (half-pixel centres, as upsample_mask) and thresholded at 0.5;
@@ -671,19 +719,49 @@ def _colour_trimap(trimap: np.ndarray) -> np.ndarray:
 
 @dataclass
 class _Hints:
-    """The clicks of a batch in ggc_apply_hints' packing, on the host, and how they are applied."""
+    """The clicks of a batch in ggc_apply_hints' packing and its brush strokes in ggc_apply_strokes', on the host, and how
+    they are applied."""
     rows: np.ndarray           # (K,3) int32 = row, col, label (1 = foreground)
     ptr: np.ndarray            # (B+1,) int32
     radius: int
     region: bool
     as_prior: bool
     geodesic: "Optional[GeodesicHints]" = None     # set: ggc_geodesic_hints paints the clicks, radius and region do not apply
+    segs: Optional[np.ndarray] = None              # (S,5) int32 = r0, c0, r1, c1, label; None: the batch has no stroke
+    seg_ptr: Optional[np.ndarray] = None           # (B+1,) int32
+    stroke_radius: int = 3
 
     @staticmethod
-    def of(hints, b: int, radius, region, as_prior, geodesic=None) -> "Optional[_Hints]":
-        """hints: one None or (fg_points, bg_points) per image, or an already packed (hints, hint_ptr) pair.
-        None when no image has a click, so that such a call launches exactly what a call without hints launches."""
+    def _strokes_of(strokes, b: int):
+        """strokes: one None or (fg_strokes, bg_strokes) per image, or a packed (strokes, stroke_ptr) pair -> that pair on
+        the host, (None, None) when no image has a stroke."""
+        if strokes is None:
+            return None, None
+        if isinstance(strokes, tuple) and len(strokes) == 2 and all(hasattr(a, "shape") for a in strokes) and len(strokes[1].shape) == 1:
+            segs, ptr = (np.asarray(a.cpu() if hasattr(a, "cpu") else a) for a in strokes)
+            segs = segs.reshape(-1, 5) if segs.size else np.zeros((0, 5), np.int32)
+            if ptr.shape != (b + 1,) or ptr[0] != 0 or (np.diff(ptr) < 0).any() or ptr[-1] != len(segs):
+                raise ValueError(f"packed strokes: stroke_ptr must be a non-decreasing ({b + 1},) array from 0 to {len(segs)}")
+        else:
+            if len(strokes) != b:
+                raise ValueError(f"strokes has {len(strokes)} entries for a batch of {b} images")
+            segs, ptr = pack_strokes(strokes)
+        if ptr[-1] == 0:
+            return None, None
+        return np.ascontiguousarray(segs, np.int32), np.ascontiguousarray(ptr, np.int32)
+
+    @staticmethod
+    def of(hints, b: int, radius, region, as_prior, geodesic=None, strokes=None, stroke_radius=3) -> "Optional[_Hints]":
+        """hints: one None or (fg_points, bg_points) per image, or an already packed (hints, hint_ptr) pair; strokes: the
+        same for brush strokes ((fg_strokes, bg_strokes) per image, or a packed (strokes, stroke_ptr) pair).
+        None when no image has a click or a stroke, so that such a call launches exactly what a call without them
+        launches; a batch without strokes has segs None and launches exactly what it did before strokes existed."""
         geodesic = _geodesic_args(geodesic, region)
+        segs, seg_ptr = _Hints._strokes_of(strokes, b)
+        if segs is not None:
+            stroke_radius = _check_stroke_radius(stroke_radius)
+            if hints is None:
+                hints = (np.zeros((0, 3), np.int32), np.zeros(b + 1, np.int32))
         if hints is None:
             return None
         if int(radius) < 0:
@@ -697,16 +775,21 @@ class _Hints:
             if len(hints) != b:
                 raise ValueError(f"hints has {len(hints)} entries for a batch of {b} images")
             rows, ptr = pack_hints(hints)
-        if ptr[-1] == 0:
+        if ptr[-1] == 0 and segs is None:
             return None
         return _Hints(np.ascontiguousarray(rows, np.int32), np.ascontiguousarray(ptr, np.int32), int(radius), bool(region),
-                      bool(as_prior), geodesic)
+                      bool(as_prior), geodesic, segs, seg_ptr, int(stroke_radius) if segs is not None else 3)
 
     def chunk(self, lo: int, hi: int) -> "Optional[_Hints]":
         k0, k1 = int(self.ptr[lo]), int(self.ptr[hi])
-        if k1 == k0:
+        segs = seg_ptr = None
+        if self.segs is not None and self.seg_ptr[hi] > self.seg_ptr[lo]:      # strokes are sliced by stroke_ptr, as clicks by hint_ptr
+            s0, s1 = int(self.seg_ptr[lo]), int(self.seg_ptr[hi])
+            segs, seg_ptr = self.segs[s0:s1], self.seg_ptr[lo:hi + 1] - s0
+        if k1 == k0 and segs is None:
             return None
-        return _Hints(self.rows[k0:k1], self.ptr[lo:hi + 1] - k0, self.radius, self.region, self.as_prior, self.geodesic)
+        return _Hints(self.rows[k0:k1], self.ptr[lo:hi + 1] - k0, self.radius, self.region, self.as_prior, self.geodesic,
+                      segs, seg_ptr, self.stroke_radius)
 
     def clicked_images(self, h: int, w: int) -> np.ndarray:
         """(B,) bool: the images with at least one click inside the frame."""
@@ -1030,8 +1113,13 @@ class GCNGrabCutPipeline:
         prior = graphs.x[:, 16:19]
         if hints is not None:
             hint_rows, hint_ptr = eng.upload_hints(hints.rows, hints.ptr)
+            all_rows, all_ptr, clicked = hint_rows, hint_ptr, None     # what the superpixels, the prior and the geodesic see
+            if hints.segs is not None:
+                segs, seg_ptr = eng.upload_strokes(hints.segs, hints.seg_ptr)
+                if hints.as_prior or hints.region or hints.geodesic is not None:
+                    all_rows, all_ptr, clicked = self._with_stroke_pixels(eng, hints, hint_rows, seg.shape, segs, seg_ptr)
             if hints.as_prior:
-                prior = self._hints_as_prior(eng, hints, hint_rows, hint_ptr, seg, graphs, bgr)
+                prior = self._hints_as_prior(eng, hints, all_rows, all_ptr, seg, graphs, bgr, clicked)
         probs = eng.predict_probs(self.model, graphs)
         trimap = eng.refine_trimap(probs, graphs.node_ptr, seg, bgr, threshold_fg, threshold_bg, filter_radius,
                                    1e-3, edge_aware)
@@ -1039,13 +1127,36 @@ class GCNGrabCutPipeline:
             timing["gcn_inference"] = tick() - t
         trimap = eng.seed_from_prior(trimap, prior, graphs.node_ptr, seg, 0.1)
         if hints is not None and hints.geodesic is not None:   # the guide is the caller's BGR batch, never gc_image
-            eng.geodesic_hints(bgr, hint_rows, hint_ptr, hints.geodesic.radius, hints.geodesic.gamma, mask=trimap)
-        elif hints is not None:                # hard constraints: over the network's trimap and the seeding alike
+            eng.geodesic_hints(bgr, all_rows, all_ptr, hints.geodesic.radius, hints.geodesic.gamma, mask=trimap)
+        elif hints is not None and hints.segs is None:   # hard constraints: over the network's trimap and the seeding alike
             eng.apply_hints(trimap, hint_rows, hint_ptr, hints.radius, hints.region, seg, graphs.node_ptr)
+        elif hints is not None:                # strokes: the superpixels under centre lines and clicks, the brush, the disks
+            if hints.region:
+                eng.apply_hints(trimap, all_rows, all_ptr, 0, True, seg, graphs.node_ptr)
+            eng.apply_strokes(trimap, segs, seg_ptr, hints.stroke_radius)
+            if len(hints.rows):
+                eng.apply_hints(trimap, hint_rows, hint_ptr, hints.radius, False)
         return seg, graphs, probs, trimap
 
     @staticmethod
-    def _hints_as_prior(eng, hints, hint_rows, hint_ptr, seg, graphs, bgr=None):
+    def _with_stroke_pixels(eng, hints, hint_rows, shape, segs, seg_ptr):
+        """The merged click list of a stroked batch on the device: per image its strokes' centre-line pixels
+        (ggc_stroke_pixels), then its clicks.  -> (rows, ptr, (B,) bool: the images with a stroke pixel or a click inside
+        the frame)."""
+        import torch
+        pix, pix_ptr = eng.stroke_pixels(tuple(shape), segs, seg_ptr)
+        pp, cp = pix_ptr.cpu().numpy().astype(np.int64), hints.ptr.astype(np.int64)
+        clicked = (np.diff(pp) > 0) | hints.clicked_images(shape[1], shape[2])
+        if cp[-1] == 0:
+            return pix, pix_ptr, clicked
+        n_pix = int(pp[-1])
+        src = np.concatenate([np.concatenate([np.arange(pp[b], pp[b + 1]), n_pix + np.arange(cp[b], cp[b + 1])])
+                              for b in range(len(pp) - 1)])
+        rows = torch.cat([pix, hint_rows])[eng.to_device(src)].contiguous()
+        return rows, eng.to_device((pp + cp).astype(np.int32)), clicked
+
+    @staticmethod
+    def _hints_as_prior(eng, hints, hint_rows, hint_ptr, seg, graphs, bgr=None, clicked=None):
         """The reference's use of encode_user_hints: the prior columns x[:, 16:19] of every image with a click inside the
         frame become its click table; the other images keep the automatic prior.  Returns a copy of the automatic prior,
         which seed_from_prior still reads.  Geodesic hints: the table is encode_geodesic_hints', computed on the host
@@ -1061,7 +1172,8 @@ class GCNGrabCutPipeline:
         else:
             table = eng.empty(graphs.x.size(0), 3)
             eng.apply_hints(None, hint_rows, hint_ptr, segments=seg, node_ptr=graphs.node_ptr, node_hints=table, shape=seg.shape)
-        clicked = hints.clicked_images(seg.size(1), seg.size(2))
+        if clicked is None:                    # (given with strokes: their centre-line pixels count as clicks)
+            clicked = hints.clicked_images(seg.size(1), seg.size(2))
         nptr = graphs.node_ptr_host
         b = 0
         while b < len(clicked):                # one copy per run of consecutive clicked images
@@ -1096,7 +1208,7 @@ class GCNGrabCutPipeline:
                              chunks: Optional[int] = None, hints=None, hint_radius: int = 5, hint_region: bool = False,
                              hints_as_prior: bool = False, return_state: bool = False, matte: bool = False,
                              matte_radius: int = MATTE_RADIUS, matte_eps: float = MATTE_EPS, full_bgr=None,
-                             foreground=False, full_cut=False, geodesic=False) -> dict:
+                             foreground=False, full_cut=False, geodesic=False, strokes=None, stroke_radius: int = 3) -> dict:
         """bgr: (B,H,W,3) uint8 tensor on the pipeline's device.  Returns device tensors.
 
         matte=True (additive) also returns "alpha" (B,H,W) float32, the soft matte of the cleaned mask (alpha_matte with
@@ -1137,6 +1249,16 @@ class GCNGrabCutPipeline:
         hint_region=True is a ValueError, and hints_as_prior=True then writes encode_geodesic_hints' soft columns (an
         encoding no shipped network was trained on).  Without clicks the option launches nothing.
 
+        Brush strokes (additive): strokes is None, a list with one None or (fg_strokes, bg_strokes) per
+        image (each a sequence of strokes, a stroke a sequence of (row, col) vertices), or a packed (strokes, stroke_ptr)
+        pair (graph_builder.pack_strokes).  Every pixel within stroke_radius of a stroke becomes definite foreground /
+        background (ggc_apply_strokes; radius 0: the centre line; the part of a stroke inside the image is painted), the
+        later segment winning, then the clicks' disks are painted over the strokes.  With hint_region / hints_as_prior a
+        stroke's centre-line pixels (ggc_stroke_pixels) count as clicks before the image's own: a stroke claims every
+        superpixel its centre line crosses.  In geodesic mode the centre line is the source set and stroke_radius is
+        ignored, as hint_radius is.  A batch without strokes launches exactly what it did before, and an image without
+        strokes in a stroked batch gets the outputs it gets without them, bit for bit.
+
         Large batches run as a software pipeline (additive, same results): the batch is cut into `chunks` contiguous
         chunks; the front stages of chunk k+1 run on the caller's stream while the GrabCut / clean-up of chunk k runs on a
         lane of its own (private context, stream and host thread).  Images are independent and image b keeps seed + b, so
@@ -1146,7 +1268,7 @@ class GCNGrabCutPipeline:
         b = bgr.size(0)
         want = self.grabcut_lanes if grabcut_lanes is None else int(grabcut_lanes)   # (an argument, so that concurrent callers do not mutate the pipeline)
         n_chunks = self.chunks if chunks is None else int(chunks)
-        hints = _Hints.of(hints, b, hint_radius, hint_region, hints_as_prior, geodesic)
+        hints = _Hints.of(hints, b, hint_radius, hint_region, hints_as_prior, geodesic, strokes, stroke_radius)
         plan = _OutputPlan.of(self, bgr.shape, None if full_bgr is None else full_bgr.shape, compose=compose,
                               min_area_ratio=min_area_ratio, keep_largest=keep_largest, matte=matte, matte_radius=matte_radius,
                               matte_eps=matte_eps, foreground=foreground, full_cut=full_cut)
@@ -1286,9 +1408,11 @@ class GCNGrabCutPipeline:
             timing["wall"] = time.perf_counter() - t_host
         return out
 
-    def segment_batch(self, images: Sequence[np.ndarray], hints=None, full_images=None, **kwargs) -> list[SegmentationResult]:
+    def segment_batch(self, images: Sequence[np.ndarray], hints=None, full_images=None, strokes=None,
+                      **kwargs) -> list[SegmentationResult]:
         """Segment equally sized BGR images as one batch (additive API).  hints: one None or (fg_points, bg_points) per
-        image, with hint_radius / hint_region / hints_as_prior / geodesic among kwargs (segment_batch_device).  full_images
+        image, with hint_radius / hint_region / hints_as_prior / geodesic among kwargs (segment_batch_device).  strokes:
+        one None or (fg_strokes, bg_strokes) per image, with stroke_radius among kwargs (segment_batch_device).  full_images
         (additive): the same images at one larger size each, (H1, W1, 3) uint8 BGR; every result's `full` then holds the
         outputs at that size (segment_batch_device's full_bgr).  foreground=True | ForegroundColours(...) among kwargs
         (with a matte) fills every result's foreground and rgba_clean.  full_cut=True | FullCut(...) among kwargs (with
@@ -1313,6 +1437,8 @@ class GCNGrabCutPipeline:
             full_bgr = self._eng.to_device(np.stack(fulls))
         timing: dict[str, float] = {}
         bgr = self._eng.to_device(np.stack(imgs))
+        if strokes is not None:
+            kwargs["strokes"] = strokes
         out = self.segment_batch_device(bgr, timing=timing, hints=hints, full_bgr=full_bgr, **kwargs)
         out.update({k: out[k].cpu() for k in _REFERENCE_FIELDS + _ADDITIVE_FIELDS if k in out})      # one copy per output, not one per image
         per_image = {k: v / len(imgs) for k, v in timing.items()}
@@ -1449,7 +1575,7 @@ class GCNGrabCutPipeline:
                 hint_region: bool = False, hints_as_prior: bool = False, matte: bool = False,
                 matte_radius: int = MATTE_RADIUS, matte_eps: float = MATTE_EPS,
                 full_image: Optional[np.ndarray] = None, foreground=False, full_cut=False,
-                geodesic=False) -> SegmentationResult:
+                geodesic=False, fg_strokes=None, bg_strokes=None, stroke_radius: int = 3) -> SegmentationResult:
         """Full pipeline on one BGR image (reference pipeline.py:265-352).
 
         Additive: fg_points / bg_points are user clicks, (row, col) pairs, applied as hard constraints on the trimap
@@ -1461,7 +1587,9 @@ class GCNGrabCutPipeline:
         with a matte, fills the result's foreground and rgba_clean (estimate_foreground under that matte's alpha);
         full_cut=True | FullCut(...), with full_image, makes the full binary_mask, overlay and rgba those of
         cut_mask_full of the cleaned mask (segment_batch_device); geodesic=True | GeodesicHints(...) paints the clicks by
-        their geodesic distance on the image instead of disks (hint_radius is then ignored; segment_batch_device)."""
+        their geodesic distance on the image instead of disks (hint_radius is then ignored; segment_batch_device);
+        fg_strokes / bg_strokes are brush strokes, sequences of polylines of (row, col) vertices, painted with
+        stroke_radius as hard constraints before the clicks (segment_batch_device's strokes)."""
         image = _check_image(image)
         full = None if full_image is None else _check_image(full_image)
         _OutputPlan.of(self, (1, *image.shape), None if full is None else (1, *full.shape), min_area_ratio=min_area_ratio,
@@ -1471,12 +1599,14 @@ class GCNGrabCutPipeline:
         timing: dict[str, float] = {}
         hints = None if fg_points is None and bg_points is None else \
             [(() if fg_points is None else fg_points, () if bg_points is None else bg_points)]
+        strokes = None if fg_strokes is None and bg_strokes is None else \
+            [(() if fg_strokes is None else fg_strokes, () if bg_strokes is None else bg_strokes)]
         out = self.segment_batch_device(self._eng.to_device(image[None]), threshold_fg, threshold_bg, refine_iters,
                                         min_area_ratio, keep_largest, edge_aware, filter_radius, timing=timing,
                                         hints=hints, hint_radius=hint_radius, hint_region=hint_region,
                                         hints_as_prior=hints_as_prior, matte=matte, matte_radius=matte_radius,
                                         matte_eps=matte_eps, full_bgr=full_bgr, foreground=foreground, full_cut=full_cut,
-                                        geodesic=geodesic)
+                                        geodesic=geodesic, strokes=strokes, stroke_radius=stroke_radius)
         return _result(out, 0, image, timing)
 
     def segment_bbox(self, image: np.ndarray, bbox: tuple[int, int, int, int], matte: bool = False,

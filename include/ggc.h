@@ -51,7 +51,9 @@
 extern "C" {
 #endif
 
-#define GGC_VERSION 404 /* 0.4.4: ggc_geodesic_hints (clicks propagated by a capped, colour-aware shortest-path distance instead of a fixed
+#define GGC_VERSION 405 /* 0.4.5: ggc_apply_strokes, ggc_stroke_pixels (brush strokes as hard constraints: polylines painted as capsules by
+                                  one exact integer rule, and their centre lines as a click list; additive, no existing entry changes);
+                           0.4.4: ggc_geodesic_hints (clicks propagated by a capped, colour-aware shortest-path distance instead of a fixed
                                   disk; additive, ggc_apply_hints does not change);
                            0.4.3: ggc_lift_labels (a working-size mask carried to a larger size as GrabCut labels with an open band
                                   around its edge: the start of a banded graph cut on the full image; no existing entry changes);
@@ -442,6 +444,46 @@ int ggc_apply_hints(ggc_ctx* ctx, ggc_stream stream, int B, int H, int W, const 
 int ggc_geodesic_hints(ggc_ctx* ctx, ggc_stream stream, int B, int H, int W, const uint8_t* bgr, const int32_t* hints,
                        const int32_t* hint_ptr, int radius, int gamma, const int32_t* segments, const int32_t* node_ptr,
                        uint8_t* mask, int32_t* dist_fg, int32_t* dist_bg, int32_t* node_dist);
+
+/* H2 — brush strokes as hard constraints (additive): the drag of a brush, where ggc_apply_hints has single clicks.  One exact
+ * integer definition; no float is involved anywhere.
+ *   strokes    [dev] i32 [S,5] = (r0, c0, r1, c1, label) straight segments, label 0 = background, nonzero = foreground;
+ *              grouped by image, order kept within an image.  A polyline of n >= 2 vertices is its n-1 segments, a
+ *              one-vertex stroke one segment with both ends equal.  |coordinate| <= 2^20; endpoints may lie outside the
+ *              image and the part inside is painted (a CLICK outside the image is ignored; a stroke is clipped).
+ *   stroke_ptr [dev] i32 [B+1]  image b owns strokes[stroke_ptr[b] .. stroke_ptr[b+1]); stroke_ptr[0] = 0, non-decreasing
+ *   radius     0 .. 16384, the brush radius in pixels
+ *   mask       [dev] u8 [B,H,W] in/out GrabCut labels
+ * Rule: for pixel p and segment a -> b let w = p - a, d = b - a, L2 = d.d, t = w.d.  dist^2(p, segment) is |w|^2 if t <= 0,
+ * |p - b|^2 if t >= L2, else (w x d)^2 / L2.  p is WITHIN RHO of the segment iff 4 dist^2 <= rho4 = max(4 radius^2, 1); the third
+ * case is decided as 4 (w x d)^2 <= rho4 L2, without division, in 128-bit integers (t and w x d fit int64 under the limits
+ * above; the squares do not).  radius >= 1: the closed capsule of that radius, boundary included, as dy*dy + dx*dx <=
+ * radius*radius is for clicks, so a one-vertex stroke paints exactly ggc_apply_hints' disk.  radius == 0: the CENTRE LINE, the
+ * pixels within half a pixel of the segment: 8-connected, holds both endpoints, exact half-pixel ties included.
+ * ggc_apply_strokes: every in-image pixel within rho of a segment of its image becomes GGC_FGD or GGC_BGD; where segments
+ * overlap the image's LAST segment wins, by index and not by timing; a pixel no stroke touches is neither read nor written.
+ * Work is O(pixels + 32x8 tiles x segments), independent of the strokes' lengths; every image's result equals that of its
+ * single-image call bit for bit.
+ * B == 0 or stroke_ptr[B] == 0 is a no-op: nothing is written.  B, H or W outside 1..65535 is GGC_E_SHAPE; radius out of
+ * range, a NULL stroke_ptr or mask, NULL strokes with segments, stroke_ptr[0] != 0, a decreasing stroke_ptr or an endpoint
+ * beyond +-2^20 is GGC_E_INVALID_ARG, all before any launch.  SYNCHRONISES the stream: stroke_ptr and the segments are read
+ * back and checked on the host. */
+int ggc_apply_strokes(ggc_ctx* ctx, ggc_stream stream, int B, int H, int W, const int32_t* strokes, const int32_t* stroke_ptr,
+                      int radius, uint8_t* mask);
+
+/* H2 — the centre-line pixels of a batch's strokes (the radius == 0 rule above) inside the image, as a click list in
+ * ggc_apply_hints' packing, so that a stroke can go wherever clicks go (superpixel regions, prior columns, geodesic sources).
+ *   hint_ptr_out [dev] i32 [B+1] out, always written: image b owns rows hint_ptr_out[b] .. hint_ptr_out[b+1)
+ *   hints_out    [dev] i32 [capacity,3] out = (row, col, label 1 | 0), or NULL: only the counts are produced (call once with
+ *                NULL, allocate hint_ptr_out[B] rows, call again: the pattern of ggc_graph_count / ggc_graph_fill)
+ * Rows are grouped by image, each image in raster order, each pixel once; a pixel's label is that of the image's last segment
+ * whose centre line holds it.  Integer sums only, no atomics: the list does not depend on launch order.  A non-NULL
+ * hints_out with capacity < hint_ptr_out[B] is GGC_E_INVALID_ARG with nothing written to hints_out.  B == 0 is a no-op; with
+ * B >= 1 and no segments hint_ptr_out is all zeros and nothing else is written.  Arguments are checked as for
+ * ggc_apply_strokes; also B*H*W must fit int32 (GGC_E_SHAPE).  Scratch: one byte per pixel and 4 bytes per row.
+ * SYNCHRONISES the stream: stroke_ptr and the segments are read back and checked, and with hints_out the total is read. */
+int ggc_stroke_pixels(ggc_ctx* ctx, ggc_stream stream, int B, int H, int W, const int32_t* strokes, const int32_t* stroke_ptr,
+                      int32_t* hint_ptr_out, int32_t* hints_out, int64_t capacity);
 
 /* C0 — next simulated click per image (additive; the standard NoC protocol of interactive segmentation).
  *   pred [dev] u8  [B,H,W]  current binary mask (nonzero = foreground)

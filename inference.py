@@ -7,6 +7,7 @@ Same command line as the reference's inference.py (flags :26-56, outputs :146-15
     python3 inference.py --input path/to/folder --output results/
     python3 inference.py --image cat.jpg --keep-largest --save mask overlay
     python3 inference.py --image cat.jpg --fg-point 120,200 --bg-point 10,10 --hint-radius 8
+    python3 inference.py --image cat.jpg --bg-stroke "40,10 40,200 90,260" --stroke-radius 4   # a brush stroke of three vertices
     python3 inference.py --image cat.jpg --save mask alpha cutout          # soft edges: alpha matte and cut-out
     python3 inference.py --image big.jpg --full-res --save mask cutout     # outputs at the photo's own size
     python3 inference.py --image big.jpg --full-res --full-mask cut --save mask   # ... the mask cut again on the photo's pixels
@@ -64,6 +65,14 @@ def build_parser() -> argparse.ArgumentParser:
     parser.add_argument("--hint-gamma", type=int, default=2, help="Weight of the colour term of the geodesic distance, 0..64")
     parser.add_argument("--geodesic-radius", type=int, default=40,
                         help="Reach of a geodesic click over flat colour, in pixels of the image as segmented, 0..16384")
+    # additive: brush strokes as hard constraints (ggc_apply_strokes), single-image runs only
+    parser.add_argument("--fg-stroke", action="append", type=_stroke, default=[], metavar='"ROW,COL ROW,COL ..."',
+                        help="Foreground brush stroke, a polyline of vertices in original-image pixels (repeatable; needs --image)")
+    parser.add_argument("--bg-stroke", action="append", type=_stroke, default=[], metavar='"ROW,COL ROW,COL ..."',
+                        help="Background brush stroke, a polyline of vertices in original-image pixels (repeatable; needs --image)")
+    parser.add_argument("--stroke-radius", type=int, default=3,
+                        help="Brush radius in pixels of the image as segmented (after --max-size), 0..16384; 0 paints the "
+                             "centre line; ignored with --hint-mode geodesic, where the centre line is the source set")
     # additive: soft alpha matte of the mask (ggc_alpha_matte), computed when --save asks for alpha or cutout
     parser.add_argument("--matte-radius", type=int, default=4,
                         help="Window radius of the alpha matte, 1..64, in pixels of the image as segmented")
@@ -116,6 +125,16 @@ def _point(text: str):
     except ValueError:
         raise argparse.ArgumentTypeError(f"expected ROW,COL (two integers), got '{text}'")
     return r, c
+
+
+def _stroke(text: str):
+    try:
+        pts = [_point(v) for v in text.split()]
+    except argparse.ArgumentTypeError:
+        pts = []
+    if not pts:
+        raise argparse.ArgumentTypeError(f"expected 'ROW,COL ROW,COL ...' (at least one vertex), got '{text}'")
+    return pts
 
 
 def scale_points(points, orig_hw, new_hw):
@@ -178,6 +197,10 @@ def main() -> None:
     args = parser.parse_args()
     if (args.fg_point or args.bg_point) and not args.image:
         parser.error("--fg-point / --bg-point are clicks on one image: use them with --image, not --input")
+    if (args.fg_stroke or args.bg_stroke) and not args.image:
+        parser.error("--fg-stroke / --bg-stroke are strokes on one image: use them with --image, not --input")
+    if not 0 <= args.stroke_radius <= 16384:
+        parser.error("--stroke-radius must be in 0..16384")
     if args.hint_radius < 0:
         parser.error("--hint-radius must be >= 0")
     if not 0 <= args.hint_gamma <= 64:
@@ -269,14 +292,19 @@ def main() -> None:
             chunk = items[i:i + args.batch]
             t0 = time.perf_counter()
             hint_kw = {}
-            if args.fg_point or args.bg_point:          # --image only: one chunk of one image
+            if args.fg_point or args.bg_point or args.fg_stroke or args.bg_stroke:   # --image only: one chunk of one image
                 from PIL import Image
                 path, image, _ = chunk[0]
                 with Image.open(path) as im:
                     orig_hw = im.size[::-1]
-                hint_kw = dict(hints=[(scale_points(args.fg_point, orig_hw, image.shape[:2]),
-                                       scale_points(args.bg_point, orig_hw, image.shape[:2]))],
-                               hint_radius=args.hint_radius)
+                if args.fg_point or args.bg_point:
+                    hint_kw = dict(hints=[(scale_points(args.fg_point, orig_hw, image.shape[:2]),
+                                           scale_points(args.bg_point, orig_hw, image.shape[:2]))],
+                                   hint_radius=args.hint_radius)
+                if args.fg_stroke or args.bg_stroke:
+                    hint_kw.update(strokes=[([scale_points(s, orig_hw, image.shape[:2]) for s in args.fg_stroke],
+                                             [scale_points(s, orig_hw, image.shape[:2]) for s in args.bg_stroke])],
+                                   stroke_radius=args.stroke_radius)
                 if args.hint_mode == "geodesic":
                     from src.gcn_grabcut import GeodesicHints
                     hint_kw.update(geodesic=GeodesicHints(args.geodesic_radius, args.hint_gamma))
