@@ -3,9 +3,10 @@
 //
 // Batched over B images with data-dependent node counts.  Design points:
 //  * region sums follow np.bincount(weights=...) exactly — float64 running sums
-//    in raster order, cast to float32 — by giving every region one lane that
-//    walks the region's bounding box in raster order (SLIC regions are compact,
-//    so the box is a few thousand pixels).  Deterministic, no float atomics.
+//    in raster order, cast to float32 — by giving every region a group of 16
+//    lanes, one per accumulator, that walks the region's bounding box in raster
+//    order (SLIC regions are compact, so the box is a few hundred pixels).
+//    Deterministic, no float atomics.
 //  * np.unique(lo*N+hi, return_counts=True) becomes a dense per-image N x N
 //    int32 matrix filled with integer atomics (exact, order independent) and
 //    read back row-major with wave ballot/prefix compaction, which yields the
@@ -16,7 +17,6 @@
 //  * ggc_graph_count synchronises twice (node counts, pair counts) so that the
 //    packed outputs can be sized exactly; ggc_graph_fill only copies.
 #include "ggc_internal.h"
-#include <atomic>
 #include <algorithm>
 #include <cmath>
 #include <vector>
@@ -97,31 +97,42 @@ __global__ void k_bbox_init(size_t n, int4* bbox) {
     if (i < n) bbox[i] = make_int4(INT32_MAX, 0, INT32_MAX, 0);
 }
 
-// ---- K2: region statistics, one lane per region, raster order, f64 sums
-// The sums must be float64 running sums in raster order (= np.bincount(weights=...)), so a lane owns a region and walks
-// its bounding box.  Read straight from global memory that walk moved 15x the bytes it needed (PMC: 15.8 GB per launch
-// against 1 GB of inputs — 64 lanes, 64 different cache lines per load).  Instead the wave stages one image ROW of the
-// union of its 64 regions' boxes in LDS with coalesced loads (labels of the rows above / below too, for the boundary
-// test), and every lane scans its own x-range of that row from LDS.  Same visits in the same order, every byte loaded
-// about twice (overlap of neighbouring waves' unions).
-struct StatsAcc {
-    double cnt = 0, sl[3] = {0, 0, 0}, sl2[3] = {0, 0, 0}, sh[3] = {0, 0, 0};
-    double sy = 0, sx = 0, syd = 0, sxd = 0, sb = 0, sg1 = 0, sgn = 0;
-};
+// ---- K2: region statistics, a group of SG lanes per region, raster order, f64 sums
+// The sums must be float64 running sums in raster order (= np.bincount(weights=...)).  Only the order of additions
+// within ONE accumulator is fixed; the 15 rounded accumulators of a region are independent of each other, so each gets
+// a lane of the region's group, and finding the members is separate from folding them.  The group walks the region's
+// bounding box row by row in chunks of SG consecutive pixels (one coalesced label read for the four groups of a wave),
+// a ballot gives the chunk's members in ascending x, the member lanes put their pixel's values into LDS, and then every
+// lane of the group walks the set bits and adds its own accumulator's addend: the same additions in the same order.
+// cnt and the boundary count are sums of 1.0 and are taken as popcounts.  (One lane per region with the rows of the
+// wave's 64 boxes staged in LDS was a 1 ms latency chain per wave at 1.5 waves per SIMD.)
+constexpr int SG = 16;                 // lanes per region
+constexpr int SG_REGIONS = 64 / SG;    // regions per wave
+constexpr int SG_COLS = 2 * SG;        // box columns whose (double)x/W is tabulated per group ...
+constexpr int SG_TAB = SG_COLS + SG;   // ... plus one chunk of spill slots for boxes wider than that
 
-__global__ void __launch_bounds__(64) k_stats(GDims d, const int32_t* __restrict__ seg,
+// order the wave's own LDS writes before its reads (a block is one wave)
+__device__ __forceinline__ void stats_lds_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+}
+
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) k_stats(GDims d, const int32_t* __restrict__ seg,
                                               const int32_t* __restrict__ n_nodes,
                                               const float* __restrict__ lab, const float* __restrict__ hsv,
                                               const float* __restrict__ grad, const int4* __restrict__ bbox,
                                               const int32_t* __restrict__ border,
                                               const uint32_t* __restrict__ gmax, RegionStats* __restrict__ out) {
-    extern __shared__ float s_row[];          // [3][Wu] labels (rows y-1, y, y+1) | [Wu][3] lab | [Wu][3] hsv | [Wu] grad | [Wu] grad/max
-                                              // | [Wu] (float)x/W | [Wu] (double)x/W: the quotients are per pixel / per column, not per visit
+    // 3.8 KB of LDS and, by amdgpu_waves_per_eu, 64 VGPRs: the block is one wave, and what bounds the kernel is how many
+    // waves have loads in flight (8 per SIMD this way; 0.94 ms per batch of 256 at 6, 0.85 at 8)
+    __shared__ float s_f[9 * 64];                                   // chunk values: lab 0-2, hsv 3-5, grad 6, grad/max 7, (float)x/W 8
+    __shared__ double s_d[SG_REGIONS * SG_TAB];                     // (double)x/W per group
     const int b = blockIdx.y, lane = threadIdx.x;
     const int N = n_nodes[b];
-    const int r0 = blockIdx.x * 64;
+    const int r0 = blockIdx.x * SG_REGIONS;
     if (r0 >= N) return;
-    const int r = r0 + lane;
+    const int g = lane / SG, li = lane % SG;
+    const int r = r0 + g;
     const bool live = r < N;
     const int H = d.H, W = d.W;
     const size_t P = (size_t)H * W;
@@ -131,105 +142,117 @@ __global__ void __launch_bounds__(64) k_stats(GDims d, const int32_t* __restrict
     const float* gr = grad + (size_t)b * P;
     const int4 bb = live ? bbox[(size_t)b * d.Nmax + r] : make_int4(INT32_MAX, 0, INT32_MAX, 0);
     const float gden = (float)((double)ord2f_g(gmax[b]) + 1e-6);
-    // union of the wave's boxes
-    int uy0 = bb.y > bb.x ? bb.x : INT32_MAX, uy1 = bb.y > bb.x ? bb.y : 0;
-    int ux0 = bb.w > bb.z ? bb.z : INT32_MAX, ux1 = bb.w > bb.z ? bb.w : 0;
+    const bool boxed = bb.y > bb.x && bb.w > bb.z;
+    const int xa = boxed ? bb.z & ~(SG - 1) : 0;                    // chunks start at multiples of SG: aligned label reads
+    const int ya = boxed ? bb.x : 0;
+
+    // This lane's accumulator: 0-2 lab, 3-5 lab^2, 6-8 hsv, 9 (float)y/H, 10 (float)x/W, 11 (double)y/H, 12 (double)x/W,
+    // 13 grad, 14 grad/max; lane 15 folds nothing that is kept.  The addend of a member at chunk position `bit` is
+    // s_f[fbase + bit] (squared for 3-5), s_d[doff + bit], or the row's quotient, which the lane keeps in a register.
+    const bool sq = li >= 3 && li < 6;
+    const bool is_row = li == 9 || li == 11;
+    const bool is_d = li == 12;
+    const int frow = li < 3 ? li : li < 9 ? li - 3 : li == 10 ? 8 : li == 13 ? 6 : li == 14 ? 7 : 0;
+    const int fbase = frow * 64 + g * SG;
+
+    // (double)x/W of the first SG_COLS columns of the box, once per region instead of once per chunk
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        uy0 = min(uy0, __shfl_xor(uy0, o, 64)); uy1 = max(uy1, __shfl_xor(uy1, o, 64));
-        ux0 = min(ux0, __shfl_xor(ux0, o, 64)); ux1 = max(ux1, __shfl_xor(ux1, o, 64));
-    }
-    const int Wu = max(ux1 - ux0, 0);
-    int32_t* s_seg = reinterpret_cast<int32_t*>(s_row);            // 3 rows, slot = (y + 1) % 3 rotates
-    float* s_lab = s_row + 3 * (size_t)Wu;
-    float* s_hsv = s_lab + 3 * (size_t)Wu;
-    float* s_grd = s_hsv + 3 * (size_t)Wu;
-    float* s_gn = s_grd + Wu;
-    float* s_xf = s_gn + Wu;
-    double* s_xd = reinterpret_cast<double*>(s_xf + Wu + (Wu & 1));          // 8-byte aligned: 12 Wu + (Wu & 1) floats precede it
-    for (int i = lane; i < Wu; i += 64) { s_xf[i] = (float)(ux0 + i) / (float)W; s_xd[i] = (double)(ux0 + i) / (double)W; }
-    // Rows are staged by LDS-DMA (global_load_lds, 4 B per lane, 256 B per instruction): a single wave cannot hide
-    // the latency of load -> store loops, but it can have a whole row of DMA pieces in flight and wait once.
-    auto dma_row = [&](const void* src, void* dst, int n_words) {   // n_words 4-byte words, contiguous on both sides
-        for (int i = 0; i < n_words; i += 64)
-            if (i + lane < n_words)
-                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)((const uint32_t*)src + i + lane),
-                                                 (__attribute__((address_space(3))) void*)((uint32_t*)dst + i), 4, 0, 0);
+    for (int q = 0; q < SG_COLS / SG; ++q) s_d[g * SG_TAB + q * SG + li] = (double)(xa + q * SG + li) / (double)W;
+    stats_lds_sync();
+
+    // Everything a chunk needs from memory, for every lane inside the box whether it turns out to be a member or not:
+    // one trip to memory per chunk, and the next chunk's trip is under way while this one is folded.
+    struct Chunk { int lbl, up, dn, lf, rt; float l0, l1, l2, h0, h1, h2, gv; };
+    auto fetch = [&](int y, int xc, bool active) {
+        Chunk c{-1, -1, -1, -1, -1, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        const int x = xc + li;
+        if (active && x >= bb.z && x < bb.w) {                       // the box lies inside the image
+            const size_t p = (size_t)y * W + x;
+            c.lbl = sg[p];
+            if (y > 0) c.up = sg[p - W];
+            if (y < H - 1) c.dn = sg[p + W];
+            if (x > 0) c.lf = sg[p - 1];
+            if (x < W - 1) c.rt = sg[p + 1];
+            c.l0 = lb[3 * p]; c.l1 = lb[3 * p + 1]; c.l2 = lb[3 * p + 2];
+            c.h0 = hv[3 * p]; c.h1 = hv[3 * p + 1]; c.h2 = hv[3 * p + 2];
+            c.gv = gr[p];
+        }
+        return c;
     };
-    auto load_seg_row = [&](int y) {                                // labels of image row y (or -1 outside) into its slot
-        int32_t* dst = s_seg + (size_t)((y + 3) % 3) * Wu;
-        if (y >= 0 && y < H) dma_row(sg + (size_t)y * W + ux0, dst, Wu);
-        else for (int i = lane; i < Wu; i += 64) dst[i] = -1;
-    };
-    StatsAcc a;
-    if (uy1 > uy0 && Wu > 0) {
-        load_seg_row(uy0 - 1);
-        load_seg_row(uy0);
-        for (int y = uy0; y < uy1; ++y) {
-            load_seg_row(y + 1);
-            const size_t row = (size_t)y * W + ux0;
-            dma_row(lb + 3 * row, s_lab, 3 * Wu);
-            dma_row(hv + 3 * row, s_hsv, 3 * Wu);
-            dma_row(gr + row, s_grd, Wu);
-            const double yf = (double)((float)y / (float)H), yd = (double)y / (double)H;
-            __builtin_amdgcn_s_waitcnt(0);                          // every DMA piece of this row has landed
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            for (int i = lane; i < Wu; i += 64) s_gn[i] = s_grd[i] / gden;
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            if (live && y >= bb.x && y < bb.y) {
-                const int32_t* cur = s_seg + (size_t)((y + 3) % 3) * Wu;
-                const int32_t* up = s_seg + (size_t)((y + 2) % 3) * Wu;
-                const int32_t* dn = s_seg + (size_t)((y + 4) % 3) * Wu;
-                for (int x = bb.z; x < bb.w; ++x) {
-                    const int i = x - ux0;
-                    if (cur[i] != r) continue;
-                    a.cnt += 1.0;
-#pragma unroll
-                    for (int c = 0; c < 3; ++c) {
-                        const float v = s_lab[3 * i + c];
-                        a.sl[c] += (double)v;
-                        a.sl2[c] += (double)(v * v);
-                        a.sh[c] += (double)s_hsv[3 * i + c];
-                    }
-                    a.sy += yf;
-                    a.sx += (double)s_xf[i];
-                    a.syd += yd;
-                    a.sxd += s_xd[i];
-                    // find_boundaries(mode="inner"): 4-neighbourhood max != min, and label != 0
-                    int mx = r, mn = r;
-                    if (y > 0) { const int u = up[i]; mx = max(mx, u); mn = min(mn, u); }
-                    if (y < H - 1) { const int u = dn[i]; mx = max(mx, u); mn = min(mn, u); }
-                    // the left / right neighbours can lie just outside the staged columns: read those from memory
-                    if (x > 0) { const int u = i > 0 ? cur[i - 1] : sg[(size_t)y * W + x - 1]; mx = max(mx, u); mn = min(mn, u); }
-                    if (x < W - 1) { const int u = i + 1 < Wu ? cur[i + 1] : sg[(size_t)y * W + x + 1]; mx = max(mx, u); mn = min(mn, u); }
-                    if (mx != mn && r != 0) a.sb += 1.0;
-                    a.sg1 += (double)s_grd[i];
-                    a.sgn += (double)s_gn[i];
-                }
+
+    double acc = 0.0, rowq = 0.0;         // rowq: (float)y/H (lane 9) or (double)y/H of row y_q
+    int cnt = 0, nb = 0, y_q = -1;        // cnt, nb: sums of 1.0, exact in any order
+    int y_n = ya, xc_n = xa;              // the chunk being fetched
+    bool act_n = boxed;
+    Chunk nxt = fetch(y_n, xc_n, act_n);
+    while (__any(act_n)) {
+        const Chunk c = nxt;
+        const int y = y_n, xc = xc_n, x = xc + li;
+        const bool active = act_n;
+        if (act_n) {
+            xc_n += SG;
+            if (xc_n >= bb.w) { xc_n = xa; ++y_n; act_n = y_n < bb.y; }
+        }
+        nxt = fetch(y_n, xc_n, act_n);
+        const bool mem = active && c.lbl == r;                       // r >= 0, lanes outside the box hold -1
+        const unsigned long long bal = __ballot(mem);
+        if (bal) {
+            const uint32_t gm = (uint32_t)(bal >> (g * SG)) & ((1u << SG) - 1u);
+            const int kc = min((xc - xa) / SG, SG_COLS / SG);
+            if (active && y != y_q) { y_q = y; rowq = li == 9 ? (double)((float)y / (float)H) : (double)y / (double)H; }
+            bool bnd = false;
+            if (mem) {
+                // find_boundaries(mode="inner"): 4-neighbourhood max != min, and label != 0; no neighbour outside the image
+                int mx = r, mn = r;
+                if (y > 0) { mx = max(mx, c.up); mn = min(mn, c.up); }
+                if (y < H - 1) { mx = max(mx, c.dn); mn = min(mn, c.dn); }
+                if (x > 0) { mx = max(mx, c.lf); mn = min(mn, c.lf); }
+                if (x < W - 1) { mx = max(mx, c.rt); mn = min(mn, c.rt); }
+                bnd = mx != mn && r != 0;
+                s_f[0 * 64 + lane] = c.l0; s_f[1 * 64 + lane] = c.l1; s_f[2 * 64 + lane] = c.l2;
+                s_f[3 * 64 + lane] = c.h0; s_f[4 * 64 + lane] = c.h1; s_f[5 * 64 + lane] = c.h2;
+                s_f[6 * 64 + lane] = c.gv;
+                s_f[7 * 64 + lane] = c.gv / gden;
+                s_f[8 * 64 + lane] = (float)x / (float)W;
+                if (kc == SG_COLS / SG) s_d[g * SG_TAB + SG_COLS + li] = (double)x / (double)W;   // beyond the table: spill slot
             }
-            __builtin_amdgcn_wave_barrier();       // everyone is done with this row before its buffers are overwritten
+            cnt += __popc(gm);
+            nb += __popc((uint32_t)(__ballot(bnd) >> (g * SG)) & ((1u << SG) - 1u));
+            stats_lds_sync();
+            const int doff = g * SG_TAB + kc * SG;
+            // members of the chunk in ascending x: every lane of the group adds its own addend, so each accumulator sees
+            // the region's pixels in raster order
+            for (uint32_t m = gm; m; m &= m - 1) {
+                const int bit = __ffs(m) - 1;
+                const float v = s_f[fbase + bit];
+                const double dv = s_d[doff + bit];
+                acc += is_row ? rowq : is_d ? dv : (double)(sq ? v * v : v);
+            }
+            stats_lds_sync();             // the chunk's values are consumed before the next chunk overwrites them
         }
     }
-    if (!live) return;
+
+    double a[SG];
+#pragma unroll
+    for (int j = 0; j < SG - 1; ++j) a[j] = __shfl(acc, g * SG + j, 64);
+    if (!live || li != 0) return;
     RegionStats s;
-    s.cnt = (float)a.cnt;
+    s.cnt = (float)(double)cnt;
     s.safe = s.cnt > 1.0f ? s.cnt : 1.0f;
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
-        const float m = (float)a.sl[c] / s.safe;
-        const float sq = (float)a.sl2[c] / s.safe;
-        float v = sq - m * m;
+        const float m = (float)a[c] / s.safe;
+        const float sq2 = (float)a[3 + c] / s.safe;
+        float v = sq2 - m * m;
         if (!(v > 0.0f)) v = (v != v) ? v : 0.0f;
         s.mlab[c] = m; s.slab[c] = sqrtf(v);
-        s.mhsv[c] = (float)a.sh[c] / s.safe;
+        s.mhsv[c] = (float)a[6 + c] / s.safe;
     }
-    s.cy = (float)a.sy / s.safe; s.cx = (float)a.sx / s.safe;
-    s.pcy = (float)(a.syd / (double)s.safe); s.pcx = (float)(a.sxd / (double)s.safe);
-    s.bpx = (float)a.sb;
-    s.mgrad = (float)a.sg1 / s.safe;
-    s.mgn = (float)a.sgn / s.safe;
+    s.cy = (float)a[9] / s.safe; s.cx = (float)a[10] / s.safe;
+    s.pcy = (float)(a[11] / (double)s.safe); s.pcx = (float)(a[12] / (double)s.safe);
+    s.bpx = (float)(double)nb;
+    s.mgrad = (float)a[13] / s.safe;
+    s.mgn = (float)a[14] / s.safe;
     s.area = s.cnt / (float)((double)H * (double)W);
     s.border = (float)border[(size_t)b * d.Nmax + r];
     out[(size_t)b * d.Nmax + r] = s;
@@ -699,16 +722,7 @@ extern "C" int ggc_graph_count(ggc_ctx* ctx, ggc_stream stream, int B, int H, in
     hipLaunchKernelGGL(k_bbox, dim3(cdiv(W, 64), cdiv(H, BBOX_ROWS), B), dim3(256), 0, st, d, segments, grad, bbox, border, gmax);
     {
         ProfScope prof(ctx, st, "graph_stats");
-        const size_t stats_lds = ((size_t)W * 15 + 2) * sizeof(float);  // 3 label rows, lab, hsv, grad, grad/max, x/W as f32 and f64
-        static std::atomic<int> stats_lds_dev[64];                      // largest size set so far, per device
-        std::atomic<int>& stats_lds_set = stats_lds_dev[ctx->device & 63];
-        if ((int)stats_lds > 48 * 1024 && stats_lds_set.load(std::memory_order_acquire) < (int)stats_lds) {
-            GGC_REQUIRE(ctx, stats_lds <= 160 * 1024, GGC_E_UNSUPPORTED, "image width %d too large for the statistics kernel", W);
-            GGC_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_stats), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                             (int)stats_lds));
-            stats_lds_set.store((int)stats_lds, std::memory_order_release);
-        }
-        hipLaunchKernelGGL(k_stats, dim3(cdiv(Nmax, 64), B), dim3(64), stats_lds, st, d, segments, n_nodes, lab, hsv, grad,
+        hipLaunchKernelGGL(k_stats, dim3(cdiv(Nmax, SG_REGIONS), B), dim3(64), 0, st, d, segments, n_nodes, lab, hsv, grad,
                            bbox, border, gmax, stats);
     }
     hipLaunchKernelGGL(k_adj, pix, dim3(256), 0, st, d, segments, dense);

@@ -8,7 +8,12 @@
 //   k_init_centers  regular-grid seeds, colour part 0
 //   10 x k_slic_assign, with k_slic_update between two assignments (9 x): the
 //                   update skimage runs after the tenth assignment feeds nothing
-//   k_connectivity  skimage's raster-order connectivity enforcement
+//   k_cn_*          skimage's raster-order connectivity enforcement, as a union-find
+//                   CCL (k_cn_reset, k_cn_merge, k_cn_size, k_cn_settle; k_cn_carve and
+//                   another round while a component reaches max_size), the discovery
+//                   ranks (k_cn_kept, k_cn_scan), the replay of the components below
+//                   min_size (k_cn_small) and the label write (k_cn_write);
+//                   k_connectivity_seq is the literal one-thread-per-image replay
 //
 // Bit-exactness with the CPU path (integer label map) dictates the structure:
 //  * assignment is pixel-centric (no atomics): a 32x8 pixel tile gathers, in
