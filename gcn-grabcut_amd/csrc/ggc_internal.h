@@ -36,6 +36,7 @@ enum Slot : int {
     S_FULLCUT,
     S_GEODESIC,
     S_STROKES,
+    S_POLYGONS,
     S_COUNT
 };
 

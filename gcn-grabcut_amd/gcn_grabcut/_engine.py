@@ -264,6 +264,23 @@ class Engine:
             self.ctx.call("ggc_stroke_pixels", *args, hints.data_ptr(), n)
         return hints, hint_ptr
 
+    # ------------------------------------------------------------------ H3
+    def upload_polygons(self, verts, poly_ptr, poly_label, image_ptr):
+        """pack_polygons' (verts [V,2], poly_ptr [P+1], poly_label [P], image_ptr [B+1]) -> the same four arrays on the
+        device, in one host-to-device copy."""
+        parts = [np.asarray(a, np.int32).ravel() for a in (image_ptr, poly_ptr, poly_label, verts)]
+        d = self.to_device(np.concatenate(parts))
+        o = np.cumsum([0] + [a.size for a in parts])
+        return d[o[3]:o[4]].view(-1, 2), d[o[1]:o[2]], d[o[2]:o[3]], d[o[0]:o[1]]
+
+    def apply_polygons(self, mask, verts, poly_ptr, poly_label, image_ptr):
+        """Lassos and filled polygons as hard constraints, in place on mask (B,H,W) uint8 (ggc_apply_polygons): the four
+        arrays of upload_polygons, on the device."""
+        b, h, w = mask.shape
+        self.ctx.call("ggc_apply_polygons", self._stream(), b, h, w, _native.ptr(verts), poly_ptr.data_ptr(),
+                      _native.ptr(poly_label), image_ptr.data_ptr(), int(poly_label.numel()), mask.data_ptr())
+        return mask
+
     def next_click(self, pred, gt) -> torch.Tensor:
         """The next simulated click of the NoC protocol per image (ggc_next_click): pred, gt (B,H,W) uint8, nonzero =
         foreground -> (B,4) int32 on the device = row, col, label (1 = fg, 0 = bg), d2; (-1,-1,-1,0) where pred == gt."""

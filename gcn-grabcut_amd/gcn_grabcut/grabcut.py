@@ -48,6 +48,7 @@ class GrabCut:
     gc = GrabCut(image)
     mask = gc.run_with_bbox((x, y, w, h))    # classical mode
     mask = gc.run_with_trimap(trimap)        # GCN-guided mode
+    mask = gc.run_with_lasso(polygon)        # classical mode from a closed outline (additive)
     gc.add_hints(fg_points=[(r, c)])         # user clicks as definite labels (additive) ...
     mask = gc.refine(2)                      # ... then GC_EVAL from the edited mask
     """
@@ -112,6 +113,23 @@ class GrabCut:
         self._snapshot("trimap_degenerate" if degenerate else "trimap_init")
         return out
 
+    def lasso_trimap(self, polygon) -> np.ndarray:
+        """Additive: the start mask of run_with_lasso, GC_PR_FGD inside the lasso (one polygon of (row, col) vertices or a
+        sequence of polygons, their union; boundary included) and GC_BGD outside (ggc_apply_polygons)."""
+        from .graph_builder import pack_polygons, lasso_list
+        lassos = lasso_list(polygon)
+        if not lassos:
+            raise ValueError("a lasso needs at least one polygon")
+        eng = self._eng
+        h, w = self.image.shape[:2]
+        start = eng.to_device(np.full((1, h, w), Label.FG_PROBABLE, np.uint8))
+        return eng.apply_polygons(start, *eng.upload_polygons(*pack_polygons([((), (), lassos)])))[0].cpu().numpy()
+
+    def run_with_lasso(self, polygon) -> np.ndarray:
+        """Additive: classical GrabCut from a lasso, the polygon sibling of run_with_bbox: lasso_trimap(polygon), then
+        run_with_trimap (so the promotion of probable labels and the single-class guard apply)."""
+        return self.run_with_trimap(self.lasso_trimap(polygon))
+
     def refine(self, extra_iter: int = 3) -> np.ndarray:
         """Continue from the current GMM state (GC_EVAL) — reference grabcut.py:153-163."""
         if self.mask is None:
@@ -175,6 +193,24 @@ class GrabCut:
                 eng.apply_strokes(self._dmask, d_segs, d_ptr, radius)
             self.mask = self._dmask[0].cpu().numpy()
         self._snapshot("strokes")
+        return self._binary()
+
+    def add_polygons(self, fg_polygons=(), bg_polygons=(), lasso=None) -> np.ndarray:
+        """Additive: paint filled polygons and lassos into the current mask (ggc_apply_polygons): every pixel outside all
+        lassos (one polygon or a sequence of them) becomes GC_BGD, then every pixel a fill covers GC_FGD / GC_BGD,
+        background fills winning where the two overlap.  The edit runs on the mask the last run left on the device; the
+        GMMs are kept, so refine(n) continues from the edited mask, as after add_strokes."""
+        if self.mask is None:
+            raise RuntimeError("Call run_with_bbox or run_with_trimap first.")
+        from .graph_builder import pack_polygons, lasso_list
+        packed = pack_polygons([(fg_polygons, bg_polygons, lasso_list(lasso))])
+        eng = self._eng
+        if self._dmask is None or not self.history or not np.array_equal(self.mask, self.history[-1].mask_copy):
+            self._dmask = eng.to_device(np.ascontiguousarray(self.mask, dtype=np.uint8)[None])   # the host mask was edited
+        if len(packed[2]):
+            eng.apply_polygons(self._dmask, *eng.upload_polygons(*packed))
+            self.mask = self._dmask[0].cpu().numpy()
+        self._snapshot("polygons")
         return self._binary()
 
     def _binary(self) -> np.ndarray:

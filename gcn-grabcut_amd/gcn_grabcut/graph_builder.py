@@ -310,3 +310,73 @@ def pack_strokes(per_image) -> "tuple[np.ndarray, np.ndarray]":
         raise ValueError(f"{ptr[-1]} stroke segments: too many for one call")
     seg = np.concatenate(rows).astype(np.int32) if rows else np.zeros((0, 5), np.int32)
     return np.ascontiguousarray(seg.reshape(-1, 5)), np.asarray(ptr, np.int32)
+
+
+POLYGON_MAX_COORD = 1 << 20         # ggc_apply_polygons' limit on a vertex coordinate
+POLYGON_BG, POLYGON_FG, POLYGON_LASSO = 0, 1, 2
+
+
+def _is_polygon(obj) -> bool:
+    """True for one polygon, a sequence of (row, col) pairs; False for a sequence of polygons (or anything else)."""
+    try:
+        a = np.asarray(obj, dtype=np.float64)
+    except (TypeError, ValueError):
+        return False
+    return a.ndim == 2 and a.shape[1] == 2
+
+
+def lasso_list(lasso) -> list:
+    """The `lasso` argument of the public calls, one polygon or a sequence of polygons (or None) -> a list of polygons."""
+    if lasso is None:
+        return []
+    if isinstance(lasso, (str, bytes)):
+        raise ValueError("lasso must be a polygon, a sequence of (row, col) vertices, or a sequence of polygons")
+    return [lasso] if _is_polygon(lasso) else list(lasso)
+
+
+def _polygon_rows(polygons, what: str) -> "list[np.ndarray]":
+    """The polygons of one label -> their vertices, one int64 [n,2] array each."""
+    if polygons is None:
+        return []
+    if isinstance(polygons, (str, bytes)):
+        raise ValueError(f"{what} must be a sequence of polygons, each a sequence of (row, col) vertices")
+    out = []
+    for i, poly in enumerate(polygons):
+        if isinstance(poly, (str, bytes)):
+            raise ValueError(f"{what}[{i}] must be a sequence of (row, col) vertices")
+        v = _click_rows(poly, 0, f"{what}[{i}]")[:, :2]
+        if len(v) < 3:
+            raise ValueError(f"{what}[{i}] has {len(v)} vertices: a polygon has at least 3")
+        if (np.abs(v) > POLYGON_MAX_COORD).any():
+            raise ValueError(f"{what}[{i}] holds a coordinate beyond +-2^20")
+        out.append(v)
+    return out
+
+
+def pack_polygons(per_image) -> "tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]":
+    """Per-image polygons -> the (verts, poly_ptr, poly_label, image_ptr) arrays of ggc_apply_polygons; the sibling of
+    pack_strokes.
+
+    per_image: one entry per image, None (no polygons) or (fg_polygons, bg_polygons, lassos), each a sequence of polygons,
+    a polygon being a sequence of n >= 3 (row, col) vertices, closed implicitly from the last to the first.  Returns verts
+    int32 [V,2], poly_ptr int32 [P+1], poly_label int32 [P] (0 = background fill, 1 = foreground fill, 2 = lasso) and
+    image_ptr int32 [B+1].  An image's lassos come first, then its foreground fills, then its background fills, each in
+    the order given, so background wins where fills overlap, as with clicks and strokes.  Vertices outside the image are
+    kept.  A polygon of fewer than 3 vertices, a wrong shape or a coordinate beyond +-2^20 is a ValueError."""
+    verts, poly_ptr, labels, image_ptr = [], [0], [], [0]
+    for b, entry in enumerate(per_image):
+        if entry is not None:
+            if isinstance(entry, (str, bytes)) or not hasattr(entry, "__len__") or len(entry) != 3:
+                raise ValueError(f"polygons[{b}] must be None or a (fg_polygons, bg_polygons, lassos) triple")
+            for polys, label, what in ((entry[2], POLYGON_LASSO, "lassos"), (entry[0], POLYGON_FG, "foreground polygons"),
+                                       (entry[1], POLYGON_BG, "background polygons")):
+                for v in _polygon_rows(polys, f"polygons[{b}] {what}"):
+                    verts.append(v)
+                    poly_ptr.append(poly_ptr[-1] + len(v))
+                    labels.append(label)
+        image_ptr.append(len(labels))
+    if poly_ptr[-1] > np.iinfo(np.int32).max // 2:
+        raise ValueError(f"{poly_ptr[-1]} polygon vertices: too many for one call")
+    v = np.concatenate(verts).astype(np.int32) if verts else np.zeros((0, 2), np.int32)
+    return (np.ascontiguousarray(v.reshape(-1, 2)), np.asarray(poly_ptr, np.int32), np.asarray(labels, np.int32),
+            np.asarray(image_ptr, np.int32))

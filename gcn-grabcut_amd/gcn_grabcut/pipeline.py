@@ -20,7 +20,8 @@ from typing import Optional, Sequence
 import numpy as np
 
 from .grabcut import GrabCut, GrabCutConfig, Label
-from .graph_builder import GraphBuilder, SuperpixelGraphConfig, graphs_to_host, _check_image, pack_hints, pack_strokes
+from .graph_builder import (GraphBuilder, SuperpixelGraphConfig, graphs_to_host, _check_image, pack_hints, pack_strokes,
+                            pack_polygons, lasso_list)
 from .metrics import evaluate, evaluate_matte, evaluate_trimap, MatteMetrics, SegmentationMetrics, TrimapMetrics
 from .model import CLASS_BG, CLASS_FG, project_to_pixels  # noqa: F401
 
@@ -522,6 +523,19 @@ def _check_stroke_radius(radius, what: str = "stroke_radius") -> int:
     return int(radius)
 
 
+def _mask_or_shape(mask_or_shape, what: str) -> np.ndarray:
+    """An (H, W) uint8 label mask, or for an (H, W) shape a mask that is all probable background (2)."""
+    if isinstance(mask_or_shape, (tuple, list)) and len(mask_or_shape) == 2 and all(isinstance(v, (int, np.integer)) for v in mask_or_shape):
+        h, w = (int(v) for v in mask_or_shape)
+        if h < 1 or w < 1:
+            raise ValueError(f"{what}: bad shape {(h, w)}")
+        return np.full((h, w), 2, np.uint8)
+    m = np.ascontiguousarray(mask_or_shape, np.uint8)
+    if m.ndim != 2 or m.size == 0:
+        raise ValueError(f"{what}: the mask must be (H, W), got {m.shape}")
+    return m
+
+
 def paint_strokes(mask_or_shape, fg_strokes, bg_strokes, radius: int = 3, device="cuda") -> np.ndarray:
     """Brush strokes painted into a GrabCut label mask (additive; ggc_apply_strokes).  mask_or_shape: an
     (H, W) uint8 mask of GrabCut labels, or an (H, W) shape for a mask that starts all probable background (2).
@@ -531,15 +545,7 @@ def paint_strokes(mask_or_shape, fg_strokes, bg_strokes, radius: int = 3, device
     mask (a copy)."""
     from ._engine import get_engine
     radius = _check_stroke_radius(radius, "radius")
-    if isinstance(mask_or_shape, (tuple, list)) and len(mask_or_shape) == 2 and all(isinstance(v, (int, np.integer)) for v in mask_or_shape):
-        h, w = (int(v) for v in mask_or_shape)
-        if h < 1 or w < 1:
-            raise ValueError(f"paint_strokes: bad shape {(h, w)}")
-        m = np.full((h, w), 2, np.uint8)
-    else:
-        m = np.ascontiguousarray(mask_or_shape, np.uint8)
-        if m.ndim != 2 or m.size == 0:
-            raise ValueError(f"paint_strokes: the mask must be (H, W), got {m.shape}")
+    m = _mask_or_shape(mask_or_shape, "paint_strokes")
     segs, ptr = pack_strokes([(fg_strokes, bg_strokes)])
     if ptr[-1] == 0:
         return m.copy()
@@ -562,6 +568,32 @@ def stroke_pixels(shape, fg_strokes, bg_strokes, device="cuda") -> np.ndarray:
     eng = get_engine(device)
     d_segs, d_ptr = eng.upload_strokes(segs, ptr)
     return eng.stroke_pixels((1, h, w), d_segs, d_ptr)[0].cpu().numpy()
+
+
+def paint_polygons(mask_or_shape, fg_polygons=(), bg_polygons=(), lasso=None, device="cuda") -> np.ndarray:
+    """Filled polygons and lassos painted into a GrabCut label mask (additive; ggc_apply_polygons).
+    mask_or_shape: an (H, W) uint8 mask of GrabCut labels, or an (H, W) shape for a mask that starts all probable
+    background (2).  fg_polygons / bg_polygons: sequences of polygons, each a sequence of n >= 3 (row, col) vertices,
+    closed implicitly; lasso: one polygon or a sequence of them.  First every pixel outside all lassos (if any is given)
+    becomes definite background (0); then every pixel a fill covers becomes definite foreground (1) / background (0),
+    background winning where the two overlap.  Covered is the even-odd rule with the boundary included; vertices may lie
+    outside the image.  -> the painted (H, W) uint8 mask (a copy)."""
+    from ._engine import get_engine
+    m = _mask_or_shape(mask_or_shape, "paint_polygons")
+    packed = pack_polygons([(fg_polygons, bg_polygons, lasso_list(lasso))])
+    if len(packed[2]) == 0:
+        return m.copy()
+    eng = get_engine(device)
+    return eng.apply_polygons(eng.to_device(m[None]), *eng.upload_polygons(*packed))[0].cpu().numpy()
+
+
+def polygon_mask(shape, polygon, device="cuda") -> np.ndarray:
+    """The pixels of an (H, W) image that a polygon COVERS (additive; ggc_apply_polygons' rule, include/ggc.h H3: on an
+    edge, or an odd crossing number) as a uint8 mask, 1 = covered."""
+    h, w = (int(v) for v in shape)
+    if h < 1 or w < 1:
+        raise ValueError(f"polygon_mask: bad shape {(h, w)}")
+    return paint_polygons(np.zeros((h, w), np.uint8), [polygon], device=device)
 
 
 def lift_labels(mask: np.ndarray, full_shape, band: Optional[int] = None, device="cuda") -> np.ndarray:
@@ -719,8 +751,8 @@ def _colour_trimap(trimap: np.ndarray) -> np.ndarray:
 
 @dataclass
 class _Hints:
-    """The clicks of a batch in ggc_apply_hints' packing and its brush strokes in ggc_apply_strokes', on the host, and how
-    they are applied."""
+    """The clicks of a batch in ggc_apply_hints' packing, its brush strokes in ggc_apply_strokes' and its polygons in
+    ggc_apply_polygons', on the host, and how they are applied."""
     rows: np.ndarray           # (K,3) int32 = row, col, label (1 = foreground)
     ptr: np.ndarray            # (B+1,) int32
     radius: int
@@ -730,6 +762,28 @@ class _Hints:
     segs: Optional[np.ndarray] = None              # (S,5) int32 = r0, c0, r1, c1, label; None: the batch has no stroke
     seg_ptr: Optional[np.ndarray] = None           # (B+1,) int32
     stroke_radius: int = 3
+    polys: Optional[tuple] = None                  # (verts, poly_ptr, poly_label, image_ptr) int32; None: the batch has no polygon
+
+    @staticmethod
+    def _polygons_of(polygons, b: int):
+        """polygons: one None or (fg_polygons, bg_polygons, lassos) per image, or a packed (verts, poly_ptr, poly_label,
+        image_ptr) tuple -> that tuple on the host, None when no image has a polygon."""
+        if polygons is None:
+            return None
+        if isinstance(polygons, tuple) and len(polygons) == 4 and all(hasattr(a, "shape") for a in polygons):
+            verts, pp, pl, ip = (np.asarray(a.cpu() if hasattr(a, "cpu") else a) for a in polygons)
+            verts = verts.reshape(-1, 2) if verts.size else np.zeros((0, 2), np.int32)
+            if ip.shape != (b + 1,) or ip[0] != 0 or (np.diff(ip) < 0).any() or ip[-1] != len(pl) or pp.shape != (len(pl) + 1,) \
+                    or pp[0] != 0 or (np.diff(pp) < 3).any() or pp[-1] != len(verts):
+                raise ValueError(f"packed polygons: image_ptr must be a non-decreasing ({b + 1},) array from 0 to P, and "
+                                 f"poly_ptr a (P+1,) array from 0 to {len(verts)} in steps of at least 3")
+        else:
+            if len(polygons) != b:
+                raise ValueError(f"polygons has {len(polygons)} entries for a batch of {b} images")
+            verts, pp, pl, ip = pack_polygons(polygons)
+        if len(pl) == 0:
+            return None
+        return tuple(np.ascontiguousarray(a, np.int32) for a in (verts, pp, pl, ip))
 
     @staticmethod
     def _strokes_of(strokes, b: int):
@@ -751,13 +805,19 @@ class _Hints:
         return np.ascontiguousarray(segs, np.int32), np.ascontiguousarray(ptr, np.int32)
 
     @staticmethod
-    def of(hints, b: int, radius, region, as_prior, geodesic=None, strokes=None, stroke_radius=3) -> "Optional[_Hints]":
+    def of(hints, b: int, radius, region, as_prior, geodesic=None, strokes=None, stroke_radius=3,
+           polygons=None) -> "Optional[_Hints]":
         """hints: one None or (fg_points, bg_points) per image, or an already packed (hints, hint_ptr) pair; strokes: the
         same for brush strokes ((fg_strokes, bg_strokes) per image, or a packed (strokes, stroke_ptr) pair).
         None when no image has a click or a stroke, so that such a call launches exactly what a call without them
-        launches; a batch without strokes has segs None and launches exactly what it did before strokes existed."""
+        launches; a batch without strokes has segs None and launches exactly what it did before strokes existed.
+        polygons: one None or (fg_polygons, bg_polygons, lassos) per image, or a packed 4-tuple (pack_polygons); a batch
+        without polygons has polys None and launches exactly what it did before polygons existed."""
         geodesic = _geodesic_args(geodesic, region)
         segs, seg_ptr = _Hints._strokes_of(strokes, b)
+        polys = _Hints._polygons_of(polygons, b)
+        if polys is not None and hints is None:
+            hints = (np.zeros((0, 3), np.int32), np.zeros(b + 1, np.int32))
         if segs is not None:
             stroke_radius = _check_stroke_radius(stroke_radius)
             if hints is None:
@@ -775,10 +835,10 @@ class _Hints:
             if len(hints) != b:
                 raise ValueError(f"hints has {len(hints)} entries for a batch of {b} images")
             rows, ptr = pack_hints(hints)
-        if ptr[-1] == 0 and segs is None:
+        if ptr[-1] == 0 and segs is None and polys is None:
             return None
         return _Hints(np.ascontiguousarray(rows, np.int32), np.ascontiguousarray(ptr, np.int32), int(radius), bool(region),
-                      bool(as_prior), geodesic, segs, seg_ptr, int(stroke_radius) if segs is not None else 3)
+                      bool(as_prior), geodesic, segs, seg_ptr, int(stroke_radius) if segs is not None else 3, polys)
 
     def chunk(self, lo: int, hi: int) -> "Optional[_Hints]":
         k0, k1 = int(self.ptr[lo]), int(self.ptr[hi])
@@ -786,10 +846,22 @@ class _Hints:
         if self.segs is not None and self.seg_ptr[hi] > self.seg_ptr[lo]:      # strokes are sliced by stroke_ptr, as clicks by hint_ptr
             s0, s1 = int(self.seg_ptr[lo]), int(self.seg_ptr[hi])
             segs, seg_ptr = self.segs[s0:s1], self.seg_ptr[lo:hi + 1] - s0
-        if k1 == k0 and segs is None:
+        polys = None
+        if self.polys is not None and self.polys[3][hi] > self.polys[3][lo]:    # polygons are sliced by image_ptr, their vertices by poly_ptr
+            verts, pp, pl, ip = self.polys
+            q0, q1 = int(ip[lo]), int(ip[hi])
+            v0, v1 = int(pp[q0]), int(pp[q1])
+            polys = (verts[v0:v1], pp[q0:q1 + 1] - v0, pl[q0:q1], ip[lo:hi + 1] - q0)
+        if k1 == k0 and segs is None and polys is None:
             return None
         return _Hints(self.rows[k0:k1], self.ptr[lo:hi + 1] - k0, self.radius, self.region, self.as_prior, self.geodesic,
-                      segs, seg_ptr, self.stroke_radius)
+                      segs, seg_ptr, self.stroke_radius, polys)
+
+    @property
+    def has_clicks(self) -> bool:
+        """The batch has a click or a stroke: what the click paths (disks, regions, prior columns, geodesic) work on.
+        Polygons are areas and feed none of them."""
+        return len(self.rows) > 0 or self.segs is not None
 
     def clicked_images(self, h: int, w: int) -> np.ndarray:
         """(B,) bool: the images with at least one click inside the frame."""
@@ -1097,7 +1169,9 @@ class GCNGrabCutPipeline:
     # ------------------------------------------------------------ batched, device resident
     def _front(self, eng, bgr, threshold_fg, threshold_bg, edge_aware, filter_radius, tick=None, timing=None, hints=None):
         """Stages 1-3 on the current stream: colour prep, SLIC, graph, network, trimap, seeding, then the user's clicks
-        (hints: a _Hints or None).  -> (seg, graphs, probs, trimap)"""
+        (hints: a _Hints or None).  Polygons (ggc_apply_polygons) are painted after the seeding and before strokes and
+        clicks, so a stroke or click inside an excluded area still wins, being the more specific edit; they are areas,
+        not clicks, and do not feed hint_region, hints_as_prior or the geodesic sources.  -> (seg, graphs, probs, trimap)"""
         cfg = self.sp_config
         t = tick() if tick else 0.0
         lab, hsv, gray, grad = eng.preprocess(bgr)
@@ -1111,6 +1185,9 @@ class GCNGrabCutPipeline:
         if self.model.training:
             self.model.eval()
         prior = graphs.x[:, 16:19]
+        polys = None if hints is None else hints.polys
+        if hints is not None and not hints.has_clicks:     # polygons only: the click paths launch nothing
+            hints = None
         if hints is not None:
             hint_rows, hint_ptr = eng.upload_hints(hints.rows, hints.ptr)
             all_rows, all_ptr, clicked = hint_rows, hint_ptr, None     # what the superpixels, the prior and the geodesic see
@@ -1126,6 +1203,8 @@ class GCNGrabCutPipeline:
         if timing is not None:
             timing["gcn_inference"] = tick() - t
         trimap = eng.seed_from_prior(trimap, prior, graphs.node_ptr, seg, 0.1)
+        if polys is not None:                  # areas first: lassos, then fills; strokes and clicks are painted over them
+            eng.apply_polygons(trimap, *eng.upload_polygons(*polys))
         if hints is not None and hints.geodesic is not None:   # the guide is the caller's BGR batch, never gc_image
             eng.geodesic_hints(bgr, all_rows, all_ptr, hints.geodesic.radius, hints.geodesic.gamma, mask=trimap)
         elif hints is not None and hints.segs is None:   # hard constraints: over the network's trimap and the seeding alike
@@ -1208,7 +1287,8 @@ class GCNGrabCutPipeline:
                              chunks: Optional[int] = None, hints=None, hint_radius: int = 5, hint_region: bool = False,
                              hints_as_prior: bool = False, return_state: bool = False, matte: bool = False,
                              matte_radius: int = MATTE_RADIUS, matte_eps: float = MATTE_EPS, full_bgr=None,
-                             foreground=False, full_cut=False, geodesic=False, strokes=None, stroke_radius: int = 3) -> dict:
+                             foreground=False, full_cut=False, geodesic=False, strokes=None, stroke_radius: int = 3,
+                             polygons=None) -> dict:
         """bgr: (B,H,W,3) uint8 tensor on the pipeline's device.  Returns device tensors.
 
         matte=True (additive) also returns "alpha" (B,H,W) float32, the soft matte of the cleaned mask (alpha_matte with
@@ -1259,6 +1339,16 @@ class GCNGrabCutPipeline:
         ignored, as hint_radius is.  A batch without strokes launches exactly what it did before, and an image without
         strokes in a stroked batch gets the outputs it gets without them, bit for bit.
 
+        Lassos and filled polygons (additive): polygons is None, a list with one None or (fg_polygons,
+        bg_polygons, lassos) per image (each a sequence of polygons, a polygon a sequence of n >= 3 (row, col) vertices,
+        closed implicitly), or a packed (verts, poly_ptr, poly_label, image_ptr) tuple (graph_builder.pack_polygons).  On
+        the trimap GrabCut starts from, every pixel outside all of an image's lassos becomes definite background, then
+        every pixel a fill covers definite foreground / background (ggc_apply_polygons: even-odd rule, boundary included,
+        the later fill winning, background fills after foreground ones); strokes and clicks are painted afterwards, so
+        one inside an excluded area still wins.  Polygons are areas, not clicks: they do not feed hint_region,
+        hints_as_prior or the geodesic sources.  A batch without polygons launches exactly what it did before, and an
+        image without polygons in a batch that has some gets the outputs it gets without them, bit for bit.
+
         Large batches run as a software pipeline (additive, same results): the batch is cut into `chunks` contiguous
         chunks; the front stages of chunk k+1 run on the caller's stream while the GrabCut / clean-up of chunk k runs on a
         lane of its own (private context, stream and host thread).  Images are independent and image b keeps seed + b, so
@@ -1268,7 +1358,7 @@ class GCNGrabCutPipeline:
         b = bgr.size(0)
         want = self.grabcut_lanes if grabcut_lanes is None else int(grabcut_lanes)   # (an argument, so that concurrent callers do not mutate the pipeline)
         n_chunks = self.chunks if chunks is None else int(chunks)
-        hints = _Hints.of(hints, b, hint_radius, hint_region, hints_as_prior, geodesic, strokes, stroke_radius)
+        hints = _Hints.of(hints, b, hint_radius, hint_region, hints_as_prior, geodesic, strokes, stroke_radius, polygons)
         plan = _OutputPlan.of(self, bgr.shape, None if full_bgr is None else full_bgr.shape, compose=compose,
                               min_area_ratio=min_area_ratio, keep_largest=keep_largest, matte=matte, matte_radius=matte_radius,
                               matte_eps=matte_eps, foreground=foreground, full_cut=full_cut)
@@ -1408,11 +1498,12 @@ class GCNGrabCutPipeline:
             timing["wall"] = time.perf_counter() - t_host
         return out
 
-    def segment_batch(self, images: Sequence[np.ndarray], hints=None, full_images=None, strokes=None,
+    def segment_batch(self, images: Sequence[np.ndarray], hints=None, full_images=None, strokes=None, polygons=None,
                       **kwargs) -> list[SegmentationResult]:
         """Segment equally sized BGR images as one batch (additive API).  hints: one None or (fg_points, bg_points) per
         image, with hint_radius / hint_region / hints_as_prior / geodesic among kwargs (segment_batch_device).  strokes:
-        one None or (fg_strokes, bg_strokes) per image, with stroke_radius among kwargs (segment_batch_device).  full_images
+        one None or (fg_strokes, bg_strokes) per image, with stroke_radius among kwargs (segment_batch_device).  polygons:
+        one None or (fg_polygons, bg_polygons, lassos) per image (segment_batch_device).  full_images
         (additive): the same images at one larger size each, (H1, W1, 3) uint8 BGR; every result's `full` then holds the
         outputs at that size (segment_batch_device's full_bgr).  foreground=True | ForegroundColours(...) among kwargs
         (with a matte) fills every result's foreground and rgba_clean.  full_cut=True | FullCut(...) among kwargs (with
@@ -1439,6 +1530,8 @@ class GCNGrabCutPipeline:
         bgr = self._eng.to_device(np.stack(imgs))
         if strokes is not None:
             kwargs["strokes"] = strokes
+        if polygons is not None:
+            kwargs["polygons"] = polygons
         out = self.segment_batch_device(bgr, timing=timing, hints=hints, full_bgr=full_bgr, **kwargs)
         out.update({k: out[k].cpu() for k in _REFERENCE_FIELDS + _ADDITIVE_FIELDS if k in out})      # one copy per output, not one per image
         per_image = {k: v / len(imgs) for k, v in timing.items()}
@@ -1575,7 +1668,8 @@ class GCNGrabCutPipeline:
                 hint_region: bool = False, hints_as_prior: bool = False, matte: bool = False,
                 matte_radius: int = MATTE_RADIUS, matte_eps: float = MATTE_EPS,
                 full_image: Optional[np.ndarray] = None, foreground=False, full_cut=False,
-                geodesic=False, fg_strokes=None, bg_strokes=None, stroke_radius: int = 3) -> SegmentationResult:
+                geodesic=False, fg_strokes=None, bg_strokes=None, stroke_radius: int = 3,
+                lasso=None, fg_polygons=None, bg_polygons=None) -> SegmentationResult:
         """Full pipeline on one BGR image (reference pipeline.py:265-352).
 
         Additive: fg_points / bg_points are user clicks, (row, col) pairs, applied as hard constraints on the trimap
@@ -1589,7 +1683,10 @@ class GCNGrabCutPipeline:
         cut_mask_full of the cleaned mask (segment_batch_device); geodesic=True | GeodesicHints(...) paints the clicks by
         their geodesic distance on the image instead of disks (hint_radius is then ignored; segment_batch_device);
         fg_strokes / bg_strokes are brush strokes, sequences of polylines of (row, col) vertices, painted with
-        stroke_radius as hard constraints before the clicks (segment_batch_device's strokes)."""
+        stroke_radius as hard constraints before the clicks (segment_batch_device's strokes); lasso, one polygon or a
+        sequence of polygons of (row, col) vertices, makes everything outside all of them definite background, and
+        fg_polygons / bg_polygons are filled areas of definite labels, all before strokes and clicks
+        (segment_batch_device's polygons)."""
         image = _check_image(image)
         full = None if full_image is None else _check_image(full_image)
         _OutputPlan.of(self, (1, *image.shape), None if full is None else (1, *full.shape), min_area_ratio=min_area_ratio,
@@ -1601,12 +1698,14 @@ class GCNGrabCutPipeline:
             [(() if fg_points is None else fg_points, () if bg_points is None else bg_points)]
         strokes = None if fg_strokes is None and bg_strokes is None else \
             [(() if fg_strokes is None else fg_strokes, () if bg_strokes is None else bg_strokes)]
+        polygons = None if lasso is None and fg_polygons is None and bg_polygons is None else \
+            [(() if fg_polygons is None else fg_polygons, () if bg_polygons is None else bg_polygons, lasso_list(lasso))]
         out = self.segment_batch_device(self._eng.to_device(image[None]), threshold_fg, threshold_bg, refine_iters,
                                         min_area_ratio, keep_largest, edge_aware, filter_radius, timing=timing,
                                         hints=hints, hint_radius=hint_radius, hint_region=hint_region,
                                         hints_as_prior=hints_as_prior, matte=matte, matte_radius=matte_radius,
                                         matte_eps=matte_eps, full_bgr=full_bgr, foreground=foreground, full_cut=full_cut,
-                                        geodesic=geodesic, strokes=strokes, stroke_radius=stroke_radius)
+                                        geodesic=geodesic, strokes=strokes, stroke_radius=stroke_radius, polygons=polygons)
         return _result(out, 0, image, timing)
 
     def segment_bbox(self, image: np.ndarray, bbox: tuple[int, int, int, int], matte: bool = False,
@@ -1635,6 +1734,34 @@ class GCNGrabCutPipeline:
             trimap[y0:y1, x0:x1] = Label.FG_DEFINITE
         extra = {}
         if plan.mat or plan.cfm or full is not None:   # GrabCut's mask is final: no clean-up, and the overlay is GrabCut's own
+            eng = self._eng
+            stage = _OutputStage(eng, plan, eng.to_device(image[None]), None if full is None else eng.to_device(full[None]),
+                                 final_mask=eng.to_device(np.ascontiguousarray(binary_mask, np.uint8)[None]))
+            stage.from_mask(eng, 0, 1)
+            extra = _optional_results(stage.out, 0)
+        return SegmentationResult(image=image, binary_mask=binary_mask, trimap=trimap,
+                                  segments=np.zeros((H, W), dtype=np.int32), overlay=gc.overlay_mask(),
+                                  rgba=gc.crop_foreground(), **extra)
+
+    def segment_lasso(self, image: np.ndarray, polygon, matte: bool = False, matte_radius: int = MATTE_RADIUS,
+                      matte_eps: float = MATTE_EPS, full_image: Optional[np.ndarray] = None, foreground=False,
+                      full_cut=False) -> SegmentationResult:
+        """Classical GrabCut with a lasso (additive; the sibling of segment_bbox, no network).  polygon:
+        one polygon, a sequence of n >= 3 (row, col) vertices, or a sequence of polygons (their union).  The mask starts
+        as probable foreground inside the lasso and definite background outside (GrabCut.run_with_lasso: ggc_apply_polygons,
+        then run_with_trimap).  The optional matte / full-image arguments are segment_bbox's.  Not promised to equal
+        segment_bbox on a rectangle: run_with_trimap applies the promotions and the degenerate guard, run_with_bbox does
+        not."""
+        image = _check_image(image)
+        full = None if full_image is None else _check_image(full_image)
+        plan = _OutputPlan.of(self, (1, *image.shape), None if full is None else (1, *full.shape), matte=matte,
+                              matte_radius=matte_radius, matte_eps=matte_eps, foreground=foreground, full_cut=full_cut)
+        gc = GrabCut(image, self.gc_config, device=self.device)
+        trimap = gc.lasso_trimap(polygon)
+        binary_mask = gc.run_with_trimap(trimap)
+        H, W = image.shape[:2]
+        extra = {}
+        if plan.mat or plan.cfm or full is not None:   # GrabCut's mask is final, as in segment_bbox
             eng = self._eng
             stage = _OutputStage(eng, plan, eng.to_device(image[None]), None if full is None else eng.to_device(full[None]),
                                  final_mask=eng.to_device(np.ascontiguousarray(binary_mask, np.uint8)[None]))

@@ -51,7 +51,9 @@
 extern "C" {
 #endif
 
-#define GGC_VERSION 405 /* 0.4.5: ggc_apply_strokes, ggc_stroke_pixels (brush strokes as hard constraints: polylines painted as capsules by
+#define GGC_VERSION 406 /* 0.4.6: ggc_apply_polygons (lassos and filled polygons as hard constraints: one exact integer point-in-polygon
+                                  rule, even-odd with a closed boundary; additive, no existing entry changes);
+                           0.4.5: ggc_apply_strokes, ggc_stroke_pixels (brush strokes as hard constraints: polylines painted as capsules by
                                   one exact integer rule, and their centre lines as a click list; additive, no existing entry changes);
                            0.4.4: ggc_geodesic_hints (clicks propagated by a capped, colour-aware shortest-path distance instead of a fixed
                                   disk; additive, ggc_apply_hints does not change);
@@ -484,6 +486,36 @@ int ggc_apply_strokes(ggc_ctx* ctx, ggc_stream stream, int B, int H, int W, cons
  * SYNCHRONISES the stream: stroke_ptr and the segments are read back and checked, and with hints_out the total is read. */
 int ggc_stroke_pixels(ggc_ctx* ctx, ggc_stream stream, int B, int H, int W, const int32_t* strokes, const int32_t* stroke_ptr,
                       int32_t* hint_ptr_out, int32_t* hints_out, int64_t capacity);
+
+/* H3 — lassos and filled polygons as hard constraints (additive): areas, where ggc_apply_strokes has lines.  One exact integer
+ * definition; no float is involved anywhere.
+ *   verts      [dev] i32 [V,2] = (row, col) vertices, grouped by polygon; |coordinate| <= 2^20; vertices may lie outside the image
+ *   poly_ptr   [dev] i32 [P+1]  polygon q owns verts[poly_ptr[q] .. poly_ptr[q+1]), at least 3 of them; poly_ptr[0] = 0,
+ *              V = poly_ptr[P].  A polygon is closed implicitly, last vertex to first; it may intersect itself.
+ *   poly_label [dev] i32 [P]    0 = background fill, 1 = foreground fill, 2 = lasso
+ *   image_ptr  [dev] i32 [B+1]  image b owns polygons image_ptr[b] .. image_ptr[b+1); image_ptr[0] = 0, image_ptr[B] = P
+ *   mask       [dev] u8 [B,H,W] in/out GrabCut labels
+ * Rule: pixel p = (r, c) is COVERED by a polygon iff (a) or (b) holds.
+ *   (a) p lies on an edge a -> b: (b.r - a.r)(c - a.c) - (b.c - a.c)(r - a.r) == 0 and p is inside the edge's bounding box.
+ *       The covered set is therefore closed, as the click disk and the stroke capsule are.
+ *   (b) the crossing number is odd (even-odd rule): an edge counts iff (a.r <= r) != (b.r <= r), half-open in rows so that a
+ *       horizontal edge never counts, and it crosses strictly to the right of p: with lo / hi the edge's ends ordered by row,
+ *       (hi.c - lo.c)(r - lo.r) - (c - lo.c)(hi.r - lo.r) > 0.
+ * Under the limits every product stays below 2^44: plain int64, no 128-bit compare.
+ * Per image, in this order: (1) LASSOS: if the image has at least one lasso, every in-image pixel covered by none of its
+ * lassos becomes GGC_BGD (lassos form a union; pixels inside a lasso are not touched); (2) FILLS, in polygon order: every
+ * in-image pixel a fill covers becomes GGC_FGD (label 1) or GGC_BGD (label 0); where fills overlap the image's LAST fill
+ * wins, by index and not by timing.  A pixel that neither step touches is neither read nor written.  No atomics; every
+ * image's result equals that of its single-image call bit for bit.  Work is O(pixels + 32x8 tiles x edges): a tile sees the
+ * edges of the polygons whose bounding box meets it, less those whose row span misses the tile's rows or that lie wholly
+ * left of it.  Scratch: 16 bytes per polygon.
+ * B == 0 is a no-op whatever the other arguments hold, as for ggc_apply_strokes; otherwise B, H or W outside 1..65535 is
+ * GGC_E_SHAPE and a negative P GGC_E_INVALID_ARG, and then P == 0 is a no-op too (no pointer is looked at): nothing is
+ * written.  With P >= 1, a NULL mask, image_ptr, poly_ptr, poly_label or verts, image_ptr or poly_ptr not starting at 0 or decreasing, image_ptr[B] != P, a
+ * polygon of fewer than 3 vertices, a label outside {0, 1, 2} or a coordinate beyond +-2^20 is GGC_E_INVALID_ARG, all before
+ * any launch.  SYNCHRONISES the stream: the four arrays are read back and checked on the host. */
+int ggc_apply_polygons(ggc_ctx* ctx, ggc_stream stream, int B, int H, int W, const int32_t* verts, const int32_t* poly_ptr,
+                       const int32_t* poly_label, const int32_t* image_ptr, int P, uint8_t* mask);
 
 /* C0 — next simulated click per image (additive; the standard NoC protocol of interactive segmentation).
  *   pred [dev] u8  [B,H,W]  current binary mask (nonzero = foreground)

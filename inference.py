@@ -8,6 +8,7 @@ Same command line as the reference's inference.py (flags :26-56, outputs :146-15
     python3 inference.py --image cat.jpg --keep-largest --save mask overlay
     python3 inference.py --image cat.jpg --fg-point 120,200 --bg-point 10,10 --hint-radius 8
     python3 inference.py --image cat.jpg --bg-stroke "40,10 40,200 90,260" --stroke-radius 4   # a brush stroke of three vertices
+    python3 inference.py --image cat.jpg --lasso "20,30 20,300 260,300 260,30"   # everything outside the outline is background
     python3 inference.py --image cat.jpg --save mask alpha cutout          # soft edges: alpha matte and cut-out
     python3 inference.py --image big.jpg --full-res --save mask cutout     # outputs at the photo's own size
     python3 inference.py --image big.jpg --full-res --full-mask cut --save mask   # ... the mask cut again on the photo's pixels
@@ -73,6 +74,14 @@ def build_parser() -> argparse.ArgumentParser:
     parser.add_argument("--stroke-radius", type=int, default=3,
                         help="Brush radius in pixels of the image as segmented (after --max-size), 0..16384; 0 paints the "
                              "centre line; ignored with --hint-mode geodesic, where the centre line is the source set")
+    # additive: lassos and filled polygons as hard constraints (ggc_apply_polygons), single-image runs only
+    parser.add_argument("--lasso", type=_polygon, default=None, metavar='"ROW,COL ROW,COL ..."',
+                        help="Lasso, a closed outline of at least 3 vertices in original-image pixels: everything outside "
+                             "it becomes definite background (needs --image)")
+    parser.add_argument("--fg-polygon", action="append", type=_polygon, default=[], metavar='"ROW,COL ROW,COL ..."',
+                        help="Filled foreground polygon of at least 3 vertices in original-image pixels (repeatable; needs --image)")
+    parser.add_argument("--bg-polygon", action="append", type=_polygon, default=[], metavar='"ROW,COL ROW,COL ..."',
+                        help="Filled background polygon of at least 3 vertices in original-image pixels (repeatable; needs --image)")
     # additive: soft alpha matte of the mask (ggc_alpha_matte), computed when --save asks for alpha or cutout
     parser.add_argument("--matte-radius", type=int, default=4,
                         help="Window radius of the alpha matte, 1..64, in pixels of the image as segmented")
@@ -134,6 +143,16 @@ def _stroke(text: str):
         pts = []
     if not pts:
         raise argparse.ArgumentTypeError(f"expected 'ROW,COL ROW,COL ...' (at least one vertex), got '{text}'")
+    return pts
+
+
+def _polygon(text: str):
+    try:
+        pts = [_point(v) for v in text.split()]
+    except argparse.ArgumentTypeError:
+        pts = []
+    if len(pts) < 3:
+        raise argparse.ArgumentTypeError(f"expected 'ROW,COL ROW,COL ROW,COL ...' (at least three vertices), got '{text}'")
     return pts
 
 
@@ -199,6 +218,8 @@ def main() -> None:
         parser.error("--fg-point / --bg-point are clicks on one image: use them with --image, not --input")
     if (args.fg_stroke or args.bg_stroke) and not args.image:
         parser.error("--fg-stroke / --bg-stroke are strokes on one image: use them with --image, not --input")
+    if (args.lasso or args.fg_polygon or args.bg_polygon) and not args.image:
+        parser.error("--lasso / --fg-polygon / --bg-polygon are polygons on one image: use them with --image, not --input")
     if not 0 <= args.stroke_radius <= 16384:
         parser.error("--stroke-radius must be in 0..16384")
     if args.hint_radius < 0:
@@ -292,7 +313,8 @@ def main() -> None:
             chunk = items[i:i + args.batch]
             t0 = time.perf_counter()
             hint_kw = {}
-            if args.fg_point or args.bg_point or args.fg_stroke or args.bg_stroke:   # --image only: one chunk of one image
+            polygons = args.lasso or args.fg_polygon or args.bg_polygon
+            if args.fg_point or args.bg_point or args.fg_stroke or args.bg_stroke or polygons:   # --image only: one chunk of one image
                 from PIL import Image
                 path, image, _ = chunk[0]
                 with Image.open(path) as im:
@@ -305,6 +327,10 @@ def main() -> None:
                     hint_kw.update(strokes=[([scale_points(s, orig_hw, image.shape[:2]) for s in args.fg_stroke],
                                              [scale_points(s, orig_hw, image.shape[:2]) for s in args.bg_stroke])],
                                    stroke_radius=args.stroke_radius)
+                if polygons:
+                    hint_kw.update(polygons=[([scale_points(p, orig_hw, image.shape[:2]) for p in args.fg_polygon],
+                                              [scale_points(p, orig_hw, image.shape[:2]) for p in args.bg_polygon],
+                                              [scale_points(args.lasso, orig_hw, image.shape[:2])] if args.lasso else [])])
                 if args.hint_mode == "geodesic":
                     from src.gcn_grabcut import GeodesicHints
                     hint_kw.update(geodesic=GeodesicHints(args.geodesic_radius, args.hint_gamma))
