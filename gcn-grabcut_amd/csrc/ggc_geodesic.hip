@@ -288,22 +288,16 @@ extern "C" int ggc_geodesic_hints(ggc_ctx* ctx, ggc_stream stream, int B, int H,
     GGC_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     std::vector<int32_t> hp;
-    int rc = read_i32(ctx, st, hint_ptr, B + 1, hp);
+    int rc = read_offsets(ctx, st, hint_ptr, B, "hint_ptr", "image", 0, hp);
     if (rc) return rc;
-    GGC_REQUIRE(ctx, hp[0] == 0, GGC_E_INVALID_ARG, "hint_ptr[0] = %d, expected 0", hp[0]);
-    for (int b = 0; b < B; ++b)
-        GGC_REQUIRE(ctx, hp[b + 1] >= hp[b], GGC_E_INVALID_ARG, "hint_ptr decreases at image %d (%d -> %d)", b, hp[b], hp[b + 1]);
     const int K = hp[B];
     if (K == 0) return GGC_OK;
     GGC_REQUIRE(ctx, hints, GGC_E_INVALID_ARG, "null hints with %d clicks", K);
     int64_t N = 0;
     if (node_dist) {
         std::vector<int32_t> np_;
-        rc = read_i32(ctx, st, node_ptr, B + 1, np_);
+        rc = read_offsets(ctx, st, node_ptr, B, "node_ptr", "image", 0, np_);
         if (rc) return rc;
-        GGC_REQUIRE(ctx, np_[0] == 0, GGC_E_INVALID_ARG, "node_ptr[0] = %d, expected 0", np_[0]);
-        for (int b = 0; b < B; ++b)
-            GGC_REQUIRE(ctx, np_[b + 1] >= np_[b], GGC_E_INVALID_ARG, "node_ptr decreases at image %d", b);
         N = np_[B];
     }
 

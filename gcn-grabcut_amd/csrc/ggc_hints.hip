@@ -4,17 +4,14 @@
 //   k_hint_flags   one lane per click: atomicOr of bit 0 (foreground) / bit 1 (background) into a flag word per node.
 //                  Integer OR is order independent, so the words do not depend on launch order.
 //   k_node_hints   one lane per node: the three columns of encode_user_hints from its flag word.
-//   k_apply_hints  one workgroup per 32x8 pixel tile of one image.  The region pass reads the pixel's flag word; the disk
-//                  pass culls the image's clicks whose disk meets the tile into an LDS list, 256 clicks at a time, keeping
-//                  click order (per-wave ballot + prefix over the four waves), and each lane walks that list for its pixel.
-//                  A later click overwrites an earlier one, so "last click wins" follows the click index, not timing.
-//                  Work is O(pixels + tiles x clicks); a pixel no hint touches is neither read nor written.
-#include "ggc_internal.h"
+//   k_apply_hints  the tile painter (ggc_paint.h).  The region pass reads the pixel's flag word; the disk pass keeps a
+//                  click when its disk meets the tile, i.e. when the nearest pixel of the tile, clipped to the image, is
+//                  within the radius.  Work is O(pixels + tiles x clicks); a pixel no hint touches is neither read nor
+//                  written.
+#include "ggc_paint.h"
 
 namespace ggc {
 namespace {
-
-constexpr int HT_W = 32, HT_H = 8, HT_THREADS = HT_W * HT_H;   // 4 waves, each two 32-pixel rows of the tile
 
 struct HDims { int B, H, W; int64_t r2; };
 
@@ -50,32 +47,28 @@ __global__ void __launch_bounds__(256) k_node_hints(int N, const int32_t* __rest
     node_hints[3 * n + 2] = f ? 0.0f : 1.0f;
 }
 
-__global__ void __launch_bounds__(HT_THREADS) k_apply_hints(HDims d, int tiles_x, const int32_t* __restrict__ hints,
+__global__ void __launch_bounds__(PT_THREADS) k_apply_hints(HDims d, int tiles_x, const int32_t* __restrict__ hints,
                                                             const int32_t* __restrict__ hint_ptr,
                                                             const int32_t* __restrict__ segments,
                                                             const int32_t* __restrict__ node_ptr,
                                                             const int32_t* __restrict__ flags, uint8_t* __restrict__ mask) {
-    __shared__ int s_r[HT_THREADS], s_c[HT_THREADS], s_l[HT_THREADS];
-    __shared__ int s_wave[HT_THREADS / WAVE];
-    const int b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int tx0 = (blockIdx.x % tiles_x) * HT_W, ty0 = (blockIdx.x / tiles_x) * HT_H;
-    const int x = tx0 + (tid & (HT_W - 1)), y = ty0 + tid / HT_W;
-    const bool inside = x < d.W && y < d.H;
-    const size_t p = (size_t)b * d.H * d.W + (size_t)y * d.W + x;
+    __shared__ int s_r[PT_THREADS], s_c[PT_THREADS], s_l[PT_THREADS];
+    __shared__ int s_wave[PT_THREADS / WAVE];
+    const PaintTile t = paint_tile(d.H, d.W, tiles_x);
     int v = -1;                                                            // new label, -1 = untouched
-    if (flags && inside) {
-        const int s = segments[p], n0 = node_ptr[b];
-        if (s >= 0 && s < node_ptr[b + 1] - n0) {
+    if (flags && t.inside) {
+        const int s = segments[t.p], n0 = node_ptr[t.b];
+        if (s >= 0 && s < node_ptr[t.b + 1] - n0) {
             const int f = flags[n0 + s];
             if (f == 1) v = GGC_FGD;                                       // every click on the region is foreground
             else if (f == 2) v = GGC_BGD;                                  // every click is background; mixed: the disks decide
         }
     }
     // the tile as a rectangle clipped to the image: a disk meets it when the nearest tile pixel is within the radius
-    const int tx1 = min(tx0 + HT_W, d.W) - 1, ty1 = min(ty0 + HT_H, d.H) - 1;
-    const int k0 = hint_ptr[b], k1 = hint_ptr[b + 1];
-    for (int base = k0; base < k1; base += HT_THREADS) {                  // block-uniform loop
-        const int k = base + tid;
+    const int tx0 = t.tx0, ty0 = t.ty0, tx1 = min(tx0 + PT_W, d.W) - 1, ty1 = min(ty0 + PT_H, d.H) - 1;
+    const int k0 = hint_ptr[t.b], k1 = hint_ptr[t.b + 1];
+    for (int base = k0; base < k1; base += PT_THREADS) {                  // block-uniform loop
+        const int k = base + threadIdx.x;
         int r = 0, c = 0, l = 0;
         bool keep = false;
         if (k < k1) {
@@ -86,25 +79,18 @@ __global__ void __launch_bounds__(HT_THREADS) k_apply_hints(HDims d, int tiles_x
                 keep = dy * dy + dx * dx <= d.r2;
             }
         }
-        const unsigned long long m = __ballot(keep);
-        if (lane == 0) s_wave[wave] = __popcll(m);
+        const PaintSlot slot = paint_slot<false>(keep, false, s_wave);
+        if (keep) { s_r[slot.pos] = r; s_c[slot.pos] = c; s_l[slot.pos] = l; }
         __syncthreads();
-        int pos = __popcll(m & ((1ull << lane) - 1ull)), n = 0;
-        for (int w = 0; w < HT_THREADS / WAVE; ++w) {
-            pos += w < wave ? s_wave[w] : 0;
-            n += s_wave[w];
-        }
-        if (keep) { s_r[pos] = r; s_c[pos] = c; s_l[pos] = l; }
-        __syncthreads();
-        if (inside) {
-            for (int i = 0; i < n; ++i) {                                  // same address in every lane: LDS broadcast
-                const int64_t dy = y - s_r[i], dx = x - s_c[i];
+        if (t.inside) {
+            for (int i = 0; i < slot.n; ++i) {                             // same address in every lane: LDS broadcast
+                const int64_t dy = t.y - s_r[i], dx = t.x - s_c[i];
                 if (dy * dy + dx * dx <= d.r2) v = s_l[i];
             }
         }
         __syncthreads();                                                   // the list is rewritten by the next 256 clicks
     }
-    if (inside && v >= 0) mask[p] = (uint8_t)v;
+    if (t.inside && v >= 0) mask[t.p] = (uint8_t)v;
 }
 
 } // namespace
@@ -125,11 +111,8 @@ extern "C" int ggc_apply_hints(ggc_ctx* ctx, ggc_stream stream, int B, int H, in
     GGC_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     std::vector<int32_t> hp;
-    int rc = read_i32(ctx, st, hint_ptr, B + 1, hp);
+    int rc = read_offsets(ctx, st, hint_ptr, B, "hint_ptr", "image", 0, hp);
     if (rc) return rc;
-    GGC_REQUIRE(ctx, hp[0] == 0, GGC_E_INVALID_ARG, "hint_ptr[0] = %d, expected 0", hp[0]);
-    for (int b = 0; b < B; ++b)
-        GGC_REQUIRE(ctx, hp[b + 1] >= hp[b], GGC_E_INVALID_ARG, "hint_ptr decreases at image %d (%d -> %d)", b, hp[b], hp[b + 1]);
     const int K = hp[B];
     if (K == 0) return GGC_OK;
     GGC_REQUIRE(ctx, hints, GGC_E_INVALID_ARG, "null hints with %d clicks", K);
@@ -138,11 +121,8 @@ extern "C" int ggc_apply_hints(ggc_ctx* ctx, ggc_stream stream, int B, int H, in
     int32_t* flags = nullptr;
     if (need_nodes) {
         std::vector<int32_t> np_;
-        rc = read_i32(ctx, st, node_ptr, B + 1, np_);
+        rc = read_offsets(ctx, st, node_ptr, B, "node_ptr", "image", 0, np_);
         if (rc) return rc;
-        GGC_REQUIRE(ctx, np_[0] == 0, GGC_E_INVALID_ARG, "node_ptr[0] = %d, expected 0", np_[0]);
-        for (int b = 0; b < B; ++b)
-            GGC_REQUIRE(ctx, np_[b + 1] >= np_[b], GGC_E_INVALID_ARG, "node_ptr decreases at image %d", b);
         const int N = np_[B];
         if (N > 0) {
             flags = scratch_t<int32_t>(ctx, S_MISC_A, (size_t)N);
@@ -154,8 +134,8 @@ extern "C" int ggc_apply_hints(ggc_ctx* ctx, ggc_stream stream, int B, int H, in
         }
     }
     if (mask) {
-        const int tiles_x = cdiv(W, HT_W), tiles = tiles_x * cdiv(H, HT_H);
-        hipLaunchKernelGGL(k_apply_hints, dim3(tiles, B), dim3(HT_THREADS), 0, st, d, tiles_x, hints, hint_ptr, segments,
+        const int tiles_x = cdiv(W, PT_W), tiles = tiles_x * cdiv(H, PT_H);
+        hipLaunchKernelGGL(k_apply_hints, dim3(tiles, B), dim3(PT_THREADS), 0, st, d, tiles_x, hints, hint_ptr, segments,
                            node_ptr, region ? flags : nullptr, mask);
     }
     GGC_LAUNCH_CHECK(ctx);

@@ -116,6 +116,11 @@ const Knobs& knobs();
 int set_err(ggc_ctx* ctx, int code, const char* fmt, ...);
 // small synchronous device -> host read through the context's pinned staging buffer (stream sync)
 int read_i32(ggc_ctx* ctx, hipStream_t st, const int32_t* dev, int n, std::vector<int32_t>& host);
+// A packed list's offsets, dev [n+1]: read to the host and checked, off[0] == 0 and every range (one per `unit`, "image" or
+// "polygon", for the message) at least min_step long, else GGC_E_INVALID_ARG.  check_offsets is the check alone, on host memory.
+int read_offsets(ggc_ctx* ctx, hipStream_t st, const int32_t* dev, int n, const char* name, const char* unit, int min_step,
+                 std::vector<int32_t>& host);
+int check_offsets(ggc_ctx* ctx, const int32_t* off, int n, const char* name, const char* unit, int min_step);
 // Returns nullptr (and sets error) on failure. Content is NOT preserved on growth.
 void* scratch(ggc_ctx* ctx, int slot, size_t bytes);
 // Destination CSR of an edge list, stable in edge order (ggc_resgcn.hip): row_ptr [N+1], col = src[eid] [E], eid [E],

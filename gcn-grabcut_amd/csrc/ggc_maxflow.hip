@@ -416,22 +416,6 @@ __global__ void k_open_init(int B, const int32_t* __restrict__ state, int32_t* _
     if (b < B && !state[b]) list[atomicAdd(n_open, 1)] = b;
 }
 
-// small synchronous device -> host read through the context's page-locked staging buffer.  (Round 3 measured the
-// alternative — a one-thread kernel publishing into host-coherent memory and the host spinning on a ticket instead of
-// hipStreamSynchronize: 58.4-58.8 vs 59.1-60.3 ms per GrabCut stage, 86.9 vs 87.1 ms per step: not worth four spinning cores.)
-int read_i32(ggc_ctx* ctx, hipStream_t st, const int32_t* dev, int n, std::vector<int32_t>& host) {
-    host.resize(n);
-    if (ctx->h_pinned && n <= ggc_ctx::H_PINNED_INTS) {
-        GGC_HIP(ctx, hipMemcpyAsync(ctx->h_pinned, dev, sizeof(int32_t) * n, hipMemcpyDeviceToHost, st));
-        GGC_HIP(ctx, hipStreamSynchronize(st));
-        std::copy(ctx->h_pinned, ctx->h_pinned + n, host.begin());
-        return GGC_OK;
-    }
-    GGC_HIP(ctx, hipMemcpyAsync(host.data(), dev, sizeof(int32_t) * n, hipMemcpyDeviceToHost, st));
-    GGC_HIP(ctx, hipStreamSynchronize(st));
-    return GGC_OK;
-}
-
 namespace {
 
 // The max-flow's scratch, one slot.  `dirty` must outlive a solve: the warm start of the next GrabCut iteration relies on

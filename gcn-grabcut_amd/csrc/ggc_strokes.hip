@@ -6,26 +6,22 @@
 // rho4 = max(4 radius^2, 1).  |coordinate| <= 2^20 keeps t and w x d inside int64; (w x d)^2 and rho4 L2 need up to 90 bits
 // and are compared as unsigned __int128 (v_mad_u64_u32 chains, no scratch).
 //
-//   k_paint_strokes   one workgroup per 32x8 pixel tile of one image, as k_apply_hints.  The image's segments are culled 256
-//                     at a time into an LDS list that keeps their order (per-wave ballot + prefix over the four waves): a
-//                     segment stays when the tile's centre is within radius + the tile's half-diagonal of it, the same
-//                     rule in doubled coordinates so that the centre is an integer.  That is conservative and never by
-//                     bounding box, so a long diagonal stroke is walked only by the tiles along it.  Each lane then walks
-//                     the list for its pixel; a later segment overwrites an earlier one, so "last segment wins" follows
-//                     the index, not timing.  Work is O(pixels + tiles x segments), independent of stroke length.
+//   k_paint_strokes   the tile painter (ggc_paint.h).  A segment is kept when the tile's centre is within radius + the
+//                     tile's half-diagonal of it, the same rule in doubled coordinates so that the centre is an integer.
+//                     That is conservative and never by bounding box, so a long diagonal stroke is walked only by the
+//                     tiles along it.  Work is O(pixels + tiles x segments), independent of stroke length.
 //                     PAINT writes the label into the mask (a pixel no stroke touches is neither read nor written);
 //                     STAMP writes 0 | 1 + label for every pixel into context scratch.
 //   ggc_stroke_pixels stamps the centre lines (radius 0), then: k_stroke_row_count (one wave per row), k_stroke_image_scan
 //                     (one workgroup per image: row offsets and the image's count), k_stroke_ptr_scan (one workgroup:
 //                     hint_ptr_out), k_stroke_fill (one wave per row, raster order by ballot + prefix).  Integer sums
 //                     only and no atomics: the list does not depend on launch order.
-#include "ggc_internal.h"
+#include "ggc_paint.h"
 #include <climits>
 
 namespace ggc {
 namespace {
 
-constexpr int ST_W = 32, ST_H = 8, ST_THREADS = ST_W * ST_H;   // 4 waves, each two 32-pixel rows of the tile
 constexpr int ST_MAX_COORD = 1 << 20, ST_MAX_RADIUS = 16384;
 
 struct SDims { int B, H, W; unsigned long long rho4, cull; };   // cull = (max(2 radius, 1) + 32)^2, doubled coordinates
@@ -45,20 +41,16 @@ __device__ __forceinline__ bool seg_within(int64_t wy, int64_t wx, int64_t dy, i
 }
 
 template <bool STAMP>
-__global__ void __launch_bounds__(ST_THREADS) k_paint_strokes(SDims d, int tiles_x, const int32_t* __restrict__ strokes,
+__global__ void __launch_bounds__(PT_THREADS) k_paint_strokes(SDims d, int tiles_x, const int32_t* __restrict__ strokes,
                                                               const int32_t* __restrict__ stroke_ptr, uint8_t* __restrict__ out) {
-    __shared__ int s_r0[ST_THREADS], s_c0[ST_THREADS], s_dr[ST_THREADS], s_dc[ST_THREADS], s_l[ST_THREADS];
-    __shared__ int s_wave[ST_THREADS / WAVE];
-    const int b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int tx0 = (blockIdx.x % tiles_x) * ST_W, ty0 = (blockIdx.x / tiles_x) * ST_H;
-    const int x = tx0 + (tid & (ST_W - 1)), y = ty0 + tid / ST_W;
-    const bool inside = x < d.W && y < d.H;
-    const size_t p = (size_t)b * d.H * d.W + (size_t)y * d.W + x;
-    const int64_t cy2 = 2 * ty0 + (ST_H - 1), cx2 = 2 * tx0 + (ST_W - 1);  // the tile's centre, doubled
+    __shared__ int s_r0[PT_THREADS], s_c0[PT_THREADS], s_dr[PT_THREADS], s_dc[PT_THREADS], s_l[PT_THREADS];
+    __shared__ int s_wave[PT_THREADS / WAVE];
+    const PaintTile t = paint_tile(d.H, d.W, tiles_x);
+    const int64_t cy2 = 2 * t.ty0 + (PT_H - 1), cx2 = 2 * t.tx0 + (PT_W - 1);   // the tile's centre, doubled
     int v = -1;                                                            // new label, -1 = untouched
-    const int k0 = stroke_ptr[b], k1 = stroke_ptr[b + 1];
-    for (int base = k0; base < k1; base += ST_THREADS) {                  // block-uniform loop
-        const int k = base + tid;
+    const int k0 = stroke_ptr[t.b], k1 = stroke_ptr[t.b + 1];
+    for (int base = k0; base < k1; base += PT_THREADS) {                  // block-uniform loop
+        const int k = base + threadIdx.x;
         int r0 = 0, c0 = 0, dr = 0, dc = 0, l = 0;
         bool keep = false;
         if (k < k1) {
@@ -67,25 +59,18 @@ __global__ void __launch_bounds__(ST_THREADS) k_paint_strokes(SDims d, int tiles
             l = strokes[5 * k + 4] != 0 ? GGC_FGD : GGC_BGD;
             keep = seg_within<1>(cy2 - 2 * (int64_t)r0, cx2 - 2 * (int64_t)c0, 2 * (int64_t)dr, 2 * (int64_t)dc, d.cull);
         }
-        const unsigned long long m = __ballot(keep);
-        if (lane == 0) s_wave[wave] = __popcll(m);
+        const PaintSlot slot = paint_slot<false>(keep, false, s_wave);
+        if (keep) { s_r0[slot.pos] = r0; s_c0[slot.pos] = c0; s_dr[slot.pos] = dr; s_dc[slot.pos] = dc; s_l[slot.pos] = l; }
         __syncthreads();
-        int pos = __popcll(m & ((1ull << lane) - 1ull)), n = 0;
-        for (int w = 0; w < ST_THREADS / WAVE; ++w) {
-            pos += w < wave ? s_wave[w] : 0;
-            n += s_wave[w];
-        }
-        if (keep) { s_r0[pos] = r0; s_c0[pos] = c0; s_dr[pos] = dr; s_dc[pos] = dc; s_l[pos] = l; }
-        __syncthreads();
-        if (inside) {
-            for (int i = 0; i < n; ++i)                                    // same address in every lane: LDS broadcast
-                if (seg_within<4>(y - s_r0[i], x - s_c0[i], s_dr[i], s_dc[i], d.rho4)) v = s_l[i];
+        if (t.inside) {
+            for (int i = 0; i < slot.n; ++i)                               // same address in every lane: LDS broadcast
+                if (seg_within<4>(t.y - s_r0[i], t.x - s_c0[i], s_dr[i], s_dc[i], d.rho4)) v = s_l[i];
         }
         __syncthreads();                                                   // the list is rewritten by the next 256 segments
     }
-    if (!inside) return;
-    if (STAMP) out[p] = (uint8_t)(v + 1);
-    else if (v >= 0) out[p] = (uint8_t)v;
+    if (!t.inside) return;
+    if (STAMP) out[t.p] = (uint8_t)(v + 1);
+    else if (v >= 0) out[t.p] = (uint8_t)v;
 }
 
 // exclusive prefix of v over the 256 threads of a workgroup; total = the sum.  s_wave: 4 words of LDS.
@@ -181,11 +166,8 @@ int read_strokes(ggc_ctx* ctx, hipStream_t st, int B, int H, int W, const int32_
                 "bad shape B=%d H=%d W=%d (each at most 65535)", B, H, W);
     GGC_REQUIRE(ctx, radius >= 0 && radius <= ST_MAX_RADIUS, GGC_E_INVALID_ARG, "stroke radius %d outside 0..%d", radius, ST_MAX_RADIUS);
     std::vector<int32_t> sp;
-    int rc = read_i32(ctx, st, stroke_ptr, B + 1, sp);
+    int rc = read_offsets(ctx, st, stroke_ptr, B, "stroke_ptr", "image", 0, sp);
     if (rc) return rc;
-    GGC_REQUIRE(ctx, sp[0] == 0, GGC_E_INVALID_ARG, "stroke_ptr[0] = %d, expected 0", sp[0]);
-    for (int b = 0; b < B; ++b)
-        GGC_REQUIRE(ctx, sp[b + 1] >= sp[b], GGC_E_INVALID_ARG, "stroke_ptr decreases at image %d (%d -> %d)", b, sp[b], sp[b + 1]);
     n_seg = sp[B];
     if (n_seg == 0) return GGC_OK;
     GGC_REQUIRE(ctx, strokes, GGC_E_INVALID_ARG, "null strokes with %d segments", n_seg);
@@ -204,6 +186,7 @@ int read_strokes(ggc_ctx* ctx, hipStream_t st, int B, int H, int W, const int32_
 
 SDims stroke_dims(int B, int H, int W, int radius) {
     const unsigned long long r2 = 2ull * (unsigned long long)radius;
+    static_assert((PT_W - 1) * (PT_W - 1) + (PT_H - 1) * (PT_H - 1) < 32 * 32, "the cull's + 32 covers the tile's doubled half-diagonal");
     const unsigned long long reach = (r2 > 1 ? r2 : 1) + 32;              // doubled: brush + the 32x8 tile's half-diagonal, sqrt(1010) < 32
     return SDims{B, H, W, r2 * r2 > 1 ? r2 * r2 : 1, reach * reach};
 }
@@ -223,8 +206,8 @@ extern "C" int ggc_apply_strokes(ggc_ctx* ctx, ggc_stream stream, int B, int H, 
     int rc = read_strokes(ctx, st, B, H, W, strokes, stroke_ptr, radius, n_seg);
     if (rc) return rc;
     if (n_seg == 0) return GGC_OK;
-    const int tiles_x = cdiv(W, ST_W), tiles = tiles_x * cdiv(H, ST_H);
-    hipLaunchKernelGGL(k_paint_strokes<false>, dim3(tiles, B), dim3(ST_THREADS), 0, st, stroke_dims(B, H, W, radius), tiles_x,
+    const int tiles_x = cdiv(W, PT_W), tiles = tiles_x * cdiv(H, PT_H);
+    hipLaunchKernelGGL(k_paint_strokes<false>, dim3(tiles, B), dim3(PT_THREADS), 0, st, stroke_dims(B, H, W, radius), tiles_x,
                        strokes, stroke_ptr, mask);
     GGC_LAUNCH_CHECK(ctx);
     return GGC_OK;
@@ -257,8 +240,8 @@ extern "C" int ggc_stroke_pixels(ggc_ctx* ctx, ggc_stream stream, int B, int H, 
             img_cnt = c.take<int32_t>((size_t)B);
         }))
         return GGC_E_OOM;
-    const int tiles_x = cdiv(W, ST_W), tiles = tiles_x * cdiv(H, ST_H), row_blocks = cdiv(rows, 256 / WAVE);
-    hipLaunchKernelGGL(k_paint_strokes<true>, dim3(tiles, B), dim3(ST_THREADS), 0, st, stroke_dims(B, H, W, 0), tiles_x,
+    const int tiles_x = cdiv(W, PT_W), tiles = tiles_x * cdiv(H, PT_H), row_blocks = cdiv(rows, 256 / WAVE);
+    hipLaunchKernelGGL(k_paint_strokes<true>, dim3(tiles, B), dim3(PT_THREADS), 0, st, stroke_dims(B, H, W, 0), tiles_x,
                        strokes, stroke_ptr, stamp);
     hipLaunchKernelGGL(k_stroke_row_count, dim3(row_blocks), dim3(256), 0, st, rows, W, stamp, row_off);
     hipLaunchKernelGGL(k_stroke_image_scan, dim3(B), dim3(256), 0, st, H, row_off, img_cnt);

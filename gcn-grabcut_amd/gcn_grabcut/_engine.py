@@ -209,11 +209,17 @@ class Engine:
         return trimap
 
     # ------------------------------------------------------------------ H0
+    def _upload_packed(self, arrays):
+        """int32 host arrays -> their flat copies on the device, views of one buffer filled by one host-to-device copy."""
+        parts = [np.asarray(a, np.int32).ravel() for a in arrays]
+        d = self.to_device(np.concatenate(parts))
+        o = np.cumsum([0] + [a.size for a in parts])
+        return [d[o[i]:o[i + 1]] for i in range(len(parts))]
+
     def upload_hints(self, hints: np.ndarray, hint_ptr: np.ndarray):
         """pack_hints' (hints [K,3], hint_ptr [B+1]) -> the same two arrays on the device, in one host-to-device copy."""
-        hint_ptr = np.asarray(hint_ptr, np.int32)
-        d = self.to_device(np.concatenate([hint_ptr, np.asarray(hints, np.int32).ravel()]))
-        return d[hint_ptr.size:].view(-1, 3), d[:hint_ptr.size]
+        ptr, rows = self._upload_packed([hint_ptr, hints])
+        return rows.view(-1, 3), ptr
 
     def apply_hints(self, mask, hints, hint_ptr, radius=5, region=False, segments=None, node_ptr=None, node_hints=None,
                     shape=None):
@@ -239,9 +245,8 @@ class Engine:
     # ------------------------------------------------------------------ H2
     def upload_strokes(self, strokes: np.ndarray, stroke_ptr: np.ndarray):
         """pack_strokes' (strokes [S,5], stroke_ptr [B+1]) -> the same two arrays on the device, in one host-to-device copy."""
-        stroke_ptr = np.asarray(stroke_ptr, np.int32)
-        d = self.to_device(np.concatenate([stroke_ptr, np.asarray(strokes, np.int32).ravel()]))
-        return d[stroke_ptr.size:].view(-1, 5), d[:stroke_ptr.size]
+        ptr, rows = self._upload_packed([stroke_ptr, strokes])
+        return rows.view(-1, 5), ptr
 
     def apply_strokes(self, mask, strokes, stroke_ptr, radius=3):
         """Brush strokes as hard constraints, in place on mask (B,H,W) uint8 (ggc_apply_strokes): strokes (S,5) int32 =
@@ -268,10 +273,8 @@ class Engine:
     def upload_polygons(self, verts, poly_ptr, poly_label, image_ptr):
         """pack_polygons' (verts [V,2], poly_ptr [P+1], poly_label [P], image_ptr [B+1]) -> the same four arrays on the
         device, in one host-to-device copy."""
-        parts = [np.asarray(a, np.int32).ravel() for a in (image_ptr, poly_ptr, poly_label, verts)]
-        d = self.to_device(np.concatenate(parts))
-        o = np.cumsum([0] + [a.size for a in parts])
-        return d[o[3]:o[4]].view(-1, 2), d[o[1]:o[2]], d[o[2]:o[3]], d[o[0]:o[1]]
+        ip, pp, pl, v = self._upload_packed([image_ptr, poly_ptr, poly_label, verts])
+        return v.view(-1, 2), pp, pl, ip
 
     def apply_polygons(self, mask, verts, poly_ptr, poly_label, image_ptr):
         """Lassos and filled polygons as hard constraints, in place on mask (B,H,W) uint8 (ggc_apply_polygons): the four

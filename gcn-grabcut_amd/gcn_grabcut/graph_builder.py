@@ -240,6 +240,30 @@ def _click_rows(points, label: int, what: str) -> np.ndarray:
     return np.concatenate([rc, np.full((len(rc), 1), label, np.int64)], 1)
 
 
+def _check_entry(entry, n: int, what: str, parts: str) -> None:
+    """One image's entry of a pack_* call: a sequence of n parts."""
+    if isinstance(entry, (str, bytes)) or not hasattr(entry, "__len__") or len(entry) != n:
+        raise ValueError(f"{what} must be None or a {parts}")
+
+
+def _pack_rows(per_image, name: str, items: str, rows_of, width: int, counted: str) -> "tuple[np.ndarray, np.ndarray]":
+    """What pack_hints and pack_strokes share: per image None or a (foreground, background) pair -> (rows int32 [n,width],
+    ptr int32 [B+1]), an image's foreground rows before its background rows.  rows_of(part, label, what) -> int64 [m,width]."""
+    rows, ptr = [], [0]
+    for b, entry in enumerate(per_image):
+        n = 0
+        if entry is not None:
+            _check_entry(entry, 2, f"{name}[{b}]", f"(fg_{items}, bg_{items}) pair")
+            for part, label, ground in ((entry[0], 1, "foreground"), (entry[1], 0, "background")):
+                rows.append(rows_of(part, label, f"{name}[{b}] {ground} {items}"))
+                n += len(rows[-1])
+        ptr.append(ptr[-1] + n)
+    if ptr[-1] > np.iinfo(np.int32).max // width:
+        raise ValueError(f"{ptr[-1]} {counted}: too many for one call")
+    packed = np.concatenate(rows).astype(np.int32) if rows else np.zeros((0, width), np.int32)
+    return np.ascontiguousarray(packed.reshape(-1, width)), np.asarray(ptr, np.int32)
+
+
 def pack_hints(per_image) -> "tuple[np.ndarray, np.ndarray]":
     """Per-image click lists -> the (hints, hint_ptr) pair of ggc_apply_hints.
 
@@ -247,21 +271,7 @@ def pack_hints(per_image) -> "tuple[np.ndarray, np.ndarray]":
     encode_user_hints.  Returns hints int32 [K,3] = (row, col, label) with label 1 = foreground, 0 = background, and
     hint_ptr int32 [B+1].  An image's foreground clicks come first, then its background clicks, each in the order given,
     so a background disk wins where the two overlap.  Clicks outside the image are kept: the kernel ignores them."""
-    rows, ptr = [], [0]
-    for b, entry in enumerate(per_image):
-        if entry is None:
-            ptr.append(ptr[-1])
-            continue
-        if isinstance(entry, (str, bytes)) or len(entry) != 2:
-            raise ValueError(f"hints[{b}] must be None or a (fg_points, bg_points) pair")
-        fg = _click_rows(entry[0], 1, f"hints[{b}] foreground points")
-        bg = _click_rows(entry[1], 0, f"hints[{b}] background points")
-        rows += [fg, bg]
-        ptr.append(ptr[-1] + len(fg) + len(bg))
-    if ptr[-1] > np.iinfo(np.int32).max // 3:
-        raise ValueError(f"{ptr[-1]} clicks: too many for one call")
-    hints = np.concatenate(rows).astype(np.int32) if rows else np.zeros((0, 3), np.int32)
-    return np.ascontiguousarray(hints.reshape(-1, 3)), np.asarray(ptr, np.int32)
+    return _pack_rows(per_image, "hints", "points", _click_rows, 3, "clicks")
 
 
 STROKE_MAX_COORD = 1 << 20          # ggc_apply_strokes' limit on an endpoint coordinate
@@ -295,21 +305,7 @@ def pack_strokes(per_image) -> "tuple[np.ndarray, np.ndarray]":
     each in the order given, so background wins where the two overlap.  Vertices outside the image are kept: the kernel
     paints the part of a segment that lies inside.  An empty stroke, a wrong shape or a coordinate beyond +-2^20 is a
     ValueError."""
-    rows, ptr = [], [0]
-    for b, entry in enumerate(per_image):
-        if entry is None:
-            ptr.append(ptr[-1])
-            continue
-        if isinstance(entry, (str, bytes)) or not hasattr(entry, "__len__") or len(entry) != 2:
-            raise ValueError(f"strokes[{b}] must be None or a (fg_strokes, bg_strokes) pair")
-        fg = _stroke_segments(entry[0], 1, f"strokes[{b}] foreground strokes")
-        bg = _stroke_segments(entry[1], 0, f"strokes[{b}] background strokes")
-        rows += [fg, bg]
-        ptr.append(ptr[-1] + len(fg) + len(bg))
-    if ptr[-1] > np.iinfo(np.int32).max // 5:
-        raise ValueError(f"{ptr[-1]} stroke segments: too many for one call")
-    seg = np.concatenate(rows).astype(np.int32) if rows else np.zeros((0, 5), np.int32)
-    return np.ascontiguousarray(seg.reshape(-1, 5)), np.asarray(ptr, np.int32)
+    return _pack_rows(per_image, "strokes", "strokes", _stroke_segments, 5, "stroke segments")
 
 
 POLYGON_MAX_COORD = 1 << 20         # ggc_apply_polygons' limit on a vertex coordinate
@@ -366,8 +362,7 @@ def pack_polygons(per_image) -> "tuple[np.ndarray, np.ndarray, np.ndarray, np.nd
     verts, poly_ptr, labels, image_ptr = [], [0], [], [0]
     for b, entry in enumerate(per_image):
         if entry is not None:
-            if isinstance(entry, (str, bytes)) or not hasattr(entry, "__len__") or len(entry) != 3:
-                raise ValueError(f"polygons[{b}] must be None or a (fg_polygons, bg_polygons, lassos) triple")
+            _check_entry(entry, 3, f"polygons[{b}]", "(fg_polygons, bg_polygons, lassos) triple")
             for polys, label, what in ((entry[2], POLYGON_LASSO, "lassos"), (entry[0], POLYGON_FG, "foreground polygons"),
                                        (entry[1], POLYGON_BG, "background polygons")):
                 for v in _polygon_rows(polys, f"polygons[{b}] {what}"):

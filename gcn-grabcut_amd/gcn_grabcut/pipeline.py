@@ -749,6 +749,33 @@ def _colour_trimap(trimap: np.ndarray) -> np.ndarray:
     return vis
 
 
+def _host_packed(arg, b: int, name: str, width: int, pack, n_arrays: int, offsets) -> "Optional[tuple]":
+    """One hint argument of a batch of b images -> its packed arrays on the host, contiguous int32, the (n, width) rows
+    first; None when arg is None.  arg: an already packed tuple of n_arrays arrays or tensors, as `pack` returns it and
+    checked here, or one entry per image for `pack`.  offsets(arrays) lists the packing's offset arrays, each as (ptr, its
+    name, the number of its ranges, the number of items they share out, the smallest range)."""
+    if arg is None:
+        return None
+    if isinstance(arg, tuple) and len(arg) == n_arrays and all(hasattr(a, "shape") for a in arg) and len(arg[1].shape) == 1:
+        arrays = [np.asarray(a.cpu() if hasattr(a, "cpu") else a) for a in arg]
+        arrays[0] = arrays[0].reshape(-1, width) if arrays[0].size else np.zeros((0, width), np.int32)
+        for ptr, ptr_name, n, total, min_step in offsets(arrays):
+            if ptr.shape != (n + 1,) or ptr[0] != 0 or (np.diff(ptr) < min_step).any() or ptr[-1] != total:
+                raise ValueError(f"packed {name}: {ptr_name} must be a ({n + 1},) array from 0 to {total} in steps of at "
+                                 f"least {min_step}")
+    else:
+        if len(arg) != b:
+            raise ValueError(f"{name} has {len(arg)} entries for a batch of {b} images")
+        arrays = pack(arg)
+    return tuple(np.ascontiguousarray(a, np.int32) for a in arrays)
+
+
+def _slice_csr(rows, ptr, lo: int, hi: int):
+    """The ranges lo .. hi-1 of a packed list -> (their rows, their offsets from 0)."""
+    k0, k1 = int(ptr[lo]), int(ptr[hi])
+    return rows[k0:k1], ptr[lo:hi + 1] - k0
+
+
 @dataclass
 class _Hints:
     """The clicks of a batch in ggc_apply_hints' packing, its brush strokes in ggc_apply_strokes' and its polygons in
@@ -765,46 +792,6 @@ class _Hints:
     polys: Optional[tuple] = None                  # (verts, poly_ptr, poly_label, image_ptr) int32; None: the batch has no polygon
 
     @staticmethod
-    def _polygons_of(polygons, b: int):
-        """polygons: one None or (fg_polygons, bg_polygons, lassos) per image, or a packed (verts, poly_ptr, poly_label,
-        image_ptr) tuple -> that tuple on the host, None when no image has a polygon."""
-        if polygons is None:
-            return None
-        if isinstance(polygons, tuple) and len(polygons) == 4 and all(hasattr(a, "shape") for a in polygons):
-            verts, pp, pl, ip = (np.asarray(a.cpu() if hasattr(a, "cpu") else a) for a in polygons)
-            verts = verts.reshape(-1, 2) if verts.size else np.zeros((0, 2), np.int32)
-            if ip.shape != (b + 1,) or ip[0] != 0 or (np.diff(ip) < 0).any() or ip[-1] != len(pl) or pp.shape != (len(pl) + 1,) \
-                    or pp[0] != 0 or (np.diff(pp) < 3).any() or pp[-1] != len(verts):
-                raise ValueError(f"packed polygons: image_ptr must be a non-decreasing ({b + 1},) array from 0 to P, and "
-                                 f"poly_ptr a (P+1,) array from 0 to {len(verts)} in steps of at least 3")
-        else:
-            if len(polygons) != b:
-                raise ValueError(f"polygons has {len(polygons)} entries for a batch of {b} images")
-            verts, pp, pl, ip = pack_polygons(polygons)
-        if len(pl) == 0:
-            return None
-        return tuple(np.ascontiguousarray(a, np.int32) for a in (verts, pp, pl, ip))
-
-    @staticmethod
-    def _strokes_of(strokes, b: int):
-        """strokes: one None or (fg_strokes, bg_strokes) per image, or a packed (strokes, stroke_ptr) pair -> that pair on
-        the host, (None, None) when no image has a stroke."""
-        if strokes is None:
-            return None, None
-        if isinstance(strokes, tuple) and len(strokes) == 2 and all(hasattr(a, "shape") for a in strokes) and len(strokes[1].shape) == 1:
-            segs, ptr = (np.asarray(a.cpu() if hasattr(a, "cpu") else a) for a in strokes)
-            segs = segs.reshape(-1, 5) if segs.size else np.zeros((0, 5), np.int32)
-            if ptr.shape != (b + 1,) or ptr[0] != 0 or (np.diff(ptr) < 0).any() or ptr[-1] != len(segs):
-                raise ValueError(f"packed strokes: stroke_ptr must be a non-decreasing ({b + 1},) array from 0 to {len(segs)}")
-        else:
-            if len(strokes) != b:
-                raise ValueError(f"strokes has {len(strokes)} entries for a batch of {b} images")
-            segs, ptr = pack_strokes(strokes)
-        if ptr[-1] == 0:
-            return None, None
-        return np.ascontiguousarray(segs, np.int32), np.ascontiguousarray(ptr, np.int32)
-
-    @staticmethod
     def of(hints, b: int, radius, region, as_prior, geodesic=None, strokes=None, stroke_radius=3,
            polygons=None) -> "Optional[_Hints]":
         """hints: one None or (fg_points, bg_points) per image, or an already packed (hints, hint_ptr) pair; strokes: the
@@ -814,48 +801,42 @@ class _Hints:
         polygons: one None or (fg_polygons, bg_polygons, lassos) per image, or a packed 4-tuple (pack_polygons); a batch
         without polygons has polys None and launches exactly what it did before polygons existed."""
         geodesic = _geodesic_args(geodesic, region)
-        segs, seg_ptr = _Hints._strokes_of(strokes, b)
-        polys = _Hints._polygons_of(polygons, b)
-        if polys is not None and hints is None:
-            hints = (np.zeros((0, 3), np.int32), np.zeros(b + 1, np.int32))
+        stroked = _host_packed(strokes, b, "strokes", 5, pack_strokes, 2, lambda a: [(a[1], "stroke_ptr", b, len(a[0]), 0)])
+        segs, seg_ptr = stroked if stroked is not None and len(stroked[0]) else (None, None)
+        polys = _host_packed(polygons, b, "polygons", 2, pack_polygons, 4,
+                             lambda a: [(a[3], "image_ptr", b, len(a[2]), 0), (a[1], "poly_ptr", len(a[2]), len(a[0]), 3)])
+        if polys is not None and len(polys[0]) == 0:
+            polys = None
         if segs is not None:
             stroke_radius = _check_stroke_radius(stroke_radius)
-            if hints is None:
-                hints = (np.zeros((0, 3), np.int32), np.zeros(b + 1, np.int32))
+        if hints is None and (segs is not None or polys is not None):      # strokes or polygons without clicks: an empty click list
+            hints = (np.zeros((0, 3), np.int32), np.zeros(b + 1, np.int32))
         if hints is None:
             return None
         if int(radius) < 0:
             raise ValueError(f"hint_radius must be >= 0, got {radius}")
-        if isinstance(hints, tuple) and len(hints) == 2 and all(hasattr(a, "shape") for a in hints) and len(hints[1].shape) == 1:
-            rows, ptr = (np.asarray(a.cpu() if hasattr(a, "cpu") else a) for a in hints)
-            rows = rows.reshape(-1, 3) if rows.size else np.zeros((0, 3), np.int32)
-            if ptr.shape != (b + 1,) or ptr[0] != 0 or (np.diff(ptr) < 0).any() or ptr[-1] != len(rows):
-                raise ValueError(f"packed hints: hint_ptr must be a non-decreasing ({b + 1},) array from 0 to {len(rows)}")
-        else:
-            if len(hints) != b:
-                raise ValueError(f"hints has {len(hints)} entries for a batch of {b} images")
-            rows, ptr = pack_hints(hints)
-        if ptr[-1] == 0 and segs is None and polys is None:
+        rows, ptr = _host_packed(hints, b, "hints", 3, pack_hints, 2, lambda a: [(a[1], "hint_ptr", b, len(a[0]), 0)])
+        if len(rows) == 0 and segs is None and polys is None:
             return None
-        return _Hints(np.ascontiguousarray(rows, np.int32), np.ascontiguousarray(ptr, np.int32), int(radius), bool(region),
-                      bool(as_prior), geodesic, segs, seg_ptr, int(stroke_radius) if segs is not None else 3, polys)
+        return _Hints(rows, ptr, int(radius), bool(region), bool(as_prior), geodesic, segs, seg_ptr,
+                      int(stroke_radius) if segs is not None else 3, polys)
 
     def chunk(self, lo: int, hi: int) -> "Optional[_Hints]":
-        k0, k1 = int(self.ptr[lo]), int(self.ptr[hi])
-        segs = seg_ptr = None
-        if self.segs is not None and self.seg_ptr[hi] > self.seg_ptr[lo]:      # strokes are sliced by stroke_ptr, as clicks by hint_ptr
-            s0, s1 = int(self.seg_ptr[lo]), int(self.seg_ptr[hi])
-            segs, seg_ptr = self.segs[s0:s1], self.seg_ptr[lo:hi + 1] - s0
-        polys = None
-        if self.polys is not None and self.polys[3][hi] > self.polys[3][lo]:    # polygons are sliced by image_ptr, their vertices by poly_ptr
+        rows, ptr = _slice_csr(self.rows, self.ptr, lo, hi)
+        segs = seg_ptr = polys = None
+        if self.segs is not None:                          # strokes are sliced by stroke_ptr, as clicks by hint_ptr
+            segs, seg_ptr = _slice_csr(self.segs, self.seg_ptr, lo, hi)
+            if len(segs) == 0:
+                segs = seg_ptr = None
+        if self.polys is not None:                         # polygons are sliced by image_ptr, their vertices by poly_ptr
             verts, pp, pl, ip = self.polys
             q0, q1 = int(ip[lo]), int(ip[hi])
-            v0, v1 = int(pp[q0]), int(pp[q1])
-            polys = (verts[v0:v1], pp[q0:q1 + 1] - v0, pl[q0:q1], ip[lo:hi + 1] - q0)
-        if k1 == k0 and segs is None and polys is None:
+            if q1 > q0:
+                polys = (*_slice_csr(verts, pp, q0, q1), *_slice_csr(pl, ip, lo, hi))
+        if len(rows) == 0 and segs is None and polys is None:
             return None
-        return _Hints(self.rows[k0:k1], self.ptr[lo:hi + 1] - k0, self.radius, self.region, self.as_prior, self.geodesic,
-                      segs, seg_ptr, self.stroke_radius, polys)
+        return _Hints(rows, ptr, self.radius, self.region, self.as_prior, self.geodesic, segs, seg_ptr, self.stroke_radius,
+                      polys)
 
     @property
     def has_clicks(self) -> bool:
@@ -1188,34 +1169,45 @@ class GCNGrabCutPipeline:
         polys = None if hints is None else hints.polys
         if hints is not None and not hints.has_clicks:     # polygons only: the click paths launch nothing
             hints = None
+        dev = None                             # the device copies _paint_hints works on
         if hints is not None:
             hint_rows, hint_ptr = eng.upload_hints(hints.rows, hints.ptr)
             all_rows, all_ptr, clicked = hint_rows, hint_ptr, None     # what the superpixels, the prior and the geodesic see
+            segs = seg_ptr = None
             if hints.segs is not None:
                 segs, seg_ptr = eng.upload_strokes(hints.segs, hints.seg_ptr)
                 if hints.as_prior or hints.region or hints.geodesic is not None:
                     all_rows, all_ptr, clicked = self._with_stroke_pixels(eng, hints, hint_rows, seg.shape, segs, seg_ptr)
             if hints.as_prior:
                 prior = self._hints_as_prior(eng, hints, all_rows, all_ptr, seg, graphs, bgr, clicked)
+            dev = (hint_rows, hint_ptr, all_rows, all_ptr, segs, seg_ptr)
         probs = eng.predict_probs(self.model, graphs)
         trimap = eng.refine_trimap(probs, graphs.node_ptr, seg, bgr, threshold_fg, threshold_bg, filter_radius,
                                    1e-3, edge_aware)
         if timing is not None:
             timing["gcn_inference"] = tick() - t
         trimap = eng.seed_from_prior(trimap, prior, graphs.node_ptr, seg, 0.1)
+        self._paint_hints(eng, trimap, polys, hints, dev, bgr, seg, graphs.node_ptr)
+        return seg, graphs, probs, trimap
+
+    @staticmethod
+    def _paint_hints(eng, trimap, polys, hints, dev, bgr, seg, node_ptr):
+        """The user's edits as hard constraints on the seeded trimap, in place: polygons, then the clicks and strokes."""
         if polys is not None:                  # areas first: lassos, then fills; strokes and clicks are painted over them
             eng.apply_polygons(trimap, *eng.upload_polygons(*polys))
-        if hints is not None and hints.geodesic is not None:   # the guide is the caller's BGR batch, never gc_image
+        if hints is None:
+            return
+        hint_rows, hint_ptr, all_rows, all_ptr, segs, seg_ptr = dev
+        if hints.geodesic is not None:         # the guide is the caller's BGR batch, never gc_image
             eng.geodesic_hints(bgr, all_rows, all_ptr, hints.geodesic.radius, hints.geodesic.gamma, mask=trimap)
-        elif hints is not None and hints.segs is None:   # hard constraints: over the network's trimap and the seeding alike
-            eng.apply_hints(trimap, hint_rows, hint_ptr, hints.radius, hints.region, seg, graphs.node_ptr)
-        elif hints is not None:                # strokes: the superpixels under centre lines and clicks, the brush, the disks
+        elif hints.segs is None:               # hard constraints: over the network's trimap and the seeding alike
+            eng.apply_hints(trimap, hint_rows, hint_ptr, hints.radius, hints.region, seg, node_ptr)
+        else:                                  # strokes: the superpixels under centre lines and clicks, the brush, the disks
             if hints.region:
-                eng.apply_hints(trimap, all_rows, all_ptr, 0, True, seg, graphs.node_ptr)
+                eng.apply_hints(trimap, all_rows, all_ptr, 0, True, seg, node_ptr)
             eng.apply_strokes(trimap, segs, seg_ptr, hints.stroke_radius)
             if len(hints.rows):
                 eng.apply_hints(trimap, hint_rows, hint_ptr, hints.radius, False)
-        return seg, graphs, probs, trimap
 
     @staticmethod
     def _with_stroke_pixels(eng, hints, hint_rows, shape, segs, seg_ptr):
