@@ -20,8 +20,8 @@
 //    ascending cluster order, the clusters whose search window meets the tile
 //    (wave ballot + prefix compaction into LDS) and every pixel scans that list
 //    with a strict '>' — identical to the sequential "lowest k wins ties";
-//  * the centroid update is one lane per cluster walking its own window in
-//    raster order with float32 running sums — identical rounding to skimage;
+//  * the centroid update scans each cluster's own window in raster order and adds
+//    the members to float32 running sums in that order — identical rounding to skimage;
 //  * all arithmetic is compiled without FMA contraction.
 #include "ggc_internal.h"
 #include "ggc_math.h"
@@ -297,22 +297,51 @@ __global__ void __launch_bounds__(256) k_slic_assign(SlicGeom g, const float* __
 //  * a group of 8 lanes owns a cluster (8 clusters per wave, neighbours along the seed grid, so their windows
 //    and shapes are alike; 16 and 4 lanes measured slower): the group reads a window row as chunks of 8 consecutive
 //    labels, the loads of a whole row block — and those of the next one — in flight together (the scan is otherwise
-//    a chain of L2 round trips), a ballot marks the cluster's pixels, the matching lanes fetch their colours;
+//    a chain of L2 round trips), a ballot marks the cluster's pixels, the matching lanes fetch their colours (the
+//    fetches of a whole row block in flight together: nothing but the LDS stores below waits for them);
 //  * the coordinate sums are sums of small integers: exact in float32 in any order while they stay below 2^24, so
 //    they are taken as integer popcount / lane-local sums (a cluster that large falls back to the ordered loop);
-//  * the colour fold walks the set bits of each group's ballot in ascending x with one ds_bpermute per channel,
-//    all groups in the same wave instruction.  Same additions, same order, a fraction of the instructions.
+//  * COMPACT: a window is about 6 % members, so the colours are not folded where they are found.  A matching lane
+//    appends its three values to the group's list in LDS, at the list's length plus the number of matching lanes
+//    below it in the chunk: chunks and rows come in raster order, so the list holds the members in the order
+//    skimage adds them;
+//  * FOLD: when some group of the wave could not take another chunk (a wave-uniform test), and once after the scan,
+//    every group adds its list to the running sums front to back and empties it: lane 0, 1, 2 of the group keeps
+//    channel 0, 1, 2, so a member costs each of them one LDS read and one add, all groups in the same wave
+//    instruction.  Every member is added once, in order, to a sum that started at +0; the window's other pixels,
+//    which the kernel used to add as +0 (bit-neutral: a sum that starts at +0 never becomes -0), are not added at all.
+//    The lists are private to a wave, whose LDS traffic is in order: no block barrier.
+// LDS: a row of upd_buf is entry i of all 8 groups, 24 consecutive words, so the 12 addresses a half-wave reads in a fold
+// step lie in different banks, and the stores of one group's chunk go to rows 24 words apart (banks 0, 24, 16, 8 of 32).
 // Measured in round 3 and not kept (same label maps each time): (a) a MEMBER BOX per cluster, grown by k_slic_assign with
 // integer min / max (ballots per wave, a 64-slot LDS table per block, 4 global atomics per cluster and block) and scanned
 // here instead of the (4 step + 1)^2 window — this kernel 0.58 -> 0.44 ms per sweep, but the assignment 0.42 -> 0.60: the
 // scan is not what bounds the update, the ordered fold is; (b) one LANE per cluster walking its member box with plain
-// predicated adds — 0.60 ms per sweep: 64 clusters per wave-load are 32-64 cache lines.
+// predicated adds — 0.60 ms per sweep: 64 clusters per wave-load are 32-64 cache lines.  Until round 7 the fold ran in
+// registers: for every chunk with a member anywhere in the wave, each of the chunk's 8 lanes was broadcast in turn
+// (ds_swizzle) and added to every lane's copy of the sums, member or not — 24 swizzles and 24 adds per chunk, 16 times
+// the additions the result needs (the loop over the set bits that form had replaced spent 14 instructions per member).
+// Round 7, per launch at batch 256 (profiles/r07_ab_slic_update.txt): 0.42 ms with the fold in registers, 0.37 with lists
+// of 64 entries, 0.35 with 32 (16: 0.35, 128: 0.57 — 48 KB of LDS, 3 waves per SIMD), 0.32 once the first block is waited
+// for before the loop.  Measured and not kept, same results each time: all blocks of an image on one XCD (0.37 -> 0.37 at
+// 64 entries, 0.42 -> 0.41 with the old fold); THREE label blocks taking turns, two in flight, with straight-line label
+// loads (90 VGPRs, 0.36).  With the loop's counters in scalar registers a row without members costs 31 vector
+// instructions instead of about 55 and the launch takes the same 0.32 ms: since the lists, instruction issue no longer bounds it.
 constexpr int UPD_LANES = 8, UPD_GROUPS = 64 / UPD_LANES, UPD_CH = 8;
+constexpr int UPD_CAP = 32;                 // entries of a group's member list: 384 B per group, 12 KB per block
+constexpr int UPD_FOLD_UNROLL = 4;          // list entries whose LDS reads are in flight together
+static_assert(UPD_CAP >= 2 * UPD_LANES && UPD_CAP % UPD_FOLD_UNROLL == 0, "a fold per chunk, or fold reads past the list");
+
+__device__ __forceinline__ void upd_wave_sync() {    // LDS traffic of one wave is in order: only the compiler needs telling
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+}
 
 __global__ void __launch_bounds__(256) k_slic_update(SlicGeom g, const float* __restrict__ image,
                                                      const int32_t* __restrict__ labels,
                                                      const int32_t* __restrict__ stale,
                                                      float* __restrict__ centers, int4* __restrict__ bounds) {
+    __shared__ float upd_buf[4][UPD_CAP][UPD_GROUPS * 3];
     const int lane = threadIdx.x & 63, sub = lane / UPD_LANES, sl = lane % UPD_LANES;
     const int k = (blockIdx.x * 4 + (threadIdx.x >> 6)) * UPD_GROUPS + sub;
     const bool live = k < g.K;
@@ -323,8 +352,23 @@ __global__ void __launch_bounds__(256) k_slic_update(SlicGeom g, const float* __
     const size_t P = (size_t)g.H * g.W;
     const int32_t* lb = labels + (size_t)b * P;
     const float* im = image + (size_t)b * P * 3;
-    float s0 = 0.f, s1 = 0.f, s2 = 0.f;
+    float s = 0.f;                                          // running sum of channel min(sl, 2): lanes 3-7 shadow lane 2
     int cnt = 0, isy = 0, isx = 0;                          // isx: this lane's share, reduced at the end
+    int nbuf = 0;                                           // length of the group's member list
+    float* const put = &upd_buf[threadIdx.x >> 6][0][sub * 3];
+    const float* const get = put + min(sl, 2);
+    auto fold = [&]() {
+        upd_wave_sync();                                    // the wave's stores before its reads
+        for (int i = 0; __any(i < nbuf); i += UPD_FOLD_UNROLL) {
+            float v[UPD_FOLD_UNROLL];
+#pragma unroll
+            for (int u = 0; u < UPD_FOLD_UNROLL; ++u) v[u] = get[(i + u) * (UPD_GROUPS * 3)];
+#pragma unroll
+            for (int u = 0; u < UPD_FOLD_UNROLL; ++u) s += i + u < nbuf ? v[u] : 0.f;      // past the end: + (+0), bit-neutral
+        }
+        nbuf = 0;
+        upd_wave_sync();                                    // the reads before the next stores
+    };
     const int rows = bd.y - bd.x, chunks = (bd.w - bd.z + UPD_LANES - 1) / UPD_LANES;
     int rows_max = rows, chunks_max = chunks;               // the wave runs the longest of its four loops
 #pragma unroll
@@ -332,9 +376,12 @@ __global__ void __launch_bounds__(256) k_slic_update(SlicGeom g, const float* __
         rows_max = max(rows_max, __shfl_xor(rows_max, off, 64));
         chunks_max = max(chunks_max, __shfl_xor(chunks_max, off, 64));
     }
+    // the same in every lane: in scalar registers the loop's counters, the row and block numbers cost no vector instruction
+    rows_max = __builtin_amdgcn_readfirstlane(rows_max);
+    chunks_max = __builtin_amdgcn_readfirstlane(chunks_max);
     // labels of (row ry, chunks c0 .. c0 + UPD_CH - 1); -1 outside the group's window.  One pointer per lane and row, the
-    // chunks at constant offsets from it, the lane's number of chunks inside the window counted once (the kernel is bound by
-    // instruction issue: the per-chunk 64-bit index arithmetic was a third of the row's instructions)
+    // chunks at constant offsets from it, the lane's number of chunks inside the window counted once (the per-chunk 64-bit
+    // index arithmetic was a third of the row's instructions)
     const int32_t* lane_p = lb + (size_t)bd.x * g.W + bd.z + sl;
     const int nvc = (bd.w - bd.z - sl + UPD_LANES - 1) / UPD_LANES;           // chunks c with bd.z + c * UPD_LANES + sl < bd.w
     auto load_row = [&](int ry, int c0, int (&lab)[UPD_CH]) {
@@ -347,39 +394,51 @@ __global__ void __launch_bounds__(256) k_slic_update(SlicGeom g, const float* __
     const int nblk = (chunks_max + UPD_CH - 1) / UPD_CH, total = rows_max * nblk;
     int cur[UPD_CH], nxt[UPD_CH];
     if (total > 0) load_row(0, 0, cur);
+    // the first block has arrived when the loop is entered: with these loads still in flight at its top, the compiler waits
+    // there for everything, the loads of the next block issued just before included
+    asm volatile("" :: "v"(cur[0]), "v"(cur[1]), "v"(cur[2]), "v"(cur[3]), "v"(cur[4]), "v"(cur[5]), "v"(cur[6]), "v"(cur[7]));
     int ry = 0, cb = 0;
     for (int t = 0; t < total; ++t) {
         int ry_n = ry, cb_n = cb + 1;
         if (cb_n == nblk) { cb_n = 0; ++ry_n; }
-        load_row(ry_n, cb_n * UPD_CH, nxt);                 // next block in flight while this one is folded (row rows_max reads nothing)
-        const int y = bd.x + ry;
+        load_row(ry_n, cb_n * UPD_CH, nxt);                 // next block in flight while this one is compacted (row rows_max reads nothing)
+        bool hit[UPD_CH], some = false;
 #pragma unroll
-        for (int c = 0; c < UPD_CH; ++c) {
-            const bool hit = cur[c] == k && live;
-            const unsigned long long bal = __ballot(hit);
-            if (bal) {
-                const int x = bd.z + (cb * UPD_CH + c) * UPD_LANES + sl;
-                unsigned int m = (unsigned int)(bal >> (sub * UPD_LANES)) & ((1u << UPD_LANES) - 1u);
-                float v0 = 0.f, v1 = 0.f, v2 = 0.f;
-                if (hit) { const float* px = im + ((size_t)y * g.W + x) * 3; v0 = px[0]; v1 = px[1]; v2 = px[2]; isx += x; }
-                const int n = __popc(m);
-                cnt += n; isy += n * y;
-                // the chunk's 8 pixels in x order, every lane of the group keeping the same running sums: lane u's value is
-                // broadcast by ds_swizzle (no address register) and added unconditionally — a lane without a hit holds +0,
-                // and s + (+0) == s bit for bit (s never is -0: it starts at +0).  The loop over the set bits this replaces
-                // spent 14 instructions per member pixel on find-first-set, three ds_bpermute and the loop test.
-                static_assert(UPD_LANES == 8, "the broadcast pattern is written for groups of 8 lanes");
-#define GGC_UPD_STEP(U) { s0 += __int_as_float(__builtin_amdgcn_ds_swizzle(__float_as_int(v0), 0x18 | ((U) << 5))); \
-                          s1 += __int_as_float(__builtin_amdgcn_ds_swizzle(__float_as_int(v1), 0x18 | ((U) << 5))); \
-                          s2 += __int_as_float(__builtin_amdgcn_ds_swizzle(__float_as_int(v2), 0x18 | ((U) << 5))); }
-                GGC_UPD_STEP(0) GGC_UPD_STEP(1) GGC_UPD_STEP(2) GGC_UPD_STEP(3) GGC_UPD_STEP(4) GGC_UPD_STEP(5) GGC_UPD_STEP(6) GGC_UPD_STEP(7)
-#undef GGC_UPD_STEP
+        for (int c = 0; c < UPD_CH; ++c) { hit[c] = cur[c] == k && live; some |= hit[c]; }
+        if (__any(some)) {                                  // most rows of a window hold no member of any of the wave's clusters
+            const int y = bd.x + ry, x0 = bd.z + cb * UPD_CH * UPD_LANES + sl;
+            const float* px = im + ((size_t)y * g.W + x0) * 3;
+            // the members' colours of the whole block in flight together: the other lanes read the image's first pixel, so
+            // that the loads are straight-line code (a load inside a branch is waited for before the branch is left)
+            float v0[UPD_CH], v1[UPD_CH], v2[UPD_CH];
+#pragma unroll
+            for (int c = 0; c < UPD_CH; ++c) {
+                const float* q = hit[c] ? px + c * UPD_LANES * 3 : im;
+                v0[c] = q[0]; v1[c] = q[1]; v2[c] = q[2];
+            }
+#pragma unroll
+            for (int c = 0; c < UPD_CH; ++c) {
+                const unsigned long long bal = __ballot(hit[c]);
+                if (bal) {
+                    if (__any(nbuf > UPD_CAP - UPD_LANES)) fold();      // some list could not take a full chunk
+                    const unsigned int m = (unsigned int)(bal >> (sub * UPD_LANES)) & ((1u << UPD_LANES) - 1u);
+                    const int n = __popc(m);
+                    cnt += n; isy += n * y;
+                    if (hit[c]) {                           // ascending x inside the chunk
+                        float* e = put + (nbuf + __popc(m & ((1u << sl) - 1u))) * (UPD_GROUPS * 3);
+                        e[0] = v0[c]; e[1] = v1[c]; e[2] = v2[c];
+                        isx += x0 + c * UPD_LANES;
+                    }
+                    nbuf += n;
+                }
             }
         }
 #pragma unroll
         for (int c = 0; c < UPD_CH; ++c) cur[c] = nxt[c];
         ry = ry_n; cb = cb_n;
     }
+    fold();
+    const float s0 = __shfl(s, lane - sl, 64), s1 = __shfl(s, lane - sl + 1, 64), s2 = __shfl(s, lane - sl + 2, 64);
 #pragma unroll
     for (int off = 1; off < UPD_LANES; off <<= 1) isx += __shfl_xor(isx, off, 64);
     float sy = (float)isy, sx = (float)isx;
