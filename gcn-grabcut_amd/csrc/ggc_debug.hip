@@ -12,6 +12,7 @@ extern "C" int ggc_debug_read_scratch(ggc_ctx* ctx, const char* name, void* host
         {"grabcut_excess_sink_dist", ggc::S_GC_G},
         {"net_states", ggc::S_STATES}, {"net_xw", ggc::S_XW}, {"net_agg", ggc::S_AGG}, {"net_hjk", ggc::S_HJK},
         {"net_score", ggc::S_SCORE}, {"net_gvec", ggc::S_GVEC}, {"net_gate", ggc::S_GATE},
+        {"scissors_planes", ggc::S_SCISSORS},
     };
     for (auto& t : tab)
         if (std::strcmp(t.n, name) == 0) {

@@ -37,6 +37,7 @@ enum Slot : int {
     S_GEODESIC,
     S_STROKES,
     S_POLYGONS,
+    S_SCISSORS,
     S_COUNT
 };
 

@@ -12,7 +12,7 @@ from .data import Data, Batch
 from .grabcut import GrabCut, GrabCutConfig, Label
 from .graph_builder import (
     GraphBuilder, SuperpixelGraph, SuperpixelGraphConfig, compute_auto_prior, encode_user_hints, pack_hints,
-    encode_geodesic_hints, pack_strokes, pack_polygons,
+    encode_geodesic_hints, pack_strokes, pack_polygons, pack_paths,
 )
 from .metrics import (
     evaluate, evaluate_batch, evaluate_trimap, boundary_f1, noc_summary, SegmentationMetrics, TrimapMetrics,
@@ -26,7 +26,8 @@ from .pipeline import (GCNGrabCutPipeline, ClosedFormMatte, ForegroundColours, F
                        alpha_matte, clean_mask, closed_form_matte, estimate_foreground, guided_filter, refine_trimap,
                        closed_form_matte_full, lift_trimap, trimap_matte, trimap_matte_full,
                        trimap_matte_warm, upsample_mask, FullCut, cut_mask_full, lift_labels,
-                       GeodesicHints, geodesic_hints, paint_strokes, stroke_pixels, paint_polygons, polygon_mask)
+                       GeodesicHints, geodesic_hints, paint_strokes, stroke_pixels, paint_polygons, polygon_mask,
+                       Scissors, trace_boundary)
 from .synthetic import synthetic_image, synthetic_batch
 from .losses import FocalLoss, LabelSmoothingCE, TrimapLoss
 from .trainer import Trainer, TrainConfig
@@ -46,6 +47,7 @@ __all__ = [
     "GeodesicHints", "geodesic_hints", "encode_geodesic_hints",
     "pack_strokes", "paint_strokes", "stroke_pixels",
     "pack_polygons", "paint_polygons", "polygon_mask",
+    "pack_paths", "Scissors", "trace_boundary",
     "ResGCNNet", "GCNTrimapNet", "GATTrimapNet", "build_model", "probs_to_node_trimap", "project_to_pixels",
     "Data", "Batch", "synthetic_image", "synthetic_batch",
     "FocalLoss", "LabelSmoothingCE", "TrimapLoss", "Trainer", "TrainConfig",

@@ -284,6 +284,42 @@ class Engine:
                       _native.ptr(poly_label), image_ptr.data_ptr(), int(poly_label.numel()), mask.data_ptr())
         return mask
 
+    # ------------------------------------------------------------------ H4
+    def upload_paths(self, anchors, path_ptr, path_closed, image_ptr):
+        """pack_paths' (anchors [A,2], path_ptr [Q+1], path_closed [Q], image_ptr [B+1]) -> the same four arrays on the
+        device, in one host-to-device copy."""
+        ip, pp, pc, a = self._upload_packed([image_ptr, path_ptr, path_closed, anchors])
+        return a.view(-1, 2), pp, pc, ip
+
+    def trace_paths(self, bgr, anchors, path_ptr, path_closed, image_ptr, margin=16, edge_cap=2048, smooth=16, capacity=0):
+        """Intelligent scissors (ggc_trace_paths, include/ggc.h H4): bgr (B,H,W,3) uint8 is the guide, the four arrays
+        of upload_paths on the device -> (verts (V,2) int32 = row, col; vert_ptr (Q+1,) int32), both on the device and
+        in ggc_apply_polygons' packing.  capacity > 0 is a guess of V: the call fills a buffer of that many rows at once
+        and is repeated only when the guess was too small (vert_ptr is written either way); 0: one call counts, the
+        next fills."""
+        b, h, w, _ = bgr.shape
+        q = int(path_closed.numel())
+        vert_ptr = torch.zeros(q + 1, dtype=torch.int32, device=self.device)
+        if b == 0 or q == 0:
+            return self.empty(0, 2, dtype=torch.int32), vert_ptr
+        args = (self._stream(), b, h, w, bgr.data_ptr(), _native.ptr(anchors), path_ptr.data_ptr(), _native.ptr(path_closed),
+                image_ptr.data_ptr(), q, int(margin), int(edge_cap), int(smooth), vert_ptr.data_ptr())
+        if capacity > 0:
+            verts = self.empty(int(capacity), 2, dtype=torch.int32)
+            try:
+                self.ctx.call("ggc_trace_paths", *args, verts.data_ptr(), int(capacity))
+                return verts[:int(vert_ptr[-1].item())], vert_ptr
+            except _native.GGCError:
+                if int(vert_ptr[-1].item()) <= capacity:       # refused for another reason
+                    raise
+        else:
+            self.ctx.call("ggc_trace_paths", *args, None, 0)
+        n = int(vert_ptr[-1].item())
+        verts = self.empty(n, 2, dtype=torch.int32)
+        if n:
+            self.ctx.call("ggc_trace_paths", *args, verts.data_ptr(), n)
+        return verts, vert_ptr
+
     def next_click(self, pred, gt) -> torch.Tensor:
         """The next simulated click of the NoC protocol per image (ggc_next_click): pred, gt (B,H,W) uint8, nonzero =
         foreground -> (B,4) int32 on the device = row, col, label (1 = fg, 0 = bg), d2; (-1,-1,-1,0) where pred == gt."""

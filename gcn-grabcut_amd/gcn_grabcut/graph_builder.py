@@ -308,6 +308,48 @@ def pack_strokes(per_image) -> "tuple[np.ndarray, np.ndarray]":
     return _pack_rows(per_image, "strokes", "strokes", _stroke_segments, 5, "stroke segments")
 
 
+def scissors_list(scissors) -> list:
+    """The `scissors` argument of the public calls, one anchor list or a sequence of them (or None) -> a list of anchor lists."""
+    if scissors is None:
+        return []
+    if isinstance(scissors, (str, bytes)):
+        raise ValueError("scissors must be a sequence of (row, col) anchors, or a sequence of such sequences")
+    return [scissors] if _is_polygon(scissors) else list(scissors)
+
+
+def pack_paths(per_image, closed: bool = True) -> "tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]":
+    """Per-image anchor paths -> the (anchors, path_ptr, path_closed, image_ptr) arrays of ggc_trace_paths (include/ggc.h
+    H4); the sibling of pack_hints.
+
+    per_image: one entry per image, None (no paths) or a sequence of paths.  A path is a sequence of (row, col) anchors,
+    closed or open as `closed` says, or an (anchors, closed) pair with its own bool.  Returns anchors int32 [A,2], path_ptr
+    int32 [Q+1], path_closed int32 [Q] and image_ptr int32 [B+1].  An open path of fewer than 2 anchors, a closed one of
+    fewer than 3 or a wrong shape is a ValueError; whether an anchor lies inside its image is checked by the call."""
+    anchors, path_ptr, flags, image_ptr = [], [0], [], [0]
+    for b, entry in enumerate(per_image):
+        if entry is not None:
+            if isinstance(entry, (str, bytes)) or not hasattr(entry, "__len__"):
+                raise ValueError(f"paths[{b}] must be None or a sequence of paths")
+            for i, path in enumerate(entry):
+                what, c = f"paths[{b}][{i}]", bool(closed)
+                if isinstance(path, tuple) and len(path) == 2 and isinstance(path[1], (bool, np.bool_)):
+                    path, c = path[0], bool(path[1])
+                if isinstance(path, (str, bytes)):
+                    raise ValueError(f"{what} must be a sequence of (row, col) anchors")
+                v = _click_rows(path, 0, what)[:, :2]
+                if len(v) < (3 if c else 2):
+                    raise ValueError(f"{what} has {len(v)} anchors: {'a closed path needs at least 3' if c else 'an open path needs at least 2'}")
+                anchors.append(v)
+                path_ptr.append(path_ptr[-1] + len(v))
+                flags.append(int(c))
+        image_ptr.append(len(flags))
+    if path_ptr[-1] > np.iinfo(np.int32).max // 2:
+        raise ValueError(f"{path_ptr[-1]} anchors: too many for one call")
+    a = np.concatenate(anchors).astype(np.int32) if anchors else np.zeros((0, 2), np.int32)
+    return (np.ascontiguousarray(a.reshape(-1, 2)), np.asarray(path_ptr, np.int32), np.asarray(flags, np.int32),
+            np.asarray(image_ptr, np.int32))
+
+
 POLYGON_MAX_COORD = 1 << 20         # ggc_apply_polygons' limit on a vertex coordinate
 POLYGON_BG, POLYGON_FG, POLYGON_LASSO = 0, 1, 2
 

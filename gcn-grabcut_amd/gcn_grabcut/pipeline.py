@@ -21,7 +21,7 @@ import numpy as np
 
 from .grabcut import GrabCut, GrabCutConfig, Label
 from .graph_builder import (GraphBuilder, SuperpixelGraphConfig, graphs_to_host, _check_image, pack_hints, pack_strokes,
-                            pack_polygons, lasso_list)
+                            pack_polygons, lasso_list, pack_paths, scissors_list, POLYGON_LASSO)
 from .metrics import evaluate, evaluate_matte, evaluate_trimap, MatteMetrics, SegmentationMetrics, TrimapMetrics
 from .model import CLASS_BG, CLASS_FG, project_to_pixels  # noqa: F401
 
@@ -596,6 +596,102 @@ def polygon_mask(shape, polygon, device="cuda") -> np.ndarray:
     return paint_polygons(np.zeros((h, w), np.uint8), [polygon], device=device)
 
 
+@dataclass(frozen=True)
+class Scissors:
+    """The options of intelligent scissors (ggc_trace_paths, include/ggc.h H4).  margin in 0..256: how
+    far, in pixels, a traced segment may leave the bounding box of its two anchors; edge_cap in 1..13770: the gradient
+    at which an edge counts as fully strong; smooth in 1..64: the cost per step that does not depend on the image, which
+    keeps a path short on flat ground.  The defaults are recorded choices backed by §5.24's study table, not tuned
+    results."""
+    margin: int = 16
+    edge_cap: int = 2048
+    smooth: int = 16
+
+    def __post_init__(self):
+        for name, lo, hi in (("margin", 0, 256), ("edge_cap", 1, 13770), ("smooth", 1, 64)):
+            v = getattr(self, name)
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= int(v) <= hi:
+                raise ValueError(f"Scissors: {name} must be an integer in [{lo}, {hi}], got {v!r}")
+
+
+def _scissors_args(options) -> Scissors:
+    if options is None:
+        return Scissors()
+    if not isinstance(options, Scissors):
+        raise ValueError(f"scissors options must be a Scissors, got {type(options).__name__}")
+    return options
+
+
+def _vertex_guess(anchors: np.ndarray, n_paths: int) -> int:
+    """A guess of the number of traced vertices (Engine.trace_paths' capacity): four times the anchors' Chebyshev spans.
+    Too small a guess costs a second call, nothing else."""
+    spans = np.abs(np.diff(anchors.astype(np.int64), axis=0)).max(axis=1).sum() if len(anchors) > 1 else 0
+    return int(4 * spans + 64 * n_paths)
+
+
+def _trace_closed(eng, bgr, per_image, options: Scissors) -> "list[list[np.ndarray]]":
+    """per_image: one None, anchor list or sequence of anchor lists per image of bgr (B,H,W,3) on the device -> per image
+    the traced closed outlines, (n, 2) int32 arrays of (row, col).  An outline of fewer than 3 vertices is a ValueError."""
+    b, h, w = int(bgr.size(0)), int(bgr.size(1)), int(bgr.size(2))
+    if isinstance(per_image, (str, bytes)) or not hasattr(per_image, "__len__") or len(per_image) != b:
+        raise ValueError(f"scissors must have one entry per image of a batch of {b}")
+    anchors, path_ptr, closed, image_ptr = pack_paths([scissors_list(s) or None for s in per_image], closed=True)
+    if len(closed) == 0:
+        return [[] for _ in range(b)]
+    if ((anchors < 0) | (anchors >= np.array([h, w]))).any():
+        raise ValueError(f"a scissors anchor lies outside the {h}x{w} image")
+    verts, vert_ptr = eng.trace_paths(bgr, *eng.upload_paths(anchors, path_ptr, closed, image_ptr), options.margin,
+                                      options.edge_cap, options.smooth, capacity=_vertex_guess(anchors, len(closed)))
+    verts, vert_ptr = verts.cpu().numpy(), vert_ptr.cpu().numpy()
+    out = []
+    for i in range(b):
+        out.append([verts[vert_ptr[q]:vert_ptr[q + 1]] for q in range(image_ptr[i], image_ptr[i + 1])])
+        for k, v in enumerate(out[-1]):
+            if len(v) < 3:
+                raise ValueError(f"scissors path {k} of image {i} traces {len(v)} vertices: an outline needs at least 3")
+    return out
+
+
+def _merge_lassos(polys: "Optional[tuple]", traced: "list[list[np.ndarray]]") -> "Optional[tuple]":
+    """The traced outlines of a batch joined to its packed polygons (or None) as lassos -> packed polygons.  An image's
+    traced lassos come before its own polygons; lassos form a union and are painted before every fill, so their place
+    among the image's polygons does not matter."""
+    if not any(traced):
+        return polys
+    if polys is None:
+        return pack_polygons([((), (), t) if t else None for t in traced])
+    verts, pp, pl, ip = polys
+    v_out, p_out, l_out, i_out = [], [0], [], [0]
+    for i, t in enumerate(traced):
+        for v in list(t) + [verts[pp[q]:pp[q + 1]] for q in range(ip[i], ip[i + 1])]:
+            v_out.append(np.asarray(v, np.int32).reshape(-1, 2))
+            p_out.append(p_out[-1] + len(v))
+        l_out += [POLYGON_LASSO] * len(t) + [int(l) for l in pl[ip[i]:ip[i + 1]]]
+        i_out.append(len(l_out))
+    return (np.ascontiguousarray(np.concatenate(v_out), np.int32), np.asarray(p_out, np.int32), np.asarray(l_out, np.int32),
+            np.asarray(i_out, np.int32))
+
+
+def trace_boundary(image: np.ndarray, anchors, closed: bool = True, scissors: Optional[Scissors] = None,
+                   device="cuda") -> np.ndarray:
+    """Intelligent scissors on one image (additive; ggc_trace_paths, DESIGN.md §5.24).  image: (H, W, 3) uint8 BGR;
+    anchors: (row, col) pairs on the object's outline, in order, inside the image.  Consecutive anchors (and with
+    closed=True the last and the first) are joined by the cheapest 8-connected path along image edges that stays within
+    scissors.margin pixels of their bounding box.  -> the (n, 2) int32 pixels of the path, (row, col), in order: a
+    polygon that lasso= takes as it is."""
+    from ._engine import get_engine
+    img = _check_image(image)
+    opt = _scissors_args(scissors)
+    packed = pack_paths([[(anchors, bool(closed))]])
+    h, w = img.shape[:2]
+    if ((packed[0] < 0) | (packed[0] >= np.array([h, w]))).any():
+        raise ValueError(f"trace_boundary: an anchor lies outside the {h}x{w} image")
+    eng = get_engine(device)
+    verts, _ = eng.trace_paths(eng.to_device(img[None]), *eng.upload_paths(*packed), opt.margin, opt.edge_cap, opt.smooth,
+                               capacity=_vertex_guess(packed[0], 1))
+    return verts.cpu().numpy()
+
+
 def lift_labels(mask: np.ndarray, full_shape, band: Optional[int] = None, device="cuda") -> np.ndarray:
     """A working-size mask carried to a larger size as GrabCut labels for a banded cut there (additive; ggc_lift_labels,
     DESIGN.md §5.18).  The mask is interpolated bilinearly (half-pixel centres, as upsample_mask) and thresholded at 0.5;
@@ -770,6 +866,12 @@ def _host_packed(arg, b: int, name: str, width: int, pack, n_arrays: int, offset
     return tuple(np.ascontiguousarray(a, np.int32) for a in arrays)
 
 
+def _packed_polygons(polygons, b: int) -> "Optional[tuple]":
+    """The polygons argument of a batch of b images -> (verts, poly_ptr, poly_label, image_ptr) on the host, or None."""
+    return _host_packed(polygons, b, "polygons", 2, pack_polygons, 4,
+                        lambda a: [(a[3], "image_ptr", b, len(a[2]), 0), (a[1], "poly_ptr", len(a[2]), len(a[0]), 3)])
+
+
 def _slice_csr(rows, ptr, lo: int, hi: int):
     """The ranges lo .. hi-1 of a packed list -> (their rows, their offsets from 0)."""
     k0, k1 = int(ptr[lo]), int(ptr[hi])
@@ -803,8 +905,7 @@ class _Hints:
         geodesic = _geodesic_args(geodesic, region)
         stroked = _host_packed(strokes, b, "strokes", 5, pack_strokes, 2, lambda a: [(a[1], "stroke_ptr", b, len(a[0]), 0)])
         segs, seg_ptr = stroked if stroked is not None and len(stroked[0]) else (None, None)
-        polys = _host_packed(polygons, b, "polygons", 2, pack_polygons, 4,
-                             lambda a: [(a[3], "image_ptr", b, len(a[2]), 0), (a[1], "poly_ptr", len(a[2]), len(a[0]), 3)])
+        polys = _packed_polygons(polygons, b)
         if polys is not None and len(polys[0]) == 0:
             polys = None
         if segs is not None:
@@ -1280,7 +1381,7 @@ class GCNGrabCutPipeline:
                              hints_as_prior: bool = False, return_state: bool = False, matte: bool = False,
                              matte_radius: int = MATTE_RADIUS, matte_eps: float = MATTE_EPS, full_bgr=None,
                              foreground=False, full_cut=False, geodesic=False, strokes=None, stroke_radius: int = 3,
-                             polygons=None) -> dict:
+                             polygons=None, scissors=None, scissors_options=None) -> dict:
         """bgr: (B,H,W,3) uint8 tensor on the pipeline's device.  Returns device tensors.
 
         matte=True (additive) also returns "alpha" (B,H,W) float32, the soft matte of the cleaned mask (alpha_matte with
@@ -1341,6 +1442,14 @@ class GCNGrabCutPipeline:
         hints_as_prior or the geodesic sources.  A batch without polygons launches exactly what it did before, and an
         image without polygons in a batch that has some gets the outputs it gets without them, bit for bit.
 
+        Intelligent scissors (additive): scissors is None or a list with, per image, None, one anchor
+        list ((row, col) pairs on the object's outline, in order, inside the image) or a sequence of anchor lists;
+        scissors_options is a Scissors (None: its defaults).  Each anchor list is traced as a closed path on bgr, the
+        working-size BGR image and never GrabCutConfig's colour-space image (ggc_trace_paths), and the traced outlines
+        join the image's lassos: the union rule above applies and they are painted where lassos are painted, so the
+        result equals that of passing trace_boundary's polygons as lassos.  An outline of fewer than 3 vertices is a
+        ValueError.  A batch without scissors launches exactly what it did before.
+
         Large batches run as a software pipeline (additive, same results): the batch is cut into `chunks` contiguous
         chunks; the front stages of chunk k+1 run on the caller's stream while the GrabCut / clean-up of chunk k runs on a
         lane of its own (private context, stream and host thread).  Images are independent and image b keeps seed + b, so
@@ -1350,6 +1459,9 @@ class GCNGrabCutPipeline:
         b = bgr.size(0)
         want = self.grabcut_lanes if grabcut_lanes is None else int(grabcut_lanes)   # (an argument, so that concurrent callers do not mutate the pipeline)
         n_chunks = self.chunks if chunks is None else int(chunks)
+        if scissors is not None:                   # traced once for the whole batch; from here on they are lassos
+            polygons = _merge_lassos(_packed_polygons(polygons, b),
+                                     _trace_closed(eng, bgr, scissors, _scissors_args(scissors_options)))
         hints = _Hints.of(hints, b, hint_radius, hint_region, hints_as_prior, geodesic, strokes, stroke_radius, polygons)
         plan = _OutputPlan.of(self, bgr.shape, None if full_bgr is None else full_bgr.shape, compose=compose,
                               min_area_ratio=min_area_ratio, keep_largest=keep_largest, matte=matte, matte_radius=matte_radius,
@@ -1491,11 +1603,12 @@ class GCNGrabCutPipeline:
         return out
 
     def segment_batch(self, images: Sequence[np.ndarray], hints=None, full_images=None, strokes=None, polygons=None,
-                      **kwargs) -> list[SegmentationResult]:
+                      scissors=None, **kwargs) -> list[SegmentationResult]:
         """Segment equally sized BGR images as one batch (additive API).  hints: one None or (fg_points, bg_points) per
         image, with hint_radius / hint_region / hints_as_prior / geodesic among kwargs (segment_batch_device).  strokes:
         one None or (fg_strokes, bg_strokes) per image, with stroke_radius among kwargs (segment_batch_device).  polygons:
-        one None or (fg_polygons, bg_polygons, lassos) per image (segment_batch_device).  full_images
+        one None or (fg_polygons, bg_polygons, lassos) per image (segment_batch_device).  scissors: one None, anchor list
+        or sequence of anchor lists per image, with scissors_options among kwargs (segment_batch_device).  full_images
         (additive): the same images at one larger size each, (H1, W1, 3) uint8 BGR; every result's `full` then holds the
         outputs at that size (segment_batch_device's full_bgr).  foreground=True | ForegroundColours(...) among kwargs
         (with a matte) fills every result's foreground and rgba_clean.  full_cut=True | FullCut(...) among kwargs (with
@@ -1524,6 +1637,8 @@ class GCNGrabCutPipeline:
             kwargs["strokes"] = strokes
         if polygons is not None:
             kwargs["polygons"] = polygons
+        if scissors is not None:
+            kwargs["scissors"] = scissors
         out = self.segment_batch_device(bgr, timing=timing, hints=hints, full_bgr=full_bgr, **kwargs)
         out.update({k: out[k].cpu() for k in _REFERENCE_FIELDS + _ADDITIVE_FIELDS if k in out})      # one copy per output, not one per image
         per_image = {k: v / len(imgs) for k, v in timing.items()}
@@ -1661,7 +1776,8 @@ class GCNGrabCutPipeline:
                 matte_radius: int = MATTE_RADIUS, matte_eps: float = MATTE_EPS,
                 full_image: Optional[np.ndarray] = None, foreground=False, full_cut=False,
                 geodesic=False, fg_strokes=None, bg_strokes=None, stroke_radius: int = 3,
-                lasso=None, fg_polygons=None, bg_polygons=None) -> SegmentationResult:
+                lasso=None, fg_polygons=None, bg_polygons=None, scissors=None,
+                scissors_options: Optional[Scissors] = None) -> SegmentationResult:
         """Full pipeline on one BGR image (reference pipeline.py:265-352).
 
         Additive: fg_points / bg_points are user clicks, (row, col) pairs, applied as hard constraints on the trimap
@@ -1678,7 +1794,9 @@ class GCNGrabCutPipeline:
         stroke_radius as hard constraints before the clicks (segment_batch_device's strokes); lasso, one polygon or a
         sequence of polygons of (row, col) vertices, makes everything outside all of them definite background, and
         fg_polygons / bg_polygons are filled areas of definite labels, all before strokes and clicks
-        (segment_batch_device's polygons)."""
+        (segment_batch_device's polygons); scissors, one list of (row, col) anchors on the object's outline or a
+        sequence of such lists, is traced along the image's edges into closed outlines that join the lassos
+        (intelligent scissors with scissors_options, a Scissors; segment_batch_device's scissors)."""
         image = _check_image(image)
         full = None if full_image is None else _check_image(full_image)
         _OutputPlan.of(self, (1, *image.shape), None if full is None else (1, *full.shape), min_area_ratio=min_area_ratio,
@@ -1697,7 +1815,8 @@ class GCNGrabCutPipeline:
                                         hints=hints, hint_radius=hint_radius, hint_region=hint_region,
                                         hints_as_prior=hints_as_prior, matte=matte, matte_radius=matte_radius,
                                         matte_eps=matte_eps, full_bgr=full_bgr, foreground=foreground, full_cut=full_cut,
-                                        geodesic=geodesic, strokes=strokes, stroke_radius=stroke_radius, polygons=polygons)
+                                        geodesic=geodesic, strokes=strokes, stroke_radius=stroke_radius, polygons=polygons,
+                                        scissors=None if scissors is None else [scissors], scissors_options=scissors_options)
         return _result(out, 0, image, timing)
 
     def segment_bbox(self, image: np.ndarray, bbox: tuple[int, int, int, int], matte: bool = False,
@@ -1734,6 +1853,18 @@ class GCNGrabCutPipeline:
         return SegmentationResult(image=image, binary_mask=binary_mask, trimap=trimap,
                                   segments=np.zeros((H, W), dtype=np.int32), overlay=gc.overlay_mask(),
                                   rgba=gc.crop_foreground(), **extra)
+
+    def segment_scissors(self, image: np.ndarray, anchors, scissors_options: Optional[Scissors] = None,
+                         **kwargs) -> SegmentationResult:
+        """Classical GrabCut from a few anchors on the object's outline (additive; the sibling of segment_lasso, no
+        network).  anchors: one list of (row, col) anchors or a sequence of such lists; each is traced
+        into a closed outline by intelligent scissors (trace_boundary with scissors_options) on the BGR image, and the
+        outlines are segment_lasso's polygons (GrabCut.run_with_lasso).  kwargs are segment_lasso's."""
+        image = _check_image(image)
+        traced = _trace_closed(self._eng, self._eng.to_device(image[None]), [anchors], _scissors_args(scissors_options))[0]
+        if not traced:
+            raise ValueError("segment_scissors needs at least one anchor list")
+        return self.segment_lasso(image, traced, **kwargs)
 
     def segment_lasso(self, image: np.ndarray, polygon, matte: bool = False, matte_radius: int = MATTE_RADIUS,
                       matte_eps: float = MATTE_EPS, full_image: Optional[np.ndarray] = None, foreground=False,

@@ -51,7 +51,9 @@
 extern "C" {
 #endif
 
-#define GGC_VERSION 406 /* 0.4.6: ggc_apply_polygons (lassos and filled polygons as hard constraints: one exact integer point-in-polygon
+#define GGC_VERSION 407 /* 0.4.7: ggc_trace_paths (intelligent scissors: a few boundary anchors joined by the cheapest path along image
+                                  edges, as vertices in ggc_apply_polygons' packing; additive, no existing entry changes);
+                           0.4.6: ggc_apply_polygons (lassos and filled polygons as hard constraints: one exact integer point-in-polygon
                                   rule, even-odd with a closed boundary; additive, no existing entry changes);
                            0.4.5: ggc_apply_strokes, ggc_stroke_pixels (brush strokes as hard constraints: polylines painted as capsules by
                                   one exact integer rule, and their centre lines as a click list; additive, no existing entry changes);
@@ -516,6 +518,53 @@ int ggc_stroke_pixels(ggc_ctx* ctx, ggc_stream stream, int B, int H, int W, cons
  * any launch.  SYNCHRONISES the stream: the four arrays are read back and checked on the host. */
 int ggc_apply_polygons(ggc_ctx* ctx, ggc_stream stream, int B, int H, int W, const int32_t* verts, const int32_t* poly_ptr,
                        const int32_t* poly_label, const int32_t* image_ptr, int P, uint8_t* mask);
+
+/* H4 — intelligent scissors (additive; live-wire, Mortensen & Barrett 1995): the user clicks a few anchors on an object's
+ * outline and consecutive anchors are joined by the cheapest 8-connected path along image edges.  One exact integer
+ * definition; no float is involved anywhere.
+ *   bgr         [dev] u8  [B,H,W,3] the images (the guide)
+ *   anchors     [dev] i32 [A,2] = (row, col), grouped by path, every anchor inside its image
+ *   path_ptr    [dev] i32 [Q+1]  path q owns anchors[path_ptr[q] .. path_ptr[q+1]); path_ptr[0] = 0, A = path_ptr[Q]
+ *   path_closed [dev] i32 [Q]    0 = open (at least 2 anchors), 1 = closed (at least 3)
+ *   image_ptr   [dev] i32 [B+1]  image b owns paths image_ptr[b] .. image_ptr[b+1); image_ptr[0] = 0, image_ptr[B] = Q
+ *   margin 0 .. 256      edge_cap 1 .. 13 770      smooth 1 .. 64
+ *   vert_ptr_out [dev] i32 [Q+1] out, always written: path q owns rows vert_ptr_out[q] .. vert_ptr_out[q+1)
+ *   verts_out    [dev] i32 [capacity,2] out = (row, col), or NULL: only the counts are produced (call once with NULL, allocate
+ *                vert_ptr_out[Q] rows, call again: the pattern of ggc_stroke_pixels).  The pair is exactly ggc_apply_polygons'
+ *                verts and poly_ptr: a traced batch goes into the painter without repacking.
+ * Guide: S_c(y,x) is H1's 3x3 box sum with replicated border.  The gradient is
+ *   G(p) = sum over c of |S_c(y, x+1) - S_c(y, x-1)| + |S_c(y+1, x) - S_c(y-1, x)|,
+ * the coordinates clamped into the image, 0 .. 6 * 2295 = 13 770.  The flatness is F(p) = ((edge_cap - min(G(p), edge_cap)) * 255)
+ * / edge_cap, floor division: 0 on a strong edge, 255 on flat ground.
+ * Arcs: the grid is 8-connected and c(p,q) = L(p,q) * (smooth + F(p) + F(q)), L = 80 axial, 113 diagonal (H1's step lengths);
+ * symmetric, at least 80.
+ * Segments: an open path of n anchors has the n - 1 segments a_i -> a_(i+1); a closed one n segments, the last a_(n-1) -> a_0.
+ * A segment's WINDOW is the bounding box of its two anchors grown by `margin` pixels on every side and clipped to the image;
+ * the cheapest path is sought inside the window only.  Consecutive anchors are at most 1024 apart (Chebyshev).
+ * Distance: for segment a -> b, D(p) = cost of the cheapest path inside the window from p to b; D(b) = 0.  D is unique
+ * whatever the relaxation order.
+ * Ranges: an arc is at most 113 * (64 + 510) = 64 862; a window side is at most 1024 + 1 + 512 = 1537 pixels and every window
+ * pixel reaches b in at most 1536 arcs (king moves inside the box), so D <= 1536 * 64 862 < 2^27.  "Unreached" is 2^30 and an arc
+ * that leaves the window costs 2^29, so every sum the relaxation forms stays at or below 2^30 + 2^29: everything fits int32.
+ * Path: starting at p = a, while p != b: emit p, then move to the first neighbour q, in the order N, NE, E, SE, S, SW, W, NW
+ * (N = row - 1, E = col + 1), that lies in the window and has D(q) + c(p,q) == D(p).  D falls by at least 80 per step, so the
+ * walk ends, and it is unique because D is.  A segment contributes its pixels from a inclusive to b exclusive; an open path
+ * appends its last anchor; a segment with a == b contributes nothing.  The vertices of path q are its segments' pixels in
+ * order.  Every path's result equals that of its single-image, single-path call bit for bit.
+ * B == 0 or Q == 0 is a no-op: nothing is written.  Otherwise, before any launch: H or W outside 1..65535 or B outside
+ * 0..65535 is GGC_E_SHAPE; GGC_E_INVALID_ARG for a negative Q, a parameter out of range, a NULL pointer (verts_out excepted),
+ * image_ptr or path_ptr not starting at 0 or decreasing, image_ptr[B] != Q, path_closed outside {0, 1}, an open path of fewer
+ * than 2 or a closed one of fewer than 3 anchors, an anchor outside its image, consecutive anchors more than 1024 apart, windows
+ * that hold more than 2^26 pixels or more than 2^21 tiles of 32x32 in all, and (after the counting pass) a non-NULL verts_out
+ * with capacity < vert_ptr_out[Q], with nothing written to verts_out.
+ * The relaxation runs in rounds, one launch each; past 1024 * (tiles of the largest window) + 2 rounds it returns
+ * GGC_E_DEVICE "scissors did not converge" (it cannot hang).  Scratch: 5 bytes per window pixel, 16 per tile, 72 per segment;
+ * ggc_debug_read_scratch "scissors_planes" reads the D planes of the last call, segment after segment in path order, each its
+ * window row-major, i32.  SYNCHRONISES the stream: the four input arrays, the work-list length every few rounds and the vertex
+ * total are read back. */
+int ggc_trace_paths(ggc_ctx* ctx, ggc_stream stream, int B, int H, int W, const uint8_t* bgr, const int32_t* anchors,
+                    const int32_t* path_ptr, const int32_t* path_closed, const int32_t* image_ptr, int Q, int margin, int edge_cap,
+                    int smooth, int32_t* vert_ptr_out, int32_t* verts_out, int64_t capacity);
 
 /* C0 — next simulated click per image (additive; the standard NoC protocol of interactive segmentation).
  *   pred [dev] u8  [B,H,W]  current binary mask (nonzero = foreground)

@@ -9,6 +9,7 @@ Same command line as the reference's inference.py (flags :26-56, outputs :146-15
     python3 inference.py --image cat.jpg --fg-point 120,200 --bg-point 10,10 --hint-radius 8
     python3 inference.py --image cat.jpg --bg-stroke "40,10 40,200 90,260" --stroke-radius 4   # a brush stroke of three vertices
     python3 inference.py --image cat.jpg --lasso "20,30 20,300 260,300 260,30"   # everything outside the outline is background
+    python3 inference.py --image cat.jpg --scissors "40,60 30,220 200,260 230,80"   # four anchors on the outline, traced into a lasso
     python3 inference.py --image cat.jpg --save mask alpha cutout          # soft edges: alpha matte and cut-out
     python3 inference.py --image big.jpg --full-res --save mask cutout     # outputs at the photo's own size
     python3 inference.py --image big.jpg --full-res --full-mask cut --save mask   # ... the mask cut again on the photo's pixels
@@ -82,6 +83,17 @@ def build_parser() -> argparse.ArgumentParser:
                         help="Filled foreground polygon of at least 3 vertices in original-image pixels (repeatable; needs --image)")
     parser.add_argument("--bg-polygon", action="append", type=_polygon, default=[], metavar='"ROW,COL ROW,COL ..."',
                         help="Filled background polygon of at least 3 vertices in original-image pixels (repeatable; needs --image)")
+    # additive: intelligent scissors (ggc_trace_paths): a few anchors on the outline, traced into a lasso
+    parser.add_argument("--scissors", action="append", type=_polygon, default=[], metavar='"ROW,COL ROW,COL ..."',
+                        help="Anchors on the object's outline, at least 3, in order and in original-image pixels: they are "
+                             "joined along the image's edges into a closed outline that acts as a lasso (repeatable; "
+                             "needs --image)")
+    parser.add_argument("--scissors-margin", type=int, default=16,
+                        help="Pixels, 0..256, that a traced segment may leave the bounding box of its two anchors")
+    parser.add_argument("--scissors-edge-cap", type=int, default=2048,
+                        help="Gradient, 1..13770, at which an edge counts as fully strong")
+    parser.add_argument("--scissors-smooth", type=int, default=16,
+                        help="Cost per step, 1..64, that does not depend on the image: larger keeps the outline shorter")
     # additive: soft alpha matte of the mask (ggc_alpha_matte), computed when --save asks for alpha or cutout
     parser.add_argument("--matte-radius", type=int, default=4,
                         help="Window radius of the alpha matte, 1..64, in pixels of the image as segmented")
@@ -220,6 +232,15 @@ def main() -> None:
         parser.error("--fg-stroke / --bg-stroke are strokes on one image: use them with --image, not --input")
     if (args.lasso or args.fg_polygon or args.bg_polygon) and not args.image:
         parser.error("--lasso / --fg-polygon / --bg-polygon are polygons on one image: use them with --image, not --input")
+    scissors_options = None
+    if args.scissors:
+        if not args.image:
+            parser.error("--scissors are anchors on one image: use them with --image, not --input")
+        from src.gcn_grabcut import Scissors
+        try:
+            scissors_options = Scissors(args.scissors_margin, args.scissors_edge_cap, args.scissors_smooth)
+        except ValueError as e:
+            parser.error(str(e))
     if not 0 <= args.stroke_radius <= 16384:
         parser.error("--stroke-radius must be in 0..16384")
     if args.hint_radius < 0:
@@ -314,7 +335,7 @@ def main() -> None:
             t0 = time.perf_counter()
             hint_kw = {}
             polygons = args.lasso or args.fg_polygon or args.bg_polygon
-            if args.fg_point or args.bg_point or args.fg_stroke or args.bg_stroke or polygons:   # --image only: one chunk of one image
+            if args.fg_point or args.bg_point or args.fg_stroke or args.bg_stroke or polygons or args.scissors:   # --image only: one chunk of one image
                 from PIL import Image
                 path, image, _ = chunk[0]
                 with Image.open(path) as im:
@@ -331,6 +352,9 @@ def main() -> None:
                     hint_kw.update(polygons=[([scale_points(p, orig_hw, image.shape[:2]) for p in args.fg_polygon],
                                               [scale_points(p, orig_hw, image.shape[:2]) for p in args.bg_polygon],
                                               [scale_points(args.lasso, orig_hw, image.shape[:2])] if args.lasso else [])])
+                if args.scissors:
+                    hint_kw.update(scissors=[[scale_points(a, orig_hw, image.shape[:2]) for a in args.scissors]],
+                                   scissors_options=scissors_options)
                 if args.hint_mode == "geodesic":
                     from src.gcn_grabcut import GeodesicHints
                     hint_kw.update(geodesic=GeodesicHints(args.geodesic_radius, args.hint_gamma))
