@@ -1,47 +1,32 @@
 // ggc_scissors.hip — H4: intelligent scissors (live-wire).  Consecutive anchors of a path are joined by the cheapest
 // 8-connected path along image edges inside a bounded window (include/ggc.h has the exact integer definition).  Everything
-// is int32; D is the unique fixed point of d(p) = min(d(p), min_q d(q) + c(p,q)) with d(b) = 0, so it does not depend on the
-// order in which tiles or pixels are relaxed, and the walk over D is a pure function of D.
+// is int32; D is the fixed point with d(b) = 0 that ggc_relax.h computes by tile relaxation, whatever the order of the
+// visits, and the walk over D is a pure function of D.
 //
 //   k_sc_guide   one workgroup per 32x32 window tile: the 36x36 pixels around the tile staged in LDS, the 3x3 box sums S
 //                of the 34x34 positions the gradient reads, then G and the flatness F, one byte per window pixel.  The
 //                same launch fills the segment's distance plane: 0 at b, 2^30 ("unreached") elsewhere.
-//   k_sc_round   one launch per round, one workgroup per listed (segment, tile) (grid-stride).  ggc_geodesic.hip's visit
-//                with one plane: F and D of tile + halo staged in LDS at row stride 35, the four arc-cost tables built
-//                from F (an arc with an end outside the window costs 2^29), then alternating column and row sweeps, in
-//                place, to the tile's fixed point against the fixed halo.  All 256 lanes belong to the one plane: lane =
-//                (run of 4 pixels, line), 8 runs x 32 lines, so each 32-lane half of a wave holds one run index and 32
-//                lines: conflict-free at the odd stride in both directions, every pixel has one writer per sweep, and no
-//                lane idles (8-pixel runs as in the geodesic visit would leave half of them without work).  Lowered pixels
-//                go back with plain stores; a lowered border pixel lists the neighbouring tiles of its window for the
-//                next round through a per-tile stamp (integer atomics only).
+//   k_sc_round   one round of ggc_relax.h with one plane (PLANES = 1, so all 256 lanes belong to it): F and D of tile + halo
+//                staged in LDS, the four arc-cost tables built from F, the visit.  A pixel outside the window holds
+//                RX_BLOCKED = 2^29 in LDS: min(2^29, D(q) + 2^29) leaves it alone, and 2^29 + 2^29 = 2^30 lowers no pixel of
+//                the window; the largest sum formed is 2^30 + 2^29.
 //   k_sc_walk    one wave per segment, from a towards b: lanes 0..7 load the eight candidates, a ballot picks the first
 //                in the order N, NE, E, SE, S, SW, W, NW with D(q) + c(p,q) == D(p); D and F of the chosen neighbour
 //                travel by shuffle, so a step is one dependent pair of loads.  Run twice: counting, then filling.
 //   k_sc_scan    one workgroup: segment counts -> segment offsets and vert_ptr_out.
 // The first work list, the segment table and the tile -> segment table are built on the host from the anchors, which it
 // has read back for the checks anyway.
-#include "ggc_internal.h"
-#include <algorithm>
+#include "ggc_relax.h"
 #include <climits>
 
 namespace ggc {
 namespace {
 
-constexpr int SC_T = 32, SC_H = SC_T + 2;              // tile edge, with halo
-constexpr int SC_S = SC_H + 1;                         // LDS row stride: odd, so 32 rows of a row sweep fall into 32 banks
-constexpr int SC_N = SC_H * SC_S;
-constexpr int SC_THREADS = 256;
-constexpr int SC_AXIAL = 80, SC_DIAG = 113;
 constexpr int SC_UNREACHED = 1 << 30;
-// An arc that leaves the window.  A pixel outside the window holds SC_BLOCKED in LDS: min(2^29, D(q) + 2^29) leaves it
-// alone, and 2^29 + 2^29 = 2^30 lowers no pixel of the window; the largest sum formed is 2^30 + 2^29.
-constexpr int SC_BLOCKED = 1 << 29;
-constexpr int SC_MAX_SWEEPS = SC_T * SC_T + 1;         // as GEO_MAX_SWEEPS: a sweep that changes something settles a pixel
 constexpr int SC_MAX_MARGIN = 256, SC_MAX_EDGE_CAP = 13770, SC_MAX_SMOOTH = 64, SC_MAX_SPAN = 1024;
 constexpr int64_t SC_MAX_AREA = (int64_t)1 << 26;      // window pixels of one call: 256 MiB of distance planes
 constexpr int64_t SC_MAX_TILES = (int64_t)1 << 21;
-constexpr int SC_PX = SC_T + 4;                        // staged pixels per tile side: the tile, the gradient's and the box's reach
+constexpr int SC_PX = RX_T + 4;                        // staged pixels per tile side: the tile, the gradient's and the box's reach
 
 struct ScSeg {                                         // one segment a -> b; 16 words
     int b, ar, ac, br, bc;                             // image, anchors (image coordinates)
@@ -56,22 +41,21 @@ struct ScWork {
     const int32_t* tile_seg;     // tile -> segment
     int32_t* plane;              // the segments' distance planes, one after the other, each its window row-major
     uint8_t* F;                  // flatness, same layout
-    int32_t* stamp;              // per tile: 1 + the round it is listed for, 0 = never listed by a visit
-    int32_t* list[2];            // ping-pong work lists
-    int32_t* cnt;                // [0..2] list lengths of rounds r, r+1, r+2 (mod 3), [3] a walk found no successor
+    RelaxLists q;                // no `touched`; list[0] starts as the host's first list
+    int32_t* lost;               // set when a walk found no successor
 };
 
-__global__ void __launch_bounds__(SC_THREADS) k_sc_guide(int H, int W, int edge_cap, int n_tiles, const uint8_t* __restrict__ bgr,
+__global__ void __launch_bounds__(RX_THREADS) k_sc_guide(int H, int W, int edge_cap, int n_tiles, const uint8_t* __restrict__ bgr,
                                                          ScWork w) {
     __shared__ uint8_t s_px[SC_PX * SC_PX * 3];
-    __shared__ uint16_t s_S[3][SC_H * SC_H];
+    __shared__ uint16_t s_S[3][RX_H * RX_H];
     const int tid = threadIdx.x;
     for (int tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {       // block-uniform
         const ScSeg g = w.seg[w.tile_seg[tile]];
         const int tr = tile - g.tile_base, tyi = tr / g.tiles_x, txi = tr - tyi * g.tiles_x;
-        const int ty0 = g.y0 + tyi * SC_T, tx0 = g.x0 + txi * SC_T;
+        const int ty0 = g.y0 + tyi * RX_T, tx0 = g.x0 + txi * RX_T;
         const uint8_t* img = bgr + (size_t)g.b * H * W * 3;
-        for (int i = tid; i < SC_PX * SC_PX; i += SC_THREADS) {           // pixel (ty0 - 2 + hy, tx0 - 2 + hx), clamped
+        for (int i = tid; i < SC_PX * SC_PX; i += RX_THREADS) {           // pixel (ty0 - 2 + hy, tx0 - 2 + hx), clamped
             const int hy = i / SC_PX, hx = i - hy * SC_PX;
             const uint8_t* px = img + 3 * ((size_t)min(max(ty0 - 2 + hy, 0), H - 1) * W + min(max(tx0 - 2 + hx, 0), W - 1));
             s_px[3 * i] = px[0]; s_px[3 * i + 1] = px[1]; s_px[3 * i + 2] = px[2];
@@ -79,8 +63,8 @@ __global__ void __launch_bounds__(SC_THREADS) k_sc_guide(int H, int W, int edge_
         __syncthreads();
         // S at (ty0 - 1 + sy, tx0 - 1 + sx).  Right for positions inside the image, where clamping the nine pixels is the
         // definition; the gradient clamps its own coordinates first, so it reads no other position.
-        for (int i = tid; i < SC_H * SC_H; i += SC_THREADS) {
-            const int sy = i / SC_H, sx = i - sy * SC_H;
+        for (int i = tid; i < RX_H * RX_H; i += RX_THREADS) {
+            const int sy = i / RX_H, sx = i - sy * RX_H;
             int s0 = 0, s1 = 0, s2 = 0;
 #pragma unroll
             for (int dy = 0; dy < 3; ++dy)
@@ -103,8 +87,8 @@ __global__ void __launch_bounds__(SC_THREADS) k_sc_guide(int H, int W, int edge_
             int G = 0;
 #pragma unroll
             for (int c = 0; c < 3; ++c)
-                G += abs((int)s_S[c][iy * SC_H + ixp] - (int)s_S[c][iy * SC_H + ixm]) +
-                     abs((int)s_S[c][iyp * SC_H + ix] - (int)s_S[c][iym * SC_H + ix]);
+                G += abs((int)s_S[c][iy * RX_H + ixp] - (int)s_S[c][iy * RX_H + ixm]) +
+                     abs((int)s_S[c][iyp * RX_H + ix] - (int)s_S[c][iym * RX_H + ix]);
             const size_t q = (size_t)g.plane_off + (size_t)(y - g.y0) * g.ww + (x - g.x0);
             w.F[q] = (uint8_t)(((edge_cap - min(G, edge_cap)) * 255) / edge_cap);
             w.plane[q] = (y == g.br && x == g.bc) ? 0 : SC_UNREACHED;
@@ -113,109 +97,34 @@ __global__ void __launch_bounds__(SC_THREADS) k_sc_guide(int H, int W, int edge_
     }
 }
 
-struct ScLds {
-    int c[4][SC_N];              // arc (y,x) -> (y,x+1), (y+1,x), (y+1,x+1), (y+1,x-1)
-    int d[SC_N];
-    uint8_t f[SC_N];
-    int nbm;
-};
-
-__device__ __forceinline__ int sc_relax(const ScLds& L, int i) {
-    const int* dd = L.d;
-    const int a = min(min(dd[i - 1] + L.c[0][i - 1], dd[i + 1] + L.c[0][i]),
-                      min(dd[i - SC_S] + L.c[1][i - SC_S], dd[i + SC_S] + L.c[1][i]));
-    const int e = min(min(dd[i - SC_S - 1] + L.c[2][i - SC_S - 1], dd[i + SC_S + 1] + L.c[2][i]),
-                      min(dd[i - SC_S + 1] + L.c[3][i - SC_S + 1], dd[i + SC_S - 1] + L.c[3][i]));
-    return min(dd[i], min(a, e));
-}
-
-// A lane owns 4 consecutive pixels of one column (step = SC_S) or one row (step = 1) and walks them there and back, in
-// place.  Pixels of other lanes are read while their owners may lower them: any value seen is the cost of a real path,
-// values only fall, and the sweep that ends the visit changed nothing, so all its reads saw final values.
-__device__ __forceinline__ bool sc_sweep(ScLds& L, int first, int step) {
-    bool changed = false;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const int i = first + k * step, v = sc_relax(L, i);
-        if (v != L.d[i]) { L.d[i] = v; changed = true; }
-    }
-#pragma unroll
-    for (int k = 2; k >= 0; --k) {
-        const int i = first + k * step, v = sc_relax(L, i);
-        if (v != L.d[i]) { L.d[i] = v; changed = true; }
-    }
-    return changed;
-}
-
-__global__ void __launch_bounds__(SC_THREADS) k_sc_round(int smooth, int round, ScWork w) {
-    __shared__ ScLds L;
+__global__ void __launch_bounds__(RX_THREADS) k_sc_round(int smooth, int round, ScWork w) {
+    __shared__ struct { RelaxLds<1> rx; uint8_t F[RX_N]; } lds;        // the guide beside the relaxation's arrays
+    auto& s_F = lds.F;
+    RelaxLds<1>& L = lds.rx;
     const int tid = threadIdx.x;
-    const int32_t* cur = w.list[round & 1];
-    int32_t* nxt = w.list[(round + 1) & 1];
-    const int n = w.cnt[round % 3];
-    int32_t* cnt_next = &w.cnt[(round + 1) % 3];
-    if (blockIdx.x == 0 && tid == 0) w.cnt[(round + 2) % 3] = 0;           // read by the previous launch, appended to by the next
-    for (int li = blockIdx.x; li < n; li += gridDim.x) {                   // block-uniform
-        const int tile = cur[li];
+    const RelaxRound rr = relax_round_begin(w.q, round);
+    for (int li = blockIdx.x; li < rr.n; li += gridDim.x) {                // block-uniform
+        const int tile = rr.cur[li];
         const ScSeg g = w.seg[w.tile_seg[tile]];
         const int tr = tile - g.tile_base, tyi = tr / g.tiles_x, txi = tr - tyi * g.tiles_x;
-        const int wy0 = tyi * SC_T, wx0 = txi * SC_T;                      // window-relative
+        const int wy0 = tyi * RX_T, wx0 = txi * RX_T;                      // window-relative
         int32_t* plane = w.plane + g.plane_off;
         const uint8_t* F = w.F + g.plane_off;
-        if (tid == 0) L.nbm = 0;
-        for (int i = tid; i < SC_H * SC_H; i += SC_THREADS) {
-            const int hy = i / SC_H, hx = i - hy * SC_H, y = wy0 + hy - 1, x = wx0 + hx - 1;
-            const bool in = y >= 0 && y < g.wh && x >= 0 && x < g.ww;
-            const int j = hy * SC_S + hx;
-            L.d[j] = in ? plane[(size_t)y * g.ww + x] : SC_BLOCKED;
-            L.f[j] = in ? F[(size_t)y * g.ww + x] : (uint8_t)0;
+        const RelaxBox box = relax_box(wy0, wx0, g.wh, g.ww);
+        for (int i = tid; i < RX_H * RX_H; i += RX_THREADS) {
+            const int hy = i / RX_H, hx = i - hy * RX_H, y = wy0 + hy - 1, x = wx0 + hx - 1;
+            const bool in = box.has(hy, hx);
+            const int j = hy * RX_S + hx;
+            L.d[0][j] = in ? plane[(size_t)y * g.ww + x] : RX_BLOCKED;
+            s_F[j] = in ? F[(size_t)y * g.ww + x] : (uint8_t)0;
         }
         __syncthreads();
-        for (int i = tid; i < SC_H * SC_H; i += SC_THREADS) {
-            const int hy = i / SC_H, hx = i - hy * SC_H, y = wy0 + hy - 1, x = wx0 + hx - 1;
-            const bool in = y >= 0 && y < g.wh && x >= 0 && x < g.ww;
-            const int j = hy * SC_S + hx;
-#pragma unroll
-            for (int a = 0; a < 4; ++a) {
-                const int oy = a == 0 ? 0 : 1, ox = a == 0 ? 1 : (a == 1 ? 0 : (a == 2 ? 1 : -1));
-                const bool ok = in && hy + oy < SC_H && hx + ox >= 0 && hx + ox < SC_H && y + oy < g.wh && x + ox >= 0 && x + ox < g.ww;
-                L.c[a][j] = ok ? (a < 2 ? SC_AXIAL : SC_DIAG) * (smooth + (int)L.f[j] + (int)L.f[j + oy * SC_S + ox]) : SC_BLOCKED;
-            }
-        }
+        relax_arcs(L, box, [&](int j, int q, int len) { return len * (smooth + (int)s_F[j] + (int)s_F[q]); });
         __syncthreads();
-        // write-back ownership: rows tid / 32 + 8k of column tid % 32 (coalesced)
-        const int wx = tid & 31, wy = tid >> 5;
-        int old[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) old[k] = L.d[(wy + 8 * k + 1) * SC_S + wx + 1];
-        __syncthreads();                                                   // the sweeps write what other lanes just read
-        // sweep ownership: run tid / 32 (4 pixels) of line tid % 32
-        const int run = tid >> 5, line = tid & 31;
-        const int first_v = (4 * run + 1) * SC_S + line + 1, first_h = (line + 1) * SC_S + 4 * run + 1;
-        for (int it = 0; it < SC_MAX_SWEEPS; ++it) {
-            const bool ch = (it & 1) ? sc_sweep(L, first_h, 1) : sc_sweep(L, first_v, SC_S);
-            if (!__syncthreads_or(ch)) break;
-        }
-        int nbm = 0;                                                       // bit (dy + 1) * 3 + (dx + 1)
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const int ly = wy + 8 * k, v = L.d[(ly + 1) * SC_S + wx + 1];
-            if (v != old[k] && wy0 + ly < g.wh && wx0 + wx < g.ww) {       // (a pixel outside the window never changes)
-                plane[(size_t)(wy0 + ly) * g.ww + wx0 + wx] = v;
-                const int Lf = wx == 0, Rt = wx == SC_T - 1, U = ly == 0, D = ly == SC_T - 1;
-                nbm |= (U & Lf) | U << 1 | (U & Rt) << 2 | Lf << 3 | Rt << 5 | (D & Lf) << 6 | D << 7 | (D & Rt) << 8;
-            }
-        }
-        if (nbm) atomicOr(&L.nbm, nbm);
-        __syncthreads();
-        if (tid < 9 && tid != 4 && ((L.nbm >> tid) & 1)) {
-            const int ny = tyi + tid / 3 - 1, nx = txi + tid % 3 - 1;
-            if (ny >= 0 && ny < g.tiles_y && nx >= 0 && nx < g.tiles_x) {
-                const int t = g.tile_base + ny * g.tiles_x + nx;
-                if (atomicExch(&w.stamp[t], round + 2) != round + 2) nxt[atomicAdd(cnt_next, 1)] = t;   // once per round
-            }
-        }
-        __syncthreads();                                                   // L is reused by the block's next tile
+        const int nbm = relax_visit(L, [&](int, int ly, int lx, int v) {
+            if (wy0 + ly < g.wh && wx0 + lx < g.ww) plane[(size_t)(wy0 + ly) * g.ww + wx0 + lx] = v;
+        });
+        relax_list_neighbours(w.q, rr, nbm, tyi, txi, g.tiles_y, g.tiles_x, g.tile_base);
     }
 }
 
@@ -232,7 +141,7 @@ __global__ void __launch_bounds__(256) k_sc_walk(int n_seg, int smooth, ScWork w
     // N, NE, E, SE, S, SW, W, NW
     const int dy = (lane == 0 || lane == 1 || lane == 7) ? -1 : ((lane >= 3 && lane <= 5) ? 1 : 0);
     const int dx = (lane >= 1 && lane <= 3) ? 1 : ((lane >= 5 && lane <= 7) ? -1 : 0);
-    const int len = (lane & 1) ? SC_DIAG : SC_AXIAL;
+    const int len = (lane & 1) ? RX_DIAG : RX_AXIAL;
     int r = g.ar - g.y0, c = g.ac - g.x0;                                  // window-relative
     const int tr = g.br - g.y0, tc = g.bc - g.x0;
     int Dp = D[(size_t)r * g.ww + c], Fp = F[(size_t)r * g.ww + c];
@@ -254,7 +163,7 @@ __global__ void __launch_bounds__(256) k_sc_walk(int n_seg, int smooth, ScWork w
         Dp = __shfl(Dq, k, WAVE); Fp = __shfl(Fq, k, WAVE);
     }
     if (!FILL) {
-        if (lost || r != tr || c != tc) { n = 0; if (lane == 0) atomicOr(&w.cnt[3], 1); }
+        if (lost || r != tr || c != tc) { n = 0; if (lane == 0) atomicOr(w.lost, 1); }
         if (lane == 0) seg_cnt[s] = n;
     } else if ((g.flags & 1) && lane == 0) {
         out[2 * (size_t)n] = g.br; out[2 * (size_t)n + 1] = g.bc;
@@ -346,7 +255,7 @@ extern "C" int ggc_trace_paths(ggc_ctx* ctx, ggc_stream stream, int B, int H, in
                 g.x0 = std::max(std::min(g.ac, g.bc) - margin, 0);
                 g.wh = std::min(std::max(g.ar, g.br) + margin, H - 1) - g.y0 + 1;
                 g.ww = std::min(std::max(g.ac, g.bc) + margin, W - 1) - g.x0 + 1;
-                g.tiles_x = cdiv(g.ww, SC_T); g.tiles_y = cdiv(g.wh, SC_T);
+                g.tiles_x = cdiv(g.ww, RX_T); g.tiles_y = cdiv(g.wh, RX_T);
                 g.flags = (!closed[q] && i == n_seg - 1) ? 1 : 0;
                 area += (int64_t)g.wh * g.ww;
                 n_tiles64 += (int64_t)g.tiles_x * g.tiles_y;
@@ -356,13 +265,9 @@ extern "C" int ggc_trace_paths(ggc_ctx* ctx, ggc_stream stream, int B, int H, in
                 g.tile_base = (int)(n_tiles64 - (int64_t)g.tiles_x * g.tiles_y);
                 max_window_tiles = std::max(max_window_tiles, g.tiles_x * g.tiles_y);
                 // b's tile and every tile that holds b in its halo: a visit reports only the pixels it lowers itself
-                const int tr = g.br - g.y0, tc = g.bc - g.x0, tyi = tr / SC_T, txi = tc / SC_T, ly = tr % SC_T, lx = tc % SC_T;
-                for (int dy = -1; dy <= 1; ++dy)
-                    for (int dx = -1; dx <= 1; ++dx) {
-                        const bool sees = (dy == 0 || (dy < 0 ? ly == 0 : ly == SC_T - 1)) && (dx == 0 || (dx < 0 ? lx == 0 : lx == SC_T - 1));
-                        const int ny = tyi + dy, nx = txi + dx;
-                        if (sees && ny >= 0 && ny < g.tiles_y && nx >= 0 && nx < g.tiles_x) first.push_back(g.tile_base + ny * g.tiles_x + nx);
-                    }
+                const int tr = g.br - g.y0, tc = g.bc - g.x0;
+                relax_tiles_holding(tr / RX_T, tc / RX_T, tr % RX_T, tc % RX_T, g.tiles_y, g.tiles_x,
+                                    [&](int ny, int nx) { first.push_back(g.tile_base + ny * g.tiles_x + nx); });
                 segs.push_back(g);
             }
         }
@@ -383,47 +288,38 @@ extern "C" int ggc_trace_paths(ggc_ctx* ctx, ggc_stream stream, int B, int H, in
             w.plane = c.take<int32_t>((size_t)area);                       // first: ggc_debug_read_scratch("scissors_planes")
             w.F = c.take<uint8_t>((size_t)area);
             dev_up = c.take<int32_t>(4 + 16 * (size_t)n_seg + 2 * (size_t)n_tiles);
-            w.list[1] = c.take<int32_t>((size_t)n_tiles);
-            w.stamp = c.take<int32_t>((size_t)n_tiles);
+            w.q.list[1] = c.take<int32_t>((size_t)n_tiles);
+            w.q.stamp = c.take<int32_t>((size_t)n_tiles);
             seg_cnt = c.take<int32_t>((size_t)n_seg);
             seg_off = c.take<int32_t>((size_t)n_seg);
             total = c.take<int32_t>(2);
         }))
         return GGC_E_OOM;
-    w.cnt = dev_up;
+    w.q.cnt = dev_up;
+    w.lost = dev_up + 3;
     w.seg = reinterpret_cast<const ScSeg*>(dev_up + 4);
     w.tile_seg = dev_up + 4 + 16 * (size_t)n_seg;
-    w.list[0] = dev_up + 4 + 16 * (size_t)n_seg + (size_t)n_tiles;
+    w.q.list[0] = dev_up + 4 + 16 * (size_t)n_seg + (size_t)n_tiles;
     GGC_HIP(ctx, hipMemcpyAsync(dev_up, up.data(), sizeof(int32_t) * up.size(), hipMemcpyHostToDevice, st));
-    GGC_HIP(ctx, hipMemsetAsync(w.stamp, 0, sizeof(int32_t) * (size_t)n_tiles, st));
+    GGC_HIP(ctx, hipMemsetAsync(w.q.stamp, 0, sizeof(int32_t) * (size_t)n_tiles, st));
     GGC_HIP(ctx, hipStreamSynchronize(st));                                // `up` is pageable: the copy has left it
 
     const int wide = 16 * std::max(ctx->n_cu, 1), grid = std::min(n_tiles, wide);
     {
         ProfScope prof(ctx, st, "scissors_guide");
-        hipLaunchKernelGGL(k_sc_guide, dim3(grid), dim3(SC_THREADS), 0, st, H, W, edge_cap, n_tiles, bgr, w);
+        hipLaunchKernelGGL(k_sc_guide, dim3(grid), dim3(RX_THREADS), 0, st, H, W, edge_cap, n_tiles, bgr, w);
     }
     GGC_LAUNCH_CHECK(ctx);
-    // Round bound, as for ggc_geodesic_hints: round j makes every pixel final whose cheapest path to b crosses a tile edge
-    // at most j times.  A cheapest path is simple and stays in its window, so it has fewer arcs than the window has pixels,
-    // at most 1024 per tile: it crosses at most J = 1024 * tiles - 1 edges.  Round J + 1 can still be listed but lowers
-    // nothing, so the list of round J + 2 is empty.
-    const int64_t max_rounds = (int64_t)SC_T * SC_T * max_window_tiles + 2;
-    int64_t round = 0;
-    int step = 6;                                                          // a window is a few tiles across: look after 6 rounds, then every 4
+    // Round bound (ggc_relax.h).  A cheapest path is simple and stays in its window, so it has fewer arcs than the window has
+    // pixels: it crosses at most J = 1024 * tiles - 1 tile edges.
+    const int64_t max_rounds = (int64_t)RX_T * RX_T * max_window_tiles + 2;
+    const auto launch_round = [&](int64_t round) {
+        ProfScope prof(ctx, st, "scissors_round");
+        hipLaunchKernelGGL(k_sc_round, dim3(grid), dim3(RX_THREADS), 0, st, smooth, (int)round, w);
+    };
+    // a window is a few tiles across: look after 6 rounds, then every 4
+    if ((rc = relax_rounds(ctx, st, launch_round, w.q.cnt, 6, 4, max_rounds, "scissors"))) return rc;
     std::vector<int32_t> host;
-    for (;;) {
-        const int64_t stop = std::min(round + step, max_rounds);
-        for (; round < stop; ++round) {
-            ProfScope prof(ctx, st, "scissors_round");
-            hipLaunchKernelGGL(k_sc_round, dim3(grid), dim3(SC_THREADS), 0, st, smooth, (int)round, w);
-        }
-        GGC_LAUNCH_CHECK(ctx);
-        if ((rc = read_i32(ctx, st, w.cnt + round % 3, 1, host))) return rc;
-        if (host[0] == 0) break;
-        GGC_REQUIRE(ctx, round < max_rounds, GGC_E_DEVICE, "scissors did not converge in %lld rounds", (long long)max_rounds);
-        step = 4;
-    }
     const int walk_blocks = cdiv(n_seg, 256 / WAVE);
     {
         ProfScope prof(ctx, st, "scissors_walk");
@@ -431,7 +327,7 @@ extern "C" int ggc_trace_paths(ggc_ctx* ctx, ggc_stream stream, int B, int H, in
     }
     hipLaunchKernelGGL(k_sc_scan, dim3(1), dim3(256), 0, st, n_seg, Q, w.seg, seg_cnt, seg_off, vert_ptr_out, total);
     GGC_LAUNCH_CHECK(ctx);
-    if ((rc = read_i32(ctx, st, w.cnt + 3, 1, host))) return rc;
+    if ((rc = read_i32(ctx, st, w.lost, 1, host))) return rc;
     GGC_REQUIRE(ctx, host[0] == 0, GGC_E_DEVICE, "a scissors walk found no successor on its distance plane");
     if (!verts_out) return GGC_OK;
     if ((rc = read_i32(ctx, st, total, 1, host))) return rc;
