@@ -12,22 +12,19 @@
 // ggc_lift_trimap and ggc_closed_form_band solve nothing: they write trimaps (a working-size trimap and alpha carried to
 // a larger size; the band of the mask front end as a trimap) with the band front end's separable dilation.
 //
-// Layout.  A tile is 16 x 16 pixels of one image and a block of 256 threads, one per pixel.  U is found over the whole
-// frame once per call by the front end; the host reads the counts and lists the tiles that hold U or touch a tile that
-// does (every window centre within r <= 16 of U), image by image.  Every later kernel runs over that list only.  Per
-// listed tile and iteration:
+// Layout.  The tile list, the fixed-order sums, the per-image scalars and the poll are ggc_cg.h's.  Listed here are the
+// tiles that hold U or touch a tile that does (ring 1: every window centre within r <= 16 of U); an image whose U is
+// empty or covers every pixel is not solved.  The vectors are full-frame float64 planes.  Per listed tile and iteration:
 //   k_cf_window  a_k, b_k of the p of the product at every centre k in K of the tile (p staged with an r halo in LDS)
 //   k_cf_pixel   (L p)_i = c_i p_i - sum_k (a_k . I_i + b_k) on U (a, b staged with an r halo in LDS); per-tile d . q
-//   k_cf_alpha   per image: alpha = rz / (d . q)
+//   k_cg_scalar  per image: alpha = rz / (d . q)
 //   k_cf_update  x += alpha d, r -= alpha q on U; per-tile r . z and r . r (z = r / diag L)
-//   k_cf_beta    per image: convergence, the iteration count, beta
+//   k_cg_scalar  per image: convergence (rel = sqrt(r.r / rr0) <= tol), the iteration count, beta
 //   k_cf_direction  d = z + beta d on U
 // The window statistics (mu_k and Delta_k^-1 from exact integer window sums, the 3x3 inverse by the adjugate in float64)
-// and diag L are computed once per call.  Every per-tile sum is a fixed LDS tree over the tile's 256 pixels, every
-// per-image sum one wave over that image's run of the tile list in a fixed order (lane 0's result), so an image's
-// iterates do not depend on the batch: a batch equals its single-image calls bit for bit.  No float atomics; the only
-// atomic is an integer count of converged images, which the host polls every CF_POLL iterations to stop early.
-#include "ggc_internal.h"
+// and diag L are computed once per call.
+#include "ggc_cg.h"
+#include "ggc_image.h"
 #include <algorithm>
 #include <cmath>
 
@@ -35,20 +32,14 @@ namespace ggc {
 
 namespace {
 
-constexpr int CF_T = 16;                          // tile side
-constexpr int CF_THREADS = CF_T * CF_T;
+constexpr int CF_T = CG_T, CF_THREADS = CG_THREADS;
 constexpr int CF_RMAX = 8;
 constexpr int CF_SMAX = CF_T + 2 * CF_RMAX;       // staged side at the largest radius
-constexpr int CF_POLL = 8;                        // iterations between polls of the converged count
 
 constexpr uint8_t F_M = 1, F_U = 2;               // flags: known value (meaningful off U), unknown
 
 struct alignas(8) CfStats { double mu[3]; double d00, d01, d02, d11, d12, d22; };   // Delta^-1, symmetric
 struct alignas(32) CfAB { double a0, a1, a2, b; };
-struct CfImage {                                  // per-image solver state
-    double rz, rr0, alpha, beta, rel;
-    int iters, done, tile_lo, tile_hi;
-};
 
 __device__ __forceinline__ double colour(const uint8_t* px, int c) { return (double)px[c] * (1.0 / 255.0); }
 
@@ -79,17 +70,6 @@ __global__ void __launch_bounds__(CF_THREADS) k_cf_dilate_h(int H, int W, int ba
     uint8_t v = 0;
     for (int xx = max(0, x - band); xx <= min(W - 1, x + band); ++xx) v |= row[xx];
     out[(size_t)blockIdx.z * H * W + (size_t)y * W + x] = v;
-}
-
-// tile_u of the block's tile = the sum of the block's u, a fixed LDS tree
-__device__ __forceinline__ void count_tile(int u, int* s_cnt, int tid, int32_t* __restrict__ tile_u) {
-    s_cnt[tid] = u;
-    __syncthreads();
-    for (int s = CF_THREADS / 2; s > 0; s >>= 1) {
-        if (tid < s) s_cnt[tid] += s_cnt[tid + s];
-        __syncthreads();
-    }
-    if (tid == 0) tile_u[((size_t)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x] = s_cnt[0];
 }
 
 // flags = m | U << 1; start = m on U; tile_u [B, tiles] = pixels of U in each tile (a block is a tile)
@@ -128,36 +108,12 @@ __global__ void __launch_bounds__(CF_THREADS) k_cf_trimap(int H, int W, const ui
         const uint8_t t = trimap[i];
         u = t != 0 && t != 255 ? 1 : 0;
         flags[i] = (t == 255 ? F_M : 0) | (u ? F_U : 0);
-        if (u) {
-            double a = 0.5;
-            if (alpha0) {
-                a = (double)alpha0[i];
-                a = !(a >= 0.0) ? 0.0 : (a > 1.0 ? 1.0 : a);
-            }
-            x[i] = a;
-        }
+        if (u) x[i] = alpha0 ? unit_clamp(alpha0[i]) : 0.5;
     }
     count_tile(u, s_cnt, tid, tile_u);
 }
 
 // ---------------------------------------------------------------- trimaps for a later solve, over the whole frame
-// the half-pixel-centre source coordinate of output index o of n1 over a source of n: ggc_upsample_matte's (ggc_matte.hip)
-__device__ __forceinline__ void lift_coord(int o, int n, int n1, int& i0, int& i1, double& w) {
-    double s = (((double)o + 0.5) * (double)n) / (double)n1 - 0.5;
-    if (s < 0.0) s = 0.0;
-    const double f = floor(s);
-    i0 = (int)f;
-    if (i0 >= n - 1) { i0 = n - 1; w = 0.0; } else { w = s - f; }
-    i1 = min(i0 + 1, n - 1);
-}
-
-__device__ __forceinline__ double lerp(double u, double v, double t) { return u + t * (v - u); }
-
-__device__ __forceinline__ double unit_clamp(float a) {
-    const double v = (double)a;
-    return !(v >= 0.0) ? 0.0 : (v > 1.0 ? 1.0 : v);
-}
-
 // One output pixel per thread, grid (cdiv(W1, 16), cdiv(H1, 16), B).  trimap_full = 255 / 0 where the source pixels of
 // nonzero weight all are, else 128 (unknown = that as a 0 / 1 plane, for the dilation); alpha0_full = the bilinear
 // interpolation of the clamped alpha.  Each output may be NULL.
@@ -168,8 +124,8 @@ __global__ void __launch_bounds__(CF_THREADS) k_cf_lift(int H, int W, int H1, in
     if (x >= W1 || y >= H1) return;
     int x0, x1, y0, y1;
     double wx, wy;
-    lift_coord(x, W, W1, x0, x1, wx);
-    lift_coord(y, H, H1, y0, y1, wy);
+    half_pixel_coord(x, W, W1, x0, x1, wx);
+    half_pixel_coord(y, H, H1, y0, y1, wy);
     const size_t src = (size_t)blockIdx.z * H * W, o = (size_t)blockIdx.z * H1 * W1 + (size_t)y * W1 + x;
     if (trimap_full) {
         const uint8_t* t = trimap + src;
@@ -205,13 +161,6 @@ __global__ void __launch_bounds__(CF_THREADS) k_cf_dilate_v_trimap(int H, int W,
 }
 
 // ---------------------------------------------------------------- per listed tile
-struct TileRef { int b, ty, tx; };
-
-__device__ __forceinline__ TileRef tile_of(const int2* __restrict__ tiles, int ntx) {
-    const int2 t = tiles[blockIdx.x];
-    return TileRef{t.x, t.y / ntx, t.y % ntx};
-}
-
 // Delta_k^-1 and mu_k of every centre of the tile that lies in K, from exact integer window sums
 __global__ void __launch_bounds__(CF_THREADS) k_cf_stats(int H, int W, int r, double eps, int ntx,
                                                          const int2* __restrict__ tiles, const uint8_t* __restrict__ bgr,
@@ -255,7 +204,7 @@ __device__ __forceinline__ double p_value(uint8_t f, const double* __restrict__ 
 
 template <bool SETUP, bool HALF = false>
 __global__ void __launch_bounds__(CF_THREADS) k_cf_window(int H, int W, int r, int ntx, const int2* __restrict__ tiles,
-                                                          const CfImage* __restrict__ img, const uint8_t* __restrict__ bgr,
+                                                          const CgImage* __restrict__ img, const uint8_t* __restrict__ bgr,
                                                           const uint8_t* __restrict__ flags, const CfStats* __restrict__ stats,
                                                           const double* __restrict__ d, CfAB* __restrict__ ab) {
     __shared__ double s_p[CF_SMAX * CF_SMAX];
@@ -296,22 +245,11 @@ __global__ void __launch_bounds__(CF_THREADS) k_cf_window(int H, int W, int r, i
     ab[base + (size_t)y * W + x] = CfAB{a0, a1, a2, mp - (a0 * st.mu[0] + a1 * st.mu[1] + a2 * st.mu[2])};
 }
 
-// the fixed-order sum of the block's 256 values (thread 0 holds it)
-__device__ __forceinline__ double block_sum(double v, double* s, int tid) {
-    s[tid] = v;
-    __syncthreads();
-    for (int k = CF_THREADS / 2; k > 0; k >>= 1) {
-        if (tid < k) s[tid] += s[tid + k];
-        __syncthreads();
-    }
-    return s[0];
-}
-
 // q = (L p) on U.  SETUP: p = the start image (d is x); r = -q, diag L, and the per-tile r . z, r . r (into part_a,
 // part_b); else the per-tile d . q (into part_a).  HALF (with SETUP): the same of the stop reference's image
 template <bool SETUP, bool HALF = false>
 __global__ void __launch_bounds__(CF_THREADS) k_cf_pixel(int H, int W, int r, int ntx, const int2* __restrict__ tiles,
-                                                         const CfImage* __restrict__ img, const uint8_t* __restrict__ bgr,
+                                                         const CgImage* __restrict__ img, const uint8_t* __restrict__ bgr,
                                                          const uint8_t* __restrict__ flags, const CfStats* __restrict__ stats,
                                                          const CfAB* __restrict__ ab, const double* __restrict__ d,
                                                          double* __restrict__ q, double* __restrict__ res,
@@ -380,70 +318,40 @@ __global__ void __launch_bounds__(CF_THREADS) k_cf_pixel(int H, int W, int r, in
     }
 }
 
-// one wave per image: the sum of part over the image's run of the tile list, lane 0's fixed order
-__device__ __forceinline__ double image_sum(const double* __restrict__ part, int lo, int hi) {
-    const int lane = threadIdx.x;
-    double v = 0.0;
-    for (int k = lo + lane; k < hi; k += WAVE) v += part[k];
-    for (int o = 1; o < WAVE; o <<= 1) v += __shfl_down(v, o, WAVE);
-    return __shfl(v, 0, WAVE);
-}
-
-// MODE 0 (after setup): rz, rr0, the trivial images; MODE 1: alpha = rz / d.q; MODE 2: convergence and beta.
-// The warm entry's set-up: MODE 3 (after the pass over the stop reference's image) rr0 = ||r_ref||^2 and the trivial
-// images; MODE 4 (after setup, in MODE 0's place) rz and the stop test on r_0 against that rr0.
-// grid B, one wave
-template <int MODE>
-__global__ void __launch_bounds__(WAVE) k_cf_scalar(int max_iter, double tol, CfImage* __restrict__ img,
-                                                    const double* __restrict__ part_a, const double* __restrict__ part_b,
-                                                    int* __restrict__ n_done) {
-    CfImage& s = img[blockIdx.x];
-    if (s.done) return;
-    const double a = image_sum(part_a, s.tile_lo, s.tile_hi);
-    const double b = MODE == 1 ? 0.0 : image_sum(part_b, s.tile_lo, s.tile_hi);
-    if (threadIdx.x != 0) return;
-    if (MODE == 0) {
-        s.rz = a;
-        s.rr0 = b;
-        s.rel = 0.0;
-        s.iters = 0;
-        if (!(b > 0.0)) { s.done = 1; atomicAdd(n_done, 1); }    // r_0 = 0: the start already solves the system
-    } else if (MODE == 3) {
-        s.rr0 = b;
-        s.rel = 0.0;
-        s.iters = 0;
-        if (!(b > 0.0)) { s.done = 1; atomicAdd(n_done, 1); }    // r_ref = 0: nothing to measure a residual against
-    } else if (MODE == 4) {
-        s.rz = a;
-        s.rel = sqrt(b / s.rr0);
-        if (s.rel <= tol) { s.done = 1; atomicAdd(n_done, 1); }  // the start is already good enough
-    } else if (MODE == 1) {
-        if (a > 0.0 && std::isfinite(a)) {
-            s.alpha = s.rz / a;
-        } else {                                                 // d = 0 or a breakdown: nothing left to do
-            s.alpha = 0.0;
-            s.done = 1;
-            atomicAdd(n_done, 1);
-        }
-    } else {
-        s.iters += 1;
-        s.rel = sqrt(b / s.rr0);
-        s.beta = a / s.rz;
-        s.rz = a;
-        if (s.rel <= tol || s.iters >= max_iter) { s.done = 1; atomicAdd(n_done, 1); }
+// The closed form's side of k_cg_scalar (grid B, one wave).  Set-up MODEs: CF_START (after the set-up pass) rz, rr0, the
+// trivial images.  The warm entry's: CF_REF (after the pass over the stop reference's image) rr0 = ||r_ref||^2 and the
+// trivial images; CF_WARM (after the set-up pass, in CF_START's place) rz and the stop test on r_0 against that rr0.
+constexpr int CF_START = 0, CF_REF = 3, CF_WARM = 4;
+struct CfSolver {
+    static __device__ __forceinline__ bool converged(CgImage& s, double rr, double tol) {
+        s.rel = sqrt(rr / s.rr0);
+        return s.rel <= tol;
     }
-}
+    template <int MODE>
+    static __device__ __forceinline__ void setup(CgImage& s, double a, double b, double tol, int* __restrict__ n_done) {
+        if (MODE == CF_WARM) {
+            s.rz = a;
+            if (converged(s, b, tol)) cg_finish(s, n_done);      // the start is already good enough
+        } else {
+            if (MODE == CF_START) s.rz = a;
+            s.rr0 = b;
+            s.rel = 0.0;
+            s.iters = 0;
+            if (!(b > 0.0)) cg_finish(s, n_done);                // r_0 (CF_REF: r_ref) = 0: solved, or nothing to measure against
+        }
+    }
+};
 
 // x += alpha d, r -= alpha q on U; per-tile r . z (part_a), r . r (part_b)
 __global__ void __launch_bounds__(CF_THREADS) k_cf_update(int H, int W, int ntx, const int2* __restrict__ tiles,
-                                                          const CfImage* __restrict__ img, const uint8_t* __restrict__ flags,
+                                                          const CgImage* __restrict__ img, const uint8_t* __restrict__ flags,
                                                           const double* __restrict__ d, const double* __restrict__ q,
                                                           const double* __restrict__ diag, double* __restrict__ x,
                                                           double* __restrict__ res, double* __restrict__ part_a,
                                                           double* __restrict__ part_b) {
     __shared__ double s_red[CF_THREADS];
     const TileRef t = tile_of(tiles, ntx);
-    const CfImage& s = img[t.b];
+    const CgImage& s = img[t.b];
     if (s.done) return;
     const int tid = threadIdx.y * CF_T + threadIdx.x;
     const int xp = t.tx * CF_T + threadIdx.x, yp = t.ty * CF_T + threadIdx.y;
@@ -469,11 +377,11 @@ __global__ void __launch_bounds__(CF_THREADS) k_cf_update(int H, int W, int ntx,
 // d = z + beta d on U (SETUP: d = z)
 template <bool SETUP>
 __global__ void __launch_bounds__(CF_THREADS) k_cf_direction(int H, int W, int ntx, const int2* __restrict__ tiles,
-                                                             const CfImage* __restrict__ img, const uint8_t* __restrict__ flags,
+                                                             const CgImage* __restrict__ img, const uint8_t* __restrict__ flags,
                                                              const double* __restrict__ res, const double* __restrict__ diag,
                                                              double* __restrict__ d) {
     const TileRef t = tile_of(tiles, ntx);
-    const CfImage& s = img[t.b];
+    const CgImage& s = img[t.b];
     if (s.done) return;
     const int xp = t.tx * CF_T + threadIdx.x, yp = t.ty * CF_T + threadIdx.y;
     if (xp >= W || yp >= H) return;
@@ -485,7 +393,7 @@ __global__ void __launch_bounds__(CF_THREADS) k_cf_direction(int H, int W, int n
 
 // the outputs over the whole frame: alpha = x on U (the start where nothing was solved), the known value elsewhere.
 // grid (cdiv(H*W, 256), B)
-__global__ void __launch_bounds__(CF_THREADS) k_cf_output(int H, int W, const CfImage* __restrict__ img,
+__global__ void __launch_bounds__(CF_THREADS) k_cf_output(int H, int W, const CgImage* __restrict__ img,
                                                           const uint8_t* __restrict__ bgr, const uint8_t* __restrict__ flags,
                                                           const double* __restrict__ x, float* __restrict__ alpha,
                                                           uint8_t* __restrict__ rgba, double* __restrict__ raw,
@@ -493,7 +401,7 @@ __global__ void __launch_bounds__(CF_THREADS) k_cf_output(int H, int W, const Cf
     const size_t P = (size_t)H * W;
     const size_t j = (size_t)blockIdx.x * CF_THREADS + threadIdx.x;
     const int b = blockIdx.y;
-    const CfImage& s = img[b];
+    const CgImage& s = img[b];
     if (blockIdx.x == 0 && threadIdx.x == 0) {
         if (iters) iters[b] = s.iters;
         if (rel) rel[b] = s.rel;
@@ -503,11 +411,10 @@ __global__ void __launch_bounds__(CF_THREADS) k_cf_output(int H, int W, const Cf
     const uint8_t f = flags[i];
     const double a = (f & F_U) ? x[i] : ((f & F_M) ? 1.0 : 0.0);
     if (raw) raw[i] = a;
-    const double c = a < 0.0 ? 0.0 : (a > 1.0 ? 1.0 : a);
-    if (alpha) alpha[i] = (float)c;
+    if (alpha) alpha[i] = (float)(a < 0.0 ? 0.0 : (a > 1.0 ? 1.0 : a));
     if (rgba) {
         rgba[4 * i] = bgr[3 * i]; rgba[4 * i + 1] = bgr[3 * i + 1]; rgba[4 * i + 2] = bgr[3 * i + 2];
-        rgba[4 * i + 3] = (uint8_t)floor(c * 255.0 + 0.5);
+        rgba[4 * i + 3] = unit_byte(a);
     }
 }
 
@@ -552,7 +459,7 @@ int cf_solve(ggc_ctx* ctx, hipStream_t st, const char* name, int B, int H, int W
     const size_t P = (size_t)B * H * W;
     const int ntx = cdiv(W, CF_T), nty = cdiv(H, CF_T), nt = ntx * nty;
     CfFront f{nullptr, nullptr, nullptr, nullptr, nullptr};
-    CfImage* img = nullptr;
+    CgImage* img = nullptr;
     int* n_done = nullptr;
     CfStats* stats = nullptr;
     CfAB* ab = nullptr;
@@ -570,7 +477,7 @@ int cf_solve(ggc_ctx* ctx, hipStream_t st, const char* name, int B, int H, int W
             diag = c.take<double>(P);
             f.tile_u = c.take<int32_t>(n_tiles_max); tiles = c.take<int2>(n_tiles_max);
             part_a = c.take<double>(n_tiles_max); part_b = c.take<double>(n_tiles_max);
-            img = c.take<CfImage>(B); n_done = c.take<int>(1);
+            img = c.take<CgImage>(B); n_done = c.take<int>(1);
         }))
         return GGC_E_OOM;
     ProfScope prof(ctx, st, name);
@@ -581,76 +488,48 @@ int cf_solve(ggc_ctx* ctx, hipStream_t st, const char* name, int B, int H, int W
     front(f, fgrid, tblk);
     GGC_LAUNCH_CHECK(ctx);
 
-    // the tile list, image by image: tiles with U and their eight neighbours (r <= 16 = the tile side).  An image whose
-    // U is empty or covers every pixel (nothing anchors it) gets no tiles: alpha = the start, 0 iterations.
-    std::vector<int32_t> cnt(n_tiles_max);
-    GGC_HIP(ctx, hipMemcpyAsync(cnt.data(), tile_u, n_tiles_max * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    GGC_HIP(ctx, hipStreamSynchronize(st));
+    // the tile list: tiles with U and their eight neighbours (r <= 16 = the tile side).  An image whose U is empty or
+    // covers every pixel (nothing anchors it) gets no tiles: alpha = the start, 0 iterations.
+    std::vector<int32_t> cnt;
+    if (int e = cg_read_counts(ctx, st, tile_u, n_tiles_max, cnt)) return e;
     std::vector<int2> list;
-    std::vector<CfImage> host_img(B);
-    int n_solve = 0;
-    for (int b = 0; b < B; ++b) {
-        const int32_t* c = cnt.data() + (size_t)b * nt;
-        int64_t u = 0;
-        for (int k = 0; k < nt; ++k) u += c[k];
-        CfImage& s = host_img[b];
-        s = CfImage{0.0, 0.0, 0.0, 0.0, 0.0, 0, 1, (int)list.size(), (int)list.size()};
-        if (u == 0 || u == (int64_t)H * W) continue;
-        for (int ty = 0; ty < nty; ++ty)
-            for (int tx = 0; tx < ntx; ++tx) {
-                bool near = false;
-                for (int dy = -1; dy <= 1 && !near; ++dy)
-                    for (int dx = -1; dx <= 1 && !near; ++dx) {
-                        const int yy = ty + dy, xx = tx + dx;
-                        near = yy >= 0 && yy < nty && xx >= 0 && xx < ntx && c[yy * ntx + xx] > 0;
-                    }
-                if (near) list.push_back(make_int2(b, ty * ntx + tx));
-            }
-        s.tile_hi = (int)list.size();
-        s.done = 0;
-        ++n_solve;
-    }
+    std::vector<CgImage> host_img;
+    std::vector<int64_t> u_count;
+    const int n_solve = cg_list_tiles(B, ntx, nty, cnt.data(), 1, (int64_t)H * W, list, host_img, u_count, nullptr);
     const int n_list = (int)list.size();
-    if (n_list > 0) GGC_HIP(ctx, hipMemcpyAsync(tiles, list.data(), list.size() * sizeof(int2), hipMemcpyHostToDevice, st));
-    GGC_HIP(ctx, hipMemcpyAsync(img, host_img.data(), B * sizeof(CfImage), hipMemcpyHostToDevice, st));
-    GGC_HIP(ctx, hipMemsetAsync(n_done, 0, sizeof(int), st));
-    GGC_HIP(ctx, hipStreamSynchronize(st));            // the host vectors go out of scope below
+    if (int e = cg_upload(ctx, st, list, host_img, tiles, img, n_done)) return e;
 
     if (n_list > 0) {
-        const double e = (double)eps, tl = (double)tol;
+        const double e = (double)eps;
+        const CgScalars sc{st, B, max_iter, (double)tol, img, part_a, part_b, n_done};
         hipLaunchKernelGGL(k_cf_stats, dim3(n_list), tblk, 0, st, H, W, radius, e, ntx, tiles, bgr, stats);
         if (warm) {     // r_ref = -(L x^1/2)_U; ab, res, diag and the partial sums are written again by the set-up proper
             hipLaunchKernelGGL((k_cf_window<true, true>), dim3(n_list), tblk, 0, st, H, W, radius, ntx, tiles, img, bgr,
                                flags, stats, x, ab);
             hipLaunchKernelGGL((k_cf_pixel<true, true>), dim3(n_list), tblk, 0, st, H, W, radius, ntx, tiles, img, bgr,
                                flags, stats, ab, x, q, res, diag, part_a, part_b);
-            hipLaunchKernelGGL(k_cf_scalar<3>, dim3(B), dim3(WAVE), 0, st, max_iter, tl, img, part_a, part_b, n_done);
+            sc.step<CfSolver, CF_REF>();
         }
         hipLaunchKernelGGL(k_cf_window<true>, dim3(n_list), tblk, 0, st, H, W, radius, ntx, tiles, img, bgr, flags, stats,
                            x, ab);
         hipLaunchKernelGGL(k_cf_pixel<true>, dim3(n_list), tblk, 0, st, H, W, radius, ntx, tiles, img, bgr, flags, stats, ab,
                            x, q, res, diag, part_a, part_b);
-        if (warm) hipLaunchKernelGGL(k_cf_scalar<4>, dim3(B), dim3(WAVE), 0, st, max_iter, tl, img, part_a, part_b, n_done);
-        else hipLaunchKernelGGL(k_cf_scalar<0>, dim3(B), dim3(WAVE), 0, st, max_iter, tl, img, part_a, part_b, n_done);
+        if (warm) sc.step<CfSolver, CF_WARM>();
+        else sc.step<CfSolver, CF_START>();
         hipLaunchKernelGGL(k_cf_direction<true>, dim3(n_list), tblk, 0, st, H, W, ntx, tiles, img, flags, res, diag, d);
         GGC_LAUNCH_CHECK(ctx);
-        for (int it = 0; it < max_iter; ++it) {
+        const int rc = cg_iterate(ctx, st, max_iter, n_done, n_solve, [&](int) {
             hipLaunchKernelGGL(k_cf_window<false>, dim3(n_list), tblk, 0, st, H, W, radius, ntx, tiles, img, bgr, flags,
                                stats, d, ab);
             hipLaunchKernelGGL(k_cf_pixel<false>, dim3(n_list), tblk, 0, st, H, W, radius, ntx, tiles, img, bgr, flags,
                                stats, ab, d, q, res, diag, part_a, part_b);
-            hipLaunchKernelGGL(k_cf_scalar<1>, dim3(B), dim3(WAVE), 0, st, max_iter, tl, img, part_a, part_b, n_done);
+            sc.step<CfSolver, CG_ALPHA>();
             hipLaunchKernelGGL(k_cf_update, dim3(n_list), tblk, 0, st, H, W, ntx, tiles, img, flags, d, q, diag, x, res,
                                part_a, part_b);
-            hipLaunchKernelGGL(k_cf_scalar<2>, dim3(B), dim3(WAVE), 0, st, max_iter, tl, img, part_a, part_b, n_done);
+            sc.step<CfSolver, CG_BETA>();
             hipLaunchKernelGGL(k_cf_direction<false>, dim3(n_list), tblk, 0, st, H, W, ntx, tiles, img, flags, res, diag, d);
-            GGC_LAUNCH_CHECK(ctx);
-            if ((it + 1) % CF_POLL == 0 && it + 1 < max_iter) {
-                std::vector<int32_t> h;
-                if (int e2 = read_i32(ctx, st, n_done, 1, h)) return e2;
-                if (h[0] >= n_solve) break;
-            }
-        }
+        });
+        if (rc) return rc;
     }
     const dim3 ogrid(cdiv((int64_t)H * W, CF_THREADS), B);
     hipLaunchKernelGGL(k_cf_output, ogrid, dim3(CF_THREADS), 0, st, H, W, img, bgr, flags, x, alpha, rgba, raw, iters,

@@ -3,22 +3,20 @@
 // Dirichlet values), solved on the device by conjugate gradients preconditioned with the exact 2 x 2 block of every
 // pixel.  include/ggc.h states the system; DESIGN.md §5.14 the tiling and the bytes.
 //
-// Layout.  A tile is 16 x 16 pixels of one image and a block of 256 threads, one per pixel.  k_fg_snap writes alpha'
-// over the whole frame and counts U per tile; the host reads the counts and lists the tiles that hold U, image by image
-// (the stencil reaches one pixel, so no neighbour tile is needed).  The CG vectors live in a compact store of 256 entries
-// per LISTED tile, six float64 per entry (F and B of the three channels); tile_slot maps a tile of the frame to its place
-// in the list.  Per listed tile and iteration:
+// Layout.  The tile list, the fixed-order sums, the per-image scalars and the poll are ggc_cg.h's.  k_fg_snap writes alpha'
+// over the whole frame and counts U per tile; listed are the tiles that hold U (ring 0: the stencil reaches one pixel, so
+// no neighbour tile is needed).  The CG vectors live in a compact store of 256 entries per LISTED tile, six float64 per
+// entry (F and B of the three channels); tile_slot maps a tile of the frame to its place in the list.  Per listed tile
+// and iteration:
 //   k_fg_apply   p = z + beta p (z = M^-1 r recomputed from r and alpha') on the tile and a one-pixel halo, staged in
 //                LDS; q = A p on the tile; per-tile p . q.  p is double-buffered: a neighbour tile reads the old p of
 //                this tile's edge while this tile writes the new one.
-//   k_fg_scalar  per image: alpha = rz / (p . q)
+//   k_cg_scalar  per image: alpha = rz / (p . q)
 //   k_fg_update  x += alpha p, r -= alpha q, z = M^-1 r; per-tile r . z and r . r
-//   k_fg_scalar  per image: convergence, the iteration count, beta
-// The link weights and the 2 x 2 inverse are recomputed from alpha' staged in LDS wherever they are needed.  Every
-// per-tile sum is a fixed LDS tree over the tile's 256 pixels, every per-image sum one wave over that image's run of the
-// tile list in a fixed order, so an image's iterates do not depend on the batch.  No float atomics; the only atomic is an
-// integer count of finished images, which the host polls every FG_POLL iterations to stop early.
-#include "ggc_internal.h"
+//   k_cg_scalar  per image: convergence (||r|| <= stop = max(tol ||r_0||, 1e-12 sqrt(6 |U|))), the iteration count, beta
+// The link weights and the 2 x 2 inverse are recomputed from alpha' staged in LDS wherever they are needed.
+#include "ggc_cg.h"
+#include "ggc_image.h"
 #include <algorithm>
 #include <cmath>
 
@@ -26,20 +24,14 @@ namespace ggc {
 
 namespace {
 
-constexpr int FG_T = 16;                          // tile side
-constexpr int FG_THREADS = FG_T * FG_T;
+constexpr int FG_T = CG_T, FG_THREADS = CG_THREADS;
 constexpr int FG_S1 = FG_T + 2;                   // tile with a one-pixel halo
 constexpr int FG_S2 = FG_T + 4;                   // ... a two-pixel halo (alpha' under the halo's preconditioner)
-constexpr int FG_POLL = 8;                        // iterations between polls of the finished count
 constexpr double FG_DELTA = 1e-6;                 // the anchor of the definition
 constexpr double FG_SNAP = 1.0 / 510.0;
 constexpr double FG_OUTSIDE = -1.0;               // alpha' staged for a pixel outside the image: no link
 
 struct alignas(16) V6 { double v[6]; };           // F (b, g, r) then B (b, g, r) of one pixel
-struct FgImage {                                  // per-image solver state
-    double rz, rr0, alpha, beta, rel, stop;       // stop: on entry the absolute floor, after setup the threshold on ||r||
-    int iters, done, tile_lo, tile_hi;
-};
 
 __device__ __forceinline__ bool is_u(double a) { return a > 0.0 && a < 1.0; }
 
@@ -60,23 +52,10 @@ __global__ void __launch_bounds__(FG_THREADS) k_fg_snap(int H, int W, const floa
         ap[i] = s;
         u = (s > 0.0f && s < 1.0f) ? 1 : 0;
     }
-    s_cnt[tid] = u;
-    __syncthreads();
-    for (int k = FG_THREADS / 2; k > 0; k >>= 1) {
-        if (tid < k) s_cnt[tid] += s_cnt[tid + k];
-        __syncthreads();
-    }
-    if (tid == 0) tile_u[((size_t)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x] = s_cnt[0];
+    count_tile(u, s_cnt, tid, tile_u);
 }
 
 // ---------------------------------------------------------------- per listed tile
-struct TileRef { int b, ty, tx; };
-
-__device__ __forceinline__ TileRef tile_of(const int2* __restrict__ tiles, int ntx) {
-    const int2 t = tiles[blockIdx.x];
-    return TileRef{t.x, t.y / ntx, t.y % ntx};
-}
-
 // alpha' of the S x S pixels from (y0, x0) of image b, FG_OUTSIDE beyond the image
 __device__ __forceinline__ void stage_alpha(double* s_a, int S, int y0, int x0, int H, int W, const float* __restrict__ ap,
                                             size_t base, int tid) {
@@ -116,17 +95,6 @@ __device__ __forceinline__ V6 precondition(const V6& r, const double* s_a, int c
 __device__ __forceinline__ size_t vec_index(const int32_t* __restrict__ tile_slot, int b, int nt, int ntx, int y, int x) {
     const int slot = tile_slot[(size_t)b * nt + (y / FG_T) * ntx + x / FG_T];
     return (size_t)slot * FG_THREADS + (y % FG_T) * FG_T + (x % FG_T);
-}
-
-// the fixed-order sum of the block's 256 values (thread 0 holds it)
-__device__ __forceinline__ double block_sum(double v, double* s, int tid) {
-    s[tid] = v;
-    __syncthreads();
-    for (int k = FG_THREADS / 2; k > 0; k >>= 1) {
-        if (tid < k) s[tid] += s[tid + k];
-        __syncthreads();
-    }
-    return s[0];
 }
 
 // x = (I, I), r = b - A x on U, and the per-tile r . z (part_a), r . r (part_b)
@@ -186,7 +154,7 @@ __global__ void __launch_bounds__(FG_THREADS) k_fg_setup(int H, int W, int ntx, 
 template <bool FIRST>
 __global__ void __launch_bounds__(FG_THREADS) k_fg_apply(int H, int W, int ntx, int nt, double eps_r, double omega,
                                                          const int2* __restrict__ tiles, const int32_t* __restrict__ tile_slot,
-                                                         const FgImage* __restrict__ img, const float* __restrict__ ap,
+                                                         const CgImage* __restrict__ img, const float* __restrict__ ap,
                                                          const V6* __restrict__ res, const V6* __restrict__ p_in,
                                                          V6* __restrict__ p_out, V6* __restrict__ q,
                                                          double* __restrict__ part_a) {
@@ -194,7 +162,7 @@ __global__ void __launch_bounds__(FG_THREADS) k_fg_apply(int H, int W, int ntx, 
     __shared__ V6 s_p[FG_S1 * FG_S1];
     __shared__ double s_red[FG_THREADS];
     const TileRef t = tile_of(tiles, ntx);
-    const FgImage& s = img[t.b];
+    const CgImage& s = img[t.b];
     if (s.done) return;                                          // uniform over the block
     const int tid = threadIdx.y * FG_T + threadIdx.x;
     const int x0 = t.tx * FG_T, y0 = t.ty * FG_T;
@@ -250,14 +218,14 @@ __global__ void __launch_bounds__(FG_THREADS) k_fg_apply(int H, int W, int ntx, 
 
 // x += alpha p, r -= alpha q on U; per-tile r . z (part_a) with z = M^-1 r, and r . r (part_b)
 __global__ void __launch_bounds__(FG_THREADS) k_fg_update(int H, int W, int ntx, double eps_r, double omega,
-                                                          const int2* __restrict__ tiles, const FgImage* __restrict__ img,
+                                                          const int2* __restrict__ tiles, const CgImage* __restrict__ img,
                                                           const float* __restrict__ ap, const V6* __restrict__ p,
                                                           const V6* __restrict__ q, V6* __restrict__ x, V6* __restrict__ res,
                                                           double* __restrict__ part_a, double* __restrict__ part_b) {
     __shared__ double s_a[FG_S1 * FG_S1];
     __shared__ double s_red[FG_THREADS];
     const TileRef t = tile_of(tiles, ntx);
-    const FgImage& s = img[t.b];
+    const CgImage& s = img[t.b];
     if (s.done) return;
     const int tid = threadIdx.y * FG_T + threadIdx.x;
     stage_alpha(s_a, FG_S1, t.ty * FG_T - 1, t.tx * FG_T - 1, H, W, ap, (size_t)t.b * H * W, tid);
@@ -282,59 +250,29 @@ __global__ void __launch_bounds__(FG_THREADS) k_fg_update(int H, int W, int ntx,
     if (tid == 0) part_b[blockIdx.x] = sb;
 }
 
-// one wave per image: the sum of part over the image's run of the tile list, lane 0's fixed order
-__device__ __forceinline__ double image_sum(const double* __restrict__ part, int lo, int hi) {
-    const int lane = threadIdx.x;
-    double v = 0.0;
-    for (int k = lo + lane; k < hi; k += WAVE) v += part[k];
-    for (int o = 1; o < WAVE; o <<= 1) v += __shfl_down(v, o, WAVE);
-    return __shfl(v, 0, WAVE);
-}
-
-// MODE 0 (after setup): rz, rr0, the threshold, the images that start solved; MODE 1: alpha = rz / p.q; MODE 2:
-// convergence and beta.  grid B, one wave
-template <int MODE>
-__global__ void __launch_bounds__(WAVE) k_fg_scalar(int max_iter, double tol, FgImage* __restrict__ img,
-                                                    const double* __restrict__ part_a, const double* __restrict__ part_b,
-                                                    int* __restrict__ n_done) {
-    FgImage& s = img[blockIdx.x];
-    if (s.done) return;
-    const double a = image_sum(part_a, s.tile_lo, s.tile_hi);
-    const double b = MODE == 1 ? 0.0 : image_sum(part_b, s.tile_lo, s.tile_hi);
-    if (threadIdx.x != 0) return;
-    if (MODE == 0) {
+// The foreground's side of k_cg_scalar (grid B, one wave).  s.stop is the absolute floor on entry and the threshold on
+// ||r|| after the set-up MODE FG_START (after k_fg_setup): rz, rr0, the threshold, the images that start solved.
+constexpr int FG_START = 0;
+struct FgSolver {
+    static __device__ __forceinline__ bool converged(CgImage& s, double rr, double) {
+        const double rn = sqrt(rr);
+        s.rel = rn / sqrt(s.rr0);
+        return rn <= s.stop;
+    }
+    template <int MODE>
+    static __device__ __forceinline__ void setup(CgImage& s, double a, double b, double tol, int* __restrict__ n_done) {
         const double r0 = sqrt(b), rel_stop = tol * r0;
         s.rz = a;
         s.rr0 = b;
         s.rel = 0.0;
         s.iters = 0;
         s.stop = rel_stop > s.stop ? rel_stop : s.stop;
-        if (!(r0 > s.stop)) { s.done = 1; atomicAdd(n_done, 1); }       // F = B = I already solves the system
-    } else if (MODE == 1) {
-        if (a > 0.0 && std::isfinite(a)) {
-            s.alpha = s.rz / a;
-        } else {                                                 // p = 0 or a breakdown: nothing left to do
-            s.alpha = 0.0;
-            s.done = 1;
-            atomicAdd(n_done, 1);
-        }
-    } else {
-        const double rn = sqrt(b);
-        s.iters += 1;
-        s.rel = rn / sqrt(s.rr0);
-        s.beta = a / s.rz;
-        s.rz = a;
-        if (rn <= s.stop || s.iters >= max_iter) { s.done = 1; atomicAdd(n_done, 1); }
+        if (!(r0 > s.stop)) cg_finish(s, n_done);                // F = B = I already solves the system
     }
-}
-
-__device__ __forceinline__ uint8_t unit_byte(double v) {         // floor(255 clamp(v, 0, 1) + 0.5); a NaN gives 0
-    const double c = v > 0.0 ? (v > 1.0 ? 1.0 : v) : 0.0;
-    return (uint8_t)floor(255.0 * c + 0.5);
-}
+};
 
 // the outputs over the whole frame.  grid (cdiv(H*W, 256), B)
-__global__ void __launch_bounds__(FG_THREADS) k_fg_output(int H, int W, int ntx, int nt, const FgImage* __restrict__ img,
+__global__ void __launch_bounds__(FG_THREADS) k_fg_output(int H, int W, int ntx, int nt, const CgImage* __restrict__ img,
                                                           const int32_t* __restrict__ tile_slot, const uint8_t* __restrict__ bgr,
                                                           const float* __restrict__ alpha, const float* __restrict__ ap,
                                                           const V6* __restrict__ x, uint8_t* __restrict__ foreground,
@@ -401,46 +339,29 @@ extern "C" int ggc_estimate_foreground(ggc_ctx* ctx, ggc_stream stream, int B, i
     int32_t *tile_u = nullptr, *tile_slot = nullptr;
     int2* tiles = nullptr;
     double *part_a = nullptr, *part_b = nullptr;
-    FgImage* img = nullptr;
+    CgImage* img = nullptr;
     int* n_done = nullptr;
-    // over the whole frame: 4 bytes per pixel, 32 per tile, 72 per image
+    // over the whole frame: 4 bytes per pixel, 32 per tile, 64 per image
     if (!carve_scratch(ctx, S_FOREGROUND, [&](Carve& c) {
             ap = c.take<float>(P);
             tile_u = c.take<int32_t>(n_tiles_max); tile_slot = c.take<int32_t>(n_tiles_max);
             tiles = c.take<int2>(n_tiles_max);
             part_a = c.take<double>(n_tiles_max); part_b = c.take<double>(n_tiles_max);
-            img = c.take<FgImage>(B); n_done = c.take<int>(1);
+            img = c.take<CgImage>(B); n_done = c.take<int>(1);
         }))
         return GGC_E_OOM;
     ProfScope prof(ctx, st, "estimate_foreground");
     hipLaunchKernelGGL(k_fg_snap, dim3(ntx, nty, B), dim3(FG_T, FG_T), 0, st, H, W, alpha, ap, tile_u);
     GGC_LAUNCH_CHECK(ctx);
 
-    // the tile list, image by image: the tiles that hold a pixel of U
-    std::vector<int32_t> cnt(n_tiles_max);
-    GGC_HIP(ctx, hipMemcpyAsync(cnt.data(), tile_u, n_tiles_max * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    GGC_HIP(ctx, hipStreamSynchronize(st));
+    // the tile list: the tiles that hold a pixel of U
+    std::vector<int32_t> cnt, slot;
+    if (int e = cg_read_counts(ctx, st, tile_u, n_tiles_max, cnt)) return e;
     std::vector<int2> list;
-    std::vector<int32_t> slot(n_tiles_max, -1);
-    std::vector<FgImage> host_img(B);
-    int n_solve = 0;
-    for (int b = 0; b < B; ++b) {
-        const int32_t* c = cnt.data() + (size_t)b * nt;
-        int64_t u = 0;
-        FgImage& s = host_img[b];
-        s = FgImage{0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0, 1, (int)list.size(), (int)list.size()};
-        for (int k = 0; k < nt; ++k) {
-            if (c[k] <= 0) continue;
-            u += c[k];
-            slot[(size_t)b * nt + k] = (int32_t)list.size();
-            list.push_back(make_int2(b, k));
-        }
-        if (u == 0) continue;
-        s.tile_hi = (int)list.size();
-        s.stop = 1e-12 * std::sqrt(6.0 * (double)u);
-        s.done = 0;
-        ++n_solve;
-    }
+    std::vector<CgImage> host_img;
+    std::vector<int64_t> u_count;
+    const int n_solve = cg_list_tiles(B, ntx, nty, cnt.data(), 0, 0, list, host_img, u_count, &slot);
+    for (int b = 0; b < B; ++b) host_img[b].stop = 1e-12 * std::sqrt(6.0 * (double)u_count[b]);
     const int n_list = (int)list.size();
     // the CG vectors, 256 entries per listed tile: x, r, q and the two p, 240 bytes per entry
     V6 *x = nullptr, *res = nullptr, *q = nullptr, *p0 = nullptr, *p1 = nullptr;
@@ -450,19 +371,17 @@ extern "C" int ggc_estimate_foreground(ggc_ctx* ctx, ggc_stream stream, int B, i
             p0 = c.take<V6>(n_vec); p1 = c.take<V6>(n_vec);
         }))
         return GGC_E_OOM;
-    if (n_list > 0) GGC_HIP(ctx, hipMemcpyAsync(tiles, list.data(), list.size() * sizeof(int2), hipMemcpyHostToDevice, st));
     GGC_HIP(ctx, hipMemcpyAsync(tile_slot, slot.data(), n_tiles_max * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    GGC_HIP(ctx, hipMemcpyAsync(img, host_img.data(), B * sizeof(FgImage), hipMemcpyHostToDevice, st));
-    GGC_HIP(ctx, hipMemsetAsync(n_done, 0, sizeof(int), st));
-    GGC_HIP(ctx, hipStreamSynchronize(st));            // the host vectors go out of scope below
+    if (int e = cg_upload(ctx, st, list, host_img, tiles, img, n_done)) return e;
 
     if (n_list > 0) {
-        const double er = (double)eps_r, om = (double)omega, tl = (double)tol;
+        const double er = (double)eps_r, om = (double)omega;
+        const CgScalars sc{st, B, max_iter, (double)tol, img, part_a, part_b, n_done};
         const dim3 tblk(FG_T, FG_T);
         hipLaunchKernelGGL(k_fg_setup, dim3(n_list), tblk, 0, st, H, W, ntx, er, om, tiles, bgr, ap, x, res, part_a, part_b);
-        hipLaunchKernelGGL(k_fg_scalar<0>, dim3(B), dim3(WAVE), 0, st, max_iter, tl, img, part_a, part_b, n_done);
+        sc.step<FgSolver, FG_START>();
         GGC_LAUNCH_CHECK(ctx);
-        for (int it = 0; it < max_iter; ++it) {
+        const int rc = cg_iterate(ctx, st, max_iter, n_done, n_solve, [&](int it) {
             V6 *p_new = (it & 1) ? p1 : p0, *p_old = (it & 1) ? p0 : p1;
             if (it == 0)
                 hipLaunchKernelGGL(k_fg_apply<true>, dim3(n_list), tblk, 0, st, H, W, ntx, nt, er, om, tiles, tile_slot, img,
@@ -470,17 +389,12 @@ extern "C" int ggc_estimate_foreground(ggc_ctx* ctx, ggc_stream stream, int B, i
             else
                 hipLaunchKernelGGL(k_fg_apply<false>, dim3(n_list), tblk, 0, st, H, W, ntx, nt, er, om, tiles, tile_slot, img,
                                    ap, res, p_old, p_new, q, part_a);
-            hipLaunchKernelGGL(k_fg_scalar<1>, dim3(B), dim3(WAVE), 0, st, max_iter, tl, img, part_a, part_b, n_done);
+            sc.step<FgSolver, CG_ALPHA>();
             hipLaunchKernelGGL(k_fg_update, dim3(n_list), tblk, 0, st, H, W, ntx, er, om, tiles, img, ap, p_new, q, x, res,
                                part_a, part_b);
-            hipLaunchKernelGGL(k_fg_scalar<2>, dim3(B), dim3(WAVE), 0, st, max_iter, tl, img, part_a, part_b, n_done);
-            GGC_LAUNCH_CHECK(ctx);
-            if ((it + 1) % FG_POLL == 0 && it + 1 < max_iter) {
-                std::vector<int32_t> h;
-                if (int e2 = read_i32(ctx, st, n_done, 1, h)) return e2;
-                if (h[0] >= n_solve) break;
-            }
-        }
+            sc.step<FgSolver, CG_BETA>();
+        });
+        if (rc) return rc;
     }
     const dim3 ogrid(cdiv((int64_t)H * W, FG_THREADS), B);
     hipLaunchKernelGGL(k_fg_output, ogrid, dim3(FG_THREADS), 0, st, H, W, ntx, nt, img, tile_slot, bgr, alpha, ap, x,

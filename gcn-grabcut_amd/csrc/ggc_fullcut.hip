@@ -12,7 +12,7 @@
 //                then the label bytes M1 | U << 1 (0 BGD, 1 FGD, 2 PR_BGD, 3 PR_FGD) as 16-byte stores
 // A neighbourhood clipped to the image holds both values exactly when the replicated one does, so the rows above the
 // first and below the last are read as those rows, and for the AND the bits outside the image count as set.
-#include "ggc_internal.h"
+#include "ggc_image.h"
 
 namespace ggc {
 
@@ -25,18 +25,6 @@ constexpr int FC_WORDS = FC_THREADS / WAVE;       // words (of 64 pixels) per bl
 constexpr int FC_MASK_ROWS = 16;                  // rows per block of k_fc_mask
 constexpr int FC_ROWS = 32;                       // rows per block of k_fc_labels
 constexpr int FC_BAND_MAX = 64;
-
-// the half-pixel-centre source coordinate of output index o of n1 over a source of n: ggc_upsample_matte's (ggc_matte.hip)
-__device__ __forceinline__ void fc_coord(int o, int n, int n1, int& i0, int& i1, double& w) {
-    double s = (((double)o + 0.5) * (double)n) / (double)n1 - 0.5;
-    if (s < 0.0) s = 0.0;
-    const double f = floor(s);
-    i0 = (int)f;
-    if (i0 >= n - 1) { i0 = n - 1; w = 0.0; } else { w = s - f; }
-    i1 = min(i0 + 1, n - 1);
-}
-
-__device__ __forceinline__ double fc_lerp(double u, double v, double t) { return u + t * (v - u); }
 
 // the bits of word w that lie inside a row of W1 pixels
 __device__ __forceinline__ u64 fc_valid(int w, int W1) {
@@ -54,8 +42,8 @@ __global__ void __launch_bounds__(FC_THREADS) k_fc_mask(int H, int W, int H1, in
     const int x = w * WAVE + lane, ya = blockIdx.y * FC_MASK_ROWS;
     int x0, x1, ry0, ry1;
     double wx, rwy;
-    fc_coord(min(x, W1 - 1), W, W1, x0, x1, wx);
-    fc_coord(min(ya + min(lane, FC_MASK_ROWS - 1), H1 - 1), H, H1, ry0, ry1, rwy);
+    half_pixel_coord(min(x, W1 - 1), W, W1, x0, x1, wx);
+    half_pixel_coord(min(ya + min(lane, FC_MASK_ROWS - 1), H1 - 1), H, H1, ry0, ry1, rwy);
     const uint8_t* m = binary + (size_t)blockIdx.z * H * W;
     u64* out = mbits + ((size_t)blockIdx.z * H1 + ya) * NW + w;
     const int rows = min(FC_MASK_ROWS, H1 - ya);
@@ -64,7 +52,7 @@ __global__ void __launch_bounds__(FC_THREADS) k_fc_mask(int H, int W, int H1, in
         const double wy = __shfl(rwy, r);
         const double m00 = m[(size_t)y0 * W + x0] != 0 ? 1.0 : 0.0, m01 = m[(size_t)y0 * W + x1] != 0 ? 1.0 : 0.0;
         const double m10 = m[(size_t)y1 * W + x0] != 0 ? 1.0 : 0.0, m11 = m[(size_t)y1 * W + x1] != 0 ? 1.0 : 0.0;
-        const double v = fc_lerp(fc_lerp(m00, m01, wx), fc_lerp(m10, m11, wx), wy);
+        const double v = lerp(lerp(m00, m01, wx), lerp(m10, m11, wx), wy);
         const u64 word = __ballot(x < W1 && v >= 0.5);
         if (lane == 0) out[(size_t)r * NW] = word;
     }

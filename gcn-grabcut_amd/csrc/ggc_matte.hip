@@ -26,7 +26,7 @@
 // horizontal taps of both.  Stage 1 writes q(a), q(b) as 4 int64 per pixel to the context's scratch; stage 2 reads them
 // back with the same walk.  Every pixel's result depends only on its own image and its position, not on the batch: a
 // batch equals its single-image calls bit for bit.  No atomics.
-#include "ggc_internal.h"
+#include "ggc_image.h"
 #include <algorithm>
 #include <cmath>
 
@@ -43,20 +43,14 @@ constexpr int MT_CPL = MT_IW / MT_W;        // staged columns per lane (3)
 struct alignas(32) MatteAB { int64_t a0, a1, a2, b; };   // fixed point, scale 2^S
 struct alignas(32) MatteMean { double c0, c1, c2, c3; };  // mean coefficients of a pixel (stage 2')
 
-__device__ __forceinline__ int mrefl101(int i, int n) {
-    if (n == 1) return 0;
-    while (i < 0 || i >= n) { if (i < 0) i = -i; if (i >= n) i = 2 * n - 2 - i; }
-    return i;
-}
-
 // the reflected image column of each staged column a lane loads (-1: past the staged width).  Columns beyond W - 1 + r
-// are only read by outputs outside the image, which are never written; clamping them first keeps mrefl101 short.
+// are only read by outputs outside the image, which are never written; clamping them first keeps refl101 short.
 __device__ __forceinline__ void staged_columns(int lane, int x0, int r, int W, int (&gx)[MT_CPL]) {
     const int iw = MT_W + 2 * r;
 #pragma unroll
     for (int j = 0; j < MT_CPL; ++j) {
         const int c = lane + MT_W * j;
-        gx[j] = c < iw ? mrefl101(min(x0 - r + c, W - 1 + r), W) : -1;
+        gx[j] = c < iw ? refl101(min(x0 - r + c, W - 1 + r), W) : -1;
     }
 }
 
@@ -141,7 +135,7 @@ __global__ void __launch_bounds__(MT_W) k_matte_ab(int H, int W, int r, double e
 #pragma unroll
     for (int k = 0; k < 13; ++k) acc[k] = 0;
     for (int dy = -r; dy <= r; ++dy) {          // the first row's window, row by row
-        stage_pixels(im, mk, W, mrefl101(y0 + dy, H), lane, gx, s_in);
+        stage_pixels(im, mk, W, refl101(y0 + dy, H), lane, gx, s_in);
         __syncthreads();
         row_moments(s_in, lane, r, tin);
 #pragma unroll
@@ -150,8 +144,8 @@ __global__ void __launch_bounds__(MT_W) k_matte_ab(int H, int W, int r, double e
     }
     for (int y = y0; y < y1; ++y) {
         if (y > y0) {                           // slide: row y + r enters, row y - 1 - r leaves (exact in uint32)
-            stage_pixels(im, mk, W, mrefl101(y + r, H), lane, gx, s_in);
-            stage_pixels(im, mk, W, mrefl101(y - 1 - r, H), lane, gx, s_out);
+            stage_pixels(im, mk, W, refl101(y + r, H), lane, gx, s_in);
+            stage_pixels(im, mk, W, refl101(y - 1 - r, H), lane, gx, s_out);
             __syncthreads();
             row_moments(s_in, lane, r, tin);
             row_moments(s_out, lane, r, tout);
@@ -185,8 +179,6 @@ __device__ __forceinline__ double matte_value(double c0, double c1, double c2, d
     return a < 0.0 ? 0.0 : (a > 1.0 ? 1.0 : a);
 }
 
-__device__ __forceinline__ uint8_t alpha_byte(double a) { return (uint8_t)floor(a * 255.0 + 0.5); }
-
 // stage 2: same grid.  MEAN = false: alpha [B,H,W] f32 and / or rgba [B,H,W,4] u8 (either may be NULL).  MEAN = true
 // (stage 2' of ggc_upsample_matte): the per-pixel mean coefficients C = (acc0 / dn, acc1 / dn, acc2 / dn, acc3 / db)
 // that the alpha of the other form is made of, to `mean` [B,H,W].
@@ -206,7 +198,7 @@ __global__ void __launch_bounds__(MT_W) k_matte_alpha(int H, int W, int r, doubl
     staged_columns(lane, x0, r, W, gx);
     uint64_t acc[4] = {0, 0, 0, 0}, tin[4], tout[4];      // window sums of q, exact modulo 2^64 (the true sums fit int64)
     for (int dy = -r; dy <= r; ++dy) {
-        stage_ab(src, W, mrefl101(y0 + dy, H), lane, gx, s_in);
+        stage_ab(src, W, refl101(y0 + dy, H), lane, gx, s_in);
         __syncthreads();
         row_sum_ab(s_in, lane, r, tin);
 #pragma unroll
@@ -215,8 +207,8 @@ __global__ void __launch_bounds__(MT_W) k_matte_alpha(int H, int W, int r, doubl
     }
     for (int y = y0; y < y1; ++y) {
         if (y > y0) {
-            stage_ab(src, W, mrefl101(y + r, H), lane, gx, s_in);
-            stage_ab(src, W, mrefl101(y - 1 - r, H), lane, gx, s_out);
+            stage_ab(src, W, refl101(y + r, H), lane, gx, s_in);
+            stage_ab(src, W, refl101(y - 1 - r, H), lane, gx, s_out);
             __syncthreads();
             row_sum_ab(s_in, lane, r, tin);
             row_sum_ab(s_out, lane, r, tout);
@@ -237,7 +229,7 @@ __global__ void __launch_bounds__(MT_W) k_matte_alpha(int H, int W, int r, doubl
                 if (alpha) alpha[i] = (float)a;
                 if (rgba) {
                     rgba[4 * i] = pb; rgba[4 * i + 1] = pg; rgba[4 * i + 2] = pr;
-                    rgba[4 * i + 3] = alpha_byte(a);
+                    rgba[4 * i + 3] = unit_byte(a);
                 }
             }
         }
@@ -256,18 +248,6 @@ constexpr int UP_PX = 4;                    // output columns per lane
 constexpr int UP_THREADS = 256;
 constexpr int UP_W = UP_PX * UP_THREADS;    // output columns of a block
 constexpr int UP_H = 32;                    // output rows of a block
-
-// the half-pixel-centre source coordinate of output index o of n1, over a source of n (cv2.INTER_LINEAR, align_corners=False)
-__device__ __forceinline__ void up_coord(int o, int n, int n1, int& i0, int& i1, double& w) {
-    double s = (((double)o + 0.5) * (double)n) / (double)n1 - 0.5;
-    if (s < 0.0) s = 0.0;
-    const double f = floor(s);
-    i0 = (int)f;
-    if (i0 >= n - 1) { i0 = n - 1; w = 0.0; } else { w = s - f; }
-    i1 = min(i0 + 1, n - 1);
-}
-
-__device__ __forceinline__ double lerp(double u, double v, double t) { return u + t * (v - u); }
 
 // the horizontal lerps of source row `row` at the lane's UP_PX columns
 __device__ __forceinline__ void up_row(const MatteMean* __restrict__ row, const int (&x0)[UP_PX], const int (&x1)[UP_PX],
@@ -295,13 +275,13 @@ __global__ void __launch_bounds__(UP_THREADS) k_upsample(int H, int W, int H1, i
     int x0[UP_PX], x1[UP_PX];
     double wx[UP_PX];
 #pragma unroll
-    for (int j = 0; j < UP_PX; ++j) up_coord(min(xb + j, W1 - 1), W, W1, x0[j], x1[j], wx[j]);
+    for (int j = 0; j < UP_PX; ++j) half_pixel_coord(min(xb + j, W1 - 1), W, W1, x0[j], x1[j], wx[j]);
     double h0[UP_PX][4], h1[UP_PX][4];
     int ra = -1, rb = -1;                       // the source rows h0 and h1 hold
     for (int y = yb; y < ye; ++y) {
         int y0, y1;
         double wy;
-        up_coord(y, H, H1, y0, y1, wy);
+        half_pixel_coord(y, H, H1, y0, y1, wy);
         if (y0 != ra) {
             if (y0 == rb) {
 #pragma unroll
@@ -358,7 +338,7 @@ __global__ void __launch_bounds__(UP_THREADS) k_upsample(int H, int W, int H1, i
 #pragma unroll
                 for (int j = 0; j < UP_PX; ++j)
                     q[j] = (uint32_t)px[3 * j] | ((uint32_t)px[3 * j + 1] << 8) | ((uint32_t)px[3 * j + 2] << 16) |
-                           ((uint32_t)alpha_byte(a[j]) << 24);
+                           ((uint32_t)unit_byte(a[j]) << 24);
                 *reinterpret_cast<uint4*>(rgba + 4 * p) = make_uint4(q[0], q[1], q[2], q[3]);
             }
         } else {
@@ -370,7 +350,7 @@ __global__ void __launch_bounds__(UP_THREADS) k_upsample(int H, int W, int H1, i
                 if (binary) binary[i] = a[j] >= 0.5 ? 1 : 0;
                 if (rgba) {
                     rgba[4 * i] = px[3 * j]; rgba[4 * i + 1] = px[3 * j + 1]; rgba[4 * i + 2] = px[3 * j + 2];
-                    rgba[4 * i + 3] = alpha_byte(a[j]);
+                    rgba[4 * i + 3] = unit_byte(a[j]);
                 }
             }
         }

@@ -17,16 +17,10 @@
 // guide statistics are shared between the BG and FG filters (10 blurs, not 14).
 // For radius 1..8 the edge-aware trimap runs as two fused kernels (k_t_stage1,
 // k_t_stage2) in which only the four (a, b) planes exist in HBM.
-#include "ggc_internal.h"
+#include "ggc_image.h"
 #include <cmath>
 
 namespace ggc {
-
-__device__ __forceinline__ int refl101(int i, int n) {
-    if (n == 1) return 0;
-    while (i < 0 || i >= n) { if (i < 0) i = -i; if (i >= n) i = 2 * n - 2 - i; }
-    return i;
-}
 
 struct TDims { int B, H, W; };
 
