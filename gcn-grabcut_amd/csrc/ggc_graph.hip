@@ -17,6 +17,7 @@
 //  * ggc_graph_count synchronises twice (node counts, pair counts) so that the
 //    packed outputs can be sized exactly; ggc_graph_fill only copies.
 #include "ggc_internal.h"
+#include "ggc_math.h"
 #include <algorithm>
 #include <cmath>
 #include <vector>
@@ -24,14 +25,6 @@
 namespace ggc {
 
 constexpr int NL_BIT = 1 << 30;
-
-__device__ __forceinline__ uint32_t f2ord_g(float f) {
-    const uint32_t u = __float_as_uint(f);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float ord2f_g(uint32_t o) {
-    return __uint_as_float((o & 0x80000000u) ? (o & 0x7FFFFFFFu) : ~o);
-}
 
 struct GDims { int B, H, W, Nmax, conn, k_nl; };
 
@@ -89,7 +82,7 @@ __global__ void __launch_bounds__(256) k_bbox(GDims d, const int32_t* __restrict
     }
     }
     for (int o = 32; o > 0; o >>= 1) gv = fmaxf(gv, __shfl_xor(gv, o, 64));
-    if ((threadIdx.x & 63) == 0 && gv > -INFINITY) atomicMax(&gmax[b], f2ord_g(gv));
+    if ((threadIdx.x & 63) == 0 && gv > -INFINITY) atomicMax(&gmax[b], f2ord(gv));
 }
 
 __global__ void k_bbox_init(size_t n, int4* bbox) {
@@ -141,7 +134,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8)))
     const float* hv = hsv + (size_t)b * P * 3;
     const float* gr = grad + (size_t)b * P;
     const int4 bb = live ? bbox[(size_t)b * d.Nmax + r] : make_int4(INT32_MAX, 0, INT32_MAX, 0);
-    const float gden = (float)((double)ord2f_g(gmax[b]) + 1e-6);
+    const float gden = (float)((double)ord2f(gmax[b]) + 1e-6);
     const bool boxed = bb.y > bb.x && bb.w > bb.z;
     const int xa = boxed ? bb.z & ~(SG - 1) : 0;                    // chunks start at multiples of SG: aligned label reads
     const int ya = boxed ? bb.x : 0;
@@ -427,8 +420,8 @@ __global__ void __launch_bounds__(256) k_extract(GDims d, const int32_t* __restr
     }
     if (lane == 0) {
         uint32_t* mx = maxima + (size_t)b * 5;
-        if (run_a) { atomicMax(&mx[0], f2ord_g(mde_a)); atomicMax(&mx[1], f2ord_g(mdx_a)); atomicMax(&mx[4], (uint32_t)msh); }
-        if (run_n) { atomicMax(&mx[2], f2ord_g(mde_n)); atomicMax(&mx[3], f2ord_g(mdx_n)); }
+        if (run_a) { atomicMax(&mx[0], f2ord(mde_a)); atomicMax(&mx[1], f2ord(mdx_a)); atomicMax(&mx[4], (uint32_t)msh); }
+        if (run_n) { atomicMax(&mx[2], f2ord(mde_n)); atomicMax(&mx[3], f2ord(mdx_n)); }
     }
 }
 
@@ -443,8 +436,8 @@ __global__ void __launch_bounds__(256) k_pair_final(int B, const int64_t* __rest
     if (q >= end) return;
     const bool nl = (q - beg) >= totals[3 * b];
     const uint32_t* mx = maxima + (size_t)b * 5;
-    const float de_den = (float)((double)ord2f_g(mx[nl ? 2 : 0]) + 1e-6);
-    const float dx_den = (float)((double)ord2f_g(mx[nl ? 3 : 1]) + 1e-6);
+    const float de_den = (float)((double)ord2f(mx[nl ? 2 : 0]) + 1e-6);
+    const float dx_den = (float)((double)ord2f(mx[nl ? 3 : 1]) + 1e-6);
     io.de[q] = io.de[q] / de_den;
     io.dxy[q] = io.dxy[q] / dx_den;
     if (!nl) io.shared[q] = io.shared[q] / (float)((double)mx[4] + 1e-6);

@@ -117,4 +117,13 @@ __host__ __device__ inline double det_log(double x) {
     return de * LN2_HI + (de * LN2_LO + 2.0 * s * q);
 }
 
+// float <-> uint32 with the floats' order, for atomicMin / atomicMax on floats of either sign
+__device__ __forceinline__ uint32_t f2ord(float f) {
+    const uint32_t u = __float_as_uint(f);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float ord2f(uint32_t o) {
+    return __uint_as_float((o & 0x80000000u) ? (o & 0x7FFFFFFFu) : ~o);
+}
+
 } // namespace ggc

@@ -1,14 +1,12 @@
 // ggc_matte_eval.hip — R2: the four matte errors of Rhemann et al. (CVPR 2009), SAD, MSE, gradient and connectivity, of
 // an 8-bit matte against the true one.  include/ggc.h states the definition; DESIGN.md §5.15 the schedule and the bytes.
 //
-// Connectivity.  The ten threshold sets S_k are labelled by a lock-free union-find (the scheme of ggc_post.hip, here
-// 4-connected), L levels per pass (all ten while the maps fit 4 GiB, else one; GGC_MATTE_EVAL_LEVELS = 1, 2, 5 or 10 fixes
-// it) into a parent map of L x 4 bytes per pixel:
-//   k_me_init    parent = the first pixel of the pixel's horizontal run inside its wave (a ballot, no atomics), area = 0
-//   k_me_merge   joins a run to the run above and across a wave boundary
-//   k_me_area    compresses parent to the root and adds the run lengths to area[root]: one integer atomic per run, and
-//                one per stretch of up to 1024 pixels that lie in one component (the large one that every low level has)
-//   k_me_best    best[b, k] = max (area << 32 | ~root): the largest component, ties to the smallest raster index
+// Connectivity.  The ten threshold sets S_k are labelled by the union-find of ggc_ccl.h with 4 neighbours, L levels per
+// pass (all ten while the maps fit 4 GiB, else one; GGC_MATTE_EVAL_LEVELS = 1, 2, 5 or 10 fixes it) into a parent map of
+// L x 4 bytes per pixel: k_me_init, k_me_merge and k_me_area are its init, merge and compress, and
+//   k_me_area    holds one count per stretch of up to 1024 pixels that lie in one component (the large one that every
+//                low level has) instead of one atomic per run
+//   k_me_best    best[b, k] = the largest component of S_k, ties to the smallest raster index
 //   k_me_lev     lev = k - 1 at the first k with the pixel outside that component; 10 while there is none
 // The whole of S_k is labelled at every level (a component of S_k may be larger than its part that is still alive).
 // Sums.  k_me_sums adds n, SAD, SSE and CONN per block in LDS and issues four integer atomics per block.
@@ -17,6 +15,7 @@
 // k_me_grad_sum adds an image's tiles with one wave in a fixed order.  No float atomics: an image's GRAD does not depend
 // on the batch.
 #include "ggc_internal.h"
+#include "ggc_ccl.h"
 #include <algorithm>
 #include <cmath>
 
@@ -37,22 +36,6 @@ constexpr int ME_SUM_BLOCKS = 120;                // blocks per image of k_me_su
 struct MDims { int B, H, W, P, L; };              // L: levels per labelling pass
 struct MTaps { double g[ME_TAPS], d[ME_TAPS]; };  // G / ||G|| and G' / ||G'||: F_x[i][j] = g[i] d[j], F_y[i][j] = d[i] g[j]
 
-__device__ __forceinline__ int me_find(const int32_t* parent, int i) {
-    int p = __hip_atomic_load(&parent[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    while (p != i) { i = p; p = __hip_atomic_load(&parent[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-    return i;
-}
-__device__ __forceinline__ void me_union(int32_t* parent, int a, int b) {
-    for (;;) {
-        a = me_find(parent, a); b = me_find(parent, b);
-        if (a == b) return;
-        if (a < b) { const int t = a; a = b; b = t; }      // link the larger root under the smaller
-        const int old = atomicMin(&parent[a], b);
-        if (old == a) return;
-        a = old;
-    }
-}
-
 __device__ __forceinline__ bool in_level(int a, int g, int k) { return 10 * a >= 255 * k && 10 * g >= 255 * k; }
 
 // The labelling kernels run over the flat index i = ((b L + j) P + p): level k0 + j of image b, pixel p.
@@ -61,7 +44,6 @@ __global__ void __launch_bounds__(ME_THREADS) k_me_init(MDims d, int k0, const u
                                                         int32_t* __restrict__ area) {
     const size_t n = (size_t)d.B * d.L * d.P;
     const size_t i = (size_t)blockIdx.x * ME_THREADS + threadIdx.x;
-    const int lane = threadIdx.x & 63;
     bool on = false, same_left = false;
     int p = 0;
     if (i < n) {
@@ -72,9 +54,9 @@ __global__ void __launch_bounds__(ME_THREADS) k_me_init(MDims d, int k0, const u
         on = in_level(pred[px], gt[px], k);
         same_left = on && (p % d.W) > 0 && in_level(pred[px - 1], gt[px - 1], k);
     }
-    const unsigned long long starts = __ballot(on && (!same_left || lane == 0));
+    const int first = ccl_run_first(on, same_left, p);
     if (i < n) {
-        parent[i] = on ? p - (lane - (63 - __clzll((long long)(starts & ((2ull << lane) - 1ull))))) : -1;
+        parent[i] = on ? first : -1;
         area[i] = 0;
     }
 }
@@ -86,10 +68,7 @@ __global__ void __launch_bounds__(ME_THREADS) k_me_merge(MDims d, int32_t* __res
     int32_t* par = parent + base;
     const int p = (int)(i - base), x = p % d.W;
     if (par[p] < 0) return;
-    const bool left = x > 0 && par[p - 1] >= 0;
-    if (left && (i & 63) == 0) me_union(par, p, p - 1);                          // the run continues across k_me_init's wave boundary
-    // the pixel above; when the left and the upper-left pixel are set too, the left pixel makes this join
-    if (p >= d.W && par[p - d.W] >= 0 && !(left && par[p - d.W - 1] >= 0)) me_union(par, p, p - d.W);
+    ccl_merge_pixel<4>(par, p, x, p >= d.W, d.W, i, [par](int q) { return par[q] >= 0; });
 }
 
 // A wave walks ME_AREA_CHUNKS consecutive chunks of 64 pixels.  While chunk after chunk lies in one component, the count
@@ -112,8 +91,7 @@ __global__ void __launch_bounds__(ME_THREADS) k_me_area(MDims d, int32_t* __rest
             base = (size_t)q * d.P;
             const int p = (int)(i - base);
             same_left = (p % d.W) > 0 && parent[i - 1] >= 0;
-            r = me_find(parent + base, p);
-            parent[i] = r;                                  // compress (roots keep pointing at themselves)
+            r = ccl_compress(parent + base, p);
         }
         const unsigned long long vmask = __ballot(valid);
         if (!vmask) continue;
@@ -129,17 +107,12 @@ __global__ void __launch_bounds__(ME_THREADS) k_me_area(MDims d, int32_t* __rest
             held_cnt += __popcll(vmask);
             continue;
         }
-        const unsigned long long starts = __ballot(valid && (!same_left || lane == 0));
-        if (valid && ((starts >> lane) & 1ull)) {           // one atomic per run (the runs of k_me_init)
-            const unsigned long long stop = (starts | ~vmask) >> lane >> 1;
-            const int len = stop ? __ffsll((long long)stop) : 64 - lane;
-            atomicAdd(&area[base + r], len);
-        }
+        ccl_count_runs(valid, same_left, vmask, area, base + r);
     }
     if (held_cnt && lane == 0) atomicAdd(&area[held], held_cnt);
 }
 
-// best[b, k - 1] = max over the components of S_k of (area << 32 | ~root); 0 when S_k is empty
+// best[b, k - 1] = the ccl_best_key of the largest component of S_k; 0 when S_k is empty
 __global__ void __launch_bounds__(ME_THREADS) k_me_best(MDims d, int k0, const int32_t* __restrict__ parent,
                                                         const int32_t* __restrict__ area,
                                                         unsigned long long* __restrict__ best) {
@@ -148,8 +121,7 @@ __global__ void __launch_bounds__(ME_THREADS) k_me_best(MDims d, int k0, const i
     const size_t q = i / d.P;
     const int p = (int)(i - q * d.P);
     if (parent[i] != p) return;                              // roots only
-    atomicMax(&best[(q / d.L) * ME_LEVELS + (k0 - 1) + (q % d.L)],
-              ((unsigned long long)(unsigned)area[i] << 32) | (unsigned long long)(0xFFFFFFFFu - (unsigned)p));
+    atomicMax(&best[(q / d.L) * ME_LEVELS + (k0 - 1) + (q % d.L)], ccl_best_key(area[i], p));
 }
 
 // one thread per pixel of the batch: the first level of this pass at which the pixel is outside the largest component
@@ -163,8 +135,7 @@ __global__ void __launch_bounds__(ME_THREADS) k_me_lev(MDims d, int k0, const in
     const int p = (int)(i - b * d.P);
     for (int j = 0; j < d.L; ++j) {
         const unsigned long long bb = best[b * ME_LEVELS + (k0 - 1) + j];
-        const int root = (int)(0xFFFFFFFFu - (unsigned)(bb & 0xFFFFFFFFull));
-        if (bb == 0 || parent[(b * d.L + j) * d.P + p] != root) { lev[i] = (uint8_t)(k0 + j - 1); return; }
+        if (bb == 0 || parent[(b * d.L + j) * d.P + p] != ccl_best_root(bb)) { lev[i] = (uint8_t)(k0 + j - 1); return; }
     }
 }
 

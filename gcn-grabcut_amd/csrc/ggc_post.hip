@@ -1,39 +1,21 @@
 // ggc_post.hip — K0 mask clean-up, O0 output composition, R0 IoU.
 //
 // clean_mask (reference pipeline.py:189-227) needs 8-connected components with
-// areas: a lock-free union-find over the foreground pixels (roots = smallest
-// pixel index of a component, so numbering follows raster order like the CPU
-// path), areas by integer atomics at the roots, then one pass applying the
-// keep rule.  overlay_mask / crop_foreground: grabcut.py:180-195.
+// areas: the union-find labelling of ggc_ccl.h over the foreground pixels (roots
+// number in raster order like the CPU path), areas by integer atomics at the
+// roots, then one pass applying the keep rule.  overlay_mask / crop_foreground: grabcut.py:180-195.
 // IoU: metrics.py:79-84.
 #include "ggc_internal.h"
+#include "ggc_ccl.h"
 
 namespace ggc {
 
 struct PDims { int B, H, W, P; };
 
-__device__ __forceinline__ int uf_find(const int32_t* parent, int i) {
-    int p = __hip_atomic_load(&parent[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    while (p != i) { i = p; p = __hip_atomic_load(&parent[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-    return i;
-}
-__device__ __forceinline__ void uf_union(int32_t* parent, int a, int b) {
-    for (;;) {
-        a = uf_find(parent, a); b = uf_find(parent, b);
-        if (a == b) return;
-        if (a < b) { const int t = a; a = b; b = t; }      // link the larger root under the smaller
-        const int old = atomicMin(&parent[a], b);
-        if (old == a) return;
-        a = old;
-    }
-}
-
-// Horizontal runs need no atomics: a pixel's parent starts as the first pixel of its run inside the wave's 64
-// consecutive pixels (ballot of the run breaks); k_cc_merge only joins runs.
+// The labelling is that of ggc_ccl.h with 8 neighbours; "q is set" is parent[q] >= 0.
 __global__ void __launch_bounds__(256) k_cc_init(PDims d, const uint8_t* __restrict__ mask, int32_t* __restrict__ parent,
                                                  int32_t* __restrict__ total) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const int lane = threadIdx.x & 63;
     int on = 0, b = -1, p = 0;
     bool same_left = false;
     if (i < (size_t)d.B * d.P) {
@@ -42,9 +24,8 @@ __global__ void __launch_bounds__(256) k_cc_init(PDims d, const uint8_t* __restr
         p = (int)(i % d.P);
         same_left = on && (p % d.W) > 0 && mask[i - 1] != 0;
     }
-    const unsigned long long starts = __ballot(on && (!same_left || lane == 0));
-    if (i < (size_t)d.B * d.P)
-        parent[i] = on ? p - (lane - (63 - __clzll((long long)(starts & ((2ull << lane) - 1ull))))) : -1;
+    const int first = ccl_run_first(on, same_left, p);
+    if (i < (size_t)d.B * d.P) parent[i] = on ? first : -1;
     // total[b] != 0  <=>  the image has foreground (pipeline.py:208).  A wave can straddle images.
     if (d.P >= 64) {
         const int b0 = __builtin_amdgcn_readfirstlane(b);
@@ -65,29 +46,12 @@ __global__ void __launch_bounds__(256) k_cc_merge(PDims d, int32_t* __restrict__
     int32_t* par = parent + base;
     const int p = y * d.W + x;
     if (par[p] < 0) return;
-    // 8-connectivity with the already-scanned neighbours (left, up-left, up, up-right).  Foreground pixels of one row
-    // that touch are one run already, so a pixel whose left neighbour is foreground only adds what that neighbour
-    // could not see: the up-right pixel when the pixel above is background.
-    const bool left = x > 0 && par[p - 1] >= 0;
-    if (left && ((base + p) & 63) == 0) uf_union(par, p, p - 1);                       // run continues across k_cc_init's wave boundary
-    if (y > 0) {
-        const bool up = par[p - d.W] >= 0;
-        const bool ul = x > 0 && par[p - d.W - 1] >= 0, ur = x + 1 < d.W && par[p - d.W + 1] >= 0;
-        if (left) {
-            if (ur && !up) uf_union(par, p, p - d.W + 1);
-        } else if (up) {
-            uf_union(par, p, p - d.W);
-        } else {
-            if (ul) uf_union(par, p, p - d.W - 1);
-            if (ur) uf_union(par, p, p - d.W + 1);
-        }
-    }
+    ccl_merge_pixel<8>(par, p, x, y > 0, d.W, base + p, [par](int q) { return par[q] >= 0; });
 }
 
 // NB: a wave of a row-block may straddle two images only if P % 64 != 0; total[] is per image so guard by image.
 __global__ void __launch_bounds__(256) k_cc_area(PDims d, int32_t* __restrict__ parent, int32_t* __restrict__ area) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const int lane = threadIdx.x & 63;
     const bool valid = i < (size_t)d.B * d.P && parent[i] >= 0;
     bool same_left = false;
     size_t base = 0;
@@ -96,20 +60,12 @@ __global__ void __launch_bounds__(256) k_cc_area(PDims d, int32_t* __restrict__ 
         base = (i / d.P) * d.P;
         const int p = (int)(i - base);
         same_left = (p % d.W) > 0 && parent[i - 1] >= 0;
-        r = uf_find(parent + base, p);
-        parent[i] = r;                                      // compress (roots keep pointing at themselves)
+        r = ccl_compress(parent + base, p);
     }
-    // one atomic per run (the runs of k_cc_init), not per pixel
-    const unsigned long long vmask = __ballot(valid);
-    const unsigned long long starts = __ballot(valid && (!same_left || lane == 0));
-    if (valid && ((starts >> lane) & 1ull)) {
-        const unsigned long long stop = (starts | ~vmask) >> lane >> 1;
-        const int len = stop ? __ffsll((long long)stop) : 64 - lane;
-        atomicAdd(&area[base + r], len);
-    }
+    ccl_count_runs(valid, same_left, __ballot(valid), area, base + r);
 }
 
-// best[b] = max over components of (area << 32 | ~root): largest area, ties to the first component in raster order
+// best[b] = the largest component's ccl_best_key
 __global__ void __launch_bounds__(256) k_cc_best(PDims d, double min_area, const int32_t* __restrict__ parent,
                                                  const int32_t* __restrict__ area, unsigned long long* __restrict__ best,
                                                  int32_t* __restrict__ any) {
@@ -118,7 +74,7 @@ __global__ void __launch_bounds__(256) k_cc_best(PDims d, double min_area, const
     const int b = (int)(i / d.P), p = (int)(i % d.P);
     if (parent[i] != p) return;                              // roots only
     const int a = area[i];
-    atomicMax(&best[b], ((unsigned long long)(unsigned)a << 32) | (unsigned long long)(0xFFFFFFFFu - (unsigned)p));
+    atomicMax(&best[b], ccl_best_key(a, p));
     if ((double)a >= min_area) atomicOr(&any[b], 1);
 }
 
@@ -136,7 +92,7 @@ __global__ void __launch_bounds__(256) k_cc_apply(PDims d, double min_area, int 
     uint8_t keep = 0;
     if (r >= 0) {
         const size_t base = (size_t)b * d.P;
-        const int best_root = (int)(0xFFFFFFFFu - (unsigned)(best[b] & 0xFFFFFFFFull));
+        const int best_root = ccl_best_root(best[b]);
         keep = (keep_largest || !any[b]) ? (r == best_root) : ((double)area[base + r] >= min_area);
     }
     out[i] = keep;

@@ -24,6 +24,7 @@
 //    the members to float32 running sums in that order — identical rounding to skimage;
 //  * all arithmetic is compiled without FMA contraction.
 #include "ggc_internal.h"
+#include "ggc_ccl.h"
 #include "ggc_math.h"
 #include <cmath>
 #include <vector>
@@ -31,14 +32,6 @@
 namespace ggc {
 
 // ---------------------------------------------------------------- min / max
-__device__ __forceinline__ uint32_t f2ord(float f) {
-    const uint32_t u = __float_as_uint(f);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float ord2f(uint32_t o) {
-    return __uint_as_float((o & 0x80000000u) ? (o & 0x7FFFFFFFu) : ~o);
-}
-
 __global__ void k_minmax_init(int B, uint32_t* mm) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < B) { mm[2 * i] = 0xFFFFFFFFu; mm[2 * i + 1] = 0u; }
@@ -526,31 +519,13 @@ __global__ void __launch_bounds__(64) k_connectivity_seq(int H, int W, const int
 //      last neighbour pixel that belongs to an earlier-discovered component; the
 //      label is inherited along that pointer chain (0 when there is none).
 // Validated pixel-for-pixel against the sequential kernel and the CPU oracle.
-__device__ __forceinline__ int cn_find(const int32_t* parent, int i) {
-    int p = __hip_atomic_load(&parent[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    while (p != i) { i = p; p = __hip_atomic_load(&parent[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-    return i;
-}
-__device__ __forceinline__ void cn_union(int32_t* parent, int a, int b) {
-    for (;;) {
-        a = cn_find(parent, a); b = cn_find(parent, b);
-        if (a == b) return;
-        if (a < b) { const int t = a; a = b; b = t; }
-        const int old = atomicMin(&parent[a], b);
-        if (old == a) return;
-        a = old;
-    }
-}
-
 struct CnDims { int B, H, W, P, min_size, max_size; };
 
-// Horizontal runs need no atomics: inside a wave's 64 consecutive pixels a pixel's parent is set straight to the first
-// pixel of its run (ballot of the run breaks), which is also the run's smallest index.  k_cn_merge then only joins
-// runs: across a 64-pixel boundary, and vertically where a run first touches a run of the row above.
+// The labelling of ggc_ccl.h with 4 neighbours over the pending pixels; q belongs with p if it is pending and has p's
+// raw label.  A pixel that is not pending keeps its parent from an earlier round.
 __global__ void __launch_bounds__(256) k_cn_reset(CnDims d, const int32_t* __restrict__ raw, const uint8_t* __restrict__ pending,
                                                   int32_t* __restrict__ parent, int32_t* __restrict__ csize) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const int lane = threadIdx.x & 63;
     const bool valid = i < (size_t)d.B * d.P && pending[i];
     bool same_left = false;
     int p = 0;
@@ -558,10 +533,9 @@ __global__ void __launch_bounds__(256) k_cn_reset(CnDims d, const int32_t* __res
         p = (int)(i % d.P);
         same_left = (p % d.W) > 0 && pending[i - 1] && raw[i - 1] == raw[i];
     }
-    const unsigned long long starts = __ballot(valid && (!same_left || lane == 0));
+    const int first = ccl_run_first(valid, same_left, p);
     if (!valid) return;
-    const int start_lane = 63 - __clzll((long long)(starts & ((2ull << lane) - 1ull)));
-    parent[i] = p - (lane - start_lane);
+    parent[i] = first;
     csize[i] = 0;
 }
 
@@ -573,19 +547,12 @@ __global__ void __launch_bounds__(256) k_cn_merge(CnDims d, const int32_t* __res
     const int p = y * d.W + x;
     if (!pending[base + p]) return;
     const int l = raw[base + p];
-    const bool same_left = x > 0 && pending[base + p - 1] && raw[base + p - 1] == l;
-    if (same_left && ((base + p) & 63) == 0) cn_union(parent + base, p, p - 1);      // run continues across k_cn_reset's wave boundary
-    if (y > 0 && pending[base + p - d.W] && raw[base + p - d.W] == l) {
-        // the left neighbour already joined this pair of runs if it sits under the same upper run
-        const bool joined = same_left && pending[base + p - d.W - 1] && raw[base + p - d.W - 1] == l;
-        if (!joined) cn_union(parent + base, p, p - d.W);
-    }
+    ccl_merge_pixel<4>(parent + base, p, x, y > 0, d.W, base + p, [=](int q) { return pending[base + q] && raw[base + q] == l; });
 }
 
 __global__ void __launch_bounds__(256) k_cn_size(CnDims d, const int32_t* __restrict__ raw, const uint8_t* __restrict__ pending,
                                                  int32_t* __restrict__ parent, int32_t* __restrict__ csize) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const int lane = threadIdx.x & 63;
     const bool valid = i < (size_t)d.B * d.P && pending[i];
     bool same_left = false;
     size_t base = 0;
@@ -594,17 +561,9 @@ __global__ void __launch_bounds__(256) k_cn_size(CnDims d, const int32_t* __rest
         base = (i / d.P) * d.P;
         const int p = (int)(i - base);
         same_left = (p % d.W) > 0 && pending[i - 1] && raw[i - 1] == raw[i];
-        r = cn_find(parent + base, p);
-        parent[i] = r;
+        r = ccl_compress(parent + base, p);
     }
-    // one atomic per run (the runs of k_cn_reset), not per pixel
-    const unsigned long long vmask = __ballot(valid);
-    const unsigned long long starts = __ballot(valid && (!same_left || lane == 0));
-    if (valid && ((starts >> lane) & 1ull)) {
-        const unsigned long long stop = (starts | ~vmask) >> lane >> 1;       // next run start or hole above this lane
-        const int len = stop ? __ffsll((long long)stop) : 64 - lane;
-        atomicAdd(&csize[base + r], len);
-    }
+    ccl_count_runs(valid, same_left, __ballot(valid), csize, base + r);
 }
 
 // components below max_size are final; count the ones that still need carving
