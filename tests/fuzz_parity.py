@@ -4,6 +4,7 @@ Environment: FUZZ_N cases (40), FUZZ_SEED (1), FUZZ_MIN / FUZZ_MAX image side (2
 the SuperpixelGraphConfig / segment() options (use_lab, connectivity, n_nonlocal, compactness, sigma, thresholds, refine_iters, ...).
     gpurun -- 'FUZZ_OPTIONS=1 FUZZ_N=120 python3 tests/fuzz_parity.py'
 FUZZ_KIND=grabcut fuzzes the GrabCut class instead (trimap / rectangle starts, refine, colour spaces, 1-5 iterations).
+The interactive and post entries (clicks, geodesic hints, strokes, polygons, scissors, next click, the tallies) are fuzzed by tests/fuzz_features.py.
 Round 3: 60 + 150 (sides 6-70) + 25 (sides 250-640) + 120 (with options) pipeline cases and 150 GrabCut-class cases, no mismatch."""
 import os, sys, time
 R = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))          # the repository this script sits in

@@ -182,6 +182,21 @@ def _raw(eng, bgr, packed, setting=DEFAULTS, verts=None, capacity=0, vert_ptr=No
                         P(args["vp"]), P(args["verts"]), args["capacity"])
 
 
+def _count_then_fill(eng, bgr, packed, setting=DEFAULTS):
+    """The two-call pattern on device arrays: count only, then the fill with exactly enough rows and one spare
+    -> (vert_ptr of the count-only call, vert_ptr of the fill, verts (V,2), the spare row), on the host, unchecked."""
+    q = int(packed[2].numel())
+    vp = torch.full((q + 1,), POISON, dtype=torch.int32, device=eng.device)
+    _raw(eng, bgr, packed, setting, vert_ptr=vp)
+    count_ptr = vp.cpu().numpy()
+    n = int(count_ptr[-1])
+    verts = torch.full((n + 1, 2), POISON, dtype=torch.int32, device=eng.device)
+    vp.fill_(POISON)
+    _raw(eng, bgr, packed, setting, vert_ptr=vp, verts=verts, capacity=n)
+    host = verts.cpu().numpy()
+    return count_ptr, vp.cpu().numpy(), host[:n], host[n]
+
+
 def test_count_only_capacity_and_no_ops(eng, kernel_batch):
     from gcn_grabcut import _native
     from gcn_grabcut.graph_builder import pack_paths

@@ -34,8 +34,10 @@ def _apply(eng, masks, per_image, radius):
     return m.cpu().numpy()
 
 
-def _pixels(eng, shape, per_image, fill=True):
-    """ggc_stroke_pixels through ctx.call: the count-only call, then (fill=True) the fill -> (hint_ptr, rows | None)."""
+def _pixels(eng, shape, per_image, fill=True, raw=False):
+    """ggc_stroke_pixels through ctx.call: the count-only call, then (fill=True) the fill -> (hint_ptr, rows | None).
+    raw=True checks nothing and returns what both calls wrote: (hint_ptr of the count-only call, rows, hint_ptr of the
+    fill, the spare row), for a caller that reports differences itself."""
     strokes, ptr = strokes_ref.pack(per_image)
     d_strokes, d_ptr = eng.upload_strokes(strokes, ptr)
     b, h, w = shape
@@ -49,6 +51,9 @@ def _pixels(eng, shape, per_image, fill=True):
     rows = torch.full((n + 1, 3), -9, dtype=torch.int32, device=eng.device)      # one spare row: it must stay untouched
     hp2 = torch.full((b + 1,), -5, dtype=torch.int32, device=eng.device)
     eng.ctx.call("ggc_stroke_pixels", *args, hp2.data_ptr(), rows.data_ptr(), n)
+    if raw:
+        rows = rows.cpu().numpy()
+        return counted, rows[:n], hp2.cpu().numpy(), rows[n]
     assert np.array_equal(hp2.cpu().numpy(), counted)                   # the count-only call equals the fill call
     rows = rows.cpu().numpy()
     assert (rows[n] == -9).all()
