@@ -25,39 +25,50 @@ __device__ __forceinline__ int dir_nb(const GcDims& d, int y, int x, int dir) {
 __host__ __device__ __forceinline__ size_t rc_idx(int dir, size_t i) { return i * 8 + (size_t)dir; }
 
 // One pixel of the network, the per-pixel part of graph construction (ggc_grabcut's k_build_graph, ggc_grid_maxflow's
-// k_gf_build): residual arcs from the n-link planes nw [4][B][P] (0 left, 1 up-left, 2 up, 3 up-right; a link that points
-// outside the image is ignored), the arc mask, and the terminal balance of the t-link difference tw (source minus sink).
-__device__ __forceinline__ void mf_init_pixel(const GcDims& d, int b, int p, int32_t tw, const int32_t* __restrict__ nw,
-                                              int32_t* __restrict__ rc, int32_t* __restrict__ ex, int32_t* __restrict__ snk,
-                                              uint8_t* __restrict__ rmask, bool warm) {
-    const size_t BP = (size_t)d.B * d.P, i = (size_t)b * d.P + p;
+// k_gf_build).  Cold: the 8 residual arcs from their capacities cap[dir] (0 for an arc that leaves the image), the arc
+// mask, and the terminal balance of the t-link difference tw (source minus sink).
+__device__ __forceinline__ void mf_cold_pixel(size_t i, int32_t tw, const int32_t (&cap)[8], int32_t* __restrict__ rc,
+                                              int32_t* __restrict__ ex, int32_t* __restrict__ snk, uint8_t* __restrict__ rmask) {
+    int arcs = 0;                                        // bit dir = residual arc towards dir (the push visits of ggc_maxflow*.hip keep it current)
+    int4* r = reinterpret_cast<int4*>(rc + rc_idx(0, i));   // the 8 arcs of a pixel: one aligned 32-byte sector
+    r[0] = make_int4(cap[0], cap[1], cap[2], cap[3]);
+    r[1] = make_int4(cap[4], cap[5], cap[6], cap[7]);
+#pragma unroll
+    for (int dir = 0; dir < 8; ++dir) arcs |= cap[dir] > 0 ? 1 << dir : 0;
+    rmask[i] = (uint8_t)arcs;
+    ex[i] = tw > 0 ? tw : 0;
+    snk[i] = tw < 0 ? -tw : 0;
+}
+
+// Capacities of a pixel's 8 arcs from the n-link planes nw [4][B][P] (0 left, 1 up-left, 2 up, 3 up-right; a link that
+// points outside the image is ignored): own planes give the arcs towards left / up-left / up / up-right, the mirrored arcs
+// read the neighbour's plane.
+__device__ __forceinline__ void mf_plane_caps(const GcDims& d, int b, int p, const int32_t* __restrict__ nw, int32_t (&cap)[8]) {
+    const size_t BP = (size_t)d.B * d.P;
     const int y = p / d.W, x = p % d.W;
     const int32_t* nwb = nw + (size_t)b * d.P;
-    // own planes give the arcs towards left / up-left / up / up-right; the mirrored arcs read the neighbour's plane
     const int dirs[4] = {0, 4, 2, 6};
-    int32_t inflow = 0;
-    int arcs = 0;                                        // bit dir = residual arc towards dir (the push visits of ggc_maxflow*.hip keep it current)
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
         const int dir = dirs[k];
-        const int32_t c0 = dir_nb(d, y, x, dir) >= 0 ? nwb[(size_t)k * BP + p] : 0;
+        cap[dir] = dir_nb(d, y, x, dir) >= 0 ? nwb[(size_t)k * BP + p] : 0;
         const int q = dir_nb(d, y, x, dir ^ 1);
-        const int32_t c1 = q >= 0 ? nwb[(size_t)k * BP + q] : 0;
-        if (warm) {   // keep the n-link flow of the previous solve: net inflow = sum (residual - capacity)
-            const int32_t ra = rc[rc_idx(dir, i)], rb = rc[rc_idx((dir ^ 1), i)];
-            inflow += (ra - c0) + (rb - c1);
-            arcs |= (ra > 0 ? 1 << dir : 0) | (rb > 0 ? 1 << (dir ^ 1) : 0);
-        } else {
-            rc[rc_idx(dir, i)] = c0;
-            rc[rc_idx((dir ^ 1), i)] = c1;
-            arcs |= (c0 > 0 ? 1 << dir : 0) | (c1 > 0 ? 1 << (dir ^ 1) : 0);
-        }
+        cap[dir ^ 1] = q >= 0 ? nwb[(size_t)k * BP + q] : 0;
     }
-    rmask[i] = (uint8_t)arcs;
-    // Warm start (dynamic graph cuts): only the t-links change between solves, and adding a constant to both t-links of a
-    // pixel never changes the cut, so the old n-link flow stays a valid preflow: the pixel's new terminal balance is its
-    // t-link difference plus what its neighbours sent it.
-    const int32_t bal = tw + inflow;
+}
+
+// Warm start (dynamic graph cuts): only the t-links change between solves, and adding a constant to both t-links of a
+// pixel never changes the cut, so the old n-link flow stays a valid preflow: the pixel's new terminal balance is its
+// t-link difference plus what its neighbours sent it, tw + sum (residual - capacity).  That sum is already in memory:
+// every push moves one amount in ex and in the two arcs of its link, a push to the sink lowers ex and snk together, so at
+// any kernel boundary ex - snk = tw_old + sum (residual - capacity), and the new balance is (ex - snk) + (tw - tw_old),
+// the same integers.  Capacities and arc masks stay: the push visits keep rmask current for the arcs inside their tile and
+// the tiles' dirty words cover arcs re-opened from a neighbouring tile (ggc_mf_sweep.h).
+// Bounds: |tw| <= 2^27 and 8 capacities <= 2^24 each give |ex - snk| <= 2^27 + 8 * 2^24 = 2^28 (< 3 * 2^27), and
+// |tw - tw_old| <= 2^28, so the new balance stays within 2^29 in int32.
+__device__ __forceinline__ void mf_warm_pixel(size_t i, int32_t tw, int32_t tw_old, int32_t* __restrict__ ex,
+                                              int32_t* __restrict__ snk) {
+    const int32_t bal = (ex[i] - snk[i]) + (tw - tw_old);
     ex[i] = bal > 0 ? bal : 0;
     snk[i] = bal < 0 ? -bal : 0;
 }
@@ -75,8 +86,10 @@ struct MfControl {
 //   dist [B][P] out: distance to the sink in the final residual graph, >= DINF when unreachable (=> foreground)
 //   rmask [B][P] arc masks of rc (bit dir = residual arc towards dir); masks_exact: every byte is current (cold start) —
 //   otherwise the tiles marked dirty by the previous solve of this call keep their mark.
+//   n_open: in/out, the number of images with state[b] == 0.  Negative: counted on the device and read back (blocking);
+//   state[] does not change between the solves of one call, so the caller hands the first solve's count to the later ones.
 int maxflow(ggc_ctx* ctx, hipStream_t st, const GcDims& d, const int32_t* state, int32_t* rc, int32_t* ex,
-            int32_t* snk, int32_t* dist, uint8_t* rmask, const MfControl& ctl, bool masks_exact);
+            int32_t* snk, int32_t* dist, uint8_t* rmask, const MfControl& ctl, bool masks_exact, int& n_open);
 
 // Tile geometry of the max-flow kernels (ggc_maxflow.hip: launches over work lists; ggc_maxflow_async.hip: one launch per sparse phase)
 constexpr int MF_RT = 32;                          // relabel tile side

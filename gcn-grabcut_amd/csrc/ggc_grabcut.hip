@@ -5,7 +5,7 @@
 //   initGMMs    seeded k-means++ on the uint8 colours (exact integer D^2
 //               sampling, 10 assignment steps), GMM fit from exact integer sums
 //   calcBeta    exact integer sum of squared neighbour differences
-//   n-links     gamma * exp(-beta d^2) quantised to int32 (scale 2^18)
+//   n-links     gamma * exp(-beta d^2) quantised to int32 (scale 2^18), computed by the cold graph build
 //   x n_iter    assign components | learn GMMs | t-links | max-flow | relabel
 //
 // Everything that feeds an integer decision is order independent (integer
@@ -289,7 +289,7 @@ constexpr int BIN_COPIES = 16, BIN_PX = 4;
 __global__ void __launch_bounds__(256) k_km_assign(GcDims d, const uint8_t* __restrict__ img,
                                                    const uint8_t* __restrict__ mask, const int32_t* __restrict__ state,
                                                    const KmState* __restrict__ km, uint8_t* __restrict__ comp,
-                                                   unsigned long long* __restrict__ acc) {
+                                                   unsigned long long* __restrict__ acc, int store_comp) {
     __shared__ unsigned int s_acc[2 * NCOMP * 4 * BIN_COPIES];     // (256 * BIN_PX) x 255 fits 32 bits easily
     const int b = blockIdx.y, tid = threadIdx.x, cp = tid % BIN_COPIES;
     if (state[b]) return;
@@ -313,7 +313,7 @@ __global__ void __launch_bounds__(256) k_km_assign(GcDims d, const uint8_t* __re
                     if (k == 0 || dist < bd) { best = k; bd = dist; }
                 }
             }
-            comp[gp] = (uint8_t)best;
+            if (store_comp) comp[gp] = (uint8_t)best;          // read by k_gmm_accum<0> after the last step only
             unsigned int* a = s_acc + (c * NCOMP + best) * 4 * BIN_COPIES + cp;
             atomicAdd(&a[0], 1u); atomicAdd(&a[BIN_COPIES], (unsigned int)px[0]);
             atomicAdd(&a[2 * BIN_COPIES], (unsigned int)px[1]); atomicAdd(&a[3 * BIN_COPIES], (unsigned int)px[2]);
@@ -340,12 +340,15 @@ __global__ void k_km_update(int B, const int32_t* __restrict__ state, KmState* _
 }
 
 // --------------------------------------------------------------- GMM learning
-// MODE 0: components already in comp[] (after k-means). MODE 1: assignGMMsComponents first.
+// MODE 0: components already in comp[] (after k-means). MODE 1: assignGMMsComponents first; with `dist` (the labels of
+// the previous iteration's max-flow) the pixel first takes that iteration's estimateSegmentation, as k_gc_relabel would
+// have: the pass over mask and the launch are this kernel's own, dist is read for probable pixels only and mask is
+// stored only where it changes.
 template <int MODE>
 __global__ void __launch_bounds__(256) k_gmm_accum(GcDims d, const uint8_t* __restrict__ img,
-                                                   const uint8_t* __restrict__ mask, const int32_t* __restrict__ state,
-                                                   const Gmm* __restrict__ gmm, uint8_t* __restrict__ comp,
-                                                   unsigned long long* __restrict__ acc) {
+                                                   uint8_t* __restrict__ mask, const int32_t* __restrict__ state,
+                                                   const Gmm* __restrict__ gmm, const uint8_t* __restrict__ comp,
+                                                   const int32_t* __restrict__ dist, unsigned long long* __restrict__ acc) {
     // Block-local bins in LDS as 32-bit counters (256 * BIN_PX pixels x 255^2 < 2^32), products stored once per
     // symmetric pair: 10 LDS atomics per pixel into BIN_COPIES-fold privatised slots (see k_km_assign); the exact
     // 64-bit totals are formed by the global flush.
@@ -360,13 +363,17 @@ __global__ void __launch_bounds__(256) k_gmm_accum(GcDims d, const uint8_t* __re
         const int p = (blockIdx.x * BIN_PX + j) * 256 + tid;
         if (p < d.P) {
             const size_t gp = (size_t)b * d.P + p;
-            const int c = is_bg(mask[gp]) ? 0 : 1;
+            uint8_t m = mask[gp];
+            if (MODE == 1 && dist && (m == GGC_PR_BGD || m == GGC_PR_FGD)) {
+                const uint8_t m1 = dist[gp] >= DINF ? GGC_PR_FGD : GGC_PR_BGD;
+                if (m1 != m) mask[gp] = m = m1;
+            }
+            const int c = is_bg(m) ? 0 : 1;
             const uint8_t* px = img + gp * 3;
             int ci = 0;
             if (MODE == 1) {   // class by class: the GMM address stays wave-uniform (scalar loads), waves are mostly one class
 #pragma unroll
                 for (int cc = 0; cc < 2; ++cc) if (c == cc) ci = gmm_which(gmm[b * 2 + cc], px);
-                comp[gp] = (uint8_t)ci;
             } else ci = comp[gp];
             unsigned int* a = s_acc + (c * NCOMP + ci) * LW * BIN_COPIES + cp;
             const unsigned int v0 = px[0], v1 = px[1], v2 = px[2];
@@ -465,41 +472,36 @@ __global__ void __launch_bounds__(256) k_beta(GcDims d, const uint8_t* __restric
     if ((threadIdx.x & 63) == 0 && s) atomicAdd(&bsum[b], s);
 }
 
-__global__ void __launch_bounds__(256) k_nweights(GcDims d, const uint8_t* __restrict__ img,
-                                                  const unsigned long long* __restrict__ bsum, int32_t* __restrict__ nw) {
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (size_t)d.B * d.P) return;
-    const int b = (int)(i / d.P), p = (int)(i % d.P);
-    const int y = p / d.W, x = p % d.W;
-    const uint8_t* im = img + (size_t)b * d.P * 3;
-    const long long bs = (long long)bsum[b];
-    double beta = 0.0;
-    if (bs > 0) beta = 1.0 / (2.0 * (double)bs / (double)(4ll * d.W * d.H - 3ll * d.W - 3ll * d.H + 2));
+// n-link between two pixels: gamma (over sqrt 2 for a diagonal link) * exp(-beta d^2), quantised.  colour_d2 is symmetric
+// in integers, so both ends of a link compute the same capacity.
+__device__ __forceinline__ double gc_beta(const GcDims& d, unsigned long long bsum) {
+    const long long bs = (long long)bsum;
+    return bs > 0 ? 1.0 / (2.0 * (double)bs / (double)(4ll * d.W * d.H - 3ll * d.W - 3ll * d.H + 2)) : 0.0;
+}
+__device__ __forceinline__ int32_t nlink_cap(double beta, bool diagonal, const uint8_t* a, const uint8_t* b) {
     const double gdiv = GAMMA / sqrt(2.0);
-    for (int k = 0; k < 4; ++k) {
-        int q; int32_t w = 0;
-        if (plane_nb(d, y, x, k, q)) {
-            const double wt = ((k & 1) ? gdiv : GAMMA) * det_exp(-beta * (double)colour_d2(im + 3 * p, im + 3 * q));
-            w = (int32_t)rint(wt * CAP_SCALE);
-        }
-        nw[((size_t)k * d.B + b) * d.P + p] = w;
-    }
+    const double wt = (diagonal ? gdiv : GAMMA) * det_exp(-beta * (double)colour_d2(a, b));
+    return (int32_t)rint(wt * CAP_SCALE);
 }
 
-// constructGCGraph: t-links cancelled against each other, clamped to +-lambda; residual arcs from the n-link planes (mf_init_pixel)
+// constructGCGraph: t-links cancelled against each other, clamped to +-lambda.  Cold: every pixel computes the capacities
+// of its 8 arcs itself (a link that leaves the image is 0) and starts from them (mf_cold_pixel); warm: an open pixel moves
+// its terminal balance by the change of its t-link difference (mf_warm_pixel), which is why tws [B][P] keeps the
+// difference of the previous build.
 __global__ void __launch_bounds__(256) k_build_graph(GcDims d, const uint8_t* __restrict__ img,
                                                      const uint8_t* __restrict__ mask, const int32_t* __restrict__ state,
-                                                     const Gmm* __restrict__ gmm, const int32_t* __restrict__ nw,
+                                                     const Gmm* __restrict__ gmm, const unsigned long long* __restrict__ bsum,
                                                      int32_t* __restrict__ rc, int32_t* __restrict__ ex,
-                                                     int32_t* __restrict__ snk, uint8_t* __restrict__ rmask, int warm) {
+                                                     int32_t* __restrict__ snk, uint8_t* __restrict__ rmask,
+                                                     int32_t* __restrict__ tws, int warm) {
     // one image per grid row: the image index is uniform, so the two GMMs (140 doubles) come through scalar loads
     const int b = blockIdx.y, p = blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= d.P || state[b]) return;
     const size_t i = (size_t)b * d.P + p;
     const uint8_t m = mask[i];
-    // Warm start, definite pixel: its t-link (+-lambda) is what it was, so the new balance tw + inflow equals the old one —
-    // and a finished solve leaves no pixel with both excess and sink capacity, so excess, sink link, capacities and arc
-    // mask are already what this kernel would write (59 % of the bench's pixels are definite background).
+    // Warm start, definite pixel: its t-link (+-lambda) is what it was, so its balance is too — and a finished solve leaves
+    // no pixel with both excess and sink capacity, so excess and sink link are already what this kernel would write (59 %
+    // of the bench's pixels are definite background).
     if (warm && (m == GGC_BGD || m == GGC_FGD)) return;
     double dv;
     if (m == GGC_BGD) dv = -LAMBDA;
@@ -513,7 +515,21 @@ __global__ void __launch_bounds__(256) k_build_graph(GcDims d, const uint8_t* __
         if (dv > LAMBDA) dv = LAMBDA;
         if (dv < -LAMBDA) dv = -LAMBDA;
     }
-    mf_init_pixel(d, b, p, (int32_t)rint(dv * CAP_SCALE), nw, rc, ex, snk, rmask, warm != 0);
+    const int32_t tw = (int32_t)rint(dv * CAP_SCALE);
+    if (warm) mf_warm_pixel(i, tw, tws[i], ex, snk);
+    else {
+        const uint8_t* im = img + (size_t)b * d.P * 3;
+        const double beta = gc_beta(d, bsum[b]);
+        const int y = p / d.W, x = p % d.W;
+        int32_t cap[8];
+#pragma unroll
+        for (int dir = 0; dir < 8; ++dir) {
+            const int q = dir_nb(d, y, x, dir);
+            cap[dir] = q >= 0 ? nlink_cap(beta, dir >= 4, im + 3 * p, im + 3 * q) : 0;
+        }
+        mf_cold_pixel(i, tw, cap, rc, ex, snk, rmask);
+    }
+    tws[i] = tw;
 }
 
 // estimateSegmentation: probable pixels take the side of the cut; foreground = cannot reach the sink
@@ -559,11 +575,11 @@ extern "C" int ggc_grabcut(ggc_ctx* ctx, ggc_stream stream, int B, int H, int W,
     Gmm* gmm = scratch_t<Gmm>(ctx, S_GC_B, (size_t)B * 2);
     unsigned long long* acc = scratch_t<unsigned long long>(ctx, S_GC_C, (size_t)B * 2 * NCOMP * ACC_W + B);
     uint8_t* comp = scratch_t<uint8_t>(ctx, S_GC_D, BP);
-    int32_t* nw = scratch_t<int32_t>(ctx, S_GC_E, BP * 4);
+    int32_t* tws = scratch_t<int32_t>(ctx, S_GC_E, BP);          // t-link differences of the last graph build
     int32_t* rc = scratch_t<int32_t>(ctx, S_GC_F, BP * 8);
     int32_t* ex = scratch_t<int32_t>(ctx, S_GC_G, BP * 3);
     uint8_t* rmask = scratch_t<uint8_t>(ctx, S_GC_L, BP);
-    if (!ctl_bytes || !gmm || !acc || !comp || !nw || !rc || !ex || !rmask) return GGC_E_OOM;
+    if (!ctl_bytes || !gmm || !acc || !comp || !tws || !rc || !ex || !rmask) return GGC_E_OOM;
     int32_t* snk = ex + BP;
     int32_t* dist = ex + 2 * BP;
     unsigned long long* bsum = acc + (size_t)B * 2 * NCOMP * ACC_W;
@@ -598,31 +614,33 @@ extern "C" int ggc_grabcut(ggc_ctx* ctx, ggc_stream stream, int B, int H, int W,
             hipLaunchKernelGGL(k_km_pick, dim3(B), dim3(128), 0, st, d, k, (uint64_t)seed, image, mask, state, d2, chunk_cnt, chunk_d2, km);
         }
         for (int it = 0; it < 10; ++it) {
-            hipLaunchKernelGGL(k_km_assign, dim3(cdiv(d.P, 256 * BIN_PX), B), dim3(256), 0, st, d, image, mask, state, km, comp, acc);
+            hipLaunchKernelGGL(k_km_assign, dim3(cdiv(d.P, 256 * BIN_PX), B), dim3(256), 0, st, d, image, mask, state, km, comp, acc, it == 9 ? 1 : 0);
             hipLaunchKernelGGL(k_km_update, dim3(cdiv(B * 2 * NCOMP, 256)), dim3(256), 0, st, B, state, km, acc, it < 9 ? 1 : 0);
         }
-        hipLaunchKernelGGL((k_gmm_accum<0>), dim3(cdiv(d.P, 256 * BIN_PX), B), dim3(256), 0, st, d, image, mask, state, gmm, comp, acc);
+        hipLaunchKernelGGL((k_gmm_accum<0>), dim3(cdiv(d.P, 256 * BIN_PX), B), dim3(256), 0, st, d, image, mask, state, gmm, comp, (const int32_t*)nullptr, acc);
         hipLaunchKernelGGL(k_gmm_learn, dim3(cdiv(B * 2, 64)), dim3(64), 0, st, B, state, acc, gmm);
     }
     GGC_LAUNCH_CHECK(ctx);
 
     if (n_iter > 0) {
         hipLaunchKernelGGL(k_beta, red, dim3(256), 0, st, d, image, bsum);
-        hipLaunchKernelGGL(k_nweights, dim3(cdiv(BP, 256)), dim3(256), 0, st, d, image, bsum, nw);
         GGC_LAUNCH_CHECK(ctx);
+        int n_open = -1;                // counted by the first solve
         for (int it = 0; it < n_iter; ++it) {
             const bool warm = knobs().mf_warm && it > 0;
             {
                 ProfScope prof(ctx, st, "grabcut_gmm");
-                hipLaunchKernelGGL((k_gmm_accum<1>), dim3(cdiv(d.P, 256 * BIN_PX), B), dim3(256), 0, st, d, image, mask, state, gmm, comp, acc);
+                hipLaunchKernelGGL((k_gmm_accum<1>), dim3(cdiv(d.P, 256 * BIN_PX), B), dim3(256), 0, st, d, image, mask, state, gmm, comp,
+                                   (const int32_t*)(it > 0 ? dist : nullptr), acc);   // it > 0: relabels from the previous cut first
                 hipLaunchKernelGGL(k_gmm_learn, dim3(cdiv(B * 2, 64)), dim3(64), 0, st, B, state, acc, gmm);
-                hipLaunchKernelGGL(k_build_graph, dim3(cdiv(d.P, 256), B), dim3(256), 0, st, d, image, mask, state, gmm, nw, rc, ex, snk, rmask, warm ? 1 : 0);
+                hipLaunchKernelGGL(k_build_graph, dim3(cdiv(d.P, 256), B), dim3(256), 0, st, d, image, mask, state, gmm, bsum, rc, ex, snk, rmask, tws, warm ? 1 : 0);
             }
             GGC_LAUNCH_CHECK(ctx);
             // launches over work lists for the dense phases, one asynchronous launch for each sparse phase
-            const int rcode = maxflow(ctx, st, d, state, rc, ex, snk, dist, rmask, mf, !warm);
+            const int rcode = maxflow(ctx, st, d, state, rc, ex, snk, dist, rmask, mf, !warm, n_open);
             if (rcode) return rcode;
-            hipLaunchKernelGGL(k_gc_relabel, dim3(cdiv(BP, 256)), dim3(256), 0, st, d, state, dist, mask);
+            // estimateSegmentation: the next iteration's k_gmm_accum<1> applies it; the last one has no successor
+            if (it == n_iter - 1) hipLaunchKernelGGL(k_gc_relabel, dim3(cdiv(BP, 256)), dim3(256), 0, st, d, state, dist, mask);
             GGC_LAUNCH_CHECK(ctx);
         }
     }

@@ -1,7 +1,7 @@
 // ggc_gridflow.hip — the max-flow of ggc_maxflow.hip on a caller's network (ggc_grid_maxflow, include/ggc.h).
 //
 // A test hook that shares the production path: k_gf_build runs the per-pixel graph set-up of ggc_grabcut
-// (mf_init_pixel, ggc_gc.h) on the given t-link differences, then maxflow() solves exactly as in a GrabCut iteration:
+// (mf_cold_pixel / mf_warm_pixel, ggc_gc.h) on the given t-link differences, then maxflow() solves exactly as in a GrabCut iteration:
 // step 0 cold, later steps warm under GGC_MF_WARM.  The networks a test builds (long corridors, walls crossed only at
 // tile corners, cuts on tile borders, capacities at the stated bounds) are what GMM likelihoods of natural images
 // never produce.
@@ -39,12 +39,17 @@ __global__ void __launch_bounds__(256) k_gf_check(GcDims d, int n_steps, const i
     if ((threadIdx.x & 63) == 0 && bad) atomicOr(err, bad);
 }
 
-__global__ void __launch_bounds__(256) k_gf_build(GcDims d, const int32_t* __restrict__ tw, const int32_t* __restrict__ nw,
-                                                  int32_t* __restrict__ rc, int32_t* __restrict__ ex, int32_t* __restrict__ snk,
-                                                  uint8_t* __restrict__ rmask, int warm) {
+// tw_old: the previous step's t-link differences for a warm step (the caller's own plane), null for a cold one
+__global__ void __launch_bounds__(256) k_gf_build(GcDims d, const int32_t* __restrict__ tw, const int32_t* __restrict__ tw_old,
+                                                  const int32_t* __restrict__ nw, int32_t* __restrict__ rc, int32_t* __restrict__ ex,
+                                                  int32_t* __restrict__ snk, uint8_t* __restrict__ rmask) {
     const int b = blockIdx.y, p = blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= d.P) return;
-    mf_init_pixel(d, b, p, tw[(size_t)b * d.P + p], nw, rc, ex, snk, rmask, warm != 0);
+    const size_t i = (size_t)b * d.P + p;
+    if (tw_old) { mf_warm_pixel(i, tw[i], tw_old[i], ex, snk); return; }
+    int32_t cap[8];
+    mf_plane_caps(d, b, p, nw, cap);
+    mf_cold_pixel(i, tw[i], cap, rc, ex, snk, rmask);
 }
 
 __global__ void __launch_bounds__(256) k_gf_side(size_t n, const int32_t* __restrict__ dist, uint8_t* __restrict__ side) {
@@ -104,11 +109,13 @@ extern "C" int ggc_grid_maxflow(ggc_ctx* ctx, ggc_stream stream, int B, int H, i
     GGC_REQUIRE(ctx, !(herr[0] & 2), GGC_E_INVALID_ARG, "an in-image n-link is negative");
     GGC_REQUIRE(ctx, !(herr[0] & 4), GGC_E_INVALID_ARG, "an in-image n-link exceeds 2^24");
 
+    int n_open = -1;                    // every image is open in every step: counted by the first solve only
     for (int s = 0; s < n_steps; ++s) {
         const bool warm = knobs().mf_warm && s > 0;
-        hipLaunchKernelGGL(k_gf_build, dim3(cdiv(d.P, 256), B), dim3(256), 0, st, d, tw + (size_t)s * BP, nw, rc, ex, snk, rmask, warm ? 1 : 0);
+        const int32_t* tw_s = tw + (size_t)s * BP;
+        hipLaunchKernelGGL(k_gf_build, dim3(cdiv(d.P, 256), B), dim3(256), 0, st, d, tw_s, warm ? tw_s - BP : nullptr, nw, rc, ex, snk, rmask);
         GGC_LAUNCH_CHECK(ctx);
-        if ((rcode = maxflow(ctx, st, d, state, rc, ex, snk, dist, rmask, mf, !warm))) return rcode;
+        if ((rcode = maxflow(ctx, st, d, state, rc, ex, snk, dist, rmask, mf, !warm, n_open))) return rcode;
         hipLaunchKernelGGL(k_gf_side, dim3(cdiv(BP, 256)), dim3(256), 0, st, BP, dist, source_side + (size_t)s * BP);
         GGC_LAUNCH_CHECK(ctx);
         if ((rcode = read_i32(ctx, st, err + 1, 1, herr))) return rcode;

@@ -560,15 +560,15 @@ struct MfTrace {
 } // namespace
 
 int maxflow(ggc_ctx* ctx, hipStream_t st, const GcDims& d, const int32_t* state, int32_t* rc, int32_t* ex,
-            int32_t* snk, int32_t* dist, uint8_t* rmask, const MfControl& ctl, bool masks_exact) {
+            int32_t* snk, int32_t* dist, uint8_t* rmask, const MfControl& ctl, bool masks_exact, int& n_open) {
     const Knobs& kn = knobs();
     const MfTiles tl{cdiv(d.W, RT), cdiv(d.H, RT), cdiv(d.W, PT_W), cdiv(d.H, PT_H)};
     MfSolve s{ctx, st, d, tl, (size_t)tl.rt_x * tl.rt_y * d.B, (size_t)tl.pt_x * tl.pt_y * d.B, rc, ex, snk, dist, rmask,
               ctl, ctl.cnt, ctl.cnt + 1, ctl.cnt + 4, {}, nullptr};
     GGC_REQUIRE(ctx, std::max(s.n_rt, s.n_pt) < (1u << 24), GGC_E_UNSUPPORTED, "batch has more max-flow tiles than a queue entry addresses");
     if (!carve_scratch(ctx, S_GC_M, [&](Carve& c) { s.w.layout(c, s.n_rt, s.n_pt); })) return GGC_E_OOM;
-    // k_build_graph writes exact masks for every pixel on a cold start; a warm start leaves the definite pixels alone, so
-    // their tiles keep their dirty marks
+    // k_build_graph writes exact masks for every pixel on a cold start; a warm start leaves capacities and masks alone, so
+    // the tiles keep their dirty marks
     if (masks_exact) GGC_HIP(ctx, hipMemsetAsync(s.w.dirty, 0, sizeof(int32_t) * s.n_pt, st));
     if (kn.mf_trace) {
         s.prof = s.w.prof;
@@ -579,9 +579,12 @@ int maxflow(ggc_ctx* ctx, hipStream_t st, const GcDims& d, const int32_t* state,
     hipLaunchKernelGGL(k_open_init, dim3(cdiv(d.B, 256)), dim3(256), 0, st, d.B, state, list_cur, s.n_open, s.rl_cnt);
     GGC_LAUNCH_CHECK(ctx);
     std::vector<int32_t> host;
-    int rcode = read_i32(ctx, st, s.n_open, 1, host);
-    if (rcode) return rcode;
-    int n_cur = host[0];
+    int rcode = GGC_OK;
+    if (n_open < 0) {                   // the first solve of a call: the later ones know the count and do not wait here
+        if ((rcode = read_i32(ctx, st, s.n_open, 1, host))) return rcode;
+        n_open = host[0];
+    }
+    int n_cur = n_open;
     if (n_cur == 0) return GGC_OK;
     MfTrace trace;
     const int max_rounds = 4096;
