@@ -38,6 +38,7 @@ enum Slot : int {
     S_STROKES,
     S_POLYGONS,
     S_SCISSORS,
+    S_OUTLINE, S_OUTLINE_LIST,
     S_COUNT
 };
 

@@ -27,7 +27,8 @@ from .pipeline import (GCNGrabCutPipeline, ClosedFormMatte, ForegroundColours, F
                        closed_form_matte_full, lift_trimap, trimap_matte, trimap_matte_full,
                        trimap_matte_warm, upsample_mask, FullCut, cut_mask_full, lift_labels,
                        GeodesicHints, geodesic_hints, paint_strokes, stroke_pixels, paint_polygons, polygon_mask,
-                       Scissors, trace_boundary)
+                       Scissors, trace_boundary,
+                       Outline, mask_outlines, mask_outlines_batch, outlines_svg_path, outlines_to_lassos)
 from .synthetic import synthetic_image, synthetic_batch
 from .losses import FocalLoss, LabelSmoothingCE, TrimapLoss
 from .trainer import Trainer, TrainConfig
@@ -48,6 +49,7 @@ __all__ = [
     "pack_strokes", "paint_strokes", "stroke_pixels",
     "pack_polygons", "paint_polygons", "polygon_mask",
     "pack_paths", "Scissors", "trace_boundary",
+    "Outline", "mask_outlines", "mask_outlines_batch", "outlines_svg_path", "outlines_to_lassos",
     "ResGCNNet", "GCNTrimapNet", "GATTrimapNet", "build_model", "probs_to_node_trimap", "project_to_pixels",
     "Data", "Batch", "synthetic_image", "synthetic_batch",
     "FocalLoss", "LabelSmoothingCE", "TrimapLoss", "Trainer", "TrainConfig",

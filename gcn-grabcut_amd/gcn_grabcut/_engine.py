@@ -320,6 +320,40 @@ class Engine:
             self.ctx.call("ggc_trace_paths", *args, verts.data_ptr(), n)
         return verts, vert_ptr
 
+    def mask_outlines(self, masks, connectivity=8, capacity=None):
+        """Mask outlines (ggc_mask_outlines, include/ggc.h K1): masks (B,H,W) uint8 on the device, any nonzero byte
+        foreground -> (verts (V,2) int32 = row, col corners; loop_ptr (Q+1,); loop_info (Q,3) = area, outer, perimeter;
+        image_ptr (B+1,); image_vert_ptr (B+1,)), all int32 on the device, verts and loop_ptr in ggc_apply_polygons'
+        packing.  capacity None: one counting call, then one filling call of exactly the counted size.  capacity =
+        (loops, vertices) is a guess: one call fills buffers of that size and is repeated only when the guess was too
+        small (the two image arrays are written either way)."""
+        b, h, w = masks.shape
+        image_ptr = torch.zeros(b + 1, dtype=torch.int32, device=self.device)
+        image_vert_ptr = torch.zeros(b + 1, dtype=torch.int32, device=self.device)
+        if b == 0:
+            return (self.empty(0, 2, dtype=torch.int32), torch.zeros(1, dtype=torch.int32, device=self.device),
+                    self.empty(0, 3, dtype=torch.int32), image_ptr, image_vert_ptr)
+        args = (self._stream(), b, h, w, masks.data_ptr(), int(connectivity), image_ptr.data_ptr(), image_vert_ptr.data_ptr())
+
+        def fill(q, v):
+            loop_ptr = torch.zeros(q + 1, dtype=torch.int32, device=self.device)
+            loop_info = self.empty(max(q, 1), 3, dtype=torch.int32)         # an empty tensor has no address: NULL means "count only"
+            verts = self.empty(max(v, 1), 2, dtype=torch.int32)
+            self.ctx.call("ggc_mask_outlines", *args, loop_ptr.data_ptr(), loop_info.data_ptr(), verts.data_ptr(), q, v)
+            n_q, n_v = int(image_ptr[-1].item()), int(image_vert_ptr[-1].item())
+            return verts[:n_v], loop_ptr[:n_q + 1], loop_info[:n_q], image_ptr, image_vert_ptr
+
+        if capacity is not None:
+            q, v = (max(int(c), 0) for c in capacity)
+            try:
+                return fill(q, v)
+            except _native.GGCError:
+                if int(image_ptr[-1].item()) <= q and int(image_vert_ptr[-1].item()) <= v:      # refused for another reason
+                    raise
+        else:
+            self.ctx.call("ggc_mask_outlines", *args, None, None, None, 0, 0)
+        return fill(int(image_ptr[-1].item()), int(image_vert_ptr[-1].item()))
+
     def next_click(self, pred, gt) -> torch.Tensor:
         """The next simulated click of the NoC protocol per image (ggc_next_click): pred, gt (B,H,W) uint8, nonzero =
         foreground -> (B,4) int32 on the device = row, col, label (1 = fg, 0 = bg), d2; (-1,-1,-1,0) where pred == gt."""

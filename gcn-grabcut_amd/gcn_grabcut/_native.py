@@ -76,6 +76,7 @@ SIGNATURES = {
     "ggc_grabcut": [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _u64, _vp],
     "ggc_grid_maxflow": [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp],
     "ggc_clean_mask": [_vp, _vp, _i, _i, _i, _vp, _f, _i, _vp],
+    "ggc_mask_outlines": [_vp, _vp, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i64, _i64],
     "ggc_compose_outputs": [_vp, _vp, _i, _i, _i, _vp, _vp, _f, _i, _i, _i, _vp, _vp],
     "ggc_alpha_matte": [_vp, _vp, _i, _i, _i, _vp, _vp, _i, _f, _vp, _vp],
     "ggc_upsample_matte": [_vp, _vp, _i, _i, _i, _vp, _vp, _i, _i, _vp, _i, _f, _vp, _vp, _vp],

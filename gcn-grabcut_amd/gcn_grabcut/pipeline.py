@@ -96,6 +96,12 @@ class SegmentationResult:
             raise ValueError("this result carries no matte: segment with matte=True or a ClosedFormMatte")
         return evaluate_matte(self.alpha, gt_alpha, region)
 
+    def outlines(self, connectivity: int = 8, full: bool = False) -> "list[Outline]":
+        """The exact vector outlines of binary_mask, or of full.binary_mask with full=True (additive; mask_outlines)."""
+        if full and self.full is None:
+            raise ValueError("this result carries no full-resolution outputs: segment with full_image=...")
+        return mask_outlines(self.full.binary_mask if full else self.binary_mask, connectivity)
+
 
 def guided_filter(guide: np.ndarray, src: np.ndarray, radius: int = 8, eps: float = 1e-3, device="cuda") -> np.ndarray:
     """Edge-preserving filter of `src` under `guide` (He et al.) — reference pipeline.py:71-100."""
@@ -594,6 +600,72 @@ def polygon_mask(shape, polygon, device="cuda") -> np.ndarray:
     if h < 1 or w < 1:
         raise ValueError(f"polygon_mask: bad shape {(h, w)}")
     return paint_polygons(np.zeros((h, w), np.uint8), [polygon], device=device)
+
+
+@dataclass(frozen=True)
+class Outline:
+    """One loop of a mask's outline (ggc_mask_outlines, include/ggc.h K1).  vertices: (n, 2) int32
+    corners (row, col) of the corner lattice, pixel (y, x) being the square between corners (y, x) and (y+1, x+1), in loop
+    order from the loop's smallest corner, the foreground on the right; area: the signed pixel count inside, negative for
+    a hole; perimeter: the loop's length in unit steps; outer: the index, in the image's list, of the outer loop of this
+    loop's component (an outer loop names itself)."""
+    vertices: np.ndarray
+    area: int
+    perimeter: int
+    outer: int
+
+    @property
+    def hole(self) -> bool:
+        return self.area < 0
+
+
+def _check_connectivity(connectivity) -> int:
+    if connectivity not in (4, 8):
+        raise ValueError(f"connectivity must be 4 or 8, got {connectivity!r}")
+    return int(connectivity)
+
+
+def mask_outlines_batch(masks, connectivity: int = 8, device="cuda") -> "list[list[Outline]]":
+    """The outlines of every mask of a batch (additive; one ggc_mask_outlines call).  masks: (B, H, W), or a sequence of
+    equally sized (H, W) masks; any nonzero value is foreground.  -> per image its loops, outer loops and holes, ordered
+    by their start (the loop's smallest corner, in raster order)."""
+    from ._engine import get_engine
+    conn = _check_connectivity(connectivity)
+    m = np.asarray(masks)
+    if m.ndim != 3:
+        raise ValueError(f"mask_outlines_batch: masks must be (B, H, W), got {m.shape}")
+    if m.shape[0] == 0:
+        return []
+    if m.shape[1] < 1 or m.shape[2] < 1:
+        raise ValueError(f"mask_outlines_batch: empty masks {m.shape}")
+    eng = get_engine(device)
+    verts, loop_ptr, info, image_ptr, _ = (t.cpu().numpy() for t in eng.mask_outlines(eng.to_device((m != 0).astype(np.uint8)), conn))
+    return [[Outline(verts[loop_ptr[q]:loop_ptr[q + 1]].copy(), int(info[q, 0]), int(info[q, 2]), int(info[q, 1]))
+             for q in range(int(image_ptr[b]), int(image_ptr[b + 1]))] for b in range(m.shape[0])]
+
+
+def mask_outlines(mask, connectivity: int = 8, device="cuda") -> "list[Outline]":
+    """The exact vector outlines of one (H, W) mask, any nonzero value foreground (additive; ggc_mask_outlines): crack
+    following on the corner lattice.  connectivity 8 joins diagonal foreground pixels into one loop (the components of
+    clean_mask), 4 separates them."""
+    m = np.asarray(mask)
+    if m.ndim != 2:
+        raise ValueError(f"mask_outlines: mask must be (H, W), got {m.shape}")
+    return mask_outlines_batch(m[None], connectivity, device)[0]
+
+
+def outlines_svg_path(outlines) -> str:
+    """The loops as one SVG path for fill-rule="evenodd": one `M x y L x y ... Z` sub-path per loop, x = col, y = row."""
+    parts = []
+    for o in outlines:
+        v = np.asarray(o.vertices)
+        parts.append("M " + " L ".join(f"{int(c)} {int(r)}" for r, c in v) + " Z")
+    return " ".join(parts)
+
+
+def outlines_to_lassos(outlines) -> "list[np.ndarray]":
+    """The outer loops as (row, col) polygons that lasso= / fg_polygons= take (holes are left out)."""
+    return [np.asarray(o.vertices, np.int32).copy() for o in outlines if not o.hole]
 
 
 @dataclass(frozen=True)

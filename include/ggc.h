@@ -51,7 +51,10 @@
 extern "C" {
 #endif
 
-#define GGC_VERSION 407 /* 0.4.7: ggc_trace_paths (intelligent scissors: a few boundary anchors joined by the cheapest path along image
+#define GGC_VERSION 408 /* 0.4.8: ggc_mask_outlines (the exact vector contours of a mask: crack-following loops on the corner lattice, as
+                                  vertices in ggc_apply_polygons' packing, with area, perimeter and outer loop; additive, no existing
+                                  entry changes);
+                           0.4.7: ggc_trace_paths (intelligent scissors: a few boundary anchors joined by the cheapest path along image
                                   edges, as vertices in ggc_apply_polygons' packing; additive, no existing entry changes);
                            0.4.6: ggc_apply_polygons (lassos and filled polygons as hard constraints: one exact integer point-in-polygon
                                   rule, even-odd with a closed boundary; additive, no existing entry changes);
@@ -585,6 +588,55 @@ int ggc_next_click(ggc_ctx* ctx, ggc_stream stream, int B, int H, int W,
 int ggc_clean_mask(ggc_ctx* ctx, ggc_stream stream, int B, int H, int W,
                    const uint8_t* mask_in, float min_area_ratio, int keep_largest,
                    uint8_t* mask_out);
+
+/* K1 — mask outlines: the exact vector contours of a mask, traced on the device.  Additive; integer only.
+ *   mask [dev] u8 [B,H,W]: any nonzero byte is foreground, everything outside the image is background.
+ * CORNER LATTICE.  The corners of an H x W image are the points (r, c), 0 <= r <= H, 0 <= c <= W; pixel (y, x) is the unit
+ * square between corners (y, x) and (y+1, x+1).
+ * CRACKS.  A crack is a directed unit step between two corners with a foreground pixel on its right and a background pixel
+ * on its left.  Row grows downwards, so a step east has "below" on its right.  Directions: 0 = E (c+1), 1 = S (r+1), 2 = W,
+ * 3 = N.  A crack leaves (r, c) in direction d iff
+ *   E: pixel (r, c) fg and (r-1, c) bg        S: (r, c-1) fg and (r, c) bg
+ *   W: (r-1, c-1) fg and (r, c-1) bg          N: (r-1, c) fg and (r-1, c-1) bg.
+ * Its key is ((r (W+1) + c) 4 + d) of its tail.  An image has at most 2HW + H + W cracks, one per unit edge
+ * (the checkerboard has all but the border edges of its clear pixels).
+ * SUCCESSOR.  The successor of a crack that arrives at corner v in direction d is the first crack that exists among those
+ * leaving v: connectivity 8 tries left (d+3)&3, straight d, right (d+1)&3, in that order; connectivity 4 tries right,
+ * straight, left.  The orders differ only at saddle corners (two diagonal foreground pixels in the 2x2 block): 8 joins the
+ * two pixels into one loop, 4 separates them.  Everywhere else exactly one candidate exists; a U-turn never does.
+ * LOOPS.  Successor is a permutation of the cracks; its cycles are the loops.  A loop STARTS at its crack of smallest key;
+ * that crack's tail is the loop's lexicographically smallest corner, the loop visits it once and turns there, no other loop
+ * starts at it, and the start points E for an outer loop and S for a hole.  The VERTICES of a loop are the tails of those of
+ * its cracks whose predecessor has another direction, in loop order from the start: an even number, at least 4.
+ * ORDER AND RECORDS.  An image's loops are ordered by start key.  Per loop:
+ *   area       half the shoelace sum  sum c_i r_(i+1) - c_(i+1) r_i  over its vertices, an exact integer: positive for an outer
+ *              loop (clockwise on screen), negative for a hole.  The areas of an image sum to its foreground pixel count.
+ *   perimeter  the loop's crack count.
+ *   outer      the index, within the image, of the outer loop of the loop's component: the component, under `connectivity`,
+ *              of the foreground pixel right of the start crack.  An outer loop names itself.
+ * An image has as many outer loops as foreground components under `connectivity`, and as many holes as background
+ * components under the dual connectivity that do not reach the border.  XOR-ing the even-odd fills of an image's loops gives
+ * the mask back: double every coordinate, fill on a (2H+1) x (2W+1) grid by H3's rule, read the odd positions.
+ *   image_ptr_out      [dev] i32 [B+1], always written: image b owns loops image_ptr_out[b] .. image_ptr_out[b+1)
+ *   image_vert_ptr_out [dev] i32 [B+1], always written: ... and rows image_vert_ptr_out[b] .. [b+1) of verts_out
+ *   loop_ptr_out       [dev] i32 [loop_capacity+1] or NULL: loop q owns rows loop_ptr_out[q] .. [q+1) of verts_out
+ *   loop_info_out      [dev] i32 [loop_capacity,3] = area, outer, perimeter; or NULL
+ *   verts_out          [dev] i32 [vert_capacity,2] = (row, col) corners; or NULL
+ * The three fill arrays are NULL together (count only: read the totals at image_ptr_out[B] and image_vert_ptr_out[B], the
+ * pattern of ggc_stroke_pixels) or all given; loop_ptr_out and verts_out are exactly ggc_apply_polygons' poly_ptr and verts.
+ * Every image's result equals that of its single-image call, bit for bit.  B == 0 is a no-op.
+ * Refused before any launch: H or W outside 1..65535 or B outside 0..65535 (GGC_E_SHAPE); (H+1)(W+1) > 2^28, so that keys
+ * and areas fit int32, a connectivity other than 4 or 8, a NULL mask or image array, only some of the fill arrays, a
+ * negative capacity (GGC_E_INVALID_ARG).  Refused after the counting pass: a capacity below the totals
+ * (GGC_E_INVALID_ARG), with nothing written to the three fill arrays.
+ * SYNCHRONISES the stream: the crack, loop and vertex totals are read back (three small reads per image group).  Scratch
+ * from the context: 0.6 bytes per corner (a bitmap over the crack keys and a prefix per 64 corners), 4 bytes per pixel for
+ * the component labelling, and 57 bytes per crack (key, successor, two ranking states, loop index).  A batch of more than
+ * 2^26 corners is worked through in image groups of at most that many, with identical results; a filling call then counts
+ * every group twice. */
+int ggc_mask_outlines(ggc_ctx* ctx, ggc_stream stream, int B, int H, int W, const uint8_t* mask, int connectivity,
+                      int32_t* image_ptr_out, int32_t* image_vert_ptr_out, int32_t* loop_ptr_out, int32_t* loop_info_out,
+                      int32_t* verts_out, int64_t loop_capacity, int64_t vert_capacity);
 
 /* O0 — replaces GrabCut.overlay_mask / crop_foreground (grabcut.py:180-195).
  *   overlay [dev] u8 [B,H,W,3]   rgba [dev] u8 [B,H,W,4]   (either may be NULL) */

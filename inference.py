@@ -20,6 +20,7 @@ Images are decoded / written with Pillow (OpenCV is not a dependency of this bui
 batches of equally sized images so that the whole batch stays resident in HBM.
 """
 import argparse
+import json
 import time
 from pathlib import Path
 
@@ -50,8 +51,12 @@ def build_parser() -> argparse.ArgumentParser:
                         help="Drop mask components smaller than this fraction of the image")
     parser.add_argument("--keep-largest", action="store_true", help="Keep only the largest connected component")
     parser.add_argument("--save", nargs="+", default=["mask", "overlay"],
-                        choices=["mask", "overlay", "rgba", "trimap", "alpha", "cutout"],
+                        choices=["mask", "overlay", "rgba", "trimap", "alpha", "cutout", "outlines"],
                         help="Which outputs to write (alpha / cutout: the soft matte and the BGRA cut-out with it)")
+    # additive: the mask's exact vector outlines (ggc_mask_outlines), written as <prefix>_outlines.json by --save outlines
+    parser.add_argument("--outline-connectivity", type=int, choices=[4, 8], default=8,
+                        help="--save outlines: 8 joins diagonal foreground pixels into one loop (as the mask clean-up "
+                             "labels components), 4 separates them")
     parser.add_argument("--batch", type=int, default=64, help="Images per device batch (additive flag)")
     # additive: user clicks as hard constraints (ggc_apply_hints), single-image runs only
     parser.add_argument("--fg-point", action="append", type=_point, default=[], metavar="ROW,COL",
@@ -166,6 +171,16 @@ def _polygon(text: str):
     if len(pts) < 3:
         raise argparse.ArgumentTypeError(f"expected 'ROW,COL ROW,COL ROW,COL ...' (at least three vertices), got '{text}'")
     return pts
+
+
+def outlines_document(shape, outlines, connectivity: int) -> dict:
+    """What --save outlines writes: the loops of a mask of `shape` on its corner lattice, (row, col) vertices with area,
+    perimeter and outer loop each, and all of them as one SVG path (x = col, y = row) for fill-rule="evenodd"."""
+    from src.gcn_grabcut import outlines_svg_path
+    return {"height": int(shape[0]), "width": int(shape[1]), "connectivity": int(connectivity),
+            "loops": [{"vertices": [[int(r), int(c)] for r, c in o.vertices], "area": int(o.area),
+                       "perimeter": int(o.perimeter), "outer": int(o.outer)} for o in outlines],
+            "svg_path": outlines_svg_path(outlines)}
 
 
 def scale_points(points, orig_hw, new_hw):
@@ -395,6 +410,10 @@ def main() -> None:
                     _write_png(f"{stem}_alpha.png", alpha_to_u8(out.alpha))
                 if "cutout" in args.save:
                     _write_png(f"{stem}_cutout.png", out.rgba_soft if foreground is None else result.rgba_clean)
+                if "outlines" in args.save:                 # on the grid of the mask file written above
+                    loops = result.outlines(args.outline_connectivity, full=result.full is not None)
+                    with open(f"{stem}_outlines.json", "w") as f:
+                        json.dump(outlines_document(out.binary_mask.shape, loops, args.outline_connectivity), f)
                 t = result.timing
                 print(f"[{n_done}/{len(paths)}] {path.name}  fg={result.binary_mask.mean():.1%}  "
                       f"graph={t.get('graph_build', 0):.4f}s gcn={t.get('gcn_inference', 0):.4f}s "
