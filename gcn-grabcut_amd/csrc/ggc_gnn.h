@@ -1,10 +1,11 @@
 // ggc_gnn.h — shared host plumbing of the three trimap networks (ggc_resgcn.hip: ResGCNNet, ggc_gcnnet.hip:
-// GCNTrimapNet, ggc_gat.hip: GATTrimapNet): the weight registry, the host-side weight layouts and the launchers one
-// network's translation unit provides to another.  The build is not relocatable device code, so a kernel can only be
-// launched from the file that defines it: the launchers are declared here and instantiated there.
+// GCNTrimapNet, ggc_gat.hip: GATTrimapNet): the weight registry, the host-side weight layouts and the launchers of the
+// kernels more than one network uses (ggc_csr.hip: graph structure, ggc_gnn_dense.hip: MFMA GEMM and per-graph readout,
+// ggc_gnn_gather.hip: the CSR gather; ggc_gcnnet.hip: the edge gate of the other two).  The build is not relocatable
+// device code, so a kernel can only be launched from the file that defines it: the launchers are declared here and
+// explicitly instantiated there, one entry per user.
 #pragma once
 #include "ggc_internal.h"
-#include <type_traits>
 
 namespace ggc {
 
@@ -165,15 +166,9 @@ inline int begin_forward(ggc_ctx* ctx, const NetSpec& s, int G, int N, int E, co
     return prepare_weights(ctx, s);
 }
 
-// f(std::integral_constant<int, D>) for the first of the widths Ws that equals D; false if none does.
-template <int... Ws, typename F>
-bool with_width(int D, int& rc, F&& f) {
-    return ((D == Ws && (rc = f(std::integral_constant<int, Ws>{}), true)) || ...);
-}
-
 // ------------------------------------------------- launchers shared across files
 
-// out[N,D] = op(A)[N,D] @ W^T on f32 MFMA (k_gemm, ggc_resgcn.hip); MODE 3 and 4 are instantiated for the other networks.
+// out[N,D] = op(A)[N,D] @ W^T on f32 MFMA (k_gemm, ggc_gnn_dense.hip)
 //   MODE 0: A = LayerNorm(A1); store                                   (GCN XW)
 //   MODE 1: A1 @ W1^T + A2 @ W2^T + bias -> LayerNorm -> GELU          (SAGE)
 //   MODE 2: A = LayerNorm(A1 * gvec[batch]); + bias -> GELU -> head -> softmax
@@ -196,19 +191,28 @@ int launch_gemm(ggc_ctx* ctx, hipStream_t st, int N, const GemmArgs& a);
 // The forward pass hands over the batch structure (G graphs, node_ptr) and the packed column words built by
 // build_agg_pack for the slice width agg_graph_slice chose; without them (ggc_gcn_aggregate) the direct gather runs.
 struct AggGraphs { int G = 0, sw = 0; const int32_t* node_ptr = nullptr; const int32_t* pack = nullptr; };
-// GCNConv (MODE 0) / SAGE-mean (MODE 1) gather over the destination CSR (ggc_resgcn.hip)
+int build_agg_pack(ggc_ctx* ctx, hipStream_t st, int N, int G, const int32_t* node_ptr, const int32_t* batch,
+                   const int32_t* row_ptr, const int32_t* col, AggGraphs& ag);
+// GCNConv (MODE 0) / SAGE-mean (MODE 1) gather over the destination CSR (ggc_gnn_gather.hip)
 template <int D, int MODE>
 int launch_aggregate(ggc_ctx* ctx, hipStream_t st, int N, const float* xw, const int32_t* row_ptr, const int32_t* col,
                      const float* dis, const float* bias, const float* gate, const float* h, float* out,
                      const AggGraphs& ag = AggGraphs{});
+// Lane layout of a D-wide row in the direct gather (k_aggregate) and in k_jk: LPR lanes x float4 cover the row, a wave
+// handles RPW rows, a block of 4 waves RPB.
+template <int D> struct AggCfg {
+    static constexpr int LPR = (D <= 32) ? 8 : (D <= 64) ? 16 : (D <= 128) ? 32 : 64;    // D > 128: a wave per row
+    static constexpr int RPW = 64 / LPR;
+    static constexpr int RPB = 4 * RPW;
+};
 
-// per-graph softmax readout and compress/expand MLP (k_graph_ctx, ggc_resgcn.hip)
+// per-graph softmax readout and compress/expand MLP (k_graph_ctx, ggc_gnn_dense.hip)
 struct CtxW { const float *wcT /*[D][D/2]*/, *bc, *weT /*[D/2][D]*/, *be; };
 template <int D>
 int launch_graph_ctx(ggc_ctx* ctx, hipStream_t st, int G, const int32_t* node_ptr, const float* score, const float* hjk,
                      const CtxW& w, float* gvec);
 
-// Graph structure of one forward, in the context's scratch (ggc_resgcn.hip): the destination CSR of the edge list and dis
+// Graph structure of one forward, in the context's scratch (ggc_csr.hip): the destination CSR of the edge list and dis
 // (build_csr); with node_ptr, the graph of every node (batch); with_dst, the destination of every CSR position (dst).
 struct Csr { int32_t *row_ptr, *col, *eid, *batch, *dst; float* dis; };
 int prepare_csr(ggc_ctx* ctx, hipStream_t st, int G, int N, int E, const int32_t* edge_src, const int32_t* edge_dst,

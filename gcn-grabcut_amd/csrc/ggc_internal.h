@@ -7,6 +7,7 @@
 #include <cstring>
 #include <map>
 #include <string>
+#include <type_traits>
 #include <vector>
 #include "../../include/ggc.h"
 #include "../../include/ggc_fmath.h"
@@ -125,7 +126,7 @@ int read_offsets(ggc_ctx* ctx, hipStream_t st, const int32_t* dev, int n, const 
 int check_offsets(ggc_ctx* ctx, const int32_t* off, int n, const char* name, const char* unit, int min_step);
 // Returns nullptr (and sets error) on failure. Content is NOT preserved on growth.
 void* scratch(ggc_ctx* ctx, int slot, size_t bytes);
-// Destination CSR of an edge list, stable in edge order (ggc_resgcn.hip): row_ptr [N+1], col = src[eid] [E], eid [E],
+// Destination CSR of an edge list, stable in edge order (ggc_csr.hip): row_ptr [N+1], col = src[eid] [E], eid [E],
 // dis = (1+indeg)^-1/2 [N] (may be NULL).  cursor: N+1 words of scratch.  Swapping src and dst gives the source CSR.
 int build_csr(ggc_ctx* ctx, hipStream_t st, int N, int E, const int32_t* src, const int32_t* dst,
               int32_t* row_ptr, int32_t* col, int32_t* eid, int32_t* cursor, float* dis);
@@ -180,6 +181,12 @@ inline size_t carve_scratch(ggc_ctx* ctx, int slot, Layout&& layout) {
 }
 
 inline int cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
+
+// f(std::integral_constant<int, D>) for the first of the widths Ws that equals D; false if none does.
+template <int... Ws, typename F>
+bool with_width(int D, int& rc, F&& f) {
+    return ((D == Ws && (rc = f(std::integral_constant<int, Ws>{}), true)) || ...);
+}
 
 // hipFuncSetAttribute applies to the CURRENT device: "already done" is remembered per device (one bit each), because one
 // process may hold contexts on several GPUs (cuda:0 then cuda:1).  Devices beyond 63 simply set the attribute every time.

@@ -228,16 +228,10 @@ static int launch_gather(ggc_ctx* ctx, hipStream_t st, int N, const float* x, co
 template <int MODE, bool EPI>
 static int gather_any(ggc_ctx* ctx, hipStream_t st, int N, int D, const float* x, const int32_t* row_ptr, const int32_t* col,
                       const float* w, const float* bias, const float* gate, const float* h, float* out, float* y) {
-    switch (D) {
-        case 32:  return launch_gather<32, MODE, EPI>(ctx, st, N, x, row_ptr, col, w, bias, gate, h, out, y);
-        case 64:  return launch_gather<64, MODE, EPI>(ctx, st, N, x, row_ptr, col, w, bias, gate, h, out, y);
-        case 96:  return launch_gather<96, MODE, EPI>(ctx, st, N, x, row_ptr, col, w, bias, gate, h, out, y);
-        case 128: return launch_gather<128, MODE, EPI>(ctx, st, N, x, row_ptr, col, w, bias, gate, h, out, y);
-        case 160: return launch_gather<160, MODE, EPI>(ctx, st, N, x, row_ptr, col, w, bias, gate, h, out, y);
-        case 192: return launch_gather<192, MODE, EPI>(ctx, st, N, x, row_ptr, col, w, bias, gate, h, out, y);
-        case 224: return launch_gather<224, MODE, EPI>(ctx, st, N, x, row_ptr, col, w, bias, gate, h, out, y);
-        case 256: return launch_gather<256, MODE, EPI>(ctx, st, N, x, row_ptr, col, w, bias, gate, h, out, y);
-    }
+    int rc;
+    if (with_width<32, 64, 96, 128, 160, 192, 224, 256>(D, rc, [&](auto d) {
+            return launch_gather<decltype(d)::value, MODE, EPI>(ctx, st, N, x, row_ptr, col, w, bias, gate, h, out, y); }))
+        return rc;
     return set_err(ctx, GGC_E_UNSUPPORTED, "D=%d unsupported in training (a multiple of 32 from 32 to 256)", D);
 }
 
@@ -292,16 +286,10 @@ int ggc_train_gcn_backward(ggc_ctx* ctx, ggc_stream stream, int N, int D, const 
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     ProfScope prof(ctx, st, "train_gcn_backward");
     const dim3 grid = grid_for((int64_t)N * D);
-    switch (D) {
-        case 32:  hipLaunchKernelGGL(k_gcn_epi_bwd<32>, grid, dim3(TB), 0, st, N, g_y, out, gate, g_out, g_gate); break;
-        case 64:  hipLaunchKernelGGL(k_gcn_epi_bwd<64>, grid, dim3(TB), 0, st, N, g_y, out, gate, g_out, g_gate); break;
-        case 96:  hipLaunchKernelGGL(k_gcn_epi_bwd<96>, grid, dim3(TB), 0, st, N, g_y, out, gate, g_out, g_gate); break;
-        case 128: hipLaunchKernelGGL(k_gcn_epi_bwd<128>, grid, dim3(TB), 0, st, N, g_y, out, gate, g_out, g_gate); break;
-        case 160: hipLaunchKernelGGL(k_gcn_epi_bwd<160>, grid, dim3(TB), 0, st, N, g_y, out, gate, g_out, g_gate); break;
-        case 192: hipLaunchKernelGGL(k_gcn_epi_bwd<192>, grid, dim3(TB), 0, st, N, g_y, out, gate, g_out, g_gate); break;
-        case 224: hipLaunchKernelGGL(k_gcn_epi_bwd<224>, grid, dim3(TB), 0, st, N, g_y, out, gate, g_out, g_gate); break;
-        case 256: hipLaunchKernelGGL(k_gcn_epi_bwd<256>, grid, dim3(TB), 0, st, N, g_y, out, gate, g_out, g_gate); break;
-    }
+    int rc;
+    with_width<32, 64, 96, 128, 160, 192, 224, 256>(D, rc, [&](auto d) {       // train_width(D): one of them matches
+        hipLaunchKernelGGL(k_gcn_epi_bwd<decltype(d)::value>, grid, dim3(TB), 0, st, N, g_y, out, gate, g_out, g_gate);
+        return GGC_OK; });
     GGC_LAUNCH_CHECK(ctx);
     return gather_any<G_SYM, false>(ctx, st, N, D, g_out, srow_ptr, scol, dis, nullptr, nullptr, nullptr, g_xw, nullptr);
 }
@@ -362,16 +350,10 @@ int ggc_train_graph_pool(ggc_ctx* ctx, ggc_stream stream, int G, int N, int D, c
     GGC_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     ProfScope prof(ctx, st, "train_graph_pool");
-    switch (D) {
-        case 32:  hipLaunchKernelGGL(k_pool<32>, dim3(G), dim3(TB), 0, st, node_ptr, h, score, attn, hb); break;
-        case 64:  hipLaunchKernelGGL(k_pool<64>, dim3(G), dim3(TB), 0, st, node_ptr, h, score, attn, hb); break;
-        case 96:  hipLaunchKernelGGL(k_pool<96>, dim3(G), dim3(TB), 0, st, node_ptr, h, score, attn, hb); break;
-        case 128: hipLaunchKernelGGL(k_pool<128>, dim3(G), dim3(TB), 0, st, node_ptr, h, score, attn, hb); break;
-        case 160: hipLaunchKernelGGL(k_pool<160>, dim3(G), dim3(TB), 0, st, node_ptr, h, score, attn, hb); break;
-        case 192: hipLaunchKernelGGL(k_pool<192>, dim3(G), dim3(TB), 0, st, node_ptr, h, score, attn, hb); break;
-        case 224: hipLaunchKernelGGL(k_pool<224>, dim3(G), dim3(TB), 0, st, node_ptr, h, score, attn, hb); break;
-        case 256: hipLaunchKernelGGL(k_pool<256>, dim3(G), dim3(TB), 0, st, node_ptr, h, score, attn, hb); break;
-    }
+    int rc;
+    with_width<32, 64, 96, 128, 160, 192, 224, 256>(D, rc, [&](auto d) {
+        hipLaunchKernelGGL(k_pool<decltype(d)::value>, dim3(G), dim3(TB), 0, st, node_ptr, h, score, attn, hb);
+        return GGC_OK; });
     GGC_LAUNCH_CHECK(ctx);
     return GGC_OK;
 }
@@ -384,16 +366,10 @@ int ggc_train_graph_pool_backward(ggc_ctx* ctx, ggc_stream stream, int G, int N,
     GGC_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     ProfScope prof(ctx, st, "train_graph_pool");
-    switch (D) {
-        case 32:  hipLaunchKernelGGL(k_pool_bwd<32>, dim3(G), dim3(TB), 0, st, node_ptr, h, attn, g_hb, g_h, g_score); break;
-        case 64:  hipLaunchKernelGGL(k_pool_bwd<64>, dim3(G), dim3(TB), 0, st, node_ptr, h, attn, g_hb, g_h, g_score); break;
-        case 96:  hipLaunchKernelGGL(k_pool_bwd<96>, dim3(G), dim3(TB), 0, st, node_ptr, h, attn, g_hb, g_h, g_score); break;
-        case 128: hipLaunchKernelGGL(k_pool_bwd<128>, dim3(G), dim3(TB), 0, st, node_ptr, h, attn, g_hb, g_h, g_score); break;
-        case 160: hipLaunchKernelGGL(k_pool_bwd<160>, dim3(G), dim3(TB), 0, st, node_ptr, h, attn, g_hb, g_h, g_score); break;
-        case 192: hipLaunchKernelGGL(k_pool_bwd<192>, dim3(G), dim3(TB), 0, st, node_ptr, h, attn, g_hb, g_h, g_score); break;
-        case 224: hipLaunchKernelGGL(k_pool_bwd<224>, dim3(G), dim3(TB), 0, st, node_ptr, h, attn, g_hb, g_h, g_score); break;
-        case 256: hipLaunchKernelGGL(k_pool_bwd<256>, dim3(G), dim3(TB), 0, st, node_ptr, h, attn, g_hb, g_h, g_score); break;
-    }
+    int rc;
+    with_width<32, 64, 96, 128, 160, 192, 224, 256>(D, rc, [&](auto d) {
+        hipLaunchKernelGGL(k_pool_bwd<decltype(d)::value>, dim3(G), dim3(TB), 0, st, node_ptr, h, attn, g_hb, g_h, g_score);
+        return GGC_OK; });
     GGC_LAUNCH_CHECK(ctx);
     return GGC_OK;
 }

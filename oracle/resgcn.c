@@ -12,7 +12,7 @@
  *
  * All arithmetic is float32.  The reference's float sums have no canonical order (PyTorch's CPU kernels vectorise and
  * block them, PyG scatters in edge order), so this restatement fixes one, and it fixes THE ORDER OF THE MI355X KERNELS
- * (csrc/ggc_resgcn.hip) — with exp / sigmoid / GELU as the shared IEEE sequences of include/ggc_fmath.h — so that the two
+ * (csrc/ggc_resgcn.hip, ggc_gnn_dense.hip, ggc_gnn_gather.hip) — with exp / sigmoid / GELU as the shared IEEE sequences of include/ggc_fmath.h — so that the two
  * produce the same bits and trimaps and masks can be compared pixel for pixel end to end:
  *   - a Linear on the vector pipe: products added in k order from 0, bias last (one rounding per multiply and per add);
  *   - a D x D Linear on the matrix pipe (GCNConv / SAGEConv / fuse): v_mfma_f32_32x32x2_f32 is a chain of fused
