@@ -40,6 +40,7 @@ enum Slot : int {
     S_POLYGONS,
     S_SCISSORS,
     S_OUTLINE, S_OUTLINE_LIST,
+    S_DIST, S_DIST_TMP,
     S_COUNT
 };
 

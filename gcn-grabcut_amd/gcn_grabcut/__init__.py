@@ -28,7 +28,9 @@ from .pipeline import (GCNGrabCutPipeline, ClosedFormMatte, ForegroundColours, F
                        trimap_matte_warm, upsample_mask, FullCut, cut_mask_full, lift_labels,
                        GeodesicHints, geodesic_hints, paint_strokes, stroke_pixels, paint_polygons, polygon_mask,
                        Scissors, trace_boundary,
-                       Outline, mask_outlines, mask_outlines_batch, outlines_svg_path, outlines_to_lassos)
+                       Outline, mask_outlines, mask_outlines_batch, outlines_svg_path, outlines_to_lassos,
+                       ModifyMask, mask_distance, mask_distance_batch, modify_mask, modify_mask_batch, grow_mask,
+                       shrink_mask, open_mask, close_mask, border_mask, mask_to_trimap)
 from .synthetic import synthetic_image, synthetic_batch
 from .losses import FocalLoss, LabelSmoothingCE, TrimapLoss
 from .trainer import Trainer, TrainConfig
@@ -50,6 +52,8 @@ __all__ = [
     "pack_polygons", "paint_polygons", "polygon_mask",
     "pack_paths", "Scissors", "trace_boundary",
     "Outline", "mask_outlines", "mask_outlines_batch", "outlines_svg_path", "outlines_to_lassos",
+    "ModifyMask", "mask_distance", "mask_distance_batch", "modify_mask", "modify_mask_batch", "grow_mask", "shrink_mask",
+    "open_mask", "close_mask", "border_mask", "mask_to_trimap",
     "ResGCNNet", "GCNTrimapNet", "GATTrimapNet", "build_model", "probs_to_node_trimap", "project_to_pixels",
     "Data", "Batch", "synthetic_image", "synthetic_batch",
     "FocalLoss", "LabelSmoothingCE", "TrimapLoss", "Trainer", "TrainConfig",

@@ -354,6 +354,29 @@ class Engine:
             self.ctx.call("ggc_mask_outlines", *args, None, None, None, 0, 0)
         return fill(int(image_ptr[-1].item()), int(image_vert_ptr[-1].item()))
 
+    def mask_distance(self, masks, border_background=False, max_distance2=0, out=None) -> torch.Tensor:
+        """The exact signed squared Euclidean distance transform (ggc_mask_distance, include/ggc.h K2): masks (B,H,W) uint8
+        on the device, any nonzero byte foreground -> (B,H,W) int32: +d2 to the nearest foreground pixel on the background,
+        -d2 to the nearest background pixel on the foreground, magnitude 2^31 - 1 where there is none or where it exceeds
+        max_distance2 > 0.  border_background: everything outside the image is background.  No synchronisation."""
+        b, h, w = masks.shape
+        if out is None:
+            out = self.empty(b, h, w, dtype=torch.int32)
+        self.ctx.call("ggc_mask_distance", self._stream(), b, h, w, masks.data_ptr(), int(bool(border_background)),
+                      int(max_distance2), out.data_ptr())
+        return out
+
+    def modify_mask(self, masks, op, r2_a, r2_b=0, border_background=False, out=None) -> torch.Tensor:
+        """One modifier of ggc_modify_mask (include/ggc.h K3) on masks (B,H,W) uint8 on the device: op 0 grow, 1 shrink,
+        2 border, 3 open, 4 close, 5 trimap; r2_a, r2_b squared radii.  -> (B,H,W) uint8 (0/1, the trimap 0/128/255); out
+        may be masks itself.  No synchronisation."""
+        b, h, w = masks.shape
+        if out is None:
+            out = torch.empty_like(masks)
+        self.ctx.call("ggc_modify_mask", self._stream(), b, h, w, masks.data_ptr(), int(op), int(r2_a), int(r2_b),
+                      int(bool(border_background)), out.data_ptr())
+        return out
+
     def next_click(self, pred, gt) -> torch.Tensor:
         """The next simulated click of the NoC protocol per image (ggc_next_click): pred, gt (B,H,W) uint8, nonzero =
         foreground -> (B,4) int32 on the device = row, col, label (1 = fg, 0 = bg), d2; (-1,-1,-1,0) where pred == gt."""

@@ -77,6 +77,8 @@ SIGNATURES = {
     "ggc_grid_maxflow": [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp],
     "ggc_clean_mask": [_vp, _vp, _i, _i, _i, _vp, _f, _i, _vp],
     "ggc_mask_outlines": [_vp, _vp, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i64, _i64],
+    "ggc_mask_distance": [_vp, _vp, _i, _i, _i, _vp, _i, _i64, _vp],
+    "ggc_modify_mask": [_vp, _vp, _i, _i, _i, _vp, _i, _i64, _i64, _i, _vp],
     "ggc_compose_outputs": [_vp, _vp, _i, _i, _i, _vp, _vp, _f, _i, _i, _i, _vp, _vp],
     "ggc_alpha_matte": [_vp, _vp, _i, _i, _i, _vp, _vp, _i, _f, _vp, _vp],
     "ggc_upsample_matte": [_vp, _vp, _i, _i, _i, _vp, _vp, _i, _i, _vp, _i, _f, _vp, _vp, _vp],

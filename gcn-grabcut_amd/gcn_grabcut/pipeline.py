@@ -102,6 +102,17 @@ class SegmentationResult:
             raise ValueError("this result carries no full-resolution outputs: segment with full_image=...")
         return mask_outlines(self.full.binary_mask if full else self.binary_mask, connectivity)
 
+    def modified(self, *steps: "ModifyMask", full: bool = False) -> np.ndarray:
+        """binary_mask, or full.binary_mask with full=True, after the steps in order (additive; modify_mask)."""
+        if full and self.full is None:
+            raise ValueError("this result carries no full-resolution outputs: segment with full_image=...")
+        return modify_mask(self.full.binary_mask if full else self.binary_mask, *steps)
+
+    def trimap_from_mask(self, inner, outer=None, full: bool = False) -> np.ndarray:
+        """A 0 / 128 / 255 trimap for trimap_matte with an unknown band of the given radii around the mask's boundary
+        (additive; mask_to_trimap)."""
+        return self.modified(ModifyMask("trimap", inner, outer), full=full)
+
 
 def guided_filter(guide: np.ndarray, src: np.ndarray, radius: int = 8, eps: float = 1e-3, device="cuda") -> np.ndarray:
     """Edge-preserving filter of `src` under `guide` (He et al.) — reference pipeline.py:71-100."""
@@ -666,6 +677,188 @@ def outlines_svg_path(outlines) -> str:
 def outlines_to_lassos(outlines) -> "list[np.ndarray]":
     """The outer loops as (row, col) polygons that lasso= / fg_polygons= take (holes are left out)."""
     return [np.asarray(o.vertices, np.int32).copy() for o in outlines if not o.hole]
+
+
+DIST_FAR = 2 ** 31 - 1                  # GGC_DIST_FAR: the magnitude where no opposite pixel exists, or beyond a cap
+MAX_RADIUS2 = 2 * 16384 ** 2            # no two pixels of a 16384 x 16384 image are further apart
+MODIFY_OPS = {"grow": 0, "shrink": 1, "border": 2, "open": 3, "close": 4, "trimap": 5}      # ggc_modify_mask's op
+_TWO_RADII = (MODIFY_OPS["border"], MODIFY_OPS["trimap"])
+
+
+def _radius2(radius, radius2, what: str) -> int:
+    """A radius as the squared integer radius the device takes: the disk is dy^2 + dx^2 <= floor(radius^2); radius2 gives
+    the integer itself (2 is the 8-neighbourhood).  Exactly one of the two."""
+    if (radius is None) == (radius2 is None):
+        raise ValueError(f"{what}: give either a radius or radius2, got {radius!r} and {radius2!r}")
+    if radius2 is not None:
+        if isinstance(radius2, (bool, np.bool_)) or not isinstance(radius2, (int, np.integer)) or radius2 < 0:
+            raise ValueError(f"{what}: radius2 must be an integer >= 0, got {radius2!r}")
+        r2 = int(radius2)
+    elif isinstance(radius, (int, np.integer)) and not isinstance(radius, (bool, np.bool_)):
+        if radius < 0:
+            raise ValueError(f"{what}: radius must be >= 0, got {radius!r}")
+        r2 = int(radius) ** 2
+    else:
+        try:
+            r = float(radius)
+        except (TypeError, ValueError):
+            raise ValueError(f"{what}: radius must be a number, got {radius!r}") from None
+        if not np.isfinite(r) or r < 0:
+            raise ValueError(f"{what}: radius must be finite and >= 0, got {radius!r}")
+        if r * r > 2 * MAX_RADIUS2:
+            raise ValueError(f"{what}: radius {radius!r} is beyond any image")
+        r2 = int(np.floor(r * r))
+    if r2 > MAX_RADIUS2:
+        raise ValueError(f"{what}: squared radius {r2} exceeds {MAX_RADIUS2} = 2 * 16384^2")
+    return r2
+
+
+def _radius2_pair(inner, outer, radius2, what: str) -> "tuple[int, int]":
+    """The two squared radii of border and trimap: outer None means outer = inner; radius2 an integer (both) or a pair."""
+    if radius2 is not None:
+        if outer is not None:
+            raise ValueError(f"{what}: give either radii or radius2, got outer={outer!r} and radius2={radius2!r}")
+        a, b = radius2 if isinstance(radius2, (tuple, list)) and len(radius2) == 2 else (radius2, radius2)
+        return _radius2(inner, a, what), _radius2(None, b, what)
+    a = _radius2(inner, None, what)
+    return a, (a if outer is None else _radius2(outer, None, what))
+
+
+@dataclass(frozen=True)
+class ModifyMask:
+    """One step of modify_mask (ggc_modify_mask, include/ggc.h K3).  op: "grow", "shrink", "border", "open",
+    "close" or "trimap" (or its number).  radius: an int or float >= 0, the disk being dy^2 + dx^2 <= floor(radius^2), or
+    radius2= the squared integer itself.  border and trimap take two radii: radius on the foreground side, outer on the
+    background side (None: the same; radius2 may be a pair).  border_background: everything outside the image is
+    background, so a shrink also eats from the image's edge."""
+    op: "str | int"
+    radius: "Optional[float]" = None
+    outer: "Optional[float]" = None
+    border_background: bool = False
+    radius2: "Optional[int | tuple]" = None
+
+    def __post_init__(self):
+        self.args()
+
+    def args(self) -> "tuple[int, int, int, bool]":
+        """(op, r2_a, r2_b, border_background) as the device takes them; raises ValueError on a bad step."""
+        op = MODIFY_OPS.get(self.op.lower()) if isinstance(self.op, str) else (self.op if self.op in MODIFY_OPS.values() else None)
+        if op is None:
+            raise ValueError(f"ModifyMask: op must be one of {sorted(MODIFY_OPS)}, got {self.op!r}")
+        what = f"ModifyMask({self.op!r})"
+        if op in _TWO_RADII:
+            r2_a, r2_b = _radius2_pair(self.radius, self.outer, self.radius2, what)
+        else:
+            if self.outer is not None or isinstance(self.radius2, (tuple, list)):
+                raise ValueError(f"{what}: only border and trimap take a second radius")
+            r2_a, r2_b = _radius2(self.radius, self.radius2, what), 0
+        return int(op), r2_a, r2_b, bool(self.border_background)
+
+
+def _mask_batch(masks, what: str) -> np.ndarray:
+    m = np.asarray(masks)
+    if m.ndim != 3:
+        raise ValueError(f"{what}: masks must be (B, H, W), got {m.shape}")
+    if m.shape[0] and (m.shape[1] < 1 or m.shape[2] < 1):
+        raise ValueError(f"{what}: empty masks {m.shape}")
+    return (m != 0).astype(np.uint8)
+
+
+def _mask_2d(mask, what: str) -> np.ndarray:
+    m = np.asarray(mask)
+    if m.ndim != 2:
+        raise ValueError(f"{what}: mask must be (H, W), got {m.shape}")
+    return m[None]
+
+
+def mask_distance_batch(masks, signed: bool = True, squared: bool = False, border_background: bool = False,
+                        max_distance=None, max_distance2=None, device="cuda") -> np.ndarray:
+    """The exact Euclidean distance transform of every mask of a batch (additive; one ggc_mask_distance call).  masks:
+    (B, H, W), any nonzero value foreground.  -> (B, H, W) float64: the distance from each background pixel to the nearest
+    foreground pixel, and with signed=True minus the distance from each foreground pixel to the nearest background pixel
+    (signed=False: its magnitude), inf where there is none; squared=True gives the exact int32 plane instead, DIST_FAR for
+    inf.  border_background: everything outside the image is background.  max_distance (or max_distance2, its exact
+    square): larger distances are reported as inf and are not searched for."""
+    from ._engine import get_engine
+    cap2 = None if max_distance is None and max_distance2 is None else _radius2(max_distance, max_distance2, "mask_distance")
+    m = _mask_batch(masks, "mask_distance_batch")
+    if m.shape[0] == 0:
+        return np.zeros(m.shape, np.int32 if squared else np.float64)
+    if cap2 == 0:                                                       # every magnitude is at least 1
+        d2 = np.where(m != 0, -DIST_FAR, DIST_FAR).astype(np.int32)
+    else:
+        eng = get_engine(device)
+        d2 = eng.mask_distance(eng.to_device(m), border_background, cap2 or 0).cpu().numpy()
+    if not signed:
+        d2 = np.abs(d2)
+    if squared:
+        return d2
+    mag = np.abs(d2).astype(np.float64)
+    dist = np.where(mag == DIST_FAR, np.inf, np.sqrt(mag))
+    return np.where(d2 < 0, -dist, dist)
+
+
+def mask_distance(mask, signed: bool = True, squared: bool = False, border_background: bool = False, max_distance=None,
+                  max_distance2=None, device="cuda") -> np.ndarray:
+    """The exact Euclidean distance transform of one (H, W) mask: mask_distance_batch of a batch of one."""
+    return mask_distance_batch(_mask_2d(mask, "mask_distance"), signed, squared, border_background, max_distance,
+                               max_distance2, device)[0]
+
+
+def modify_mask_batch(masks, *steps: ModifyMask, device="cuda") -> np.ndarray:
+    """Apply the steps in order to every mask of a batch, on the device (additive; one ggc_modify_mask call per step, no
+    host round trip between them).  masks: (B, H, W), any nonzero value foreground.  -> (B, H, W) uint8 {0, 1}; after a
+    trimap step 0 / 128 / 255 (a step after it reads every nonzero value as foreground)."""
+    from ._engine import get_engine
+    for s in steps:
+        if type(s).__name__ != "ModifyMask":                         # by name: the package is importable under two names
+            raise ValueError(f"modify_mask: steps must be ModifyMask, got {type(s).__name__}")
+    args = [s.args() for s in steps]
+    m = _mask_batch(masks, "modify_mask_batch")
+    if m.shape[0] == 0 or not args:
+        return m
+    eng = get_engine(device)
+    cur = eng.to_device(m)
+    for op, r2_a, r2_b, border in args:
+        eng.modify_mask(cur, op, r2_a, r2_b, border, out=cur)           # in place: the row pass never reads the mask
+    return cur.cpu().numpy()
+
+
+def modify_mask(mask, *steps: ModifyMask, device="cuda") -> np.ndarray:
+    """Apply the steps in order to one (H, W) mask: modify_mask_batch of a batch of one."""
+    return modify_mask_batch(_mask_2d(mask, "modify_mask"), *steps, device=device)[0]
+
+
+def grow_mask(mask, radius=None, border_background: bool = False, radius2=None, device="cuda") -> np.ndarray:
+    """Grow the selection by `radius` pixels: dilation by the exact disk dy^2 + dx^2 <= floor(radius^2) (or radius2)."""
+    return modify_mask(mask, ModifyMask("grow", radius, None, border_background, radius2), device=device)
+
+
+def shrink_mask(mask, radius=None, border_background: bool = False, radius2=None, device="cuda") -> np.ndarray:
+    """Shrink the selection by `radius` pixels: erosion by the same disk; border_background also eats from the edge."""
+    return modify_mask(mask, ModifyMask("shrink", radius, None, border_background, radius2), device=device)
+
+
+def open_mask(mask, radius=None, border_background: bool = False, radius2=None, device="cuda") -> np.ndarray:
+    """Shrink, then grow: drops specks thinner than the disk."""
+    return modify_mask(mask, ModifyMask("open", radius, None, border_background, radius2), device=device)
+
+
+def close_mask(mask, radius=None, border_background: bool = False, radius2=None, device="cuda") -> np.ndarray:
+    """Grow, then shrink: fills pinholes and gaps thinner than the disk."""
+    return modify_mask(mask, ModifyMask("close", radius, None, border_background, radius2), device=device)
+
+
+def border_mask(mask, inner=None, outer=None, border_background: bool = False, radius2=None, device="cuda") -> np.ndarray:
+    """The border band of the selection: foreground pixels within `inner` of the background and background pixels within
+    `outer` of the foreground (None: outer = inner; radius2 an integer or a pair of squared radii)."""
+    return modify_mask(mask, ModifyMask("border", inner, outer, border_background, radius2), device=device)
+
+
+def mask_to_trimap(mask, inner=None, outer=None, border_background: bool = False, radius2=None, device="cuda") -> np.ndarray:
+    """A trimap for trimap_matte from a mask: 255 on the foreground further than `inner` from the background, 0 on the
+    background further than `outer` from the foreground, 128 (unknown) on the band between."""
+    return modify_mask(mask, ModifyMask("trimap", inner, outer, border_background, radius2), device=device)
 
 
 @dataclass(frozen=True)

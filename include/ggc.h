@@ -51,7 +51,9 @@
 extern "C" {
 #endif
 
-#define GGC_VERSION 408 /* 0.4.8: ggc_mask_outlines (the exact vector contours of a mask: crack-following loops on the corner lattice, as
+#define GGC_VERSION 409 /* 0.4.9: ggc_mask_distance, ggc_modify_mask (the exact squared Euclidean distance transform of a mask, signed, and
+                                  grow / shrink / border / open / close / trimap as thresholds of it; additive, no existing entry changes);
+                           0.4.8: ggc_mask_outlines (the exact vector contours of a mask: crack-following loops on the corner lattice, as
                                   vertices in ggc_apply_polygons' packing, with area, perimeter and outer loop; additive, no existing
                                   entry changes);
                            0.4.7: ggc_trace_paths (intelligent scissors: a few boundary anchors joined by the cheapest path along image
@@ -637,6 +639,56 @@ int ggc_clean_mask(ggc_ctx* ctx, ggc_stream stream, int B, int H, int W,
 int ggc_mask_outlines(ggc_ctx* ctx, ggc_stream stream, int B, int H, int W, const uint8_t* mask, int connectivity,
                       int32_t* image_ptr_out, int32_t* image_vert_ptr_out, int32_t* loop_ptr_out, int32_t* loop_info_out,
                       int32_t* verts_out, int64_t loop_capacity, int64_t vert_capacity);
+
+/* K2 — exact distance transform of a mask.  Additive; integer only.
+ *   mask [dev] u8 [B,H,W]: any nonzero byte is foreground.   signed_d2_out [dev] i32 [B,H,W].
+ * DISTANCE.  Between pixels (y, x) and (y', x') it is d2 = (y-y')^2 + (x-x')^2, the squared Euclidean distance of their centres.
+ *   background pixel p:  out[p] = +min over foreground q of d2(p, q)   (>= 1)
+ *   foreground pixel p:  out[p] = -min over background q of d2(p, q)   (<= -1)
+ * so the output is never 0 and its sign gives the mask back.
+ * BORDER.  With flags bit 0, GGC_DIST_BORDER_BG, every position outside the image counts as background (K1's convention): a
+ * foreground pixel of row y is then at most min(y+1, H-y)^2 from background, and likewise in x.  Without the bit nothing
+ * exists outside the image (scipy.ndimage.distance_transform_edt's convention).  Foreground never exists outside the image.
+ * FAR.  Where no opposite pixel exists the magnitude is GGC_DIST_FAR = INT32_MAX (an all-foreground image without the bit is
+ * -GGC_DIST_FAR everywhere).
+ * CAP.  max_dist2 == 0: unbounded.  max_dist2 > 0: every magnitude greater than max_dist2 is reported as GGC_DIST_FAR, and
+ * the row pass looks at most floor(sqrt(max_dist2)) columns to each side, which is what makes a small radius cheap.
+ * METHOD.  A column pass leaves per pixel the 16-bit distance g, within its column, to the nearest pixel of the other class
+ * (all ones in its 15 bits = none, the pixel's class in bit 15); a row pass takes min over x' of g(y,x')^2 + (x-x')^2 with the
+ * row staged in LDS, walking outward from x until k^2 reaches the best so far (csrc/ggc_edt.h).  Exact in every case; an
+ * unbounded call costs O(distance to the answer) per pixel, O(W) where the only opposite pixel is far away.
+ * Every image's result equals that of its single-image call, bit for bit.  B == 0 is a no-op.
+ * Refused before any launch: H or W outside 1..16384, or B*H*W >= 2^31 (GGC_E_SHAPE); a NULL pointer with B > 0, unknown
+ * flag bits, a negative max_dist2 (GGC_E_INVALID_ARG).
+ * No host synchronisation, nothing of data-dependent size.  Scratch from the context: 2 bytes per pixel (g). */
+#define GGC_DIST_BORDER_BG 1
+#define GGC_DIST_FAR 2147483647
+int ggc_mask_distance(ggc_ctx* ctx, ggc_stream stream, int B, int H, int W, const uint8_t* mask, int flags, int64_t max_dist2,
+                      int32_t* signed_d2_out);
+
+/* K3 — modify a mask by a distance: thresholds of K2, fused into its row pass (no int32 plane is written).
+ *   mask_in [dev] u8 [B,H,W], any nonzero byte foreground.   out [dev] u8 [B,H,W]; may alias mask_in.
+ * D_out(p) / D_in(p) are K2's magnitudes of a background / foreground pixel.  r2_a, r2_b are SQUARED radii: the disk is
+ * dy^2 + dx^2 <= r2 (r2 = 1: the 4-neighbourhood, r2 = 2: the 8-neighbourhood).
+ *   op 0 GROW    1 where fg or D_out <= r2_a (dilation by the exact disk)
+ *   op 1 SHRINK  1 where fg and D_in > r2_a
+ *   op 2 BORDER  1 where (fg and D_in <= r2_a) or (bg and D_out <= r2_b): GROW(r2_b) minus SHRINK(r2_a)
+ *   op 3 OPEN    GROW(r2_a) of SHRINK(r2_a)
+ *   op 4 CLOSE   SHRINK(r2_a) of GROW(r2_a)
+ *   op 5 TRIMAP  255 where fg and D_in > r2_a, 0 where bg and D_out > r2_b, else 128 (what O3t reads as a trimap)
+ * flags as K2; the bit bears on every shrink step (D_in).  r2 = 0 makes GROW and SHRINK the identity normalised to {0,1} and
+ * BORDER empty.  r2_b must be 0 for ops 0, 1, 3, 4.  Each step runs K2 capped at its own radius; OPEN and CLOSE run two steps
+ * on the device through a u8 plane of scratch, with no host round trip.
+ * Refused before any launch: as K2, and an unknown op, a negative radius, a nonzero r2_b where it has no meaning
+ * (GGC_E_INVALID_ARG).  Scratch: 2 bytes per pixel, 3 for OPEN and CLOSE. */
+#define GGC_MODIFY_GROW 0
+#define GGC_MODIFY_SHRINK 1
+#define GGC_MODIFY_BORDER 2
+#define GGC_MODIFY_OPEN 3
+#define GGC_MODIFY_CLOSE 4
+#define GGC_MODIFY_TRIMAP 5
+int ggc_modify_mask(ggc_ctx* ctx, ggc_stream stream, int B, int H, int W, const uint8_t* mask_in, int op, int64_t r2_a,
+                    int64_t r2_b, int flags, uint8_t* out);
 
 /* O0 — replaces GrabCut.overlay_mask / crop_foreground (grabcut.py:180-195).
  *   overlay [dev] u8 [B,H,W,3]   rgba [dev] u8 [B,H,W,4]   (either may be NULL) */

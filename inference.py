@@ -51,12 +51,17 @@ def build_parser() -> argparse.ArgumentParser:
                         help="Drop mask components smaller than this fraction of the image")
     parser.add_argument("--keep-largest", action="store_true", help="Keep only the largest connected component")
     parser.add_argument("--save", nargs="+", default=["mask", "overlay"],
-                        choices=["mask", "overlay", "rgba", "trimap", "alpha", "cutout", "outlines"],
+                        choices=["mask", "overlay", "rgba", "trimap", "alpha", "cutout", "outlines", "modified"],
                         help="Which outputs to write (alpha / cutout: the soft matte and the BGRA cut-out with it)")
     # additive: the mask's exact vector outlines (ggc_mask_outlines), written as <prefix>_outlines.json by --save outlines
     parser.add_argument("--outline-connectivity", type=int, choices=[4, 8], default=8,
                         help="--save outlines: 8 joins diagonal foreground pixels into one loop (as the mask clean-up "
                              "labels components), 4 separates them")
+    # additive: modify the selection by a distance (ggc_modify_mask), written as <prefix>_modified.png by --save modified
+    parser.add_argument("--modify", action="append", type=_modify_step, default=[], metavar="OP:R[:R2]",
+                        help="--save modified: grow, shrink, open or close the mask by R pixels, or take its border or a "
+                             "trimap with R pixels into the foreground and R2 (default R) into the background, by exact "
+                             "Euclidean distance (repeatable, applied in order)")
     parser.add_argument("--batch", type=int, default=64, help="Images per device batch (additive flag)")
     # additive: user clicks as hard constraints (ggc_apply_hints), single-image runs only
     parser.add_argument("--fg-point", action="append", type=_point, default=[], metavar="ROW,COL",
@@ -173,6 +178,18 @@ def _polygon(text: str):
     return pts
 
 
+def _modify_step(text: str):
+    """OP:R[:R2] -> a ModifyMask step."""
+    from src.gcn_grabcut import ModifyMask
+    parts = text.split(":")
+    try:
+        if len(parts) not in (2, 3):
+            raise ValueError("expected OP:R or OP:R:R2")
+        return ModifyMask(parts[0], float(parts[1]), float(parts[2]) if len(parts) == 3 else None)
+    except ValueError as e:
+        raise argparse.ArgumentTypeError(f"--modify {text!r}: {e}")
+
+
 def outlines_document(shape, outlines, connectivity: int) -> dict:
     """What --save outlines writes: the loops of a mask of `shape` on its corner lattice, (row, col) vertices with area,
     perimeter and outer loop each, and all of them as one SVG path (x = col, y = row) for fill-rule="evenodd"."""
@@ -256,6 +273,8 @@ def main() -> None:
             scissors_options = Scissors(args.scissors_margin, args.scissors_edge_cap, args.scissors_smooth)
         except ValueError as e:
             parser.error(str(e))
+    if bool(args.modify) != ("modified" in args.save):
+        parser.error("--modify steps are written by --save modified: give both or neither")
     if not 0 <= args.stroke_radius <= 16384:
         parser.error("--stroke-radius must be in 0..16384")
     if args.hint_radius < 0:
@@ -414,6 +433,9 @@ def main() -> None:
                     loops = result.outlines(args.outline_connectivity, full=result.full is not None)
                     with open(f"{stem}_outlines.json", "w") as f:
                         json.dump(outlines_document(out.binary_mask.shape, loops, args.outline_connectivity), f)
+                if "modified" in args.save:                 # the mask file written above after the --modify steps
+                    modified = result.modified(*args.modify, full=result.full is not None)
+                    _write_png(f"{stem}_modified.png", modified if modified.max(initial=0) > 1 else modified * 255)
                 t = result.timing
                 print(f"[{n_done}/{len(paths)}] {path.name}  fg={result.binary_mask.mean():.1%}  "
                       f"graph={t.get('graph_build', 0):.4f}s gcn={t.get('gcn_inference', 0):.4f}s "

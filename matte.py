@@ -5,12 +5,18 @@ matte.py — alpha mattes from images and trimaps with the closed-form matte on 
     python3 matte.py --input data/images --trimaps data/trimaps --output mattes/ --save alpha cutout
     python3 matte.py --image cat.jpg --trimap cat_trimap.png --save cutout --decontaminate
     python3 matte.py --image cat_small.jpg --trimap cat_small_trimap.png --full-image cat.jpg   # solved at cat.jpg's size
+    python3 matte.py --image cat.jpg --mask cat_mask.png --band 3:5     # the trimap is made from a mask: unknown within 3 px inside, 5 outside
 
 A trimap is an 8-bit grey image of the photo's size: 255 = foreground, 0 = background, every other byte unknown (the
 convention of the matting benchmarks and of evaluate_matte.py --trimaps).  The matting Laplacian is solved on the
 unknown pixels (gcn_grabcut.trimap_matte, ggc_trimap_matte; DESIGN.md §5.16).  With --input, trimaps are matched by stem;
 images of one size are solved as one batch.  Outputs are named as inference.py names them: <stem>_alpha.png (8-bit grey)
 and <stem>_cutout.png (BGRA cut-out with that alpha).
+
+With --mask and --band INNER[:OUTER] instead of --trimap, the trimap is made on the device from a binary mask (any nonzero
+byte foreground, for instance inference.py's <stem>_mask.png): foreground further than INNER pixels from the background
+stays 255, background further than OUTER (default INNER) from the foreground stays 0, the band between is unknown
+(gcn_grabcut.mask_to_trimap, ggc_modify_mask).
 
 With --full-image (or --full-images DIR, matched by stem) the image and trimap are the working-size version of a larger
 photo: the matte is solved at the working size, lifted, and solved again on the larger photo from there
@@ -34,6 +40,11 @@ def build_parser() -> argparse.ArgumentParser:
     src.add_argument("--input", help="Directory of images (with --trimaps)")
     parser.add_argument("--trimap", default=None, help="Trimap of --image: 255 foreground, 0 background, else unknown")
     parser.add_argument("--trimaps", default=None, help="Directory of trimaps of --input, matched by stem")
+    parser.add_argument("--mask", default=None,
+                        help="Instead of --trimap: a binary mask of --image (any nonzero byte foreground); goes with --band")
+    parser.add_argument("--band", default=None, metavar="INNER[:OUTER]",
+                        help="With --mask: the unknown band around the mask's boundary, INNER pixels into the foreground "
+                             "and OUTER (default INNER) into the background, by exact Euclidean distance")
     parser.add_argument("--output", default="results", help="Output directory")
     parser.add_argument("--save", nargs="+", default=["alpha"], choices=["alpha", "cutout"],
                         help="Which outputs to write: the matte, the BGRA cut-out with it")
@@ -69,7 +80,7 @@ def _read(path: Path, mode: str):
 def collect(args) -> list:
     """(image path, trimap path, full image path or None) triples."""
     if args.image:
-        pairs = [(Path(args.image), Path(args.trimap), Path(args.full_image) if args.full_image else None)]
+        pairs = [(Path(args.image), Path(args.trimap or args.mask), Path(args.full_image) if args.full_image else None)]
     else:
         in_dir, tri_dir = Path(args.input), Path(args.trimaps)
         for d, flag in ((in_dir, "--input"), (tri_dir, "--trimaps")):
@@ -102,8 +113,10 @@ def collect(args) -> list:
 def main() -> None:
     parser = build_parser()
     args = parser.parse_args()
-    if args.image and (args.trimap is None or args.trimaps is not None):
-        parser.error("--image goes with --trimap (one file), not --trimaps")
+    if args.image and ((args.trimap is None) == (args.mask is None) or args.trimaps is not None):
+        parser.error("--image goes with --trimap (one file) or with --mask and --band, not --trimaps")
+    if (args.mask is None) != (args.band is None) or (args.mask is not None and not args.image):
+        parser.error("--mask and --band go together, with --image")
     if args.input and (args.trimaps is None or args.trimap is not None):
         parser.error("--input goes with --trimaps (a directory), not --trimap")
     if args.image and args.full_images is not None:
@@ -115,7 +128,16 @@ def main() -> None:
     if args.batch < 1:
         parser.error("--batch must be >= 1")
     from src.gcn_grabcut._engine import (check_closed_form_args, check_closed_form_shape, check_lift_args, get_engine)
-    from src.gcn_grabcut.pipeline import ForegroundColours, _write_png, alpha_to_u8
+    from src.gcn_grabcut.pipeline import ForegroundColours, ModifyMask, _write_png, alpha_to_u8
+    band = None
+    if args.band is not None:
+        try:
+            radii = [float(t) for t in args.band.split(":")]
+            if len(radii) not in (1, 2):
+                raise ValueError(f"--band takes INNER or INNER:OUTER, got {args.band!r}")
+            band = ModifyMask("trimap", radii[0], radii[1] if len(radii) == 2 else None).args()
+        except ValueError as e:
+            parser.error(str(e))
     cf = (args.cf_radius, args.cf_eps, args.cf_iters, args.cf_tol)
     try:
         check_closed_form_args(cf[0], cf[1], 0, cf[2], cf[3])
@@ -155,6 +177,9 @@ def main() -> None:
             t0 = time.perf_counter()
             bgr = eng.to_device(np.stack([im for _, im, _, _ in chunk]))
             tri = eng.to_device(np.stack([t for _, _, t, _ in chunk]))
+            if band is not None:                          # --mask: the trimap is made here, from the mask that was read
+                tri = eng.modify_mask(tri, *band)
+                chunk = [(p, im, t, f) for (p, im, _, f), t in zip(chunk, tri.cpu().numpy())]
             if chunk[0][3] is None:
                 alpha, rgba, iters, rel = eng.trimap_matte(bgr, tri, *cf, want_rgba=True)
             else:                                         # the working-size solve, the lift, the warm solve at full size
