@@ -41,6 +41,7 @@ enum Slot : int {
     S_SCISSORS,
     S_OUTLINE, S_OUTLINE_LIST,
     S_DIST, S_DIST_TMP,
+    S_WAND,
     S_COUNT
 };
 
@@ -114,6 +115,7 @@ struct Knobs {
     int agg_direct;             // GGC_AGG_DIRECT (0): 1 = GCNConv gather straight from L2 (k_aggregate) instead of the graph-resident kernel
     int slic_seq_connectivity;  // GGC_SLIC_SEQ_CONNECTIVITY (0): 1 = literal one-thread-per-image raster replay of skimage's connectivity pass
     int matte_eval_levels;      // GGC_MATTE_EVAL_LEVELS (0): threshold levels labelled per pass of ggc_matte_errors, 1 | 2 | 5 | 10; 0 = 10 while the maps fit 4 GiB, else 1
+    int wand_seeds_per_pass;    // GGC_WAND_SEEDS_PER_PASS (0): seeds labelled per pass of ggc_wand_select, 1..4096; 0 = as many as keep the parent maps within 1 GiB
 };
 const Knobs& knobs();
 

@@ -27,7 +27,7 @@ from .pipeline import (GCNGrabCutPipeline, ClosedFormMatte, ForegroundColours, F
                        closed_form_matte_full, lift_trimap, trimap_matte, trimap_matte_full,
                        trimap_matte_warm, upsample_mask, FullCut, cut_mask_full, lift_labels,
                        GeodesicHints, geodesic_hints, paint_strokes, stroke_pixels, paint_polygons, polygon_mask,
-                       Scissors, trace_boundary,
+                       Scissors, trace_boundary, Wand, wand_select, wand_select_batch, paint_wand,
                        Outline, mask_outlines, mask_outlines_batch, outlines_svg_path, outlines_to_lassos,
                        ModifyMask, mask_distance, mask_distance_batch, modify_mask, modify_mask_batch, grow_mask,
                        shrink_mask, open_mask, close_mask, border_mask, mask_to_trimap)
@@ -51,6 +51,7 @@ __all__ = [
     "pack_strokes", "paint_strokes", "stroke_pixels",
     "pack_polygons", "paint_polygons", "polygon_mask",
     "pack_paths", "Scissors", "trace_boundary",
+    "Wand", "wand_select", "wand_select_batch", "paint_wand",
     "Outline", "mask_outlines", "mask_outlines_batch", "outlines_svg_path", "outlines_to_lassos",
     "ModifyMask", "mask_distance", "mask_distance_batch", "modify_mask", "modify_mask_batch", "grow_mask", "shrink_mask",
     "open_mask", "close_mask", "border_mask", "mask_to_trimap",

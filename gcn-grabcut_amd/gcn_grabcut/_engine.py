@@ -320,6 +320,20 @@ class Engine:
             self.ctx.call("ggc_trace_paths", *args, verts.data_ptr(), n)
         return verts, vert_ptr
 
+    # ------------------------------------------------------------------ H5
+    def wand_select(self, bgr, seeds, seed_ptr, tolerance=32, connectivity=8, sample=1, mask=None, select=True, counts=False):
+        """Magic wand (ggc_wand_select, include/ggc.h H5): bgr (B,H,W,3) uint8, seeds (K,3) int32 = row, col, label and
+        seed_ptr (B+1,) int32 on the device (upload_hints).  mask (B,H,W) uint8 GrabCut labels is painted in place;
+        select=True gives the (B,H,W) uint8 selection, 255 | 0; counts=True the (B,2) int32 pixels decided by a
+        foreground / background seed.  -> (mask, select, counts), None for what was not asked for.  A batch without a
+        seed is a no-op of the entry: its selection and counts are the zeros they are made as."""
+        b, h, w, _ = bgr.shape
+        sel = torch.zeros(b, h, w, dtype=torch.uint8, device=self.device) if select else None
+        cnt = torch.zeros(b, 2, dtype=torch.int32, device=self.device) if counts else None
+        self.ctx.call("ggc_wand_select", self._stream(), b, h, w, bgr.data_ptr(), _native.ptr(seeds) or None, seed_ptr.data_ptr(),
+                      int(tolerance), int(connectivity), int(sample), _native.ptr(mask), _native.ptr(sel), _native.ptr(cnt))
+        return mask, sel, cnt
+
     def mask_outlines(self, masks, connectivity=8, capacity=None):
         """Mask outlines (ggc_mask_outlines, include/ggc.h K1): masks (B,H,W) uint8 on the device, any nonzero byte
         foreground -> (verts (V,2) int32 = row, col corners; loop_ptr (Q+1,); loop_info (Q,3) = area, outer, perimeter;

@@ -72,6 +72,7 @@ SIGNATURES = {
     "ggc_stroke_pixels": [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _i64],
     "ggc_apply_polygons": [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp],
     "ggc_trace_paths": [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _i64],
+    "ggc_wand_select": [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp],
     "ggc_next_click": [_vp, _vp, _i, _i, _i, _vp, _vp, _vp],
     "ggc_grabcut": [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _u64, _vp],
     "ggc_grid_maxflow": [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp],

@@ -130,6 +130,57 @@ class GrabCut:
         run_with_trimap (so the promotion of probable labels and the single-class guard apply)."""
         return self.run_with_trimap(self.lasso_trimap(polygon))
 
+    def wand_trimap(self, bg_points, fg_points=(), wand=None) -> np.ndarray:
+        """Additive: the start mask of run_with_wand: GC_BGD on what the background seeds' magic-wand selections hold on
+        self.image, GC_FGD on the foreground seeds', GC_PR_FGD elsewhere (ggc_wand_select; `wand` is a pipeline.Wand,
+        None: its defaults; background seeds come after foreground ones and win).  A ValueError if no pixel is decided
+        as background, or every pixel is: GrabCut would have no background model, or nothing left to cut."""
+        from .pipeline import _wand_args
+        from .graph_builder import pack_hints
+        wand = _wand_args(wand)
+        rows, ptr = pack_hints([(fg_points if fg_points is not None else (), bg_points if bg_points is not None else ())])
+        eng = self._eng
+        h, w = self.image.shape[:2]
+        n_bg = 0
+        start = eng.to_device(np.full((1, h, w), Label.FG_PROBABLE, np.uint8))
+        if ptr[-1]:
+            d_rows, d_ptr = eng.upload_hints(rows, ptr)
+            _, _, counts = eng.wand_select(eng.to_device(np.ascontiguousarray(self.image)[None]), d_rows, d_ptr, *wand.args(),
+                                           mask=start, select=False, counts=True)
+            n_bg = int(counts[0, 1].item())
+        if n_bg == 0:
+            raise ValueError("the wand selected no background pixel: give a background seed inside the image")
+        if n_bg == h * w:
+            raise ValueError("the wand selected every pixel as background: lower the tolerance or move the seed")
+        return start[0].cpu().numpy()
+
+    def run_with_wand(self, bg_points, fg_points=(), wand=None) -> np.ndarray:
+        """Additive: classical GrabCut from magic-wand seeds, the sibling of run_with_lasso: wand_trimap(bg_points,
+        fg_points, wand), then run_with_trimap (so the promotion of probable labels and the single-class guard apply)."""
+        return self.run_with_trimap(self.wand_trimap(bg_points, fg_points, wand))
+
+    def add_wand(self, fg_points=(), bg_points=(), wand=None) -> np.ndarray:
+        """Additive: paint magic-wand selections into the current mask as GC_FGD / GC_BGD (ggc_wand_select on self.image;
+        `wand` is a pipeline.Wand, None: its defaults; background seeds win where selections overlap).  The edit runs on
+        the mask the last run left on the device; the GMMs are kept, so refine(n) continues from the edited mask, as
+        after add_strokes."""
+        if self.mask is None:
+            raise RuntimeError("Call run_with_bbox or run_with_trimap first.")
+        from .pipeline import _wand_args
+        from .graph_builder import pack_hints
+        wand = _wand_args(wand)
+        rows, ptr = pack_hints([(fg_points, bg_points)])
+        eng = self._eng
+        if self._dmask is None or not self.history or not np.array_equal(self.mask, self.history[-1].mask_copy):
+            self._dmask = eng.to_device(np.ascontiguousarray(self.mask, dtype=np.uint8)[None])   # the host mask was edited
+        if ptr[-1]:
+            d_rows, d_ptr = eng.upload_hints(rows, ptr)
+            eng.wand_select(eng.to_device(np.ascontiguousarray(self.image)[None]), d_rows, d_ptr, *wand.args(),
+                            mask=self._dmask, select=False)
+            self.mask = self._dmask[0].cpu().numpy()
+        self._snapshot("wand")
+        return self._binary()
+
     def refine(self, extra_iter: int = 3) -> np.ndarray:
         """Continue from the current GMM state (GC_EVAL) — reference grabcut.py:153-163."""
         if self.mask is None:

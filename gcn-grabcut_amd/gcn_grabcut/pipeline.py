@@ -614,6 +614,108 @@ def polygon_mask(shape, polygon, device="cuda") -> np.ndarray:
 
 
 @dataclass(frozen=True)
+class Wand:
+    """The options of the magic wand (ggc_wand_select, include/ggc.h H5).  tolerance in 0..255: how far,
+    in the channel that differs most, a pixel's colour may lie from the seed's; connectivity 4 or 8: the neighbours
+    through which a selection spreads from its seed; contiguous=False: "select similar", every pixel within the
+    tolerance wherever it lies; sample 1, 3 or 5: the side of the window around the seed whose mean is the seed's
+    colour.  The defaults are recorded choices (the ones image editors ship with), not tuned results."""
+    tolerance: int = 32
+    connectivity: int = 8
+    contiguous: bool = True
+    sample: int = 1
+
+    def __post_init__(self):
+        t = self.tolerance
+        if isinstance(t, bool) or not isinstance(t, (int, np.integer)) or not 0 <= int(t) <= 255:
+            raise ValueError(f"Wand: tolerance must be an integer in [0, 255], got {t!r}")
+        for name, allowed in (("connectivity", (4, 8)), ("sample", (1, 3, 5))):
+            v = getattr(self, name)
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or int(v) not in allowed:
+                raise ValueError(f"Wand: {name} must be one of {allowed}, got {v!r}")
+        if not isinstance(self.contiguous, (bool, np.bool_)):
+            raise ValueError(f"Wand: contiguous must be a bool, got {self.contiguous!r}")
+
+    def args(self) -> "tuple[int, int, int]":
+        """(tolerance, connectivity, sample) as ggc_wand_select takes them: connectivity 0 = not contiguous."""
+        return int(self.tolerance), int(self.connectivity) if self.contiguous else 0, int(self.sample)
+
+
+def _wand_args(wand) -> Wand:
+    if wand is None:
+        return Wand()
+    if not isinstance(wand, Wand):
+        raise ValueError(f"wand must be a Wand or None, got {type(wand).__name__}")
+    return wand
+
+
+def _image_batch(images_or_array, what: str) -> np.ndarray:
+    """A (B, H, W, 3) uint8 array, or a sequence of equally sized (H, W, 3) uint8 images -> (B, H, W, 3) uint8."""
+    if isinstance(images_or_array, np.ndarray) and images_or_array.ndim == 4:
+        a = images_or_array
+        if a.dtype != np.uint8 or a.shape[3] != 3 or a.shape[1] < 1 or a.shape[2] < 1:
+            raise ValueError(f"{what}: the batch must be (B, H, W, 3) uint8, got {a.shape} {a.dtype}")
+        return np.ascontiguousarray(a)
+    imgs = [_check_image(im) for im in images_or_array]
+    if any(im.shape != imgs[0].shape for im in imgs):
+        raise ValueError(f"{what} needs images of one size; group them by shape")
+    return np.stack(imgs) if imgs else np.zeros((0, 1, 1, 3), np.uint8)
+
+
+def wand_select_batch(images_or_array, seeds, wand: Optional[Wand] = None, return_counts: bool = False, device="cuda"):
+    """Magic-wand selections of a batch (additive; ggc_wand_select).  images_or_array: (B, H, W, 3)
+    uint8 BGR, or a sequence of equally sized images; seeds: one None or (fg_points, bg_points) per image, (row, col)
+    pairs, or a packed (seeds, seed_ptr) pair (graph_builder.pack_hints).  A seed selects the pixels within the wand's
+    tolerance of its colour (and connected to it, if contiguous); foreground seeds add, background seeds subtract, an
+    image's later seed winning where selections overlap (its background seeds come after its foreground ones).
+    -> (B, H, W) uint8, 255 = selected; with return_counts=True also (B, 2) int32, the pixels decided by a foreground /
+    background seed."""
+    wand = _wand_args(wand)
+    imgs = _image_batch(images_or_array, "wand_select_batch")
+    b, h, w = imgs.shape[:3]
+    rows, ptr = _host_packed(seeds if seeds is not None else [None] * b, b, "seeds", 3, pack_hints, 2,
+                             lambda a: [(a[1], "seed_ptr", b, len(a[0]), 0)])
+    if b == 0 or len(rows) == 0:
+        z = np.zeros((b, h, w), np.uint8)
+        return (z, np.zeros((b, 2), np.int32)) if return_counts else z
+    from ._engine import get_engine
+    eng = get_engine(device)
+    d_rows, d_ptr = eng.upload_hints(rows, ptr)
+    _, sel, cnt = eng.wand_select(eng.to_device(imgs), d_rows, d_ptr, *wand.args(), counts=return_counts)
+    return (sel.cpu().numpy(), cnt.cpu().numpy()) if return_counts else sel.cpu().numpy()
+
+
+def wand_select(image: np.ndarray, fg_points, bg_points=(), wand: Optional[Wand] = None, device="cuda") -> np.ndarray:
+    """The magic-wand selection of one (H, W, 3) uint8 BGR image (additive; wand_select_batch): fg_points add, bg_points
+    subtract.  -> (H, W) uint8, 255 = selected."""
+    img = _check_image(image)
+    return wand_select_batch(img[None], [(fg_points if fg_points is not None else (), bg_points if bg_points is not None else ())],
+                             wand, device=device)[0]
+
+
+def paint_wand(mask_or_shape, image: np.ndarray, fg_points=(), bg_points=(), wand: Optional[Wand] = None, device="cuda") -> np.ndarray:
+    """Magic-wand selections painted into a GrabCut label mask (additive; ggc_wand_select), as
+    paint_strokes and paint_polygons paint theirs.  mask_or_shape: an (H, W) uint8 mask of GrabCut labels, or an (H, W)
+    shape for a mask that starts all probable background (2).  Every pixel a foreground seed's selection holds becomes
+    definite foreground (1), a background seed's definite background (0), background winning where the two overlap;
+    every other pixel keeps its label.  -> the painted (H, W) uint8 mask (a copy)."""
+    from ._engine import get_engine
+    wand = _wand_args(wand)
+    img = _check_image(image)
+    m = _mask_or_shape(mask_or_shape, "paint_wand")
+    if m.shape != img.shape[:2]:
+        raise ValueError(f"paint_wand: mask {m.shape} does not match the image {img.shape[:2]}")
+    rows, ptr = pack_hints([(fg_points if fg_points is not None else (), bg_points if bg_points is not None else ())])
+    if ptr[-1] == 0:
+        return m.copy()
+    eng = get_engine(device)
+    d_rows, d_ptr = eng.upload_hints(rows, ptr)
+    md = eng.to_device(m[None])
+    eng.wand_select(eng.to_device(img[None]), d_rows, d_ptr, *wand.args(), mask=md, select=False)
+    return md[0].cpu().numpy()
+
+
+@dataclass(frozen=True)
 class Outline:
     """One loop of a mask's outline (ggc_mask_outlines, include/ggc.h K1).  vertices: (n, 2) int32
     corners (row, col) of the corner lattice, pixel (y, x) being the square between corners (y, x) and (y+1, x+1), in loop
@@ -1157,16 +1259,22 @@ class _Hints:
     seg_ptr: Optional[np.ndarray] = None           # (B+1,) int32
     stroke_radius: int = 3
     polys: Optional[tuple] = None                  # (verts, poly_ptr, poly_label, image_ptr) int32; None: the batch has no polygon
+    wand_rows: Optional[np.ndarray] = None         # (K,3) int32 wand seeds in ggc_apply_hints' packing; None: the batch has none
+    wand_ptr: Optional[np.ndarray] = None          # (B+1,) int32
+    wand: "Optional[Wand]" = None                  # the options the seeds are selected with
 
     @staticmethod
     def of(hints, b: int, radius, region, as_prior, geodesic=None, strokes=None, stroke_radius=3,
-           polygons=None) -> "Optional[_Hints]":
+           polygons=None, wands=None, wand=None) -> "Optional[_Hints]":
         """hints: one None or (fg_points, bg_points) per image, or an already packed (hints, hint_ptr) pair; strokes: the
         same for brush strokes ((fg_strokes, bg_strokes) per image, or a packed (strokes, stroke_ptr) pair).
         None when no image has a click or a stroke, so that such a call launches exactly what a call without them
         launches; a batch without strokes has segs None and launches exactly what it did before strokes existed.
         polygons: one None or (fg_polygons, bg_polygons, lassos) per image, or a packed 4-tuple (pack_polygons); a batch
-        without polygons has polys None and launches exactly what it did before polygons existed."""
+        without polygons has polys None and launches exactly what it did before polygons existed.
+        wands: one None or (fg_points, bg_points) per image, the seeds of the magic wand, or a packed (seeds, seed_ptr)
+        pair; wand: their Wand (None: the defaults).  A batch without wand seeds has wand_rows None and launches exactly
+        what it did before the wand existed."""
         geodesic = _geodesic_args(geodesic, region)
         stroked = _host_packed(strokes, b, "strokes", 5, pack_strokes, 2, lambda a: [(a[1], "stroke_ptr", b, len(a[0]), 0)])
         segs, seg_ptr = stroked if stroked is not None and len(stroked[0]) else (None, None)
@@ -1175,21 +1283,24 @@ class _Hints:
             polys = None
         if segs is not None:
             stroke_radius = _check_stroke_radius(stroke_radius)
-        if hints is None and (segs is not None or polys is not None):      # strokes or polygons without clicks: an empty click list
+        wanded = _host_packed(wands, b, "wands", 3, pack_hints, 2, lambda a: [(a[1], "seed_ptr", b, len(a[0]), 0)])
+        wand_rows, wand_ptr = wanded if wanded is not None and len(wanded[0]) else (None, None)
+        wand = _wand_args(wand) if wand_rows is not None else None
+        if hints is None and (segs is not None or polys is not None or wand_rows is not None):   # areas or strokes without clicks: an empty click list
             hints = (np.zeros((0, 3), np.int32), np.zeros(b + 1, np.int32))
         if hints is None:
             return None
         if int(radius) < 0:
             raise ValueError(f"hint_radius must be >= 0, got {radius}")
         rows, ptr = _host_packed(hints, b, "hints", 3, pack_hints, 2, lambda a: [(a[1], "hint_ptr", b, len(a[0]), 0)])
-        if len(rows) == 0 and segs is None and polys is None:
+        if len(rows) == 0 and segs is None and polys is None and wand_rows is None:
             return None
         return _Hints(rows, ptr, int(radius), bool(region), bool(as_prior), geodesic, segs, seg_ptr,
-                      int(stroke_radius) if segs is not None else 3, polys)
+                      int(stroke_radius) if segs is not None else 3, polys, wand_rows, wand_ptr, wand)
 
     def chunk(self, lo: int, hi: int) -> "Optional[_Hints]":
         rows, ptr = _slice_csr(self.rows, self.ptr, lo, hi)
-        segs = seg_ptr = polys = None
+        segs = seg_ptr = polys = wand_rows = wand_ptr = None
         if self.segs is not None:                          # strokes are sliced by stroke_ptr, as clicks by hint_ptr
             segs, seg_ptr = _slice_csr(self.segs, self.seg_ptr, lo, hi)
             if len(segs) == 0:
@@ -1199,15 +1310,19 @@ class _Hints:
             q0, q1 = int(ip[lo]), int(ip[hi])
             if q1 > q0:
                 polys = (*_slice_csr(verts, pp, q0, q1), *_slice_csr(pl, ip, lo, hi))
-        if len(rows) == 0 and segs is None and polys is None:
+        if self.wand_rows is not None:                     # wand seeds are sliced by seed_ptr, as clicks by hint_ptr
+            wand_rows, wand_ptr = _slice_csr(self.wand_rows, self.wand_ptr, lo, hi)
+            if len(wand_rows) == 0:
+                wand_rows = wand_ptr = None
+        if len(rows) == 0 and segs is None and polys is None and wand_rows is None:
             return None
         return _Hints(rows, ptr, self.radius, self.region, self.as_prior, self.geodesic, segs, seg_ptr, self.stroke_radius,
-                      polys)
+                      polys, wand_rows, wand_ptr, self.wand if wand_rows is not None else None)
 
     @property
     def has_clicks(self) -> bool:
         """The batch has a click or a stroke: what the click paths (disks, regions, prior columns, geodesic) work on.
-        Polygons are areas and feed none of them."""
+        Polygons and wand seeds are areas and feed none of them."""
         return len(self.rows) > 0 or self.segs is not None
 
     def clicked_images(self, h: int, w: int) -> np.ndarray:
@@ -1516,9 +1631,10 @@ class GCNGrabCutPipeline:
     # ------------------------------------------------------------ batched, device resident
     def _front(self, eng, bgr, threshold_fg, threshold_bg, edge_aware, filter_radius, tick=None, timing=None, hints=None):
         """Stages 1-3 on the current stream: colour prep, SLIC, graph, network, trimap, seeding, then the user's clicks
-        (hints: a _Hints or None).  Polygons (ggc_apply_polygons) are painted after the seeding and before strokes and
-        clicks, so a stroke or click inside an excluded area still wins, being the more specific edit; they are areas,
-        not clicks, and do not feed hint_region, hints_as_prior or the geodesic sources.  -> (seg, graphs, probs, trimap)"""
+        (hints: a _Hints or None).  Polygons (ggc_apply_polygons), then wand selections (ggc_wand_select), are painted
+        after the seeding and before strokes and clicks, so a stroke or click inside an excluded area still wins, being
+        the more specific edit; they are areas, not clicks, and do not feed hint_region, hints_as_prior or the geodesic
+        sources.  -> (seg, graphs, probs, trimap)"""
         cfg = self.sp_config
         t = tick() if tick else 0.0
         lab, hsv, gray, grad = eng.preprocess(bgr)
@@ -1533,7 +1649,8 @@ class GCNGrabCutPipeline:
             self.model.eval()
         prior = graphs.x[:, 16:19]
         polys = None if hints is None else hints.polys
-        if hints is not None and not hints.has_clicks:     # polygons only: the click paths launch nothing
+        wands = None if hints is None or hints.wand_rows is None else (hints.wand_rows, hints.wand_ptr, hints.wand)
+        if hints is not None and not hints.has_clicks:     # areas only: the click paths launch nothing
             hints = None
         dev = None                             # the device copies _paint_hints works on
         if hints is not None:
@@ -1553,14 +1670,17 @@ class GCNGrabCutPipeline:
         if timing is not None:
             timing["gcn_inference"] = tick() - t
         trimap = eng.seed_from_prior(trimap, prior, graphs.node_ptr, seg, 0.1)
-        self._paint_hints(eng, trimap, polys, hints, dev, bgr, seg, graphs.node_ptr)
+        self._paint_hints(eng, trimap, polys, hints, dev, bgr, seg, graphs.node_ptr, wands)
         return seg, graphs, probs, trimap
 
     @staticmethod
-    def _paint_hints(eng, trimap, polys, hints, dev, bgr, seg, node_ptr):
-        """The user's edits as hard constraints on the seeded trimap, in place: polygons, then the clicks and strokes."""
+    def _paint_hints(eng, trimap, polys, hints, dev, bgr, seg, node_ptr, wands=None):
+        """The user's edits as hard constraints on the seeded trimap, in place: polygons, then wand selections, then the
+        strokes and clicks.  Areas come first and the more precise tools go on top."""
         if polys is not None:                  # areas first: lassos, then fills; strokes and clicks are painted over them
             eng.apply_polygons(trimap, *eng.upload_polygons(*polys))
+        if wands is not None:                  # (seeds, seed_ptr, Wand) on the host; the guide is the caller's BGR batch, never gc_image
+            eng.wand_select(bgr, *eng.upload_hints(wands[0], wands[1]), *wands[2].args(), mask=trimap, select=False)
         if hints is None:
             return
         hint_rows, hint_ptr, all_rows, all_ptr, segs, seg_ptr = dev
@@ -1646,7 +1766,7 @@ class GCNGrabCutPipeline:
                              hints_as_prior: bool = False, return_state: bool = False, matte: bool = False,
                              matte_radius: int = MATTE_RADIUS, matte_eps: float = MATTE_EPS, full_bgr=None,
                              foreground=False, full_cut=False, geodesic=False, strokes=None, stroke_radius: int = 3,
-                             polygons=None, scissors=None, scissors_options=None) -> dict:
+                             polygons=None, scissors=None, scissors_options=None, wands=None, wand=None) -> dict:
         """bgr: (B,H,W,3) uint8 tensor on the pipeline's device.  Returns device tensors.
 
         matte=True (additive) also returns "alpha" (B,H,W) float32, the soft matte of the cleaned mask (alpha_matte with
@@ -1715,6 +1835,15 @@ class GCNGrabCutPipeline:
         result equals that of passing trace_boundary's polygons as lassos.  An outline of fewer than 3 vertices is a
         ValueError.  A batch without scissors launches exactly what it did before.
 
+        Magic wand (additive): wands is None, a list with one None or (fg_points, bg_points) per image
+        ((row, col) seeds), or a packed (seeds, seed_ptr) pair (graph_builder.pack_hints); wand is a Wand (None: its
+        defaults).  On the trimap GrabCut starts from, every pixel that a seed selects on bgr, the working-size BGR image
+        and never GrabCutConfig's colour-space image (ggc_wand_select), becomes definite foreground / background, an
+        image's later seed winning, background seeds after foreground ones.  Selections are painted after the polygons
+        and before strokes and clicks.  Wand seeds are areas, not clicks: they do not feed hint_region, hints_as_prior or
+        the geodesic sources.  A batch without wand seeds launches exactly what it did before, and an image without them
+        in a batch that has some gets the outputs it gets without them, bit for bit.
+
         Large batches run as a software pipeline (additive, same results): the batch is cut into `chunks` contiguous
         chunks; the front stages of chunk k+1 run on the caller's stream while the GrabCut / clean-up of chunk k runs on a
         lane of its own (private context, stream and host thread).  Images are independent and image b keeps seed + b, so
@@ -1727,7 +1856,8 @@ class GCNGrabCutPipeline:
         if scissors is not None:                   # traced once for the whole batch; from here on they are lassos
             polygons = _merge_lassos(_packed_polygons(polygons, b),
                                      _trace_closed(eng, bgr, scissors, _scissors_args(scissors_options)))
-        hints = _Hints.of(hints, b, hint_radius, hint_region, hints_as_prior, geodesic, strokes, stroke_radius, polygons)
+        hints = _Hints.of(hints, b, hint_radius, hint_region, hints_as_prior, geodesic, strokes, stroke_radius, polygons,
+                          wands, wand)
         plan = _OutputPlan.of(self, bgr.shape, None if full_bgr is None else full_bgr.shape, compose=compose,
                               min_area_ratio=min_area_ratio, keep_largest=keep_largest, matte=matte, matte_radius=matte_radius,
                               matte_eps=matte_eps, foreground=foreground, full_cut=full_cut)
@@ -1868,12 +1998,14 @@ class GCNGrabCutPipeline:
         return out
 
     def segment_batch(self, images: Sequence[np.ndarray], hints=None, full_images=None, strokes=None, polygons=None,
-                      scissors=None, **kwargs) -> list[SegmentationResult]:
+                      scissors=None, wands=None, **kwargs) -> list[SegmentationResult]:
         """Segment equally sized BGR images as one batch (additive API).  hints: one None or (fg_points, bg_points) per
         image, with hint_radius / hint_region / hints_as_prior / geodesic among kwargs (segment_batch_device).  strokes:
         one None or (fg_strokes, bg_strokes) per image, with stroke_radius among kwargs (segment_batch_device).  polygons:
         one None or (fg_polygons, bg_polygons, lassos) per image (segment_batch_device).  scissors: one None, anchor list
-        or sequence of anchor lists per image, with scissors_options among kwargs (segment_batch_device).  full_images
+        or sequence of anchor lists per image, with scissors_options among kwargs (segment_batch_device).  wands: one None
+        or (fg_points, bg_points) of magic-wand seeds per image, with wand=Wand(...) among kwargs (segment_batch_device).
+        full_images
         (additive): the same images at one larger size each, (H1, W1, 3) uint8 BGR; every result's `full` then holds the
         outputs at that size (segment_batch_device's full_bgr).  foreground=True | ForegroundColours(...) among kwargs
         (with a matte) fills every result's foreground and rgba_clean.  full_cut=True | FullCut(...) among kwargs (with
@@ -1904,6 +2036,8 @@ class GCNGrabCutPipeline:
             kwargs["polygons"] = polygons
         if scissors is not None:
             kwargs["scissors"] = scissors
+        if wands is not None:
+            kwargs["wands"] = wands
         out = self.segment_batch_device(bgr, timing=timing, hints=hints, full_bgr=full_bgr, **kwargs)
         out.update({k: out[k].cpu() for k in _REFERENCE_FIELDS + _ADDITIVE_FIELDS if k in out})      # one copy per output, not one per image
         per_image = {k: v / len(imgs) for k, v in timing.items()}
@@ -2042,7 +2176,8 @@ class GCNGrabCutPipeline:
                 full_image: Optional[np.ndarray] = None, foreground=False, full_cut=False,
                 geodesic=False, fg_strokes=None, bg_strokes=None, stroke_radius: int = 3,
                 lasso=None, fg_polygons=None, bg_polygons=None, scissors=None,
-                scissors_options: Optional[Scissors] = None) -> SegmentationResult:
+                scissors_options: Optional[Scissors] = None, fg_wand=None, bg_wand=None,
+                wand: Optional[Wand] = None) -> SegmentationResult:
         """Full pipeline on one BGR image (reference pipeline.py:265-352).
 
         Additive: fg_points / bg_points are user clicks, (row, col) pairs, applied as hard constraints on the trimap
@@ -2061,7 +2196,10 @@ class GCNGrabCutPipeline:
         fg_polygons / bg_polygons are filled areas of definite labels, all before strokes and clicks
         (segment_batch_device's polygons); scissors, one list of (row, col) anchors on the object's outline or a
         sequence of such lists, is traced along the image's edges into closed outlines that join the lassos
-        (intelligent scissors with scissors_options, a Scissors; segment_batch_device's scissors)."""
+        (intelligent scissors with scissors_options, a Scissors; segment_batch_device's scissors); fg_wand / bg_wand are
+        magic-wand seeds, (row, col) pairs: what each selects on the image with `wand` (a Wand; None: its defaults)
+        becomes definite foreground / background, after the polygons and before strokes and clicks
+        (segment_batch_device's wands)."""
         image = _check_image(image)
         full = None if full_image is None else _check_image(full_image)
         _OutputPlan.of(self, (1, *image.shape), None if full is None else (1, *full.shape), min_area_ratio=min_area_ratio,
@@ -2075,13 +2213,16 @@ class GCNGrabCutPipeline:
             [(() if fg_strokes is None else fg_strokes, () if bg_strokes is None else bg_strokes)]
         polygons = None if lasso is None and fg_polygons is None and bg_polygons is None else \
             [(() if fg_polygons is None else fg_polygons, () if bg_polygons is None else bg_polygons, lasso_list(lasso))]
+        wands = None if fg_wand is None and bg_wand is None else \
+            [(() if fg_wand is None else fg_wand, () if bg_wand is None else bg_wand)]
         out = self.segment_batch_device(self._eng.to_device(image[None]), threshold_fg, threshold_bg, refine_iters,
                                         min_area_ratio, keep_largest, edge_aware, filter_radius, timing=timing,
                                         hints=hints, hint_radius=hint_radius, hint_region=hint_region,
                                         hints_as_prior=hints_as_prior, matte=matte, matte_radius=matte_radius,
                                         matte_eps=matte_eps, full_bgr=full_bgr, foreground=foreground, full_cut=full_cut,
                                         geodesic=geodesic, strokes=strokes, stroke_radius=stroke_radius, polygons=polygons,
-                                        scissors=None if scissors is None else [scissors], scissors_options=scissors_options)
+                                        scissors=None if scissors is None else [scissors], scissors_options=scissors_options,
+                                        wands=wands, wand=wand)
         return _result(out, 0, image, timing)
 
     def segment_bbox(self, image: np.ndarray, bbox: tuple[int, int, int, int], matte: bool = False,
@@ -2130,6 +2271,34 @@ class GCNGrabCutPipeline:
         if not traced:
             raise ValueError("segment_scissors needs at least one anchor list")
         return self.segment_lasso(image, traced, **kwargs)
+
+    def segment_wand(self, image: np.ndarray, bg_points, fg_points=(), wand: Optional[Wand] = None, matte: bool = False,
+                     matte_radius: int = MATTE_RADIUS, matte_eps: float = MATTE_EPS, full_image: Optional[np.ndarray] = None,
+                     foreground=False, full_cut=False) -> SegmentationResult:
+        """Classical GrabCut from magic-wand seeds (additive; the sibling of segment_lasso, no network).
+        bg_points: (row, col) seeds on the backdrop; fg_points: optional seeds on the object.  The mask starts as definite
+        background on what the background seeds select, definite foreground on what the foreground seeds select and
+        probable foreground elsewhere (GrabCut.run_with_wand: ggc_wand_select, then run_with_trimap).  A ValueError if
+        no pixel is selected as background, or every pixel is.  The optional matte / full-image arguments are
+        segment_bbox's."""
+        image = _check_image(image)
+        full = None if full_image is None else _check_image(full_image)
+        plan = _OutputPlan.of(self, (1, *image.shape), None if full is None else (1, *full.shape), matte=matte,
+                              matte_radius=matte_radius, matte_eps=matte_eps, foreground=foreground, full_cut=full_cut)
+        gc = GrabCut(image, self.gc_config, device=self.device)
+        trimap = gc.wand_trimap(bg_points, fg_points, wand)
+        binary_mask = gc.run_with_trimap(trimap)
+        H, W = image.shape[:2]
+        extra = {}
+        if plan.mat or plan.cfm or full is not None:   # GrabCut's mask is final, as in segment_bbox
+            eng = self._eng
+            stage = _OutputStage(eng, plan, eng.to_device(image[None]), None if full is None else eng.to_device(full[None]),
+                                 final_mask=eng.to_device(np.ascontiguousarray(binary_mask, np.uint8)[None]))
+            stage.from_mask(eng, 0, 1)
+            extra = _optional_results(stage.out, 0)
+        return SegmentationResult(image=image, binary_mask=binary_mask, trimap=trimap,
+                                  segments=np.zeros((H, W), dtype=np.int32), overlay=gc.overlay_mask(),
+                                  rgba=gc.crop_foreground(), **extra)
 
     def segment_lasso(self, image: np.ndarray, polygon, matte: bool = False, matte_radius: int = MATTE_RADIUS,
                       matte_eps: float = MATTE_EPS, full_image: Optional[np.ndarray] = None, foreground=False,

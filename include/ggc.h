@@ -39,6 +39,7 @@
  *   GGC_AGG_DIRECT=1              GCNConv gather straight from L2 instead of the graph-resident kernel
  *   GGC_SLIC_SEQ_CONNECTIVITY=1   literal one-thread-per-image replay of skimage's connectivity pass (A/B reference)
  *   GGC_MATTE_EVAL_LEVELS=1|2|5|10   threshold levels that ggc_matte_errors labels per pass (default: 10 while its maps fit 4 GiB, else 1)
+ *   GGC_WAND_SEEDS_PER_PASS=n     seeds that ggc_wand_select labels per pass, 1..4096 (default: as many as keep its maps within 1 GiB)
  * The Python binding adds GGC_HIP_LIBRARY=<path> (load another build of the library, tools/build_variant.sh).
  */
 #ifndef GGC_H
@@ -51,7 +52,9 @@
 extern "C" {
 #endif
 
-#define GGC_VERSION 409 /* 0.4.9: ggc_mask_distance, ggc_modify_mask (the exact squared Euclidean distance transform of a mask, signed, and
+#define GGC_VERSION 410 /* 0.4.10: ggc_wand_select (magic wand: flood select by colour tolerance from seed pixels, contiguous or not, as
+                                  GrabCut labels, a selection plane and counts; additive, no existing entry changes);
+                           0.4.9: ggc_mask_distance, ggc_modify_mask (the exact squared Euclidean distance transform of a mask, signed, and
                                   grow / shrink / border / open / close / trimap as thresholds of it; additive, no existing entry changes);
                            0.4.8: ggc_mask_outlines (the exact vector contours of a mask: crack-following loops on the corner lattice, as
                                   vertices in ggc_apply_polygons' packing, with area, perimeter and outer loop; additive, no existing
@@ -570,6 +573,42 @@ int ggc_apply_polygons(ggc_ctx* ctx, ggc_stream stream, int B, int H, int W, con
 int ggc_trace_paths(ggc_ctx* ctx, ggc_stream stream, int B, int H, int W, const uint8_t* bgr, const int32_t* anchors,
                     const int32_t* path_ptr, const int32_t* path_closed, const int32_t* image_ptr, int Q, int margin, int edge_cap,
                     int smooth, int32_t* vert_ptr_out, int32_t* verts_out, int64_t capacity);
+
+/* H5 — magic wand (additive): a seed selects the pixels that look like it, where every other tool defines a region by geometry
+ * or by a path cost.  One exact integer definition; no float and no division is involved anywhere.
+ *   bgr       [dev] u8  [B,H,W,3] the images
+ *   seeds     [dev] i32 [K,3] = (row, col, label), label 0 = background / subtract, nonzero = foreground / add
+ *   seed_ptr  [dev] i32 [B+1]  image b owns seeds[seed_ptr[b] .. seed_ptr[b+1]); seed_ptr[0] = 0, non-decreasing
+ *             (ggc_apply_hints' packing).  A seed outside its image is ignored.
+ *   tolerance 0 .. 255      connectivity 4, 8 or 0 = not contiguous ("select similar")      sample n in {1, 3, 5}
+ *   mask      [dev] u8  [B,H,W] in/out GrabCut labels, may be NULL
+ *   select    [dev] u8  [B,H,W] out, may be NULL
+ *   counts    [dev] i32 [B,2]   out, may be NULL                          (at least one of the three must be given)
+ * Reference colour of seed s at (r, c): ref_c(s) = sum of the n x n bytes I_c(clamp(r+dy, 0, H-1), clamp(c+dx, 0, W-1)), |dy|, |dx|
+ * <= n / 2: a box sum with replicated border, as H1's guide.
+ * Match: match(p, s) iff for all three channels |n^2 I_c(p) - ref_c(s)| <= n^2 tolerance: the max-channel metric against the
+ * window's mean, without the division.  The largest value is 25 * 255 = 6375: everything fits int32.
+ * Selection: Sel(s) = { p : match(p, s) } when connectivity == 0; otherwise the 4- or 8-connected component, within that set, of
+ * the seed's own pixel.  If the seed's own pixel does not match its reference (possible with sample > 1), Sel(s) is empty.
+ * Combination, per image: a pixel is DECIDED by the last seed of its image, in seed order, whose Sel holds it; by index and
+ * not by timing.
+ *   mask     a decided pixel becomes GGC_FGD or GGC_BGD; an undecided pixel is neither read nor written
+ *   select   written for every pixel: 255 if a foreground seed decided it, 0 if a background seed did or nothing did (a later
+ *            background seed subtracts)
+ *   counts   [b] = (pixels decided by a foreground seed, by a background seed), written for every image, by integer atomics
+ * The result is a set defined without reference to any schedule; every image's outputs equal those of its single-image call
+ * bit for bit; the pass size (below) never changes an output.
+ * B == 0 or K = seed_ptr[B] == 0 is a no-op: select and counts are not written.  Otherwise, before any launch: B, H or W outside
+ * 1..65535 or H*W beyond int32 is GGC_E_SHAPE; a tolerance, connectivity or sample outside its set, a NULL bgr or seed_ptr, NULL
+ * seeds with K > 0, seed_ptr[0] != 0, a decreasing seed_ptr or all three outputs NULL is GGC_E_INVALID_ARG.
+ * Schedule: contiguous selections label one plane per live seed by union-find (csrc/ggc_ccl.h), S seeds per pass: as many as
+ * keep the parent maps (4 bytes per pixel per seed) within 1 GiB, at least one, unless GGC_WAND_SEEDS_PER_PASS fixes S; passes
+ * run in seed order.  Scratch: those maps, one byte per pixel of the batch, 24 bytes per seed.  connectivity == 0 is one
+ * streaming launch without scratch planes.  SYNCHRONISES the stream: seed_ptr and the seeds are read back, the live seeds'
+ * table is uploaded. */
+int ggc_wand_select(ggc_ctx* ctx, ggc_stream stream, int B, int H, int W, const uint8_t* bgr, const int32_t* seeds,
+                    const int32_t* seed_ptr, int tolerance, int connectivity, int sample, uint8_t* mask, uint8_t* select,
+                    int32_t* counts);
 
 /* C0 — next simulated click per image (additive; the standard NoC protocol of interactive segmentation).
  *   pred [dev] u8  [B,H,W]  current binary mask (nonzero = foreground)

@@ -10,6 +10,7 @@ Same command line as the reference's inference.py (flags :26-56, outputs :146-15
     python3 inference.py --image cat.jpg --bg-stroke "40,10 40,200 90,260" --stroke-radius 4   # a brush stroke of three vertices
     python3 inference.py --image cat.jpg --lasso "20,30 20,300 260,300 260,30"   # everything outside the outline is background
     python3 inference.py --image cat.jpg --scissors "40,60 30,220 200,260 230,80"   # four anchors on the outline, traced into a lasso
+    python3 inference.py --image cat.jpg --bg-wand "0,0 0,399" --wand-tolerance 24 --save mask selection   # the backdrop by magic wand
     python3 inference.py --image cat.jpg --save mask alpha cutout          # soft edges: alpha matte and cut-out
     python3 inference.py --image big.jpg --full-res --save mask cutout     # outputs at the photo's own size
     python3 inference.py --image big.jpg --full-res --full-mask cut --save mask   # ... the mask cut again on the photo's pixels
@@ -51,8 +52,9 @@ def build_parser() -> argparse.ArgumentParser:
                         help="Drop mask components smaller than this fraction of the image")
     parser.add_argument("--keep-largest", action="store_true", help="Keep only the largest connected component")
     parser.add_argument("--save", nargs="+", default=["mask", "overlay"],
-                        choices=["mask", "overlay", "rgba", "trimap", "alpha", "cutout", "outlines", "modified"],
-                        help="Which outputs to write (alpha / cutout: the soft matte and the BGRA cut-out with it)")
+                        choices=["mask", "overlay", "rgba", "trimap", "alpha", "cutout", "outlines", "modified", "selection"],
+                        help="Which outputs to write (alpha / cutout: the soft matte and the BGRA cut-out with it; "
+                             "selection: what the --fg-wand / --bg-wand seeds select, as <prefix>_selection.png)")
     # additive: the mask's exact vector outlines (ggc_mask_outlines), written as <prefix>_outlines.json by --save outlines
     parser.add_argument("--outline-connectivity", type=int, choices=[4, 8], default=8,
                         help="--save outlines: 8 joins diagonal foreground pixels into one loop (as the mask clean-up "
@@ -93,6 +95,20 @@ def build_parser() -> argparse.ArgumentParser:
                         help="Filled foreground polygon of at least 3 vertices in original-image pixels (repeatable; needs --image)")
     parser.add_argument("--bg-polygon", action="append", type=_polygon, default=[], metavar='"ROW,COL ROW,COL ..."',
                         help="Filled background polygon of at least 3 vertices in original-image pixels (repeatable; needs --image)")
+    # additive: the magic wand (ggc_wand_select): seeds select the pixels that look like them, single-image runs only
+    parser.add_argument("--fg-wand", action="append", type=_stroke, default=[], metavar='"ROW,COL ROW,COL ..."',
+                        help="Foreground magic-wand seeds in original-image pixels: what each selects becomes definite "
+                             "foreground (repeatable; needs --image)")
+    parser.add_argument("--bg-wand", action="append", type=_stroke, default=[], metavar='"ROW,COL ROW,COL ..."',
+                        help="Background magic-wand seeds in original-image pixels: what each selects becomes definite "
+                             "background, over the foreground seeds' (repeatable; needs --image)")
+    parser.add_argument("--wand-tolerance", type=int, default=32,
+                        help="How far a pixel's colour may lie from a seed's, 0..255, in the channel that differs most")
+    parser.add_argument("--wand-connectivity", type=int, choices=[4, 8, 0], default=8,
+                        help="Neighbours through which a selection spreads from its seed; 0 selects every similar pixel, "
+                             "connected to the seed or not")
+    parser.add_argument("--wand-sample", type=int, choices=[1, 3, 5], default=1,
+                        help="Side of the window around a seed whose mean colour is the seed's colour")
     # additive: intelligent scissors (ggc_trace_paths): a few anchors on the outline, traced into a lasso
     parser.add_argument("--scissors", action="append", type=_polygon, default=[], metavar='"ROW,COL ROW,COL ..."',
                         help="Anchors on the object's outline, at least 3, in order and in original-image pixels: they are "
@@ -190,6 +206,22 @@ def _modify_step(text: str):
         raise argparse.ArgumentTypeError(f"--modify {text!r}: {e}")
 
 
+def wand_options(parser, args):
+    """The Wand of --wand-* when the run has wand seeds, else None; parser.error on options that do not fit together."""
+    seeds = bool(args.fg_wand or args.bg_wand)
+    if seeds and not args.image:
+        parser.error("--fg-wand / --bg-wand are seeds on one image: use them with --image, not --input")
+    if "selection" in args.save and not seeds:
+        parser.error("--save selection writes what --fg-wand / --bg-wand seeds select: give at least one")
+    if not seeds:
+        return None
+    from src.gcn_grabcut import Wand
+    try:
+        return Wand(args.wand_tolerance, args.wand_connectivity or 8, args.wand_connectivity != 0, args.wand_sample)
+    except ValueError as e:
+        parser.error(str(e))
+
+
 def outlines_document(shape, outlines, connectivity: int) -> dict:
     """What --save outlines writes: the loops of a mask of `shape` on its corner lattice, (row, col) vertices with area,
     perimeter and outer loop each, and all of them as one SVG path (x = col, y = row) for fill-rule="evenodd"."""
@@ -273,6 +305,7 @@ def main() -> None:
             scissors_options = Scissors(args.scissors_margin, args.scissors_edge_cap, args.scissors_smooth)
         except ValueError as e:
             parser.error(str(e))
+    wand = wand_options(parser, args)
     if bool(args.modify) != ("modified" in args.save):
         parser.error("--modify steps are written by --save modified: give both or neither")
     if not 0 <= args.stroke_radius <= 16384:
@@ -369,7 +402,7 @@ def main() -> None:
             t0 = time.perf_counter()
             hint_kw = {}
             polygons = args.lasso or args.fg_polygon or args.bg_polygon
-            if args.fg_point or args.bg_point or args.fg_stroke or args.bg_stroke or polygons or args.scissors:   # --image only: one chunk of one image
+            if args.fg_point or args.bg_point or args.fg_stroke or args.bg_stroke or polygons or args.scissors or wand:   # --image only: one chunk of one image
                 from PIL import Image
                 path, image, _ = chunk[0]
                 with Image.open(path) as im:
@@ -389,6 +422,10 @@ def main() -> None:
                 if args.scissors:
                     hint_kw.update(scissors=[[scale_points(a, orig_hw, image.shape[:2]) for a in args.scissors]],
                                    scissors_options=scissors_options)
+                if wand is not None:
+                    wand_seeds = (scale_points([p for s in args.fg_wand for p in s], orig_hw, image.shape[:2]),
+                                  scale_points([p for s in args.bg_wand for p in s], orig_hw, image.shape[:2]))
+                    hint_kw.update(wands=[wand_seeds], wand=wand)
                 if args.hint_mode == "geodesic":
                     from src.gcn_grabcut import GeodesicHints
                     hint_kw.update(geodesic=GeodesicHints(args.geodesic_radius, args.hint_gamma))
@@ -433,6 +470,9 @@ def main() -> None:
                     loops = result.outlines(args.outline_connectivity, full=result.full is not None)
                     with open(f"{stem}_outlines.json", "w") as f:
                         json.dump(outlines_document(out.binary_mask.shape, loops, args.outline_connectivity), f)
+                if "selection" in args.save:                # the wand's own selection, at the size the image was segmented at
+                    from src.gcn_grabcut import wand_select
+                    _write_png(f"{stem}_selection.png", wand_select(result.image, *wand_seeds, wand, device=args.device))
                 if "modified" in args.save:                 # the mask file written above after the --modify steps
                     modified = result.modified(*args.modify, full=result.full is not None)
                     _write_png(f"{stem}_modified.png", modified if modified.max(initial=0) > 1 else modified * 255)
