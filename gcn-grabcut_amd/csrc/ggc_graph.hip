@@ -7,13 +7,16 @@
 //    lanes, one per accumulator, that walks the region's bounding box in raster
 //    order (SLIC regions are compact, so the box is a few hundred pixels).
 //    Deterministic, no float atomics.
-//  * np.unique(lo*N+hi, return_counts=True) becomes a dense per-image N x N
-//    int32 matrix filled with integer atomics (exact, order independent) and
-//    read back row-major with wave ballot/prefix compaction, which yields the
-//    pairs already sorted by code.  288 GB of HBM makes the dense form cheap:
-//    256 images x 700^2 x 4 B = 0.5 GB.
-//  * the non-local k-NN (argpartition) is one wave per node over an LDS row of
-//    distances: k rounds of wave arg-min with ties to the lowest index.
+//  * np.unique(lo*N+hi, return_counts=True): an image's pairs and their counts
+//    are collected in one CU's LDS (a hash table of integer atomics: exact,
+//    order independent) and ranked through an N x N bitset, which yields them
+//    sorted by code (k_region_scan, k_topology, k_emit).  Images that do not
+//    fit the tables, small batches and GGC_GRAPH_ONCHIP=0 take the form this
+//    replaced: a dense per-image N x N int32 matrix in HBM, read back row-major
+//    with wave ballot/prefix compaction (256 images x 700^2 x 4 B = 0.5 GB).
+//  * the non-local k-NN (argpartition): on chip a thread per node that keeps
+//    its k best in registers, dense a wave per node over an LDS row of
+//    distances with k rounds of wave arg-min; ties go to the lowest index.
 //  * ggc_graph_count synchronises twice (node counts, pair counts) so that the
 //    packed outputs can be sized exactly; ggc_graph_fill only copies.
 #include "ggc_internal.h"
@@ -425,6 +428,382 @@ __global__ void __launch_bounds__(256) k_extract(GDims d, const int32_t* __restr
     }
 }
 
+// ---- on-chip topology: the same pair lists without the dense matrix
+// An image's region topology fits in one CU's LDS.  k_region_scan reads the label map and the gradient once and keeps the
+// boxes, the frame counts and an open-addressing table of (lo*Nmax+hi, shared-boundary count) in LDS; all of it is integer
+// min/max/add or a float max, so the order of the pixels does not matter.  k_topology then ranks the pairs through an
+// N x N bitset, which is the dense matrix's row-major walk (the order np.unique gives) at one bit per entry, runs the k-NN
+// on mean-Lab staged in LDS, and writes both sorted lists; k_emit computes the pair features from the lists.
+// What does not fit (N, k, or the number of distinct pairs) goes through the dense kernels above.
+constexpr int OC_NMAX = 704;                        // regions per image (a multiple of 64)
+constexpr int OC_WPR = OC_NMAX / 32;                // bitset words per row
+constexpr int OC_SLOT_BITS = 13;
+constexpr int OC_SLOTS = 1 << OC_SLOT_BITS;         // pair table slots ...
+constexpr int OC_PAIRS = OC_SLOTS / 4 * 3;          // ... of which at most this many are taken (distinct adjacent pairs per image)
+constexpr int OC_KMAX = 8;                          // non-local neighbours per node
+constexpr int OC_NL = OC_NMAX * OC_KMAX;            // non-local pairs per image
+constexpr int OC_THREADS = 1024;
+constexpr int OC_WAVES = OC_THREADS / 64;
+constexpr int OC_BANDS_MAX = 8;                     // workgroups that share one image's rows when the batch is small
+constexpr int OC_MIN_BATCH = 24;                    // smaller batches keep the dense kernels
+constexpr uint32_t OC_EMPTY = 0xFFFFFFFFu;
+constexpr uint32_t OC_NONE = 0xFFFFu;
+constexpr size_t OC_LDS_SCAN = (size_t)OC_SLOTS * 8 + (size_t)OC_NMAX * 20 + 64;
+constexpr size_t OC_LDS_TOPO = (size_t)OC_NMAX * OC_WPR * 4 + (size_t)OC_NMAX * 12 + (size_t)(OC_NMAX + 1) * 4 +
+                               (size_t)OC_PAIRS * 4 + (size_t)OC_NL * 2 + 256;
+static_assert(OC_LDS_SCAN <= 160 * 1024 && OC_LDS_TOPO <= 160 * 1024, "the on-chip tables must fit one CU's LDS");
+static_assert((size_t)OC_NMAX * OC_NMAX < OC_EMPTY && OC_NMAX < (int)OC_NONE && OC_NMAX <= OC_THREADS, "pair keys and node ids must stay below their empty marks");
+
+struct OnchipLists {
+    uint32_t* band_key; uint32_t* band_cnt;   // [B][bands][OC_PAIRS] unsorted (key, count) of each band of rows
+    int32_t* band_n;                          // [B][bands]
+    uint32_t* adj_key; uint32_t* adj_cnt;     // [B][OC_PAIRS] ascending by key, counts summed over the bands
+    uint32_t* nl_key;                         // [B][OC_NL] ascending by key
+};
+
+__global__ void __launch_bounds__(OC_THREADS) k_region_scan(GDims d, int bands, const int32_t* __restrict__ seg,
+                                                            const float* __restrict__ grad, int4* __restrict__ bbox,
+                                                            int32_t* __restrict__ border, uint32_t* __restrict__ gmax,
+                                                            uint32_t* __restrict__ maxima, int32_t* __restrict__ totals,
+                                                            OnchipLists L) {
+    __shared__ uint32_t s_key[OC_SLOTS], s_cnt[OC_SLOTS];
+    __shared__ int s_y0[OC_NMAX], s_y1[OC_NMAX], s_x0[OC_NMAX], s_x1[OC_NMAX], s_border[OC_NMAX];
+    __shared__ uint32_t s_gmax;
+    __shared__ int s_new, s_out, s_over;
+    const int band = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
+    const int lane = tid & 63, wave = tid >> 6;
+    const int H = d.H, W = d.W, Nmax = d.Nmax;
+    for (int i = tid; i < OC_SLOTS; i += OC_THREADS) { s_key[i] = OC_EMPTY; s_cnt[i] = 0; }
+    for (int i = tid; i < Nmax; i += OC_THREADS) { s_y0[i] = INT32_MAX; s_y1[i] = 0; s_x0[i] = INT32_MAX; s_x1[i] = 0; s_border[i] = 0; }
+    if (tid == 0) { s_gmax = 0; s_new = 0; s_out = 0; s_over = 0; }
+    __syncthreads();
+
+    auto insert = [&](uint32_t key, int n) {
+        if (__hip_atomic_load(&s_over, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) return;   // the batch takes the dense path anyway
+        uint32_t h = (key * 2654435761u) >> (32 - OC_SLOT_BITS);
+        for (int t = 0; t < OC_SLOTS; ++t) {
+            const uint32_t prev = atomicCAS(&s_key[h], OC_EMPTY, key);
+            if (prev == OC_EMPTY && atomicAdd(&s_new, 1) >= OC_PAIRS) atomicOr(&s_over, 1);
+            if (prev == OC_EMPTY || prev == key) { atomicAdd(&s_cnt[h], (uint32_t)n); return; }
+            h = (h + 1) & (OC_SLOTS - 1);
+        }
+        atomicOr(&s_over, 1);
+    };
+    // lanes next to each other that hold the same key form a run; its first lane adds the run's length once
+    auto add_runs = [&](uint32_t key) {
+        const uint32_t kl = __shfl_up(key, 1, 64);
+        const bool has = key != OC_EMPTY;
+        const unsigned long long hm = __ballot(has);
+        if (!hm) return;
+        const unsigned long long starts = __ballot(has && (lane == 0 || kl != key));
+        if (has && ((starts >> lane) & 1ull)) {
+            const unsigned long long stop = (starts | ~hm) >> lane >> 1;
+            insert(key, stop ? __ffsll((long long)stop) : 64 - lane);
+        }
+    };
+    auto key_of = [&](bool on, int u, int v) {
+        return on && u != v ? (uint32_t)(min(u, v) * Nmax + max(u, v)) : OC_EMPTY;
+    };
+
+    const int rows_per = (H + bands - 1) / bands;
+    const int y_beg = min(band * rows_per, H), y_end = min(y_beg + rows_per, H);
+    const int nseg = (W + 63) / 64;
+    const int items = (y_end - y_beg) * nseg;
+    const int32_t* sg = seg + (size_t)b * H * W;
+    const float* gr = grad + (size_t)b * H * W;
+    // what one 64-pixel row segment needs from memory; three segments of loads are in flight per wave while one is folded.
+    // A wave takes every OC_WAVES-th segment of the band; its place (row py, segment ps of the row) is kept in scalar
+    // registers and stepped.  The kernel is bound by instruction issue (about 300 wave instructions per segment), not by
+    // these loads: one segment in flight measured the same (profiles/r17_graph_onchip.txt).
+    struct Seg { int y, x, s, rt, dn, dr; float g; };
+    int py = y_beg, ps = __builtin_amdgcn_readfirstlane(wave);
+    auto settle = [&]() { while (ps >= nseg && py < y_end) { ps -= nseg; ++py; } };
+    auto fetch = [&]() {
+        settle();
+        Seg c{py, ps * 64 + lane, -1, -1, -1, -1, -INFINITY};
+        if (py < y_end && c.x < W) {
+            const size_t p = (size_t)c.y * W + c.x;
+            c.s = sg[p];
+            c.g = gr[p];
+            if (c.x + 1 < W) c.rt = sg[p + 1];
+            if (c.y + 1 < H) {
+                c.dn = sg[p + W];
+                if (d.conn == 8 && c.x + 1 < W) c.dr = sg[p + W + 1];
+            }
+        }
+        ps += OC_WAVES;
+        return c;
+    };
+    float gv = -INFINITY;
+    Seg nxt = fetch(), nxt2 = fetch(), nxt3 = fetch();
+    for (int it = wave; it < items; it += OC_WAVES) {
+        const Seg c = nxt;
+        nxt = nxt2; nxt2 = nxt3;
+        nxt3 = fetch();
+        const int y = c.y, x = c.x;
+        bool valid = x < W;
+        if (valid && (unsigned)c.s >= (unsigned)Nmax) { atomicOr(&s_over, 1); valid = false; }   // not a label of this batch
+        const int s = valid ? c.s : -1;
+        if (valid) {
+            const int mult = (y == 0) + (y == H - 1) + (x == 0) + (x == W - 1);
+            if (mult) atomicAdd(&s_border[s], mult);
+            gv = fmaxf(gv, c.g);
+        }
+        // a region's pixels inside the segment form runs; a run's first lane folds the whole run into the region's box
+        const int s_left = __shfl_up(s, 1, 64);
+        const unsigned long long vmask = __ballot(valid);
+        const unsigned long long starts = __ballot(valid && (lane == 0 || s_left != s));
+        if (valid && ((starts >> lane) & 1ull)) {
+            const unsigned long long stop = (starts | ~vmask) >> lane >> 1;
+            const int len = stop ? __ffsll((long long)stop) : 64 - lane;
+            atomicMin(&s_y0[s], y); atomicMax(&s_y1[s], y + 1);
+            atomicMin(&s_x0[s], x); atomicMax(&s_x1[s], x + len);
+        }
+        // the links of k_adj
+        const bool rt = valid && x + 1 < W, dn = valid && y + 1 < H;
+        add_runs(key_of(rt, s, c.rt));
+        add_runs(key_of(dn, s, c.dn));
+        if (d.conn == 8) {
+            add_runs(key_of(rt && dn, s, c.dr));
+            add_runs(key_of(rt && dn, c.rt, c.dn));
+        }
+    }
+    for (int o = 32; o > 0; o >>= 1) gv = fmaxf(gv, __shfl_xor(gv, o, 64));
+    if (lane == 0 && gv > -INFINITY) atomicMax(&s_gmax, f2ord(gv));
+    __syncthreads();
+
+    // one band per image owns the image's words and stores them; several bands merge into words the host has initialised
+    const bool over = s_over != 0;
+    if (bands == 1) {
+        for (int i = tid; i < Nmax; i += OC_THREADS) {
+            bbox[(size_t)b * Nmax + i] = make_int4(s_y0[i], s_y1[i], s_x0[i], s_x1[i]);
+            border[(size_t)b * Nmax + i] = s_border[i];
+        }
+        if (tid < 5) maxima[(size_t)b * 5 + tid] = 0;
+        if (tid < 3) totals[3 * b + tid] = tid == 2 ? (int)over : 0;
+        if (tid == 0) gmax[b] = s_gmax;
+    } else {
+        for (int i = tid; i < Nmax; i += OC_THREADS) {
+            if (s_y1[i] > 0) {
+                int4* bb = bbox + (size_t)b * Nmax + i;
+                atomicMin(&bb->x, s_y0[i]); atomicMax(&bb->y, s_y1[i]);
+                atomicMin(&bb->z, s_x0[i]); atomicMax(&bb->w, s_x1[i]);
+            }
+            if (s_border[i]) atomicAdd(&border[(size_t)b * Nmax + i], s_border[i]);
+        }
+        if (tid == 0) {
+            atomicMax(&gmax[b], s_gmax);
+            if (over) atomicOr(&totals[3 * b + 2], 1);
+        }
+    }
+    const size_t base = ((size_t)b * bands + band) * OC_PAIRS;
+    if (!over)
+        for (int i = tid; i < OC_SLOTS; i += OC_THREADS)
+            if (s_key[i] != OC_EMPTY) {
+                const int q = atomicAdd(&s_out, 1);      // below OC_PAIRS: s_new never passed it
+                L.band_key[base + q] = s_key[i];
+                L.band_cnt[base + q] = s_cnt[i];
+            }
+    if (tid == 0) L.band_n[(size_t)b * bands + band] = over ? 0 : s_new;
+}
+
+// exclusive scan of one value per thread over the workgroup; `total` is the sum.  part: OC_WAVES + 1 words of LDS.
+__device__ __forceinline__ int oc_block_scan(int v, int* part, int& total) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    int inc = v;
+    for (int o = 1; o < 64; o <<= 1) {
+        const int u = __shfl_up(inc, o, 64);
+        if (lane >= o) inc += u;
+    }
+    __syncthreads();                                  // part may still be read from the scan before
+    if (lane == 63) part[wave] = inc;
+    __syncthreads();
+    int pre = 0, sum = 0;
+    for (int w = 0; w < OC_WAVES; ++w) { const int p = part[w]; if (w < wave) pre += p; sum += p; }
+    total = sum;
+    return pre + inc - v;
+}
+
+// set bits of a bitset row in the columns [a, e)
+__device__ __forceinline__ int oc_row_popc(const uint32_t* row, int a, int e) {
+    int n = 0;
+    if (e <= a) return 0;
+    for (int w = a >> 5; w <= (e - 1) >> 5; ++w) {
+        uint32_t m = row[w];
+        if (w == a >> 5) m &= ~0u << (a & 31);
+        if (w == (e - 1) >> 5) m &= ~0u >> (31 - ((e - 1) & 31));
+        n += __popc(m);
+    }
+    return n;
+}
+
+// Row i's k nearest nodes in mean-Lab among those that are neither i nor adjacent to it: one thread walks j upwards with
+// the K best so far sorted in registers.  A distance enters only where it is strictly smaller, so equal distances stay in
+// ascending j: the first k_nl entries are k_knn's k rounds of lexicographic (distance, j) arg-min.  Every thread reads the
+// same l[j] (an LDS broadcast), and no step crosses lanes; a wave per row spent most of its instructions on the arg-min
+// butterflies.  NaN and infinite distances never enter, as k_knn never emits them.
+template <int K>
+__device__ __forceinline__ void oc_knn_row(int i, int N, int k_nl, const float* l0, const float* l1, const float* l2,
+                                           const uint32_t* row, uint16_t* choice) {
+    float bd[K]; int bj[K];
+#pragma unroll
+    for (int t = 0; t < K; ++t) { bd[t] = INFINITY; bj[t] = (int)OC_NONE; }
+    const float a0 = l0[i], a1 = l1[i], a2 = l2[i];
+    uint32_t word = 0;
+    for (int j = 0; j < N; ++j) {
+        if ((j & 31) == 0) word = row[j >> 5];
+        const float dx = a0 - l0[j], dy = a1 - l1[j], dz = a2 - l2[j];
+        const float v = sqrtf((dx * dx + dy * dy) + dz * dz);
+        if (j != i && !((word >> (j & 31)) & 1u) && v < bd[K - 1]) {
+#pragma unroll
+            for (int t = K - 1; t > 0; --t) {
+                const bool shift = v < bd[t - 1], here = v < bd[t];
+                bj[t] = shift ? bj[t - 1] : here ? j : bj[t];
+                bd[t] = shift ? bd[t - 1] : here ? v : bd[t];
+            }
+            if (v < bd[0]) { bd[0] = v; bj[0] = j; }
+        }
+    }
+#pragma unroll
+    for (int t = 0; t < K; ++t)
+        if (t < k_nl && bj[t] != (int)OC_NONE) choice[t] = (uint16_t)bj[t];
+}
+
+// ---- sorted adjacent pairs, non-local k nearest neighbours in mean-Lab, sorted non-local pairs (workgroup per image)
+__global__ void __launch_bounds__(OC_THREADS) k_topology(GDims d, int bands, const int32_t* __restrict__ n_nodes,
+                                                         const RegionStats* __restrict__ st, OnchipLists L,
+                                                         int32_t* __restrict__ totals) {
+    __shared__ uint32_t s_bits[OC_NMAX * OC_WPR];
+    __shared__ float s_l0[OC_NMAX], s_l1[OC_NMAX], s_l2[OC_NMAX];
+    __shared__ int s_off[OC_NMAX + 1];
+    __shared__ uint32_t s_sum[OC_PAIRS];
+    __shared__ uint16_t s_choice[OC_NL];
+    __shared__ int s_part[OC_WAVES + 1];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const int lane = tid & 63, wave = tid >> 6;
+    if (totals[3 * b + 2]) return;                    // the scan met what the tables do not hold
+    const int N = n_nodes[b], Nmax = d.Nmax;
+    const RegionStats* s = st + (size_t)b * Nmax;
+    for (int i = tid; i < N * OC_WPR; i += OC_THREADS) s_bits[i] = 0;
+    for (int i = tid; i < OC_PAIRS; i += OC_THREADS) s_sum[i] = 0;
+    for (int i = tid; i < N; i += OC_THREADS) { s_l0[i] = s[i].mlab[0]; s_l1[i] = s[i].mlab[1]; s_l2[i] = s[i].mlab[2]; }
+    __syncthreads();
+    // adjacency as a symmetric bitset; labels from N on belong to no node (the dense rows stop at N too)
+    for (int g = 0; g < bands; ++g) {
+        const size_t base = ((size_t)b * bands + g) * OC_PAIRS;
+        const int n = L.band_n[(size_t)b * bands + g];
+        for (int e = tid; e < n; e += OC_THREADS) {
+            const uint32_t key = L.band_key[base + e];
+            const int lo = key / Nmax, hi = key % Nmax;
+            if (hi >= N) continue;
+            atomicOr(&s_bits[lo * OC_WPR + (hi >> 5)], 1u << (hi & 31));
+            atomicOr(&s_bits[hi * OC_WPR + (lo >> 5)], 1u << (lo & 31));
+        }
+    }
+    __syncthreads();
+    // row i of the dense matrix holds its pairs (i, j > i) in ascending j: a pair's place is its row's offset plus the
+    // row's bits below it
+    int n_adj;
+    {
+        const int c = tid < N ? oc_row_popc(s_bits + tid * OC_WPR, tid + 1, N) : 0;
+        const int off = oc_block_scan(c, s_part, n_adj);
+        if (tid < N) s_off[tid] = off;
+    }
+    if (n_adj > OC_PAIRS) {                           // the bands' union is larger than any one band's table
+        if (tid == 0) totals[3 * b + 2] = 1;
+        return;
+    }
+    __syncthreads();
+    for (int g = 0; g < bands; ++g) {
+        const size_t base = ((size_t)b * bands + g) * OC_PAIRS;
+        const int n = L.band_n[(size_t)b * bands + g];
+        for (int e = tid; e < n; e += OC_THREADS) {
+            const uint32_t key = L.band_key[base + e];
+            const int lo = key / Nmax, hi = key % Nmax;
+            if (hi >= N) continue;
+            const int q = s_off[lo] + oc_row_popc(s_bits + lo * OC_WPR, lo + 1, hi);
+            atomicAdd(&s_sum[q], L.band_cnt[base + e]);
+            L.adj_key[(size_t)b * OC_PAIRS + q] = key;      // two bands that saw the pair store the same word
+        }
+    }
+    __syncthreads();
+    for (int q = tid; q < n_adj; q += OC_THREADS) L.adj_cnt[(size_t)b * OC_PAIRS + q] = s_sum[q];
+
+    // k-NN: thread per row
+    const bool knn = d.k_nl > 0 && N > d.k_nl + 1;    // graph_builder.py:291
+    int n_nl = 0;
+    if (knn) {
+        for (int i = tid; i < N * OC_KMAX; i += OC_THREADS) s_choice[i] = (uint16_t)OC_NONE;
+        __syncthreads();
+        if (tid < N) {
+            if (d.k_nl <= 4) oc_knn_row<4>(tid, N, d.k_nl, s_l0, s_l1, s_l2, s_bits + tid * OC_WPR, s_choice + tid * OC_KMAX);
+            else oc_knn_row<OC_KMAX>(tid, N, d.k_nl, s_l0, s_l1, s_l2, s_bits + tid * OC_WPR, s_choice + tid * OC_KMAX);
+        }
+        __syncthreads();
+        // both ends may have chosen each other: the pairs pass through a bitset of their own, which also sorts them
+        for (int i = tid; i < N * OC_WPR; i += OC_THREADS) s_bits[i] = 0;
+        __syncthreads();
+        for (int e = tid; e < N * d.k_nl; e += OC_THREADS) {
+            const int i = e / d.k_nl, j = s_choice[i * OC_KMAX + e % d.k_nl];
+            if (j == (int)OC_NONE) continue;
+            const int lo = min(i, j), hi = max(i, j);
+            atomicOr(&s_bits[lo * OC_WPR + (hi >> 5)], 1u << (hi & 31));
+        }
+        __syncthreads();
+        const int c = tid < N ? oc_row_popc(s_bits + tid * OC_WPR, 0, N) : 0;
+        int q = oc_block_scan(c, s_part, n_nl);
+        if (tid < N)
+            for (int w = 0; w < OC_WPR; ++w)
+                for (uint32_t m = s_bits[tid * OC_WPR + w]; m; m &= m - 1)
+                    L.nl_key[(size_t)b * OC_NL + q++] = (uint32_t)(tid * Nmax + w * 32 + __ffs(m) - 1);
+    }
+    if (tid == 0) { totals[3 * b] = n_adj; totals[3 * b + 1] = n_nl; }
+}
+
+// ---- raw pair features from the sorted lists: entry q of image b goes to pair_ptr[b] + q, adjacent pairs first
+__global__ void __launch_bounds__(256) k_emit(GDims d, const RegionStats* __restrict__ st, OnchipLists L,
+                                              const int64_t* __restrict__ pair_ptr, const int32_t* __restrict__ totals,
+                                              PairOut out, uint32_t* __restrict__ maxima) {
+    const int b = blockIdx.y;
+    const int n_adj = totals[3 * b], n_all = n_adj + totals[3 * b + 1];
+    if ((int)(blockIdx.x * 256) >= n_all) return;
+    const int e = blockIdx.x * 256 + threadIdx.x, lane = threadIdx.x & 63;
+    const bool isa = e < n_adj, isn = !isa && e < n_all;
+    float mde_a = 0.f, mdx_a = 0.f, mde_n = 0.f, mdx_n = 0.f;
+    int msh = 0;
+    if (isa || isn) {
+        const uint32_t key = isa ? L.adj_key[(size_t)b * OC_PAIRS + e] : L.nl_key[(size_t)b * OC_NL + (e - n_adj)];
+        const int i = key / d.Nmax, j = key % d.Nmax;
+        const RegionStats* s = st + (size_t)b * d.Nmax;
+        const float dx = s[i].mlab[0] - s[j].mlab[0], dy = s[i].mlab[1] - s[j].mlab[1], dz = s[i].mlab[2] - s[j].mlab[2];
+        const float de = sqrtf((dx * dx + dy * dy) + dz * dz);
+        const float cy = s[i].cy - s[j].cy, cx = s[i].cx - s[j].cx;
+        const float dxy = sqrtf(cy * cy + cx * cx);
+        const float gc = fabsf(s[i].mgn - s[j].mgn);
+        const int64_t q = pair_ptr[b] + e;
+        out.lo[q] = i; out.hi[q] = j; out.de[q] = de; out.dxy[q] = dxy; out.gc[q] = gc;
+        if (isa) {
+            const int v = (int)L.adj_cnt[(size_t)b * OC_PAIRS + e];
+            out.shared[q] = (float)v;
+            mde_a = fmaxf(mde_a, de); mdx_a = fmaxf(mdx_a, dxy); msh = v;
+        } else {
+            out.shared[q] = 0.0f;
+            mde_n = fmaxf(mde_n, de); mdx_n = fmaxf(mdx_n, dxy);
+        }
+    }
+    const bool any_a = __ballot(isa) != 0, any_n = __ballot(isn) != 0;
+    for (int o = 32; o > 0; o >>= 1) {
+        mde_a = fmaxf(mde_a, __shfl_xor(mde_a, o, 64)); mdx_a = fmaxf(mdx_a, __shfl_xor(mdx_a, o, 64));
+        mde_n = fmaxf(mde_n, __shfl_xor(mde_n, o, 64)); mdx_n = fmaxf(mdx_n, __shfl_xor(mdx_n, o, 64));
+        msh = max(msh, __shfl_xor(msh, o, 64));
+    }
+    if (lane == 0) {
+        uint32_t* mx = maxima + (size_t)b * 5;
+        if (any_a) { atomicMax(&mx[0], f2ord(mde_a)); atomicMax(&mx[1], f2ord(mdx_a)); atomicMax(&mx[4], (uint32_t)msh); }
+        if (any_n) { atomicMax(&mx[2], f2ord(mde_n)); atomicMax(&mx[3], f2ord(mdx_n)); }
+    }
+}
+
 // ---- K9: final edge attributes in place (de, dxy, shared normalised per image and per pair kind)
 __global__ void __launch_bounds__(256) k_pair_final(int B, const int64_t* __restrict__ pair_ptr,
                                                     const int32_t* __restrict__ totals,
@@ -675,9 +1054,8 @@ extern "C" int ggc_graph_count(ggc_ctx* ctx, ggc_stream stream, int B, int H, in
     ctx->graph.valid = false;
 
     // sync 1: node counts
-    std::vector<int32_t> nn(B);
-    GGC_HIP(ctx, hipMemcpyAsync(nn.data(), n_nodes, sizeof(int32_t) * B, hipMemcpyDeviceToHost, st));
-    GGC_HIP(ctx, hipStreamSynchronize(st));
+    std::vector<int32_t> nn;
+    if (const int rc = read_i32(ctx, st, n_nodes, B, nn)) return rc;
     int Nmax = 1;
     GraphState& gs = ctx->graph;
     gs.node_ptr.assign(B + 1, 0);
@@ -686,8 +1064,6 @@ extern "C" int ggc_graph_count(ggc_ctx* ctx, ggc_stream stream, int B, int H, in
         Nmax = std::max(Nmax, nn[b]);
         gs.node_ptr[b + 1] = gs.node_ptr[b] + nn[b];
     }
-    GGC_REQUIRE(ctx, (size_t)B * Nmax * Nmax * 4 < (size_t)64 << 30, GGC_E_OOM,
-                "dense adjacency of %d x %d^2 exceeds 64 GiB", B, Nmax);
     GDims d{B, H, W, Nmax, connectivity, n_nonlocal};
     const size_t BN = (size_t)B * Nmax;
 
@@ -695,47 +1071,95 @@ extern "C" int ggc_graph_count(ggc_ctx* ctx, ggc_stream stream, int B, int H, in
     int32_t* border = scratch_t<int32_t>(ctx, S_G_AUX2, BN);
     uint32_t* small = scratch_t<uint32_t>(ctx, S_G_AUX3, (size_t)B * 16);   // gmax[B] | maxima[B,5] | totals[B,3]
     RegionStats* stats = scratch_t<RegionStats>(ctx, S_G_STATS, BN);
-    int32_t* dense = scratch_t<int32_t>(ctx, S_G_PAIRCNT, BN * Nmax);
-    int32_t* cnt_adj = scratch_t<int32_t>(ctx, S_G_NL, BN * 2);
     float* feat = scratch_t<float>(ctx, S_G_FEAT, BN * 16);
     float* prior = scratch_t<float>(ctx, S_G_PRIOR, BN * 3);
     float* work = scratch_t<float>(ctx, S_G_X, BN * 3);
-    if (!bbox || !border || !small || !stats || !dense || !cnt_adj || !feat || !prior || !work) return GGC_E_OOM;
-    int32_t* cnt_nl = cnt_adj + BN;
+    if (!bbox || !border || !small || !stats || !feat || !prior || !work) return GGC_E_OOM;
     uint32_t* gmax = small;
     uint32_t* maxima = small + B;
-    int32_t* totals = reinterpret_cast<int32_t*>(small + (size_t)B * 6);
+    int32_t* totals = reinterpret_cast<int32_t*>(small + (size_t)B * 6);   // {n_adj, n_nl, on-chip tables overflowed}
     float* contrast = work + BN * 2;
+    const dim3 rows(cdiv(Nmax, 4), B);
 
-    hipLaunchKernelGGL(k_bbox_init, dim3(cdiv(BN, 256)), dim3(256), 0, st, BN, bbox);
-    GGC_HIP(ctx, hipMemsetAsync(border, 0, sizeof(int32_t) * BN, st));
-    GGC_HIP(ctx, hipMemsetAsync(small, 0, sizeof(uint32_t) * (size_t)B * 16, st));
-    GGC_HIP(ctx, hipMemsetAsync(dense, 0, sizeof(int32_t) * BN * Nmax, st));
-    const dim3 pix(cdiv(W, 64), cdiv(H, 4), B);
-    hipLaunchKernelGGL(k_bbox, dim3(cdiv(W, 64), cdiv(H, BBOX_ROWS), B), dim3(256), 0, st, d, segments, grad, bbox, border, gmax);
+    // The topology through the dense matrix: for what the on-chip tables do not hold, and with GGC_GRAPH_ONCHIP=0.
+    int32_t *dense = nullptr, *cnt_adj = nullptr, *cnt_nl = nullptr;
+    auto dense_topology = [&]() -> int {
+        GGC_REQUIRE(ctx, (size_t)B * Nmax * Nmax * 4 < (size_t)64 << 30, GGC_E_OOM,
+                    "dense adjacency of %d x %d^2 exceeds 64 GiB", B, Nmax);
+        dense = scratch_t<int32_t>(ctx, S_G_PAIRCNT, BN * Nmax);
+        cnt_adj = scratch_t<int32_t>(ctx, S_G_NL, BN * 2);
+        if (!dense || !cnt_adj) return GGC_E_OOM;
+        cnt_nl = cnt_adj + BN;
+        GGC_HIP(ctx, hipMemsetAsync(dense, 0, sizeof(int32_t) * BN * Nmax, st));
+        hipLaunchKernelGGL(k_adj, dim3(cdiv(W, 64), cdiv(H, 4), B), dim3(256), 0, st, d, segments, dense);
+        GGC_LAUNCH_CHECK(ctx);
+        if (n_nonlocal > 0) {
+            const size_t lds = (size_t)4 * Nmax * sizeof(float);
+            GGC_REQUIRE(ctx, lds <= 64 * 1024, GGC_E_UNSUPPORTED, "k-NN row buffer for %d nodes exceeds LDS", Nmax);
+            ProfScope prof(ctx, st, "graph_knn");
+            hipLaunchKernelGGL(k_knn, rows, dim3(256), lds, st, d, n_nodes, stats, dense);
+        }
+        hipLaunchKernelGGL(k_rowcount, rows, dim3(256), 0, st, d, n_nodes, dense, cnt_adj, cnt_nl);
+        hipLaunchKernelGGL(k_rowscan, dim3(B), dim3(256), 0, st, d, n_nodes, cnt_adj, cnt_nl, totals);
+        GGC_LAUNCH_CHECK(ctx);
+        return GGC_OK;
+    };
+
+    // k_topology is one workgroup per image: below OC_MIN_BATCH images the dense kernels, which spread an image's rows
+    // over the chip, are the faster way (profiles/r17_graph_onchip.txt); GGC_GRAPH_ONCHIP=2 takes the tables at any size
+    bool onchip = knobs().graph_onchip && (B >= OC_MIN_BATCH || knobs().graph_onchip >= 2) && Nmax <= OC_NMAX &&
+                  n_nonlocal <= OC_KMAX;
+    // one workgroup per image fills the chip at batch 256; a small batch splits each image's rows over several
+    const int bands = std::max(1, std::min({OC_BANDS_MAX, ctx->n_cu / B, H}));
+    OnchipLists lists{};
+    if (onchip) {
+        const size_t got = carve_scratch(ctx, S_G_LISTS, [&](Carve& c) {
+            lists.band_key = c.take<uint32_t>((size_t)B * bands * OC_PAIRS);
+            lists.band_cnt = c.take<uint32_t>((size_t)B * bands * OC_PAIRS);
+            lists.band_n = c.take<int32_t>((size_t)B * bands);
+            lists.adj_key = c.take<uint32_t>((size_t)B * OC_PAIRS);
+            lists.adj_cnt = c.take<uint32_t>((size_t)B * OC_PAIRS);
+            lists.nl_key = c.take<uint32_t>((size_t)B * OC_NL);
+        });
+        if (!got) return GGC_E_OOM;
+    }
+    if (!onchip || bands > 1) {
+        hipLaunchKernelGGL(k_bbox_init, dim3(cdiv(BN, 256)), dim3(256), 0, st, BN, bbox);
+        GGC_HIP(ctx, hipMemsetAsync(border, 0, sizeof(int32_t) * BN, st));
+        GGC_HIP(ctx, hipMemsetAsync(small, 0, sizeof(uint32_t) * (size_t)B * 16, st));
+    }
+    if (onchip)
+        hipLaunchKernelGGL(k_region_scan, dim3(bands, B), dim3(OC_THREADS), 0, st, d, bands, segments, grad, bbox, border,
+                           gmax, maxima, totals, lists);
+    else
+        hipLaunchKernelGGL(k_bbox, dim3(cdiv(W, 64), cdiv(H, BBOX_ROWS), B), dim3(256), 0, st, d, segments, grad, bbox,
+                           border, gmax);
     {
         ProfScope prof(ctx, st, "graph_stats");
         hipLaunchKernelGGL(k_stats, dim3(cdiv(Nmax, SG_REGIONS), B), dim3(64), 0, st, d, segments, n_nodes, lab, hsv, grad,
                            bbox, border, gmax, stats);
     }
-    hipLaunchKernelGGL(k_adj, pix, dim3(256), 0, st, d, segments, dense);
     GGC_LAUNCH_CHECK(ctx);
-    const dim3 rows(cdiv(Nmax, 4), B);
-    if (n_nonlocal > 0) {
-        const size_t lds = (size_t)4 * Nmax * sizeof(float);
-        GGC_REQUIRE(ctx, lds <= 64 * 1024, GGC_E_UNSUPPORTED, "k-NN row buffer for %d nodes exceeds LDS", Nmax);
+    if (onchip) {
         ProfScope prof(ctx, st, "graph_knn");
-        hipLaunchKernelGGL(k_knn, rows, dim3(256), lds, st, d, n_nodes, stats, dense);
+        hipLaunchKernelGGL(k_topology, dim3(B), dim3(OC_THREADS), 0, st, d, bands, n_nodes, stats, lists, totals);
+        GGC_LAUNCH_CHECK(ctx);
+    } else if (const int rc = dense_topology()) {
+        return rc;
     }
-    hipLaunchKernelGGL(k_rowcount, rows, dim3(256), 0, st, d, n_nodes, dense, cnt_adj, cnt_nl);
-    hipLaunchKernelGGL(k_rowscan, dim3(B), dim3(256), 0, st, d, n_nodes, cnt_adj, cnt_nl, totals);
-    GGC_LAUNCH_CHECK(ctx);
 
-    // sync 2: pair counts
-    std::vector<int32_t> tot((size_t)B * 3);
-    GGC_HIP(ctx, hipMemcpyAsync(tot.data(), totals, sizeof(int32_t) * B * 3, hipMemcpyDeviceToHost, st));
-    GGC_HIP(ctx, hipStreamSynchronize(st));
-    std::vector<int64_t> pair_ptr(B + 1, 0);
+    // sync 2: pair counts, and whether any image overflowed the on-chip tables (then the batch goes the dense way)
+    std::vector<int32_t> tot;
+    if (const int rc = read_i32(ctx, st, totals, B * 3, tot)) return rc;
+    if (onchip) {
+        for (int b = 0; b < B && onchip; ++b) onchip = tot[3 * b + 2] == 0;
+        if (!onchip) {
+            if (const int rc = dense_topology()) return rc;
+            if (const int rc = read_i32(ctx, st, totals, B * 3, tot)) return rc;
+        }
+    }
+    std::vector<int64_t>& pair_ptr = gs.pair_ptr;
+    pair_ptr.assign(B + 1, 0);
     gs.edge_ptr.assign(B + 1, 0);
     for (int b = 0; b < B; ++b) {
         pair_ptr[b + 1] = pair_ptr[b] + tot[3 * b] + tot[3 * b + 1];
@@ -746,16 +1170,20 @@ extern "C" int ggc_graph_count(ggc_ctx* ctx, ggc_stream stream, int B, int H, in
     int32_t* plo = scratch_t<int32_t>(ctx, S_G_PAIRS, (size_t)std::max<int64_t>(n_pairs, 1) * 2);
     float* pattr = scratch_t<float>(ctx, S_G_EDGE_ATTR, (size_t)std::max<int64_t>(n_pairs, 1) * 5);
     if (!ptrs || !plo || !pattr) return GGC_E_OOM;
+    // both sources live in the context until the next count, which first waits for this stream
     GGC_HIP(ctx, hipMemcpyAsync(ptrs, gs.node_ptr.data(), sizeof(int64_t) * (B + 1), hipMemcpyHostToDevice, st));
     GGC_HIP(ctx, hipMemcpyAsync(ptrs + (B + 1), pair_ptr.data(), sizeof(int64_t) * (B + 1), hipMemcpyHostToDevice, st));
-    GGC_HIP(ctx, hipStreamSynchronize(st));   // the host vectors above go out of scope
     const size_t np1 = (size_t)std::max<int64_t>(n_pairs, 1);
     PairOut po{plo, plo + np1, pattr, pattr + np1, pattr + 2 * np1, pattr + 3 * np1};
     float* flag = pattr + 4 * np1;
     int64_t max_pairs = 0;
     for (int b = 0; b < B; ++b) max_pairs = std::max(max_pairs, pair_ptr[b + 1] - pair_ptr[b]);
-    hipLaunchKernelGGL(k_extract, rows, dim3(256), 0, st, d, n_nodes, dense, stats, cnt_adj, cnt_nl, ptrs + (B + 1),
-                       totals, po, maxima);
+    if (!onchip)
+        hipLaunchKernelGGL(k_extract, rows, dim3(256), 0, st, d, n_nodes, dense, stats, cnt_adj, cnt_nl, ptrs + (B + 1),
+                           totals, po, maxima);
+    else if (max_pairs > 0)
+        hipLaunchKernelGGL(k_emit, dim3(cdiv(max_pairs, 256), B), dim3(256), 0, st, d, stats, lists, ptrs + (B + 1), totals,
+                           po, maxima);
     if (max_pairs > 0)
         hipLaunchKernelGGL(k_pair_final, dim3(cdiv(max_pairs, 256), B), dim3(256), 0, st, B, ptrs + (B + 1), totals,
                            maxima, po, flag);

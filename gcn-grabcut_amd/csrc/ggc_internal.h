@@ -23,7 +23,7 @@ enum Slot : int {
     S_PRE_A, S_PRE_B, S_PRE_C, S_PRE_D,
     S_SLIC_IMG, S_SLIC_TMP, S_SLIC_CENTERS, S_SLIC_DIST, S_SLIC_LABELS, S_SLIC_AUX,
     S_SLIC_AUX2, S_SLIC_AUX3, S_SLIC_AUX4, S_SLIC_MINMAX,
-    S_G_STATS, S_G_FEAT, S_G_PAIRS, S_G_PAIRCNT, S_G_NL, S_G_EDGE_SRC, S_G_EDGE_DST,
+    S_G_STATS, S_G_FEAT, S_G_PAIRS, S_G_PAIRCNT, S_G_NL, S_G_LISTS, S_G_EDGE_DST,
     S_G_EDGE_ATTR, S_G_PTR, S_G_PRIOR, S_G_AUX, S_G_AUX2, S_G_AUX3, S_G_X,
     S_T_A, S_T_B, S_T_C,
     S_GC_A, S_GC_B, S_GC_C, S_GC_D, S_GC_E, S_GC_F, S_GC_G, S_GC_H, S_GC_I, S_GC_J,
@@ -68,6 +68,7 @@ struct GraphState {
     int B = 0, H = 0, W = 0;
     int64_t n_total = 0, e_total = 0;
     std::vector<int64_t> node_ptr, edge_ptr;
+    std::vector<int64_t> pair_ptr;         // undirected pairs before each image; kept here so its upload needs no host wait
     int64_t max_pairs = 0;                 // largest per-image undirected pair count
     int n_max = 0;                         // row stride of the per-image scratch tables
     const int32_t* n_nodes_dev = nullptr;  // caller's n_nodes[B] (must outlive ggc_graph_fill)
@@ -115,6 +116,7 @@ struct Knobs {
     int agg_direct;             // GGC_AGG_DIRECT (0): 1 = GCNConv gather straight from L2 (k_aggregate) instead of the graph-resident kernel
     int slic_seq_connectivity;  // GGC_SLIC_SEQ_CONNECTIVITY (0): 1 = literal one-thread-per-image raster replay of skimage's connectivity pass
     int matte_eval_levels;      // GGC_MATTE_EVAL_LEVELS (0): threshold levels labelled per pass of ggc_matte_errors, 1 | 2 | 5 | 10; 0 = 10 while the maps fit 4 GiB, else 1
+    int graph_onchip;           // GGC_GRAPH_ONCHIP (1): 0 = region-graph topology through the dense B x N x N matrix even where the on-chip tables fit
     int wand_seeds_per_pass;    // GGC_WAND_SEEDS_PER_PASS (0): seeds labelled per pass of ggc_wand_select, 1..4096; 0 = as many as keep the parent maps within 1 GiB
 };
 const Knobs& knobs();

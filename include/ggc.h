@@ -38,7 +38,11 @@
  *                                 0..64, larger values are clamped to 64: a partial round never closes an image)
  *   GGC_AGG_DIRECT=1              GCNConv gather straight from L2 instead of the graph-resident kernel
  *   GGC_SLIC_SEQ_CONNECTIVITY=1   literal one-thread-per-image replay of skimage's connectivity pass (A/B reference)
- *   GGC_MATTE_EVAL_LEVELS=1|2|5|10   threshold levels that ggc_matte_errors labels per pass (default: 10 while its maps fit 4 GiB, else 1)
+ *   GGC_GRAPH_ONCHIP=0|1|2        region-graph topology of ggc_graph_count from on-chip pair tables instead of the dense
+ *                                 B x N x N matrix: 0 never, 1 (default) for batches of at least 24 images, 2 at any batch size;
+ *                                 in each case only where an image has at most 704 regions, 6144 distinct adjacent pairs and
+ *                                 n_nonlocal <= 8, else the dense kernels run (same outputs, byte for byte)
+ *   GGC_MATTE_EVAL_LEVELS=1|2|5|10  threshold levels that ggc_matte_errors labels per pass (default: 10 while its maps fit 4 GiB, else 1)
  *   GGC_WAND_SEEDS_PER_PASS=n     seeds that ggc_wand_select labels per pass, 1..4096 (default: as many as keep its maps within 1 GiB)
  * The Python binding adds GGC_HIP_LIBRARY=<path> (load another build of the library, tools/build_variant.sh).
  */
