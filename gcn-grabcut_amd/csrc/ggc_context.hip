@@ -30,6 +30,8 @@ const Knobs& knobs() {
         k.matte_eval_levels = num("GGC_MATTE_EVAL_LEVELS", 0, 0);
         if (k.matte_eval_levels > 10 || (k.matte_eval_levels && 10 % k.matte_eval_levels != 0)) k.matte_eval_levels = 0;   // the passes must tile the ten levels
         k.graph_onchip = num("GGC_GRAPH_ONCHIP", 1, 0);
+        k.graph_bands = num("GGC_GRAPH_BANDS", 0, 0);
+        if (k.graph_bands > 8) k.graph_bands = 0;
         k.wand_seeds_per_pass = num("GGC_WAND_SEEDS_PER_PASS", 0, 0);
         if (k.wand_seeds_per_pass > 4096) k.wand_seeds_per_pass = 0;
         return k;

@@ -1091,7 +1091,10 @@ extern "C" int ggc_graph_count(ggc_ctx* ctx, ggc_stream stream, int B, int H, in
         if (!dense || !cnt_adj) return GGC_E_OOM;
         cnt_nl = cnt_adj + BN;
         GGC_HIP(ctx, hipMemsetAsync(dense, 0, sizeof(int32_t) * BN * Nmax, st));
-        hipLaunchKernelGGL(k_adj, dim3(cdiv(W, 64), cdiv(H, 4), B), dim3(256), 0, st, d, segments, dense);
+        {
+            ProfScope prof(ctx, st, "graph_dense");
+            hipLaunchKernelGGL(k_adj, dim3(cdiv(W, 64), cdiv(H, 4), B), dim3(256), 0, st, d, segments, dense);
+        }
         GGC_LAUNCH_CHECK(ctx);
         if (n_nonlocal > 0) {
             const size_t lds = (size_t)4 * Nmax * sizeof(float);
@@ -1110,7 +1113,9 @@ extern "C" int ggc_graph_count(ggc_ctx* ctx, ggc_stream stream, int B, int H, in
     bool onchip = knobs().graph_onchip && (B >= OC_MIN_BATCH || knobs().graph_onchip >= 2) && Nmax <= OC_NMAX &&
                   n_nonlocal <= OC_KMAX;
     // one workgroup per image fills the chip at batch 256; a small batch splits each image's rows over several
-    const int bands = std::max(1, std::min({OC_BANDS_MAX, ctx->n_cu / B, H}));
+    // (GGC_GRAPH_BANDS pins the number, for tests)
+    const int bands = knobs().graph_bands ? std::min({OC_BANDS_MAX, knobs().graph_bands, H})
+                                          : std::max(1, std::min({OC_BANDS_MAX, ctx->n_cu / B, H}));
     OnchipLists lists{};
     if (onchip) {
         const size_t got = carve_scratch(ctx, S_G_LISTS, [&](Carve& c) {
@@ -1128,10 +1133,11 @@ extern "C" int ggc_graph_count(ggc_ctx* ctx, ggc_stream stream, int B, int H, in
         GGC_HIP(ctx, hipMemsetAsync(border, 0, sizeof(int32_t) * BN, st));
         GGC_HIP(ctx, hipMemsetAsync(small, 0, sizeof(uint32_t) * (size_t)B * 16, st));
     }
-    if (onchip)
+    if (onchip) {
+        ProfScope prof(ctx, st, "graph_scan");
         hipLaunchKernelGGL(k_region_scan, dim3(bands, B), dim3(OC_THREADS), 0, st, d, bands, segments, grad, bbox, border,
                            gmax, maxima, totals, lists);
-    else
+    } else
         hipLaunchKernelGGL(k_bbox, dim3(cdiv(W, 64), cdiv(H, BBOX_ROWS), B), dim3(256), 0, st, d, segments, grad, bbox,
                            border, gmax);
     {

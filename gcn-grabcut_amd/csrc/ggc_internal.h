@@ -117,6 +117,7 @@ struct Knobs {
     int slic_seq_connectivity;  // GGC_SLIC_SEQ_CONNECTIVITY (0): 1 = literal one-thread-per-image raster replay of skimage's connectivity pass
     int matte_eval_levels;      // GGC_MATTE_EVAL_LEVELS (0): threshold levels labelled per pass of ggc_matte_errors, 1 | 2 | 5 | 10; 0 = 10 while the maps fit 4 GiB, else 1
     int graph_onchip;           // GGC_GRAPH_ONCHIP (1): 0 = region-graph topology through the dense B x N x N matrix even where the on-chip tables fit
+    int graph_bands;            // GGC_GRAPH_BANDS (0): 1..8 = row bands (workgroups) per image of the on-chip region scan, clamped to the rows; 0 = by batch size and CU count
     int wand_seeds_per_pass;    // GGC_WAND_SEEDS_PER_PASS (0): seeds labelled per pass of ggc_wand_select, 1..4096; 0 = as many as keep the parent maps within 1 GiB
 };
 const Knobs& knobs();

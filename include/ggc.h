@@ -42,6 +42,9 @@
  *                                 B x N x N matrix: 0 never, 1 (default) for batches of at least 24 images, 2 at any batch size;
  *                                 in each case only where an image has at most 704 regions, 6144 distinct adjacent pairs and
  *                                 n_nonlocal <= 8, else the dense kernels run (same outputs, byte for byte)
+ *   GGC_GRAPH_BANDS=n             row bands (workgroups) per image of that on-chip scan, 1..8, clamped to the image's rows
+ *                                 (default 0: min(8, CUs / batch, rows)); the profiler scope "graph_scan" counts its launches
+ *                                 and "graph_dense" those of the dense matrix, so the two tell which path a call took
  *   GGC_MATTE_EVAL_LEVELS=1|2|5|10  threshold levels that ggc_matte_errors labels per pass (default: 10 while its maps fit 4 GiB, else 1)
  *   GGC_WAND_SEEDS_PER_PASS=n     seeds that ggc_wand_select labels per pass, 1..4096 (default: as many as keep its maps within 1 GiB)
  * The Python binding adds GGC_HIP_LIBRARY=<path> (load another build of the library, tools/build_variant.sh).
