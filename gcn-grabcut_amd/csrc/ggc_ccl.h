@@ -39,6 +39,36 @@ __device__ __forceinline__ void ccl_union(int32_t* parent, int a, int b) {
     }
 }
 
+// The same two on a forest kept in LDS: the parent map of one tile, whose indices are tile-local (row * tile width + column,
+// so their order inside the tile is the raster order of the image).  The rule is the one above, an index no larger than the
+// pixel's own at every store, so the loops end for the same reason; the loads are workgroup-scope, the atomicMin an LDS one.
+__device__ __forceinline__ int ccl_find_lds(const int* par, int i) {
+    int p = __hip_atomic_load(&par[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    while (p != i) { i = p; p = __hip_atomic_load(&par[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
+    return i;
+}
+__device__ __forceinline__ void ccl_union_lds(int* par, int a, int b) {
+    for (;;) {
+        a = ccl_find_lds(par, a); b = ccl_find_lds(par, b);
+        if (a == b) return;
+        if (a < b) { const int t = a; a = b; b = t; }
+        const int old = atomicMin(&par[a], b);
+        if (old == a) return;
+        a = old;
+    }
+}
+
+// Raster rank from per-segment flag words: a segment is 64 consecutive pixels of a row, its word has a bit per flagged
+// pixel, and prefix is the exclusive sum of the words' popcounts in raster order of the segments.
+__host__ __device__ inline int ccl_rank_in_word(unsigned long long word, int lane) {
+    const unsigned long long below = word & ((1ull << lane) - 1ull);
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __popcll(below);
+#else
+    return __builtin_popcountll(below);
+#endif
+}
+
 // The lane at which `lane`'s run starts: the highest start at or below it.  starts must have one (a set lane always has).
 __host__ __device__ inline int ccl_run_start_lane(unsigned long long starts, int lane) {
     const unsigned long long below = starts & ((2ull << lane) - 1ull);          // lane 63: 2 << 63 wraps to 0, all ones

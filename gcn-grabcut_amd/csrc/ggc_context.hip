@@ -27,6 +27,7 @@ const Knobs& knobs() {
         k.mf_partial_rounds = std::min(64, num("GGC_MF_PARTIAL_ROUNDS", 3, 0));
         k.agg_direct = num("GGC_AGG_DIRECT", 0, 0);
         k.slic_seq_connectivity = num("GGC_SLIC_SEQ_CONNECTIVITY", 0, 0);
+        k.slic_cn_tiles = num("GGC_SLIC_CN_TILES", 1, 0);
         k.matte_eval_levels = num("GGC_MATTE_EVAL_LEVELS", 0, 0);
         if (k.matte_eval_levels > 10 || (k.matte_eval_levels && 10 % k.matte_eval_levels != 0)) k.matte_eval_levels = 0;   // the passes must tile the ten levels
         k.graph_onchip = num("GGC_GRAPH_ONCHIP", 1, 0);

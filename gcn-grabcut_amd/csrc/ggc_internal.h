@@ -115,6 +115,7 @@ struct Knobs {
     int mf_partial_rounds;      // GGC_MF_PARTIAL_ROUNDS (3, at most 64): first rounds of a solve whose relabel stops after the work-list launches
     int agg_direct;             // GGC_AGG_DIRECT (0): 1 = GCNConv gather straight from L2 (k_aggregate) instead of the graph-resident kernel
     int slic_seq_connectivity;  // GGC_SLIC_SEQ_CONNECTIVITY (0): 1 = literal one-thread-per-image raster replay of skimage's connectivity pass
+    int slic_cn_tiles;          // GGC_SLIC_CN_TILES (1): 0 = SLIC connectivity by the rounds on a pending plane from the start, no tile-local first round
     int matte_eval_levels;      // GGC_MATTE_EVAL_LEVELS (0): threshold levels labelled per pass of ggc_matte_errors, 1 | 2 | 5 | 10; 0 = 10 while the maps fit 4 GiB, else 1
     int graph_onchip;           // GGC_GRAPH_ONCHIP (1): 0 = region-graph topology through the dense B x N x N matrix even where the on-chip tables fit
     int graph_bands;            // GGC_GRAPH_BANDS (0): 1..8 = row bands (workgroups) per image of the on-chip region scan, clamped to the rows; 0 = by batch size and CU count

@@ -12,7 +12,10 @@
 //                   CCL (k_cn_reset, k_cn_merge, k_cn_size, k_cn_settle; k_cn_carve and
 //                   another round while a component reaches max_size), the discovery
 //                   ranks (k_cn_kept, k_cn_scan), the replay of the components below
-//                   min_size (k_cn_small) and the label write (k_cn_write);
+//                   min_size (k_cn_small) and the label write (k_cn_write).  The first
+//                   round runs in LDS tiles unless GGC_SLIC_CN_TILES=0 (k_cn_tile,
+//                   k_cn_border, k_cn_finish, k_cn_flag, k_cn_rank, k_cn_replay,
+//                   k_cn_label), and is the whole pass on real SLIC maps;
 //                   k_connectivity_seq is the literal one-thread-per-image replay
 //
 // Bit-exactness with the CPU path (integer label map) dictates the structure:
@@ -650,7 +653,8 @@ __global__ void __launch_bounds__(1024) k_cn_scan(CnDims d, int32_t* __restrict_
 }
 
 // small components: replay the BFS, remember the last neighbour of an earlier component
-__global__ void __launch_bounds__(64) k_cn_small(CnDims d, int tag, const int32_t* __restrict__ parent,
+// (only those of at least min_n pixels: 0 for all of them, or the ones that k_cn_replay's on-chip queue cannot hold)
+__global__ void __launch_bounds__(64) k_cn_small(CnDims d, int tag, int min_n, const int32_t* __restrict__ parent,
                                                  const int32_t* __restrict__ csize, int32_t* __restrict__ mark,
                                                  int32_t* __restrict__ queue, int32_t* __restrict__ qtop,
                                                  int32_t* __restrict__ tgt) {
@@ -659,7 +663,7 @@ __global__ void __launch_bounds__(64) k_cn_small(CnDims d, int tag, const int32_
     const int b = (int)(i / d.P);
     const size_t base = (size_t)b * d.P;
     const int r = (int)(i - base);
-    if (parent[i] != r || csize[i] >= d.min_size) return;
+    if (parent[i] != r || csize[i] >= d.min_size || csize[i] < min_n) return;
     const int n = csize[i];
     int32_t* q = queue + base + atomicAdd(&qtop[b], n);
     int size = 1, visited = 0, last = -1;
@@ -693,6 +697,269 @@ __global__ void __launch_bounds__(256) k_cn_write(CnDims d, const int32_t* __res
         if (csize[base + r] >= d.min_size) { lab = rank[base + r]; break; }
         const int t = tgt[base + r];
         if (t < 0) { lab = 0; break; }
+        r = t;
+    }
+    out[i] = lab;
+}
+
+// ------------------------------------------- connectivity enforcement, tile-local first round
+// The first round has every pixel pending, so its labelling needs no pending plane, and most of its unions are between
+// pixels a few rows apart.  k_cn_tile labels a CN_TW x CN_TH tile in LDS and writes each pixel's parent as the image index
+// of its tile-local root; k_cn_border joins across tile borders with ccl_union on global memory; k_cn_finish compresses and
+// adds the tile-local sizes at the final roots; k_cn_flag, which needs the finished sizes, flags the kept roots in one word
+// per row segment (ranked by k_cn_rank), counts the components of max_size pixels or more and lists the roots below
+// min_size; k_cn_replay replays those from an on-chip queue; k_cn_label writes the labels.  With a component of max_size or
+// more the call starts over with the rounds above: real SLIC maps have none.
+//
+// Why the loops end, and why a root is its component's smallest raster index.  Inside a tile the index is
+// t = row * CN_TW + column, so for two pixels of one tile t1 < t2 exactly when their image indices p1 < p2.  k_cn_tile
+// keeps the rule of ggc_ccl.h on t (run start, then atomicMin of the smaller root at the larger), so a tile-local root is
+// the smallest t of its piece, and the image index written for a pixel is that of a pixel of its own piece no larger
+// than its own.  From there on parent[] holds image indices only; k_cn_border stores through ccl_union (the smaller of
+// two roots at the larger) and k_cn_finish stores roots, so every store is again an index no larger than the pixel's own.
+constexpr int CN_TW = 64, CN_TH = 16;       // a tile row is a wave; four rows per wave of the 256-thread block
+constexpr int CN_QCAP = 256;                // pixels the on-chip replay queue holds; a larger small component is replayed by k_cn_small
+constexpr int CN_SEEN_ROW = 2 * CN_QCAP / 32;   // words per row of the visited bitmap: columns -CN_QCAP .. CN_QCAP - 1 around the root
+static_assert(CN_TW == 64 && CN_TH % 4 == 0, "a tile row is one wave, the rows split over four waves");
+typedef unsigned long long cn_word;
+
+__global__ void __launch_bounds__(256) k_cn_tile(CnDims d, const int32_t* __restrict__ raw, int32_t* __restrict__ parent,
+                                                 int32_t* __restrict__ csize, cn_word* __restrict__ troot) {
+    constexpr int RPW = CN_TH / 4;
+    __shared__ int s_lab[CN_TH * CN_TW], s_par[CN_TH * CN_TW], s_cnt[CN_TH * CN_TW];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int x = blockIdx.x * CN_TW + lane, y0 = blockIdx.y * CN_TH;
+    const size_t base = (size_t)blockIdx.z * d.P;
+    int lab[RPW], root[RPW];
+    bool on[RPW], same_left[RPW];
+#pragma unroll
+    for (int j = 0; j < RPW; ++j) {
+        const int ty = wave * RPW + j, t = ty * CN_TW + lane;
+        on[j] = x < d.W && y0 + ty < d.H;
+        lab[j] = on[j] ? raw[base + (size_t)(y0 + ty) * d.W + x] : 0;
+        const int left = __shfl_up(lab[j], 1, 64);
+        same_left[j] = on[j] && lane > 0 && left == lab[j];        // lane - 1 is in the image when this lane is
+        const int first = ccl_run_first(on[j], same_left[j], t);
+        s_lab[t] = lab[j];
+        s_par[t] = on[j] ? first : t;
+        s_cnt[t] = 0;
+    }
+    __syncthreads();
+    // the pixel above is in the image when this one is; rows of other waves were written before the barrier
+#pragma unroll
+    for (int j = 0; j < RPW; ++j) {
+        const int ty = wave * RPW + j, t = ty * CN_TW + lane;
+        if (on[j] && ty > 0 && s_lab[t - CN_TW] == lab[j] && !(same_left[j] && s_lab[t - CN_TW - 1] == lab[j]))
+            ccl_union_lds(s_par, t, t - CN_TW);
+    }
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < RPW; ++j) {
+        const int ty = wave * RPW + j, t = ty * CN_TW + lane;
+        root[j] = on[j] ? ccl_find_lds(s_par, t) : t;
+        const cn_word vmask = __ballot(on[j]);
+        const cn_word starts = __ballot(on[j] && (!same_left[j] || lane == 0));
+        if (on[j] && ((starts >> lane) & 1ull)) atomicAdd(&s_cnt[root[j]], ccl_run_length(starts, vmask, lane));
+    }
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < RPW; ++j) {
+        const int ty = wave * RPW + j, t = ty * CN_TW + lane, y = y0 + ty;
+        const bool is_root = on[j] && root[j] == t;
+        const cn_word roots = __ballot(is_root);
+        if (y >= d.H) continue;                                     // the whole wave: y does not depend on the lane
+        if (lane == 0) troot[((size_t)blockIdx.z * d.H + y) * gridDim.x + blockIdx.x] = roots;
+        if (!on[j]) continue;
+        const size_t p = base + (size_t)y * d.W + x;
+        parent[p] = (y0 + root[j] / CN_TW) * d.W + blockIdx.x * CN_TW + root[j] % CN_TW;
+        if (is_root) csize[p] = s_cnt[t];
+    }
+}
+
+// One thread per pixel of a tile's first column (joined to the pixel on its left) or first row (to the pixel above); the
+// image's own first column and row have no such neighbour.  A pair is left out where the pair before it along the border
+// joins the same two pieces: both of its pixels are then in the tiles of this pair's and touch them there.
+__global__ void __launch_bounds__(256) k_cn_border(CnDims d, const int32_t* __restrict__ raw, int32_t* __restrict__ parent) {
+    const int nvb = (d.W - 1) / CN_TW, nhb = (d.H - 1) / CN_TH;
+    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= nvb * d.H + nhb * d.W) return;
+    const size_t base = (size_t)blockIdx.y * d.P;
+    const int32_t* r = raw + base;
+    int32_t* par = parent + base;
+    if (idx < nvb * d.H) {
+        const int x = (idx / d.H + 1) * CN_TW, y = idx % d.H, p = y * d.W + x;
+        if (r[p] != r[p - 1]) return;
+        if (y % CN_TH != 0 && r[p - d.W] == r[p] && r[p - d.W - 1] == r[p]) return;
+        ccl_union(par, p, p - 1);
+    } else {
+        const int j = idx - nvb * d.H;
+        const int y = (j / d.W + 1) * CN_TH, x = j % d.W, p = y * d.W + x;
+        if (r[p] != r[p - d.W]) return;
+        if (x % CN_TW != 0 && r[p - 1] == r[p] && r[p - d.W - 1] == r[p]) return;
+        ccl_union(par, p, p - d.W);
+    }
+}
+
+// Compress; a tile-local root that is not its component's root hands its piece's size on.  csize is complete at the roots
+// when the launch ends, not before: nothing here reads it at a root.
+__global__ void __launch_bounds__(256) k_cn_finish(CnDims d, int32_t* __restrict__ parent, int32_t* __restrict__ csize,
+                                                   const cn_word* __restrict__ troot) {
+    const int lane = threadIdx.x & 63, x = blockIdx.x * CN_TW + lane, y = blockIdx.y * 4 + (threadIdx.x >> 6);
+    if (x >= d.W || y >= d.H) return;
+    const size_t base = (size_t)blockIdx.z * d.P;
+    int32_t* par = parent + base;
+    const int p = y * d.W + x;
+    const int p0 = __hip_atomic_load(&par[p], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (p0 == p) return;
+    const int r = ccl_find(par, p0);
+    if (r != p0) par[p] = r;
+    if ((troot[((size_t)blockIdx.z * d.H + y) * gridDim.x + blockIdx.x] >> lane) & 1ull) atomicAdd(&csize[base + r], csize[base + p]);
+}
+
+// counters: [0] components of max_size or more, [1] the longest list of an image (k_cn_rank), [2] small components that the
+// queue cannot hold.  The roots to replay are listed per image, list[b * P ..] with lcount[b] entries: one counter for the
+// whole batch took 64 000 returning atomics on one address, 0.56 ms per launch at batch 256.
+__global__ void __launch_bounds__(256) k_cn_flag(CnDims d, const int32_t* __restrict__ parent, const int32_t* __restrict__ csize,
+                                                 cn_word* __restrict__ kmask, int32_t* __restrict__ counters,
+                                                 int32_t* __restrict__ lcount, int32_t* __restrict__ list) {
+    const int lane = threadIdx.x & 63, x = blockIdx.x * CN_TW + lane, y = blockIdx.y * 4 + (threadIdx.x >> 6);
+    if (y >= d.H) return;
+    const size_t i = (size_t)blockIdx.z * d.P + (size_t)y * d.W + x;
+    const bool root = x < d.W && parent[i] == y * d.W + x;
+    const int n = root ? csize[i] : 0;
+    const bool small = root && n < d.min_size, fits = small && n <= CN_QCAP;
+    const cn_word kept = __ballot(root && n >= d.min_size), big = __ballot(root && n >= d.max_size);
+    const cn_word listed = __ballot(fits), spilled = __ballot(small && !fits);
+    if (lane == 0) {
+        kmask[((size_t)blockIdx.z * d.H + y) * gridDim.x + blockIdx.x] = kept;
+        if (big) atomicAdd(&counters[0], __popcll(big));
+        if (spilled) atomicAdd(&counters[2], __popcll(spilled));
+    }
+    if (!listed) return;
+    int pos = 0;
+    if (lane == 0) pos = atomicAdd(&lcount[blockIdx.z], __popcll(listed));
+    pos = __shfl(pos, 0, 64);
+    if (fits) list[(size_t)blockIdx.z * d.P + pos + ccl_rank_in_word(listed, lane)] = y * d.W + x;
+}
+
+// prefix[b][s] = kept roots of image b in the row segments before s; n_nodes = max(total, 1).  One block per image.
+__global__ void __launch_bounds__(256) k_cn_rank(int n_seg, const cn_word* __restrict__ kmask, int32_t* __restrict__ prefix,
+                                                 int32_t* __restrict__ n_nodes, const int32_t* __restrict__ lcount,
+                                                 int32_t* __restrict__ counters) {
+    __shared__ int32_t wsum[4];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const size_t off = (size_t)blockIdx.x * n_seg;
+    int32_t carry = 0;
+    for (int s0 = 0; s0 < n_seg; s0 += 256) {
+        const int s = s0 + tid;
+        const int32_t c = s < n_seg ? __popcll(kmask[off + s]) : 0;
+        int32_t incl = c;
+        for (int o = 1; o < 64; o <<= 1) { const int32_t v = __shfl_up(incl, o, 64); if (lane >= o) incl += v; }
+        if (lane == 63) wsum[wave] = incl;
+        __syncthreads();
+        int32_t run = carry + incl - c, total = 0;
+#pragma unroll
+        for (int w = 0; w < 4; ++w) { if (w < wave) run += wsum[w]; total += wsum[w]; }
+        if (s < n_seg) prefix[off + s] = run;
+        carry += total;
+        __syncthreads();
+    }
+    if (tid == 0) {
+        n_nodes[blockIdx.x] = carry > 0 ? carry : 1;
+        if (lcount[blockIdx.x] > 0) atomicMax(&counters[1], lcount[blockIdx.x]);
+    }
+}
+
+// The replay of k_cn_small by one wave per listed root, with the queue and the visited set in LDS.  The wave pops up to 64
+// queued pixels at once, a lane each, and loads their four neighbours' parents together.  Pixels already in the queue were
+// going to be popped in that order anyway, so only two things depend on the order inside the batch.  `last` is the
+// neighbour of an earlier component seen last: the highest direction of the highest lane that has one.  The pixels to
+// append are taken in (lane, direction) order, the first occurrence of each: the wave walks the candidates in that order,
+// and a pixel taken is struck from every later lane's candidates.  The visited set is a bitmap around the root: a pixel of
+// a component of n <= CN_QCAP pixels lies in rows 0 .. n - 1 below the root and fewer than n columns to either side.
+__global__ void __launch_bounds__(64) k_cn_replay(CnDims d, const int32_t* __restrict__ parent, const int32_t* __restrict__ csize,
+                                                  const int32_t* __restrict__ list, const int32_t* __restrict__ lcount,
+                                                  int32_t* __restrict__ tgt) {
+    __shared__ int s_q[CN_QCAP];
+    __shared__ unsigned s_seen[CN_QCAP * CN_SEEN_ROW];
+    const int lane = threadIdx.x;
+    if ((int)blockIdx.x >= lcount[blockIdx.y]) return;             // the grid is as wide as the longest list
+    const size_t base = (size_t)blockIdx.y * d.P;
+    const int32_t* par = parent + base;
+    const int r = list[base + blockIdx.x], yr = r / d.W, xr = r - yr * d.W;
+    const size_t i = base + r;
+    const int n = min(csize[i], CN_QCAP);
+    for (int k = lane; k < n * CN_SEEN_ROW; k += 64) s_seen[k] = 0;
+    __syncthreads();
+    if (lane == 0) { s_q[0] = r; s_seen[CN_QCAP >> 5] = 1u << (CN_QCAP & 31); }
+    __syncthreads();
+    int head = 0, size = 1, last = -1;
+    while (head < size) {
+        const int cnt = min(64, size - head);
+        const bool active = lane < cnt;
+        const int pc = active ? s_q[head + lane] : 0;
+        const int yc = pc / d.W, xc = pc - yc * d.W;
+        int pp[4], rp[4], word[4];
+        unsigned bit[4];
+        bool inb[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int xx = xc + (k == 0 ? 1 : k == 1 ? -1 : 0), yy = yc + (k == 2 ? 1 : k == 3 ? -1 : 0);
+            inb[k] = active && xx >= 0 && xx < d.W && yy >= 0 && yy < d.H;
+            pp[k] = yy * d.W + xx;
+            rp[k] = inb[k] ? par[pp[k]] : 0x7FFFFFFF;
+            const int dy = yy - yr, col = xx - xr + CN_QCAP;
+            const bool in_map = dy >= 0 && dy < n && col >= 0 && col < 2 * CN_QCAP;     // true for every pixel of the component
+            word[k] = in_map ? dy * CN_SEEN_ROW + (col >> 5) : -1;
+            bit[k] = 1u << (col & 31);
+        }
+        int mine = -1;
+        unsigned m = 0;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            if (rp[k] == r) { if (word[k] >= 0 && !(s_seen[word[k]] & bit[k])) m |= 1u << k; }
+            else if (rp[k] < r) mine = rp[k];
+        }
+        const cn_word have = __ballot(mine >= 0);
+        if (have) last = __shfl(mine, 63 - __clzll((long long)have), 64);
+        for (;;) {
+            const cn_word todo = __ballot(m != 0);
+            if (!todo || size >= n) break;
+            const int src = __ffsll((long long)todo) - 1;
+            const int k0 = __ffs((int)m) - 1;                       // of this lane; the one of lane src is used
+            const int c = __shfl(k0 == 0 ? pp[0] : k0 == 1 ? pp[1] : k0 == 2 ? pp[2] : pp[3], src, 64);
+            const int cw = __shfl(k0 == 0 ? word[0] : k0 == 1 ? word[1] : k0 == 2 ? word[2] : word[3], src, 64);
+            const unsigned cb = __shfl(k0 == 0 ? bit[0] : k0 == 1 ? bit[1] : k0 == 2 ? bit[2] : bit[3], src, 64);
+            if (lane == 0) { s_q[size] = c; s_seen[cw] |= cb; }
+            size += 1;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) if (pp[k] == c) m &= ~(1u << k);
+        }
+        head += cnt;
+        __syncthreads();
+    }
+    if (lane == 0) tgt[i] = last;
+}
+
+// k_cn_write's chain rule; the rank of a kept root comes from its row segment's prefix and flag word.
+__global__ void __launch_bounds__(256) k_cn_label(CnDims d, int n_tx, const int32_t* __restrict__ parent,
+                                                  const int32_t* __restrict__ csize, const int32_t* __restrict__ tgt,
+                                                  const cn_word* __restrict__ kmask, const int32_t* __restrict__ prefix,
+                                                  int32_t* __restrict__ out) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (size_t)d.B * d.P) return;
+    const size_t b = i / d.P, base = b * d.P;
+    int r = parent[i];
+    int lab = 0;
+    for (;;) {
+        if (csize[base + r] >= d.min_size) {
+            const int yr = r / d.W, xr = r - yr * d.W;
+            const size_t s = (b * d.H + yr) * n_tx + xr / CN_TW;
+            lab = prefix[s] + ccl_rank_in_word(kmask[s], xr % CN_TW);
+            break;
+        }
+        const int t = tgt[base + r];
+        if (t < 0) break;
         r = t;
     }
     out[i] = lab;
@@ -745,6 +1012,98 @@ static Grid regular_grid(int H, int W, int n_points) {
 
 using namespace ggc;
 
+// The rounds on a pending plane: label what is pending, settle the components below max_size, carve the others, again.
+static int connectivity_rounds(ggc_ctx* ctx, hipStream_t st, const CnDims& cd, const int32_t* raw, int32_t* segments,
+                               int32_t* n_nodes) {
+    ProfScope prof(ctx, st, "slic_cn_rounds");
+    const int B = cd.B, H = cd.H, W = cd.W;
+    const size_t BP = (size_t)B * cd.P;
+    int32_t* work = scratch_t<int32_t>(ctx, S_SLIC_AUX3, BP * 6 + (size_t)B * (size_t)cd.max_size + 2 * (size_t)B + 16);
+    uint8_t* pending = scratch_t<uint8_t>(ctx, S_SLIC_AUX4, BP);
+    if (!work || !pending) return GGC_E_OOM;
+    int32_t *parent = work, *csize = work + BP, *rank = work + 2 * BP, *tgt = work + 3 * BP, *mark = work + 4 * BP;
+    int32_t* queue = work + 5 * BP;                       // per image P (+ max_size slack at the very end)
+    int32_t* qtop = work + 6 * BP + (size_t)B * cd.max_size;
+    int32_t* n_big = qtop + B;
+    GGC_HIP(ctx, hipMemsetAsync(pending, 1, BP, st));
+    GGC_HIP(ctx, hipMemsetAsync(mark, 0, sizeof(int32_t) * BP, st));
+    const dim3 g1(cdiv(BP, 256)), g2(cdiv(W, 64), cdiv(H, 4), B), g64(cdiv(BP, 64));
+    for (int round = 0; round < 4096; ++round) {
+        GGC_HIP(ctx, hipMemsetAsync(qtop, 0, sizeof(int32_t) * (B + 1), st));
+        hipLaunchKernelGGL(k_cn_reset, g1, dim3(256), 0, st, cd, raw, pending, parent, csize);
+        hipLaunchKernelGGL(k_cn_merge, g2, dim3(256), 0, st, cd, raw, pending, parent);
+        hipLaunchKernelGGL(k_cn_size, g1, dim3(256), 0, st, cd, raw, pending, parent, csize);
+        hipLaunchKernelGGL(k_cn_settle, g1, dim3(256), 0, st, cd, pending, parent, csize, n_big);
+        GGC_LAUNCH_CHECK(ctx);
+        int32_t h_big = 0;
+        GGC_HIP(ctx, hipMemcpyAsync(&h_big, n_big, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        GGC_HIP(ctx, hipStreamSynchronize(st));
+        if (h_big == 0) break;
+        hipLaunchKernelGGL(k_cn_carve, g64, dim3(64), 0, st, cd, round + 1, pending, parent, csize, mark, queue, qtop);
+        GGC_LAUNCH_CHECK(ctx);
+    }
+    hipLaunchKernelGGL(k_cn_kept, g1, dim3(256), 0, st, cd, parent, csize, rank);
+    hipLaunchKernelGGL(k_cn_scan, dim3(B), dim3(1024), 0, st, cd, rank, n_nodes);
+    GGC_HIP(ctx, hipMemsetAsync(qtop, 0, sizeof(int32_t) * (B + 1), st));
+    hipLaunchKernelGGL(k_cn_small, g64, dim3(64), 0, st, cd, 0x7FFFFFFF, 0, parent, csize, mark, queue, qtop, tgt);
+    hipLaunchKernelGGL(k_cn_write, g1, dim3(256), 0, st, cd, parent, csize, rank, tgt, segments);
+    GGC_LAUNCH_CHECK(ctx);
+    return GGC_OK;
+}
+
+// The tile-local first round.  done = false: a component has max_size pixels or more, nothing was written, and the caller
+// runs the rounds above from the start (they size the scratch slot for themselves; its content is not kept on growth, which
+// is why the call does not go on from this labelling).  The mark, queue and pending planes are neither allocated nor touched
+// unless min_size allows a small component larger than the on-chip queue; then the ones that are (counters[2]) go through
+// k_cn_small, which needs a mark plane and a queue.
+static int connectivity_tiles(ggc_ctx* ctx, hipStream_t st, const CnDims& cd, const int32_t* raw, int32_t* segments,
+                              int32_t* n_nodes, bool& done) {
+    const int B = cd.B, H = cd.H, W = cd.W, n_tx = cdiv(W, CN_TW), n_seg = H * n_tx;
+    const size_t BP = (size_t)B * cd.P, n_words = (size_t)B * n_seg;
+    const bool may_spill = cd.min_size - 1 > CN_QCAP;
+    int32_t *parent, *csize, *tgt, *list, *prefix, *counters, *lcount, *mark = nullptr, *queue = nullptr, *qtop = nullptr;
+    cn_word *troot, *kmask;
+    if (!carve_scratch(ctx, S_SLIC_AUX3, [&](Carve& c) {
+            parent = c.take<int32_t>(BP); csize = c.take<int32_t>(BP); tgt = c.take<int32_t>(BP); list = c.take<int32_t>(BP);
+            troot = c.take<cn_word>(n_words); kmask = c.take<cn_word>(n_words); prefix = c.take<int32_t>(n_words);
+            counters = c.take<int32_t>(4 + (size_t)B); lcount = counters + 4;
+            if (may_spill) { mark = c.take<int32_t>(BP); queue = c.take<int32_t>(BP); qtop = c.take<int32_t>((size_t)B + 1); }
+        }))
+        return GGC_E_OOM;
+    const dim3 g_tile(n_tx, cdiv(H, CN_TH), B), g_row(n_tx, cdiv(H, 4), B);
+    const int n_border = ((W - 1) / CN_TW) * H + ((H - 1) / CN_TH) * W;
+    std::vector<int32_t> h;
+    {
+        ProfScope tiles(ctx, st, "slic_cn_tiles");
+        GGC_HIP(ctx, hipMemsetAsync(counters, 0, sizeof(int32_t) * (4 + (size_t)B), st));
+        hipLaunchKernelGGL(k_cn_tile, g_tile, dim3(256), 0, st, cd, raw, parent, csize, troot);
+        if (n_border > 0) hipLaunchKernelGGL(k_cn_border, dim3(cdiv(n_border, 256), B), dim3(256), 0, st, cd, raw, parent);
+        hipLaunchKernelGGL(k_cn_finish, g_row, dim3(256), 0, st, cd, parent, csize, troot);
+        hipLaunchKernelGGL(k_cn_flag, g_row, dim3(256), 0, st, cd, parent, csize, kmask, counters, lcount, list);
+        hipLaunchKernelGGL(k_cn_rank, dim3(B), dim3(256), 0, st, n_seg, kmask, prefix, n_nodes, lcount, counters);
+        GGC_LAUNCH_CHECK(ctx);
+        const int rc = read_i32(ctx, st, counters, 3, h);
+        if (rc != GGC_OK) return rc;
+    }
+    if (h[0] > 0) return GGC_OK;                                // done stays false
+    if (h[1] > 0) {
+        ProfScope replay(ctx, st, "slic_cn_replay");
+        hipLaunchKernelGGL(k_cn_replay, dim3(h[1], B), dim3(64), 0, st, cd, parent, csize, list, lcount, tgt);
+    }
+    if (h[2] > 0) {
+        ProfScope spill(ctx, st, "slic_cn_spill");
+        GGC_REQUIRE(ctx, may_spill, GGC_E_DEVICE, "SLIC connectivity: %d small components above the queue capacity", h[2]);
+        GGC_HIP(ctx, hipMemsetAsync(mark, 0, sizeof(int32_t) * BP, st));
+        GGC_HIP(ctx, hipMemsetAsync(qtop, 0, sizeof(int32_t) * ((size_t)B + 1), st));
+        hipLaunchKernelGGL(k_cn_small, dim3(cdiv(BP, 64)), dim3(64), 0, st, cd, 0x7FFFFFFF, CN_QCAP + 1, parent, csize, mark,
+                           queue, qtop, tgt);
+    }
+    hipLaunchKernelGGL(k_cn_label, dim3(cdiv(BP, 256)), dim3(256), 0, st, cd, n_tx, parent, csize, tgt, kmask, prefix, segments);
+    GGC_LAUNCH_CHECK(ctx);
+    done = true;
+    return GGC_OK;
+}
+
 static int enforce_connectivity(ggc_ctx* ctx, hipStream_t st, int B, int H, int W, const int32_t* raw, int min_size,
                                 int max_size, int32_t* segments, int32_t* n_nodes) {
     const size_t P = (size_t)H * W;
@@ -758,42 +1117,15 @@ static int enforce_connectivity(ggc_ctx* ctx, hipStream_t st, int B, int H, int 
         GGC_LAUNCH_CHECK(ctx);
         return GGC_OK;
     }
-    {
-        ProfScope prof(ctx, st, "slic_connectivity");
-        const size_t BP = (size_t)B * P;
-        const CnDims cd{B, H, W, (int)P, min_size, std::max(max_size, 1)};
-        int32_t* work = scratch_t<int32_t>(ctx, S_SLIC_AUX3, BP * 6 + (size_t)B * (size_t)cd.max_size + 2 * (size_t)B + 16);
-        uint8_t* pending = scratch_t<uint8_t>(ctx, S_SLIC_AUX4, BP);
-        if (!work || !pending) return GGC_E_OOM;
-        int32_t *parent = work, *csize = work + BP, *rank = work + 2 * BP, *tgt = work + 3 * BP, *mark = work + 4 * BP;
-        int32_t* queue = work + 5 * BP;                       // per image P (+ max_size slack at the very end)
-        int32_t* qtop = work + 6 * BP + (size_t)B * cd.max_size;
-        int32_t* n_big = qtop + B;
-        GGC_HIP(ctx, hipMemsetAsync(pending, 1, BP, st));
-        GGC_HIP(ctx, hipMemsetAsync(mark, 0, sizeof(int32_t) * BP, st));
-        const dim3 g1(cdiv(BP, 256)), g2(cdiv(W, 64), cdiv(H, 4), B), g64(cdiv(BP, 64));
-        for (int round = 0; round < 4096; ++round) {
-            GGC_HIP(ctx, hipMemsetAsync(qtop, 0, sizeof(int32_t) * (B + 1), st));
-            hipLaunchKernelGGL(k_cn_reset, g1, dim3(256), 0, st, cd, raw, pending, parent, csize);
-            hipLaunchKernelGGL(k_cn_merge, g2, dim3(256), 0, st, cd, raw, pending, parent);
-            hipLaunchKernelGGL(k_cn_size, g1, dim3(256), 0, st, cd, raw, pending, parent, csize);
-            hipLaunchKernelGGL(k_cn_settle, g1, dim3(256), 0, st, cd, pending, parent, csize, n_big);
-            GGC_LAUNCH_CHECK(ctx);
-            int32_t h_big = 0;
-            GGC_HIP(ctx, hipMemcpyAsync(&h_big, n_big, sizeof(int32_t), hipMemcpyDeviceToHost, st));
-            GGC_HIP(ctx, hipStreamSynchronize(st));
-            if (h_big == 0) break;
-            hipLaunchKernelGGL(k_cn_carve, g64, dim3(64), 0, st, cd, round + 1, pending, parent, csize, mark, queue, qtop);
-            GGC_LAUNCH_CHECK(ctx);
-        }
-        hipLaunchKernelGGL(k_cn_kept, g1, dim3(256), 0, st, cd, parent, csize, rank);
-        hipLaunchKernelGGL(k_cn_scan, dim3(B), dim3(1024), 0, st, cd, rank, n_nodes);
-        GGC_HIP(ctx, hipMemsetAsync(qtop, 0, sizeof(int32_t) * (B + 1), st));
-        hipLaunchKernelGGL(k_cn_small, g64, dim3(64), 0, st, cd, 0x7FFFFFFF, parent, csize, mark, queue, qtop, tgt);
-        hipLaunchKernelGGL(k_cn_write, g1, dim3(256), 0, st, cd, parent, csize, rank, tgt, segments);
-        GGC_LAUNCH_CHECK(ctx);
+    ProfScope prof(ctx, st, "slic_connectivity");
+    const size_t BP = (size_t)B * P;
+    const CnDims cd{B, H, W, (int)P, min_size, std::max(max_size, 1)};
+    if (knobs().slic_cn_tiles) {
+        bool done = false;
+        const int rc = connectivity_tiles(ctx, st, cd, raw, segments, n_nodes, done);
+        if (rc != GGC_OK || done) return rc;
     }
-    return GGC_OK;
+    return connectivity_rounds(ctx, st, cd, raw, segments, n_nodes);
 }
 
 extern "C" int ggc_slic(ggc_ctx* ctx, ggc_stream stream, int B, int H, int W, const float* image,

@@ -38,7 +38,13 @@
  *                                 0..64, larger values are clamped to 64: a partial round never closes an image)
  *   GGC_AGG_DIRECT=1              GCNConv gather straight from L2 instead of the graph-resident kernel
  *   GGC_SLIC_SEQ_CONNECTIVITY=1   literal one-thread-per-image replay of skimage's connectivity pass (A/B reference)
- *   GGC_GRAPH_ONCHIP=0|1|2        region-graph topology of ggc_graph_count from on-chip pair tables instead of the dense
+ *   GGC_SLIC_CN_TILES=0           SLIC connectivity by the rounds on a pending plane throughout (default 1: the first round labels
+ *                                 64 x 16 tiles in LDS and replays the components below min_size from an on-chip queue of 256
+ *                                 pixels).  Profiler scopes inside "slic_connectivity" tell what ran: "slic_cn_tiles" the tile
+ *                                 round, "slic_cn_replay" the on-chip replay, "slic_cn_spill" the replay of small components
+ *                                 above 256 pixels through global memory, "slic_cn_rounds" the rounds on the pending plane
+ *                                 (the knob at 0, or a component of max_size pixels or more)
+ *   GGC_GRAPH_ONCHIP=0|1|2       region-graph topology of ggc_graph_count from on-chip pair tables instead of the dense
  *                                 B x N x N matrix: 0 never, 1 (default) for batches of at least 24 images, 2 at any batch size;
  *                                 in each case only where an image has at most 704 regions, 6144 distinct adjacent pairs and
  *                                 n_nonlocal <= 8, else the dense kernels run (same outputs, byte for byte)
@@ -175,7 +181,7 @@ int ggc_slic_rgb(ggc_ctx* ctx, ggc_stream stream, int B, int H, int W,
 
 /* Step 7 of ggc_slic alone — skimage's _enforce_label_connectivity_cython
  * (SURVEY Appendix A.1): raw_labels, segments [dev] i32 [B,H,W]; n_nodes [dev] i32 [B].
- * SYNCHRONISES the stream once per carve round (components of >= max_size pixels). */
+ * SYNCHRONISES the stream once, and once more per carve round (components of >= max_size pixels). */
 int ggc_slic_enforce_connectivity(ggc_ctx* ctx, ggc_stream stream, int B, int H, int W,
                                   const int32_t* raw_labels, int min_size, int max_size,
                                   int32_t* segments, int32_t* n_nodes);
