@@ -66,11 +66,16 @@ __device__ __forceinline__ void mf_plane_caps(const GcDims& d, int b, int p, con
 // the tiles' dirty words cover arcs re-opened from a neighbouring tile (ggc_mf_sweep.h).
 // Bounds: |tw| <= 2^27 and 8 capacities <= 2^24 each give |ex - snk| <= 2^27 + 8 * 2^24 = 2^28 (< 3 * 2^27), and
 // |tw - tw_old| <= 2^28, so the new balance stays within 2^29 in int32.
-__device__ __forceinline__ void mf_warm_pixel(size_t i, int32_t tw, int32_t tw_old, int32_t* __restrict__ ex,
-                                              int32_t* __restrict__ snk) {
-    const int32_t bal = (ex[i] - snk[i]) + (tw - tw_old);
+// ex_old, snk_old: the pixel's words as loaded by the caller (k_build_graph issues them with its other loads)
+__device__ __forceinline__ void mf_warm_pixel(size_t i, int32_t tw, int32_t tw_old, int32_t ex_old, int32_t snk_old,
+                                              int32_t* __restrict__ ex, int32_t* __restrict__ snk) {
+    const int32_t bal = (ex_old - snk_old) + (tw - tw_old);
     ex[i] = bal > 0 ? bal : 0;
     snk[i] = bal < 0 ? -bal : 0;
+}
+__device__ __forceinline__ void mf_warm_pixel(size_t i, int32_t tw, int32_t tw_old, int32_t* __restrict__ ex,
+                                              int32_t* __restrict__ snk) {
+    mf_warm_pixel(i, tw, tw_old, ex[i], snk[i], ex, snk);
 }
 
 // The max-flow's words in ggc_grabcut's control block, which the start of every call zeroes.
