@@ -42,6 +42,7 @@ enum Slot : int {
     S_OUTLINE, S_OUTLINE_LIST,
     S_DIST, S_DIST_TMP,
     S_WAND,
+    S_CLONE, S_CLONE_VEC,
     S_COUNT
 };
 

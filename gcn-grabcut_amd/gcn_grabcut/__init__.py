@@ -30,7 +30,8 @@ from .pipeline import (GCNGrabCutPipeline, ClosedFormMatte, ForegroundColours, F
                        Scissors, trace_boundary, Wand, wand_select, wand_select_batch, paint_wand,
                        Outline, mask_outlines, mask_outlines_batch, outlines_svg_path, outlines_to_lassos,
                        ModifyMask, mask_distance, mask_distance_batch, modify_mask, modify_mask_batch, grow_mask,
-                       shrink_mask, open_mask, close_mask, border_mask, mask_to_trimap)
+                       shrink_mask, open_mask, close_mask, border_mask, mask_to_trimap,
+                       Clone, composite_over, composite_over_batch, seamless_clone, seamless_clone_batch)
 from .synthetic import synthetic_image, synthetic_batch
 from .losses import FocalLoss, LabelSmoothingCE, TrimapLoss
 from .trainer import Trainer, TrainConfig
@@ -55,6 +56,7 @@ __all__ = [
     "Outline", "mask_outlines", "mask_outlines_batch", "outlines_svg_path", "outlines_to_lassos",
     "ModifyMask", "mask_distance", "mask_distance_batch", "modify_mask", "modify_mask_batch", "grow_mask", "shrink_mask",
     "open_mask", "close_mask", "border_mask", "mask_to_trimap",
+    "Clone", "composite_over", "composite_over_batch", "seamless_clone", "seamless_clone_batch",
     "ResGCNNet", "GCNTrimapNet", "GATTrimapNet", "build_model", "probs_to_node_trimap", "project_to_pixels",
     "Data", "Batch", "synthetic_image", "synthetic_batch",
     "FocalLoss", "LabelSmoothingCE", "TrimapLoss", "Trainer", "TrainConfig",

@@ -644,6 +644,50 @@ class Engine:
                       iters.data_ptr(), rel.data_ptr())
         return (fg, rgba, iters, rel) if want_rgba else (fg, iters, rel)
 
+    def composite_over(self, rgba, background, offsets, out=None):
+        """The BGRA cut-outs rgba (B,Hs,Ws,4) uint8 placed on background (B,H,W,3) uint8 (ggc_composite_over): integer
+        alpha-over, (a c + (255 - a) bg + 127) // 255.  offsets: (B,2) integers on the host, row and column of each
+        cut-out's pixel (0, 0) in its background, negative allowed.
+        -> (B,H,W,3) uint8; out: preallocated (it may be background).  The call does not synchronise."""
+        off = check_composite_args(tuple(rgba.shape), tuple(background.shape), offsets, (rgba.dtype, background.dtype), 4,
+                                   "composite_over")
+        b, hs, ws, _ = rgba.shape
+        _, h, w, _ = background.shape
+        if out is None:
+            out = self.empty(b, h, w, 3, dtype=torch.uint8)
+        elif tuple(out.shape) != (b, h, w, 3) or out.dtype != torch.uint8:
+            raise ValueError(f"composite_over: out must be {(b, h, w, 3)} uint8, got {tuple(out.shape)} {out.dtype}")
+        rgba, background = rgba.contiguous(), background.contiguous()
+        self.ctx.call("ggc_composite_over", self._stream(), b, hs, ws, rgba.data_ptr(), h, w, background.data_ptr(),
+                      self.to_device(off).data_ptr(), out.data_ptr())
+        return out
+
+    def poisson_clone(self, source, mask, target, offsets, mixed, max_iter, tol, want_raw=False):
+        """Seamless cloning (ggc_poisson_clone): the pixels of source (B,Hs,Ws,3) uint8 selected by mask (B,Hs,Ws) uint8
+        (non-zero) cloned into target (B,H,W,3) uint8 in the gradient domain, with the source's gradients (mixed False)
+        or the stronger of the source's and the target's (mixed True).  offsets: (B,2) integers on the host, as
+        composite_over's, each within +-32768.
+        -> (composite (B,H,W,3) uint8, n_omega (B,) int32, iters (B,) int32, rel_residual (B,) float64), with want_raw
+        also raw (B,H,W,3) float64, the unclamped solution, after composite.  The call synchronises its stream."""
+        off = check_composite_args(tuple(source.shape), tuple(target.shape), offsets, (source.dtype, target.dtype), 3,
+                                   "poisson_clone")
+        check_clone_args(mixed, max_iter, tol)
+        b, hs, ws, _ = source.shape
+        _, h, w, _ = target.shape
+        if tuple(mask.shape) != (b, hs, ws):
+            raise ValueError(f"poisson_clone: mask {tuple(mask.shape)} does not match source {tuple(source.shape)}")
+        if mask.dtype != torch.uint8:
+            raise ValueError(f"poisson_clone: mask must be uint8, got {mask.dtype}")
+        comp = self.empty(b, h, w, 3, dtype=torch.uint8)
+        raw = self.empty(b, h, w, 3, dtype=torch.float64) if want_raw else None
+        n_omega, iters = self.empty(b, dtype=torch.int32), self.empty(b, dtype=torch.int32)
+        rel = self.empty(b, dtype=torch.float64)
+        source, mask, target = source.contiguous(), mask.contiguous(), target.contiguous()
+        self.ctx.call("ggc_poisson_clone", self._stream(), b, hs, ws, source.data_ptr(), mask.data_ptr(), h, w,
+                      target.data_ptr(), self.to_device(off).data_ptr(), int(bool(mixed)), int(max_iter), float(tol),
+                      comp.data_ptr(), _native.ptr(raw), n_omega.data_ptr(), iters.data_ptr(), rel.data_ptr())
+        return (comp, raw, n_omega, iters, rel) if want_raw else (comp, n_omega, iters, rel)
+
     def matte_errors(self, pred_u8, gt_u8, region=None, want_grad=True, want_levels=False):
         """The four matte errors of pred_u8 against gt_u8, both (B,H,W) uint8 alpha levels on the device
         (ggc_matte_errors); region (B,H,W) uint8 or None restricts the sums to its nonzero pixels.
@@ -780,6 +824,44 @@ def check_foreground_args(eps_r, omega, max_iter, tol) -> None:
         raise ValueError(f"foreground max_iter must be an integer in 1..{CF_MAX_ITER_MAX}, got {max_iter}")
     if not (np.isfinite(tol) and 1e-12 <= float(tol) < 1.0):
         raise ValueError(f"foreground tol must be in [1e-12, 1), got {tol}")
+
+
+CLONE_OFFSET_MAX = 32768
+CLONE_BATCH_MAX = 65535
+
+
+def check_composite_args(source_shape, target_shape, offsets, dtypes=(), channels=4, what="composite_over") -> np.ndarray:
+    """The shape rules of ggc_composite_over and ggc_poisson_clone, checked on the host so that a bad argument is a
+    ValueError: source (B,Hs,Ws,channels) and target (B,H,W,3) uint8 with B <= 65535 and every side in 1..32768; offsets
+    (B,2) integers within +-32768.  -> the offsets as a contiguous (B,2) int32 array."""
+    if len(source_shape) != 4 or source_shape[3] != channels or min(source_shape[1:3]) < 1:
+        raise ValueError(f"{what}: the source must be (B,Hs,Ws,{channels}), got {tuple(source_shape)}")
+    if len(target_shape) != 4 or target_shape[3] != 3 or min(target_shape[1:3]) < 1:
+        raise ValueError(f"{what}: the background must be (B,H,W,3), got {tuple(target_shape)}")
+    if source_shape[0] != target_shape[0]:
+        raise ValueError(f"{what}: {source_shape[0]} sources for {target_shape[0]} backgrounds")
+    if source_shape[0] > CLONE_BATCH_MAX or max(*source_shape[1:3], *target_shape[1:3]) > UPSAMPLE_SIDE_MAX:
+        raise ValueError(f"{what} takes at most {CLONE_BATCH_MAX} images of at most {UPSAMPLE_SIDE_MAX} on a side, got "
+                         f"{tuple(source_shape)} on {tuple(target_shape)}")
+    for d in dtypes:
+        if str(d).replace("torch.", "") != "uint8":                  # a torch or a numpy dtype
+            raise ValueError(f"{what}: images must be uint8, got {d}")
+    off = np.asarray(offsets)
+    if off.dtype.kind not in "iu" or off.shape != (source_shape[0], 2):
+        raise ValueError(f"{what}: offsets must be ({source_shape[0]}, 2) integers (row, col), got {off.shape} {off.dtype}")
+    if off.size and np.abs(off.astype(np.int64)).max() > CLONE_OFFSET_MAX:
+        raise ValueError(f"{what}: offsets must lie within +-{CLONE_OFFSET_MAX}, got {off.tolist()}")
+    return np.ascontiguousarray(off, np.int32)
+
+
+def check_clone_args(mixed, max_iter, tol) -> None:
+    """The argument range of ggc_poisson_clone, checked on the host so that a bad value is a ValueError."""
+    if not isinstance(mixed, (bool, np.bool_)) and mixed not in (0, 1):
+        raise ValueError(f"clone mixed must be a bool, got {mixed!r}")
+    if isinstance(max_iter, bool) or int(max_iter) != max_iter or not 1 <= int(max_iter) <= CF_MAX_ITER_MAX:
+        raise ValueError(f"clone max_iter must be an integer in 1..{CF_MAX_ITER_MAX}, got {max_iter}")
+    if not (np.isfinite(tol) and 1e-12 <= float(tol) < 1.0):
+        raise ValueError(f"clone tol must be in [1e-12, 1), got {tol}")
 
 
 MATTE_EVAL_BATCH_MAX = 65535

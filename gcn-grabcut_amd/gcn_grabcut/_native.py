@@ -90,6 +90,8 @@ SIGNATURES = {
     "ggc_closed_form_band": [_vp, _vp, _i, _i, _i, _vp, _i, _vp],
     "ggc_lift_labels": [_vp, _vp, _i, _i, _i, _vp, _i, _i, _i, _vp, _vp],
     "ggc_estimate_foreground": [_vp, _vp, _i, _i, _i, _vp, _vp, _f, _f, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp],
+    "ggc_composite_over": [_vp, _vp, _i, _i, _i, _vp, _i, _i, _vp, _vp, _vp],
+    "ggc_poisson_clone": [_vp, _vp, _i, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _f, _vp, _vp, _vp, _vp, _vp],
     "ggc_matte_errors": [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp],
     "ggc_mask_iou": [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp],
     "ggc_region_label_stats": [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp],

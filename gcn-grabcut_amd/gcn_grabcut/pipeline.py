@@ -113,6 +113,23 @@ class SegmentationResult:
         (additive; mask_to_trimap)."""
         return self.modified(ModifyMask("trimap", inner, outer), full=full)
 
+    def composite_onto(self, background: np.ndarray, offset=(0, 0), method: str = "over", full: bool = False) -> np.ndarray:
+        """This result placed on background (H, W, 3) uint8 BGR with its pixel (0, 0) at offset = (row, col) (additive).
+        method "over": alpha-over of the cleanest cut-out the result carries, rgba_clean, else rgba_soft, else rgba
+        (composite_over); "seamless" | "mixed": the image under binary_mask cloned in the gradient domain with the
+        source's or with mixed gradients (seamless_clone).  full=True uses result.full's members.  -> (H, W, 3) uint8 BGR."""
+        if method not in ("over", "seamless", "mixed"):
+            raise ValueError(f"composite_onto: method must be 'over', 'seamless' or 'mixed', got {method!r}")
+        if full and self.full is None:
+            raise ValueError("this result carries no full-resolution outputs: segment with full_image=...")
+        r = self.full if full else self
+        if method == "over":
+            clean = None if full else self.rgba_clean
+            return composite_over(clean if clean is not None else r.rgba_soft if r.rgba_soft is not None else r.rgba,
+                                  background, offset)
+        image = r.rgba[..., :3] if full else self.image          # the full-size cut-out keeps the full image's bytes
+        return seamless_clone(np.ascontiguousarray(image), r.binary_mask, background, offset, mixed=method == "mixed")
+
 
 def guided_filter(guide: np.ndarray, src: np.ndarray, radius: int = 8, eps: float = 1e-3, device="cuda") -> np.ndarray:
     """Edge-preserving filter of `src` under `guide` (He et al.) — reference pipeline.py:71-100."""
@@ -425,6 +442,130 @@ def estimate_foreground(image: np.ndarray, alpha: np.ndarray, eps_r: float = FG_
                                              eng.to_device(np.ascontiguousarray(a, np.float32)[None]), eps_r, omega,
                                              max_iter, tol)
     return _with_info(fg[0].cpu().numpy(), iters, rel, return_info)
+
+
+CLONE_MAX_ITER = 10000
+CLONE_TOL = 1e-7
+
+
+@dataclass(frozen=True)
+class Clone:
+    """The options of seamless cloning (ggc_poisson_clone, include/ggc.h O6).  mixed=False keeps the
+    source's gradients inside the pasted region ("seamless"); mixed=True takes, per pixel pair and channel, the stronger
+    of the source's and the target's gradient, so that the target's texture shows through flat parts of the source.
+    The solve stops when the residual falls to tol times its start, or after max_iter iterations.  The defaults are
+    recorded choices, not tuned results."""
+    mixed: bool = False
+    max_iter: int = CLONE_MAX_ITER
+    tol: float = CLONE_TOL
+
+    def __post_init__(self):
+        from ._engine import check_clone_args
+        if not isinstance(self.mixed, (bool, np.bool_)):
+            raise ValueError(f"Clone: mixed must be a bool, got {self.mixed!r}")
+        check_clone_args(self.mixed, self.max_iter, self.tol)
+
+    def args(self) -> "tuple[bool, int, float]":
+        return bool(self.mixed), int(self.max_iter), float(self.tol)
+
+
+def _offsets(offset, b: int, what: str) -> np.ndarray:
+    """One (row, col) pair for every image, or one pair per image -> (B, 2) int64."""
+    try:
+        off = np.asarray(offset)
+    except ValueError:
+        off = None
+    if off is None or off.dtype.kind not in "iu" or off.shape not in ((2,), (b, 2)):
+        raise ValueError(f"{what}: offset must be a (row, col) pair of integers, or one pair per image, got {offset!r}")
+    return np.broadcast_to(off.astype(np.int64), (b, 2))
+
+
+def _rgba_batch(cutouts, what: str) -> np.ndarray:
+    """A (B, Hs, Ws, 4) uint8 array, or a sequence of equally sized (Hs, Ws, 4) uint8 BGRA cut-outs -> (B, Hs, Ws, 4)."""
+    a = cutouts if isinstance(cutouts, np.ndarray) and cutouts.ndim == 4 else None
+    if a is None:
+        items = [np.asarray(c) for c in cutouts]
+        if any(c.ndim != 3 or c.shape != items[0].shape for c in items):
+            raise ValueError(f"{what} needs (Hs, Ws, 4) cut-outs of one size; group them by shape")
+        a = np.stack(items) if items else np.zeros((0, 1, 1, 4), np.uint8)
+    if a.dtype != np.uint8 or a.shape[3] != 4 or a.shape[1] < 1 or a.shape[2] < 1:
+        raise ValueError(f"{what}: cut-outs must be (Hs, Ws, 4) uint8 BGRA, got {a.shape[1:]} {a.dtype}")
+    return np.ascontiguousarray(a)
+
+
+def composite_over_batch(cutouts, backgrounds, offsets=(0, 0), device="cuda") -> np.ndarray:
+    """BGRA cut-outs placed on backgrounds by alpha-over (additive; ggc_composite_over).  cutouts:
+    (B, Hs, Ws, 4) uint8 or a sequence of equally sized cut-outs (rgba, rgba_soft or rgba_clean of a result); backgrounds:
+    (B, H, W, 3) uint8 BGR or a sequence of equally sized images; offsets: one (row, col) pair, or one per image, the
+    place of the cut-out's pixel (0, 0) in the background, negative allowed, within +-32768.  Integer arithmetic:
+    (a c + (255 - a) bg + 127) // 255 per channel where the cut-out covers the background, the background elsewhere.
+    -> (B, H, W, 3) uint8 BGR."""
+    from ._engine import check_composite_args, get_engine
+    rgba = _rgba_batch(cutouts, "composite_over_batch")
+    bg = _image_batch(backgrounds, "composite_over_batch")
+    if len(rgba) != len(bg):
+        raise ValueError(f"composite_over_batch: {len(rgba)} cut-outs for {len(bg)} backgrounds")
+    off = check_composite_args(rgba.shape, bg.shape, _offsets(offsets, len(bg), "composite_over_batch"),
+                               (rgba.dtype, bg.dtype), 4, "composite_over_batch")
+    if len(bg) == 0:
+        return bg.copy()
+    eng = get_engine(device)
+    return eng.composite_over(eng.to_device(rgba), eng.to_device(bg), off).cpu().numpy()
+
+
+def composite_over(rgba: np.ndarray, background: np.ndarray, offset=(0, 0), device="cuda") -> np.ndarray:
+    """One (Hs, Ws, 4) uint8 BGRA cut-out placed on an (H, W, 3) uint8 BGR background with its pixel (0, 0) at offset =
+    (row, col) (additive; composite_over_batch).  -> (H, W, 3) uint8 BGR."""
+    c = np.asarray(rgba)
+    if c.ndim != 3:
+        raise ValueError(f"composite_over: the cut-out must be (Hs, Ws, 4) uint8 BGRA, got {c.shape}")
+    return composite_over_batch(c[None], _check_image(background)[None], offset, device)[0]
+
+
+def seamless_clone_batch(sources, masks, targets, offsets=(0, 0), clone: Optional[Clone] = None, return_info: bool = False,
+                         device="cuda"):
+    """Seamless (Poisson) cloning of a batch (additive; ggc_poisson_clone).  sources: (B, Hs, Ws, 3)
+    uint8 BGR or a sequence of equally sized images; masks: (B, Hs, Ws), non-zero = selected; targets: (B, H, W, 3) uint8
+    BGR or a sequence of equally sized images; offsets as composite_over_batch's.  Inside the selection the result has
+    the source's gradients (or, with Clone(mixed=True), the stronger of the source's and the target's) and meets the
+    target's colours at its boundary; outside it is the target.
+    -> (B, H, W, 3) uint8 BGR; with return_info also (n_omega, iterations, relative residual), (B,) arrays."""
+    from ._engine import check_composite_args, get_engine
+    if clone is None:
+        clone = Clone()
+    if not isinstance(clone, Clone):
+        raise ValueError(f"clone must be a Clone or None, got {type(clone).__name__}")
+    src = _image_batch(sources, "seamless_clone_batch")
+    tgt = _image_batch(targets, "seamless_clone_batch")
+    m = masks if isinstance(masks, np.ndarray) else (np.stack([np.asarray(x) for x in masks]) if len(masks) else
+                                                     np.zeros((0, 1, 1), np.uint8))
+    if m.shape != src.shape[:3]:
+        raise ValueError(f"seamless_clone_batch: masks {m.shape} do not match the sources {src.shape[:3]}")
+    if m.dtype.kind not in "biu":
+        raise ValueError(f"seamless_clone_batch: masks must be bool or integer arrays (non-zero = selected), got {m.dtype}")
+    if len(src) != len(tgt):
+        raise ValueError(f"seamless_clone_batch: {len(src)} sources for {len(tgt)} targets")
+    off = check_composite_args(src.shape, tgt.shape, _offsets(offsets, len(tgt), "seamless_clone_batch"),
+                               (src.dtype, tgt.dtype), 3, "seamless_clone_batch")
+    if len(tgt) == 0:
+        z = np.zeros(0, np.int32)
+        return (tgt.copy(), z, z, np.zeros(0)) if return_info else tgt.copy()
+    eng = get_engine(device)
+    comp, n, it, rel = eng.poisson_clone(eng.to_device(src), eng.to_device(np.ascontiguousarray(m != 0).view(np.uint8)),
+                                         eng.to_device(tgt), off, *clone.args())
+    comp = comp.cpu().numpy()
+    return (comp, n.cpu().numpy(), it.cpu().numpy(), rel.cpu().numpy()) if return_info else comp
+
+
+def seamless_clone(source: np.ndarray, mask: np.ndarray, target: np.ndarray, offset=(0, 0), mixed: bool = False,
+                   max_iter: int = CLONE_MAX_ITER, tol: float = CLONE_TOL, return_info: bool = False, device="cuda"):
+    """Seamless (Poisson) cloning of one image (additive; seamless_clone_batch): the pixels of source (Hs, Ws, 3) uint8
+    BGR selected by mask (Hs, Ws), non-zero = selected, cloned into target (H, W, 3) uint8 BGR with the source's pixel
+    (0, 0) at offset = (row, col).  mixed=True uses mixed gradients.
+    -> (H, W, 3) uint8 BGR; with return_info, (composite, |Omega|, iterations, relative residual)."""
+    out = seamless_clone_batch(_check_image(source)[None], np.asarray(mask)[None], _check_image(target)[None], offset,
+                               Clone(mixed, max_iter, tol), return_info, device)
+    return (out[0][0], int(out[1][0]), int(out[2][0]), float(out[3][0])) if return_info else out[0]
 
 
 def upsample_mask(image: np.ndarray, mask: np.ndarray, full_image: np.ndarray, radius: int = MATTE_RADIUS,

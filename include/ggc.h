@@ -65,7 +65,10 @@
 extern "C" {
 #endif
 
-#define GGC_VERSION 410 /* 0.4.10: ggc_wand_select (magic wand: flood select by colour tolerance from seed pixels, contiguous or not, as
+#define GGC_VERSION 411 /* 0.4.11: ggc_composite_over, ggc_poisson_clone (a cut-out placed on a new background: integer alpha-over at an offset,
+                                  and gradient-domain "seamless" cloning after Perez, Gangnet and Blake, PCG on the device; additive,
+                                  no existing entry changes);
+                           0.4.10: ggc_wand_select (magic wand: flood select by colour tolerance from seed pixels, contiguous or not, as
                                   GrabCut labels, a selection plane and counts; additive, no existing entry changes);
                            0.4.9: ggc_mask_distance, ggc_modify_mask (the exact squared Euclidean distance transform of a mask, signed, and
                                   grow / shrink / border / open / close / trimap as thresholds of it; additive, no existing entry changes);
@@ -943,6 +946,56 @@ int ggc_estimate_foreground(ggc_ctx* ctx, ggc_stream stream, int B, int H, int W
                             float eps_r, float omega, int max_iter, float tol,
                             uint8_t* foreground, uint8_t* rgba, double* raw_f, double* raw_b, int32_t* iters,
                             double* rel_residual);
+
+/* O5 — a cut-out placed on a new background (additive): alpha-over of a BGRA cut-out at an offset.  All arithmetic is
+ * integer.
+ *   rgba       [dev] u8  [B,Hs,Ws,4]  BGRA, as rgba / rgba_soft / rgba_clean
+ *   background [dev] u8  [B,H,W,3]
+ *   offsets    [dev] i32 [B,2]        row, col of the source's pixel (0,0) in the background; may be negative, and any
+ *                                     value is taken (a source that lies wholly outside changes nothing)
+ *   out        [dev] u8  [B,H,W,3]    for a pixel p whose source pixel p - offset exists, with a = that pixel's alpha byte
+ *                                     and c its colour: (a c + (255 - a) bg + 127) / 255 per channel, integer division;
+ *                                     bg everywhere else.  out may be background itself (in place)
+ *   H, W, Hs, Ws in 1..32768, B <= 65535 (else GGC_E_SHAPE); B == 0 does nothing.
+ * Does not synchronise; no scratch; every image is independent of its batch. */
+int ggc_composite_over(ggc_ctx* ctx, ggc_stream stream, int B, int Hs, int Ws, const uint8_t* rgba, int H, int W,
+                       const uint8_t* background, const int32_t* offsets, uint8_t* out);
+
+/* O6 — gradient-domain ("seamless", Poisson) cloning of a selected source region into a target (additive; Perez, Gangnet
+ * and Blake, SIGGRAPH 2003, with source or mixed gradients).  Per image and independently per colour channel, in byte
+ * units, g the source and t the target:
+ *   Omega     the target pixels p inside the target whose source pixel p - offset exists and is selected (mask != 0)
+ *   N_p       the 4-neighbours of p that lie inside the target: no links across the target's border, so a pixel on it
+ *             has degree |N_p| = 2 or 3
+ *   system    for p in Omega:  |N_p| f_p - sum_{q in N_p and Omega} f_q = sum_{q in N_p \ Omega} t_q + sum_{q in N_p} v_pq
+ *   guidance  d_s = g_p - g_q when q's source pixel exists, else 0;  d_t = t_p - t_q
+ *             mixed = 0: v_pq = d_s;  mixed = 1: v_pq = d_t where |d_t| > |d_s|, else d_s (a tie goes to d_s), per
+ *             channel.  The right-hand side is an exact integer.
+ *   solve     preconditioned CG in float64, one CG over the three channels of an image; Jacobi preconditioner |N_p|;
+ *             start f = g, the plain paste.  An image stops when ||r_j||_2 <= max(tol ||r_0||_2, 2.55e-10 sqrt(3 |Omega|))
+ *             (unpreconditioned residual) or after max_iter iterations; the test is made on r_0 too, so an image cloned
+ *             onto itself takes 0 iterations: its r_0 is exactly 0 and its composite is the target bit for bit.
+ *   unsolved  an image whose Omega is empty is not solved: its composite is the target.  An image with |Omega| = H W is
+ *             not solved either (nothing anchors it): its composite is the pasted source.  Both report 0 iterations and
+ *             rel_residual 0.
+ *   source [dev] u8 [B,Hs,Ws,3]   mask [dev] u8 [B,Hs,Ws]   target [dev] u8 [B,H,W,3]   offsets [dev] i32 [B,2] = row, col
+ *   of the source's pixel (0,0) in the target, each within +-32768 (else GGC_E_INVALID_ARG, found after the front pass)
+ *   mixed 0 | 1, 1 <= max_iter <= 100000, 1e-12 <= tol < 1 (else GGC_E_INVALID_ARG); H, W, Hs, Ws in 1..32768,
+ *   B <= 65535 (else GGC_E_SHAPE); B == 0 does nothing
+ *   composite [dev] u8 [B,H,W,3]  = floor(clamp(f, 0, 255) + 0.5) on Omega, the target's bytes elsewhere
+ *   raw       [dev] f64 [B,H,W,3] = f unclamped on Omega, t elsewhere
+ *   n_omega   [dev] i32 [B]       = |Omega|
+ *   iters [dev] i32 [B]     rel_residual [dev] f64 [B] = ||r_j|| / ||r_0|| (0 for an image with 0 iterations)
+ *   (each may be NULL, not all of them)
+ * The CG vectors and dot products are float64.  Every per-image reduction runs in one fixed order over that image's
+ * tiles, so every image's outputs equal its single-image call bit for bit and two runs are identical; no float atomics.
+ * Work is restricted to the 16 x 16 tiles that hold Omega, listed once per call.  The entry SYNCHRONISES its stream: once
+ * to build that list on the host, and every 8 iterations to read the count of finished images (an integer atomic) and
+ * stop when all are done.  Scratch from the context: 1 byte per target pixel, 32 bytes per 16 x 16 tile and 64 bytes per
+ * image over the whole batch, plus 30720 bytes (256 pixels x 5 vectors x 24 bytes) per LISTED tile. */
+int ggc_poisson_clone(ggc_ctx* ctx, ggc_stream stream, int B, int Hs, int Ws, const uint8_t* source, const uint8_t* mask,
+                      int H, int W, const uint8_t* target, const int32_t* offsets, int mixed, int max_iter, float tol,
+                      uint8_t* composite, double* raw, int32_t* n_omega, int32_t* iters, double* rel_residual);
 
 /* R0 — IoU = tp / (tp + fp + fn + 1e-8) per image (metrics.py:79-84).
  *   iou [dev] f64 [B] (may be NULL)   counts [dev] u64 [B,3] = tp, fp, fn (may be NULL) */

@@ -16,6 +16,7 @@ Same command line as the reference's inference.py (flags :26-56, outputs :146-15
     python3 inference.py --image big.jpg --full-res --full-mask cut --save mask   # ... the mask cut again on the photo's pixels
     python3 inference.py --image cat.jpg --matte-method closed-form --save alpha cutout   # closed-form matte
     python3 inference.py --image big.jpg --full-res --matte-method closed-form-full --save alpha cutout   # ... solved at the photo's own size
+    python3 inference.py --image cat.jpg --background beach.jpg --paste-at 40,120 --composite seamless --save mask composite   # the result on a new background
 
 Images are decoded / written with Pillow (OpenCV is not a dependency of this build); folders are processed in
 batches of equally sized images so that the whole batch stays resident in HBM.
@@ -52,9 +53,11 @@ def build_parser() -> argparse.ArgumentParser:
                         help="Drop mask components smaller than this fraction of the image")
     parser.add_argument("--keep-largest", action="store_true", help="Keep only the largest connected component")
     parser.add_argument("--save", nargs="+", default=["mask", "overlay"],
-                        choices=["mask", "overlay", "rgba", "trimap", "alpha", "cutout", "outlines", "modified", "selection"],
+                        choices=["mask", "overlay", "rgba", "trimap", "alpha", "cutout", "outlines", "modified", "selection",
+                                 "composite"],
                         help="Which outputs to write (alpha / cutout: the soft matte and the BGRA cut-out with it; "
-                             "selection: what the --fg-wand / --bg-wand seeds select, as <prefix>_selection.png)")
+                             "selection: what the --fg-wand / --bg-wand seeds select, as <prefix>_selection.png; composite: the result "
+                             "on --background, as <prefix>_composite.png)")
     # additive: the mask's exact vector outlines (ggc_mask_outlines), written as <prefix>_outlines.json by --save outlines
     parser.add_argument("--outline-connectivity", type=int, choices=[4, 8], default=8,
                         help="--save outlines: 8 joins diagonal foreground pixels into one loop (as the mask clean-up "
@@ -163,6 +166,14 @@ def build_parser() -> argparse.ArgumentParser:
                         help="--full-mask cut: half-width of the open band in original pixels, 0..64 "
                              "(default: one and a half working pixels)")
     parser.add_argument("--full-cut-iters", type=int, default=1, help="--full-mask cut: GrabCut iterations at the original size")
+    # additive: the result placed on another picture (ggc_composite_over, ggc_poisson_clone), written by --save composite
+    parser.add_argument("--background", default=None,
+                        help="--save composite: the picture every result is placed on")
+    parser.add_argument("--paste-at", type=_point, default=(0, 0), metavar="ROW,COL",
+                        help="Row and column of --background where the result's top-left pixel lands (may be negative: --paste-at=-3,12)")
+    parser.add_argument("--composite", choices=["over", "seamless", "mixed"], default="over",
+                        help="How the result is placed: alpha-over of its cleanest cut-out, or the image under its mask "
+                             "cloned in the gradient domain with the image's (seamless) or with mixed gradients")
     return parser
 
 
@@ -364,6 +375,15 @@ def main() -> None:
             check_foreground_args(*foreground.args())
         except ValueError as e:
             parser.error(str(e))
+    background = None
+    if (args.background is not None) != ("composite" in args.save):
+        parser.error("--background is what --save composite places the result on: give both or neither")
+    if args.background is not None:
+        if max(abs(v) for v in args.paste_at) > 32768:
+            parser.error("--paste-at must lie within +-32768")
+        background = read_bgr(Path(args.background), 0)
+        if background is None:
+            parser.error(f"cannot read --background {args.background}")
     from src.gcn_grabcut import GCNGrabCutPipeline
     from src.gcn_grabcut.graph_builder import SuperpixelGraphConfig
     from src.gcn_grabcut.pipeline import _colour_trimap, _write_png, alpha_to_u8, nearest_upsample
@@ -476,6 +496,9 @@ def main() -> None:
                 if "modified" in args.save:                 # the mask file written above after the --modify steps
                     modified = result.modified(*args.modify, full=result.full is not None)
                     _write_png(f"{stem}_modified.png", modified if modified.max(initial=0) > 1 else modified * 255)
+                if "composite" in args.save:                # the files written above, placed on --background
+                    _write_png(f"{stem}_composite.png", result.composite_onto(background, args.paste_at, args.composite,
+                                                                              full=result.full is not None))
                 t = result.timing
                 print(f"[{n_done}/{len(paths)}] {path.name}  fg={result.binary_mask.mean():.1%}  "
                       f"graph={t.get('graph_build', 0):.4f}s gcn={t.get('gcn_inference', 0):.4f}s "
