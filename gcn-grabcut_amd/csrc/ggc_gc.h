@@ -107,13 +107,17 @@ void mf_zero3(hipStream_t st, int32_t* a, size_t na, int32_t* b, size_t nb, int3
 // Sparse phases as one asynchronous launch each (ggc_maxflow_async.hip): a pool of waves over a ticket queue of tiles.
 // Queue control words (int32, every hot counter on its own 128-byte line):
 constexpr int AQ_HEAD = 0, AQ_TAIL = 32, AQ_PENDING = 64, AQ_DONE = 96, AQ_BUDGET = 97, AQ_VISITS = 128, AQ_WORDS = 160;
-// queue <- list[0 .. *count) (device-side count; the tiles' membership flags in `flag` are set), then ONE launch that ends
-// at the relabel's fixpoint.  ring: cap 64-bit slots, cap = number of relabel tiles of the batch.
+// The queue starts with list[0 .. *count) (device-side count; the tiles' membership flags in `flag` are set): ONE launch that
+// ends at the relabel's fixpoint.  ring: cap 64-bit slots, cap = number of relabel tiles of the batch; ring and q are zero
+// (k_mf_rinit).  prof: the trace clocks under GGC_MF_TRACE (table 2), null otherwise.
 int maxflow_relax_async(ggc_ctx* ctx, hipStream_t st, const GcDims& d, const MfTiles& tl, uint8_t* rmask, int32_t* dirty, const int32_t* rc, int32_t* dist,
                         const int32_t* count, const int32_t* list, int32_t* flag, unsigned long long* ring, int32_t* q, int cap,
-                        int grid, int32_t* err_flag);
-// the same for one push phase on 32 x th tiles (th = 16 | 32): chains of at most gen_max tile hops, at most `inner` sweeps per
-// visit.  list: the active scan's 32x8 push tiles (n_list_max = their number in the batch); state: one word per tile.
+                        int grid, int32_t* err_flag, long long* prof = nullptr);
+// the same for one push phase on 32 x th tiles (th = 8 | 16 | 32): chains of at most gen_max tile hops, at most `inner` sweeps
+// per visit.  list: the active scan's 32x8 push tiles (n_list_max = their number in the batch); state: one word per tile.
+// th = 8: the list is the queue's start, and the active scan has left ring and q zero and state "queued" (1) for the listed
+// tiles, 0 for the others of every open image; th = 16 | 32: a zero-fill and a fill launch go first.
+int maxflow_push_async_tile(int th);               // the tile height a requested one runs as
 int maxflow_push_async(ggc_ctx* ctx, hipStream_t st, const GcDims& d, const MfTiles& tl, int th, int inner, int gen_max, int32_t* rc,
                        int32_t* ex, int32_t* snk, int32_t* dist, uint8_t* rmask, int32_t* dirty, const int32_t* count, const int32_t* list, int n_list_max, int32_t* state,
                        unsigned long long* ring, int32_t* q, int waves, int32_t* err_flag, long long* prof = nullptr);

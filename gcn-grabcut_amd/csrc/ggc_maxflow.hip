@@ -51,6 +51,16 @@ void mf_zero3(hipStream_t st, int32_t* a, size_t na, int32_t* b, size_t nb, int3
     if (n) hipLaunchKernelGGL(k_mf_zero3, dim3(cdiv(n, 256)), dim3(256), 0, st, a, na, b, nb, c, nc);
 }
 
+// Ring and control words of an asynchronous launch's queue, zeroed on the way by a kernel that runs before it anyway (2-D grid,
+// every thread calls it): the launch itself then needs no set-up launch.  Zeroed EVERY time: a launch that ended on its visit
+// budget or on the time-out leaves entries behind.
+__device__ __forceinline__ void aq_zero(unsigned long long* __restrict__ ring, int32_t* __restrict__ q, int cap) {
+    const size_t n_thr = (size_t)gridDim.x * gridDim.y * blockDim.x;
+    const size_t i0 = ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * blockDim.x + threadIdx.x;
+    for (size_t i = i0; i < (size_t)cap; i += n_thr) ring[i] = 0ull;
+    if (i0 < (size_t)AQ_WORDS) q[i0] = 0;
+}
+
 // The same through a per-block list.  Every append used to be a returning atomicAdd on the ONE counter of the next list, and
 // same-address atomics retire at ~90 per microsecond chip-wide: a dense launch appends ~15 000 tiles, i.e. >= 150 us of
 // counter traffic — which is what those launches took (139-165 us), whatever the grid or the occupancy.  A block now
@@ -82,13 +92,16 @@ __device__ __forceinline__ void flush_tiles(OutList& L, int32_t* __restrict__ li
 // its own): BOTH membership flags of every relabel tile it looks at (tiles of closed images are never listed again), the
 // image's active-pixel count, and the words the active scan and k_done_update accumulate into (scan[0]: open images,
 // scan[4..6]: push-list counters, scan[7]: active total).  The relabel counters themselves are zeroed by k_done_update / k_open_init.
+// And the queue of the asynchronous relabel launch that follows the work-list launches: ring[0 .. cap) and q (aq_zero).
 __global__ void __launch_bounds__(256) k_mf_rinit(GcDims d, MfTiles tl, const int32_t* __restrict__ open_list,
                                                   const int32_t* __restrict__ snk, int32_t* __restrict__ dist,
                                                   int32_t* __restrict__ list, int32_t* __restrict__ flag, int32_t* __restrict__ flag2,
-                                                  int32_t* __restrict__ count, int32_t* __restrict__ active, int32_t* __restrict__ scan) {
+                                                  int32_t* __restrict__ count, int32_t* __restrict__ active, int32_t* __restrict__ scan,
+                                                  unsigned long long* __restrict__ ring, int32_t* __restrict__ q, int cap) {
     constexpr int T = MF_RT;
     __shared__ OutList outl;
     if (threadIdx.x == 0) outl.n = 0;
+    aq_zero(ring, q, cap);
     if (blockIdx.x == 0 && threadIdx.x == 0) active[open_list[blockIdx.y]] = 0;
     if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x < 8 && (threadIdx.x == 0 || threadIdx.x >= 4)) scan[threadIdx.x] = 0;   // not [1..3]: the relabel counters this launch appends to
     __syncthreads();
@@ -353,13 +366,18 @@ __global__ void __launch_bounds__(PT_N) k_mf_pr_list(GcDims d, MfTiles tl, int p
 // A wave scans one 32x8 push tile (4 pixels per lane, rows of 128 bytes) and appends it once when it holds an active pixel:
 // no per-pixel membership test.  (The pixel-strided scan this replaces sent every active pixel through the tile's flag —
 // 920 k flag reads and LDS appends in the first round of a 64-image solve: 203 us, against ~25 us for the 61 MB it reads.)
+// aq_st != null (asynchronous push on 32x8 tiles, whose tiles are these tiles): the scan also leaves the queue of that launch
+// ready — ring[0 .. cap) and q zero, and the state word of every push tile of an open image "queued" (1) when it is listed
+// and 0 otherwise (a closed image's words are never read: its tiles are neither listed nor anybody's neighbours).
 __global__ void __launch_bounds__(256) k_mf_active(GcDims d, MfTiles tl, const int32_t* __restrict__ open_list,
                                                    const int32_t* __restrict__ ex, const int32_t* __restrict__ dist,
                                                    int32_t* __restrict__ active, int32_t* __restrict__ flag, int32_t* __restrict__ flag2,
-                                                   int32_t* __restrict__ list, int32_t* __restrict__ count) {
+                                                   int32_t* __restrict__ list, int32_t* __restrict__ count,
+                                                   int32_t* __restrict__ aq_st, unsigned long long* __restrict__ ring, int32_t* __restrict__ q, int cap) {
     __shared__ OutList outl;
     __shared__ int s_n;
     if (threadIdx.x == 0) { outl.n = 0; s_n = 0; }
+    if (aq_st) aq_zero(ring, q, cap);
     __syncthreads();
     const int tiles_per_image = tl.pt_x * tl.pt_y;
     const int b = open_list[blockIdx.y];
@@ -387,6 +405,7 @@ __global__ void __launch_bounds__(256) k_mf_active(GcDims d, MfTiles tl, const i
             const int tile = b * tiles_per_image + tr;
             flag[tile] = n > 0 ? 1 : 0;                                    // both membership flags of every push tile of an open image: one writer
             flag2[tile] = 0;                                               // per tile, no zero-fill launch before the scan
+            if (aq_st) aq_st[tile] = n > 0 ? 1 : 0;
             if (n > 0) {
                 const int i = atomicAdd(&outl.n, 1);
                 if (i < OUT_CAP) outl.buf[i] = tile; else list[atomicAdd(count, 1)] = tile;
@@ -426,7 +445,7 @@ struct MfWork {
     unsigned long long* ring;            // ticket ring of the asynchronous launches, one slot per tile of the larger kind
     int32_t* aq;                         // its control words
     int32_t* busy;                       // state word per tile of an asynchronous push
-    long long* prof;                     // GGC_MF_TRACE clocks [2][64][8]: asynchronous push waves | tile visits
+    long long* prof;                     // GGC_MF_TRACE clocks [3][64][8]: asynchronous push waves | tile visits (push, dense relabel) | asynchronous relabel visits
     int32_t* dirty;                      // one word per push tile: a neighbour pushed into it since its arc masks were last exact
     void layout(Carve& c, size_t n_rt, size_t n_pt) {
         for (auto& p : rl_list) p = c.take<int32_t>(n_rt);
@@ -436,7 +455,7 @@ struct MfWork {
         ring = c.take<unsigned long long>(std::max(n_rt, n_pt));
         aq = c.take<int32_t>(AQ_WORDS);
         busy = c.take<int32_t>(n_pt);
-        prof = c.take<long long>(2 * 64 * 8);
+        prof = c.take<long long>(3 * 64 * 8);
         dirty = c.take<int32_t>(n_pt);
     }
 };
@@ -460,7 +479,7 @@ struct MfSolve {
         const int grid = (int)std::min<size_t>(RELAX_GRID * scale, std::max<size_t>(16, cdiv((size_t)n_cur * per_image, 4)));
         ProfScope ps(ctx, st, "maxflow_relabel");
         hipLaunchKernelGGL(k_mf_rinit, dim3(cdiv(per_image, 4), n_cur), dim3(256), 0, st, d, tl, open, snk, dist, w.rl_list[0], w.rl_flag[0],
-                           w.rl_flag[1], rl_cnt, ctl.active, n_open);
+                           w.rl_flag[1], rl_cnt, ctl.active, n_open, w.ring, w.aq, partial ? 0 : (int)n_rt);
         int phase = 0;
         for (; phase < kn.mf_relax_dense; ++phase) {
             int32_t *li = w.rl_list[phase & 1], *lo = w.rl_list[(phase + 1) & 1], *fi = w.rl_flag[phase & 1], *fo = w.rl_flag[(phase + 1) & 1];
@@ -474,7 +493,7 @@ struct MfSolve {
         const int pool = (int)std::min<size_t>(ASYNC_GRID * scale, std::max<size_t>(16, cdiv((size_t)n_cur * per_image, 16)));
         launches = phase + 1;
         return maxflow_relax_async(ctx, st, d, tl, rmask, w.dirty, rc, dist, rl_cnt + phase % 3, w.rl_list[phase & 1], w.rl_flag[phase & 1],
-                                   w.ring, w.aq, (int)n_rt, pool, ctl.err);
+                                   w.ring, w.aq, (int)n_rt, pool, ctl.err, prof);
     }
 
     // Push phase over the push tiles the active scan listed.  n_cur: the images open when the round began (the grids follow
@@ -504,7 +523,8 @@ struct MfSolve {
 };
 
 // GGC_MF_TRACE=1: per-round diagnostics on stderr, blocking (tools/mf_trace.py reads them).  The clocks of the relabel
-// visits are table 1 of the trace clocks, those of an asynchronous push tables 0 (per wave) and 1 (inside the visit).
+// visits are table 1 of the trace clocks (dense launches) and table 2 (asynchronous launch), those of an asynchronous push
+// tables 0 (per wave) and 1 (inside the visit).
 struct MfTrace {
     std::chrono::steady_clock::time_point t_prev = std::chrono::steady_clock::now();
     double push_ms = 0.0;
@@ -512,14 +532,18 @@ struct MfTrace {
     // after the active scan: the relabel visits' clocks, active pixels and open images, the stragglers by image
     int round(const MfSolve& s, int round, int n_next, int total_active, int relax_launches) {
         ggc_ctx* ctx = s.ctx;
-        long long hh[64 * 8], h[7] = {0, 0, 0, 0, 0, 0, 0};
+        long long hh[128 * 8];
         GGC_HIP(ctx, hipStreamSynchronize(s.st));
         GGC_HIP(ctx, hipMemcpy(hh, s.prof + 64 * 8, sizeof hh, hipMemcpyDeviceToHost));
         GGC_HIP(ctx, hipMemsetAsync(s.prof + 64 * 8, 0, sizeof hh, s.st));
-        for (int i = 0; i < 64; ++i) for (int k = 0; k < 7; ++k) h[k] += hh[i * 8 + k];
-        if (h[3] > 0)
-            std::fprintf(stderr, "    [relabel visits] %lld dense visits: per visit load+fill %.2f us, sweeps %.2f us (%.1f sweeps, %.1f BFS levels, %lld visits fell back), write-back %.2f us\n",
-                         h[3], 0.01 * h[0] / h[3], 0.01 * h[1] / h[3], (double)h[4] / h[3], (double)h[5] / h[3], h[6], 0.01 * h[2] / h[3]);
+        for (int t = 0; t < 2; ++t) {                      // dense launches | the asynchronous launch (write-back includes its hand-over)
+            long long h[7] = {0, 0, 0, 0, 0, 0, 0};
+            for (int i = 0; i < 64; ++i) for (int k = 0; k < 7; ++k) h[k] += hh[(t * 64 + i) * 8 + k];
+            if (h[3] > 0)
+                std::fprintf(stderr, "    [%s] %lld %s visits: per visit load+fill %.2f us, sweeps %.2f us (%.1f sweeps, %.1f BFS levels, %lld visits fell back), write-back %.2f us\n",
+                             t ? "async relabel visits" : "relabel visits", h[3], t ? "asynchronous" : "dense", 0.01 * h[0] / h[3], 0.01 * h[1] / h[3],
+                             (double)h[4] / h[3], (double)h[5] / h[3], h[6], 0.01 * h[2] / h[3]);
+        }
         std::vector<int32_t> act;
         if (int rcode = read_i32(ctx, s.st, s.ctl.active, s.d.B, act)) return rcode;
         const auto t_now = std::chrono::steady_clock::now();
@@ -572,7 +596,7 @@ int maxflow(ggc_ctx* ctx, hipStream_t st, const GcDims& d, const int32_t* state,
     if (masks_exact) GGC_HIP(ctx, hipMemsetAsync(s.w.dirty, 0, sizeof(int32_t) * s.n_pt, st));
     if (kn.mf_trace) {
         s.prof = s.w.prof;
-        GGC_HIP(ctx, hipMemsetAsync(s.prof, 0, 2 * 64 * 8 * sizeof(long long), st));
+        GGC_HIP(ctx, hipMemsetAsync(s.prof, 0, 3 * 64 * 8 * sizeof(long long), st));
     }
     GGC_HIP(ctx, hipMemsetAsync(s.n_open, 0, sizeof(int32_t), st));
     int32_t *list_cur = ctl.lists, *list_nxt = ctl.lists + d.B;
@@ -605,7 +629,8 @@ int maxflow(ggc_ctx* ctx, hipStream_t st, const GcDims& d, const int32_t* state,
         // ---- who still has work?  (active pixel = excess that can still reach the sink)
         // (active[], the open-image count, the push-list counters and the active total were zeroed by this round's k_mf_rinit)
         hipLaunchKernelGGL(k_mf_active, dim3(std::min(cdiv(tl.pt_x * tl.pt_y, 4), 128), n_cur), dim3(256), 0, st, d, tl, list_cur, ex, dist,
-                           ctl.active, s.w.pt_flag[0], s.w.pt_flag[1], s.w.pt_list[0], s.pr_cnt);
+                           ctl.active, s.w.pt_flag[0], s.w.pt_flag[1], s.w.pt_list[0], s.pr_cnt,
+                           maxflow_push_async_tile(kn.mf_async_tile) == PT_H ? s.w.busy : nullptr, s.w.ring, s.w.aq, (int)s.n_pt);
         hipLaunchKernelGGL(k_done_update, dim3(cdiv(n_cur, 256)), dim3(256), 0, st, n_cur, list_cur, ctl.active, list_nxt, s.n_open, partial ? 1 : 0, s.rl_cnt);
         GGC_LAUNCH_CHECK(ctx);
         if ((rcode = read_i32(ctx, st, s.n_open, 8, host))) return rcode;

@@ -15,6 +15,11 @@
 //    takes t = tail++ and publishes {t + 1, payload} into the same slot once it is empty.  `pending` counts entries
 //    queued or in flight; the visit that brings it to zero raises `done` and every waiting wave leaves.  A tile is in
 //    the queue at most once (membership flag, test-and-set), so `cap` = number of tiles never overflows.
+//    The FIRST entries are not in the ring at all: the kernel before the launch left a work list with a device-side count n,
+//    and a consumer whose ticket is below n reads list[ticket] (no wait, no ring traffic); ring tickets start after them,
+//    and `pending` counts from n.  So a launch needs no set-up launch: ring and control words are zeroed by kernels that run
+//    anyway (k_mf_rinit for the relabel, k_mf_active for the push), never assumed empty from the launch before — one that
+//    ends on its visit budget or on the time-out leaves entries behind.
 //  * memory: the per-XCD L2s are not coherent with each other inside a launch.  Every word another wave may change —
 //    labels, excess, residual capacities, sink links, flags, locks, the ring — is therefore WRITTEN with a device-scope
 //    atomic read-modify-write (performed at memory) and READ with an sc1 load; tools/micro/xcd_atomics.hip measured 0
@@ -30,8 +35,8 @@
 //    scan, as before.
 //  * a hop costs memory round trips (~2 us each for device-scope atomics and sc1 loads), so both kernels FOLLOW: the wave
 //    that finishes a visit continues with one of the tiles it would have queued (no ring traffic on the critical path), and
-//    the push works on 32x16 / 32x32 tiles with an active-pixel bitmask, where a sweep costs what the active pixels cost
-//    and one visit carries excess across the whole tile.
+//    a push sweep works one active pixel per lane, carried in a register from sweep to sweep (32x8 tiles by default, 32x16
+//    and 32x32 on request), so it costs what the active pixels cost and one visit carries excess across the tile.
 #include "ggc_gc.h"
 #include "ggc_mf_sweep.h"
 #include <algorithm>
@@ -46,22 +51,30 @@ constexpr long long AQ_TIMEOUT = 200000000ll;        // 2 s of wall_clock64 (100
 __device__ __forceinline__ unsigned long long ldg64(const unsigned long long* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ void drain() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }   // this wave's loads, stores and atomics are done
 
+// The entries a launch starts with: list[0 .. n) of the kernel before it (n = 0: everything comes through the ring).
+struct AqInit { const int32_t* list; int n; };
+
 // consumer side, lane 0 of a wave; returns the payload (>= 0) to every lane, or -1 when the launch is over
-__device__ __forceinline__ int aq_pop(unsigned long long* __restrict__ ring, int32_t* __restrict__ q, int cap, int lane,
+__device__ __forceinline__ int aq_pop(unsigned long long* __restrict__ ring, int32_t* __restrict__ q, int cap, const AqInit& in, int lane,
                                       int32_t* __restrict__ err_flag) {
     int payload = -1;
     if (lane == 0) {
         const unsigned t = (unsigned)atomicAdd(&q[AQ_HEAD], 1);
-        unsigned long long* slot = ring + t % (unsigned)cap;
-        const long long t0 = wall_clock64();
-        for (int n = 0;; ++n) {
-            const unsigned long long v = ldg64(slot);
-            if ((unsigned)(v >> 32) == t + 1u) { atomicExch(slot, 0ull); payload = (int)(unsigned)v; break; }
-            if ((n & 3) == 3) {
-                if (ldg(&q[AQ_DONE]) || ldg(&q[AQ_PENDING]) == 0) break;       // nothing queued, nothing in flight
-                if (wall_clock64() - t0 > AQ_TIMEOUT) { if (err_flag) atomicOr(err_flag, 4); atomicExch(&q[AQ_DONE], 1); break; }
+        if (t < (unsigned)in.n) {
+            payload = in.list[t];                                          // written before the launch: a plain load, nothing to wait for
+        } else {
+            const unsigned tr = t - (unsigned)in.n;                        // ring ticket
+            unsigned long long* slot = ring + tr % (unsigned)cap;
+            const long long t0 = wall_clock64();
+            for (int n = 0;; ++n) {
+                const unsigned long long v = ldg64(slot);
+                if ((unsigned)(v >> 32) == tr + 1u) { atomicExch(slot, 0ull); payload = (int)(unsigned)v; break; }
+                if ((n & 3) == 3) {
+                    if (ldg(&q[AQ_DONE]) || ldg(&q[AQ_PENDING]) + in.n == 0) break;   // nothing queued, nothing in flight
+                    if (wall_clock64() - t0 > AQ_TIMEOUT) { if (err_flag) atomicOr(err_flag, 4); atomicExch(&q[AQ_DONE], 1); break; }
+                }
+                __builtin_amdgcn_s_sleep(4);
             }
-            __builtin_amdgcn_s_sleep(4);
         }
     }
     return __builtin_amdgcn_readfirstlane(payload);
@@ -79,42 +92,44 @@ __device__ __forceinline__ void aq_push(unsigned long long* __restrict__ ring, i
         __builtin_amdgcn_s_sleep(2);
     }
 }
-__device__ __forceinline__ void aq_finish(int32_t* __restrict__ q) {
-    if (atomicSub(&q[AQ_PENDING], 1) == 1) atomicExch(&q[AQ_DONE], 1);
-}
-
-// queue <- the work list a launch-driven kernel (or the active scan) has just produced: list[0 .. *count), flags already set
-__global__ void __launch_bounds__(256) k_aq_init(const int32_t* __restrict__ count, const int32_t* __restrict__ list,
-                                                 unsigned long long* __restrict__ ring, int32_t* __restrict__ q, int cap, int budget_per_item) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    const int n = min(*count, cap);
-    if (i < cap) ring[i] = i < n ? (((unsigned long long)(unsigned)(i + 1)) << 32) | (unsigned)list[i] : 0ull;
-    if (i == 0) {
-        q[AQ_HEAD] = 0; q[AQ_TAIL] = n; q[AQ_PENDING] = n; q[AQ_DONE] = n == 0 ? 1 : 0; q[AQ_VISITS] = 0;
-        q[AQ_BUDGET] = (int)min((long long)n * budget_per_item + 4096, (long long)0x3fffffff);
-    }
+// AQ_PENDING holds the entries queued or in flight MINUS the in.n the launch started with (it starts at zero)
+__device__ __forceinline__ void aq_finish(int32_t* __restrict__ q, const AqInit& in) {
+    if (atomicSub(&q[AQ_PENDING], 1) + in.n == 1) atomicExch(&q[AQ_DONE], 1);
 }
 
 // ---- global relabel, asynchronous ---------------------------------------------------------------------------------
+// The visit is the bit-row BFS of the dense launches with the sweeps as its fallback (ggc_mf_sweep.h).  It is safe against
+// the other waves of the launch: the BFS takes only label-1 pixels and the halo as sources, tests `start < its label`
+// afterwards (a label another wave lowered before the load: fallback to the sweeps, which carry any start label on), and
+// labels go back by atomicMin where they fell (a label lowered behind the visit's back: a harmless write).
+#ifndef GGC_MF_RELAX_ASYNC_BFS
+#define GGC_MF_RELAX_ASYNC_BFS 1    // 1 = BFS visit with the sweeps as fallback, 0 = sweeps only
+#endif
+// count / list: the work list of the last launch-driven relabel kernel, the queue's first entries; ring and q zeroed by k_mf_rinit.
+// PROF (GGC_MF_TRACE): the visits' clocks into table 2 of the trace clocks.
+template <bool PROF>
 __global__ void __launch_bounds__(256) k_mf_relax_async(GcDims d, MfTiles tl, uint8_t* __restrict__ rmask, int32_t* __restrict__ dirty,
                                                         const int32_t* __restrict__ rc, int32_t* __restrict__ dist, int32_t* __restrict__ flag,
+                                                        const int32_t* __restrict__ count, const int32_t* __restrict__ list,
                                                         unsigned long long* __restrict__ ring, int32_t* __restrict__ q, int cap,
-                                                        int32_t* __restrict__ err_flag) {
+                                                        int32_t* __restrict__ err_flag, long long* __restrict__ prof) {
     __shared__ RelaxWaveLds lds[4];
     RelaxWaveLds& S = lds[threadIdx.x >> 6];
     const int tiles_per_image = tl.rt_x * tl.rt_y;
-    MfRelaxClocks<false> ck;
+    const AqInit in{list, min(*count, cap)};
+    MfRelaxClocks<PROF> ck;
     int tile = -1;                                                         // >= 0: the neighbour this wave follows into
     for (;;) {
         int lane = threadIdx.x & 63;
         asm volatile("" : "+v"(lane));                                     // keeps the lane arithmetic inside the loop (no hoist + spill)
         if (tile < 0) {
-            tile = aq_pop(ring, q, cap, lane, err_flag);
+            tile = aq_pop(ring, q, cap, in, lane, err_flag);
             if (tile < 0) break;
             if (lane == 0) atomicExch(&flag[tile], 0);                     // consumed: a halo change from now on re-queues the tile
             drain();                                                       // ... and the loads below come after it
         }
-        const int nbm = mf_relax_visit<true, false>(d, tl, tile, lane, S, rmask, dirty, rc, dist, flag, ck);
+        ck.begin();
+        const int nbm = mf_relax_visit<true, PROF, GGC_MF_RELAX_ASYNC_BFS != 0>(d, tl, tile, lane, S, rmask, dirty, rc, dist, flag, ck);
         drain();                                                           // the new labels are at memory before a neighbour is told
         const int b = tile / tiles_per_image, tr = tile % tiles_per_image;
         const int tyi = tr / tl.rt_x, txi = tr % tl.rt_x;
@@ -135,22 +150,33 @@ __global__ void __launch_bounds__(256) k_mf_relax_async(GcDims d, MfTiles tl, ui
             if (cand && lane != fl && atomicExch(&flag[nb], 1) == 0) aq_push(ring, q, cap, nb, err_flag);
             drain();                                                       // the entries count as pending before this visit ends
         }
-        if (next < 0 && lane == 0) aq_finish(q);                           // (following keeps this visit's pending unit)
+        if (next < 0 && lane == 0) aq_finish(q, in);                       // (following keeps this visit's pending unit)
         tile = next;
         mf_wave_sync();
+        ck.end();
+    }
+    if (PROF && (threadIdx.x & 63) == 0 && ck.sum[3]) {
+        unsigned long long* o = reinterpret_cast<unsigned long long*>(prof) + (128 + (blockIdx.x & 63)) * 8;
+        for (int k = 0; k < 7; ++k) atomicAdd(&o[k], (unsigned long long)ck.sum[k]);
     }
 }
 
 // ---- push-relabel sweeps, asynchronous --------------------------------------------------------------------------------
 constexpr int ST_Q = 1, ST_BUSY = 2;                  // tile state word: queued (or owed a visit) | a wave holds it
 
-// One wave, one 32 x TH tile (TH/2 pixels per lane for loading and write-back).  The tile's active pixels (excess that can
-// still reach the sink) are a bitmask, one word per row; a sweep compacts it into a list and hands one pixel to each lane,
-// so a sweep costs what the active pixels cost and a visit can afford enough of them to carry excess across the tile.
+// One wave, one 32 x TH tile (TH/2 pixels per lane for loading and write-back).  A sweep works one active pixel (excess that
+// can still reach the sink) per lane, so it costs what the active pixels cost and a visit can afford enough sweeps to carry
+// excess across the tile.  A lane CARRIES its next pixel in a register from sweep to sweep: the receiver when it pushed inside
+// the tile, its own pixel when that kept excess and nothing went to a receiver inside the tile.  Only what a lane cannot
+// carry — its own pixel's remainder when it goes on with the receiver — is handed to a lane that carries nothing, or, when
+// every lane is taken, spilled into a bitmask in LDS, one word per row; the mask's words are read in the round trip of the
+// pixel's own reads, and only a sweep that finds it non-empty compacts mask and carried pixels into a list and deals the
+// lanes new pixels (the first 64 in row-major order; bits beyond stay).  The mask also holds the visit's first pixels.
+// Two lanes may carry the same pixel: the exchange on its excess hands it to one of them, the other sees 0.
 template <int TH>
 struct PushTileLds {
     int ex[32 * TH]; int sk[32 * TH]; int d[TH + 2][34]; int rc[8][32 * TH];
-    uint32_t mask[32]; unsigned short list[32 * TH];
+    uint32_t mask[32]; unsigned short list[64];
 };
 
 // Returns the 9-bit mask of tiles owed a visit: bit (dy + 1) * 3 + (dx + 1) for a neighbour that received excess, bit 4
@@ -211,10 +237,11 @@ __device__ int push_tile_visit(const GcDims& d, int tyi, int txi, int inner, siz
     int nbm = 0;
     const long long tv1 = prof ? wall_clock64() : 0;
     int n_sw = 0;
-    for (int it = 0; it < inner; ++it) {
-        // ---- bitmask -> list (row-major), mask cleared
-        // every lane reads all TH row words (broadcast reads) and forms the row offsets itself: no cross-lane step (a prefix
-        // scan by __shfl_up is five dependent LDS-crossbar round trips, a third of a sparse sweep)
+    int cur = -1;                                                          // the pixel this lane carries into the next sweep
+    // ---- bitmask -> list (row-major) -> one pixel per lane; the rows' bits that 64 lanes do not take stay in the mask
+    // every lane reads all TH row words (broadcast reads) and forms the row offsets itself: no cross-lane step (a prefix
+    // scan by __shfl_up is five dependent LDS-crossbar round trips)
+    auto deal = [&]() {
         uint32_t w = 0u;
         int off = 0, n_act = 0;
 #pragma unroll
@@ -225,75 +252,106 @@ __device__ int push_tile_visit(const GcDims& d, int tyi, int txi, int inner, siz
             off += r < lane ? cr : 0;
             n_act += cr;
         }
-        if (n_act == 0) break;
-        ++n_sw;
-        mf_wave_sync();                                                    // every lane has read the words before they are cleared
-        if (lane < TH) S.mask[lane] = 0u;
-        while (w) { const int bit = __ffs(w) - 1; S.list[off++] = (unsigned short)(lane * 32 + bit); w &= w - 1; }
+        mf_wave_sync();                                                    // every lane has read the words before they are rewritten
+        while (w && off < 64) { const int bit = __ffs(w) - 1; S.list[off++] = (unsigned short)(lane * 32 + bit); w &= w - 1; }
+        if (lane < TH) S.mask[lane] = w;
         mf_wave_sync();
-        // ---- one active pixel per lane.  A lane TAKES the pixel's excess with an exchange and gives back what it could not
-        // push, so what a neighbouring lane pushes into the pixel meanwhile is kept.  A pixel that keeps excess, or that a push
-        // inside the tile reaches, is looked at again in the next sweep.  (Chasing a unit of excess from pixel to pixel
-        // within a sweep, and parking pixels that only climb, were measured and removed: DESIGN.md 5.5.)
-        for (int k0 = 0; k0 < n_act; k0 += 64) {
-            int slot = k0 + lane < n_act ? (int)S.list[k0 + lane] : -1;
-            if (slot >= 0) {
-                const int ly = slot >> 5, plx = slot & 31;
-                const int e = atomicExch(&S.ex[slot], 0);
-                const int dp = S.d[ly + 1][plx + 1];
-                const int sk = S.sk[slot];
-                int r[8], hq[8];
+        cur = lane < n_act ? (int)S.list[lane] : -1;
+    };
+    deal();                                                                // the fill's mask
+    for (int it = 0; it < inner; ++it) {
+        // ---- one round trip: the spill words and the carried pixel.  A lane TAKES the pixel's excess with an exchange and
+        // gives back what it could not push, so what a neighbouring lane pushes into the pixel meanwhile is kept.  (Chasing a
+        // unit of excess from pixel to pixel within a sweep, and parking pixels that only climb, were measured and removed:
+        // DESIGN.md 5.5.)
+        uint32_t sp = 0u;
+#pragma unroll
+        for (int r = 0; r < TH; ++r) sp |= S.mask[r];
+        int carry = -1, spill = -1;
+        if (cur >= 0) {
+            const int slot = cur, ly = slot >> 5, plx = slot & 31;
+            const int e = atomicExch(&S.ex[slot], 0);
+            const int dp = S.d[ly + 1][plx + 1];
+            const int sk = S.sk[slot];
+            int r[8], hq[8];
+#pragma unroll
+            for (int dir = 0; dir < 8; ++dir) {
+                r[dir] = __hip_atomic_load(&S.rc[dir][slot], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                hq[dir] = S.d[ly + 1 + dir_dy(dir)][plx + 1 + dir_dx(dir)];
+            }
+            if (e <= 0) {
+                // nothing left (or another lane carried the same pixel and took it)
+            } else if (dp >= d.P) {
+                atomicAdd(&S.ex[slot], e);                                 // cannot reach the sink: the excess stays where it is
+            } else {
+                int hmin = sk > 0 ? 0 : DINF, best = sk > 0 ? 8 : -1, rb = 0;
 #pragma unroll
                 for (int dir = 0; dir < 8; ++dir) {
-                    r[dir] = __hip_atomic_load(&S.rc[dir][slot], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                    hq[dir] = S.d[ly + 1 + dir_dy(dir)][plx + 1 + dir_dx(dir)];
+                    const bool ok = r[dir] > 0 && hq[dir] < hmin;
+                    hmin = ok ? hq[dir] : hmin; best = ok ? dir : best; rb = ok ? r[dir] : rb;
                 }
-                if (e <= 0) {
-                    slot = -1;                                         // nothing left
-                } else if (dp >= d.P) {
-                    atomicAdd(&S.ex[slot], e); slot = -1;              // cannot reach the sink: the excess stays where it is
-                } else {
-                    int hmin = sk > 0 ? 0 : DINF, best = sk > 0 ? 8 : -1, rb = 0;
-#pragma unroll
-                    for (int dir = 0; dir < 8; ++dir) {
-                        const bool ok = r[dir] > 0 && hq[dir] < hmin;
-                        hmin = ok ? hq[dir] : hmin; best = ok ? dir : best; rb = ok ? r[dir] : rb;
-                    }
-                    if (best >= 0 && dp > hmin) {
-                        if (best == 8) {
-                            const int dl = min(e, sk);
-                            S.sk[slot] = sk - dl;                      // only the holder of the pixel's excess touches its sink link
-                            if (e - dl > 0) atomicAdd(&S.ex[slot], e - dl); else slot = -1;   // sink link full: on to the neighbours
-                        } else {
-                            const int dl = min(e, rb), rem = e - dl;
-                            atomicSub(&S.rc[best][slot], dl);
-                            if (rem > 0) { atomicAdd(&S.ex[slot], rem); atomicOr(&S.mask[ly], 1u << plx); }   // the rest: next sweep
-                            const int qlx = plx + dir_dx(best), qly = ly + dir_dy(best);
-                            if (qlx >= 0 && qlx < 32 && qly >= 0 && qly < TH) {
-                                const int qt = qly * 32 + qlx;
-                                atomicAdd(&S.rc[best ^ 1][qt], dl);
-                                atomicAdd(&S.ex[qt], dl);
-                                slot = qt;                              // the receiver: next sweep
-                            } else {                                    // across the tile edge: straight to memory
-                                const int gy = tyi * TH + qly, gx = txi * 32 + qlx;
-                                const size_t qg = base + (size_t)gy * d.W + gx;
-                                atomicAdd(&rc[rc_idx((best ^ 1), qg)], dl);
-                                atomicAdd(&ex[qg], dl);
-                                const int tdy = qly < 0 ? -1 : (qly >= TH ? 1 : 0), tdx = qlx < 0 ? -1 : (qlx >= 32 ? 1 : 0);
-                                nbm |= 1 << ((tdy + 1) * 3 + tdx + 1);
-                                slot = rem > 0 ? slot : -1;
-                            }
-                        }
+                if (best >= 0 && dp > hmin) {
+                    if (best == 8) {
+                        const int dl = min(e, sk);
+                        S.sk[slot] = sk - dl;                              // only the holder of the pixel's excess touches its sink link
+                        if (e - dl > 0) { atomicAdd(&S.ex[slot], e - dl); carry = slot; }   // sink link full: on to the neighbours
                     } else {
-                        const int nd = (best >= 0 && hmin < DINF) ? hmin + 1 : DINF;
-                        S.d[ly + 1][plx + 1] = nd;
-                        atomicAdd(&S.ex[slot], e);                     // give it back; with the new label the next sweep can push
-                        if (nd >= d.P) slot = -1;
+                        const int dl = min(e, rb), rem = e - dl;
+                        atomicSub(&S.rc[best][slot], dl);
+                        if (rem > 0) atomicAdd(&S.ex[slot], rem);
+                        // (dir_dx / dir_dy of a direction known only at run time, from bit tables: no branches)
+                        const int qlx = plx + ((0x62 >> best) & 1) - ((0x91 >> best) & 1), qly = ly + ((0xa8 >> best) & 1) - ((0x54 >> best) & 1);
+                        if (qlx >= 0 && qlx < 32 && qly >= 0 && qly < TH) {
+                            const int qt = qly * 32 + qlx;
+                            atomicAdd(&S.rc[best ^ 1][qt], dl);
+                            atomicAdd(&S.ex[qt], dl);
+                            carry = qt;                                    // on with the receiver ...
+                            spill = rem > 0 ? slot : -1;                   // ... and the rest, which this lane cannot carry too, to the mask
+                        } else {                                           // across the tile edge: straight to memory
+                            const int gy = tyi * TH + qly, gx = txi * 32 + qlx;
+                            const size_t qg = base + (size_t)gy * d.W + gx;
+                            atomicAdd(&rc[rc_idx((best ^ 1), qg)], dl);
+                            atomicAdd(&ex[qg], dl);
+                            const int tdy = qly < 0 ? -1 : (qly >= TH ? 1 : 0), tdx = qlx < 0 ? -1 : (qlx >= 32 ? 1 : 0);
+                            nbm |= 1 << ((tdy + 1) * 3 + tdx + 1);
+                            carry = rem > 0 ? slot : -1;
+                        }
                     }
+                } else {
+                    const int nd = (best >= 0 && hmin < DINF) ? hmin + 1 : DINF;
+                    S.d[ly + 1][plx + 1] = nd;
+                    atomicAdd(&S.ex[slot], e);                             // give it back; with the new label the next sweep can push
+                    carry = nd >= d.P ? -1 : slot;
                 }
             }
-            if (slot >= 0) atomicOr(&S.mask[slot >> 5], 1u << (slot & 31));
+        }
+        sp = __builtin_amdgcn_readfirstlane(sp);                           // (every lane read the same words)
+        if (sp == 0u && !__any(cur >= 0)) break;                           // no lane carries a pixel, nothing spilled
+        ++n_sw;
+        if (sp == 0u) {
+            // A remainder goes to an IDLE lane where there is one: the k-th lane with a remainder leaves it in list[k], the
+            // k-th lane that carries nothing picks it up (ranks from two ballots; one LDS write and read, only in a sweep that
+            // has a remainder).  Only remainders beyond the idle lanes reach the mask, and with it the next sweep's deal.
+            const unsigned long long rem_m = __ballot(spill >= 0);
+            if (rem_m) {
+                const unsigned long long idle_m = __ballot(carry < 0);
+                const int n_rem = __popcll(rem_m), n_idle = __popcll(idle_m);
+                const int k_rem = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(rem_m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)rem_m, 0u));
+                const int k_idle = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(idle_m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)idle_m, 0u));
+                if (spill >= 0) {
+                    if (k_rem < n_idle) S.list[k_rem] = (unsigned short)spill;
+                    else atomicOr(&S.mask[spill >> 5], 1u << (spill & 31));
+                }
+                mf_wave_sync();
+                if (carry < 0 && k_idle < n_rem) carry = (int)S.list[k_idle];
+            }
+            cur = carry;
             mf_wave_sync();
+        } else {                                                           // the mask is not empty: carried pixels into it, and a new deal
+            if (carry >= 0) atomicOr(&S.mask[carry >> 5], 1u << (carry & 31));
+            if (spill >= 0) atomicOr(&S.mask[spill >> 5], 1u << (spill & 31));
+            mf_wave_sync();
+            deal();
         }
     }
     const long long tv2 = prof ? wall_clock64() : 0;
@@ -349,12 +407,16 @@ template <int TH>
 __global__ void __launch_bounds__(64) k_mf_push_async(GcDims d, int bt_x, int bt_y, int pt_y, int inner, int gen_max, int32_t* __restrict__ dirty, int32_t* __restrict__ rc,
                                                       int32_t* __restrict__ ex, int32_t* __restrict__ snk, int32_t* __restrict__ dist,
                                                       uint8_t* __restrict__ rmask, int32_t* __restrict__ st, unsigned long long* __restrict__ ring,
-                                                      int32_t* __restrict__ q, int cap, int32_t* __restrict__ err_flag,
+                                                      int32_t* __restrict__ q, int cap, const int32_t* __restrict__ count,
+                                                      const int32_t* __restrict__ list, int32_t* __restrict__ err_flag,
                                                       long long* __restrict__ prof) {
     __shared__ PushTileLds<TH> S;
     const int tiles_per_image = bt_x * bt_y;
     const size_t BP = (size_t)d.B * d.P;
-    const int budget = ldg(&q[AQ_BUDGET]);
+    // count != null (32x8 tiles): the queue starts with the active scan's list, which left every listed tile's state word
+    // "queued" and zeroed ring and q; the visit budget follows from the same count.  null: k_aq_fill_big filled the ring.
+    const AqInit in{list, count ? min(*count, cap) : 0};
+    const int budget = count ? (int)min((long long)in.n * gen_max + 4096, (long long)0x3fffffff) : ldg(&q[AQ_BUDGET]);
     int tile = -1, gen = 0;
     // GGC_MF_TRACE (prof != null): where a wave's time goes — waiting for a queue entry, the visit, the hand-over — in
     // wall_clock64 ticks, kept in registers and added up once when the wave leaves
@@ -365,7 +427,7 @@ __global__ void __launch_bounds__(64) k_mf_push_async(GcDims d, int bt_x, int bt
         asm volatile("" : "+v"(lane));
         const long long t_0 = prof ? wall_clock64() : 0;
         if (tile < 0) {
-            const int payload = aq_pop(ring, q, cap, lane, err_flag);
+            const int payload = aq_pop(ring, q, cap, in, lane, err_flag);
             if (payload < 0) { if (prof) p_wait += wall_clock64() - t_0; break; }
             tile = payload & 0xffffff; gen = payload >> 24;
         } else if (prof) ++p_follow;
@@ -411,7 +473,7 @@ __global__ void __launch_bounds__(64) k_mf_push_async(GcDims d, int bt_x, int bt
             if (cand && lane != fl) aq_push(ring, q, cap, ((gen + 1) << 24) | nb, err_flag);
             drain();
         }
-        if (next < 0 && lane == 0) aq_finish(q);
+        if (next < 0 && lane == 0) aq_finish(q, in);
         tile = next; gen = gen + 1;
         mf_wave_sync();
         if (prof) { p_wait += t_1 - t_0; p_visit += t_2 - t_1; p_hand += wall_clock64() - t_2; ++p_n; }
@@ -447,31 +509,39 @@ __global__ void __launch_bounds__(256) k_aq_fill_big(const int32_t* __restrict__
 
 int maxflow_relax_async(ggc_ctx* ctx, hipStream_t st, const GcDims& d, const MfTiles& tl, uint8_t* rmask, int32_t* dirty, const int32_t* rc, int32_t* dist,
                         const int32_t* count, const int32_t* list, int32_t* flag, unsigned long long* ring, int32_t* q, int cap,
-                        int grid, int32_t* err_flag) {
-    hipLaunchKernelGGL(k_aq_init, dim3(cdiv(cap, 256)), dim3(256), 0, st, count, list, ring, q, cap, 0);
-    hipLaunchKernelGGL(k_mf_relax_async, dim3(grid), dim3(256), 0, st, d, tl, rmask, dirty, rc, dist, flag, ring, q, cap, err_flag);
+                        int grid, int32_t* err_flag, long long* prof) {
+    if (prof)
+        hipLaunchKernelGGL(k_mf_relax_async<true>, dim3(grid), dim3(256), 0, st, d, tl, rmask, dirty, rc, dist, flag, count, list, ring, q, cap, err_flag, prof);
+    else
+        hipLaunchKernelGGL(k_mf_relax_async<false>, dim3(grid), dim3(256), 0, st, d, tl, rmask, dirty, rc, dist, flag, count, list, ring, q, cap, err_flag, prof);
     GGC_LAUNCH_CHECK(ctx);
     return GGC_OK;
 }
 
+int maxflow_push_async_tile(int th) { return th >= 32 ? 32 : (th >= 16 ? 16 : 8); }
+
 int maxflow_push_async(ggc_ctx* ctx, hipStream_t st, const GcDims& d, const MfTiles& tl, int th, int inner, int gen_max, int32_t* rc,
                        int32_t* ex, int32_t* snk, int32_t* dist, uint8_t* rmask, int32_t* dirty, const int32_t* count, const int32_t* list, int n_list_max, int32_t* state,
                        unsigned long long* ring, int32_t* q, int waves, int32_t* err_flag, long long* prof) {
-    th = th >= 32 ? 32 : (th >= 16 ? 16 : 8);
+    th = maxflow_push_async_tile(th);
     const int bt_x = tl.pt_x, bt_y = cdiv(d.H, th), cap = bt_x * bt_y * d.B;
     gen_max = std::min(gen_max, 127);
+    if (th == 8) {                      // the active scan's tiles ARE the queue's tiles: it left ring, q and the state words ready
+        hipLaunchKernelGGL(k_mf_push_async<8>, dim3(waves), dim3(64), 0, st, d, bt_x, bt_y, tl.pt_y, inner, gen_max, dirty, rc, ex, snk, dist, rmask, state, ring, q, cap,
+                           count, list, err_flag, prof);
+        GGC_LAUNCH_CHECK(ctx);
+        return GGC_OK;
+    }
+    const int32_t* no_list = nullptr;
     mf_zero3(st, reinterpret_cast<int32_t*>(ring), (size_t)cap * 2, q, AQ_WORDS, state, (size_t)cap);
     hipLaunchKernelGGL(k_aq_fill_big, dim3(cdiv(n_list_max, 256)), dim3(256), 0, st, count, list, tl.pt_x, tl.pt_y, th, bt_x, bt_y, state, ring, q,
                        gen_max);
     if (th == 32)
         hipLaunchKernelGGL(k_mf_push_async<32>, dim3(waves), dim3(64), 0, st, d, bt_x, bt_y, tl.pt_y, inner, gen_max, dirty, rc, ex, snk, dist, rmask, state, ring, q, cap,
-                           err_flag, prof);
-    else if (th == 8)
-        hipLaunchKernelGGL(k_mf_push_async<8>, dim3(waves), dim3(64), 0, st, d, bt_x, bt_y, tl.pt_y, inner, gen_max, dirty, rc, ex, snk, dist, rmask, state, ring, q, cap,
-                           err_flag, prof);
+                           no_list, no_list, err_flag, prof);
     else
         hipLaunchKernelGGL(k_mf_push_async<16>, dim3(waves), dim3(64), 0, st, d, bt_x, bt_y, tl.pt_y, inner, gen_max, dirty, rc, ex, snk, dist, rmask, state, ring, q, cap,
-                           err_flag, prof);
+                           no_list, no_list, err_flag, prof);
     GGC_LAUNCH_CHECK(ctx);
     return GGC_OK;
 }

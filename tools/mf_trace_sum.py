@@ -1,0 +1,33 @@
+"""Visit-weighted means of the [async visit], [async push] and relabel-visit lines of GGC_MF_TRACE logs:
+   GGC_MF_TRACE=1 python3 tools/mf_trace.py 2> LOG; python3 tools/mf_trace_sum.py LOG ..."""
+import re
+import sys
+
+for path in sys.argv[1:]:
+    L = open(path).read().splitlines()
+    n = 0; acc = [0.0] * 8; launches = 0; alive = 0.0; foll = 0
+    pend = None
+    for l in L:
+        m = re.search(r"\[async visit\] load\+fill ([\d.]+) us, sweeps ([\d.]+) us \(([\d.]+) sweeps\), write-back\+drain ([\d.]+)", l)
+        if m: pend = [float(x) for x in m.groups()]; continue
+        m = re.search(r"\[async push\] (\d+) waves alive ([\d.]+) us on average; (\d+) visits \((\d+) followed\): per visit wait\+lock ([\d.]+) us, visit ([\d.]+) us, hand-over ([\d.]+)", l)
+        if m and pend:
+            v = int(m.group(3)); n += v; launches += 1; foll += int(m.group(4)); alive += float(m.group(2))
+            for i, x in enumerate(pend + [float(m.group(5)), float(m.group(6)), float(m.group(7))]): acc[i] += x * v
+            pend = None
+    if n:
+        a = [x / n for x in acc]
+        print(f"{path}: push launches {launches}, visits {n} ({foll} followed), waves alive {alive / launches:.1f} us/launch mean; per visit: "
+              f"load+fill {a[0]:.2f}, sweeps {a[1]:.2f} ({a[2]:.2f} sweeps, {a[1] / max(a[2], 1e-9):.3f} us each), write-back+drain {a[3]:.2f}, "
+              f"wait+lock {a[4]:.2f}, visit {a[5]:.2f}, hand-over {a[6]:.2f}")
+    for tag in ("async relabel visits", "relabel visits"):
+        n = 0; acc = [0.0] * 6
+        for l in L:
+            m = re.search(r"\[" + tag + r"\] (\d+) \w+ visits: per visit load\+fill ([\d.]+) us, sweeps ([\d.]+) us \(([\d.]+) sweeps, ([\d.]+) BFS levels, (\d+) visits fell back\), write-back ([\d.]+)", l)
+            if m:
+                v = int(m.group(1)); n += v
+                for i, x in enumerate([float(m.group(k)) for k in (2, 3, 4, 5, 7)]): acc[i] += x * v
+                acc[5] += int(m.group(6))
+        if n:
+            a = [x / n for x in acc[:5]]
+            print(f"   [{tag}] {n} visits: load+fill {a[0]:.2f}, sweeps|levels {a[1]:.2f} ({a[2]:.2f} sweeps, {a[3]:.2f} levels, {int(acc[5])} fell back), write-back(+hand-over) {a[4]:.2f}")
