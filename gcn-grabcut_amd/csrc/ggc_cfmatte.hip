@@ -309,13 +309,8 @@ __global__ void __launch_bounds__(CF_THREADS) k_cf_pixel(int H, int W, int r, in
             }
         }
     }
-    const double sa = block_sum(va, s_red, tid);
-    if (tid == 0) part_a[blockIdx.x] = sa;
-    if constexpr (SETUP) {
-        __syncthreads();
-        const double sb = block_sum(vb, s_red, tid);
-        if (tid == 0) part_b[blockIdx.x] = sb;
-    }
+    if constexpr (SETUP) tile_partials(va, vb, s_red, tid, part_a, part_b);
+    else tile_partial(va, s_red, tid, part_a);
 }
 
 // The closed form's side of k_cg_scalar (grid B, one wave).  Set-up MODEs: CF_START (after the set-up pass) rz, rr0, the
@@ -367,11 +362,7 @@ __global__ void __launch_bounds__(CF_THREADS) k_cf_update(int H, int W, int ntx,
             vb = ri * ri;
         }
     }
-    const double sa = block_sum(va, s_red, tid);
-    if (tid == 0) part_a[blockIdx.x] = sa;
-    __syncthreads();
-    const double sb = block_sum(vb, s_red, tid);
-    if (tid == 0) part_b[blockIdx.x] = sb;
+    tile_partials(va, vb, s_red, tid, part_a, part_b);
 }
 
 // d = z + beta d on U (SETUP: d = z)

@@ -1,16 +1,19 @@
-// ggc_cg.h — the tile-list conjugate-gradient core shared by ggc_cfmatte.hip and ggc_foreground.hip.
+// ggc_cg.h — the tile-list conjugate-gradient core shared by ggc_cfmatte.hip, ggc_foreground.hip and ggc_clone.hip
+// (DESIGN.md §5.26).
 //
-// Both solve a sparse symmetric positive definite system on the unknown pixels U of every image of a batch by
+// All three solve a sparse symmetric positive definite system on the unknown pixels U of every image of a batch by
 // preconditioned conjugate gradients.  A tile is CG_T x CG_T pixels of one image and a block of CG_THREADS threads, one per
 // pixel.  The solver's front end counts U per tile over the whole frame (count_tile); the host reads the counts and lists
 // the tiles to work on, image by image (cg_list_tiles), so that an image owns the run [tile_lo, tile_hi) of the list.
 // Every later kernel runs over the list only, one block per entry (tile_of).  What a solver adds is its operator, its
-// preconditioner, its vector layout, the set-up of the first residual and its stop rule.
+// preconditioner, its vector layout, the set-up of the first residual and its stop rule.  The closed form keeps full-frame
+// vectors and its own kernels; the foreground and the clone share a compact vector store, its kernels, its stop rule and
+// its host driver (ggc_cg_compact.h) and add a policy each.
 //
 // Sums.  A per-tile sum is a fixed LDS tree over the tile's 256 values (block_sum), written to the tile's place in the
-// list; a per-image sum is one wave over the image's run of those, each lane a fixed stride and the lanes folded in a
-// fixed order (image_sum).  Neither depends on what else is listed, so an image's iterates do not depend on the batch: a
-// batch equals its single-image calls bit for bit.  No float atomics.
+// list (tile_partial, tile_partials); a per-image sum is one wave over the image's run of those, each lane a fixed stride
+// and the lanes folded in a fixed order (image_sum).  Neither depends on what else is listed, so an image's iterates do not
+// depend on the batch: a batch equals its single-image calls bit for bit.  No float atomics.
 //
 // Scalars.  CgImage holds an image's rz, alpha, beta, the stop reference, the iteration count and `done`; k_cg_scalar, one
 // wave per image, steps it twice per iteration: CG_ALPHA after the operator (alpha = rz / p.q, or the end of the image on
@@ -38,7 +41,7 @@ __device__ __forceinline__ TileRef tile_of(const int2* __restrict__ tiles, int n
 }
 
 struct CgImage {                                  // per-image solver state
-    double rz, rr0, alpha, beta, rel, stop;       // stop: the solver's own (the foreground's threshold on ||r||)
+    double rz, rr0, alpha, beta, rel, stop;       // stop: the solver's own (CgResidualStop's threshold on ||r||)
     int iters, done, tile_lo, tile_hi;
 };
 
@@ -52,6 +55,18 @@ __device__ __forceinline__ T block_sum(T v, T* s, int tid) {
         __syncthreads();
     }
     return s[0];
+}
+
+// the block's sum of va to its tile's place in part_a; tile_partials: and that of vb to part_b
+__device__ __forceinline__ void tile_partial(double va, double* s_red, int tid, double* __restrict__ part_a) {
+    const double sa = block_sum(va, s_red, tid);
+    if (tid == 0) part_a[blockIdx.x] = sa;
+}
+__device__ __forceinline__ void tile_partials(double va, double vb, double* s_red, int tid, double* __restrict__ part_a,
+                                              double* __restrict__ part_b) {
+    tile_partial(va, s_red, tid, part_a);
+    __syncthreads();
+    tile_partial(vb, s_red, tid, part_b);
 }
 
 // over the whole frame, grid (ntx, nty, B), a block is a tile: tile_u [B, tiles] of the block's tile = the sum of its u

@@ -3,19 +3,14 @@
 // 2003, with source or mixed gradients, solved on the device by conjugate gradients with the Jacobi preconditioner.
 // include/ggc.h states both rules; DESIGN.md §5.31 the tiling and the bytes.
 //
-// Layout of the clone.  The tile list, the fixed-order sums, the per-image scalars and the poll are ggc_cg.h's; this is
-// its third client, the sibling of ggc_foreground.hip with a scalar diagonal and a one-pixel halo.  k_clone_front writes a
-// byte per target pixel, CL_IN | |N_p| on Omega and 0 elsewhere, and counts Omega per tile; listed are the tiles that hold
-// Omega (ring 0).  The CG vectors live in a compact store of 256 entries per LISTED tile, three float64 per entry;
-// tile_slot maps a tile of the frame to its place in the list.  Per listed tile and iteration:
-//   k_clone_apply   p = z + beta p (z = r / |N_p| from r and the byte plane) on the tile and a one-pixel halo, staged in
-//                   LDS; q = A p on the tile; per-tile p . q.  p is double-buffered: a neighbour tile reads the old p of
-//                   this tile's edge while this tile writes the new one.
-//   k_cg_scalar     per image: alpha = rz / (p . q)
-//   k_clone_update  x += alpha p, r -= alpha q, z = r / |N_p|; per-tile r . z and r . r
-//   k_cg_scalar     per image: convergence (||r|| <= stop = max(tol ||r_0||, 2.55e-10 sqrt(3 |Omega|))), the count, beta
-// z and the stencil's membership are never stored as vectors.
-#include "ggc_cg.h"
+// Layout of the clone.  The tile list, the sums and the scalars are ggc_cg.h's; the compact vector store, the iteration's
+// kernels, the stop rule (||r|| <= max(tol ||r_0||, 2.55e-10 sqrt(3 |Omega|))) and the host driver are
+// ggc_cg_compact.h's.  Here are the front end (k_clone_front: a byte per target pixel, CL_IN | |N_p| on Omega and 0
+// elsewhere, and Omega per tile), the set-up, the output and the policy CloneProblem: three float64 per entry, the byte
+// plane as the field, the 4-neighbour Laplacian and the Jacobi preconditioner r / |N_p|, which reads the pixel's own byte
+// only: the apply stages the plane with a one-pixel halo, the update reads it directly.  The stencil's membership is never
+// stored as a vector.
+#include "ggc_cg_compact.h"
 #include <algorithm>
 #include <cmath>
 
@@ -24,14 +19,44 @@ namespace ggc {
 namespace {
 
 constexpr int CL_T = CG_T, CL_THREADS = CG_THREADS;
-constexpr int CL_S = CL_T + 2;                    // tile with a one-pixel halo
+constexpr int CL_S = CGC_S1;                      // tile with a one-pixel halo
 constexpr int CL_IN = 8;                          // the plane's byte: CL_IN | degree on Omega, 0 on the rest of the target
 constexpr int CL_DEG = 7;
 constexpr int CL_OUTSIDE = 0x80;                  // staged for a pixel outside the target: no link
 constexpr int CL_OFFSET_MAX = 32768;
-constexpr double CL_FLOOR = 2.55e-10;             // the absolute floor on ||r||, per sqrt of an unknown: 1e-12 of the byte range
 
-struct V3 { double v[3]; };                       // b, g, r of one pixel
+using V3 = CgVec<3>;                              // b, g, r of one pixel
+
+// the clone's policy for ggc_cg_compact.h.  s_f: the plane's bytes staged with row stride S, c the pixel's index in it
+struct CloneProblem {
+    static constexpr int N = 3, HALO = 1, UPDATE_HALO = 0;
+    using Stored = uint8_t;
+    using Field = uint8_t;
+    static constexpr uint8_t OUTSIDE = CL_OUTSIDE;
+    static constexpr double FLOOR = 2.55e-10;                    // 1e-12 of the byte range
+    struct Params {};
+
+    static __device__ __forceinline__ bool unknown(int f) { return f & CL_IN; }
+
+    static __device__ __forceinline__ V3 precondition(const V3& r, const uint8_t* s_f, int c, int, Params) {
+        const double deg = (double)(s_f[c] & CL_DEG);
+        V3 z;
+        for (int k = 0; k < 3; ++k) z.v[k] = r.v[k] / deg;
+        return z;
+    }
+
+    // (A p) at the pixel staged at s_p[c] and s_f[cf]
+    static __device__ __forceinline__ V3 apply(const V3* s_p, int c, const uint8_t* s_f, int cf, int, Params) {
+        const double deg = (double)(s_f[cf] & CL_DEG);
+        const V3 p = s_p[c];
+        V3 qi;
+        for (int ch = 0; ch < 3; ++ch) {                         // p is 0 off Omega and beyond the target
+            const double nsum = ((s_p[c - CL_S].v[ch] + s_p[c - 1].v[ch]) + s_p[c + 1].v[ch]) + s_p[c + CL_S].v[ch];
+            qi.v[ch] = deg * p.v[ch] - nsum;
+        }
+        return qi;
+    }
+};
 
 // the source pixel of target pixel (y, x) of image b, or -1 where it does not exist.  off = offsets + 2 b
 __device__ __forceinline__ int64_t source_index(int y, int x, const int32_t* __restrict__ off, int b, int Hs, int Ws) {
@@ -79,21 +104,6 @@ __global__ void __launch_bounds__(CL_THREADS) k_clone_front(int Hs, int Ws, int 
 }
 
 // ---------------------------------------------------------------- per listed tile
-// the plane's bytes of the 18 x 18 pixels from (y0, x0) of image b, CL_OUTSIDE beyond the target
-__device__ __forceinline__ void stage_plane(uint8_t* s_f, int y0, int x0, int H, int W, const uint8_t* __restrict__ plane,
-                                            size_t base, int tid) {
-    for (int e = tid; e < CL_S * CL_S; e += CL_THREADS) {
-        const int yy = y0 + e / CL_S, xx = x0 + e % CL_S;
-        s_f[e] = (yy >= 0 && yy < H && xx >= 0 && xx < W) ? plane[base + (size_t)yy * W + xx] : (uint8_t)CL_OUTSIDE;
-    }
-}
-
-// where the CG vectors keep pixel (y, x) of image b: its tile's slot in the list, then the pixel within the tile
-__device__ __forceinline__ size_t vec_index(const int32_t* __restrict__ tile_slot, int b, int nt, int ntx, int y, int x) {
-    const int slot = tile_slot[(size_t)b * nt + (y / CL_T) * ntx + x / CL_T];
-    return (size_t)slot * CL_THREADS + (y % CL_T) * CL_T + (x % CL_T);
-}
-
 // x = g, r = b - A g on Omega (exact integers), and the per-tile r . z (part_a), r . r (part_b)
 template <bool MIXED>
 __global__ void __launch_bounds__(CL_THREADS) k_clone_setup(int Hs, int Ws, int H, int W, int ntx,
@@ -110,7 +120,7 @@ __global__ void __launch_bounds__(CL_THREADS) k_clone_setup(int Hs, int Ws, int 
     const int tid = threadIdx.y * CL_T + threadIdx.x;
     const int x0 = t.tx * CL_T - 1, y0 = t.ty * CL_T - 1;
     const size_t base = (size_t)t.b * H * W;
-    stage_plane(s_f, y0, x0, H, W, plane, base, tid);
+    cgc_stage<CloneProblem>(s_f, CL_S, y0, x0, H, W, plane, base, tid);
     for (int e = tid; e < CL_S * CL_S; e += CL_THREADS) {
         const int yy = y0 + e / CL_S, xx = x0 + e % CL_S;
         const bool in = yy >= 0 && yy < H && xx >= 0 && xx < W;
@@ -153,123 +163,8 @@ __global__ void __launch_bounds__(CL_THREADS) k_clone_setup(int Hs, int Ws, int 
         res[j] = r;
         for (int k = 0; k < 3; ++k) { va += r.v[k] * (r.v[k] / deg); vb += r.v[k] * r.v[k]; }
     }
-    const double sa = block_sum(va, s_red, tid);
-    if (tid == 0) part_a[blockIdx.x] = sa;
-    __syncthreads();
-    const double sb = block_sum(vb, s_red, tid);
-    if (tid == 0) part_b[blockIdx.x] = sb;
+    tile_partials(va, vb, s_red, tid, part_a, part_b);
 }
-
-// p = z + beta p_in (FIRST: p = z) on the tile and its halo, the tile's part written to p_out; q = A p; per-tile p . q
-template <bool FIRST>
-__global__ void __launch_bounds__(CL_THREADS) k_clone_apply(int H, int W, int ntx, int nt, const int2* __restrict__ tiles,
-                                                            const int32_t* __restrict__ tile_slot,
-                                                            const CgImage* __restrict__ img, const uint8_t* __restrict__ plane,
-                                                            const V3* __restrict__ res, const V3* __restrict__ p_in,
-                                                            V3* __restrict__ p_out, V3* __restrict__ q,
-                                                            double* __restrict__ part_a) {
-    __shared__ uint8_t s_f[CL_S * CL_S];
-    __shared__ V3 s_p[CL_S * CL_S];
-    __shared__ double s_red[CL_THREADS];
-    const TileRef t = tile_of(tiles, ntx);
-    const CgImage& s = img[t.b];
-    if (s.done) return;                                          // uniform over the block
-    const int tid = threadIdx.y * CL_T + threadIdx.x;
-    const int x0 = t.tx * CL_T, y0 = t.ty * CL_T;
-    stage_plane(s_f, y0 - 1, x0 - 1, H, W, plane, (size_t)t.b * H * W, tid);
-    __syncthreads();
-    const double beta = FIRST ? 0.0 : s.beta;
-    for (int e = tid; e < CL_S * CL_S; e += CL_THREADS) {
-        const int ey = e / CL_S, ex = e % CL_S;
-        const int f = s_f[e];
-        V3 p;
-        for (int k = 0; k < 3; ++k) p.v[k] = 0.0;
-        if (f & CL_IN) {                                         // in the target, in Omega: its tile is listed
-            const bool own = ey >= 1 && ey <= CL_T && ex >= 1 && ex <= CL_T;
-            const size_t j = own ? (size_t)blockIdx.x * CL_THREADS + (ey - 1) * CL_T + (ex - 1)
-                                 : vec_index(tile_slot, t.b, nt, ntx, y0 - 1 + ey, x0 - 1 + ex);
-            const double deg = (double)(f & CL_DEG);
-            const V3 r = res[j];
-            for (int k = 0; k < 3; ++k) p.v[k] = r.v[k] / deg;
-            if constexpr (!FIRST) {
-                const V3 po = p_in[j];
-                for (int k = 0; k < 3; ++k) p.v[k] = p.v[k] + beta * po.v[k];
-            }
-            if (own) p_out[j] = p;
-        }
-        s_p[e] = p;
-    }
-    __syncthreads();
-    const int c = (threadIdx.y + 1) * CL_S + threadIdx.x + 1;
-    const int f = s_f[c];
-    double va = 0.0;
-    if (f & CL_IN) {
-        const double deg = (double)(f & CL_DEG);
-        const V3 p = s_p[c];
-        V3 qi;
-        for (int ch = 0; ch < 3; ++ch) {                         // p is 0 off Omega and beyond the target
-            const double nsum = ((s_p[c - CL_S].v[ch] + s_p[c - 1].v[ch]) + s_p[c + 1].v[ch]) + s_p[c + CL_S].v[ch];
-            qi.v[ch] = deg * p.v[ch] - nsum;
-        }
-        q[(size_t)blockIdx.x * CL_THREADS + tid] = qi;
-        for (int k = 0; k < 3; ++k) va += p.v[k] * qi.v[k];
-    }
-    const double sa = block_sum(va, s_red, tid);
-    if (tid == 0) part_a[blockIdx.x] = sa;
-}
-
-// x += alpha p, r -= alpha q on Omega; per-tile r . z (part_a) with z = r / |N_p|, and r . r (part_b)
-__global__ void __launch_bounds__(CL_THREADS) k_clone_update(int H, int W, int ntx, const int2* __restrict__ tiles,
-                                                             const CgImage* __restrict__ img, const uint8_t* __restrict__ plane,
-                                                             const V3* __restrict__ p, const V3* __restrict__ q,
-                                                             V3* __restrict__ x, V3* __restrict__ res,
-                                                             double* __restrict__ part_a, double* __restrict__ part_b) {
-    __shared__ double s_red[CL_THREADS];
-    const TileRef t = tile_of(tiles, ntx);
-    const CgImage& s = img[t.b];
-    if (s.done) return;
-    const int tid = threadIdx.y * CL_T + threadIdx.x;
-    const int xx = t.tx * CL_T + threadIdx.x, yy = t.ty * CL_T + threadIdx.y;
-    const int f = (xx < W && yy < H) ? plane[(size_t)t.b * H * W + (size_t)yy * W + xx] : 0;
-    double va = 0.0, vb = 0.0;
-    if (f & CL_IN) {
-        const size_t j = (size_t)blockIdx.x * CL_THREADS + tid;
-        const double al = s.alpha, deg = (double)(f & CL_DEG);
-        const V3 pj = p[j], qj = q[j];
-        V3 xj = x[j], rj = res[j];
-        for (int k = 0; k < 3; ++k) { xj.v[k] += al * pj.v[k]; rj.v[k] -= al * qj.v[k]; }
-        x[j] = xj;
-        res[j] = rj;
-        for (int k = 0; k < 3; ++k) { va += rj.v[k] * (rj.v[k] / deg); vb += rj.v[k] * rj.v[k]; }
-    }
-    const double sa = block_sum(va, s_red, tid);
-    if (tid == 0) part_a[blockIdx.x] = sa;
-    __syncthreads();
-    const double sb = block_sum(vb, s_red, tid);
-    if (tid == 0) part_b[blockIdx.x] = sb;
-}
-
-// The clone's side of k_cg_scalar (grid B, one wave), the foreground's form.  s.stop is the absolute floor on entry and
-// the threshold on ||r|| after the set-up MODE CL_START (after k_clone_setup): rz, rr0, the threshold, the images that
-// start solved (a clone onto itself: r_0 = 0).
-constexpr int CL_START = 0;
-struct CloneSolver {
-    static __device__ __forceinline__ bool converged(CgImage& s, double rr, double) {
-        const double rn = sqrt(rr);
-        s.rel = rn / sqrt(s.rr0);
-        return rn <= s.stop;
-    }
-    template <int MODE>
-    static __device__ __forceinline__ void setup(CgImage& s, double a, double b, double tol, int* __restrict__ n_done) {
-        const double r0 = sqrt(b), rel_stop = tol * r0;
-        s.rz = a;
-        s.rr0 = b;
-        s.rel = 0.0;
-        s.iters = 0;
-        s.stop = rel_stop > s.stop ? rel_stop : s.stop;
-        if (!(r0 > s.stop)) cg_finish(s, n_done);
-    }
-};
 
 // the outputs over the whole frame.  grid (cdiv(H*W, 256), B).  An Omega pixel of an image that was not solved (Omega the
 // whole target: no listed tile) takes the source's colour, the plain paste.
@@ -354,88 +249,43 @@ extern "C" int ggc_poisson_clone(ggc_ctx* ctx, ggc_stream stream, int B, int Hs,
     if (B == 0) return GGC_OK;
     GGC_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    const size_t P = (size_t)B * H * W;
-    const int ntx = cdiv(W, CL_T), nty = cdiv(H, CL_T), nt = ntx * nty;
-    const size_t n_tiles_max = (size_t)B * nt;
-    uint8_t* plane = nullptr;
-    int32_t *tile_u = nullptr, *tile_slot = nullptr;
-    int2* tiles = nullptr;
-    double *part_a = nullptr, *part_b = nullptr;
-    CgImage* img = nullptr;
-    int* n_done = nullptr;
-    // over the whole frame: 1 byte per pixel, 32 per tile, 64 per image
-    if (!carve_scratch(ctx, S_CLONE, [&](Carve& c) {
-            plane = c.take<uint8_t>(P);
-            tile_u = c.take<int32_t>(n_tiles_max); tile_slot = c.take<int32_t>(n_tiles_max);
-            tiles = c.take<int2>(n_tiles_max);
-            part_a = c.take<double>(n_tiles_max); part_b = c.take<double>(n_tiles_max);
-            img = c.take<CgImage>(B); n_done = c.take<int>(1);
-        }))
-        return GGC_E_OOM;
+    CgCompactFrame<CloneProblem> f;                              // the field is the byte plane: 1 byte per pixel
+    if (!cg_compact_frame(ctx, S_CLONE, B, H, W, f)) return GGC_E_OOM;
     ProfScope prof(ctx, st, "poisson_clone");
-    hipLaunchKernelGGL(k_clone_front, dim3(ntx, nty, B), dim3(CL_T, CL_T), 0, st, Hs, Ws, H, W, mask, offsets, plane, tile_u);
+    hipLaunchKernelGGL(k_clone_front, dim3(f.ntx, f.nty, B), dim3(CL_T, CL_T), 0, st, Hs, Ws, H, W, mask, offsets, f.field,
+                       f.tile_u);
     GGC_LAUNCH_CHECK(ctx);
 
-    // the offsets come to the host with the counts, under the one synchronisation of the tile list
-    std::vector<int32_t> cnt, slot, off(2 * (size_t)B);
+    // the offsets come to the host with the counts, under the one synchronisation of the tile list.  An image whose Omega
+    // is the whole target is not solved; the CG vectors take 120 bytes per entry
+    std::vector<int32_t> off(2 * (size_t)B), host_n(B);
     GGC_HIP(ctx, hipMemcpyAsync(off.data(), offsets, off.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    if (int e = cg_read_counts(ctx, st, tile_u, n_tiles_max, cnt)) return e;
-    for (size_t k = 0; k < off.size(); ++k)
-        GGC_REQUIRE(ctx, off[k] >= -CL_OFFSET_MAX && off[k] <= CL_OFFSET_MAX, GGC_E_INVALID_ARG,
-                    "clone offset %d of image %d outside +-%d", off[k], (int)(k / 2), CL_OFFSET_MAX);
-    // the tile list: the tiles that hold a pixel of Omega; an image whose Omega is the whole target is not solved
-    std::vector<int2> list;
-    std::vector<CgImage> host_img;
-    std::vector<int64_t> u_count;
-    const int n_solve = cg_list_tiles(B, ntx, nty, cnt.data(), 0, (int64_t)H * W, list, host_img, u_count, &slot);
-    std::vector<int32_t> host_n(B);
-    for (int b = 0; b < B; ++b) {
-        host_img[b].stop = CL_FLOOR * std::sqrt(3.0 * (double)u_count[b]);
-        host_n[b] = (int32_t)u_count[b];
-    }
-    const int n_list = (int)list.size();
-    // the CG vectors, 256 entries per listed tile: x, r, q and the two p, 120 bytes per entry
-    V3 *x = nullptr, *res = nullptr, *q = nullptr, *p0 = nullptr, *p1 = nullptr;
-    const size_t n_vec = (size_t)n_list * CL_THREADS;
-    if (n_list > 0 && !carve_scratch(ctx, S_CLONE_VEC, [&](Carve& c) {
-            x = c.take<V3>(n_vec); res = c.take<V3>(n_vec); q = c.take<V3>(n_vec);
-            p0 = c.take<V3>(n_vec); p1 = c.take<V3>(n_vec);
-        }))
-        return GGC_E_OOM;
-    GGC_HIP(ctx, hipMemcpyAsync(tile_slot, slot.data(), n_tiles_max * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    if (n_omega) GGC_HIP(ctx, hipMemcpyAsync(n_omega, host_n.data(), (size_t)B * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    if (int e = cg_upload(ctx, st, list, host_img, tiles, img, n_done)) return e;
-
-    if (n_list > 0) {
-        const CgScalars sc{st, B, max_iter, (double)tol, img, part_a, part_b, n_done};
-        const dim3 tblk(CL_T, CL_T);
-        if (mixed)
-            hipLaunchKernelGGL(k_clone_setup<true>, dim3(n_list), tblk, 0, st, Hs, Ws, H, W, ntx, tiles, source, target,
-                               offsets, plane, x, res, part_a, part_b);
-        else
-            hipLaunchKernelGGL(k_clone_setup<false>, dim3(n_list), tblk, 0, st, Hs, Ws, H, W, ntx, tiles, source, target,
-                               offsets, plane, x, res, part_a, part_b);
-        sc.step<CloneSolver, CL_START>();
-        GGC_LAUNCH_CHECK(ctx);
-        const int rc = cg_iterate(ctx, st, max_iter, n_done, n_solve, [&](int it) {
-            V3 *p_new = (it & 1) ? p1 : p0, *p_old = (it & 1) ? p0 : p1;
-            if (it == 0)
-                hipLaunchKernelGGL(k_clone_apply<true>, dim3(n_list), tblk, 0, st, H, W, ntx, nt, tiles, tile_slot, img, plane,
-                                   res, p_old, p_new, q, part_a);
+    V3* x = nullptr;
+    const int rc = cg_compact_solve(
+        ctx, st, f, S_CLONE_VEC, B, H, W, (int64_t)H * W, max_iter, (double)tol, CloneProblem::Params{},
+        [&](const std::vector<int64_t>& u_count) {
+            for (size_t k = 0; k < off.size(); ++k)
+                GGC_REQUIRE(ctx, off[k] >= -CL_OFFSET_MAX && off[k] <= CL_OFFSET_MAX, GGC_E_INVALID_ARG,
+                            "clone offset %d of image %d outside +-%d", off[k], (int)(k / 2), CL_OFFSET_MAX);
+            for (int b = 0; b < B; ++b) host_n[b] = (int32_t)u_count[b];
+            if (n_omega)
+                GGC_HIP(ctx, hipMemcpyAsync(n_omega, host_n.data(), (size_t)B * sizeof(int32_t), hipMemcpyHostToDevice, st));
+            return (int)GGC_OK;
+        },
+        [&](int n_list, dim3 tblk, V3* x0, V3* res) {
+            if (mixed)
+                hipLaunchKernelGGL(k_clone_setup<true>, dim3(n_list), tblk, 0, st, Hs, Ws, H, W, f.ntx, f.tiles, source, target,
+                                   offsets, f.field, x0, res, f.part_a, f.part_b);
             else
-                hipLaunchKernelGGL(k_clone_apply<false>, dim3(n_list), tblk, 0, st, H, W, ntx, nt, tiles, tile_slot, img, plane,
-                                   res, p_old, p_new, q, part_a);
-            sc.step<CloneSolver, CG_ALPHA>();
-            hipLaunchKernelGGL(k_clone_update, dim3(n_list), tblk, 0, st, H, W, ntx, tiles, img, plane, p_new, q, x, res,
-                               part_a, part_b);
-            sc.step<CloneSolver, CG_BETA>();
-        });
-        if (rc) return rc;
-    }
+                hipLaunchKernelGGL(k_clone_setup<false>, dim3(n_list), tblk, 0, st, Hs, Ws, H, W, f.ntx, f.tiles, source, target,
+                                   offsets, f.field, x0, res, f.part_a, f.part_b);
+        },
+        x);
+    if (rc) return rc;
     if (composite || raw || iters || rel_residual) {
         const dim3 ogrid(cdiv((int64_t)H * W, CL_THREADS), B);
-        hipLaunchKernelGGL(k_clone_output, ogrid, dim3(CL_THREADS), 0, st, Hs, Ws, H, W, ntx, nt, img, tile_slot, source,
-                           target, offsets, plane, x, composite, raw, iters, rel_residual);
+        hipLaunchKernelGGL(k_clone_output, ogrid, dim3(CL_THREADS), 0, st, Hs, Ws, H, W, f.ntx, f.nt, f.img, f.tile_slot, source,
+                           target, offsets, f.field, x, composite, raw, iters, rel_residual);
         GGC_LAUNCH_CHECK(ctx);
     }
     return GGC_OK;

@@ -1,24 +1,30 @@
-"""The tile-list CG core (csrc/ggc_cg.h) under both of its solvers, ggc_trimap_matte and ggc_estimate_foreground, at the
-smallest shapes where its pieces can go wrong: one partial tile (5 x 5), a 2 x 3 tile grid with partial edge tiles
+"""The tile-list CG core (csrc/ggc_cg.h, csrc/ggc_cg_compact.h) under its three solvers, ggc_trimap_matte,
+ggc_estimate_foreground and ggc_poisson_clone (source and mixed gradients), at the smallest shapes where its pieces can go wrong: one partial tile (5 x 5), a 2 x 3 tile grid with partial edge tiles
 (17 x 33), and 130 x 130 with every one of its 9 x 9 = 81 tiles listed, more than one wave, so that the per-image sum takes
 its second stride.  Batches hold an image with nothing to solve between two that are solved.  max_iter is far above the
 poll interval and tol is met long before it, so the early-out path runs.
 
 Checked: a batch equals its single-image calls bit for bit in every output, iters and rel included; an image with nothing
 to solve returns its start with iters == 0; convergence comes before max_iter; and the results agree with the float64
-restatements (tests/trimap_matte_ref.py, tests/foreground_ref.py) under the comparisons and tolerances of
-test_trimap_matte_gpu.py and test_foreground_gpu.py.  The restatements solved to 1e-12 are left out at 130 x 130 (seconds
+restatements (tests/trimap_matte_ref.py, tests/foreground_ref.py, tests/clone_ref.py's exact sparse solve) under the
+comparisons and tolerances of test_trimap_matte_gpu.py, test_foreground_gpu.py and test_clone_gpu.py.  The restatements solved to 1e-12 are left out at 130 x 130 (seconds
 on the host); the residual certificates, one application of the operator, are kept there.  On the host the restatements
 take, at these tolerances: matte 6 (5 x 5, r = 2), 148 and 74 (17 x 33, r = 1, 2) and 811 (130 x 130) iterations with at
-most 2.1e-4 between the 1e-4 and the 1e-12 solutions; foreground 17, 32 and 32 with at most 1.5e-4 levels."""
+most 2.1e-4 between the 1e-4 and the 1e-12 solutions; foreground 17, 32 and 32 with at most 1.5e-4 levels; clone (Omega
+the inner 3 x 3 of 5 x 5, everything but the outer ring of 17 x 33 and 130 x 130, tol 1e-9) 5, 83 and 401 with source
+gradients, 5, 80 and 373 with mixed ones, at most 1.5e-5 levels from the exact solve, which takes 0.3 s at 130 x 130 and
+is kept there."""
 import functools
 
 import numpy as np
 import pytest
 import torch
 
+import clone_ref as cr
 import foreground_ref as fr
 import trimap_matte_ref as tm
+import test_clone_cpu as cc
+from test_clone_gpu import _clone
 from test_foreground_cpu import AGREE_LEVELS, DEFAULTS
 from test_trimap_matte_cpu import EPS, MAX_ITER, TAU, TOL
 
@@ -28,7 +34,7 @@ MATTE_KEYS = ("alpha", "rgba", "raw", "iters", "rel")
 MATTE_SHAPES = [(5, 5, 2), (17, 33, 1), (17, 33, 2), (130, 130, 1)]            # h, w, r
 FG_SHAPES = [(5, 5), (17, 33), (130, 130)]
 F32 = lambda v: float(np.float32(v))                              # the entries take eps, eps_r, omega and tol as float32
-assert MAX_ITER > 10 * CG_POLL and DEFAULTS["max_iter"] > 10 * CG_POLL
+assert MAX_ITER > 10 * CG_POLL and DEFAULTS["max_iter"] > 10 * CG_POLL and cc.MAX_ITER > 10 * CG_POLL
 
 
 def _stream():
@@ -86,6 +92,26 @@ def _fg_case(h, w):
     a = np.random.default_rng(h * w).uniform(0.05, 0.95, (h, w)).astype(np.float32)
     a[0], a[-1] = 1.0, 0.0
     return _image(h, w, h * w), a
+
+
+@functools.lru_cache(maxsize=None)
+def _clone_batch(h, w, middle):
+    """Three noise sources and targets of one size at offset (0, 0).  Omega of the first and the last is everything but
+    the outer ring (5 x 5: the inner 3 x 3), so that halo fetches cross tiles in both directions; the middle image is not
+    solved: an empty mask, or Omega the whole target."""
+    rng = np.random.default_rng(1000 + h * w)
+    s, t = (rng.integers(0, 256, (h, w, 3)).astype(np.uint8) for _ in range(2))
+    m = np.zeros((h, w), np.uint8)
+    m[1:-1, 1:-1] = 1
+    masks = np.stack([m, np.zeros_like(m) if middle == "empty" else np.ones_like(m), m])
+    return np.stack([s, s[::-1], s[:, ::-1]]), masks, np.stack([t, t[::-1], t[:, ::-1]]), np.zeros((3, 2), np.int32)
+
+
+@functools.lru_cache(maxsize=None)
+def _clone_exact(h, w, j, mixed):
+    srcs, masks, tgts, offs = _clone_batch(h, w, "empty")
+    sys_ = cr.assemble(srcs[j], masks[j], tgts[j], offs[j], mixed)
+    return sys_, cr.exact(sys_)
 
 
 @functools.lru_cache(maxsize=None)
@@ -185,3 +211,30 @@ def test_foreground_batch_with_a_trivial_image_equals_its_single_calls(gpu_ctx, 
     assert np.array_equal(full["raw_f"][1].cpu().numpy(), imgs[1] / 255.0)
     assert np.array_equal(full["raw_b"][1].cpu().numpy(), imgs[1] / 255.0)
     assert all(1 <= iters[j] < DEFAULTS["max_iter"] and rel[j] <= DEFAULTS["tol"] for j in (0, 2)), (iters, rel)
+
+
+@pytest.mark.parametrize("middle", ["empty", "whole"])
+@pytest.mark.parametrize("mixed", [False, True])
+@pytest.mark.parametrize("h,w", FG_SHAPES)
+def test_clone_batch_with_a_trivial_image_equals_its_single_calls_and_the_exact_solve(gpu_ctx, h, w, mixed, middle):
+    srcs, masks, tgts, offs = _clone_batch(h, w, middle)
+    full = _clone(gpu_ctx, srcs, masks, tgts, offs, mixed)
+    _assert_batch_equals_singles(
+        full, lambda j: _clone(gpu_ctx, srcs[j:j + 1], masks[j:j + 1], tgts[j:j + 1], offs[j:j + 1], mixed))
+    iters, rel, n = full["iters"].tolist(), full["rel"].tolist(), full["n_omega"].tolist()
+    comp, raw = full["composite"].cpu().numpy(), full["raw"].cpu().numpy()
+    print(f"{h}x{w} mixed={mixed} middle {middle}: |Omega| {n} iters {iters} rel {rel}")
+    assert iters[1] == 0 and rel[1] == 0.0
+    want = tgts[1] if middle == "empty" else srcs[1]             # the target, or the pasted source
+    assert n[1] == (0 if middle == "empty" else h * w)
+    assert np.array_equal(comp[1], want) and np.array_equal(raw[1], want.astype(np.float64))
+    for j in (0, 2):
+        sys_, exact = _clone_exact(h, w, j, mixed)
+        om = sys_["omega"]
+        res, res0 = cr.residual_norms(sys_, raw[j])
+        err = np.abs(raw[j][om] - exact).max()
+        print(f"image {j}: residual {res / res0:.3e} |raw - exact| {err:.2e} levels")
+        assert n[j] == (h - 2) * (w - 2) and 1 <= iters[j] < cc.MAX_ITER, (n, iters)
+        assert res <= 2.0 * F32(cc.TOL) * res0, res / res0
+        assert np.array_equal(comp[j][~om], tgts[j][~om]) and np.array_equal(comp[j][om], cr.to_bytes(raw[j][om]))
+        assert err <= cc.AGREE_LEVELS, (j, err)

@@ -1,10 +1,11 @@
-"""experiment helper: one digest per seeded case of every entry that csrc/ggc_cg.h and csrc/ggc_image.h serve, over the
-raw outputs, iters and rel_residual.  Run it once per library (GGC_HIP_LIBRARY selects one per process) and compare the
-lines: two libraries that compute the same bits print the same text.
+"""experiment helper: one digest per seeded case of every entry that csrc/ggc_cg.h, csrc/ggc_cg_compact.h and
+csrc/ggc_image.h serve, over the raw outputs, iters and rel_residual.  Run it once per library (GGC_HIP_LIBRARY selects one
+per process) and compare the lines: two libraries that compute the same bits print the same text.
 
 Entries: ggc_closed_form_matte, ggc_trimap_matte (with and without alpha0), ggc_trimap_matte_warm, ggc_estimate_foreground,
-ggc_lift_trimap, ggc_closed_form_band, ggc_alpha_matte, ggc_upsample_matte, ggc_lift_labels, and ggc_refine_trimap in its
-fused (radius <= 8) and unfused forms.  The solver batches hold images with nothing to solve (no unknown pixel, every pixel
+ggc_poisson_clone (source and mixed gradients; composite, raw, n_omega, iters and rel), ggc_lift_trimap,
+ggc_closed_form_band, ggc_alpha_matte, ggc_upsample_matte, ggc_lift_labels, and ggc_refine_trimap in its fused
+(radius <= 8) and unfused forms.  The solver batches hold images with nothing to solve (no unknown pixel, every pixel
 unknown) between images that are solved."""
 import hashlib
 import sys
@@ -94,6 +95,24 @@ for eps_r, omega, tol in ((5e-3, 1.0, 1e-6), (1e-2, 0.1, 1e-4)):
            empty(B, H, W, 3, dtype=torch.float64), empty(B, dtype=torch.int32), empty(B, dtype=torch.float64)]
     call("ggc_estimate_foreground", B, H, W, bgr, dev(alphas), eps_r, omega, 400, tol, *out)
     report(f"estimate_foreground eps_r={eps_r} omega={omega} iters {out[4].tolist()}", *out)
+
+# the clone: a source larger than the target that overhangs it at every offset used; between the solved images an empty
+# mask, a mask that covers the target (Omega = the whole target: not solved) and a one-pixel mask
+HS, WS = 96, 120
+crng = np.random.default_rng(11)
+yy, xx = np.mgrid[0:HS, 0:WS]
+cmasks = np.stack([(yy - 48) ** 2 + (xx - 60) ** 2 <= 30 ** 2, np.zeros((HS, WS), bool), np.ones((HS, WS), bool),
+                   (yy == 40) & (xx == 50), crng.random((HS, WS)) < 0.6, (yy - 30) ** 2 + (xx - 90) ** 2 <= 25 ** 2])
+offs = np.array([(-13, -15), (-3, 4), (-20, -25), (-9, -7), (-26, -30), (-40, 10)], np.int32)     # (-40, 10): cut by two borders
+BC = len(cmasks)
+csrc, ctgt = dev(crng.integers(0, 256, (BC, HS, WS, 3)).astype(np.uint8)), dev(crng.integers(0, 256, (BC, H, W, 3)).astype(np.uint8))
+cmask, coff = dev(cmasks.astype(np.uint8) * 255), dev(offs)
+for mixed in (0, 1):
+    for tol in (1e-7, 1e-4):
+        out = [empty(BC, H, W, 3, dtype=torch.uint8), empty(BC, H, W, 3, dtype=torch.float64), empty(BC, dtype=torch.int32),
+               empty(BC, dtype=torch.int32), empty(BC, dtype=torch.float64)]
+        call("ggc_poisson_clone", BC, HS, WS, csrc, cmask, H, W, ctgt, coff, mixed, 3000, tol, *out)
+        report(f"poisson_clone mixed={mixed} tol={tol} n_omega {out[2].tolist()} iters {out[3].tolist()}", *out)
 
 for grow in (0, 3):
     for h1, w1 in ((H1, W1), (H, W), (4 * H, 4 * W)):

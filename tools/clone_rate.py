@@ -18,8 +18,8 @@ from gcn_grabcut.synthetic import synthetic_image  # noqa: E402
 
 REPS = int(os.environ.get("REPS", "5"))
 HBM_PEAK = 8.0e12                                 # bytes per second, the part's specification
-# per pixel of Omega and iteration: k_clone_apply reads r and the old p and writes the new p and q (4 x 24 bytes);
-# k_clone_update reads p, q, x, r and writes x, r (6 x 24 bytes).  Per listed pixel: the byte plane, staged with its halo
+# per pixel of Omega and iteration: k_cgc_apply<CloneProblem> reads r and the old p and writes the new p and q (4 x 24
+# bytes); k_cgc_update<CloneProblem> reads p, q, x, r and writes x, r (6 x 24 bytes).  Per listed pixel: the byte plane, staged with its halo
 # by the first and read once by the second (324 / 256 + 1 bytes).  The halo's r and p (68 entries a tile at most, held by
 # neighbour tiles that read them too) are left out.
 BYTES_OMEGA, BYTES_LISTED = 240.0, 324.0 / 256.0 + 1.0
