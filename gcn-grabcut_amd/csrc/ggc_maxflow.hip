@@ -12,7 +12,7 @@
 // Mapping to the hardware:
 //  * both phases work on LDS-resident tiles.  Relabel: a 32x32 tile + halo of labels
 //    is relaxed to a local fixpoint per visit.  Push: a 32x8 tile of excess / residual
-//    capacities / labels runs `inner` sweeps with LDS atomics; pushes across the tile
+//    capacities / labels runs `inner` sweeps with LDS atomics, a wave per tile; pushes across the tile
 //    edge use global atomics, and the write-back applies DELTAS atomically because a
 //    neighbouring tile may have added to this tile's excess or reverse arcs meanwhile.
 //    Every stale value is a lower bound of the true one, which is the asynchrony the
@@ -26,6 +26,7 @@
 //  * images without active pixels leave the open-image list; converged tiles cost nothing.
 #include "ggc_gc.h"
 #include "ggc_mf_sweep.h"
+#include "ggc_mf_push.h"
 #include <algorithm>
 #include <chrono>
 #include <cstdlib>
@@ -184,7 +185,70 @@ __global__ void __launch_bounds__(256) k_mf_relax_wave(GcDims d, MfTiles tl, int
     flush_tiles(outl, list_out, n_out);
 }
 
-// Push-relabel sweeps over a work list of 32x8 tiles, one pixel per thread.
+// Push-relabel sweeps over a work list of 32x8 tiles, a WAVE per tile (4 tiles per block per step of the list, no block
+// barrier inside a visit): push_tile_visit<8, false> of ggc_mf_push.h, the visit of the asynchronous launch with the memory
+// rules of a launch over a work list.  A sweep costs what the tile's active pixels cost (11 to 56 of 256 in the bench) instead
+// of four waves running the whole active path behind a block barrier.  A tile is on a list at most once per launch, so no
+// second wave can hold it and it needs no state word.  The next tile's list entry is fetched one visit ahead; its loads are
+// hidden by the other resident waves (12 tiles in flight per CU), not by a register prefetch.
+// PROF (GGC_MF_TRACE): the visits' clocks into table 3 of the trace clocks.
+#ifndef GGC_MF_PUSH_WAVE
+#define GGC_MF_PUSH_WAVE 1          // dense push launches: 1 = k_mf_pr_wave, 0 = k_mf_pr_list (a block per tile, one pixel per thread)
+#endif
+constexpr int PUSH_WAVE_GRID_DIV = 2;   // blocks of k_mf_pr_wave = blocks k_mf_pr_list would get / this (a block visits four tiles at a time; measured: 1, 2, 4)
+template <bool PROF>
+__global__ void __launch_bounds__(256) k_mf_pr_wave(GcDims d, MfTiles tl, int phase, int inner, long long* __restrict__ prof,
+                                                    int32_t* __restrict__ rc, int32_t* __restrict__ ex,
+                                                    int32_t* __restrict__ snk, int32_t* __restrict__ dist, uint8_t* __restrict__ rmask,
+                                                    int32_t* __restrict__ dirty, int32_t* __restrict__ counters, const int32_t* __restrict__ list_in,
+                                                    int32_t* __restrict__ list_out, int32_t* __restrict__ flag_in,
+                                                    int32_t* __restrict__ flag_out) {
+    __shared__ PushTileLds<PT_H> lds[4];
+    __shared__ OutList outl;
+    if (threadIdx.x == 0) outl.n = 0;
+    __syncthreads();
+    const int wv = threadIdx.x >> 6;
+    const int n_in = counters[phase % 3];
+    int32_t* n_out = counters + (phase + 1) % 3;
+    if (blockIdx.x == 0 && threadIdx.x == 0) counters[(phase + 2) % 3] = 0;       // the list after next starts empty
+    const int tiles_per_image = tl.pt_x * tl.pt_y;
+    const size_t BP = (size_t)d.B * d.P;
+    const int G = gridDim.x * 4;
+    long long pv[4] = {0, 0, 0, 0}, p_all = 0, p_n = 0;                    // GGC_MF_TRACE: kept in registers, one set of atomics per wave
+    int tile_nx = blockIdx.x * 4 + wv < n_in ? list_in[blockIdx.x * 4 + wv] : 0;   // the list entry of the NEXT visit, one visit ahead
+    for (int t = blockIdx.x * 4 + wv; t < n_in; t += G) {
+        int lane = threadIdx.x & 63;
+        asm volatile("" : "+v"(lane));                                     // keeps the lane arithmetic inside the loop (no hoist + spill)
+        const long long t_0 = PROF ? wall_clock64() : 0;
+        const int tile = __builtin_amdgcn_readfirstlane(tile_nx);
+        tile_nx = t + G < n_in ? list_in[t + G] : 0;
+        const int b = tile / tiles_per_image, tr = tile % tiles_per_image;
+        const int tyi = tr / tl.pt_x, txi = tr % tl.pt_x;
+        if (lane == 0) flag_in[tile] = 0;                                  // consumed
+        const int nbm = push_tile_visit<PT_H, false>(d, tyi, txi, inner, (size_t)b * d.P, BP, rc, ex, snk, dist, rmask, lds[wv], lane, PROF, pv);
+        if (lane < 9 && (nbm >> lane) & 1) {
+            const int ty = tyi + lane / 3 - 1, tx = txi + lane % 3 - 1;
+            if (ty >= 0 && ty < tl.pt_y && tx >= 0 && tx < tl.pt_x) {
+                const int nbt = b * tiles_per_image + ty * tl.pt_x + tx;
+                if (lane != 4) dirty[nbt] = 1;                             // its border arcs may have been re-opened (ggc_mf_sweep.h)
+                push_tile_l(nbt, flag_out, outl, list_out, n_out);
+            }
+        }
+        mf_wave_sync();
+        if (PROF) { p_all += wall_clock64() - t_0; ++p_n; }
+    }
+    if (PROF && (threadIdx.x & 63) == 0 && p_n) {
+        unsigned long long* o = reinterpret_cast<unsigned long long*>(prof) + (192 + (blockIdx.x & 63)) * 8;
+        atomicAdd(&o[0], (unsigned long long)pv[0]); atomicAdd(&o[1], (unsigned long long)pv[1]);
+        atomicAdd(&o[2], (unsigned long long)(p_all - pv[0] - pv[1]));     // write-back + hand-over
+        atomicAdd(&o[3], (unsigned long long)p_n); atomicAdd(&o[4], (unsigned long long)pv[2]); atomicAdd(&o[5], (unsigned long long)pv[3]);
+    }
+    flush_tiles(outl, list_out, n_out);
+}
+
+// The same with a 256-thread block per tile, one pixel per thread and a block barrier per sweep: the dense push until
+// k_mf_pr_wave, kept for comparison (-DGGC_MF_PUSH_WAVE=0, tools/build_variant.sh).
+#if !GGC_MF_PUSH_WAVE
 __global__ void __launch_bounds__(PT_N) k_mf_pr_list(GcDims d, MfTiles tl, int phase, int inner,
                                                     int32_t* __restrict__ rc, int32_t* __restrict__ ex,
                                                     int32_t* __restrict__ snk, int32_t* __restrict__ dist, uint8_t* __restrict__ rmask,
@@ -361,6 +425,7 @@ __global__ void __launch_bounds__(PT_N) k_mf_pr_list(GcDims d, MfTiles tl, int p
     }
     flush_tiles(outl, list_out, n_out);
 }
+#endif
 
 // per image: number of pixels whose excess can still reach the sink; their push tiles form the round's first work list.
 // A wave scans one 32x8 push tile (4 pixels per lane, rows of 128 bytes) and appends it once when it holds an active pixel:
@@ -437,6 +502,8 @@ __global__ void k_open_init(int B, const int32_t* __restrict__ state, int32_t* _
 
 namespace {
 
+constexpr int MF_PROF_TABLES = 4;
+
 // The max-flow's scratch, one slot.  `dirty` must outlive a solve: the warm start of the next GrabCut iteration relies on
 // the marks it left.  The slot keeps its size through the solves of a call, so it is not reallocated in between.
 struct MfWork {
@@ -445,7 +512,7 @@ struct MfWork {
     unsigned long long* ring;            // ticket ring of the asynchronous launches, one slot per tile of the larger kind
     int32_t* aq;                         // its control words
     int32_t* busy;                       // state word per tile of an asynchronous push
-    long long* prof;                     // GGC_MF_TRACE clocks [3][64][8]: asynchronous push waves | tile visits (push, dense relabel) | asynchronous relabel visits
+    long long* prof;                     // GGC_MF_TRACE clocks [MF_PROF_TABLES][64][8]: asynchronous push waves | tile visits (asynchronous push, dense relabel) | asynchronous relabel visits | dense push visits
     int32_t* dirty;                      // one word per push tile: a neighbour pushed into it since its arc masks were last exact
     void layout(Carve& c, size_t n_rt, size_t n_pt) {
         for (auto& p : rl_list) p = c.take<int32_t>(n_rt);
@@ -455,7 +522,7 @@ struct MfWork {
         ring = c.take<unsigned long long>(std::max(n_rt, n_pt));
         aq = c.take<int32_t>(AQ_WORDS);
         busy = c.take<int32_t>(n_pt);
-        prof = c.take<long long>(3 * 64 * 8);
+        prof = c.take<long long>(MF_PROF_TABLES * 64 * 8);
         dirty = c.take<int32_t>(n_pt);
     }
 };
@@ -514,9 +581,17 @@ struct MfSolve {
         const int pr_grid = (int)std::min<size_t>(PUSH_GRID * scale, std::max<size_t>(64, (size_t)n_cur * tl.pt_x * tl.pt_y / 2));
         // an active pixel opens at most its own tile: empty blocks only add dispatch time to launches that are pure latency
         const int grid = (int)std::min<long long>(pr_grid, std::max<long long>(128, 2ll * total_active));
-        for (int phase = 0; phase < launches; ++phase)
-            hipLaunchKernelGGL(k_mf_pr_list, dim3(grid), dim3(PT_N), 0, st, d, tl, phase, kn.mf_dense_sweeps, rc, ex, snk, dist, rmask, w.dirty, pr_cnt,
-                               w.pt_list[phase & 1], w.pt_list[(phase + 1) & 1], w.pt_flag[phase & 1], w.pt_flag[(phase + 1) & 1]);
+        for (int phase = 0; phase < launches; ++phase) {
+            int32_t *li = w.pt_list[phase & 1], *lo = w.pt_list[(phase + 1) & 1], *fi = w.pt_flag[phase & 1], *fo = w.pt_flag[(phase + 1) & 1];
+#if GGC_MF_PUSH_WAVE
+            // a block visits four tiles at a time
+            const int grid_w = std::max(32, cdiv(grid, PUSH_WAVE_GRID_DIV));
+            if (prof) hipLaunchKernelGGL(k_mf_pr_wave<true>, dim3(grid_w), dim3(256), 0, st, d, tl, phase, kn.mf_dense_sweeps, prof, rc, ex, snk, dist, rmask, w.dirty, pr_cnt, li, lo, fi, fo);
+            else hipLaunchKernelGGL(k_mf_pr_wave<false>, dim3(grid_w), dim3(256), 0, st, d, tl, phase, kn.mf_dense_sweeps, prof, rc, ex, snk, dist, rmask, w.dirty, pr_cnt, li, lo, fi, fo);
+#else
+            hipLaunchKernelGGL(k_mf_pr_list, dim3(grid), dim3(PT_N), 0, st, d, tl, phase, kn.mf_dense_sweeps, rc, ex, snk, dist, rmask, w.dirty, pr_cnt, li, lo, fi, fo);
+#endif
+        }
         GGC_LAUNCH_CHECK(ctx);
         return GGC_OK;
     }
@@ -524,7 +599,7 @@ struct MfSolve {
 
 // GGC_MF_TRACE=1: per-round diagnostics on stderr, blocking (tools/mf_trace.py reads them).  The clocks of the relabel
 // visits are table 1 of the trace clocks (dense launches) and table 2 (asynchronous launch), those of an asynchronous push
-// tables 0 (per wave) and 1 (inside the visit).
+// tables 0 (per wave) and 1 (inside the visit), those of a dense push round's visits table 3.
 struct MfTrace {
     std::chrono::steady_clock::time_point t_prev = std::chrono::steady_clock::now();
     double push_ms = 0.0;
@@ -564,7 +639,16 @@ struct MfTrace {
         ggc_ctx* ctx = s.ctx;
         GGC_HIP(ctx, hipStreamSynchronize(s.st));
         push_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_prev).count();
-        if (waves == 0) return GGC_OK;
+        if (waves == 0) {                                  // a dense round: the visits of k_mf_pr_wave, table 3 (nothing with k_mf_pr_list)
+            long long hd[64 * 8], v[6] = {0, 0, 0, 0, 0, 0};
+            GGC_HIP(ctx, hipMemcpy(hd, s.prof + 192 * 8, sizeof hd, hipMemcpyDeviceToHost));
+            GGC_HIP(ctx, hipMemsetAsync(s.prof + 192 * 8, 0, sizeof hd, s.st));
+            for (int i = 0; i < 64; ++i) for (int k = 0; k < 6; ++k) v[k] += hd[i * 8 + k];
+            if (v[3] > 0)
+                std::fprintf(stderr, "    [dense push visits] %lld visits: per visit load+fill %.2f us, sweeps %.2f us (%.2f sweeps, %.2f with a deal), write-back+hand-over %.2f us\n",
+                             v[3], 0.01 * v[0] / v[3], 0.01 * v[1] / v[3], (double)v[4] / v[3], (double)v[5] / v[3], 0.01 * v[2] / v[3]);
+            return GGC_OK;
+        }
         long long hh[128 * 8], h[7] = {0, 0, 0, 0, 0, 0, 0}, g[3] = {0, 0, 0};
         GGC_HIP(ctx, hipMemcpy(hh, s.prof, sizeof hh, hipMemcpyDeviceToHost));
         GGC_HIP(ctx, hipMemsetAsync(s.prof, 0, sizeof hh, s.st));
@@ -596,7 +680,7 @@ int maxflow(ggc_ctx* ctx, hipStream_t st, const GcDims& d, const int32_t* state,
     if (masks_exact) GGC_HIP(ctx, hipMemsetAsync(s.w.dirty, 0, sizeof(int32_t) * s.n_pt, st));
     if (kn.mf_trace) {
         s.prof = s.w.prof;
-        GGC_HIP(ctx, hipMemsetAsync(s.prof, 0, 3 * 64 * 8 * sizeof(long long), st));
+        GGC_HIP(ctx, hipMemsetAsync(s.prof, 0, MF_PROF_TABLES * 64 * 8 * sizeof(long long), st));
     }
     GGC_HIP(ctx, hipMemsetAsync(s.n_open, 0, sizeof(int32_t), st));
     int32_t *list_cur = ctl.lists, *list_nxt = ctl.lists + d.B;

@@ -32,7 +32,7 @@
  *   GGC_MF_ASYNC_HOPS=n           longest chain of tile visits in an asynchronous push launch (24)
  *   GGC_MF_ASYNC_SWEEPS=n         sweeps per asynchronous push visit (12)
  *   GGC_MF_DENSE_LAUNCHES0=n / GGC_MF_DENSE_LAUNCHES=n   push launches of the first / a later dense round (8 / 12)
- *   GGC_MF_DENSE_SWEEPS=n         sweeps per dense push visit (8)
+ *   GGC_MF_DENSE_SWEEPS=n         sweeps per dense push visit, one step each for up to 64 of the tile's active pixels (8)
  *   GGC_MF_RELAX_DENSE=n          work-list launches of a global relabel before the asynchronous launch takes over (3)
  *   GGC_MF_PARTIAL_ROUNDS=n       first rounds of a solve whose relabel stops after those launches (3; 0 = every relabel exact;
  *                                 0..64, larger values are clamped to 64: a partial round never closes an image)

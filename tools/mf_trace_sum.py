@@ -1,4 +1,5 @@
-"""Visit-weighted means of the [async visit], [async push] and relabel-visit lines of GGC_MF_TRACE logs:
+"""Visit-weighted means of the [async visit], [async push], relabel-visit and [dense push visits] lines of GGC_MF_TRACE logs
+(the dense push visits of a solve's first round and of its later rounds apart):
    GGC_MF_TRACE=1 python3 tools/mf_trace.py 2> LOG; python3 tools/mf_trace_sum.py LOG ..."""
 import re
 import sys
@@ -31,3 +32,18 @@ for path in sys.argv[1:]:
         if n:
             a = [x / n for x in acc[:5]]
             print(f"   [{tag}] {n} visits: load+fill {a[0]:.2f}, sweeps|levels {a[1]:.2f} ({a[2]:.2f} sweeps, {a[3]:.2f} levels, {int(acc[5])} fell back), write-back(+hand-over) {a[4]:.2f}")
+    rows = {"first round": [0, [0.0] * 5], "later rounds": [0, [0.0] * 5]}
+    first = True                                           # a "round 0:" line precedes the first dense push of a solve
+    for l in L:
+        m = re.search(r"\[ggc maxflow\] round (\d+):", l)
+        if m: first = m.group(1) == "0"; continue
+        m = re.search(r"\[dense push visits\] (\d+) visits: per visit load\+fill ([\d.]+) us, sweeps ([\d.]+) us \(([\d.]+) sweeps, ([\d.]+) with a deal\), write-back\+hand-over ([\d.]+)", l)
+        if m:
+            row = rows["first round" if first else "later rounds"]
+            v = int(m.group(1)); row[0] += v
+            for i in range(5): row[1][i] += float(m.group(2 + i)) * v
+    for tag, (n, acc) in rows.items():
+        if n:
+            a = [x / n for x in acc]
+            print(f"   [dense push visits, {tag}] {n} visits: load+fill {a[0]:.2f}, sweeps {a[1]:.2f} ({a[2]:.2f} sweeps, {a[1] / max(a[2], 1e-9):.3f} us each, "
+                  f"{a[3]:.2f} with a deal), write-back+hand-over {a[4]:.2f}")
