@@ -21,10 +21,11 @@ const Knobs& knobs() {
         k.mf_async_sweeps = num("GGC_MF_ASYNC_SWEEPS", 12, 1);
         k.mf_dense_launches = num("GGC_MF_DENSE_LAUNCHES", 12, 1);
         k.mf_dense_launches0 = num("GGC_MF_DENSE_LAUNCHES0", 8, 1);
-        k.mf_dense_sweeps = num("GGC_MF_DENSE_SWEEPS", 8, 1);
+        k.mf_dense_sweeps = num("GGC_MF_DENSE_SWEEPS", 12, 1);
         k.mf_relax_dense = num("GGC_MF_RELAX_DENSE", 3, 1);
         // a partial round never closes an image, so a value near the driver's round cap (4096) would fail every solve
         k.mf_partial_rounds = std::min(64, num("GGC_MF_PARTIAL_ROUNDS", 3, 0));
+        k.mf_label_slack = std::min(1 << 20, num("GGC_MF_LABEL_SLACK", 0, -1));   // (the ceiling is formed as label + 1 + slack in int32)
         k.agg_direct = num("GGC_AGG_DIRECT", 0, 0);
         k.slic_seq_connectivity = num("GGC_SLIC_SEQ_CONNECTIVITY", 0, 0);
         k.slic_cn_tiles = num("GGC_SLIC_CN_TILES", 1, 0);

@@ -100,6 +100,10 @@ int maxflow(ggc_ctx* ctx, hipStream_t st, const GcDims& d, const int32_t* state,
 constexpr int MF_RT = 32;                          // relabel tile side
 constexpr int MF_PT_W = 32, MF_PT_H = 8;           // push tile
 struct MfTiles { int rt_x, rt_y, pt_x, pt_y; };    // tiles per image
+// Words between the label-ceiling words of two images (lmax[b * MF_LMAX_STRIDE]): a 128-byte line each.  k_mf_active raises
+// an image's word with one atomic per block, about 8 000 per launch at 64 open images; packed into two lines they queue
+// behind each other in one L2 channel (measured: the scan 29 -> 47 us).
+constexpr int MF_LMAX_STRIDE = 32;
 
 // up to three int32 regions zeroed by one launch on `st` (ggc_maxflow.hip)
 void mf_zero3(hipStream_t st, int32_t* a, size_t na, int32_t* b, size_t nb, int32_t* c, size_t nc);
@@ -117,8 +121,9 @@ int maxflow_relax_async(ggc_ctx* ctx, hipStream_t st, const GcDims& d, const MfT
 // per visit.  list: the active scan's 32x8 push tiles (n_list_max = their number in the batch); state: one word per tile.
 // th = 8: the list is the queue's start, and the active scan has left ring and q zero and state "queued" (1) for the listed
 // tiles, 0 for the others of every open image; th = 16 | 32: a zero-fill and a fill launch go first.
+// lmax [B], slack: the images' label ceilings (push_tile_visit, ggc_mf_push.h); slack < 0: none.
 int maxflow_push_async_tile(int th);               // the tile height a requested one runs as
-int maxflow_push_async(ggc_ctx* ctx, hipStream_t st, const GcDims& d, const MfTiles& tl, int th, int inner, int gen_max, int32_t* rc,
+int maxflow_push_async(ggc_ctx* ctx, hipStream_t st, const GcDims& d, const MfTiles& tl, int th, int inner, int gen_max, const int32_t* lmax, int slack, int32_t* rc,
                        int32_t* ex, int32_t* snk, int32_t* dist, uint8_t* rmask, int32_t* dirty, const int32_t* count, const int32_t* list, int n_list_max, int32_t* state,
                        unsigned long long* ring, int32_t* q, int waves, int32_t* err_flag, long long* prof = nullptr);
 

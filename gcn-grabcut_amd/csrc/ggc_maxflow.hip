@@ -94,16 +94,24 @@ __device__ __forceinline__ void flush_tiles(OutList& L, int32_t* __restrict__ li
 // image's active-pixel count, and the words the active scan and k_done_update accumulate into (scan[0]: open images,
 // scan[4..6]: push-list counters, scan[7]: active total).  The relabel counters themselves are zeroed by k_done_update / k_open_init.
 // And the queue of the asynchronous relabel launch that follows the work-list launches: ring[0 .. cap) and q (aq_zero).
+// lmax: the image's label-ceiling word of THIS round (k_mf_active fills it), zeroed with active[].
+// PROF (GGC_MF_TRACE): before a label is overwritten, parked[pixel] = the pixel holds excess and a label in [lim, DINF),
+// lim from lmax_prev, the ceiling word of the round before (null in a solve's first round: nothing is marked); k_mf_active
+// counts how many of the marked pixels the relabel found a way to the sink for.
+template <bool PROF>
 __global__ void __launch_bounds__(256) k_mf_rinit(GcDims d, MfTiles tl, const int32_t* __restrict__ open_list,
                                                   const int32_t* __restrict__ snk, int32_t* __restrict__ dist,
                                                   int32_t* __restrict__ list, int32_t* __restrict__ flag, int32_t* __restrict__ flag2,
-                                                  int32_t* __restrict__ count, int32_t* __restrict__ active, int32_t* __restrict__ scan,
-                                                  unsigned long long* __restrict__ ring, int32_t* __restrict__ q, int cap) {
+                                                  int32_t* __restrict__ count, int32_t* __restrict__ active, int32_t* __restrict__ lmax,
+                                                  int32_t* __restrict__ scan,
+                                                  unsigned long long* __restrict__ ring, int32_t* __restrict__ q, int cap,
+                                                  const int32_t* __restrict__ lmax_prev, int slack, const int32_t* __restrict__ ex,
+                                                  uint8_t* __restrict__ parked) {
     constexpr int T = MF_RT;
     __shared__ OutList outl;
     if (threadIdx.x == 0) outl.n = 0;
     aq_zero(ring, q, cap);
-    if (blockIdx.x == 0 && threadIdx.x == 0) active[open_list[blockIdx.y]] = 0;
+    if (blockIdx.x == 0 && threadIdx.x == 0) { active[open_list[blockIdx.y]] = 0; lmax[(size_t)open_list[blockIdx.y] * MF_LMAX_STRIDE] = 0; }
     if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x < 8 && (threadIdx.x == 0 || threadIdx.x >= 4)) scan[threadIdx.x] = 0;   // not [1..3]: the relabel counters this launch appends to
     __syncthreads();
     const int tiles_per_image = tl.rt_x * tl.rt_y;
@@ -117,6 +125,16 @@ __global__ void __launch_bounds__(256) k_mf_rinit(GcDims d, MfTiles tl, const in
 #pragma unroll
         for (int r = 0; r < 16; ++r) sv[r] = snk[base + (size_t)min(ty0 + 16 * h + r, d.H - 1) * d.W + min(tx0 + lx, d.W - 1)];
         bool open_px = false;
+        if (PROF) {
+            const int lim = (lmax_prev && slack >= 0) ? min(d.P, lmax_prev[(size_t)b * MF_LMAX_STRIDE] + 1 + slack) : d.P;
+            for (int r = 0; r < 16; ++r) {
+                const int y = ty0 + 16 * h + r, x = tx0 + lx;
+                if (x < d.W && y < d.H) {
+                    const size_t i = base + (size_t)y * d.W + x;
+                    parked[i] = (lmax_prev && ex[i] > 0 && dist[i] >= lim && dist[i] < DINF) ? 1 : 0;
+                }
+            }
+        }
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             const int y = ty0 + 16 * h + r, x = tx0 + lx;
@@ -197,7 +215,8 @@ __global__ void __launch_bounds__(256) k_mf_relax_wave(GcDims d, MfTiles tl, int
 #endif
 constexpr int PUSH_WAVE_GRID_DIV = 2;   // blocks of k_mf_pr_wave = blocks k_mf_pr_list would get / this (a block visits four tiles at a time; measured: 1, 2, 4)
 template <bool PROF>
-__global__ void __launch_bounds__(256) k_mf_pr_wave(GcDims d, MfTiles tl, int phase, int inner, long long* __restrict__ prof,
+__global__ void __launch_bounds__(256) k_mf_pr_wave(GcDims d, MfTiles tl, int phase, int inner, const int32_t* __restrict__ lmax, int slack,
+                                                    long long* __restrict__ prof,
                                                     int32_t* __restrict__ rc, int32_t* __restrict__ ex,
                                                     int32_t* __restrict__ snk, int32_t* __restrict__ dist, uint8_t* __restrict__ rmask,
                                                     int32_t* __restrict__ dirty, int32_t* __restrict__ counters, const int32_t* __restrict__ list_in,
@@ -225,7 +244,7 @@ __global__ void __launch_bounds__(256) k_mf_pr_wave(GcDims d, MfTiles tl, int ph
         const int b = tile / tiles_per_image, tr = tile % tiles_per_image;
         const int tyi = tr / tl.pt_x, txi = tr % tl.pt_x;
         if (lane == 0) flag_in[tile] = 0;                                  // consumed
-        const int nbm = push_tile_visit<PT_H, false>(d, tyi, txi, inner, (size_t)b * d.P, BP, rc, ex, snk, dist, rmask, lds[wv], lane, PROF, pv);
+        const int nbm = push_tile_visit<PT_H, false>(d, lmax + (size_t)b * MF_LMAX_STRIDE, slack, tyi, txi, inner, (size_t)b * d.P, BP, rc, ex, snk, dist, rmask, lds[wv], lane, PROF, pv);
         if (lane < 9 && (nbm >> lane) & 1) {
             const int ty = tyi + lane / 3 - 1, tx = txi + lane % 3 - 1;
             if (ty >= 0 && ty < tl.pt_y && tx >= 0 && tx < tl.pt_x) {
@@ -249,7 +268,7 @@ __global__ void __launch_bounds__(256) k_mf_pr_wave(GcDims d, MfTiles tl, int ph
 // The same with a 256-thread block per tile, one pixel per thread and a block barrier per sweep: the dense push until
 // k_mf_pr_wave, kept for comparison (-DGGC_MF_PUSH_WAVE=0, tools/build_variant.sh).
 #if !GGC_MF_PUSH_WAVE
-__global__ void __launch_bounds__(PT_N) k_mf_pr_list(GcDims d, MfTiles tl, int phase, int inner,
+__global__ void __launch_bounds__(PT_N) k_mf_pr_list(GcDims d, MfTiles tl, int phase, int inner, const int32_t* __restrict__ lmax, int slack,
                                                     int32_t* __restrict__ rc, int32_t* __restrict__ ex,
                                                     int32_t* __restrict__ snk, int32_t* __restrict__ dist, uint8_t* __restrict__ rmask,
                                                     int32_t* __restrict__ dirty, int32_t* __restrict__ counters, const int32_t* __restrict__ list_in,
@@ -326,6 +345,7 @@ __global__ void __launch_bounds__(PT_N) k_mf_pr_list(GcDims d, MfTiles tl, int p
         __syncthreads();
         if (tid == 0) { flag_in[tile] = 0; s_nbm = 0; }                                   // consumed
         const int d0 = s_d[(tid >> 5) + 1][lx + 1];
+        const int lim = slack < 0 ? d.P : min(d.P, lmax[(size_t)b * MF_LMAX_STRIDE] + 1 + slack);   // the image's label ceiling (ggc_mf_push.h)
         int nbm = 0;
         for (int it = 0; it < inner; ++it) {
             int act = 0;
@@ -333,7 +353,7 @@ __global__ void __launch_bounds__(PT_N) k_mf_pr_list(GcDims d, MfTiles tl, int p
                 const int slot = tid, ly = slot >> 5;
                 const int e = __hip_atomic_load(&s_ex[slot], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
                 const int dp = s_d[ly + 1][lx + 1];
-                if (e > 0 && dp < d.P) {
+                if (e > 0 && dp < lim) {
                     act = 1;
                     // the 8 residual capacities and 8 neighbour labels are read in one batch and the arg-min is branch-free:
                     // one LDS round trip per sweep instead of a chain of up to 16
@@ -409,7 +429,7 @@ __global__ void __launch_bounds__(PT_N) k_mf_pr_list(GcDims d, MfTiles tl, int p
             if (sk != sk0) snk[base + p] = sk;
             const int d1 = s_d[ly + 1][lx + 1];
             if (d1 != d0) dist[base + p] = d1;
-            left |= (e1 > 0 && d1 < d.P) ? 1 : 0;
+            left |= (e1 > 0 && d1 < lim) ? 1 : 0;
         }
         if (nbm) atomicOr(&s_nbm, nbm);
         if (__syncthreads_or(left) && tid == 0) s_nbm |= 1 << 4;           // still has work
@@ -434,21 +454,28 @@ __global__ void __launch_bounds__(PT_N) k_mf_pr_list(GcDims d, MfTiles tl, int p
 // aq_st != null (asynchronous push on 32x8 tiles, whose tiles are these tiles): the scan also leaves the queue of that launch
 // ready — ring[0 .. cap) and q zero, and the state word of every push tile of an open image "queued" (1) when it is listed
 // and 0 otherwise (a closed image's words are never read: its tiles are neither listed nor anybody's neighbours).
+// The scan holds every label of the image, so it also leaves lmax[b], the image's largest FINITE label: the push phase that
+// follows parks excess above it (the label ceiling, ggc_mf_push.h).  A running maximum per lane, one reduction per wave and
+// one atomicMax per block; k_mf_rinit zeroed the word.
+// PROF (GGC_MF_TRACE): of the pixels k_mf_rinit<true> marked as parked above the previous ceiling, how many still hold excess
+// (slot 7 of the rows of trace table 2) and how many of those the relabel gave a finite label (slot 7 of table 1).
+template <bool PROF>
 __global__ void __launch_bounds__(256) k_mf_active(GcDims d, MfTiles tl, const int32_t* __restrict__ open_list,
                                                    const int32_t* __restrict__ ex, const int32_t* __restrict__ dist,
-                                                   int32_t* __restrict__ active, int32_t* __restrict__ flag, int32_t* __restrict__ flag2,
+                                                   int32_t* __restrict__ active, int32_t* __restrict__ lmax, int32_t* __restrict__ flag, int32_t* __restrict__ flag2,
                                                    int32_t* __restrict__ list, int32_t* __restrict__ count,
-                                                   int32_t* __restrict__ aq_st, unsigned long long* __restrict__ ring, int32_t* __restrict__ q, int cap) {
+                                                   int32_t* __restrict__ aq_st, unsigned long long* __restrict__ ring, int32_t* __restrict__ q, int cap,
+                                                   const uint8_t* __restrict__ parked, long long* __restrict__ prof) {
     __shared__ OutList outl;
-    __shared__ int s_n;
-    if (threadIdx.x == 0) { outl.n = 0; s_n = 0; }
+    __shared__ int s_n, s_l;
+    if (threadIdx.x == 0) { outl.n = 0; s_n = 0; s_l = 0; }
     if (aq_st) aq_zero(ring, q, cap);
     __syncthreads();
     const int tiles_per_image = tl.pt_x * tl.pt_y;
     const int b = open_list[blockIdx.y];
     const int lane = threadIdx.x & 63, lx = lane & 31, r0 = lane >> 5;
     const size_t base = (size_t)b * d.P;
-    int n_block = 0;
+    int n_block = 0, l_lane = 0, n_parked = 0, n_wrong = 0;
     for (int tr = blockIdx.x * 4 + (threadIdx.x >> 6); tr < tiles_per_image; tr += gridDim.x * 4) {
         const int tyi = tr / tl.pt_x, txi = tr - tyi * tl.pt_x;
         const int x = txi * PT_W + lx;
@@ -464,6 +491,8 @@ __global__ void __launch_bounds__(256) k_mf_active(GcDims d, MfTiles tl, const i
         for (int j = 0; j < PT_H / 2; ++j) {
             const int y = tyi * PT_H + r0 + 2 * j;
             n += (x < d.W && y < d.H && ev[j] > 0 && dv[j] < DINF) ? 1 : 0;
+            l_lane = max(l_lane, dv[j] < DINF ? dv[j] : 0);                // (a clamped address repeats a pixel of the image)
+            if (PROF && x < d.W && y < d.H && ev[j] > 0 && parked[base + (size_t)y * d.W + x]) { ++n_parked; n_wrong += dv[j] < DINF ? 1 : 0; }
         }
         for (int o = 32; o > 0; o >>= 1) n += __shfl_xor(n, o, 64);
         if (lane == 0) {
@@ -478,9 +507,17 @@ __global__ void __launch_bounds__(256) k_mf_active(GcDims d, MfTiles tl, const i
             }
         }
     }
+    for (int o = 32; o > 0; o >>= 1) l_lane = max(l_lane, __shfl_xor(l_lane, o, 64));
     if (lane == 0 && n_block) atomicAdd(&s_n, n_block);
+    if (lane == 0 && l_lane) atomicMax(&s_l, l_lane);
+    if (PROF) {
+        for (int o = 32; o > 0; o >>= 1) { n_parked += __shfl_xor(n_parked, o, 64); n_wrong += __shfl_xor(n_wrong, o, 64); }
+        unsigned long long* o = reinterpret_cast<unsigned long long*>(prof) + (64 + (blockIdx.x & 63)) * 8;
+        if (lane == 0 && n_parked) { atomicAdd(&o[64 * 8 + 7], (unsigned long long)n_parked); atomicAdd(&o[7], (unsigned long long)n_wrong); }
+    }
     __syncthreads();
     if (threadIdx.x == 0 && s_n) atomicAdd(&active[b], s_n);
+    if (threadIdx.x == 0 && s_l) atomicMax(&lmax[(size_t)b * MF_LMAX_STRIDE], s_l);
     flush_tiles(outl, list, count);
 }
 
@@ -514,7 +551,9 @@ struct MfWork {
     int32_t* busy;                       // state word per tile of an asynchronous push
     long long* prof;                     // GGC_MF_TRACE clocks [MF_PROF_TABLES][64][8]: asynchronous push waves | tile visits (asynchronous push, dense relabel) | asynchronous relabel visits | dense push visits
     int32_t* dirty;                      // one word per push tile: a neighbour pushed into it since its arc masks were last exact
-    void layout(Carve& c, size_t n_rt, size_t n_pt) {
+    int32_t* lmax;                       // [2][B * MF_LMAX_STRIDE] largest finite label per image, one word per 128-byte line, the word of an even round | of an odd round (label ceiling)
+    uint8_t* parked;                     // GGC_MF_TRACE only, [B * P]: pixels whose excess the ceiling parked (k_mf_rinit<true>)
+    void layout(Carve& c, size_t n_rt, size_t n_pt, size_t B, size_t n_parked) {
         for (auto& p : rl_list) p = c.take<int32_t>(n_rt);
         for (auto& p : rl_flag) p = c.take<int32_t>(n_rt);
         for (auto& p : pt_list) p = c.take<int32_t>(n_pt);
@@ -524,6 +563,8 @@ struct MfWork {
         busy = c.take<int32_t>(n_pt);
         prof = c.take<long long>(MF_PROF_TABLES * 64 * 8);
         dirty = c.take<int32_t>(n_pt);
+        lmax = c.take<int32_t>(2 * B * MF_LMAX_STRIDE);
+        parked = c.take<uint8_t>(n_parked);
     }
 };
 
@@ -540,13 +581,22 @@ struct MfSolve {
     // have a pixel away from the sink; the first launches relax every listed tile (bandwidth work, plain stores), and the long
     // sparse rest of the front runs inside ONE asynchronous launch that ends at the exact fixpoint (nothing to read back).
     // A PARTIAL relabel stops after the work-list launches.  `launches`: how many relabel launches ran.
-    int relabel(const int32_t* open, int n_cur, size_t scale, bool partial, int& launches) {
+    // The image's label-ceiling words alternate between two rows by the round's parity: the row k_mf_rinit zeroes and
+    // k_mf_active fills is not the one the trace still reads the previous ceiling from.
+    int32_t* lmax_row(int round) const { return w.lmax + (size_t)(round & 1) * d.B * MF_LMAX_STRIDE; }
+
+    int relabel(const int32_t* open, int round, int n_cur, size_t scale, bool partial, int& launches) {
         const Knobs& kn = knobs();
         const int per_image = tl.rt_x * tl.rt_y;
         const int grid = (int)std::min<size_t>(RELAX_GRID * scale, std::max<size_t>(16, cdiv((size_t)n_cur * per_image, 4)));
         ProfScope ps(ctx, st, "maxflow_relabel");
-        hipLaunchKernelGGL(k_mf_rinit, dim3(cdiv(per_image, 4), n_cur), dim3(256), 0, st, d, tl, open, snk, dist, w.rl_list[0], w.rl_flag[0],
-                           w.rl_flag[1], rl_cnt, ctl.active, n_open, w.ring, w.aq, partial ? 0 : (int)n_rt);
+        const int32_t* no_prev = nullptr;
+        if (prof) hipLaunchKernelGGL(k_mf_rinit<true>, dim3(cdiv(per_image, 4), n_cur), dim3(256), 0, st, d, tl, open, snk, dist, w.rl_list[0], w.rl_flag[0],
+                                     w.rl_flag[1], rl_cnt, ctl.active, lmax_row(round), n_open, w.ring, w.aq, partial ? 0 : (int)n_rt,
+                                     round > 0 ? lmax_row(round - 1) : no_prev, kn.mf_label_slack, ex, w.parked);
+        else hipLaunchKernelGGL(k_mf_rinit<false>, dim3(cdiv(per_image, 4), n_cur), dim3(256), 0, st, d, tl, open, snk, dist, w.rl_list[0], w.rl_flag[0],
+                                w.rl_flag[1], rl_cnt, ctl.active, lmax_row(round), n_open, w.ring, w.aq, partial ? 0 : (int)n_rt,
+                                no_prev, -1, ex, w.parked);
         int phase = 0;
         for (; phase < kn.mf_relax_dense; ++phase) {
             int32_t *li = w.rl_list[phase & 1], *lo = w.rl_list[(phase + 1) & 1], *fi = w.rl_flag[phase & 1], *fo = w.rl_flag[(phase + 1) & 1];
@@ -571,12 +621,12 @@ struct MfSolve {
         ProfScope ps(ctx, st, "maxflow_push");
         if (round > 0 && total_active <= kn.mf_async_push_active) {
             waves = (int)std::min<long long>(4ll * ASYNC_GRID * (long long)scale, std::max<long long>(64, total_active / 4));
-            return maxflow_push_async(ctx, st, d, tl, kn.mf_async_tile, kn.mf_async_sweeps, kn.mf_async_hops, rc, ex, snk, dist, rmask, w.dirty,
+            return maxflow_push_async(ctx, st, d, tl, kn.mf_async_tile, kn.mf_async_sweeps, kn.mf_async_hops, lmax_row(round), kn.mf_label_slack, rc, ex, snk, dist, rmask, w.dirty,
                                       pr_cnt, w.pt_list[0], (int)n_pt, w.busy, w.ring, w.aq, waves, ctl.err, prof);
         }
         waves = 0;
         // dense round.  First round: labels go stale fastest while most excess is still moving, an early relabel pays
-        // (8 launches vs 12: +3 %); sweeps per visit measured flat from 6 to 12 and worse either side.
+        // (8 launches vs 12: +3 %); sweeps per visit: 12 under the label ceiling (8 before it; profiles/r24_label_ceiling.txt).
         const int launches = round == 0 ? kn.mf_dense_launches0 : kn.mf_dense_launches;
         const int pr_grid = (int)std::min<size_t>(PUSH_GRID * scale, std::max<size_t>(64, (size_t)n_cur * tl.pt_x * tl.pt_y / 2));
         // an active pixel opens at most its own tile: empty blocks only add dispatch time to launches that are pure latency
@@ -586,10 +636,10 @@ struct MfSolve {
 #if GGC_MF_PUSH_WAVE
             // a block visits four tiles at a time
             const int grid_w = std::max(32, cdiv(grid, PUSH_WAVE_GRID_DIV));
-            if (prof) hipLaunchKernelGGL(k_mf_pr_wave<true>, dim3(grid_w), dim3(256), 0, st, d, tl, phase, kn.mf_dense_sweeps, prof, rc, ex, snk, dist, rmask, w.dirty, pr_cnt, li, lo, fi, fo);
-            else hipLaunchKernelGGL(k_mf_pr_wave<false>, dim3(grid_w), dim3(256), 0, st, d, tl, phase, kn.mf_dense_sweeps, prof, rc, ex, snk, dist, rmask, w.dirty, pr_cnt, li, lo, fi, fo);
+            if (prof) hipLaunchKernelGGL(k_mf_pr_wave<true>, dim3(grid_w), dim3(256), 0, st, d, tl, phase, kn.mf_dense_sweeps, lmax_row(round), kn.mf_label_slack, prof, rc, ex, snk, dist, rmask, w.dirty, pr_cnt, li, lo, fi, fo);
+            else hipLaunchKernelGGL(k_mf_pr_wave<false>, dim3(grid_w), dim3(256), 0, st, d, tl, phase, kn.mf_dense_sweeps, lmax_row(round), kn.mf_label_slack, prof, rc, ex, snk, dist, rmask, w.dirty, pr_cnt, li, lo, fi, fo);
 #else
-            hipLaunchKernelGGL(k_mf_pr_list, dim3(grid), dim3(PT_N), 0, st, d, tl, phase, kn.mf_dense_sweeps, rc, ex, snk, dist, rmask, w.dirty, pr_cnt, li, lo, fi, fo);
+            hipLaunchKernelGGL(k_mf_pr_list, dim3(grid), dim3(PT_N), 0, st, d, tl, phase, kn.mf_dense_sweeps, lmax_row(round), kn.mf_label_slack, rc, ex, snk, dist, rmask, w.dirty, pr_cnt, li, lo, fi, fo);
 #endif
         }
         GGC_LAUNCH_CHECK(ctx);
@@ -611,6 +661,8 @@ struct MfTrace {
         GGC_HIP(ctx, hipStreamSynchronize(s.st));
         GGC_HIP(ctx, hipMemcpy(hh, s.prof + 64 * 8, sizeof hh, hipMemcpyDeviceToHost));
         GGC_HIP(ctx, hipMemsetAsync(s.prof + 64 * 8, 0, sizeof hh, s.st));
+        long long n_wrong = 0, n_parked = 0;               // slot 7 of the two tables' rows: the active scan's count of parked excess
+        for (int i = 0; i < 64; ++i) { n_wrong += hh[i * 8 + 7]; n_parked += hh[(64 + i) * 8 + 7]; }
         for (int t = 0; t < 2; ++t) {                      // dense launches | the asynchronous launch (write-back includes its hand-over)
             long long h[7] = {0, 0, 0, 0, 0, 0, 0};
             for (int i = 0; i < 64; ++i) for (int k = 0; k < 7; ++k) h[k] += hh[(t * 64 + i) * 8 + k];
@@ -631,6 +683,19 @@ struct MfTrace {
             for (int b = 0; b < s.d.B; ++b) if (act[b]) std::fprintf(stderr, " %d:%d", b, act[b]);
             std::fprintf(stderr, "\n");
         }
+        // the label ceiling: the largest finite label of the images still open (k_mf_active), and what the relabel made of the
+        // excess the previous push phase parked at or above its ceiling
+        std::vector<int32_t> lm;
+        if (int rcode = read_i32(ctx, s.st, s.lmax_row(round), s.d.B * MF_LMAX_STRIDE, lm)) return rcode;
+        int lo = 0, hi = 0, n_l = 0; long long sum = 0;
+        for (int b = 0; b < s.d.B; ++b) if (act[b]) { const int l = lm[(size_t)b * MF_LMAX_STRIDE]; lo = n_l ? std::min(lo, l) : l; hi = std::max(hi, l); sum += l; ++n_l; }
+        std::fprintf(stderr, "    [ceiling] slack %d, lmax of %d open images: min %d, mean %.1f, max %d; parked pixels with excess %lld, of them finite after the relabel %lld\n",
+                     knobs().mf_label_slack, n_l, lo, n_l ? (double)sum / n_l : 0.0, hi, n_parked, n_wrong);
+        if (n_next > 0 && n_next <= 12) {
+            std::fprintf(stderr, "    [lmax]");
+            for (int b = 0; b < s.d.B; ++b) if (act[b]) std::fprintf(stderr, " %d:%d", b, lm[(size_t)b * MF_LMAX_STRIDE]);
+            std::fprintf(stderr, "\n");
+        }
         return GGC_OK;
     }
 
@@ -649,18 +714,20 @@ struct MfTrace {
                              v[3], 0.01 * v[0] / v[3], 0.01 * v[1] / v[3], (double)v[4] / v[3], (double)v[5] / v[3], 0.01 * v[2] / v[3]);
             return GGC_OK;
         }
-        long long hh[128 * 8], h[7] = {0, 0, 0, 0, 0, 0, 0}, g[3] = {0, 0, 0};
+        long long hh[128 * 8], h[8] = {0, 0, 0, 0, 0, 0, 0, 0}, g[3] = {0, 0, 0}, n_idle = 0, l_high = 0;
         GGC_HIP(ctx, hipMemcpy(hh, s.prof, sizeof hh, hipMemcpyDeviceToHost));
         GGC_HIP(ctx, hipMemsetAsync(s.prof, 0, sizeof hh, s.st));
-        for (int i = 0; i < 64; ++i) for (int k = 0; k < 7; ++k) h[k] += hh[i * 8 + k];
+        for (int i = 0; i < 64; ++i) for (int k = 0; k < 8; ++k) h[k] += hh[i * 8 + k];
         for (int i = 0; i < 64; ++i) for (int k = 0; k < 3; ++k) g[k] += hh[(64 + i) * 8 + k];
+        for (int i = 0; i < 64; ++i) { n_idle += hh[(64 + i) * 8 + 3]; l_high = std::max(l_high, hh[(64 + i) * 8 + 4]); }
         if (h[3] > 0)
             std::fprintf(stderr, "    [async visit] load+fill %.2f us, sweeps %.2f us (%.1f sweeps), write-back+drain %.2f us\n", 0.01 * g[0] / h[3],
                          0.01 * g[1] / h[3], (double)g[2] / h[3], 0.01 * (h[1] - g[0] - g[1]) / h[3]);
         if (h[6] > 0)
             std::fprintf(stderr, "    [async push] %d waves alive %.1f us on average; %lld visits (%lld followed): per visit wait+lock %.2f us, "
-                         "visit %.2f us, hand-over %.2f us\n", waves, 0.01 * h[5] / h[6], h[3], h[4], h[3] ? 0.01 * h[0] / h[3] : 0.0,
-                         h[3] ? 0.01 * h[1] / h[3] : 0.0, h[3] ? 0.01 * h[2] / h[3] : 0.0);
+                         "visit %.2f us, hand-over %.2f us; chains cut by the hop limit %lld, ended with nothing to hand on %lld, highest label written %lld\n",
+                         waves, 0.01 * h[5] / h[6], h[3], h[4], h[3] ? 0.01 * h[0] / h[3] : 0.0,
+                         h[3] ? 0.01 * h[1] / h[3] : 0.0, h[3] ? 0.01 * h[2] / h[3] : 0.0, h[7], n_idle, l_high);
         return GGC_OK;
     }
 };
@@ -674,7 +741,7 @@ int maxflow(ggc_ctx* ctx, hipStream_t st, const GcDims& d, const int32_t* state,
     MfSolve s{ctx, st, d, tl, (size_t)tl.rt_x * tl.rt_y * d.B, (size_t)tl.pt_x * tl.pt_y * d.B, rc, ex, snk, dist, rmask,
               ctl, ctl.cnt, ctl.cnt + 1, ctl.cnt + 4, {}, nullptr};
     GGC_REQUIRE(ctx, std::max(s.n_rt, s.n_pt) < (1u << 24), GGC_E_UNSUPPORTED, "batch has more max-flow tiles than a queue entry addresses");
-    if (!carve_scratch(ctx, S_GC_M, [&](Carve& c) { s.w.layout(c, s.n_rt, s.n_pt); })) return GGC_E_OOM;
+    if (!carve_scratch(ctx, S_GC_M, [&](Carve& c) { s.w.layout(c, s.n_rt, s.n_pt, (size_t)d.B, kn.mf_trace ? (size_t)d.B * d.P : 0); })) return GGC_E_OOM;
     // k_build_graph writes exact masks for every pixel on a cold start; a warm start leaves capacities and masks alone, so
     // the tiles keep their dirty marks
     if (masks_exact) GGC_HIP(ctx, hipMemsetAsync(s.w.dirty, 0, sizeof(int32_t) * s.n_pt, st));
@@ -709,12 +776,15 @@ int maxflow(ggc_ctx* ctx, hipStream_t st, const GcDims& d, const int32_t* state,
         // decides "no active pixel left" is always a full one.  Measured: 57.7 -> 52.9 ms per GrabCut stage (batch 256).
         const bool partial = round < kn.mf_partial_rounds;
         int relax_launches = 0;
-        if ((rcode = s.relabel(list_cur, n_cur, scale, partial, relax_launches))) return rcode;
+        if ((rcode = s.relabel(list_cur, round, n_cur, scale, partial, relax_launches))) return rcode;
         // ---- who still has work?  (active pixel = excess that can still reach the sink)
         // (active[], the open-image count, the push-list counters and the active total were zeroed by this round's k_mf_rinit)
-        hipLaunchKernelGGL(k_mf_active, dim3(std::min(cdiv(tl.pt_x * tl.pt_y, 4), 128), n_cur), dim3(256), 0, st, d, tl, list_cur, ex, dist,
-                           ctl.active, s.w.pt_flag[0], s.w.pt_flag[1], s.w.pt_list[0], s.pr_cnt,
-                           maxflow_push_async_tile(kn.mf_async_tile) == PT_H ? s.w.busy : nullptr, s.w.ring, s.w.aq, (int)s.n_pt);
+        int32_t* aq_st = maxflow_push_async_tile(kn.mf_async_tile) == PT_H ? s.w.busy : nullptr;
+        const dim3 scan_grid(std::min(cdiv(tl.pt_x * tl.pt_y, 4), 128), n_cur);
+        if (s.prof) hipLaunchKernelGGL(k_mf_active<true>, scan_grid, dim3(256), 0, st, d, tl, list_cur, ex, dist, ctl.active, s.lmax_row(round), s.w.pt_flag[0],
+                                       s.w.pt_flag[1], s.w.pt_list[0], s.pr_cnt, aq_st, s.w.ring, s.w.aq, (int)s.n_pt, s.w.parked, s.prof);
+        else hipLaunchKernelGGL(k_mf_active<false>, scan_grid, dim3(256), 0, st, d, tl, list_cur, ex, dist, ctl.active, s.lmax_row(round), s.w.pt_flag[0],
+                                s.w.pt_flag[1], s.w.pt_list[0], s.pr_cnt, aq_st, s.w.ring, s.w.aq, (int)s.n_pt, s.w.parked, s.prof);
         hipLaunchKernelGGL(k_done_update, dim3(cdiv(n_cur, 256)), dim3(256), 0, st, n_cur, list_cur, ctl.active, list_nxt, s.n_open, partial ? 1 : 0, s.rl_cnt);
         GGC_LAUNCH_CHECK(ctx);
         if ((rcode = read_i32(ctx, st, s.n_open, 8, host))) return rcode;

@@ -167,13 +167,16 @@ constexpr int ST_Q = 1, ST_BUSY = 2;                  // tile state word: queued
 
 // The tile visit is push_tile_visit<TH, true> of ggc_mf_push.h (sc1 loads, every write-back a device-scope atomic).
 
-template <int TH>
-__global__ void __launch_bounds__(64) k_mf_push_async(GcDims d, int bt_x, int bt_y, int pt_y, int inner, int gen_max, int32_t* __restrict__ dirty, int32_t* __restrict__ rc,
+// PROF (GGC_MF_TRACE): the wave's clocks and chain counters; the untraced instance carries none of that state.
+template <int TH, bool PROF>
+__global__ void __launch_bounds__(64) k_mf_push_async(GcDims d, int bt_x, int bt_y, int pt_y, int inner, int gen_max, const int32_t* __restrict__ lmax, int slack,
+                                                      int32_t* __restrict__ dirty, int32_t* __restrict__ rc,
                                                       int32_t* __restrict__ ex, int32_t* __restrict__ snk, int32_t* __restrict__ dist,
                                                       uint8_t* __restrict__ rmask, int32_t* __restrict__ st, unsigned long long* __restrict__ ring,
                                                       int32_t* __restrict__ q, int cap, const int32_t* __restrict__ count,
                                                       const int32_t* __restrict__ list, int32_t* __restrict__ err_flag,
-                                                      long long* __restrict__ prof) {
+                                                      long long* __restrict__ prof_p) {
+    long long* const prof = PROF ? prof_p : nullptr;
     __shared__ PushTileLds<TH> S;
     const int tiles_per_image = bt_x * bt_y;
     const size_t BP = (size_t)d.B * d.P;
@@ -184,7 +187,7 @@ __global__ void __launch_bounds__(64) k_mf_push_async(GcDims d, int bt_x, int bt
     int tile = -1, gen = 0;
     // GGC_MF_TRACE (prof != null): where a wave's time goes — waiting for a queue entry, the visit, the hand-over — in
     // wall_clock64 ticks, kept in registers and added up once when the wave leaves
-    long long p_wait = 0, p_visit = 0, p_hand = 0, p_n = 0, p_follow = 0, pv[4] = {0, 0, 0, 0};
+    long long p_wait = 0, p_visit = 0, p_hand = 0, p_n = 0, p_follow = 0, p_cut = 0, p_idle = 0, pv[4] = {0, 0, 0, 0};
     const long long t_start = prof ? wall_clock64() : 0;
     for (;;) {
         int lane = threadIdx.x & 63;
@@ -207,7 +210,7 @@ __global__ void __launch_bounds__(64) k_mf_push_async(GcDims d, int bt_x, int bt
         const long long t_1 = prof ? wall_clock64() : 0;
         const int b = tile / tiles_per_image, tr = tile % tiles_per_image;
         const int tyi = tr / bt_x, txi = tr % bt_x;
-        const int nbm = push_tile_visit<TH, true>(d, tyi, txi, inner, (size_t)b * d.P, BP, rc, ex, snk, dist, rmask, S, lane, prof != nullptr, pv);
+        const int nbm = push_tile_visit<TH, true>(d, lmax + (size_t)b * MF_LMAX_STRIDE, slack, tyi, txi, inner, (size_t)b * d.P, BP, rc, ex, snk, dist, rmask, S, lane, PROF, pv);
         drain();                                                           // the write-back is at memory
         const long long t_2 = prof ? wall_clock64() : 0;
         const bool left = (nbm >> 4) & 1;
@@ -228,6 +231,10 @@ __global__ void __launch_bounds__(64) k_mf_push_async(GcDims d, int bt_x, int bt
                 cand = (atomicOr(&st[nb], ST_Q) & (ST_Q | ST_BUSY)) == 0;  // idle: ours to arrange; busy: its holder re-queues it
             }
         }
+        if (prof) {                                                        // how the chain ends here, if it does: on the hop limit, or with nothing to hand on
+            const bool any = __ballot(cand) != 0ull;
+            if (!any) ++p_idle; else if (gen + 1 >= gen_max) ++p_cut;
+        }
         if (gen + 1 >= gen_max) cand = false;                              // chain length reached: left for the next relabel
         const unsigned long long cm = __ballot(cand);
         int next = -1;
@@ -242,13 +249,16 @@ __global__ void __launch_bounds__(64) k_mf_push_async(GcDims d, int bt_x, int bt
         mf_wave_sync();
         if (prof) { p_wait += t_1 - t_0; p_visit += t_2 - t_1; p_hand += wall_clock64() - t_2; ++p_n; }
     }
+    if (prof) for (int o = 32; o > 0; o >>= 1) pv[3] = max(pv[3], __shfl_xor(pv[3], o, 64));   // the highest label any lane wrote back
     if (prof && (threadIdx.x & 63) == 0) {
         unsigned long long* o = reinterpret_cast<unsigned long long*>(prof) + (blockIdx.x & 63) * 8;
+        atomicAdd(&o[7], (unsigned long long)p_cut);
         atomicAdd(&o[0], (unsigned long long)p_wait); atomicAdd(&o[1], (unsigned long long)p_visit); atomicAdd(&o[2], (unsigned long long)p_hand);
         atomicAdd(&o[3], (unsigned long long)p_n); atomicAdd(&o[4], (unsigned long long)p_follow);
         atomicAdd(&o[5], (unsigned long long)(wall_clock64() - t_start)); atomicAdd(&o[6], 1ull);
         unsigned long long* o2 = o + 64 * 8;                               // second table: inside the visit
         atomicAdd(&o2[0], (unsigned long long)pv[0]); atomicAdd(&o2[1], (unsigned long long)pv[1]); atomicAdd(&o2[2], (unsigned long long)pv[2]);
+        atomicAdd(&o2[3], (unsigned long long)p_idle); atomicMax(&o2[4], (unsigned long long)pv[3]);
     }
 }
 
@@ -284,14 +294,16 @@ int maxflow_relax_async(ggc_ctx* ctx, hipStream_t st, const GcDims& d, const MfT
 
 int maxflow_push_async_tile(int th) { return th >= 32 ? 32 : (th >= 16 ? 16 : 8); }
 
-int maxflow_push_async(ggc_ctx* ctx, hipStream_t st, const GcDims& d, const MfTiles& tl, int th, int inner, int gen_max, int32_t* rc,
+int maxflow_push_async(ggc_ctx* ctx, hipStream_t st, const GcDims& d, const MfTiles& tl, int th, int inner, int gen_max, const int32_t* lmax, int slack, int32_t* rc,
                        int32_t* ex, int32_t* snk, int32_t* dist, uint8_t* rmask, int32_t* dirty, const int32_t* count, const int32_t* list, int n_list_max, int32_t* state,
                        unsigned long long* ring, int32_t* q, int waves, int32_t* err_flag, long long* prof) {
     th = maxflow_push_async_tile(th);
     const int bt_x = tl.pt_x, bt_y = cdiv(d.H, th), cap = bt_x * bt_y * d.B;
     gen_max = std::min(gen_max, 127);
     if (th == 8) {                      // the active scan's tiles ARE the queue's tiles: it left ring, q and the state words ready
-        hipLaunchKernelGGL(k_mf_push_async<8>, dim3(waves), dim3(64), 0, st, d, bt_x, bt_y, tl.pt_y, inner, gen_max, dirty, rc, ex, snk, dist, rmask, state, ring, q, cap,
+        if (prof) hipLaunchKernelGGL((k_mf_push_async<8, true>), dim3(waves), dim3(64), 0, st, d, bt_x, bt_y, tl.pt_y, inner, gen_max, lmax, slack, dirty, rc, ex, snk, dist, rmask, state, ring, q, cap,
+                           count, list, err_flag, prof);
+        else hipLaunchKernelGGL((k_mf_push_async<8, false>), dim3(waves), dim3(64), 0, st, d, bt_x, bt_y, tl.pt_y, inner, gen_max, lmax, slack, dirty, rc, ex, snk, dist, rmask, state, ring, q, cap,
                            count, list, err_flag, prof);
         GGC_LAUNCH_CHECK(ctx);
         return GGC_OK;
@@ -301,10 +313,14 @@ int maxflow_push_async(ggc_ctx* ctx, hipStream_t st, const GcDims& d, const MfTi
     hipLaunchKernelGGL(k_aq_fill_big, dim3(cdiv(n_list_max, 256)), dim3(256), 0, st, count, list, tl.pt_x, tl.pt_y, th, bt_x, bt_y, state, ring, q,
                        gen_max);
     if (th == 32)
-        hipLaunchKernelGGL(k_mf_push_async<32>, dim3(waves), dim3(64), 0, st, d, bt_x, bt_y, tl.pt_y, inner, gen_max, dirty, rc, ex, snk, dist, rmask, state, ring, q, cap,
+        if (prof) hipLaunchKernelGGL((k_mf_push_async<32, true>), dim3(waves), dim3(64), 0, st, d, bt_x, bt_y, tl.pt_y, inner, gen_max, lmax, slack, dirty, rc, ex, snk, dist, rmask, state, ring, q, cap,
+                           no_list, no_list, err_flag, prof);
+        else hipLaunchKernelGGL((k_mf_push_async<32, false>), dim3(waves), dim3(64), 0, st, d, bt_x, bt_y, tl.pt_y, inner, gen_max, lmax, slack, dirty, rc, ex, snk, dist, rmask, state, ring, q, cap,
                            no_list, no_list, err_flag, prof);
     else
-        hipLaunchKernelGGL(k_mf_push_async<16>, dim3(waves), dim3(64), 0, st, d, bt_x, bt_y, tl.pt_y, inner, gen_max, dirty, rc, ex, snk, dist, rmask, state, ring, q, cap,
+        if (prof) hipLaunchKernelGGL((k_mf_push_async<16, true>), dim3(waves), dim3(64), 0, st, d, bt_x, bt_y, tl.pt_y, inner, gen_max, lmax, slack, dirty, rc, ex, snk, dist, rmask, state, ring, q, cap,
+                           no_list, no_list, err_flag, prof);
+        else hipLaunchKernelGGL((k_mf_push_async<16, false>), dim3(waves), dim3(64), 0, st, d, bt_x, bt_y, tl.pt_y, inner, gen_max, lmax, slack, dirty, rc, ex, snk, dist, rmask, state, ring, q, cap,
                            no_list, no_list, err_flag, prof);
     GGC_LAUNCH_CHECK(ctx);
     return GGC_OK;

@@ -33,9 +33,16 @@ __device__ __forceinline__ int mf_push_ld(const int32_t* p) { return ASYNC ? ldg
 //           boundaries order the rest): plain loads; a pixel of the tile's interior has no other writer during the launch and
 //           goes back with plain stores where it changed; only what a neighbouring tile's visit may add to meanwhile — the
 //           excess of the border ring, the arcs that leave the tile — goes back as an atomic delta.
-// prof: pv[0..2] += ticks of load + fill, ticks of the sweeps, sweeps; ASYNC = false also pv[3] += sweeps that ended in a deal.
+// lim_p, slack: the image's LABEL CEILING for this push phase.  *lim_p is the largest finite label the relabel before this
+// phase gave the image (k_mf_active), and a pixel whose label reaches lim = min(d.P, *lim_p + 1 + slack) is treated exactly
+// like one at d.P: it keeps its excess, is not active and waits for the next global relabel (slack < 0: lim = d.P).  Right
+// after a relabel no pixel holds label *lim_p + 1, so everything above it is cut off from the sink (the gap theorem); where
+// local relabels have filled that level since, the ceiling parks excess that could still have moved, which costs a round and
+// never the result.  The word was written by an earlier kernel: a plain load, issued with the tile's loads.
+// prof: pv[0..2] += ticks of load + fill, ticks of the sweeps, sweeps; ASYNC = false also pv[3] += sweeps that ended in a deal,
+// ASYNC = true pv[3] = max(pv[3], the highest finite label this lane wrote back).
 template <int TH, bool ASYNC>
-__device__ int push_tile_visit(const GcDims& d, int tyi, int txi, int inner, size_t base, size_t BP,
+__device__ int push_tile_visit(const GcDims& d, const int32_t* __restrict__ lim_p, int slack, int tyi, int txi, int inner, size_t base, size_t BP,
                                int32_t* __restrict__ rc, int32_t* __restrict__ ex, int32_t* __restrict__ snk,
                                int32_t* __restrict__ dist, uint8_t* __restrict__ rmask, PushTileLds<TH>& S, int lane,
                                bool prof, long long (&pv)[4]) {
@@ -43,6 +50,7 @@ __device__ int push_tile_visit(const GcDims& d, int tyi, int txi, int inner, siz
     const long long tv0 = prof ? wall_clock64() : 0;
     const int lx = lane & 31, r0 = lane >> 5;
     const int x = txi * 32 + lx;
+    const int lmax = *lim_p;
     int e0[NPX], sk0[NPX], r0v[NPX][8];
     // every load of the visit is issued unconditionally from a clamped address, then masked
 #pragma unroll
@@ -69,6 +77,7 @@ __device__ int push_tile_visit(const GcDims& d, int tyi, int txi, int inner, siz
         if (i < HALO) sd[i] = (gx >= 0 && gx < d.W && gy >= 0 && gy < d.H) ? hv[k] : DINF;
     }
     if (lane < 32) S.mask[lane] = 0u;
+    const int lim = slack < 0 ? d.P : min(d.P, lmax + 1 + slack);
     mf_wave_sync();
 #pragma unroll
     for (int j = 0; j < NPX; ++j) {
@@ -82,7 +91,7 @@ __device__ int push_tile_visit(const GcDims& d, int tyi, int txi, int inner, siz
             if (!inb) r0v[j][dir] = 0;
             S.rc[dir][slot] = r0v[j][dir];
         }
-        const bool a = e0[j] > 0 && S.d[ly + 1][lx + 1] < d.P;
+        const bool a = e0[j] > 0 && S.d[ly + 1][lx + 1] < lim;
         const unsigned long long m = __ballot(a);                          // lanes 0-31: row 2j, lanes 32-63: row 2j + 1
         if (lane == 0) { S.mask[2 * j] = (uint32_t)m; S.mask[2 * j + 1] = (uint32_t)(m >> 32); }
     }
@@ -134,7 +143,7 @@ __device__ int push_tile_visit(const GcDims& d, int tyi, int txi, int inner, siz
             }
             if (e <= 0) {
                 // nothing left (or another lane carried the same pixel and took it)
-            } else if (dp >= d.P) {
+            } else if (dp >= lim) {
                 atomicAdd(&S.ex[slot], e);                                 // cannot reach the sink: the excess stays where it is
             } else {
                 int hmin = sk > 0 ? 0 : DINF, best = sk > 0 ? 8 : -1, rb = 0;
@@ -174,7 +183,7 @@ __device__ int push_tile_visit(const GcDims& d, int tyi, int txi, int inner, siz
                     const int nd = (best >= 0 && hmin < DINF) ? hmin + 1 : DINF;
                     S.d[ly + 1][plx + 1] = nd;
                     atomicAdd(&S.ex[slot], e);                             // give it back; with the new label the next sweep can push
-                    carry = nd >= d.P ? -1 : slot;
+                    carry = nd >= lim ? -1 : slot;
                 }
             }
         }
@@ -266,7 +275,7 @@ __device__ int push_tile_visit(const GcDims& d, int tyi, int txi, int inner, siz
             if (sk1 != sk0[j]) snk[p] = sk1;
         }
         // the label: compare with the halo copy's origin is not kept, so write when the pixel was relabelled (d only rises here)
-        left |= (e1 > 0 && d1 < d.P) ? 1 : 0;
+        left |= (e1 > 0 && d1 < lim) ? 1 : 0;
     }
     // labels: a pixel's label is written when it differs from what memory held at load time
 #pragma unroll
@@ -276,6 +285,7 @@ __device__ int push_tile_visit(const GcDims& d, int tyi, int txi, int inner, siz
         if (i < HALO && hy >= 1 && hy <= TH && hx >= 1 && hx <= 32) {
             const int gy = tyi * TH + hy - 1, gx = txi * 32 + hx - 1;
             if (gx < d.W && gy < d.H && sd[i] != hv[k]) {
+                if (ASYNC && prof && sd[i] < DINF) pv[3] = max(pv[3], (long long)sd[i]);
                 if (ASYNC) atomicExch(&dist[base + (size_t)gy * d.W + gx], sd[i]);
                 else dist[base + (size_t)gy * d.W + gx] = sd[i];
             }

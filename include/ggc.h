@@ -32,10 +32,13 @@
  *   GGC_MF_ASYNC_HOPS=n           longest chain of tile visits in an asynchronous push launch (24)
  *   GGC_MF_ASYNC_SWEEPS=n         sweeps per asynchronous push visit (12)
  *   GGC_MF_DENSE_LAUNCHES0=n / GGC_MF_DENSE_LAUNCHES=n   push launches of the first / a later dense round (8 / 12)
- *   GGC_MF_DENSE_SWEEPS=n         sweeps per dense push visit, one step each for up to 64 of the tile's active pixels (8)
+ *   GGC_MF_DENSE_SWEEPS=n         sweeps per dense push visit, one step each for up to 64 of the tile's active pixels (12)
  *   GGC_MF_RELAX_DENSE=n          work-list launches of a global relabel before the asynchronous launch takes over (3)
  *   GGC_MF_PARTIAL_ROUNDS=n       first rounds of a solve whose relabel stops after those launches (3; 0 = every relabel exact;
  *                                 0..64, larger values are clamped to 64: a partial round never closes an image)
+ *   GGC_MF_LABEL_SLACK=n          label ceiling of the push phases: a pixel whose label reaches (the image's largest finite label
+ *                                 after the round's relabel) + 1 + n keeps its excess until the next global relabel, as a pixel
+ *                                 at label H * W does; negative = no ceiling (0)
  *   GGC_AGG_DIRECT=1              GCNConv gather straight from L2 instead of the graph-resident kernel
  *   GGC_SLIC_SEQ_CONNECTIVITY=1   literal one-thread-per-image replay of skimage's connectivity pass (A/B reference)
  *   GGC_SLIC_CN_TILES=0           SLIC connectivity by the rounds on a pending plane throughout (default 1: the first round labels
